@@ -33,6 +33,45 @@ from bench_extras import config_chain_leg, content_sweep_leg, device_rate, host_
 from bench_launch import (check_rccl_world, launch_ranks, preflight, refuse_without_library_exchange,  # noqa: E402,F401
                           run_teeing_stderr, visible_gpu_count, wants_library_exchange)
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_MAX_FRAMES = 128
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, kps_t, desc_t, counts_t, match_t, frame_ids, cap):
+    """--dump-outputs: the last timed step's outputs as a caller of the batch path receives them, for a fixed, seeded
+    sample of the batch's frames.  kps_t / desc_t / counts_t are the step's [B + 1, ...] record arrays (row 0 = the previous
+    batch's last frame), match_t the [B, cap] best / second / arg rows (None without the match), frame_ids[f] the global
+    sequence frame at batch position f.  Row i of every file is frame frame_index[i]; entries past its keypoint count are
+    zero (the device leaves there whatever an earlier step wrote).  Integers are stored as float64, which holds them
+    exactly; descriptor bytes as float32."""
+    from visual_sgraphs_amd import orb
+    B = len(frame_ids)
+    per_frame = 8 + 2 * 8 + cap * (7 * 8 + 32 * 4 + (3 * 8 if match_t is not None else 0))
+    n = min(B, DUMP_MAX_FRAMES, DUMP_LIMIT_BYTES // per_frame)
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    counts = counts_t[1:].cpu().numpy()[pos]
+    kps = np.ascontiguousarray(kps_t[1:].cpu().numpy()[pos]).view(orb.KP_DTYPE).reshape(n, cap)
+    desc = desc_t[1:].cpu().numpy()[pos]
+    valid = np.arange(cap)[None, :] < np.clip(counts[:, :1], 0, cap)
+    fields = np.stack([kps[k].astype(np.float64) for k in orb.KP_DTYPE.names], axis=-1)  # x y size angle response octave class_id
+    arrays = {
+        "frame_index": np.asarray(frame_ids, np.float64)[pos],
+        "counts": counts.astype(np.float64),  # (keypoints, monoIndex) per frame
+        "keypoints": np.where(valid[..., None], fields, 0.0),
+        "descriptors": np.where(valid[..., None], desc.astype(np.float32), np.float32(0)),
+    }
+    if match_t is not None:
+        for name, t in zip(("best", "second", "arg"), match_t):
+            arrays["match_" + name] = np.where(valid, t.cpu().numpy()[pos].astype(np.float64), 0.0)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {"dir": str(out), "frames": int(n), "of_frames": int(B), "bytes": int(total), "files": sorted(arrays)}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -77,9 +116,16 @@ def main():
     ap.add_argument("--no-preflight", action="store_true", help="--gpus N > 1: start the ranks without the preflight checks")
     ap.add_argument("--one-device", action="store_true",
                     help="dry run of the multi-rank path on a single GPU: every rank uses device 0 (needs gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (counts, keypoints, descriptors, "
+                         "match rows of a fixed, seeded sample of the batch's frames) as DIR/<name>.npy in float32 / "
+                         "float64, at most 64 MB in all; the same arguments give the same inputs, so two builds can be "
+                         "compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.preflight:
         sys.exit(preflight(args.gpus, args.batch, args.workload, one_device=args.one_device))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -438,6 +484,11 @@ def main():
             okb &= np.array_equal(d_bsecond[0, :n].cpu().numpy(), rs)
             parity["boundary_match_row"] = bool(okb)
             parity["bit_exact_vs_oracle"] = bool(parity["bit_exact_vs_oracle"] and okb)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        order = np.arange(B)[::-1] if timed_out["input"] == 1 else np.arange(B)
+        dumped = dump_outputs(args.dump_outputs, *timed_out["set"], None if args.no_match else timed_out["match"],
+                              t_first + order, cap)
     del timed_out
 
     if rank != 0:
@@ -616,6 +667,7 @@ def main():
                                  "steady clocks after ~0.1-0.2 s of load)",
                    "inputs": "resident in HBM" + (": two batches (the frames in forward / reverse order) alternate from step to "
                                                   "step" if rotate else "")},
+        **({"outputs_dumped": dumped} if dumped else {}),
         "parity": parity,
         "roofline": roofline, "cpu_baseline": cpu,
     }

@@ -19,6 +19,13 @@ def test_shard_frames_partition():
                 assert sharding.global_frame_index(r, li, world) == f
 
 
+def _host_barrier():
+    """dist.barrier() of the worker ranks without touching the GPU: torch's barrier asks the HIP runtime for the device
+    count even on gloo, which opens the GPU in every rank (eight ranks and the test process exceed what one GPU may
+    have open at once).  A gloo all-reduce of a host tensor returns on no rank before every rank has entered it."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _fake_records(rank, B, cap):
     g = torch.Generator().manual_seed(100 + rank)
     counts = torch.randint(0, cap, (B, 2), dtype=torch.int32, generator=g)
@@ -59,7 +66,7 @@ def _worker(rank, world, port, B, cap, q):
         ok &= torch.equal(c[r * B:(r + 1) * B], rc) and torch.equal(k[r * B:(r + 1) * B], rk)
         ok &= torch.equal(d[r * B:(r + 1) * B], rd)
     q.put((rank, bool(ok)))
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -94,7 +101,7 @@ def _boundary_worker(rank, world, port, B, cap, q):
         ok &= torch.equal(c[0], pc[B - 1]) and torch.equal(k[0], pk[B - 1]) and torch.equal(d[0], pd[B - 1])
         ok &= not recv[0, 8:16].any()  # flags / pad words of the header are zero
     q.put((rank, bool(ok)))
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -191,7 +198,7 @@ def _seq_worker(rank, world, port, n_frames, q):
             continue  # frame 0 has no predecessor in a single batch
         out[t] = [a.tolist() for a in ol.block_best2(local[i], prev)]
     q.put((rank, out))
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -313,7 +320,7 @@ def _steps_worker(rank, world, port, B, n_steps, exchange, q):
         if rank == 0:
             tail = got_last  # what the NEXT step's first frame (the next global frame) is matched against
     q.put((rank, out))
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -382,7 +389,7 @@ def _c5_worker(rank, world, port, n_streams, n_frames, q):
         if f > 0:
             out[(s, f)] = [a.tolist() for a in ol.block_best2(record(s, f), record(s, f - 1))]
     q.put((rank, owned, out))
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
