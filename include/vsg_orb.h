@@ -292,6 +292,55 @@ int vsg_bow_transform(vsg_vocab *voc, const uint8_t *desc, int n, int levelsup, 
                       int bow_cap, int *n_bow, int32_t *fv_node, int32_t *fv_off, int32_t *fv_idx, int fv_cap,
                       int *n_fv, int32_t *word_of, int32_t *node_of, double *weight_of);
 
+/* ---- TemplatedVocabulary::score (TemplatedVocabulary.h:1214-1219, ScoringObject.cpp:21-314) with the vocabulary's
+ * scoring type: one query BowVector (ids, vals, n) against m BowVectors in CSR form (vector c = m_ids / m_vals
+ * [off[c], off[c+1])); out[c] = score(query, vector c), bit-identical doubles.  Every BowVector has strictly ascending
+ * word ids < the vocabulary's word count.  Each pair is summed as ONE chain in ascending shared word id, as the merge
+ * loop does; L2 keeps its score >= 1 clamp.  KL scoring (log) returns VSG_ERR_UNSUPPORTED: the device cannot reproduce
+ * the host's log bit for bit.  Query BowVectors of more than 12288 words: VSG_ERR_UNSUPPORTED. */
+int vsg_vocab_score(vsg_vocab *voc, const int32_t *ids, const double *vals, int n, const int32_t *off,
+                    const int32_t *m_ids, const double *m_vals, int m, double *out);
+
+/* ---- KeyFrameDatabase (KeyFrameDatabase.h, KeyFrameDatabase.cc:31-96, 592-830) resident on the device.  Keyframes are
+ * the caller's uint64 ids (KeyFrame::mnId), maps int32 ids (KeyFrame::GetMap(); a keyframe no call has given a map has
+ * map -1).  Every keyframe's BowVector and the inverted file stay on the device; posting lists keep the reference's
+ * order: add appends to each word's list, erase removes the keyframe's FIRST entry in each list of its BowVector (the
+ * BowVector of its last add), clear / clear_map drop entries.  Adding an id twice without an erase gives two entries.
+ * The database keeps, per keyframe id, the KeyFrame members the queries use (mnRelocQuery, mnRelocWords, mRelocScore,
+ * mnPlaceRecognitionQuery, mnPlaceRecognitionWords, mPlaceRecognitionScore), across queries, erase, re-add and clear;
+ * all start at 0 (mRelocScore, uninitialised in the reference, is defined as 0).  There is no bad flag: callers erase a
+ * keyframe when it turns bad, as KeyFrame::SetBadFlag does (KeyFrame.cc:809).  Thread-safe: every call takes the
+ * database's lock (mMutex); a query runs on the calling thread's stream, one enqueue and one wait.  KL scoring: the
+ * queries return VSG_ERR_UNSUPPORTED; so do query BowVectors of more than 12288 words. */
+typedef struct vsg_kfdb vsg_kfdb;
+/* KeyFrameDatabase(const ORBVocabulary &voc) (:31-34) */
+int vsg_kfdb_create(vsg_vocab *voc, vsg_kfdb **out);
+void vsg_kfdb_destroy(vsg_kfdb *db);
+/* add(pKF) (:36-42): pKF->mBowVec as ascending (bow_ids, bow_vals); map_id = pKF->GetMap() */
+int vsg_kfdb_add(vsg_kfdb *db, uint64_t kf_id, int32_t map_id, const int32_t *bow_ids, const double *bow_vals, int n);
+/* erase(pKF) (:44-62), clear() (:64-68), clearMap(pMap) (:70-96) */
+int vsg_kfdb_erase(vsg_kfdb *db, uint64_t kf_id);
+int vsg_kfdb_clear(vsg_kfdb *db);
+int vsg_kfdb_clear_map(vsg_kfdb *db, int32_t map_id);
+/* KeyFrame::GetMap() changes when maps merge (KeyFrame::UpdateMap): the new map of each keyframe id */
+int vsg_kfdb_set_map(vsg_kfdb *db, const uint64_t *kf_ids, const int32_t *map_ids, int n);
+/* GetBestCovisibilityKeyFrames(10) of n keyframes: neighbours of kf_ids[j] are neigh_ids[offsets[j] .. offsets[j+1]) in
+ * the reference's order (only the first 10 are kept); a neighbour need not be in the database */
+int vsg_kfdb_set_covisibility(vsg_kfdb *db, const uint64_t *kf_ids, const int32_t *offsets, const uint64_t *neigh_ids,
+                              int n);
+/* DetectRelocalizationCandidates(F, pMap) (:719-830): query_id = F->mnId, (bow_ids, bow_vals, n) = F->mBowVec.  The
+ * candidates in the reference's order; more than cap: VSG_ERR_CAPACITY with *n_out = the number needed. */
+int vsg_kfdb_detect_relocalization_candidates(vsg_kfdb *db, uint64_t query_id, const int32_t *bow_ids,
+                                              const double *bow_vals, int n, int32_t map_id, uint64_t *out_ids, int cap,
+                                              int *n_out);
+/* DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates) (:592-717): query_kf_id = pKF->mnId, the BowVector
+ * pKF->mBowVec, connected_ids = pKF->GetConnectedKeyFrames(), map_id = pKF->GetMap(), bad_map_ids = the maps whose
+ * IsBad() is true.  loop_out / merge_out hold nNumCandidates ids each. */
+int vsg_kfdb_detect_n_best_candidates(vsg_kfdb *db, uint64_t query_kf_id, const int32_t *bow_ids,
+                                      const double *bow_vals, int n, const uint64_t *connected_ids, int n_conn,
+                                      int32_t map_id, const int32_t *bad_map_ids, int n_bad, int nNumCandidates,
+                                      uint64_t *loop_out, int *n_loop, uint64_t *merge_out, int *n_merge);
+
 /* int ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
  * (ORBmatcher.h:68, ORBmatcher.cc:643-756); candidate lists from F2.GetFeaturesInArea per F1 keypoint. */
 int vsg_search_for_initialization(int device, const uint8_t *desc1, const float *angle1, const int32_t *octave1,

@@ -255,10 +255,105 @@ class ORBVocabulary {
     for (int i = 0; i < nb; ++i) bowVec.emplace_hint(bowVec.end(), (unsigned)ids[i], vals[i]);
     featVec.node.resize(nf), featVec.off.resize(nf + 1), featVec.idx.resize(featVec.off[nf]);
   }
+  // TemplatedVocabulary::score(v1, v2) (TemplatedVocabulary.h:1214-1219) with the vocabulary's scoring type: the
+  // reference's double, bit for bit.  KL scoring throws (VSG_ERR_UNSUPPORTED).
+  double score(const std::map<unsigned, double> &v1, const std::map<unsigned, double> &v2) const {
+    std::vector<int32_t> a, b;
+    std::vector<double> av, bv;
+    flatten(v1, a, av), flatten(v2, b, bv);
+    const int32_t off[2] = {0, (int32_t)b.size()};
+    double out = 0;
+    check(vsg_vocab_score(v_, a.data(), av.data(), (int)v1.size(), off, b.data(), bv.data(), 1, &out), "vsg_vocab_score");
+    return out;
+  }
+  static void flatten(const std::map<unsigned, double> &v, std::vector<int32_t> &ids, std::vector<double> &vals) {
+    ids.clear(), vals.clear();  // one padding element: never an empty vector (data() is passed along with the size)
+    ids.reserve(v.size() + 1), vals.reserve(v.size() + 1);
+    for (const auto &kv : v) ids.push_back((int32_t)kv.first), vals.push_back(kv.second);
+    ids.push_back(0), vals.push_back(0.0);
+  }
   vsg_vocab *handle() const { return v_; }
 
  private:
   vsg_vocab *v_ = nullptr;
+};
+
+// KeyFrameDatabase (KeyFrameDatabase.h) on the device.  The reference's methods take KeyFrame* / Frame* / Map*; here a
+// keyframe is its mnId, a map an int id, and the caller mirrors what the database reads from a KeyFrame: its map
+// (add / SetMap when maps merge) and GetBestCovisibilityKeyFrames(10) (SetCovisibility).  INTEGRATION.md shows the glue.
+class KeyFrameDatabase {
+ public:
+  typedef std::map<unsigned, double> BowVector;
+  explicit KeyFrameDatabase(const ORBVocabulary &voc) { check(vsg_kfdb_create(voc.handle(), &db_), "vsg_kfdb_create"); }
+  ~KeyFrameDatabase() { vsg_kfdb_destroy(db_); }
+  KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+  KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+
+  void add(uint64_t kf_id, int32_t map_id, const BowVector &bow) {
+    std::vector<int32_t> ids;
+    std::vector<double> vals;
+    ORBVocabulary::flatten(bow, ids, vals);
+    check(vsg_kfdb_add(db_, kf_id, map_id, ids.data(), vals.data(), (int)bow.size()), "vsg_kfdb_add");
+    ++n_named_;
+  }
+  void erase(uint64_t kf_id) { check(vsg_kfdb_erase(db_, kf_id), "vsg_kfdb_erase"); }
+  void clear() { check(vsg_kfdb_clear(db_), "vsg_kfdb_clear"); }
+  void clearMap(int32_t map_id) { check(vsg_kfdb_clear_map(db_, map_id), "vsg_kfdb_clear_map"); }
+  void SetMap(const std::vector<uint64_t> &kf_ids, const std::vector<int32_t> &map_ids) {
+    if (kf_ids.size() != map_ids.size()) throw std::runtime_error("vsg_kfdb_set_map: sizes differ");
+    check(vsg_kfdb_set_map(db_, kf_ids.data(), map_ids.data(), (int)kf_ids.size()), "vsg_kfdb_set_map");
+    n_named_ += kf_ids.size();
+  }
+  // neighbours[j] = kf_ids[j]->GetBestCovisibilityKeyFrames(10), as mnIds
+  void SetCovisibility(const std::vector<uint64_t> &kf_ids, const std::vector<std::vector<uint64_t>> &neighbours) {
+    if (kf_ids.size() != neighbours.size()) throw std::runtime_error("vsg_kfdb_set_covisibility: sizes differ");
+    std::vector<int32_t> off(1, 0);
+    std::vector<uint64_t> flat;
+    for (size_t j = 0; j < neighbours.size(); ++j) {
+      flat.insert(flat.end(), neighbours[j].begin(), neighbours[j].end());
+      off.push_back((int32_t)flat.size());
+    }
+    flat.push_back(0);
+    check(vsg_kfdb_set_covisibility(db_, kf_ids.data(), off.data(), flat.data(), (int)kf_ids.size()),
+          "vsg_kfdb_set_covisibility");
+    n_named_ += kf_ids.size() + flat.size();
+  }
+  // DetectRelocalizationCandidates(F, pMap) (KeyFrameDatabase.cc:719-830): F = (F->mnId, F->mBowVec)
+  std::vector<uint64_t> DetectRelocalizationCandidates(uint64_t frame_id, const BowVector &bow, int32_t map_id) {
+    std::vector<int32_t> ids;
+    std::vector<double> vals;
+    ORBVocabulary::flatten(bow, ids, vals);
+    // a query updates the keyframes' query state and cannot be repeated: room for every keyframe id ever named
+    std::vector<uint64_t> out((size_t)n_named_ + 1);
+    int n = 0;
+    check(vsg_kfdb_detect_relocalization_candidates(db_, frame_id, ids.data(), vals.data(), (int)bow.size(), map_id,
+                                                    out.data(), (int)out.size(), &n),
+          "vsg_kfdb_detect_relocalization_candidates");
+    out.resize(n);
+    return out;
+  }
+  // DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates) (KeyFrameDatabase.cc:592-717)
+  void DetectNBestCandidates(uint64_t kf_id, const BowVector &bow, const std::vector<uint64_t> &connected, int32_t map_id,
+                             const std::vector<int32_t> &bad_maps, std::vector<uint64_t> &vpLoopCand,
+                             std::vector<uint64_t> &vpMergeCand, int nNumCandidates) {
+    std::vector<int32_t> ids;
+    std::vector<double> vals;
+    ORBVocabulary::flatten(bow, ids, vals);
+    vpLoopCand.assign((size_t)(nNumCandidates > 0 ? nNumCandidates : 1), 0);
+    vpMergeCand.assign(vpLoopCand.size(), 0);
+    int nl = 0, nm = 0;
+    check(vsg_kfdb_detect_n_best_candidates(db_, kf_id, ids.data(), vals.data(), (int)bow.size(),
+                                            connected.empty() ? nullptr : connected.data(), (int)connected.size(), map_id,
+                                            bad_maps.empty() ? nullptr : bad_maps.data(), (int)bad_maps.size(),
+                                            nNumCandidates, vpLoopCand.data(), &nl, vpMergeCand.data(), &nm),
+          "vsg_kfdb_detect_n_best_candidates");
+    vpLoopCand.resize(nl), vpMergeCand.resize(nm);
+  }
+  vsg_kfdb *handle() const { return db_; }
+
+ private:
+  vsg_kfdb *db_ = nullptr;
+  uint64_t n_named_ = 0;  // ids passed to add / SetMap / SetCovisibility: bounds the candidates of a query
 };
 
 // VS_GRAPHS::ORBmatcher (ORBmatcher.h:34-99) on flattened views.  The reference's methods take Frame& / KeyFrame* /

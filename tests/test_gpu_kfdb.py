@@ -1,0 +1,292 @@
+"""GPU parity of TemplatedVocabulary::score and of the device-resident KeyFrameDatabase (vsg_kfdb_*) against
+tests/kfdb_reference.py: scores bit for bit, candidate lists id for id, order included."""
+import struct
+import threading
+
+import numpy as np
+import pytest
+
+import kfdb_reference as kr
+from visual_sgraphs_amd import orb, synth
+
+pytestmark = pytest.mark.gpu
+
+SCORINGS = (kr.L1_NORM, kr.L2_NORM, kr.CHI_SQUARE, kr.BHATTACHARYYA, kr.DOT_PRODUCT)
+
+
+def with_scoring(blob, scoring):
+    """The same vocabulary image with another scoring type (the third int of the header)."""
+    return blob[:8] + struct.pack("<i", scoring) + blob[12:]
+
+
+@pytest.fixture(scope="module")
+def voc_blob():
+    return synth.synthetic_vocabulary(10, 6, seed=7)  # the reference's k = 10, L = 6: 10^6 words
+
+
+@pytest.fixture(scope="module")
+def descriptors():
+    """ORB descriptors of three synthetic sequences, 70 frames each (keyframes t < 60, query frames t >= 60)."""
+    ex = orb.ORBextractor(1000, 1.2, 8, 20, 7, device=0, max_batch=10)
+    out = {}
+    for s in range(3):
+        for t0 in range(0, 70, 10):
+            imgs = np.stack([synth.sequence_frame(640, 480, 21 + s, t) for t in range(t0, t0 + 10)])
+            for t, (_, _, d) in zip(range(t0, t0 + 10), ex.extract_batch(imgs)):
+                out[(s, t)] = d
+    ex.close()
+    return out
+
+
+def bow_of(voc, d):
+    b = voc.transform(d, 4)
+    return b["bow_ids"], b["bow_vals"]
+
+
+def test_score_every_type_bit_identical(voc_blob, descriptors):
+    frames = [descriptors[(s, t)] for s in range(3) for t in (0, 1, 5, 30)]
+    for scoring in SCORINGS:
+        voc = orb.ORBVocabulary(with_scoring(voc_blob, scoring))
+        assert voc.scoring == scoring
+        bows = [bow_of(voc, d) for d in frames]
+        for a in bows[:4]:
+            got = voc.score_many(a, bows)
+            want = np.array([kr.score(scoring, *a, *b) for b in bows], np.float64)
+            assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), scoring
+        assert voc.score(bows[0], bows[1]) == kr.score(scoring, *bows[0], *bows[1])
+        assert got.max() > 0  # words are shared
+        voc.close()
+    kl = orb.ORBVocabulary(with_scoring(voc_blob, kr.KL))
+    b = bow_of(kl, frames[0])
+    with pytest.raises(orb.VsgError) as ei:
+        kl.score(b, b)
+    assert ei.value.code == -3  # VSG_ERR_UNSUPPORTED
+    db = orb.KeyFrameDatabase(kl)
+    db.add(1, b, 0)
+    with pytest.raises(orb.VsgError) as ei:
+        db.DetectRelocalizationCandidates(5, b, 0)
+    assert ei.value.code == -3
+    db.close()
+    kl.close()
+
+
+class Both:
+    """The GPU database and the restatement, driven by the same operations."""
+
+    def __init__(self, voc):
+        self.gpu = orb.KeyFrameDatabase(voc)
+        self.ref = kr.KeyFrameDatabase(voc.scoring)
+        self.n_queries = 0
+
+    def add(self, kf, bow, m):
+        self.gpu.add(kf, bow, m)
+        self.ref.add(kf, *bow, m)
+
+    def erase(self, kf):
+        self.gpu.erase(kf)
+        self.ref.erase(kf)
+
+    def clear(self):
+        self.gpu.clear()
+        self.ref.clear()
+
+    def clear_map(self, m):
+        self.gpu.clearMap(m)
+        self.ref.clearMap(m)
+
+    def set_map(self, kfs, maps):
+        self.gpu.set_map(kfs, maps)
+        for k, m in zip(kfs, maps):
+            self.ref.set_map(k, m)
+
+    def set_covisibility(self, neigh):
+        self.gpu.set_covisibility(neigh)
+        for k, n in neigh.items():
+            self.ref.set_covisibility(k, n)
+
+    def reloc(self, qid, bow, m):
+        got = self.gpu.DetectRelocalizationCandidates(qid, bow, m)
+        want = self.ref.DetectRelocalizationCandidates(qid, *bow, m)
+        assert got == want, (qid, got, want)
+        self.n_queries += 1
+        return got
+
+    def nbest(self, qid, bow, conn, m, n, bad=()):
+        got = self.gpu.DetectNBestCandidates(qid, bow, conn, m, n, bad)
+        want = self.ref.DetectNBestCandidates(qid, *bow, conn, m, n, bad)
+        assert got == want, (qid, got, want)
+        self.n_queries += 1
+        return got
+
+
+def window_covisibility(kf, present_ids):
+    """Time-window covisibility: neighbours within 5 frames of the same sequence, weight 6 - |dt|; equal weights
+    (t - d and t + d) tie and keep the later frame first.  Neighbours need not be in the database."""
+    s, t = divmod(kf, 1000)
+    out = []
+    for d in range(1, 6):
+        for u in (t + d, t - d):
+            if 0 <= u < 60:
+                out.append(s * 1000 + u)
+    return out
+
+
+def test_scripted_database_matches_the_reference(voc_blob, descriptors):
+    voc = orb.ORBVocabulary(voc_blob)
+    bows = {k: bow_of(voc, d) for k, d in descriptors.items()}
+    kid = lambda s, t: (s + 1) * 1000 + t  # noqa: E731
+    db = Both(voc)
+    rng = np.random.default_rng(2024)
+    present, erased, pending = set(), set(), [(s, t) for t in range(60) for s in range(3)]
+    for s, t in pending[:60]:
+        db.add(kid(s, t), bows[(s, t)], s)
+        present.add(kid(s, t))
+    pending = pending[60:]
+    db.set_covisibility({k: window_covisibility(k, present) for k in present})
+    qid, n_ops, last_qid = 1, 0, 1
+    n_reloc = n_nbest = 0
+    while n_ops < 260:
+        op = rng.choice(["add", "erase", "readd", "map", "covis", "reloc", "nbest", "reloc", "nbest"],
+                        p=[.2, .08, .06, .03, .07, .2, .2, .08, .08])
+        if op == "add" and pending:
+            s, t = pending.pop(0)
+            db.add(kid(s, t), bows[(s, t)], s)
+            present.add(kid(s, t))
+        elif op == "erase" and present:
+            k = int(rng.choice(sorted(present)))
+            db.erase(k)
+            present.discard(k), erased.add(k)
+        elif op == "readd" and erased:
+            k = int(rng.choice(sorted(erased)))
+            s, t = divmod(k, 1000)
+            db.add(k, bows[(s - 1, t)], db.ref.kfs[k].map)
+            erased.discard(k), present.add(k)
+        elif op == "map" and present:
+            ks = [int(x) for x in rng.choice(sorted(present), 5, replace=False)]
+            db.set_map(ks, [int(rng.integers(0, 4)) for _ in ks])
+        elif op == "covis" and present:
+            ks = [int(x) for x in rng.choice(sorted(present), 8, replace=False)]
+            db.set_covisibility({k: window_covisibility(k, present)[int(rng.integers(0, 3)):] for k in ks})
+        elif op == "reloc":
+            s, t = int(rng.integers(0, 3)), int(rng.integers(0, 70))
+            q = last_qid if rng.random() < 0.15 else qid  # a repeated query id: the state is not reset
+            db.reloc(q, bows[(s, t)], int(rng.integers(0, 3)))
+            last_qid, qid = q, qid + 1
+            n_reloc += 1
+        elif op == "nbest" and present:
+            k = int(rng.choice(sorted(present)))
+            s, t = divmod(k, 1000)
+            conn = window_covisibility(k, present)[:int(rng.integers(0, 6))]
+            bad = [int(rng.integers(0, 3))] if rng.random() < 0.3 else []
+            db.nbest(k, bows[(s - 1, t)], conn, db.ref.kfs[k].map, 3, bad)
+            n_nbest += 1
+        else:
+            continue
+        n_ops += 1
+        if n_ops == 150:
+            db.clear_map(2)
+    # clear() keeps the keyframes' query state; the database works on afterwards
+    db.clear()
+    assert db.reloc(qid, bows[(0, 10)], 0) == []
+    for s, t in [(0, 10), (0, 11), (1, 12)]:
+        db.add(kid(s, t), bows[(s, t)], s)
+    db.reloc(qid + 1, bows[(0, 10)], 0)
+    db.nbest(kid(1, 12), bows[(1, 12)], [], 1, 3)
+    assert n_reloc >= 40 and n_nbest >= 30
+    hits = sum(1 for k in db.ref.kfs.values() if k.mnRelocQuery)
+    assert hits > 50
+
+
+def test_stale_score_and_double_add_on_the_device():
+    voc = orb.ORBVocabulary(synth.synthetic_vocabulary(10, 3, seed=3))
+
+    def uniform(words):
+        words = list(words)
+        return np.array(words, np.int32), np.full(len(words), 1.0 / len(words))
+    db = Both(voc)
+    db.add(1, uniform(range(0, 10)), 0)
+    db.add(2, uniform(range(10, 20)), 0)
+    db.set_covisibility({1: [2]})
+    assert db.reloc(100, uniform(range(10, 20)), 0) == [2]
+    assert db.reloc(101, uniform(list(range(0, 10)) + [10]), 0) == [2]  # 2's stale score from query 100 wins
+    fresh = Both(voc)
+    fresh.add(1, uniform(range(0, 10)), 0)
+    fresh.add(2, uniform(range(10, 20)), 0)
+    fresh.set_covisibility({1: [2]})
+    assert fresh.reloc(101, uniform(list(range(0, 10)) + [10]), 0) == [1]
+    dbl = Both(voc)
+    dbl.add(1, uniform(range(5)), 0)
+    dbl.add(2, uniform(range(5)), 0)
+    dbl.add(1, uniform(range(5)), 0)
+    assert dbl.reloc(7, uniform(range(5)), 0) == [1]  # 10 words against 5
+    dbl.erase(1)
+    assert dbl.reloc(8, uniform(range(5)), 0) == [2, 1]
+    assert dbl.reloc(0, uniform(range(5)), 0) == [2, 1]  # the state is no longer fresh: id 0 finds them
+    dbl.erase(1)
+    dbl.erase(1)  # nothing left to erase
+    assert dbl.nbest(9, uniform(range(5)), [], 0, 3) == ([2], [])
+    fresh0 = Both(voc)
+    fresh0.add(1, uniform(range(5)), 0)
+    assert fresh0.reloc(0, uniform(range(5)), 0) == []  # query-id state starts at 0
+    assert fresh0.nbest(0, uniform(range(5)), [], 0, 3) == ([], [])
+
+
+def zipf_bows(rng, n, words, nwords, a=1.1):
+    """n BowVectors of `words` distinct Zipf-distributed word ids (< nwords), L1-normalised random values."""
+    out = []
+    for _ in range(n):
+        ids = set()
+        while len(ids) < words:
+            ids.update(int(x) for x in np.minimum(rng.zipf(a, 2 * words) - 1, nwords - 1))
+        ids = np.sort(rng.permutation(np.array(sorted(ids), np.int64))[:words]).astype(np.int32)
+        v = rng.random(len(ids)) + 0.05
+        out.append((ids, v / v.sum()))
+    return out
+
+
+def test_scale_twenty_thousand_keyframes(voc_blob):
+    voc = orb.ORBVocabulary(voc_blob)
+    rng = np.random.default_rng(77)
+    n = 20000
+    bows = zipf_bows(rng, n + 100, 150, voc.nwords)
+    db = Both(voc)
+    for k in range(n):
+        db.add(k + 1, bows[k], k % 4)
+    db.set_covisibility({k: [k + d for d in (1, -1, 2, -2, 3) if 0 < k + d <= n] for k in range(1, n + 1, 3)})
+    lens = []
+    for q in range(50):
+        b = bows[n + q] if q % 2 else bows[int(rng.integers(0, n))]
+        lens.append(len(db.reloc(10 ** 6 + q, b, q % 4)))
+        db.nbest(int(rng.integers(1, n + 1)), b, [], q % 4, 3, [3] if q % 5 == 0 else [])
+    assert max(lens) > 0
+
+
+def test_two_threads_add_while_querying(voc_blob):
+    voc = orb.ORBVocabulary(voc_blob)
+    rng = np.random.default_rng(5)
+    base = zipf_bows(rng, 400, 150, 500000)
+    extra = [(ids + 500000, v) for ids, v in zipf_bows(rng, 400, 150, 400000)]  # words no query has
+    queries = zipf_bows(rng, 40, 150, 500000)
+    serial = kr.KeyFrameDatabase(voc.scoring)
+    gpu = orb.KeyFrameDatabase(voc)
+    for k, b in enumerate(base):
+        serial.add(k + 1, *b, 0)
+        gpu.add(k + 1, b, 0)
+    want = [serial.DetectRelocalizationCandidates(900 + i, *q, 0) for i, q in enumerate(queries)]
+    want_nb = [serial.DetectNBestCandidates(2000 + i, *q, [], 0, 3) for i, q in enumerate(queries)]
+    errors = []
+
+    def adder():
+        try:
+            for k, b in enumerate(extra):
+                gpu.add(10 ** 5 + k, b, 0)
+        except Exception as e:  # surfaced below
+            errors.append(e)
+    th = threading.Thread(target=adder)
+    th.start()
+    got = [gpu.DetectRelocalizationCandidates(900 + i, q, 0) for i, q in enumerate(queries)]
+    got_nb = [gpu.DetectNBestCandidates(2000 + i, q, [], 0, 3) for i, q in enumerate(queries)]
+    th.join()
+    assert not errors
+    assert got == want and got_nb == want_nb
+    assert any(want)

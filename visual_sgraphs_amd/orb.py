@@ -65,6 +65,10 @@ EXPORTS = [
     "vsg_orb_extract_to_frame",
     # round 5
     "vsg_host_kind", "vsg_orb_set_direct_registered",
+    # TemplatedVocabulary::score and the device-resident KeyFrameDatabase
+    "vsg_vocab_score", "vsg_kfdb_create", "vsg_kfdb_destroy", "vsg_kfdb_add", "vsg_kfdb_erase", "vsg_kfdb_clear",
+    "vsg_kfdb_clear_map", "vsg_kfdb_set_map", "vsg_kfdb_set_covisibility", "vsg_kfdb_detect_relocalization_candidates",
+    "vsg_kfdb_detect_n_best_candidates",
 ]
 
 
@@ -269,6 +273,21 @@ def load_library():
     L.vsg_shard_send_recv_boundary.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.vsg_shard_boundary_record.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.vsg_copy_d2d_async.argtypes = [ci, vp, vp, C.c_size_t, vp]
+    u64, i32 = C.c_uint64, C.c_int32
+    _u64p = C.POINTER(C.c_uint64)
+    L.vsg_vocab_score.argtypes = [vp, _i32p, _f64p, ci, _i32p, _i32p, _f64p, ci, _f64p]
+    L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
+    L.vsg_kfdb_destroy.argtypes = [vp]
+    L.vsg_kfdb_destroy.restype = None
+    L.vsg_kfdb_add.argtypes = [vp, u64, i32, _i32p, _f64p, ci]
+    L.vsg_kfdb_erase.argtypes = [vp, u64]
+    L.vsg_kfdb_clear.argtypes = [vp]
+    L.vsg_kfdb_clear_map.argtypes = [vp, i32]
+    L.vsg_kfdb_set_map.argtypes = [vp, _u64p, _i32p, ci]
+    L.vsg_kfdb_set_covisibility.argtypes = [vp, _u64p, _i32p, _u64p, ci]
+    L.vsg_kfdb_detect_relocalization_candidates.argtypes = [vp, u64, _i32p, _f64p, ci, i32, _u64p, ci, _i32p]
+    L.vsg_kfdb_detect_n_best_candidates.argtypes = [vp, u64, _i32p, _f64p, ci, _u64p, ci, i32, _i32p, ci, ci, _u64p,
+                                                    _i32p, _u64p, _i32p]
     _lib = L
     return L
 
@@ -799,6 +818,132 @@ class ORBVocabulary:
         return dict(bow_ids=bi[:nb.value].copy(), bow_vals=bv[:nb.value].copy(),
                     fv=(fn[:nf.value].copy(), fo[:nf.value + 1].copy(), fi[:fo[nf.value]].copy()),
                     word=w_of[:n].copy(), node=n_of[:n].copy(), weight=wt[:n].copy())
+
+
+    def score(self, a, b):
+        """TemplatedVocabulary::score(a, b) (TemplatedVocabulary.h:1214-1219): a and b are BowVectors as (ids, vals)
+        pairs or transform() dicts.  KL scoring raises VSG_ERR_UNSUPPORTED."""
+        return float(self.score_many(a, [b])[0])
+
+    def score_many(self, a, bs):
+        """score(a, b) for every BowVector b of `bs`: float64 array, bit-identical to the reference's doubles."""
+        qi, qv = _bow_arrays(a)
+        vs = [_bow_arrays(b) for b in bs]
+        off = np.zeros(len(vs) + 1, np.int32)
+        off[1:] = np.cumsum([len(i) for i, _ in vs]) if vs else []
+        ids = np.concatenate([i for i, _ in vs] + [np.zeros(1, np.int32)]).astype(np.int32)
+        vals = np.concatenate([v for _, v in vs] + [np.zeros(1, np.float64)]).astype(np.float64)
+        out = np.zeros(max(len(vs), 1), np.float64)
+        f64p = C.POINTER(C.c_double)
+        _check(self._L.vsg_vocab_score(self._h, _p(qi, _i32p), _p(qv, f64p), len(qi) if qi.size else 0, _p(off, _i32p),
+                                       _p(ids, _i32p), _p(vals, f64p), len(vs), _p(out, f64p)), "vsg_vocab_score")
+        return out[:len(vs)]
+
+
+def _bow_arrays(b):
+    """(ids int32, vals float64) of a BowVector given as a transform() dict or an (ids, vals) pair; the arrays have at
+    least one element (n is passed separately)."""
+    if isinstance(b, dict):
+        b = (b["bow_ids"], b["bow_vals"])
+    ids = np.ascontiguousarray(b[0], dtype=np.int32).reshape(-1)
+    vals = np.ascontiguousarray(b[1], dtype=np.float64).reshape(-1)
+    if len(ids) != len(vals):
+        raise ValueError("BowVector ids and values differ in length")
+    return ids, vals
+
+
+class KeyFrameDatabase:
+    """VS_GRAPHS::KeyFrameDatabase (orb_slam3/include/KeyFrameDatabase.h) resident on the device (vsg_kfdb_*).
+
+    Keyframes are the caller's integer ids (KeyFrame::mnId), maps integer ids (KeyFrame::GetMap()).  BowVectors are
+    (ids, vals) pairs or ORBVocabulary.transform() dicts.  The caller mirrors what the reference reads from KeyFrame:
+    the map (add / set_map) and GetBestCovisibilityKeyFrames(10) (set_covisibility)."""
+
+    def __init__(self, voc):
+        self._L = load_library()
+        self._voc = voc  # the vocabulary outlives the database
+        self._h = C.c_void_p()
+        self._seen = set()  # every keyframe id given to the database (bounds the candidates of a query)
+        _check(self._L.vsg_kfdb_create(voc._h, C.byref(self._h)), "vsg_kfdb_create")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._L.vsg_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, kf_id, bow, map_id=0):
+        i, v = _bow_arrays(bow)
+        self._seen.add(int(kf_id))
+        _check(self._L.vsg_kfdb_add(self._h, int(kf_id), int(map_id), _p(i, _i32p), _p(v, C.POINTER(C.c_double)), len(i)),
+               "vsg_kfdb_add")
+
+    def erase(self, kf_id):
+        _check(self._L.vsg_kfdb_erase(self._h, int(kf_id)), "vsg_kfdb_erase")
+
+    def clear(self):
+        _check(self._L.vsg_kfdb_clear(self._h), "vsg_kfdb_clear")
+
+    def clearMap(self, map_id):
+        _check(self._L.vsg_kfdb_clear_map(self._h, int(map_id)), "vsg_kfdb_clear_map")
+
+    def set_map(self, kf_ids, map_ids):
+        k = np.ascontiguousarray(kf_ids, dtype=np.uint64).reshape(-1)
+        m = np.ascontiguousarray(map_ids, dtype=np.int32).reshape(-1)
+        assert len(k) == len(m)
+        self._seen.update(int(x) for x in k)
+        if len(k):
+            _check(self._L.vsg_kfdb_set_map(self._h, _p(k, C.POINTER(C.c_uint64)), _p(m, _i32p), len(k)), "vsg_kfdb_set_map")
+
+    def set_covisibility(self, neighbours):
+        """neighbours: {kf_id: [neighbour ids in GetBestCovisibilityKeyFrames order]} (the first 10 are used)."""
+        if not neighbours:
+            return
+        ids = np.array(list(neighbours.keys()), dtype=np.uint64)
+        lists = [list(neighbours[int(k)]) for k in ids]
+        off = np.zeros(len(ids) + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in lists])
+        nb = np.array([x for l in lists for x in l] + [0], dtype=np.uint64)
+        self._seen.update(int(x) for x in ids)
+        self._seen.update(int(x) for l in lists for x in l[:10])
+        u64p = C.POINTER(C.c_uint64)
+        _check(self._L.vsg_kfdb_set_covisibility(self._h, _p(ids, u64p), _p(off, _i32p), _p(nb, u64p), len(ids)),
+               "vsg_kfdb_set_covisibility")
+
+    def DetectRelocalizationCandidates(self, query_id, bow, map_id):
+        """KeyFrameDatabase::DetectRelocalizationCandidates(F, pMap): list of keyframe ids, in the reference's order."""
+        i, v = _bow_arrays(bow)
+        u64p = C.POINTER(C.c_uint64)
+        # a query updates the keyframes' query state, so it cannot be repeated with a larger buffer: room for every
+        # keyframe id the database has seen
+        cap = max(len(self._seen), 1)
+        out, n = np.zeros(cap, np.uint64), C.c_int32()
+        _check(self._L.vsg_kfdb_detect_relocalization_candidates(self._h, int(query_id), _p(i, _i32p),
+                                                                 _p(v, C.POINTER(C.c_double)), len(i), int(map_id),
+                                                                 _p(out, u64p), cap, C.byref(n)),
+               "vsg_kfdb_detect_relocalization_candidates")
+        return [int(x) for x in out[:n.value]]
+
+    def DetectNBestCandidates(self, query_kf_id, bow, connected_ids, map_id, nNumCandidates, bad_map_ids=()):
+        """KeyFrameDatabase::DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates): (loop, merge) id lists."""
+        i, v = _bow_arrays(bow)
+        u64p = C.POINTER(C.c_uint64)
+        conn = np.array(list(connected_ids) + [0], dtype=np.uint64)
+        bad = np.array(list(bad_map_ids) + [0], dtype=np.int32)
+        nn = int(nNumCandidates)
+        lo, me = np.zeros(max(nn, 1), np.uint64), np.zeros(max(nn, 1), np.uint64)
+        nl, nm = C.c_int32(), C.c_int32()
+        _check(self._L.vsg_kfdb_detect_n_best_candidates(self._h, int(query_kf_id), _p(i, _i32p),
+                                                         _p(v, C.POINTER(C.c_double)), len(i), _p(conn, u64p),
+                                                         len(conn) - 1, int(map_id), _p(bad, _i32p), len(bad) - 1, nn,
+                                                         _p(lo, u64p), C.byref(nl), _p(me, u64p), C.byref(nm)),
+               "vsg_kfdb_detect_n_best_candidates")
+        return [int(x) for x in lo[:nl.value]], [int(x) for x in me[:nm.value]]
 
 
 def ComputeDistinctiveDescriptors(desc, off, device=0):
