@@ -29,6 +29,31 @@ def test_no_untested_environment_switch_in_the_library():
     assert names == TESTED_SWITCHES, names ^ TESTED_SWITCHES
 
 
+def test_no_build_time_switch_in_the_library():
+    """CPU-side guard: the only preprocessor conditionals under csrc/ tell the HIP compiler from a host compiler and the
+    device pass from the host pass.  A -D switch would build code that the default build never runs and no test covers."""
+    allowed = re.compile(r"#\s*if\s+defined\s*\(\s*(__HIPCC__|__HIP_DEVICE_COMPILE__)\s*\)\s*(//.*)?$")
+    bad = []
+    for f in sorted(p for p in CSRC.iterdir() if p.suffix in (".hip", ".h", ".inc")):
+        depth = 0
+        for no, line in enumerate(f.read_text().splitlines(), 1):
+            d = line.strip()
+            m = re.match(r"#\s*(\w+)", d)
+            if not m or m.group(1) not in ("if", "ifdef", "ifndef", "elif", "else", "endif"):
+                continue
+            if m.group(1) in ("if", "ifdef", "ifndef"):
+                if not allowed.match(d):
+                    bad.append(f"{f.name}:{no}: {d}")
+                depth += 1
+            elif m.group(1) == "elif" or depth == 0:
+                bad.append(f"{f.name}:{no}: {d}")
+            elif m.group(1) == "endif":
+                depth -= 1
+        if depth:
+            bad.append(f"{f.name}: unterminated #if")
+    assert not bad, "\n".join(bad)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("switch", ["VSG_NO_OVERLAP", "VSG_GRAPH", "VSG_ROCTX", ""])
 def test_switch_gives_the_oracles_output(switch):

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Diagnostic build for tools/oct_stamps.py: a COPY of visual_sgraphs_amd/csrc with s_memtime stamps at the phase boundaries
 of DistributeOctTree (tid 0 of every level's workgroup of frame 0; a debug export reads them back), compiled into
-tools/_bin/libvsg_octstamp<suffix>.so.  The tree itself is never touched; the real kernel executes no stamp.
-    python tools/build_oct_stamps.py [suffix] [-DVSG_...]"""
+tools/_bin/libvsg_octstamp<suffix>.so with the SOURCES and FLAGS of visual_sgraphs_amd/build.py.  The tree itself is never
+touched; the real kernel executes no stamp.
+    python tools/build_oct_stamps.py [suffix] [--sort-rounds] [extra hipcc flags]
+--sort-rounds also stamps every round of the octree's parallel introsort replay."""
 import shutil
 import subprocess
 import sys
@@ -10,7 +12,8 @@ import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "visual_sgraphs_amd" / "csrc"
+sys.path.insert(0, str(ROOT))
+from visual_sgraphs_amd.build import CSRC, FLAGS, SOURCES  # noqa: E402
 
 
 def sub(s, old, new, what):
@@ -19,8 +22,11 @@ def sub(s, old, new, what):
 
 
 def main():
-    suffix = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else ""
-    flags = [a for a in sys.argv[1:] if a.startswith("-")]
+    args = sys.argv[1:]
+    sort_rounds = "--sort-rounds" in args  # this tool's option, not the compiler's
+    args = [a for a in args if a != "--sort-rounds"]
+    suffix = args[0] if args and not args[0].startswith("-") else ""
+    flags = [a for a in args if a.startswith("-")]
     with tempfile.TemporaryDirectory() as td:
         d = Path(td) / "csrc"
         shutil.copytree(CSRC, d, ignore=shutil.ignore_patterns("_obj"))
@@ -66,8 +72,9 @@ __device__ __forceinline__ void vsg_oct_stamp(int tag) {
 '''
         s = sub(s, '#include "vsg_octree_core.h"', stamp + '#include "vsg_octree_core.h"', "include")
         s = sub(s, "  octree::Work W;\n  octree::carve(W, oct_lds, cap, a.hist_big != 0);\n  BlockGroup g;", "  VSG_OCT_STAMP(0);\n  octree::Work W;\n  octree::carve(W, oct_lds, cap, a.hist_big != 0);\n  BlockGroup g;", "enter")
-        if "--sort-rounds" in sys.argv:  # one stamp per round of the introsort replay (each stamp costs the wave ~1 k cycles)
-            s = sub(s, "          }\n        }\n        __syncthreads();\n      }\n      return;\n    }\n#endif", "          }\n        }\n        __syncthreads();\n        VSG_OCT_STAMP(50);\n      }\n      return;\n    }\n#endif", "sort round")
+        if sort_rounds:  # one stamp per round of the introsort replay (each stamp costs the wave ~1 k cycles)
+            s = sub(s, "        __syncthreads();\n      }\n      return;\n    }\n    if (tid >= 64) return;",
+                    "        __syncthreads();\n        VSG_OCT_STAMP(50);\n      }\n      return;\n    }\n    if (tid >= 64) return;", "sort round")
         s = sub(s, "  if (threadIdx.x == 0) sel_count[frame * kMaxLevels + level] = n;\n", "  if (threadIdx.x == 0) sel_count[frame * kMaxLevels + level] = n;\n  VSG_OCT_STAMP(31);\n", "exit")
         export = '''extern "C" int vsg_debug_oct_stamps(unsigned long long *out, int reset) {
   hipDeviceSynchronize();
@@ -84,9 +91,7 @@ __device__ __forceinline__ void vsg_oct_stamp(int tag) {
         k.write_text(s)
         out = ROOT / "tools" / "_bin" / f"libvsg_octstamp{suffix}.so"
         out.parent.mkdir(exist_ok=True)
-        srcs = ["vsg_kernels.hip", "vsg_orb.hip", "vsg_match.hip", "vsg_grid.hip", "vsg_bow.hip", "vsg_frame.hip", "vsg_ctx.hip", "vsg_shard.hip"]
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-w",
-               "-mllvm", "-amdgpu-mfma-vgpr-form"] + flags + ["-o", str(out)] + [str(d / x) for x in srcs] + ["-ldl", "-lpthread"]
+        cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + flags + ["-o", str(out)] + [str(d / x) for x in SOURCES] + ["-ldl", "-lpthread"]
         subprocess.check_call(cmd, cwd=str(d))
         print("built", out)
 

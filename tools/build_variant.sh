@@ -1,12 +1,17 @@
 #!/bin/bash
-# Build a library variant for in-run A/B (tools/ab_lib.sh, tools/pmc_ab.sh): tools/_bin/libvsg_<name>.so with extra
-# -D flags; the in-tree library is not touched.   Usage: tools/build_variant.sh <name> [-DVSG_...=..] ...
+# Build a library variant for in-run A/B (tools/ab_lib.sh, tools/ab_chain.sh, tools/pmc_ab.sh): tools/_bin/libvsg_<name>.so
+# from the sources as they are, with the SOURCES and FLAGS of visual_sgraphs_amd/build.py plus any extra flags; the in-tree
+# library is not touched.  The library has no build-time switches: a variant is an edit of the sources (a constant, a code
+# path) on a branch of its own.   Usage: tools/build_variant.sh <name> [extra hipcc flags] ...
 set -e
 name=$1; shift
 cd "$(dirname "$0")/.."
-C=visual_sgraphs_amd/csrc
 mkdir -p tools/_bin
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -w -mllvm -amdgpu-mfma-vgpr-form "$@" \
-  -o tools/_bin/libvsg_$name.so $C/vsg_kernels.hip $C/vsg_orb.hip $C/vsg_match.hip $C/vsg_grid.hip $C/vsg_bow.hip \
-  $C/vsg_frame.hip $C/vsg_ctx.hip $C/vsg_shard.hip -ldl -lpthread
+eval "$(python3 -c '
+import shlex
+from visual_sgraphs_amd.build import CSRC, FLAGS, SOURCES
+print("flags=(%s)" % " ".join(map(shlex.quote, FLAGS)))
+print("srcs=(%s)" % " ".join(shlex.quote(str(CSRC / s)) for s in SOURCES))
+')"
+/opt/rocm/bin/hipcc "${flags[@]}" "$@" -o tools/_bin/libvsg_$name.so "${srcs[@]}" -ldl -lpthread
 echo "built tools/_bin/libvsg_$name.so"

@@ -14,7 +14,9 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
+sys.path.insert(0, str(ROOT))
 from source_hash import source_hash  # noqa: E402
+from visual_sgraphs_amd.build import CSRC, FLAGS  # noqa: E402
 
 FULL = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_lshrrev_b32", "v_ashrrev_i32",
         "v_mov_b32", "v_add_f32", "v_mul_f32", "v_fma_f32", "v_min_i16", "v_add_u16", "v_sub_u16", "v_not_b32",
@@ -25,15 +27,14 @@ KERNELS = {"k_pyramid": "pyramid", "k_fast_cells": "fast", "k_blur": "blur", "k_
 
 
 def main():
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-mllvm",
-             "-amdgpu-mfma-vgpr-form", "--cuda-device-only", "-S"]
+    flags = [f for f in FLAGS if f != "-shared"] + ["--cuda-device-only", "-S"]
     out = {"source_hash": source_hash(), "rates_cycles": {"full": 2.3, "half": 4.2},
            "_comment": __doc__.split("python tools")[0].strip()}
     with tempfile.TemporaryDirectory() as td:
         for src in ("vsg_kernels.hip", "vsg_match.hip"):
             asm = Path(td) / (src + ".s")
-            subprocess.run(["hipcc"] + flags + ["-o", str(asm), str(ROOT / "visual_sgraphs_amd" / "csrc" / src)],
-                           check=True, stderr=subprocess.DEVNULL, cwd=str(ROOT / "visual_sgraphs_amd" / "csrc"))
+            subprocess.run(["hipcc"] + flags + ["-o", str(asm), str(CSRC / src)], check=True, stderr=subprocess.DEVNULL,
+                           cwd=str(CSRC))
             name, counts = None, None
             for line in asm.read_text().splitlines():
                 m = re.match(r"^(_Z\w+):\s", line + " ")

@@ -92,24 +92,16 @@ __global__ __launch_bounds__(256) void k_bow_descend(const NodeRec *__restrict__
 // FeatureVector.cpp:31-45).  The reference inserts feature by feature into two std::maps; the same content falls out of
 // two sorts of (id << 32 | feature) keys -- ascending ids, the features of an id in feature order.  Two launches: the rank
 // of every key among the frame's keys, computed all over the chip (k_bow_rank; stopped words -- weight <= 0 -- take no part),
-// then one workgroup per container (k_bow_assemble): group heads by a block scan, and the floating point exactly as the
-// reference orders it:
-//   * addWeight: every feature of a word carries the word's weight, so the running sum in feature order is the weight
-//     added to itself (count - 1) times, left to right -- the head's thread does just that;
-//   * normalize(): the L1 / L2 norm is ONE sequential sum in ascending word id (thread 0), then a correctly rounded
-//     division (and square root) per entry -- IEEE operations, no contraction (-ffp-contract=off): bit-identical doubles.
-// The host copies the result out of the pinned arena, nothing else; the FeatureVector also stays RESIDENT in the frame
-// (Frame::mFeatVec), where the SearchByBoW kernels join it with another frame's without a host round trip.
+// then one workgroup per container (k_bow_assemble): group heads by a block scan, and addWeight exactly as the reference
+// orders it: every feature of a word carries the word's weight, so the running sum in feature order is the weight added to
+// itself (count - 1) times, left to right -- the head's thread does just that.  The FeatureVector also stays RESIDENT in the
+// frame (Frame::mFeatVec), where the SearchByBoW kernels join it with another frame's without a host round trip.
 enum { kAsmMax = 2048, kAsmThreads = 1024 };  // features a frame may hold for the device assembly (C4: 2000 + 24)
 // BowVector::normalize (BowVector.cpp:62-84) is ONE dependent chain of n_bow double additions (the reference's loop order IS
 // the result) followed by n_bow divisions: nothing a GPU has to offer -- one lane, ~10 cycles per dependent v_add_f64 at
 // <= 2.4 GHz against 4 cycles at the host's clock.  Measured (profiles/r06_*_bow_norm_ab.txt): the chain on the device
 // lengthens k_bow_assemble by more than the whole host pass takes.  So the kernel leaves the values as addWeight made them
-// and the host normalises what it copies out; -DVSG_BOW_NORM_DEVICE=1 builds the all-device form (same bytes, tested).
-#ifndef VSG_BOW_NORM_DEVICE
-#define VSG_BOW_NORM_DEVICE 0
-#endif
-constexpr bool kNormOnDevice = VSG_BOW_NORM_DEVICE != 0;
+// and the host normalises what it copies out (bow_normalize_host).
 struct BowOut {
   int *hdr;  // {n_bow, n_fv, features with a non-stopped word, 0}
   int *bow_ids;
@@ -183,15 +175,14 @@ __global__ __launch_bounds__(kAsmThreads) void k_bow_rank(const int *__restrict_
 }
 
 // Step 2, two workgroups side by side: block 0 turns the sorted word keys into the BowVector, block 1 the sorted node keys
-// into the FeatureVector (the BowVector's sequential norm is the long pole; the FeatureVector finishes in its shadow).
+// into the FeatureVector.
 __global__ __launch_bounds__(kAsmThreads) void k_bow_assemble(const uint64_t *__restrict__ sorted_w,
                                                               const uint64_t *__restrict__ sorted_n,
                                                               const double *__restrict__ weight_of, int n, int tf,
-                                                              int scoring, int normalize, BowOut o) {
+                                                              BowOut o) {
   __shared__ uint64_t key[kAsmMax];
   __shared__ double vals[kAsmMax];
   __shared__ int wsum[kAsmThreads / 64];
-  __shared__ double s_norm;
   const int tid = threadIdx.x;
   const bool words = blockIdx.x == 0;
   // m = features with a non-stopped word = keys in either sorted array; every global load of the prologue is requested
@@ -226,38 +217,9 @@ __global__ __launch_bounds__(kAsmThreads) void k_bow_assemble(const uint64_t *__
       o.bow_ids[j] = (int)(key[p] >> 32);
     }
     __syncthreads();
-    if (!normalize) {  // the values as addWeight left them; normalize() runs on the host (see bow_finish)
-      for (int j = tid; j < n_bow; j += kAsmThreads) o.bow_vals[j] = vals[j];
-      if (tid == 0) o.hdr[0] = n_bow, o.hdr[2] = m, o.hdr[3] = 0;
-      return;
-    }
-    const bool must = scoring != 5;  // DotProductScoring: no normalisation (ScoringObject.h:73-89)
-    if (tid == 0) {
-      double norm = 0.0;
-      if (tf && !must) {
-        norm = (double)n_bow;  // TemplatedVocabulary.h:1181-1186: divide by the number of words
-      } else if (must) {       // BowVector::normalize (:62-84): L2 for L2Scoring, L1 otherwise -- ONE sum in id order
-        // sixteen values requested at a time, then added IN ORDER (one dependent chain of n_bow additions is what the
-        // reference's loop is; the LDS round trips need not be part of it)
-        const bool l2 = scoring == 1;
-        int j = 0;
-        for (; j + 16 <= n_bow; j += 16) {
-          double v[16];
-#pragma unroll
-          for (int q = 0; q < 16; q++) v[q] = vals[j + q];
-#pragma unroll
-          for (int q = 0; q < 16; q++) norm += l2 ? v[q] * v[q] : fabs(v[q]);
-        }
-        for (; j < n_bow; j++) norm += l2 ? vals[j] * vals[j] : fabs(vals[j]);
-        if (l2) norm = sqrt(norm);
-      }
-      s_norm = norm;
-      o.hdr[0] = n_bow, o.hdr[2] = m, o.hdr[3] = 0;
-    }
-    __syncthreads();
-    const double norm = s_norm;
-    const bool divide = (tf && !must && n_bow > 0) || (must && norm > 0.0);
-    for (int j = tid; j < n_bow; j += kAsmThreads) o.bow_vals[j] = divide ? vals[j] / norm : vals[j];
+    // the values as addWeight left them; normalize() runs on the host (see bow_finish)
+    for (int j = tid; j < n_bow; j += kAsmThreads) o.bow_vals[j] = vals[j];
+    if (tid == 0) o.hdr[0] = n_bow, o.hdr[2] = m, o.hdr[3] = 0;
   } else {  // ---- FeatureVector: node id -> the features below it, ascending (FeatureVector.cpp:31-45)
     const int n_fv = n_heads;
     for (int q = 0; q < 2; q++) {
@@ -540,8 +502,7 @@ int bow_enqueue(BowCall *b, vsg_vocab *voc, const uint8_t *desc, const uint8_t *
     uint64_t *s_sw = (uint64_t *)(dv + dSortW), *s_sn = (uint64_t *)(dv + dSortN);
     hipLaunchKernelGGL(k_bow_rank, dim3((n + 63) / 64), dim3(kAsmThreads), 0, c->stream, s_word, s_node, s_w, n, s_sw, s_sn);
     B_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bow_assemble, dim3(2), dim3(kAsmThreads), 0, c->stream, s_sw, s_sn, s_w, n, tf, voc->scoring,
-                       (int)kNormOnDevice, o);
+    hipLaunchKernelGGL(k_bow_assemble, dim3(2), dim3(kAsmThreads), 0, c->stream, s_sw, s_sn, s_w, n, tf, o);
     B_TRY(hipGetLastError());
     if (res) {
       // the joins of the SearchByBoW kernels launch one wavefront per POSSIBLE node of the FeatureVector's level
@@ -567,14 +528,14 @@ int bow_finish(BowCall *b, int32_t *bow_ids, double *bow_vals, int bow_cap, int 
   if (word_of) memcpy(word_of, word, 4 * (size_t)n);
   if (node_of) memcpy(node_of, node, 4 * (size_t)n);
   if (weight_of) memcpy(weight_of, w, 8 * (size_t)n);
-  if (b->device_assembly) {  // the kernel left everything in final form: copy, nothing else
+  if (b->device_assembly) {  // the kernel left everything in final form but the BowVector's norm
     const int *hdr = (const int *)(hp + b->oHdr);
     const int nb = hdr[0], nf = hdr[1], m = hdr[2];
     *n_bow = nb, *n_fv = nf;
     if (bow_ids && bow_vals && nb <= bow_cap) {
       memcpy(bow_ids, hp + b->oBowId, 4 * (size_t)nb);
       memcpy(bow_vals, hp + b->oBowVal, 8 * (size_t)nb);
-      if (!kNormOnDevice) bow_normalize_host(b->voc, bow_vals, nb);
+      bow_normalize_host(b->voc, bow_vals, nb);
     }
     if (fv_node && fv_idx && nf <= fv_cap) {
       memcpy(fv_node, hp + b->oFvNode, 4 * (size_t)nf);

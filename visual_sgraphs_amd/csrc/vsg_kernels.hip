@@ -41,20 +41,18 @@ __device__ __forceinline__ const uint8_t *level_ptr(const FrameGeom *fg, const S
 // ONE frame are spread over all eight private L2s and every L2 fetches the frame (and its halos) again.  The remap
 // gives the blocks that share an XCD whole frames: block L of the launch works on frame 8 * (slot / nx) + L % 8, item
 // slot % nx (slot = L / 8).  Bijective over the first ny & ~7 frames; the tail frames keep the plain mapping.  A
-// pure speed choice: results do not depend on it.  VSG_NO_XCD_REMAP builds without it (A/B).
+// pure speed choice: results do not depend on it.
 struct BlockXY {
   int x, y;
 };
 __device__ __forceinline__ BlockXY frame_major_block() {
   BlockXY b = {(int)blockIdx.x, (int)blockIdx.y};
-#ifndef VSG_NO_XCD_REMAP
   const unsigned nx = gridDim.x, ny8 = gridDim.y & ~7u;
   if (blockIdx.y < ny8) {
     const unsigned L = blockIdx.y * nx + blockIdx.x, slot = L >> 3, q = slot / nx;
     b.y = (int)(q * 8 + (L & 7));
     b.x = (int)(slot - q * nx);
   }
-#endif
   return b;
 }
 
@@ -101,10 +99,7 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 // ORBextractor.cc:1184), writing to HBM only the part of each level it owns.  Ownership boundaries are the source
 // indices of the destination boundaries, so tiles partition every level without gaps or overlaps; the ~25 % halo
 // is recomputed instead of communicated.  HBM traffic: level 0 read once (+halo), levels 1.. written once.
-#ifndef VSG_PYR_NT
-#define VSG_PYR_NT 256
-#endif
-constexpr int kPyrThreads = VSG_PYR_NT;  // threads per pyramid tile (512: 0.196 -> 0.203 ms, 1024: 0.31 ms per 256 C2 frames)
+constexpr int kPyrThreads = 256;  // threads per pyramid tile (512: 0.196 -> 0.203 ms, 1024: 0.31 ms per 256 C2 frames)
 
 __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ pyr, const FrameGeom *__restrict__ fg,
                                                  const Short4 *__restrict__ tile_tab, Src0 s0,
@@ -133,12 +128,7 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
     const int x0a = T.need[0][0] & ~3, y0 = T.need[0][1];
     const int w4 = ((T.need[0][2] - x0a) + 3) >> 2, hh = T.need[0][3] - y0, pitch = 4 * w4;
     const uint8_t *src = s0.base + (size_t)frame * s0.frame_stride + (size_t)y0 * s0.pitch + x0a;
-#ifdef VSG_PYR_STAGE1
-    const bool narrow = true;
-#else
-    const bool narrow = w4 < 4;
-#endif
-    if (narrow) {
+    if (w4 < 4) {
       const float inv = __builtin_amdgcn_rcpf((float)w4);
       for (int i = tid; i < w4 * hh; i += kPyrThreads) {
         const int r = div_small(i, inv), c = i - r * w4;
@@ -319,24 +309,9 @@ __device__ __forceinline__ int wave_inclusive_scan_i32(int v) {
   return v;
 }
 
-// phase 1b's trigger (see there): NUM x (runs with a passer) > DEN x (runs of the cell), per pass: more than half of the
-// runs at iniThFAST, more than a quarter in the minThFAST pass -- there the two-pair test passes 17-50 % of a natural
-// cell's pixels and the four-pair test removes 60 % of them for the price of 4 % of the pass (in-run A/Bs of eight
-// settings: profiles/r05_a_fast_pass_ablation.txt, r05_d_fast_stage_b_trigger_ab.txt)
-#ifndef VSG_FAST_STAGE_B_NUM
-#define VSG_FAST_STAGE_B_NUM(pass) ((pass) ? 4 : 2)
-#define VSG_FAST_STAGE_B_DEN(pass) 1
-#endif
-#ifndef VSG_OD_SPATIAL
-#define VSG_OD_SPATIAL 0  // k_orient_desc processes a level's keypoints in Morton order of their cells (experiment)
-#endif
-#ifndef VSG_FAST_STAGE_C
-#define VSG_FAST_STAGE_C 0  // phase 1c: 0 = off (default), 1 = with phase 1b in both passes, 2 = minThFAST pass only, 3 = iniThFAST pass only
-#endif
-#ifndef VSG_FAST_NT
-#define VSG_FAST_NT 128  // threads per FAST cell: 2 waves keep more cells resident per CU than 4 (measured: 0.47 ->
-                         // 0.38 ms per 256 frames); 1 wave runs out of LDS before it runs out of wave slots
-#endif
+// threads per FAST cell: 2 waves keep more cells resident per CU than 4 (measured: 0.47 -> 0.38 ms per 256 frames); 1 wave
+// runs out of LDS before it runs out of wave slots
+constexpr int kFastThreads = 128;
 
 // ------------------------------------------------------------------------------------------------
 // The cell kernel.  Per cell: the valid region (3 px inside the reference's sub-image) staged in LDS, a cheap necessary
@@ -438,9 +413,8 @@ __device__ __forceinline__ uint32_t fast_flag_mask8(uint32_t m8) {
 
 // More than 80 SGPRs (VCC and the reserved ones included) cost a wave slot per SIMD on gfx950: with 75-77 numbered SGPRs
 // the one-cell form of this kernel ran at 0.470 ms per 512 C2 frames, capped (a few scalars live in VGPR lanes) at 0.440.
-#ifndef VSG_FAST_SGPRS
-#define VSG_FAST_SGPRS 80
-#endif
+constexpr int kFastSgprs = 80;
+constexpr int kFastWaves = 8;  // waves per SIMD k_fast_cells is compiled for
 // One cell's record (FastCellRec, vsg_common.h) as ONE 32-byte scalar load, and what the staging code derives from it.
 struct FastCell {
   uint32_t w3, first_mask, last_mask, cand_off, xy;
@@ -484,29 +458,13 @@ __device__ __forceinline__ FastCell load_fast_cell(const FastCellRec *__restrict
 // A comparison on a value that passed through an empty asm is not loop-invariant to the compiler: it is made where it is
 // used (one v_cmp) instead of once in front of the cell loop, parked as a 64-bit lane mask in two VGPR lanes and read back
 // with two v_readlane_b32 at every use (the SGPR cap again)
-#ifndef VSG_FAST_OPQ
-#define VSG_FAST_OPQ 1
-#endif
-#ifndef VSG_FAST_HINTS
-#define VSG_FAST_HINTS 1
-#endif
-#if VSG_FAST_OPQ
 #define VSG_OPQ(x) ([&] { int t_ = (x); asm volatile("" : "+v"(t_)); return t_; }())
-#else
-#define VSG_OPQ(x) (x)
-#endif
 // block-frequency hints for the paths that almost never run (slivers, tiles that were not prefetched, the one-entry-per-pixel
 // re-unpack, levels of more than 4096 cells): the register allocator weighs spills by block frequency
-#if VSG_FAST_HINTS
 #define VSG_COLD(x) __builtin_expect(!!(x), 0)
 #define VSG_HOT(x) __builtin_expect(!!(x), 1)
-#else
-#define VSG_COLD(x) (x)
-#define VSG_HOT(x) (x)
-#endif
-#ifndef VSG_FAST_KA
-#define VSG_FAST_KA 3   // bit 0: the next cell's image bases, 1: the cell counter, 2: the candidate segment, 3: the record array
-#endif
+// Re-loaded from the kernarg segment: the next cell's image bases and the cell counter.  The record array and the candidate
+// segment stay arguments (re-loading them as well was slower: profiles/r06_c_fast_kernarg_ab.txt)
 struct FastKArgs {
   const uint8_t *pyr;
   const FrameGeom *fg;
@@ -530,11 +488,7 @@ __device__ __forceinline__ FastKArgsPtr fast_kargs() {
 // L2 (profiles/r03_c_fast_ablation.txt: 0.065 / 0.074 / 0.108 / 0.221 ms for workgroups that end at once / after the
 // descriptors / after a staging pass without loads / after the real staging pass, of 0.441 ms).
 template <int NT, int kTileP, int kScoreP, int kPre>
-#ifndef VSG_FAST_WAVES_MIN
-#define VSG_FAST_WAVES_MIN 8
-#define VSG_FAST_WAVES_MAX 8
-#endif
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS), amdgpu_waves_per_eu(VSG_FAST_WAVES_MIN, VSG_FAST_WAVES_MAX))) void k_fast_cells(
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amdgpu_waves_per_eu(kFastWaves, kFastWaves))) void k_fast_cells(
     const uint8_t *__restrict__ pyr, const FrameGeom *__restrict__ fg, const FastCellRec *__restrict__ recs, Src0 s0,
     uint32_t *__restrict__ cand, int *__restrict__ cand_count, int *__restrict__ cell_count, int tile_bytes,
     int score_bytes, int queue_cap, int cells_per_wg, int pyr_frame_bytes, int total_cells, int cand_frame, int th_pack) {
@@ -614,19 +568,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
     // the record of the next cell: its scalar load runs beside the LDS writes below.  Its inputs come from the kernarg
     // segment again (see FastKArgs); the record array carries one empty record past its end, so no clamp of the index
     FastCell N;
-#if VSG_FAST_KA & 1
     {
       const FastKArgsPtr ka = fast_kargs();
       const Src0 ks0 = {ka->s0.base, ka->s0.frame_stride, ka->s0.pitch};
-#if VSG_FAST_KA & 8
-      N = load_fast_cell(ka->recs + (ci + 1), ks0, ka->pyr, ka->pyr_frame_bytes, frame);
-#else
       N = load_fast_cell(recs + (ci + 1), ks0, ka->pyr, ka->pyr_frame_bytes, frame);
-#endif
     }
-#else
-    N = load_fast_cell(recs + (ci + 1), s0, pyr, pyr_frame_bytes, frame);
-#endif
     const bool live = C.live();
     if (live) {
       if (VSG_COLD(C.tdw() < 4)) {  // a sliver of a cell at the right edge of a level (cell-uniform)
@@ -656,12 +602,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
     have_pre = ci + 1 < c_end && fetch(N);
     const bool seg = (th_pack >> 16) != 0;
     auto my_count = [&]() -> int * {  // the cell's counter, from the kernarg segment at the moment it is written
-#if VSG_FAST_KA & 2
       const FastKArgsPtr ka = fast_kargs();
       return ka->cell_count + ((size_t)frame * ka->total_cells + ci);
-#else
-      return cell_count + ((size_t)frame * total_cells + ci);
-#endif
     };
     if (!live) {  // empty cell
       if (seg && VSG_OPQ(tid) == 0) *my_count() = 0;
@@ -687,9 +629,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
         const int p1_off = (p1_row + 3) * kTileP + 4 * (g0 + 2 * p1_rr);
         uint32_t keep = 0;
         int nq = 0, thr = iniTh;
-#ifdef VSG_FAST_PASS_UNROLL
-#pragma unroll VSG_FAST_PASS_UNROLL
-#endif
         for (int pass = 0; pass < 2; pass++) {
           if (VSG_OPQ(tid) < 5) s_cnt[tid] = 0;
           __syncthreads();  // the tile is staged / the previous pass is done with the score rows
@@ -742,7 +681,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
             thr = minTh;
             continue;
           }
-#ifndef VSG_FAST_NO_STAGE_B
           // ---- phase 1b, dense cells only: the same necessary test on the two DIAGONAL ring pairs (ring positions 2 / 10
           // and 6 / 14: offsets (+-2, +-2)), run entry by run entry.  A 9-arc holds one pixel of every opposite pair, so a
           // corner on a side needs that side on all four tested pairs.  On the frames the pipeline is tuned on a cell
@@ -751,8 +689,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
           // test, on ramps on both sides, and the cell scored its whole area two or three times per threshold (FAST launch
           // 1.05-2.47 ms instead of 0.39 per 512 frames: profiles/r04_b_bench_content_sweep_before_stage_b.json).  The
           // diagonals see the other phase of a checkerboard and the iso-line of a ramp.  Cell-uniform trigger: the share of
-          // the cell's runs that hold a passer (VSG_FAST_STAGE_B_NUM / _DEN above).
-          if (VSG_FAST_STAGE_B_NUM(pass) * s_cnt[4] > VSG_FAST_STAGE_B_DEN(pass) * nruns) {
+          // the cell's runs that hold a passer -- more than half of them at iniThFAST, more than a quarter in the minThFAST
+          // pass; there the two-pair test passes 17-50 % of a natural cell's pixels and the four-pair test removes 60 % of
+          // them for the price of 4 % of the pass (in-run A/Bs of eight settings: profiles/r05_a_fast_pass_ablation.txt,
+          // r05_d_fast_stage_b_trigger_ab.txt).
+          if ((pass ? 4 : 2) * s_cnt[4] > nruns) {
             const int nr1 = s_cnt[4];
             const int t6 = thr <= 2 ? 0 : min(64, (thr + 1) >> 2);
             const uint32_t K = (uint32_t)(128 - t6) * 0x01010101u, H = 0x80808080u;
@@ -783,50 +724,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
               runF[e] = F0 & VSG_BITOP3(g[1], g[0] >> 2, 0xC0C0C0C0u, (A & C) | (B & ~C));
             }
             __syncthreads();
-#if VSG_FAST_STAGE_C
-            // ---- phase 1c (round 6 experiment, VERDICT r5 #2b; OFF by default -- measured: profiles/r06_d_fast_stage_c_ab.txt):
-            // the same necessary test on the remaining FOUR ring pairs (1 / 9, 3 / 11, 5 / 13, 7 / 15: rows +-3 at columns -+1,
-            // rows +-1 at columns -+3), run entry by run entry, for cells that took phase 1b.  ~95 vector instructions per run
-            // entry against 62 per queued pixel it removes.
-            if (VSG_FAST_STAGE_C == 1 || (VSG_FAST_STAGE_C == 2 && pass == 1) || (VSG_FAST_STAGE_C == 3 && pass == 0)) {
-              for (int e = tid; e < nr1; e += NT) {
-                const uint32_t F0 = runF[e];
-                if (!F0) continue;
-                const int runB = runI[e];
-                const uint32_t *pc = (const uint32_t *)&qtile[runB];
-                const uint32_t *p3u = pc - 3 * (kTileP / 4), *p3d = pc + 3 * (kTileP / 4), *p1u = pc - (kTileP / 4),
-                               *p1d = pc + (kTileP / 4);
-                uint32_t u3[4] = {p3u[-1], p3u[0], p3u[1], p3u[2]}, d3[4] = {p3d[-1], p3d[0], p3d[1], p3d[2]};
-                uint32_t u1[4] = {p1u[-1], p1u[0], p1u[1], p1u[2]}, d1[4] = {p1d[-1], p1d[0], p1d[1], p1d[2]};
-                const uint32_t qc[2] = {pc[0], pc[1]};
-                const int col = runB - kTileP * div_small(runB, 1.0f / kTileP);
-                const uint32_t left = (g0 == 0 && col == 0) ? 0u : ~0u;  // the dword left of tile column 0 (see phase 1)
-                u3[0] &= left, d3[0] &= left, u1[0] &= left, d1[0] &= left;
-                uint32_t g[2];
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                  const uint32_t n9 = __builtin_amdgcn_alignbyte(u3[k + 1], u3[k], 3);       // row -3, columns -1
-                  const uint32_t n7 = __builtin_amdgcn_alignbyte(u3[k + 2], u3[k + 1], 1);   // row -3, columns +1
-                  const uint32_t n15 = __builtin_amdgcn_alignbyte(d3[k + 1], d3[k], 3);      // row +3, columns -1
-                  const uint32_t n1 = __builtin_amdgcn_alignbyte(d3[k + 2], d3[k + 1], 1);   // row +3, columns +1
-                  const uint32_t n11 = __builtin_amdgcn_alignbyte(u1[k + 1], u1[k], 1);      // row -1, columns -3
-                  const uint32_t n5 = __builtin_amdgcn_alignbyte(u1[k + 2], u1[k + 1], 3);   // row -1, columns +3
-                  const uint32_t n13 = __builtin_amdgcn_alignbyte(d1[k + 1], d1[k], 1);      // row +1, columns -3
-                  const uint32_t n3 = __builtin_amdgcn_alignbyte(d1[k + 2], d1[k + 1], 3);   // row +1, columns +3
-                  const uint32_t A = qc[k] + K, B = K - qc[k];
-                  const uint32_t dA = VSG_BITOP3((A - n1) | (A - n9), (A - n7) | (A - n15), (A - n3) | (A - n11), A & B & C);
-                  const uint32_t dark = dA & ((A - n5) | (A - n13));
-                  const uint32_t bA = VSG_BITOP3((B + n1) | (B + n9), (B + n7) | (B + n15), (B + n3) | (B + n11), A & B & C);
-                  const uint32_t bright = bA & ((B + n5) | (B + n13));
-                  g[k] = VSG_BITOP3(dark, bright >> 1, H, (A & C) | (B & ~C));
-                }
-                runF[e] = F0 & VSG_BITOP3(g[1], g[0] >> 2, 0xC0C0C0C0u, (A & C) | (B & ~C));
-              }
-              __syncthreads();
-            }
-#endif
+            // (phase 1c, the same test on the remaining four ring pairs: slower, profiles/r06_d_fast_stage_c_ab.txt)
           }
-#endif
           // ---- run list -> pixel queue.  Entry = the run's dword index in the tile << 5 | bit position of the flag in the
           // run's word (bit 0 of the position: dark side; bit 2, set in every flag position, cleared = retry); phase 2 turns
           // an entry into the pixel's byte offset in the tile -- two shifts and two masks, no division by the run count, no
@@ -921,15 +820,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(VSG_FAST_SGPRS),
             __syncthreads();
           }
           // ---- phase 3: non-max suppression inside the cell
-          uint32_t *seg_out;
-#if VSG_FAST_KA & 4
-          {
-            const FastKArgsPtr ka = fast_kargs();
-            seg_out = ka->cand + ((size_t)frame * ka->cand_frame + C.cand_off);
-          }
-#else
-          seg_out = cand + ((size_t)frame * cand_frame + C.cand_off);
-#endif
+          uint32_t *seg_out = cand + ((size_t)frame * cand_frame + C.cand_off);
           keep = 0;  // bit per loop iteration: queued pixel survives NMS
           int it = 0;
           int nbias = kScoreP + 1;  // the 3 x 3 neighbourhood at non-negative offsets from one register (see kBias)
@@ -1092,9 +983,7 @@ struct BlockGroup {
   // A_k < B_k; it returns min(A_K, B_{K-1}) at the first K with A_K >= B_K.  The pairs are disjoint, so ranks from
   // wave ballots, one parallel round of swaps and a popcount reproduce a whole partition step.  Median selection
   // and the (rare) heapsort fallback stay on lane 0.  Other waves fall through; the caller's barrier orders them.
-#ifndef VSG_OCT_RANK_UNROLL
-#define VSG_OCT_RANK_UNROLL 6  // neighbour keys in flight at a time in the register form's stable ranks
-#endif
+  static constexpr int kRankUnroll = 6;  // neighbour keys in flight at a time in the register form's stable ranks
   // n <= 64 (the careful phase of every level whose list holds at most 64 splittable nodes: all of C2's): the array lives
   // in the 64 lanes' REGISTERS.  Median selection reads three lanes (v_readlane, scalar compares), the A / B position
   // lists are ranks of two ballots, lane k learns (A_k, B_k) through two ds_permute, the partners through two more and
@@ -1178,7 +1067,7 @@ struct BlockGroup {
       const int lo_t = lane > 15 ? lane - 15 : 0, hi_t = lane + 15 < n - 1 ? lane + 15 : n - 1;
       int rank = lo_t;
       // (six neighbours in flight at a time: all thirty at once cost the whole kernel ~ 150 spilled registers)
-#pragma unroll VSG_OCT_RANK_UNROLL
+#pragma unroll kRankUnroll
       for (int i = 0; i < 30; i++) {
         const int d = i < 15 ? i - 15 : i - 14;
         const int j = lane + d;
@@ -1192,22 +1081,17 @@ struct BlockGroup {
     __threadfence_block();
   }
   __device__ bool sort_to_proc(introsort::item_t *a, int n, uint16_t *proc) {
-#ifndef VSG_OCT_NO_REGSORT
     if (n <= 64) {
       sort_partition_phase_regs(a, n, proc);
       return true;
     }
-#endif
     return false;
   }
   __device__ void sort_partition_phase(introsort::item_t *a, int n, uint16_t *posA, uint16_t *posB) {
-#ifndef VSG_OCT_NO_REGSORT  // A/B builds: the LDS form for every n
     if (n <= 64) {
       sort_partition_phase_regs(a, n);
       return;
     }
-#endif
-#ifndef VSG_OCT_SERIAL_SORT
     // More than 64 items (1200+ features per frame, photographs, 1280x720): the ranges the quicksort loop leaves behind are
     // disjoint and each is partitioned from its own data alone, so the ORDER in which introsort works them off does not
     // change the result -- all ranges of one recursion depth are partitioned at once, one range per wave: as many rounds as
@@ -1318,7 +1202,6 @@ struct BlockGroup {
       }
       return;
     }
-#endif
     if (tid >= 64) return;
     const int lane = tid;
     const uint64_t lt = (1ull << lane) - 1;
@@ -1378,19 +1261,14 @@ struct BlockGroup {
   }
 };
 
-#ifndef VSG_OCT_K
-#define VSG_OCT_K 8
-#endif
-constexpr int kOctRegPts = VSG_OCT_K;  // candidates per thread held in registers (x 256 threads = 2048 per level; 12 costs a wave of occupancy and loses)
+constexpr int kOctRegPts = 8;  // candidates per thread held in registers (x 256 threads = 2048 per level; 12 costs a wave of occupancy and loses)
 
-#ifndef VSG_OCT_NT
-#define VSG_OCT_NT 256
-#endif
-constexpr int kOctThreads = VSG_OCT_NT;  // threads per (frame, level) octree
-
-// 5 waves per SIMD = 5 octrees per CU (96 VGPRs, 10 dwords spilled off the hot paths): the kernel is latency-bound,
+constexpr int kOctThreads = 256;  // threads per (frame, level) octree
+// k_octree: 5 waves per SIMD = 5 octrees per CU (96 VGPRs, 10 dwords spilled off the hot paths): the kernel is latency-bound,
 // so residency is worth more than registers, and 96-register waves leave room for the blur waves that run beside it
 // (4 waves / 127 VGPRs: 0.167 ms per 512 frames and 256 k frames/s; 5: 0.160 ms and 260 k; 6: 255 k; 8: 0.185 ms)
+constexpr int kOctWaves = 5;
+
 // Candidates of a level whose cells wrote their survivors into fixed segments.  LDS holds the exclusive prefix of the
 // cell counts and the segment offsets; candidate p lives in the cell found by bisection of the prefix, at segment
 // offset + (p - prefix).
@@ -1456,10 +1334,7 @@ struct SegRegPts {
   }
 };
 
-#ifndef VSG_OCT_FEW
-#define VSG_OCT_FEW 8
-#endif
-constexpr int kOctFewFrames = VSG_OCT_FEW;  // calls of up to this many frames take the 4-waves-per-SIMD octree launch (k_octree_few; the fused launch is compiled for 4 waves anyway)
+constexpr int kOctFewFrames = 8;  // calls of up to this many frames take the 4-waves-per-SIMD octree launch (k_octree_few; the fused launch is compiled for 4 waves anyway)
 struct OctArgs {
   const FrameGeom *fg;
   const uint32_t *cand;
@@ -1580,51 +1455,21 @@ __device__ __forceinline__ void octree_block(const OctArgs &a, int level, int fr
                                          : octree::distribute<kMemU>(g, P, cand + coff, npts, node_of + coff, W, out);
   }
   if (threadIdx.x == 0) sel_count[frame * kMaxLevels + level] = n;
-#if VSG_OD_SPATIAL
-  // Experiment (OFF by default: profiles/r06_e_orient_desc_order_ab.txt): the PROCESSING order of the level's
-  // keypoints for k_orient_desc -- Morton order of their 32 x 32 px cells, so that the twelve keypoints of one of its workgroups
-  // are spatial neighbours -- as a permutation in the level's slice of the (by now idle) node_of scratch; the OUTPUT slot of a
-  // keypoint stays its position in the octree's list.  Rank by counting: n <= sel_cap keys, n^2 / 256 comparisons per thread.
-  {
-    __syncthreads();  // out[0..n) is written (same workgroup: the barrier orders it)
-    auto key_of = [&](int i) -> uint32_t {
-      const uint32_t c = out[i];
-      uint32_t x = VSG_CAND_X(c) >> 5, y = VSG_CAND_Y(c) >> 5, m = 0;
-#pragma unroll
-      for (int b = 0; b < 6; b++) m |= ((x >> b) & 1u) << (2 * b) | ((y >> b) & 1u) << (2 * b + 1);
-      return (m << 16) | (uint32_t)i;  // unique: ties by list position
-    };
-    uint16_t *ord = node_of + coff;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const uint32_t ki = key_of(i);
-      int r = 0;
-      for (int j = 0; j < n; j++) r += key_of(j) < ki;
-      ord[r] = (uint16_t)i;
-    }
-  }
-#endif
+  // (k_orient_desc in Morton order of the keypoints' cells: no faster, profiles/r06_e_orient_desc_order_ab.txt)
 }
 
-#ifndef VSG_OCT_WAVES
-#define VSG_OCT_WAVES 5
-#endif
 // Points per batch of the memory-form sweeps (octree::MemPtsT), per kernel: the stand-alone launch (1280x720 and wider: every
 // level 0 is memory-resident) and the few-frame launch of geometries too large for the fused one take 8; the launch that also
 // carries the blur keeps 1 -- their register
 // allocation is what the default content's register-form levels run on (C2 / 1024, rectangles: octree stage 0.2037 -> 0.2105 ms with
 // 4, unchanged with 1; C4 / 256: 0.318 -> 0.252 with 1, 0.205 with 8; profiles/r06_u_*)
-#ifndef VSG_OCT_MEM_BATCH
-#define VSG_OCT_MEM_BATCH 8
-#endif
-#ifndef VSG_OCT_MEM_BATCH_FUSED
-#define VSG_OCT_MEM_BATCH_FUSED 1
-#endif
+constexpr int kOctMemBatch = 8, kOctMemBatchFused = 1;
 
-__global__ __launch_bounds__(kOctThreads) __attribute__((amdgpu_waves_per_eu(VSG_OCT_WAVES, VSG_OCT_WAVES))) void k_octree(OctArgs a) {
+__global__ __launch_bounds__(kOctThreads) __attribute__((amdgpu_waves_per_eu(kOctWaves, kOctWaves))) void k_octree(OctArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t oct_lds[];
   __shared__ int wtot[2 * kMaxWaves];
   __shared__ int sort_stack[kSortStackInts];
-  octree_block<VSG_OCT_MEM_BATCH>(a, blockIdx.x, blockIdx.y, oct_lds, wtot, sort_stack);
+  octree_block<kOctMemBatch>(a, blockIdx.x, blockIdx.y, oct_lds, wtot, sort_stack);
 }
 // calls of a few frames: registers instead of residency
 template <int kMemU>
@@ -1707,12 +1552,7 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 // arithmetic (shifted tap words, clamp bit, two-offset row addresses) that is 92 VGPRs = 5 waves per SIMD, 0.216 ms per
 // 512 C2 frames against 0.220-0.226 with 14 rows ahead (104 VGPRs, 4 waves) and 0.253 for the round-4 arithmetic (in-run
 // A/B, profiles/r05_p_*)
-#ifndef VSG_BLUR_AHEAD
-#define VSG_BLUR_AHEAD 12
-#endif
-#ifndef VSG_BLUR_AHEAD_ALONE
-#define VSG_BLUR_AHEAD_ALONE 10
-#endif
+constexpr int kBlurAheadFused = 12, kBlurAheadAlone = 10;
 template <int kBlurAhead>
 __device__ __forceinline__ void blur_block(const uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur,
                                            const FrameGeom *__restrict__ fg, const Src0 &s0, BlockXY blk) {
@@ -1885,7 +1725,7 @@ __device__ __forceinline__ void blur_block(const uint8_t *__restrict__ pyr, uint
 
 __global__ __launch_bounds__(256) void k_blur(const uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur,
                                               const FrameGeom *__restrict__ fg, Src0 s0) {
-  blur_block<VSG_BLUR_AHEAD_ALONE>(pyr, blur, fg, s0, frame_major_block());
+  blur_block<kBlurAheadAlone>(pyr, blur, fg, s0, frame_major_block());
 }
 
 // Latency path of the blocking single-frame calls: the blur workgroups ride in the octree's launch (blocks
@@ -1893,7 +1733,7 @@ __global__ __launch_bounds__(256) void k_blur(const uint8_t *__restrict__ pyr, u
 // stream whose fork / join events cost the chain as much GPU idle time as the blur itself takes (measured: 5-7 us at
 // each of the two cross-stream waits against 12 us of blur).  Both need only the pyramid.  Throughput batches keep the
 // two kernels apart: there the blur is issue-bound work that wants its own occupancy.
-// (VSG_OB_WAVES, vsg_kernels.h: 4 waves per SIMD = 128 registers.  With the round-5 blur arithmetic the blur's waves are
+// (kOctBlurWaves, vsg_kernels.h: 4 waves per SIMD = 128 registers.  With the round-5 blur arithmetic the blur's waves are
 // bound by memory latency more than by issue slots, and 12 rows of loads in flight at 4 waves beat 7 rows at 5 waves and the
 // octree's 59 spilled registers: + 1.0-1.2 % on the 512-frame step, 3 waves - 2.5 %: profiles/r05_p_*)
 template <int kMemU>
@@ -1914,10 +1754,10 @@ __device__ __forceinline__ void octree_blur_body(const OctArgs &a, const uint8_t
   if (blk.x < nlevels)
     octree_block<kMemU>(a, blk.x, blk.y, oct_lds, wtot, sort_stack);
   else
-    blur_block<VSG_BLUR_AHEAD>(pyr, blur, a.fg, s0, BlockXY{blk.x - nlevels, blk.y});
+    blur_block<kBlurAheadFused>(pyr, blur, a.fg, s0, BlockXY{blk.x - nlevels, blk.y});
 }
 template <int kMemU>
-__global__ __launch_bounds__(kOctThreads) __attribute__((amdgpu_waves_per_eu(VSG_OB_WAVES, VSG_OB_WAVES))) void k_octree_blur(
+__global__ __launch_bounds__(kOctThreads) __attribute__((amdgpu_waves_per_eu(kOctBlurWaves, kOctBlurWaves))) void k_octree_blur(
     OctArgs a, const uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, Src0 s0, int nlevels, int nframes, int lead) {
   extern __shared__ __attribute__((aligned(16))) uint8_t oct_lds[];
   __shared__ int wtot[2 * kMaxWaves];
@@ -1925,7 +1765,7 @@ __global__ __launch_bounds__(kOctThreads) __attribute__((amdgpu_waves_per_eu(VSG
   octree_blur_body<kMemU>(a, pyr, blur, s0, nlevels, nframes, lead, oct_lds, wtot, sort_stack);
 }
 // (Rounds 3-5 had a second instantiation of this launch for calls of a few frames, compiled for 4 waves per SIMD; since round 5
-// k_octree_blur itself is compiled for VSG_OB_WAVES = 4 waves -- 125 registers, nothing in scratch -- the two were the same code
+// k_octree_blur itself is compiled for kOctBlurWaves = 4 waves -- 125 registers, nothing in scratch -- the two were the same code
 // object twice; one-frame calls take k_octree_blur.)
 
 // ------------------------------------------------------------------------------------------------
@@ -2000,10 +1840,7 @@ __constant__ int c_umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9
 // ds_read_u8 meets 4.6 distinct dwords on its busiest bank on average (the real pattern under random rotations, simulated);
 // at 80 bytes (20 dwords: eight row classes) 3.1 -- what 32 random addresses give.  The test reads are two thirds of the
 // LDS pipe's busy time in this kernel.  80 keeps the tile rows 16-byte aligned for the b128 commits.
-#ifndef VSG_OD_PITCH
-#define VSG_OD_PITCH 80
-#endif
-enum { kPatchR = 18, kPatchW = 2 * kPatchR + 1, kPatchP = VSG_OD_PITCH, kPatchRows = 40 };
+enum { kPatchR = 18, kPatchW = 2 * kPatchR + 1, kPatchP = 80, kPatchRows = 40 };
 static_assert(kPatchP % 16 == 0 && kPatchP >= 64 && kPatchP < 256, "tile rows are committed as aligned 16-byte stores");
 
 // IC_Angle lane layout: 16 rows x 4 (unaligned) qwords per load instruction (lane = 4 * row + column), 2 instructions
@@ -2050,23 +1887,18 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VSG_OD_G
-#define VSG_OD_G 3
-#endif
 // keypoints a wavefront works through one after the other: amortises the workgroup prologue (pattern + disc tables
 // into LDS, one barrier).  1: 0.343, 2: 0.296, 3 and 4: 0.291 ms per 512 C2 frames; workgroups of hundreds of keypoints (a
 // launch that fills the chip once) lose badly: 0.34-0.44 ms, the frames of the resident workgroups thrash the XCD's L2;
 // requesting the first keypoint's patches before the prologue's barrier: 0.293 -> 0.300 (profiles/r04_d_*, steps 4-5)
-constexpr int kOdKpPerWave = VSG_OD_G;
+constexpr int kOdKpPerWave = 3;
 
-#ifndef VSG_OD_SGPRS
-#define VSG_OD_SGPRS 72
-#endif
+constexpr int kOdSgprs = 72;  // SGPR cap of k_orient_desc
 // kSelf (latency path, no lapping area: RGB-D / stereo, vLappingArea = {0, 0}): the kernel derives what k_slots would have
 // handed it -- the level starts from the octree's per-level counts, slot = keypoint index -- in its own prologue, and the
 // 8 us k_slots launch leaves the one-frame chain (two dependent loads in front of a keypoint instead of a kernel).
 template <bool kMirror, bool kSelf>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(VSG_OD_SGPRS))) void k_orient_desc(const uint8_t *__restrict__ pyr, const uint8_t *__restrict__ blur,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(kOdSgprs))) void k_orient_desc(const uint8_t *__restrict__ pyr, const uint8_t *__restrict__ blur,
                                                      const FrameGeom *__restrict__ fg, Src0 s0,
                                                      const uint32_t *__restrict__ sel, const int *__restrict__ sel_count,
                                                      const int4 *__restrict__ slots, const FrameHeader *__restrict__ hdr,
@@ -2148,16 +1980,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(VSG_OD_SGPRS)))
       l = 0;
       while (g >= s_hdr[3 + l]) l++;  // wave-uniform (g < n = s_hdr[2 + kMaxLevels])
       l = __builtin_amdgcn_readfirstlane(l);
-#if VSG_OD_SPATIAL
-      // processing position g - level start -> the keypoint's position in the octree's list (the octree's epilogue wrote
-      // the permutation into node_of, which travels in the unused `slots` argument of this launch form)
-      const int i = ((const uint16_t *)slots)[(size_t)frame * fg->cand_frame + fg->lv[l].cand_off + (g - s_hdr[2 + l])];
-      c = sel[(size_t)frame * fg->sel_frame + fg->lv[l].sel_off + i];
-      slot = s_hdr[2 + l] + i;
-#else
       c = sel[(size_t)frame * fg->sel_frame + fg->lv[l].sel_off + (g - s_hdr[2 + l])];
       slot = g;
-#endif
     } else {
       int4 r = rec[0];
 #pragma unroll
@@ -2625,11 +2449,11 @@ void launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const
   // tile row = up to 3 alignment bytes + vw + 6 ring bytes, rounded up to dwords; score rows (vw + 2 used) have the
   // tile's pitch: a pixel's score sits a constant away from its tile byte (k_fast_cells phase 2)
   if (maxVw <= 40)
-    launch_fast_t<VSG_FAST_NT, 52, 52, 2 * (128 / VSG_FAST_NT)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    launch_fast_t<kFastThreads, 52, 52, 2 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
   else if (maxVw <= 56)
-    launch_fast_t<VSG_FAST_NT, 68, 68, 3 * (128 / VSG_FAST_NT)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    launch_fast_t<kFastThreads, 68, 68, 3 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
   else
-    launch_fast_t<VSG_FAST_NT, 84, 84, 4 * (128 / VSG_FAST_NT)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    launch_fast_t<kFastThreads, 84, 84, 4 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
 }
 // dynamic LDS of one octree workgroup (also what every blur workgroup of the fused launch is charged)
 size_t octree_lds_bytes(const FrameGeom &fg, int maxQuota, int maxCellsPerLevel) {
@@ -2679,12 +2503,12 @@ void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, c
     // frame of the default content -- 1-2 % LONGER, the same register-allocation effect as in the batch launch (profiles/r06_u_*)
     const dim3 grid(fg.nlevels + fg.total_blur_blocks, nframes + lead);
     if (few && 5 * work_lds > 160 * 1024) {
-      lds_limit_ensure(5, dev, (const void *)k_octree_blur<VSG_OCT_MEM_BATCH>, lds);
-      hipLaunchKernelGGL(k_octree_blur<VSG_OCT_MEM_BATCH>, grid, dim3(kOctThreads), lds, s, a, blur_pyr, blur_out, *blur_s0,
+      lds_limit_ensure(5, dev, (const void *)k_octree_blur<kOctMemBatch>, lds);
+      hipLaunchKernelGGL(k_octree_blur<kOctMemBatch>, grid, dim3(kOctThreads), lds, s, a, blur_pyr, blur_out, *blur_s0,
                          fg.nlevels, nframes, lead);
     } else {
-      lds_limit_ensure(2, dev, (const void *)k_octree_blur<VSG_OCT_MEM_BATCH_FUSED>, lds);
-      hipLaunchKernelGGL(k_octree_blur<VSG_OCT_MEM_BATCH_FUSED>, grid, dim3(kOctThreads), lds, s, a, blur_pyr, blur_out, *blur_s0,
+      lds_limit_ensure(2, dev, (const void *)k_octree_blur<kOctMemBatchFused>, lds);
+      hipLaunchKernelGGL(k_octree_blur<kOctMemBatchFused>, grid, dim3(kOctThreads), lds, s, a, blur_pyr, blur_out, *blur_s0,
                          fg.nlevels, nframes, lead);
     }
     return;
@@ -2696,13 +2520,13 @@ void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, c
   // chain); where the workspace caps a CU at four workgroups anyway (1280x720 / 2000: 33 KB) the 5-waves form measures 0.8 %
   // more frames/s (115.3-116.8 against 115.1-115.6 k, profiles/r05_p_*) and stays.
   if (few) {
-    lds_limit_ensure(6, dev, (const void *)k_octree_few<VSG_OCT_MEM_BATCH>, lds);
-    hipLaunchKernelGGL(k_octree_few<VSG_OCT_MEM_BATCH>, grid, block, lds, s, a);
+    lds_limit_ensure(6, dev, (const void *)k_octree_few<kOctMemBatch>, lds);
+    hipLaunchKernelGGL(k_octree_few<kOctMemBatch>, grid, block, lds, s, a);
     return;
   }
   if (5 * work_lds <= 160 * 1024) {
-    lds_limit_ensure(4, dev, (const void *)k_octree_few<VSG_OCT_MEM_BATCH_FUSED>, lds);
-    hipLaunchKernelGGL(k_octree_few<VSG_OCT_MEM_BATCH_FUSED>, grid, block, lds, s, a);
+    lds_limit_ensure(4, dev, (const void *)k_octree_few<kOctMemBatchFused>, lds);
+    hipLaunchKernelGGL(k_octree_few<kOctMemBatchFused>, grid, block, lds, s, a);
     return;
   }
   lds_limit_ensure(1, dev, (const void *)k_octree, lds);

@@ -94,10 +94,7 @@ __global__ void k_hamming_pairs(const uint8_t *a, const uint8_t *b, const int *i
 __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) {
   return min(max(a, b), max(min(a, b), c));  // folded to v_med3_u32
 }
-#ifndef VSG_MATCH_QW
-#define VSG_MATCH_QW 2
-#endif
-enum { kMatchQW = VSG_MATCH_QW, kBest2Rows = 128 * kMatchQW };  // query sets of 32 per wave; A rows per workgroup
+enum { kMatchQW = 2, kBest2Rows = 128 * kMatchQW };  // query sets of 32 per wave; A rows per workgroup
 
 // ---- the best / second-best scan on the matrix cores.  A Hamming distance matrix is a GEMM over +-1 vectors:
 // with s(x) = 2*bit - 1, sum_k s(a_k) * s(b_k) = 256 - 2 * dist.  The train rows are expanded with their bits
@@ -115,9 +112,6 @@ enum { kMatchQW = VSG_MATCH_QW, kBest2Rows = 128 * kMatchQW };  // query sets of
 // (2 * dist << 19 | index == dist << 20 | index) and the two lanes of a column merge at the end: tie handling follows the
 // packed-key rule above (an xor + popcount form of this scan measured 0.182 ms per 256 x 1006^2 pairs against 0.088 ms
 // for the i8 form: DESIGN 8, round 1).
-#ifndef VSG_MATCH_TR
-#define VSG_MATCH_TR 1
-#endif
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(256) void k_block_best2_mfma(const uint8_t *a_base,
                                                           size_t block_stride, const int *counts_a, const int *counts_b,
                                                           int count_stride, int fixed_na, int fixed_nb, int max_rows,
                                                           int *best, int *second, int *argbest) {
-  constexpr int TR = VSG_MATCH_TR;  // 32-row train tiles per iteration (independent MFMA chains, one barrier)
+  constexpr int TR = 1;  // 32-row train tiles per iteration (independent MFMA chains, one barrier)
   __shared__ i32x4 tiles[2][TR][8 * 32];  // double buffer of [tile][descriptor dword d = 2 * k-step + half][train row r]
   __shared__ uint32_t lut[256];           // byte -> its 8 bits as FP4 nibbles
   {
@@ -171,10 +165,7 @@ __global__ __launch_bounds__(256) void k_block_best2_mfma(const uint8_t *a_base,
   // round trip several thousand, so a one-iteration prefetch left every iteration waiting on memory.  With two query sets per
   // wave: groups of 4 / 6 / 8 / 10 tiles = 0.185 / 0.200 / 0.181 / 0.188 ms per 1024 x 1006^2 pairs (122 VGPRs at 8: still 4 waves
   // per SIMD; profiles/r06_f_*)
-#ifndef VSG_MATCH_PF
-#define VSG_MATCH_PF 8
-#endif
-  constexpr int kPf = VSG_MATCH_PF;
+  constexpr int kPf = 8;
   uint32_t wa[kPf], wn[kPf];
 #pragma unroll
   for (int j = 0; j < kPf; j++) wa[j] = fetch(32 * j), wn[j] = 0u;

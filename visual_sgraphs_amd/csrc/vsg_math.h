@@ -208,10 +208,7 @@ VSG_HD float fast_atan2_deg_sel(float y, float x) {
   return a;
 }
 
-#ifndef VSG_SINCOS_FMA
-#define VSG_SINCOS_FMA 1
-#endif
-typedef SinCosF<(VSG_SINCOS_FMA != 0)> SinCos;
+typedef SinCosF<true> SinCos;
 
 // a = cosf(angle*factorPI), b = sinf(angle*factorPI)   (ORBextractor.cc:102,107-108)
 VSG_HD void brief_rotation(float angle_deg, float *a, float *b) {
@@ -225,7 +222,7 @@ VSG_HD void brief_rotation(float angle_deg, float *a, float *b) {
 VSG_HD void brief_rotation_of_moments(float m01, float m10, float *angle_deg, float *a, float *b) {
   const float factorPI = 0x1.1df46ap-6f;
   const float ang_deg = fast_atan2_deg_sel(m01, m10);
-  sincos_pair<(VSG_SINCOS_FMA != 0)>(fmul(ang_deg, factorPI), a, b);
+  sincos_pair<true>(fmul(ang_deg, factorPI), a, b);
   *angle_deg = ang_deg;
 }
 

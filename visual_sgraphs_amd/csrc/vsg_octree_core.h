@@ -859,9 +859,6 @@ VSG_OCT_HD int distribute_pts(G &g, const Params &P, PT &pts, int npts, Work &W,
   bool finish = false;
   // histogram mode for the first hist_D passes (hist_* above); hist_D = 0: the label-based passes
   int hist_D = nL >= 1 && nL <= kFuseRoots ? hist_depth(W, nL) : 0, hist_pass = 0;
-#ifdef VSG_OCT_NO_FUSE
-  hist_D = 0;  // A/B builds (tools/build_variant.sh): the regular passes from the start
-#endif
   if (hist_D) hist_setup(g, W, cur, nL, pts, npts, hist_D);
   while (!finish) {  // (:617)
     const int prevSize = nL;
