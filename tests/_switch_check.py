@@ -27,6 +27,8 @@ def main():
         assert_same_output(ex(img), ref(img), f"single frame call {t}")
         checked += 1
     launches = ex.chain_graph_launches()
+    forms = ex.debug_launch_forms()
+    assert forms["latency_chain"] == 1 and forms["orient_mirror"] == 1 and forms["nframes"] == 1, forms
     # a throughput batch
     imgs = np.stack([synth.sequence_frame(W, H, 5, t % 35) for t in range(70)])
     outs = ex.extract_batch(imgs)
@@ -37,6 +39,14 @@ def main():
         ref(imgs[69])
         assert np.array_equal(ex.image_pyramid(l, frame=69), ref.pyramid_level(l)), l
         assert np.array_equal(ex.blurred_level(l, frame=69), ref.blurred_level(l)), l
+    forms = ex.debug_launch_forms()
+    assert forms["latency_chain"] == 0 and forms["orient_mirror"] == 0 and forms["nframes"] == 70, forms
+    # one more blocking one-frame call: under VSG_GRAPH a replay, which reports what its captured enqueue recorded
+    img = synth.sequence_frame(W, H, 3, 12)
+    assert_same_output(ex(img), ref(img), "single frame call after the batch")
+    assert ex.chain_graph_launches() == (launches + 1 if launches else 0)
+    forms = ex.debug_launch_forms()
+    assert forms["latency_chain"] == 1 and forms["orient_mirror"] == 1 and forms["nframes"] == 1, forms
     print("OK", checked, launches)
 
 

@@ -17,7 +17,9 @@ def lib():
     return orb.load_library()
 
 
-def test_header_symbols_are_exported(lib):
+def test_header_and_debug_hook_symbols_are_exported(lib):
+    """Every symbol of include/vsg_orb.h and, listed exactly, every hook of include/vsg_orb_debug.h (now with
+    vsg_debug_last_launch_forms) is exported, and orb.EXPORTS binds exactly those."""
     from visual_sgraphs_amd import orb
     header = (ROOT / "include" / "vsg_orb.h").read_text()
     declared = sorted(set(re.findall(r"\b(vsg_[a-z0-9_]+)\s*\(", header)))
@@ -27,11 +29,23 @@ def test_header_symbols_are_exported(lib):
     # the test / measurement hooks live in a header of their own, outside the boundary a maintainer binds (VERDICT r5 #8b)
     assert not [n for n in declared if n.startswith("vsg_debug_")], "debug hooks belong in include/vsg_orb_debug.h"
     dbg = sorted(set(re.findall(r"\b(vsg_debug_[a-z0-9_]+)\s*\(", (ROOT / "include" / "vsg_orb_debug.h").read_text())))
-    assert dbg == ["vsg_debug_call_profile", "vsg_debug_device_sort"]
+    assert dbg == ["vsg_debug_call_profile", "vsg_debug_device_sort", "vsg_debug_last_launch_forms"]
     for name in dbg:
         assert hasattr(lib, name), f"{name} declared in include/vsg_orb_debug.h but not exported"
     assert "vsg_orb_debug.h" not in (ROOT / "INTEGRATION.md").read_text()
     assert sorted(orb.EXPORTS) == sorted(declared + dbg)
+
+
+def test_launch_forms_record_matches_the_header():
+    """orb.debug_launch_forms reads vsg_launch_forms through ctypes: the same int fields in the same order, and the same
+    VSG_OCT_* values."""
+    from visual_sgraphs_amd import orb
+    text = (ROOT / "include" / "vsg_orb_debug.h").read_text()
+    body = re.search(r"typedef struct vsg_launch_forms \{(.*?)\} vsg_launch_forms;", text, re.S).group(1)
+    assert re.findall(r"^\s*int (\w+);", body, re.M) == list(orb.LAUNCH_FORM_FIELDS)
+    enum = dict((k, int(v)) for k, v in re.findall(r"(VSG_OCT_\w+) = (\d+)", text))
+    assert enum == {"VSG_" + n: getattr(orb, n) for n in ("OCT_BLUR_MEMBATCH", "OCT_BLUR_MEMBATCH_FUSED",
+                                                           "OCT_FEW_MEMBATCH", "OCT_FEW_MEMBATCH_FUSED", "OCT_STANDALONE")}
 
 
 def test_keypoint_record_is_cv_keypoint_layout():

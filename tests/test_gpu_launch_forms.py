@@ -1,0 +1,359 @@
+"""The extractor's batched launch forms, each compared with the CPU oracle and each proven reached by the launch-forms hook
+(vsg_debug_last_launch_forms, include/vsg_orb_debug.h).
+
+vsg_orb_submit_batch sends a blocking call of up to 8 frames down the latency chain; everything else -- larger blocking
+batches and every device-entry call -- takes the throughput chain, whose choices depend on the geometry, the batch size and
+the entry point: FAST cells per workgroup and tile class (launch_fast), the octree launch form, its histogram, label area and
+lead (launch_octree), the blur fused into the octree's launch or on its own stream, the pyramid tiling, k_slots for a lapping
+area, and segmented candidate lists.  Every frame of every batch here is compared with or_extract_batch_mt bit for bit, and
+every test asserts through the hook the form it exists for, so that a test cannot pass on another path after a gate moves.
+
+Batches repeat a few distinct frames (rectangles, value noise, a photograph, a low-contrast frame) so that the oracle's share
+stays small."""
+import math
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+from visual_sgraphs_amd import orb, synth
+
+pytestmark = pytest.mark.gpu
+
+SCALES = [1.1, 1.2, 1.25, 1.3, 1.5, 2.0, 2.5]  # the scale factors of tests/test_gpu_extract.py _fuzz_cases
+
+
+def _reference_configs():
+    import json
+    from pathlib import Path
+    cases = json.loads((Path(__file__).parent / "golden" / "reference_configs.json").read_text())["cases"]
+    return [tuple(c["params"][k] for k in ("w", "h", "nFeatures", "scaleFactor", "nLevels", "iniThFAST", "minThFAST"))
+            for c in cases]
+
+
+def _uniq(w, h, seed):
+    """Four distinct frames: rectangles, value noise, a photograph (the class rotates with the seed), low contrast."""
+    photo = synth.PHOTO_CLASSES[seed % len(synth.PHOTO_CLASSES)]
+    return np.stack([synth.sequence_frame(w, h, seed, 0), synth.content_frame("value_noise", w, h, seed, 1),
+                     synth.content_frame(photo, w, h, seed, 2), synth.frame(w, h, seed + 3, amplitude_div=8)])
+
+
+def _batch(uniq, B):
+    idx = np.arange(B) % len(uniq)
+    return np.ascontiguousarray(uniq[idx]), idx
+
+
+def _host(ex, frames, lap=(0, 0)):
+    """The blocking host entry (vsg_orb_extract_batch) as [B, 2] counts, [B, cap] records, [B, cap, 32] descriptors."""
+    B, H, W = frames.shape
+    cap = ex.capacity(H, W)
+    outs = ex.extract_batch(frames, lap)
+    counts = np.zeros((B, 2), np.int32)
+    kps = np.zeros((B, cap), orb.KP_DTYPE)
+    desc = np.zeros((B, cap, 32), np.uint8)
+    for f, (mono, k, d) in enumerate(outs):
+        counts[f] = len(k), mono
+        kps[f, :len(k)], desc[f, :len(k)] = k, d
+    return counts, kps, desc
+
+
+def _device(ex, frames, lap=(0, 0)):
+    """The device entry (vsg_orb_extract_batch_device) on a torch stream, read back as _host returns it."""
+    import torch
+    B, H, W = frames.shape
+    cap = ex.capacity(H, W)
+    dev = torch.device("cuda", 0)
+    d_gray = torch.from_numpy(np.ascontiguousarray(frames)).to(dev)
+    d_kps = torch.zeros((B, cap, 28), dtype=torch.uint8, device=dev)
+    d_desc = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+    d_counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    st = torch.cuda.Stream(device=dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(st):
+        ex.extract_batch_device(d_gray.data_ptr(), B, H * W, H, W, W, d_kps.data_ptr(), d_desc.data_ptr(),
+                                d_counts.data_ptr(), cap, lap, st.cuda_stream)
+    torch.cuda.synchronize(dev)
+    return d_counts.cpu().numpy(), d_kps.cpu().numpy(), d_desc.cpu().numpy()
+
+
+def _oracle(uniq, cfg, cap, lap=(0, 0)):
+    w, h, nf, sf, nl, ini, mn = cfg
+    return ol.extract_batch(uniq, nf, cap, sf, nl, ini, mn, lap)
+
+
+def _check(got, want, idx, what):
+    bad = ol.compare_batch(*got, want[0][idx], want[1][idx], want[2][idx])
+    assert bad == [], f"{what}: {len(bad)} of {len(idx)} frames differ from the oracle, first {bad[:8]}"
+
+
+def _fast_k(forms, B):
+    """launch_fast's cells-per-workgroup gate (vsg_kernels.hip launch_fast_t) for the hook's cus and total_cells."""
+    return 3 if forms["total_cells"] * B >= 3 * 4 * 16 * forms["cus"] else 1
+
+
+def _big_batch(forms):
+    """The smallest batch that takes 3 FAST cells per workgroup, plus 3 (plus 1 more if that is a multiple of 8): the XCD
+    block remap gets a tail."""
+    B = math.ceil(3 * 4 * 16 * forms["cus"] / forms["total_cells"]) + 3
+    return B + 1 if B % 8 == 0 else B
+
+
+def _run(cfg, B, entry, lap=(0, 0), seed=0, uniq=None):
+    """One batch of B frames through `entry` ("host" / "device"), every frame compared with the oracle.  Returns the
+    hook's record and the handle."""
+    w, h, nf, sf, nl, ini, mn = cfg
+    if uniq is None:
+        uniq = _uniq(w, h, seed)
+    frames, idx = _batch(uniq, B)
+    ex = orb.ORBextractor(nf, sf, nl, ini, mn, max_batch=B)
+    got = (_host if entry == "host" else _device)(ex, frames, lap)
+    forms = ex.debug_launch_forms()
+    assert forms["nframes"] == B and forms["latency_chain"] == 0 and forms["orient_mirror"] == 0, forms
+    _check(got, _oracle(uniq, cfg, ex.capacity(h, w), lap), idx, f"{cfg} B={B} {entry} lap={lap}")
+    return forms, ex
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# a. every reference configuration as a 12-frame blocking batch and as a device batch large enough for 3 FAST cells per
+# workgroup.  The fused-blur / octree form each configuration takes (launch_octree / the gate in vsg_orb.hip enqueue_range):
+# five workgroups of the octree workspace (vsg_kernels.hip octree_lds_bytes) must fit a CU's 160 KB for the fused launch.
+#   1241x376 / 2000: 32 372 B (x5 = 161 860 <= 163 840) -- the fused launch, NOT the two streams the gate comment in
+#                    vsg_orb.hip once predicted for it;
+#   752x480 / 2000 / 7 levels (NTU VIRAL): 33 604 B -- the only reference configuration with two streams (k_octree when the
+#                    batch has more than 8 frames).
+FUSED, TWO = "fused", "two-stream"
+EXPECT = {  # (w, h, nFeatures, nLevels, iniThFAST) -> blur form of both legs
+    (752, 480, 2000, 7, 20): TWO,
+}
+
+
+def _cfg_id(c):
+    return f"{c[0]}x{c[1]}_n{c[2]}_l{c[4]}_t{c[5]}"
+
+
+@pytest.mark.parametrize("cfg", _reference_configs(), ids=_cfg_id)
+def test_reference_configuration_batches(cfg):
+    w, h, nf, sf, nl, ini, mn = cfg
+    form = EXPECT.get((w, h, nf, nl, ini), FUSED)
+    seed = (w * 31 + h * 17 + nf + ini) % 1000
+    uniq = _uniq(w, h, seed)
+    # mid leg: 12 frames through the blocking host entry -- the throughput chain, with a 4-frame tail for the block remap
+    mid, _ = _run(cfg, 12, "host", uniq=uniq)
+    assert mid["fast_cells_per_wg"] == _fast_k(mid, 12), mid
+    assert mid["fast_tile_pitch"] in (52, 68, 84) and mid["cand_segmented"] == 1, mid
+    # big leg: the device entry with the smallest batch that takes 3 cells per FAST workgroup, plus 3
+    B = _big_batch(mid)
+    smallest = math.ceil(3 * 4 * 16 * mid["cus"] / mid["total_cells"])
+    assert B % 8 != 0 and B - smallest in (3, 4) and _fast_k(mid, smallest) == 3 and _fast_k(mid, smallest - 1) == 1
+    big, _ = _run(cfg, B, "device", uniq=uniq)
+    assert big["fast_cells_per_wg"] == 3 and big["fast_tile_pitch"] == mid["fast_tile_pitch"], big
+    for leg in (mid, big):
+        assert leg["fused_blur"] == (form == FUSED), (form, leg)
+        want = orb.OCT_BLUR_MEMBATCH_FUSED if form == FUSED else orb.OCT_STANDALONE
+        assert leg["octree_kernel"] == want, (form, leg)
+        assert leg["octree_lead"] == 0 and leg["self_slots"] == 1 and leg["pyramid_tiling"] in (0, 1), leg
+
+
+def test_the_lds_edge_geometries_take_the_forms_the_gate_gives():
+    """The two geometries at the fused launch's LDS edge, as the table above records them: KITTI's workspace lies 1 980 B
+    under five per CU, C4's (1280x720 / 2000) 12 380 B over -- one must be fused, the other two-stream."""
+    kitti, _ = _run((1241, 376, 2000, 1.2, 8, 20, 7), 12, "host")
+    assert kitti["fused_blur"] == 1 and kitti["octree_kernel"] == orb.OCT_BLUR_MEMBATCH_FUSED, kitti
+    assert kitti["octree_hist_big"] == 0 and kitti["octree_label_bytes"] > 0, kitti
+    c4, _ = _run((1280, 720, 2000, 1.2, 8, 20, 7), 12, "host")
+    assert c4["fused_blur"] == 0 and c4["octree_kernel"] == orb.OCT_STANDALONE, c4
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# b. lapping areas in batches: k_slots + k_orient_desc<false, false>
+def _lap_cases():
+    rng = np.random.default_rng(77)
+    c752 = (752, 480, 1200, 1.2, 8, 20, 7)
+    a = int(rng.integers(19, 700))
+    r1 = (a, int(rng.integers(a, 752)))                         # lap0 <= lap1
+    b = int(rng.integers(100, 752))
+    r2 = (b, int(rng.integers(19, b)))                          # lap0 > lap1: nothing overlaps
+    return [((512, 512, 1000, 1.2, 8, 20, 7), (0, 511)),         # TUM-VI stereo settings
+            ((848, 800, 1000, 1.2, 8, 15, 7), (0, 847)),         # RealSense T265 stereo settings
+            (c752, r1), (c752, r2),
+            ((512, 512, 1000, 1.2, 8, 20, 7), "on-keypoints")]
+
+
+def _keypoint_ends(uniq, cfg):
+    """A lapping area whose ends sit exactly on the x of octave-0 keypoints the oracle returns for the batch's first frame
+    (x >= lap0 && x <= lap1 is inclusive at both ends: vsg_kernels.hip slots_of_frame)."""
+    w, h, nf, sf, nl, ini, mn = cfg
+    _, k, _ = ol.OracleExtractor(nf, sf, nl, ini, mn)(uniq[0])
+    xs = np.unique(k["x"][k["octave"] == 0])
+    xs = xs[(xs == np.floor(xs)) & (xs >= 19)]
+    assert len(xs) >= 8
+    return int(xs[len(xs) // 4]), int(xs[(3 * len(xs)) // 4])
+
+
+@pytest.mark.parametrize("case", range(5), ids=["tumvi_0_511", "t265_0_847", "random", "random_reversed", "on_keypoints"])
+def test_lapping_area_batches(case):
+    cfg, lap = _lap_cases()[case]
+    w, h = cfg[0], cfg[1]
+    uniq = _uniq(w, h, 500 + case)
+    if lap == "on-keypoints":
+        lap = _keypoint_ends(uniq, cfg)
+        _, k, _ = ol.OracleExtractor(*cfg[2:])(uniq[0])
+        on0 = k["x"][k["octave"] == 0]
+        assert (on0 == lap[0]).any() and (on0 == lap[1]).any()
+    slots = 0 if lap[1] >= 19 and lap[0] <= lap[1] else 1
+    mid, _ = _run(cfg, 12, "host", lap, uniq=uniq)
+    assert mid["self_slots"] == slots, (lap, mid)
+    B = _big_batch(mid)
+    big, _ = _run(cfg, B, "device", lap, uniq=uniq)
+    assert big["self_slots"] == slots and big["fast_cells_per_wg"] == 3, (lap, big)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# c. seeded random batched geometries
+def _batch_cases(n, seed):
+    rng = np.random.default_rng(seed)
+    cases = []
+    while len(cases) < n:
+        w, h = int(rng.integers(150, 1921)), int(rng.integers(120, 1081))
+        nl = int(rng.integers(1, 9))
+        sc = SCALES[len(cases) % len(SCALES)]  # every scale factor, 2.5 included (per-level k_resize)
+        nf = int(rng.integers(50, 3000))
+        ini = int(rng.integers(8, 60))
+        mn = int(rng.integers(2, ini + 1))
+        div = int(rng.choice([1, 1, 1, 2, 4, 8]))
+        top = sc ** (nl - 1)
+        if nl == 1 and nf > 2400:
+            continue
+        if w / top < 80 or h / top < 80 or w / h > 3.5 or w < 0.6 * h:
+            continue
+        B = int(rng.integers(9, 41))
+        cases.append((w, h, nf, sc, nl, ini, mn, div, B, "host" if len(cases) % 2 == 0 else "device",
+                      int(rng.integers(0, 1 << 20))))
+    return cases
+
+
+@pytest.mark.parametrize("case", _batch_cases(24, 4242),
+                         ids=lambda c: f"{c[0]}x{c[1]}_n{c[2]}_s{c[3]}_l{c[4]}_B{c[8]}_{c[9]}")
+def test_fuzz_random_batched_geometries(case):
+    w, h, nf, sc, nl, ini, mn, div, B, entry, seed = case
+    photo = synth.PHOTO_CLASSES[seed % len(synth.PHOTO_CLASSES)]
+    uniq = np.stack([synth.sequence_frame(w, h, seed, 0), synth.content_frame("value_noise", w, h, seed, 1),
+                     synth.content_frame(photo, w, h, seed, 2), synth.frame(w, h, seed + 3, amplitude_div=div)])
+    forms, _ = _run((w, h, nf, sc, nl, ini, mn), B, entry, uniq=uniq)
+    assert forms["fast_cells_per_wg"] == _fast_k(forms, B), forms
+    if sc > 2 and nl > 1:
+        assert forms["pyramid_tiling"] == -1, forms  # no fused tiling for scale factors above 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# d. targeted forms
+def test_fused_launch_with_the_octree_lead_away_from_c2():
+    """k_octree_blur's octree workgroups run 64 rows ahead of the blur's in launches of 256 frames or more."""
+    forms, _ = _run((512, 512, 1000, 1.2, 8, 20, 7), 256, "device", uniq=np.concatenate(
+        [_uniq(512, 512, 900 + s) for s in range(8)]))
+    assert forms["fused_blur"] == 1 and forms["octree_kernel"] == orb.OCT_BLUR_MEMBATCH_FUSED, forms
+    assert forms["octree_lead"] == 64, forms
+
+
+def test_standalone_octree_on_a_batch_of_photographs():
+    """1280x720 / 2000: the workspace keeps five workgroups off a CU, so a batch of more than 8 frames takes k_octree (5
+    waves, batched memory-form sweeps) on two streams; photographs give it more than 2048 level-0 candidates per frame, more
+    than the octree holds in registers."""
+    cfg = (1280, 720, 2000, 1.2, 8, 20, 7)
+    uniq = np.stack([synth.content_frame(k, 1280, 720, 61, t) for t, k in enumerate(synth.PHOTO_CLASSES)])
+    forms, ex = _run(cfg, 12, "host", uniq=uniq)
+    assert forms["fused_blur"] == 0 and forms["octree_kernel"] == orb.OCT_STANDALONE, forms
+    # the small histogram, and no LDS label area: the node arrays fill the workgroup's share (launch_octree)
+    assert forms["octree_hist_big"] == 0 and forms["octree_label_bytes"] == 0, forms
+    assert all(len(ex.candidates(0, frame=t)[0]) > 2048 for t in range(len(uniq)))
+
+
+def test_serialised_many_frame_batch_takes_the_few_frames_octree_with_fused_sweeps():
+    """set_serialize(1) keeps the blur out of the octree's launch; a 64-frame C2 batch then takes
+    k_octree_few<kOctMemBatchFused> (five workspaces fit a CU)."""
+    cfg = (640, 480, 1000, 1.2, 8, 20, 7)
+    uniq = _uniq(640, 480, 31)
+    frames, idx = _batch(uniq, 64)
+    ex = orb.ORBextractor(1000, 1.2, 8, 20, 7, max_batch=64)
+    ex.set_serialize(1)
+    got = _host(ex, frames)
+    forms = ex.debug_launch_forms()
+    assert forms["fused_blur"] == 0 and forms["octree_kernel"] == orb.OCT_FEW_MEMBATCH_FUSED, forms
+    _check(got, _oracle(uniq, cfg, ex.capacity(480, 640)), idx, "serialised C2 x 64")
+
+
+def test_entry_point_split_at_the_lds_edge():
+    """1280x720 / 2000, 4 frames: the blocking host entry takes the latency chain with the blur fused into
+    k_octree_blur<kOctMemBatch>; the device entry keeps two streams and takes k_octree_few<kOctMemBatch>.  Both give the
+    oracle's output."""
+    cfg = (1280, 720, 2000, 1.2, 8, 20, 7)
+    uniq = _uniq(1280, 720, 71)
+    ex = orb.ORBextractor(2000, 1.2, 8, 20, 7, max_batch=4)
+    host = _host(ex, uniq)
+    fh = ex.debug_launch_forms()
+    assert fh["latency_chain"] == 1 and fh["orient_mirror"] == 1, fh
+    assert fh["fused_blur"] == 1 and fh["octree_kernel"] == orb.OCT_BLUR_MEMBATCH, fh
+    dev = _device(ex, uniq)
+    fd = ex.debug_launch_forms()
+    assert fd["latency_chain"] == 0 and fd["orient_mirror"] == 0, fd
+    assert fd["fused_blur"] == 0 and fd["octree_kernel"] == orb.OCT_FEW_MEMBATCH, fd
+    idx = np.arange(4)
+    assert ol.compare_batch(*host, *dev) == []
+    _check(host, _oracle(uniq, cfg, ex.capacity(720, 1280)), idx, "host entry")
+    _check(dev, _oracle(uniq, cfg, ex.capacity(720, 1280)), idx, "device entry")
+
+
+def test_blocking_entry_boundary_between_8_and_9_frames():
+    """752x480 / 1200: 8 frames through the blocking host entry are the latency chain, 9 the throughput chain; the frames
+    both batches share come out identical, and as the oracle's."""
+    cfg = (752, 480, 1200, 1.2, 8, 20, 7)
+    uniq = _uniq(752, 480, 81)
+    frames, idx = _batch(uniq, 9)
+    ex = orb.ORBextractor(1200, 1.2, 8, 20, 7, max_batch=9)
+    g8 = _host(ex, frames[:8])
+    f8 = ex.debug_launch_forms()
+    g9 = _host(ex, frames)
+    f9 = ex.debug_launch_forms()
+    assert f8["latency_chain"] == 1 and f9["latency_chain"] == 0, (f8, f9)
+    assert ol.compare_batch(g8[0], g8[1], g8[2], g9[0][:8], g9[1][:8], g9[2][:8]) == []
+    _check(g9, _oracle(uniq, cfg, ex.capacity(480, 752)), idx, "9-frame batch")
+
+
+def test_segmented_candidate_lists_in_a_batch():
+    """2400x2336 / 3 levels: 4 355 cells on level 0, more than kOctMaxCells -- k_fast_cells appends one list per level
+    (cand_segmented 0) -- in a 9-frame throughput batch; plus the level-0 candidate multiset of the last frame."""
+    cfg = (2400, 2336, 1500, 1.2, 3, 20, 7)
+    uniq = np.stack([synth.frame(2400, 2336, 4321), synth.content_frame("photo_china", 2400, 2336, 5, 1),
+                     synth.frame(2400, 2336, 4322, amplitude_div=8)])
+    forms, ex = _run(cfg, 9, "host", uniq=uniq)
+    assert forms["cand_segmented"] == 0, forms
+    ref = ol.OracleExtractor(1500, 1.2, 3, 20, 7)
+    ref(uniq[8 % len(uniq)])
+    gx, gy, gr = ex.candidates(0, frame=8)
+    rx, ry, rr = ref.candidates(0)
+    assert sorted(zip(gx.tolist(), gy.tolist(), gr.tolist())) == sorted(zip(rx.tolist(), ry.tolist(), rr.tolist()))
+
+
+@pytest.mark.parametrize("which", [-1, 0, 1])
+@pytest.mark.parametrize("cfg", [(512, 512, 1000, 1.2, 8, 20, 7), (1241, 376, 2000, 1.2, 8, 20, 7)], ids=_cfg_id)
+def test_pyramid_tilings_on_large_batches(cfg, which):
+    """ComputePyramid's throughput tilings forced (and automatic) on batches of the big-leg size: level bytes of three
+    frames and every frame's output as the oracle's."""
+    w, h, nf, sf, nl, ini, mn = cfg
+    uniq = _uniq(w, h, 91)
+    probe = orb.ORBextractor(nf, sf, nl, ini, mn, max_batch=1)
+    probe(uniq[0])
+    B = _big_batch(probe.debug_launch_forms())
+    frames, idx = _batch(uniq, B)
+    ex = orb.ORBextractor(nf, sf, nl, ini, mn, max_batch=B)
+    ex.set_pyramid_tiling(which)
+    got = _host(ex, frames)
+    forms = ex.debug_launch_forms()
+    assert forms["pyramid_tiling"] == which if which >= 0 else forms["pyramid_tiling"] in (0, 1), forms
+    assert forms["latency_chain"] == 0 and forms["fast_cells_per_wg"] == 3, forms
+    _check(got, _oracle(uniq, cfg, ex.capacity(h, w)), idx, f"tiling {which}")
+    ref = ol.OracleExtractor(nf, sf, nl, ini, mn)
+    for t in (0, B // 2, B - 1):
+        ref(frames[t])
+        for l in range(nl):
+            assert np.array_equal(ex.image_pyramid(l, frame=t), ref.pyramid_level(l)), (which, t, l)

@@ -6,6 +6,8 @@ case and exits 1.
     python tools/fuzz_gpu.py --cases 300 --seed 1
 """
 import argparse
+import collections
+import json
 import sys
 from pathlib import Path
 
@@ -23,9 +25,9 @@ def same(got, want):
     return got[0] == want[0] and got[1].tobytes() == want[1].tobytes() and np.array_equal(got[2], want[2])
 
 
-def geometry(rng):
+def geometry(rng, wmax=1000, hmax=760):
     while True:
-        w, h = int(rng.integers(150, 1000)), int(rng.integers(120, 760))
+        w, h = int(rng.integers(150, wmax)), int(rng.integers(120, hmax))
         nl = int(rng.integers(1, 9))
         sc = float(rng.choice([1.1, 1.2, 1.25, 1.3, 1.5, 2.0, 2.5]))
         nf = int(rng.integers(50, 2400))
@@ -50,6 +52,60 @@ def case_batch(rng):
     ref = ol.OracleExtractor(nf, sc, nl, ini, mn)
     outs = ex.extract_batch(imgs, lap)
     return all(same(outs[i], ref(imgs[i], lap)) for i in range(B)), ("batch", w, h, nf, sc, nl, ini, mn, B, lap, kinds)
+
+
+# (fused_blur, octree_kernel, fast_cells_per_wg, pyramid_tiling, self_slots) of every batch_big case (the launch-forms hook)
+FORMS_SEEN = collections.Counter()
+
+
+def _extract_device(ex, frames, lap):
+    import torch
+    B, H, W = frames.shape
+    cap = ex.capacity(H, W)
+    dev = torch.device("cuda", 0)
+    d_gray = torch.from_numpy(frames).to(dev)
+    d_kps = torch.zeros((B, cap, 28), dtype=torch.uint8, device=dev)
+    d_desc = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+    d_counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    st = torch.cuda.Stream(device=dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(st):
+        ex.extract_batch_device(d_gray.data_ptr(), B, H * W, H, W, W, d_kps.data_ptr(), d_desc.data_ptr(),
+                                d_counts.data_ptr(), cap, lap, st.cuda_stream)
+    torch.cuda.synchronize(dev)
+    return d_counts.cpu().numpy(), d_kps.cpu().numpy(), d_desc.cpu().numpy()
+
+
+def case_batch_big(rng):
+    """The throughput chain: 9..64 frames through the blocking host entry, or 1..64 through the device entry (which never
+    takes the latency chain; its batches of up to 8 frames reach the few-frame octree forms), up to 1920x1080 with every scale
+    factor, a random content class per distinct frame (photographs included), a random lapping area.  The oracle runs on the
+    distinct frames only (on ORACLE_THREADS host threads)."""
+    w, h, nf, sc, nl, ini, mn = geometry(rng, 1921, 1081)
+    host = rng.random() < 0.5
+    B = int(rng.integers(9, 65)) if host else int(rng.integers(1, 65))
+    lap = (int(rng.integers(-10, w)), int(rng.integers(-10, w + 50)))
+    nuniq = int(rng.integers(1, 4))
+    kinds = [str(rng.choice(("rectangles",) + tuple(synth.CONTENT_CLASSES))) for _ in range(nuniq)]
+    uniq = np.stack([synth.content_frame(k, w, h, int(rng.integers(0, 1 << 20)), int(rng.integers(0, 40))) for k in kinds])
+    idx = rng.integers(0, nuniq, B)
+    frames = np.ascontiguousarray(uniq[idx])
+    ex = orb.ORBextractor(nf, sc, nl, ini, mn, max_batch=B)
+    cap = ex.capacity(h, w)
+    if host:
+        counts = np.zeros((B, 2), np.int32)
+        kps = np.zeros((B, cap), orb.KP_DTYPE)
+        desc = np.zeros((B, cap, 32), np.uint8)
+        for f, (mono, k, d) in enumerate(ex.extract_batch(frames, lap)):
+            counts[f] = len(k), mono
+            kps[f, :len(k)], desc[f, :len(k)] = k, d
+    else:
+        counts, kps, desc = _extract_device(ex, frames, lap)
+    f = ex.debug_launch_forms()
+    FORMS_SEEN[(f["fused_blur"], f["octree_kernel"], f["fast_cells_per_wg"], f["pyramid_tiling"], f["self_slots"])] += 1
+    rc, rk, rd = ol.extract_batch(uniq, nf, cap, sc, nl, ini, mn, lap, nthreads=ORACLE_THREADS)
+    ok = f["latency_chain"] == 0 and f["nframes"] == B and ol.compare_batch(counts, kps, desc, rc[idx], rk[idx], rd[idx]) == []
+    return ok, ("batch_big", w, h, nf, sc, nl, ini, mn, B, "host" if host else "device", lap, kinds, idx.tolist(), f)
 
 
 def case_colour(rng):
@@ -469,7 +525,9 @@ def _finish(ex, ref, ticket, buf, lap, pinned):
     return bool(ok)
 
 
-CASES = {"undistort": case_undistort, "resident": case_resident, "async": case_async, "window": case_window, "batch": case_batch, "colour": case_colour, "best2": case_best2, "stereo": case_stereo, "bow": case_bow, "bow_search": case_bow_search}
+CASES = {"undistort": case_undistort, "resident": case_resident, "async": case_async, "window": case_window, "batch": case_batch, "colour": case_colour, "best2": case_best2, "stereo": case_stereo, "bow": case_bow, "bow_search": case_bow_search,
+         "batch_big": case_batch_big}
+ORACLE_THREADS = None  # --oracle-threads (default: every host thread this process may use)
 
 
 def run_child(args, argv):
@@ -518,12 +576,14 @@ def main():
                          "(vsg_orb_set_direct_registered); default = the library's default route, which stages them")
     ap.add_argument("--stop-at", type=int, default=-1, help="run cases up to this index only (the random stream stays the same)")
     ap.add_argument("--runs", type=int, default=1, help="repeat the run this many times, each in a fresh child process")
+    ap.add_argument("--oracle-threads", type=int, default=0, help="host threads of the batch_big oracle (0: all)")
     ap.add_argument("--child", action="store_true", help="(internal) this process runs the cases itself")
     args = ap.parse_args()
     if not args.child:
         sys.exit(run_child(args, sys.argv[1:]))
-    global TRACE, ALLOC, ALLOC_ONLY, DIRECT_REGISTERED
+    global TRACE, ALLOC, ALLOC_ONLY, DIRECT_REGISTERED, ORACLE_THREADS
     TRACE = args.trace
+    ORACLE_THREADS = args.oracle_threads or None
     ALLOC = not args.registered_only
     ALLOC_ONLY = args.alloc_only
     DIRECT_REGISTERED = args.direct_registered
@@ -545,7 +605,10 @@ def main():
         if not ok:
             print("MISMATCH", desc)
             sys.exit(1)
-    print("fuzz ok:", counts)
+    # batch_big: how often each launch-form tuple (fused_blur, octree_kernel, fast_cells_per_wg, pyramid_tiling, self_slots)
+    # was taken, on the same (last) line as the counts
+    forms = " forms " + json.dumps({",".join(map(str, k)): v for k, v in sorted(FORMS_SEEN.items())}) if FORMS_SEEN else ""
+    print("fuzz ok:", counts, f"seed {args.seed}" + forms)
 
 
 if __name__ == "__main__":

@@ -28,13 +28,21 @@ void launch_resize(hipStream_t s, uint8_t *pyr, const FrameGeom *d_fg, const Sho
                    const FrameGeom &fg, int level, int nframes);
 void launch_pyramid(hipStream_t s, uint8_t *pyr, const FrameGeom *d_fg, const Short4 *d_tile_tab, const Src0 &s0,
                     const PyrTile *d_tiles, int ntiles, int ldsA, int ldsB, int tabMax, int nframes, int *cand_count);
-void launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs, const Src0 &s0,
-                 uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh, int maxVw, int maxArea,
-                 int nframes, int cus);
-void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, const int *cand_count,
-                   const CellDesc *d_cells, const int *cell_count, uint32_t *cand2, uint16_t *node_of, uint32_t *sel,
-                   int *sel_count, const FrameGeom &fg, int maxQuota, int maxCellsPerLevel, int nframes,
-                   const uint8_t *blur_pyr = nullptr, uint8_t *blur_out = nullptr, const Src0 *blur_s0 = nullptr);
+// what launch_fast / launch_octree chose (the hook vsg_debug_last_launch_forms reports it)
+struct FastForm {
+  int cells_per_wg = 0, tile_pitch = 0;
+};
+struct OctreeForm {
+  int kernel = 0;  // VSG_OCT_* (include/vsg_orb_debug.h)
+  int hist_big = 0, label_bytes = 0, lead = 0;
+};
+FastForm launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs, const Src0 &s0,
+                     uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh, int maxVw, int maxArea,
+                     int nframes, int cus);
+OctreeForm launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, const int *cand_count,
+                         const CellDesc *d_cells, const int *cell_count, uint32_t *cand2, uint16_t *node_of, uint32_t *sel,
+                         int *sel_count, const FrameGeom &fg, int maxQuota, int maxCellsPerLevel, int nframes,
+                         const uint8_t *blur_pyr = nullptr, uint8_t *blur_out = nullptr, const Src0 *blur_s0 = nullptr);
 size_t octree_lds_bytes(const FrameGeom &fg, int maxQuota, int maxCellsPerLevel);
 // waves per SIMD the fused octree + blur launch is compiled for = its 256-thread workgroups per CU (the LDS they need decides
 // whether a geometry takes that launch: vsg_orb.hip)

@@ -20,6 +20,7 @@
 #include "vsg_math.h"
 #include "vsg_octree_core.h"
 #include "vsg_kernels.h"
+#include "../../include/vsg_orb_debug.h"
 
 namespace vsg {
 
@@ -2420,7 +2421,7 @@ void launch_pyramid(hipStream_t s, uint8_t *pyr, const FrameGeom *d_fg, const Sh
                      d_tile_tab, s0, d_tiles, a16, ab16, cand_count);
 }
 template <int NT, int TP, int SP, int PRE>
-static void launch_fast_t(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs,
+static FastForm launch_fast_t(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs,
                           const Src0 &s0, uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh,
                           int maxArea, int nframes, int cus) {
   // Cells per workgroup: the first cell of a workgroup waits for its tile, the others find theirs fetched -- 2, 3 and 4
@@ -2442,18 +2443,21 @@ static void launch_fast_t(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_
   hipLaunchKernelGGL((k_fast_cells<NT, TP, SP, PRE>), grid, block, lds, s, pyr, d_fg, d_recs, s0, cand, cand_count,
                      cell_count, tile_bytes, score_bytes, maxArea, cells_per_wg, fg.pyr_frame_bytes, fg.total_cells,
                      fg.cand_frame, th_pack);
+  FastForm f;
+  f.cells_per_wg = cells_per_wg, f.tile_pitch = TP;
+  return f;
 }
-void launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs, const Src0 &s0,
-                 uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh, int maxVw, int maxArea,
-                 int nframes, int cus) {
+FastForm launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs, const Src0 &s0,
+                     uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh, int maxVw, int maxArea,
+                     int nframes, int cus) {
   // tile row = up to 3 alignment bytes + vw + 6 ring bytes, rounded up to dwords; score rows (vw + 2 used) have the
   // tile's pitch: a pixel's score sits a constant away from its tile byte (k_fast_cells phase 2)
   if (maxVw <= 40)
-    launch_fast_t<kFastThreads, 52, 52, 2 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    return launch_fast_t<kFastThreads, 52, 52, 2 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
   else if (maxVw <= 56)
-    launch_fast_t<kFastThreads, 68, 68, 3 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    return launch_fast_t<kFastThreads, 68, 68, 3 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
   else
-    launch_fast_t<kFastThreads, 84, 84, 4 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    return launch_fast_t<kFastThreads, 84, 84, 4 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
 }
 // dynamic LDS of one octree workgroup (also what every blur workgroup of the fused launch is charged)
 size_t octree_lds_bytes(const FrameGeom &fg, int maxQuota, int maxCellsPerLevel) {
@@ -2464,10 +2468,10 @@ size_t octree_lds_bytes(const FrameGeom &fg, int maxQuota, int maxCellsPerLevel)
   return prefix_off + (fg.cand_segmented ? (2 * (size_t)maxCellsPerLevel + 1) * 4 : 0);
 }
 
-void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, const int *cand_count,
-                   const CellDesc *d_cells, const int *cell_count, uint32_t *cand2, uint16_t *node_of, uint32_t *sel,
-                   int *sel_count, const FrameGeom &fg, int maxQuota, int maxCellsPerLevel, int nframes,
-                   const uint8_t *blur_pyr, uint8_t *blur_out, const Src0 *blur_s0) {
+OctreeForm launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, const int *cand_count,
+                         const CellDesc *d_cells, const int *cell_count, uint32_t *cand2, uint16_t *node_of, uint32_t *sel,
+                         int *sel_count, const FrameGeom &fg, int maxQuota, int maxCellsPerLevel, int nframes,
+                         const uint8_t *blur_pyr, uint8_t *blur_out, const Src0 *blur_s0) {
   const int cap = octree::node_capacity(maxQuota);
   const size_t prefix_bytes = fg.cand_segmented ? (2 * (size_t)maxCellsPerLevel + 1) * 4 : 0;
   // Node labels of levels whose candidates overflow the registers (octree_block), and the workspace class: every octree
@@ -2491,11 +2495,14 @@ void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, c
   const OctArgs a = {d_fg, cand, cand_count, d_cells, cell_count, cand2, node_of, sel, sel_count, cap, prefix_off,
                      (int)lab_off, (int)(lab_bytes / 2), hist_big ? 1 : 0};
   const bool few = nframes <= kOctFewFrames;  // a call waits for ONE workgroup per level
+  OctreeForm form;
+  form.hist_big = hist_big ? 1 : 0, form.label_bytes = (int)lab_bytes;
   if (blur_out) {  // the blur of the same frames as extra workgroups of this launch (latency path)
     // octree workgroups `lead` frames ahead of the blur's (see the kernel); only for launches long enough to have a tail
     // (64 rows, a multiple of 8 = whole XCD rounds: 317.5 -> 320.5 k frames/s at 512 C2 frames; 32 and 128 measured the same +-0.3 %)
     constexpr int kLead = 64;
     const int lead = nframes >= 4 * kLead ? kLead : 0;
+    form.lead = lead;
     // Few-frame calls of the geometries whose levels are memory-resident as a rule (1280x720 / 2000: the workspace size that also
     // keeps their BATCHES out of this launch) take the instantiation with batched memory-form sweeps: one 1280x720 frame per
     // call 0.180 -> 0.173 ms, the building photograph 0.362 -> 0.302.  Everything else keeps the other one: with batched sweeps
@@ -2506,12 +2513,14 @@ void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, c
       lds_limit_ensure(5, dev, (const void *)k_octree_blur<kOctMemBatch>, lds);
       hipLaunchKernelGGL(k_octree_blur<kOctMemBatch>, grid, dim3(kOctThreads), lds, s, a, blur_pyr, blur_out, *blur_s0,
                          fg.nlevels, nframes, lead);
+      form.kernel = VSG_OCT_BLUR_MEMBATCH;
     } else {
       lds_limit_ensure(2, dev, (const void *)k_octree_blur<kOctMemBatchFused>, lds);
       hipLaunchKernelGGL(k_octree_blur<kOctMemBatchFused>, grid, dim3(kOctThreads), lds, s, a, blur_pyr, blur_out, *blur_s0,
                          fg.nlevels, nframes, lead);
+      form.kernel = VSG_OCT_BLUR_MEMBATCH_FUSED;
     }
-    return;
+    return form;
   }
   dim3 grid(fg.nlevels, nframes), block(kOctThreads);
   // The 4-waves-per-SIMD instantiation (126 VGPRs, no spills, no scratch) for calls of a few frames AND for every geometry
@@ -2522,15 +2531,19 @@ void launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, c
   if (few) {
     lds_limit_ensure(6, dev, (const void *)k_octree_few<kOctMemBatch>, lds);
     hipLaunchKernelGGL(k_octree_few<kOctMemBatch>, grid, block, lds, s, a);
-    return;
+    form.kernel = VSG_OCT_FEW_MEMBATCH;
+    return form;
   }
   if (5 * work_lds <= 160 * 1024) {
     lds_limit_ensure(4, dev, (const void *)k_octree_few<kOctMemBatchFused>, lds);
     hipLaunchKernelGGL(k_octree_few<kOctMemBatchFused>, grid, block, lds, s, a);
-    return;
+    form.kernel = VSG_OCT_FEW_MEMBATCH_FUSED;
+    return form;
   }
   lds_limit_ensure(1, dev, (const void *)k_octree, lds);
   hipLaunchKernelGGL(k_octree, grid, block, lds, s, a);
+  form.kernel = VSG_OCT_STANDALONE;
+  return form;
 }
 void launch_debug_sort(hipStream_t s, uint64_t *d_items, int n) {
   hipLaunchKernelGGL(k_debug_sort, dim3(1), dim3(256), (size_t)n * 16 + 2 * (n + 2) * 2 + 32, s, d_items, n);

@@ -159,6 +159,7 @@ struct ChainGraph {
   hipGraphExec_t exec = nullptr;
   int seen = 0;  // eager runs with this key so far: the graph is captured on the second call
   long stamp = 0;
+  vsg_launch_forms forms = {};  // what the captured enqueue chose (a replay reports it)
 };
 enum { kChainGraphs = 8 };
 
@@ -181,6 +182,8 @@ struct vsg_orb {
   int gray_coeffs[3] = {4899, 9617, 1868};  // [OCV] 4.2 R2Y, G2Y, B2Y
   int gray_shift = 14;                        // yuv_shift
   int last_frames = 0;
+  vsg_launch_forms forms = {};  // launch forms of the last enqueue (vsg_debug_last_launch_forms)
+  bool have_forms = false;
   // device
   FrameGeom *d_fg = nullptr;
   Short4 *d_tab = nullptr;
@@ -475,6 +478,10 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   int *flags = h->d_flags + F * fg.out_cap;
   int4 *slots = h->d_slots + F * fg.out_cap;
   FrameHeader *hdr = h->d_hdr + F;
+  vsg_launch_forms &rec = h->forms;
+  rec = vsg_launch_forms();
+  rec.cus = h->cus, rec.total_cells = fg.total_cells, rec.nframes = nf, rec.cand_segmented = fg.cand_segmented ? 1 : 0;
+  h->have_forms = true;
   Range r_all("vsg_orb: enqueue stage chain");
   if (tm) HIP_TRY(hipEventRecord(h->ev[0], s));
   // tiling: the coarser one when it still gives the chip enough workgroups and leaves three of them per CU; without a
@@ -495,6 +502,7 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
     else if (P0.ok && P0.lds_bytes() <= kPyrLdsLimit)
       ti = 0;
   }
+  rec.pyramid_tiling = ti;
   range_push("ComputePyramid");
   if (ti < 0) {
     launch_zero(s, cand_count, nf * kMaxLevels);  // the fused kernel clears the candidate counters itself
@@ -511,8 +519,9 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   // shares the CUs, while the octree leaves most issue slots free.  Measured on MI355X (C2, one batch of 256):
   // 254 k frames/s against 250 k with the blur released right after the pyramid.
   if (tm || tmf) HIP_TRY(hipEventRecord(h->ev[8], s));
-  launch_fast(s, pyr, h->d_fg, h->d_fast, s0, cand, cand_count, cell_count, fg, h->G.fastMaxVh, h->G.fastMaxVw,
-              h->G.fastMaxArea, nf, h->cus);
+  const FastForm ff = launch_fast(s, pyr, h->d_fg, h->d_fast, s0, cand, cand_count, cell_count, fg, h->G.fastMaxVh,
+                                  h->G.fastMaxVw, h->G.fastMaxArea, nf, h->cus);
+  rec.fast_cells_per_wg = ff.cells_per_wg, rec.fast_tile_pitch = ff.tile_pitch;
   if (tm || tmf) HIP_TRY(hipEventRecord(h->ev[2], s));
   // The blur's workgroups ride in the octree's launch (k_octree_blur): both need only the pyramid, the octree is a
   // latency-bound handful of workgroups per frame and the blur issue-bound filler, and inside ONE kernel (one register
@@ -529,8 +538,9 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   // (kFusedLdsWorkgroups is a MEASURED threshold, not the launch's residency: the fused launch is compiled for kOctBlurWaves = 4
   // workgroups per CU.  Geometries whose octree workspace -- vsg_octree_core.h work_bytes, + 1.8 KB per workgroup since round 5's
   // histogram / cell-position tables -- lies between 160 / 5 = 32 KB and 160 / 4 = 40 KB take the two-stream form: 1280x720 / 2000
-  // at 33 KB is the measured case above; nothing between 29 and 33 KB occurs among the reference's configurations
-  // (tests/golden/reference_configs.json: 640x480 / 1000-1500 = 17-23 KB, 752x480 / 1200 = 20 KB, 1241x376 / 2000 = 33 KB).)
+  // (35 244 B) is the measured case above.  Among the reference's configurations (tests/golden/reference_configs.json) only
+  // 752x480 / 2000 / 7 levels (33 604 B) takes two streams; 1241x376 / 2000 (32 372 B, five of them 1 980 B under 160 KB) is
+  // fused, as are 640x480 / 1000-1250 (17-21 KB) and 752x480 / 1200 (20 KB).  tests/test_gpu_launch_forms.py asserts each.)
   constexpr int kFusedLdsWorkgroups = 5;
   const bool lds_fits = kFusedLdsWorkgroups * octree_lds_bytes(fg, h->G.maxQuota, h->G.maxCellsPerLevel) <= 160 * 1024;
   const bool fused_blur = !tm && sb != s && (lds_fits || (h->one_stream && nf <= 8));
@@ -540,10 +550,12 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   // the geometries whose octree workspace keeps the blur out of its launch -- 1280x720 / 2000 -- k_slots was 51 us of a
   // 128-frame step, 5 %: profiles/r05_v_c4_kernel_stats_timed_region.csv)
   const bool self_slots = !tm && (lap1 < kEdgeThreshold || lap0 > lap1);
+  rec.fused_blur = fused_blur ? 1 : 0, rec.self_slots = self_slots ? 1 : 0;
+  OctreeForm of;
   if (fused_blur) {
     Range r_tail("DistributeOctTree (+ blur workgroups) + slots + IC_Angle / rBRIEF");
-    launch_octree(s, h->d_fg, cand, cand_count, h->d_cells, cell_count, h->d_cand2 + F * fg.cand_frame, nodeof, sel,
-                  sel_count, fg, h->G.maxQuota, h->G.maxCellsPerLevel, nf, pyr, blur, &s0);
+    of = launch_octree(s, h->d_fg, cand, cand_count, h->d_cells, cell_count, h->d_cand2 + F * fg.cand_frame, nodeof, sel,
+                       sel_count, fg, h->G.maxQuota, h->G.maxCellsPerLevel, nf, pyr, blur, &s0);
     if (!self_slots) launch_slots(s, h->d_fg, sel, sel_count, flags, slots, hdr, lap0, lap1, nf);
   } else {
   HIP_TRY(hipEventRecord(ev_pyr, s));
@@ -557,8 +569,8 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   const bool octree_first = sb != s;
   if (octree_first) {
     if (tm) HIP_TRY(hipEventRecord(h->ev[10], s));
-    launch_octree(s, h->d_fg, cand, cand_count, h->d_cells, cell_count, h->d_cand2 + F * fg.cand_frame, nodeof, sel,
-                  sel_count, fg, h->G.maxQuota, h->G.maxCellsPerLevel, nf);
+    of = launch_octree(s, h->d_fg, cand, cand_count, h->d_cells, cell_count, h->d_cand2 + F * fg.cand_frame, nodeof, sel,
+                       sel_count, fg, h->G.maxQuota, h->G.maxCellsPerLevel, nf);
     if (tm) HIP_TRY(hipEventRecord(h->ev[3], s));
   }
   HIP_TRY(hipStreamWaitEvent(sb, ev_pyr, 0));
@@ -569,8 +581,8 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   Range r_tail("DistributeOctTree + slots + IC_Angle / rBRIEF");
   if (!octree_first) {
     if (tm) HIP_TRY(hipEventRecord(h->ev[10], s));
-    launch_octree(s, h->d_fg, cand, cand_count, h->d_cells, cell_count, h->d_cand2 + F * fg.cand_frame, nodeof, sel,
-                  sel_count, fg, h->G.maxQuota, h->G.maxCellsPerLevel, nf);
+    of = launch_octree(s, h->d_fg, cand, cand_count, h->d_cells, cell_count, h->d_cand2 + F * fg.cand_frame, nodeof, sel,
+                       sel_count, fg, h->G.maxQuota, h->G.maxCellsPerLevel, nf);
     if (tm) HIP_TRY(hipEventRecord(h->ev[3], s));
   }
   if (!self_slots) launch_slots(s, h->d_fg, sel, sel_count, flags, slots, hdr, lap0, lap1, nf);
@@ -578,8 +590,11 @@ static int enqueue_range(vsg_orb *h, const Src0 &src, int f0, int nf, int lap0, 
   HIP_TRY(hipStreamWaitEvent(s, ev_blur, 0));
   if (tm) HIP_TRY(hipEventRecord(h->ev[9], s));
   }
+  rec.octree_kernel = of.kernel, rec.octree_hist_big = of.hist_big, rec.octree_label_bytes = of.label_bytes;
+  rec.octree_lead = of.lead;
   OutMirror mir = h->mirror;
   if (mir.kps) mir.kps += F * mir.capacity, mir.desc += F * mir.capacity * 32, mir.counts += F * 2;
+  rec.orient_mirror = mir.kps ? 1 : 0;
   launch_orient_desc(s, pyr, blur, h->d_fg, s0, sel, sel_count, slots, hdr, h->d_pattern, d_kps + F * capacity,
                      d_desc + F * capacity * 32, d_counts + F * 2, capacity, fg, nf, mir, self_slots);
   if (tm) HIP_TRY(hipEventRecord(h->ev[5], s));
@@ -1038,6 +1053,7 @@ static int tail_stream_work(vsg_orb *h, Slot &S, int nframes, int lap0, int lap1
   int rc = enqueue_pipeline(h, s0, nframes, lap0, lap1, S.d_kps, S.d_desc, S.d_counts, fg.out_cap, h->s_main);
   h->mirror = OutMirror();
   if (rc != VSG_OK) return rc;
+  h->forms.latency_chain = mirror_out ? 1 : 0;
   if (mirror_out) return VSG_OK;
   if (!h->one_stream) {
     const int rs = need_stream(h, &h->s_d2h);
@@ -1145,9 +1161,11 @@ static int run_chain(vsg_orb *h, Slot &S, int slot_index, const uint8_t *src_dev
       return chain_stream_work(h, S, src_dev, sframe, sstride, nframes, lap0, lap1, E, capacity);
     }
     g->graph = graph, g->exec = exec;
+    g->forms = h->forms;
   }
   HIP_TRY(hipGraphLaunch(g->exec, h->s_main));
   h->chain_launches++;
+  h->forms = g->forms, h->have_forms = true;
   // what enqueue_pipeline notes on the host when it runs (it only ran while being recorded)
   const FrameGeom &fg = h->G.fg;
   h->last_src0 = {S.d_in, (size_t)h->rows * h->in_pitch, h->in_pitch};
@@ -1728,6 +1746,16 @@ int vsg_debug_device_sort(int device, uint64_t *items, int n) {
   HIP_TRY(hipMemcpyAsync(c->h_pin, c->d_buf, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   memcpy(items, c->h_pin, sizeof(uint64_t) * n);
+  return VSG_OK;
+}
+
+int vsg_debug_last_launch_forms(vsg_orb *h, vsg_launch_forms *out) {
+  if (!h || !out) return VSG_ERR_INVALID;
+  if (!h->have_forms) {
+    set_err("vsg_debug_last_launch_forms: the handle has not enqueued a batch yet");
+    return VSG_ERR_INVALID;
+  }
+  *out = h->forms;
   return VSG_OK;
 }
 

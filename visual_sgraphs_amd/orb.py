@@ -69,7 +69,20 @@ EXPORTS = [
     "vsg_vocab_score", "vsg_kfdb_create", "vsg_kfdb_destroy", "vsg_kfdb_add", "vsg_kfdb_erase", "vsg_kfdb_clear",
     "vsg_kfdb_clear_map", "vsg_kfdb_set_map", "vsg_kfdb_set_covisibility", "vsg_kfdb_detect_relocalization_candidates",
     "vsg_kfdb_detect_n_best_candidates",
+    # test hook: the launch forms of the last enqueue
+    "vsg_debug_last_launch_forms",
 ]
+
+# include/vsg_orb_debug.h vsg_launch_forms, field for field
+LAUNCH_FORM_FIELDS = ("latency_chain", "pyramid_tiling", "fast_cells_per_wg", "fast_tile_pitch", "cand_segmented",
+                      "fused_blur", "octree_kernel", "octree_hist_big", "octree_label_bytes", "octree_lead", "self_slots",
+                      "orient_mirror", "cus", "total_cells", "nframes")
+# vsg_launch_forms.octree_kernel (VSG_OCT_*)
+OCT_BLUR_MEMBATCH, OCT_BLUR_MEMBATCH_FUSED, OCT_FEW_MEMBATCH, OCT_FEW_MEMBATCH_FUSED, OCT_STANDALONE = 1, 2, 3, 4, 5
+
+
+class _LaunchForms(C.Structure):
+    _fields_ = [(n, C.c_int) for n in LAUNCH_FORM_FIELDS]
 
 
 class VsgError(RuntimeError):
@@ -215,6 +228,7 @@ def load_library():
     L.vsg_orb_slots.argtypes = [vp]
     L.vsg_orb_chain_graph_launches.argtypes = [vp]
     L.vsg_orb_chain_graph_launches.restype = C.c_long
+    L.vsg_debug_last_launch_forms.argtypes = [vp, C.POINTER(_LaunchForms)]
     L.vsg_orb_submit_batch.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, ci, ci, ci, vp, vp, ci]
     L.vsg_orb_wait.argtypes = [vp, ci, _i32p, _i32p]
     L.vsg_orb_copy_pyramid.argtypes = [vp, ci, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -444,6 +458,12 @@ class ORBextractor:
     def chain_graph_launches(self):
         """Blocking calls served by one hipGraphLaunch so far (latency mode, include/vsg_orb.h)."""
         return self._L.vsg_orb_chain_graph_launches(self._h)
+
+    def debug_launch_forms(self):
+        """Test hook: the launch forms the last enqueue of this handle took (include/vsg_orb_debug.h), as a dict."""
+        f = _LaunchForms()
+        _check(self._L.vsg_debug_last_launch_forms(self._h, C.byref(f)), "vsg_debug_last_launch_forms")
+        return {n: int(getattr(f, n)) for n in LAUNCH_FORM_FIELDS}
 
     def submit_batch(self, images, kps_out, desc_out, vLappingArea=(0, 0)):
         """images [B,H,W] uint8 (pinned via `pin()` => DMA straight from it), kps_out [B,cap] KP_DTYPE, desc_out
