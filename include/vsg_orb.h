@@ -464,6 +464,39 @@ int vsg_orb_extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols
                              vsg_keypoint *kps, uint8_t *desc, int capacity, int *n, vsg_frame *f, const float K4[4],
                              const float *dist, int ndist, float min_x, float min_y, float max_x, float max_y,
                              vsg_keypoint *keys_un_out);
+/* RGB-D Frame (Frame.cc:344-358 with the step between UndistortKeyPoints and AssignFeaturesToGrid):
+ * vsg_orb_extract_to_frame + Tracking::GrabImageRGBD's depth conversion (Tracking.cc:1610-1611) +
+ * Frame::ComputeStereoFromRGBD (Frame.cc:1129-1150), in ONE enqueue and ONE wait.  depth: the depth plane (rows x cols of
+ * the gray image, `depth_stride` bytes per row) as VSG_DEPTH_U16 (TUM PNG, RealSense) or VSG_DEPTH_F32; depth_scale =
+ * Tracking::mDepthMapFactor (vsg_depth_map_scale), converted as convertTo(CV_32F, depth_scale) unless the plane is F32
+ * and |depth_scale - 1| <= 1e-5; mbf = Frame::mbf.  d = depth at ((int)mvKeys[i].y, (int)mvKeys[i].x); d > 0:
+ * mvDepth[i] = d, mvuRight[i] = mvKeysUn[i].x - mbf / d, otherwise both -1 (so are keypoints whose truncated pixel lies
+ * outside the plane, or NaN coordinates: undefined behaviour in the reference).  The resident frame has mvuRight
+ * (the stereo gates of SearchByProjection / Fuse apply); u_right / depth_out (capacity entries each, may be NULL)
+ * receive mvuRight / mvDepth.  Pinned depth (vsg_host_alloc, hipHostMalloc) is read in place, any other memory is
+ * staged behind the extractor's enqueue.  Sizes other than rows x cols: VSG_ERR_INVALID; other types:
+ * VSG_ERR_UNSUPPORTED.  Returns as vsg_orb_extract_to_frame; on failure the frame is empty. */
+#define VSG_DEPTH_U16 0
+#define VSG_DEPTH_F32 1
+int vsg_orb_extract_to_frame_rgbd(vsg_orb *h, const uint8_t *gray, int rows, int cols, int stride, int lap0, int lap1,
+                                  vsg_keypoint *kps, uint8_t *desc, int capacity, int *n, vsg_frame *f,
+                                  const float K4[4], const float *dist, int ndist, float min_x, float min_y, float max_x,
+                                  float max_y, vsg_keypoint *keys_un_out, const void *depth, int depth_type,
+                                  size_t depth_stride, int depth_rows, int depth_cols, float depth_scale, float mbf,
+                                  float *u_right, float *depth_out);
+/* Tracking's mDepthMapFactor from the settings' RGBD.DepthMapFactor (Tracking.cc:638-642): 1 when |yaml| < 1e-5,
+ * otherwise 1.0f / yaml.  Host arithmetic. */
+float vsg_depth_map_scale(float yaml_value);
+/* Throughput form of the depth step for the outputs of vsg_orb_extract_batch_device(_color): d_kps [nframes][capacity]
+ * (mvKeys), d_counts [nframes][2] and nframes depth planes at d_depth + f * frame_stride (rows x cols, depth_stride
+ * bytes per row) on `device`.  Each record is undistorted as vsg_frame_from_extractor_undistort does (K4 / dist / ndist;
+ * ndist = 0 or dist[0] == 0: none) and sampled as vsg_orb_extract_to_frame_rgbd; d_u_right / d_depth_out
+ * [nframes][capacity] receive mvuRight / mvDepth, -1 past each frame's count.  One launch, asynchronous on `stream`
+ * (NULL = the caller's NULL stream). */
+int vsg_rgbd_depth_batch_device(int device, const void *d_depth, int depth_type, int nframes, size_t frame_stride,
+                                size_t depth_stride, int rows, int cols, float depth_scale, float mbf, const float K4[4],
+                                const float *dist, int ndist, const vsg_keypoint *d_kps, const int *d_counts,
+                                int capacity, float *d_u_right, float *d_depth_out, void *stream);
 int vsg_frame_size(const vsg_frame *f);
 /* test / debug read-back of the device copy: grid CSR (cell_start[64*48+1], entries[n]) of the left (0) or right (1) grid */
 int vsg_frame_copy_grid(vsg_frame *f, int right, int32_t *cell_start, int32_t *entries);

@@ -575,6 +575,31 @@ class ResidentFrame {
     if (mvKeysUn) mvKeysUn->resize(n);
     return mono;
   }
+  // The RGB-D Frame constructor's front end (vsg_orb_extract_to_frame_rgbd): ExtractInto + GrabImageRGBD's depth
+  // conversion + ComputeStereoFromRGBD (Frame.cc:1129-1150), one call and one wait.  depth: rows x cols of
+  // VSG_DEPTH_U16 / VSG_DEPTH_F32, depthStride bytes per row; depthMapFactor = DepthMapScale(RGBD.DepthMapFactor);
+  // mbf = Frame::mbf.  The resident frame carries mvuRight; mvuRight / mvDepth come back sized to N.
+  int ExtractIntoRGBD(ORBextractor &ex, const uint8_t *gray, int rows, int cols, int stride, const int lapping[2],
+                      const void *depth, int depthType, size_t depthStride, float depthMapFactor, float mbf,
+                      std::vector<vsg_keypoint> &mvKeys, std::vector<uint8_t> &descriptors, const float K4[4],
+                      const float *dist, int ndist, float mnMinX, float mnMinY, float mnMaxX, float mnMaxY,
+                      std::vector<vsg_keypoint> *mvKeysUn, std::vector<float> &mvuRight, std::vector<float> &mvDepth) {
+    const int cap = vsg_orb_capacity(ex.handle(), rows, cols);
+    check(cap, "vsg_orb_capacity");
+    mvKeys.resize(cap), descriptors.resize((size_t)cap * 32), mvuRight.resize(cap), mvDepth.resize(cap);
+    if (mvKeysUn) mvKeysUn->resize(cap);
+    int n = 0;
+    const int mono = vsg_orb_extract_to_frame_rgbd(
+        ex.handle(), gray, rows, cols, stride, lapping[0], lapping[1], mvKeys.data(), descriptors.data(), cap, &n, f_, K4,
+        dist, ndist, mnMinX, mnMinY, mnMaxX, mnMaxY, mvKeysUn ? mvKeysUn->data() : nullptr, depth, depthType,
+        depthStride, rows, cols, depthMapFactor, mbf, mvuRight.data(), mvDepth.data());
+    check(mono, "vsg_orb_extract_to_frame_rgbd");
+    mvKeys.resize(n), descriptors.resize((size_t)n * 32), mvuRight.resize(n), mvDepth.resize(n);
+    if (mvKeysUn) mvKeysUn->resize(n);
+    return mono;
+  }
+  // Tracking's mDepthMapFactor from the settings' RGBD.DepthMapFactor (Tracking.cc:638-642)
+  static float DepthMapScale(float yamlDepthMapFactor) { return vsg_depth_map_scale(yamlDepthMapFactor); }
   // Frame::ComputeImageBounds (Frame.cc:924-955): {mnMinX, mnMinY, mnMaxX, mnMaxY}
   static void ImageBounds(int cols, int rows, const float K4[4], const float *dist, int ndist, float out[4]) {
     check(vsg_camera_image_bounds(cols, rows, K4, dist, ndist, out), "vsg_camera_image_bounds");

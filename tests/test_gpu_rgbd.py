@@ -1,0 +1,462 @@
+"""GPU tests of the RGB-D frame path: vsg_orb_extract_to_frame_rgbd (one frame, one call, one wait) and
+vsg_rgbd_depth_batch_device (the throughput form), against tests/rgbd_reference.py on the oracle's keypoints.  mvuRight /
+mvDepth are compared as bytes; keypoints, descriptors and grids as the gray-only path produces them."""
+import os
+import subprocess
+import sys
+import threading
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+import rgbd_reference as rr
+import scenarios as sc
+from visual_sgraphs_amd import orb, synth
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+W, H = 640, 480
+MBF = np.float32(40.0)  # Camera.bf of RealSense_D435i.yaml
+F32 = np.float32
+# (dtype, mDepthMapFactor): D435i (RGBD.DepthMapFactor 1000), uint16 at 1, float32 inside the 1e-5 gate, float32 at 0.5
+DEPTHS = {"u16_d435i": (np.uint16, rr.depth_map_scale(1000.0)), "u16_one": (np.uint16, F32(1.0)),
+          "f32_unscaled": (np.float32, F32(1.000005)), "f32_half": (np.float32, F32(0.5))}
+
+
+@pytest.fixture(params=sc.CAMERA_NAMES)
+def camera(request):
+    """The three cameras of the scenarios: no distortion, TUM1 (C1) and RealSense D435i (C5)."""
+    return request.param
+
+
+def _cam(name, w=W, h=H):
+    """(K4, dist, bounds) of the camera for a w x h image; K4 = dist = None without distortion."""
+    if name == "image":
+        return None, None, (0.0, 0.0, float(w), float(h))
+    c = ol.scaled_camera(name, w, h)
+    return c["K4"], c["dist"], ol.image_bounds(c)
+
+
+_REF = {}
+
+
+def _oracle(nfeat, img_key, img):
+    """(mono, mvKeys, descriptors) of the oracle extractor, cached per image."""
+    key = (nfeat, img_key)
+    if key not in _REF:
+        _REF[key] = ol.OracleExtractor(nfeat, 1.2, 8, 20, 7)(img)
+    return _REF[key]
+
+
+def _image(seed):
+    return synth.sequence_frame(W, H, seed, 0)
+
+
+def _expected(rk, camera, depth, scale):
+    cam = None if camera == "image" else ol.scaled_camera(camera, W, H)
+    kun = rk if cam is None else ol.undistort_keypoints(rk, cam)
+    ur, d = rr.rgbd_frame(rk, kun, depth, scale, MBF)
+    return kun, ur, d
+
+
+def _padded(plane, extra):
+    """The plane inside rows of cols + extra elements (a padded stride), as a view."""
+    buf = np.full((plane.shape[0], plane.shape[1] + extra), 7, plane.dtype)
+    buf[:, :plane.shape[1]] = plane
+    return buf[:, :plane.shape[1]]
+
+
+def _check_frame(f, ex, camera, img, depth, scale, nfeat, got, img_key):
+    mono, k, d, ur, dep = got
+    rm, rk, rd = _oracle(nfeat, img_key, img)
+    assert mono == rm and k.tobytes() == rk.tobytes() and np.array_equal(d, rd)
+    kun, want_ur, want_d = _expected(rk, camera, np.asarray(depth), scale)
+    assert ur.tobytes() == want_ur.tobytes() and dep.tobytes() == want_d.tobytes()
+    assert f.N == len(rk) and f.kps.tobytes() == kun.tobytes()
+    return kun, want_ur
+
+
+# ------------------------------------------------------------------------------------------------ one frame, one call
+@pytest.mark.parametrize("nfeat", [1000, 1250])
+@pytest.mark.parametrize("kind", ["pageable", "pageable_padded", "pinned", "torch_pinned", "registered"])
+@pytest.mark.parametrize("depth_kind", list(DEPTHS))
+def test_one_call_equals_reference(camera, nfeat, kind, depth_kind):
+    dtype, scale = DEPTHS[depth_kind]
+    K4, dist, bounds = _cam(camera)
+    img = _image(5)
+    plane = rr.depth_plane(11, H, W, dtype)
+    ex = orb.ORBextractor(nfeat, 1.2, 8, 20, 7)
+    f = orb.Frame(ex.capacity(H, W))
+    keep = None
+    if kind == "pageable":
+        depth = plane
+    elif kind == "pageable_padded":
+        depth = _padded(plane, 37 if dtype == np.uint16 else 5)
+        assert depth.strides[0] != depth.shape[1] * depth.itemsize
+    elif kind == "pinned":
+        keep = orb.PinnedArray(plane.shape, dtype)
+        keep.a[:] = plane
+        depth = keep.a
+        assert orb.host_kind(depth) == "vsg_host_alloc"
+    elif kind == "torch_pinned":
+        import torch
+        keep = torch.zeros(plane.nbytes, dtype=torch.uint8).pin_memory()  # somebody else's hipHostMalloc block
+        depth = keep.numpy().view(dtype).reshape(plane.shape)
+        depth[:] = plane
+        assert depth.ctypes.data == keep.data_ptr() and orb.host_kind(depth) in ("hipHostMalloc", "registered")
+    else:
+        depth = orb.pin(plane.copy())
+        keep = depth
+    try:
+        got = f.extract_into_rgbd(ex, img, depth, bounds, K4, dist, scale, MBF)
+        _check_frame(f, ex, camera, img, plane, scale, nfeat, got, 5)
+        assert np.any(got[4] > 0) and np.any(got[4] == -1)  # holes and depths
+        # keypoints, descriptors and grid are what the gray-only call produces
+        g = orb.Frame(ex.capacity(H, W))
+        mono, k, d = g.extract_into(ex, img, bounds, K4, dist)
+        assert mono == got[0] and k.tobytes() == got[1].tobytes() and np.array_equal(d, got[2])
+        assert g.kps.tobytes() == f.kps.tobytes()
+        assert all(np.array_equal(a, b) for a, b in zip(f.grid(), g.grid()))
+    finally:
+        if kind == "registered":
+            orb.unpin(keep)
+
+
+def test_special_values_at_keypoint_pixels(camera):
+    """Extract once, then plant NaN, +-0, negatives, +-inf and subnormals at the keypoints' pixels (float32 plane read
+    unscaled and scaled) and 0 / 65535 in a uint16 plane: the same image gives the same keypoints, the depths follow."""
+    K4, dist, bounds = _cam(camera)
+    img = _image(6)
+    ex = orb.ORBextractor(1250, 1.2, 8, 20, 7)
+    f = orb.Frame(ex.capacity(H, W))
+    base = rr.depth_plane(12, H, W, np.float32)
+    _, k, _, _, _ = f.extract_into_rgbd(ex, img, base, bounds, K4, dist, F32(1.0), MBF)
+    assert len(k) > 100
+    sub = np.array([0x00000001, 0x00012345, 0x007FFFFF], np.uint32).view(np.float32)
+    specials = np.concatenate([[np.nan, 0.0, -0.0, -1.5, -np.inf, np.inf], sub, -sub]).astype(np.float32)
+    plane = base.copy()
+    rows, cols = k["y"].astype(np.int32), k["x"].astype(np.int32)
+    for j in range(min(len(k), 8 * len(specials))):
+        plane[rows[j], cols[j]] = specials[j % len(specials)]
+    for scale in (F32(1.0), F32(0.5)):
+        got = f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, scale, MBF)
+        _check_frame(f, ex, camera, img, plane, scale, 1250, got, 6)
+        if scale == 1.0:
+            dep = got[4]
+            assert np.isinf(dep).any() and (dep.view(np.uint32) == 0x00012345).any()
+    u16 = rr.depth_plane(12, H, W, np.uint16)
+    for j in range(min(len(k), 64)):
+        u16[rows[j], cols[j]] = (0, 65535)[j % 2]
+    got = f.extract_into_rgbd(ex, img, u16, bounds, K4, dist, F32(0.001), MBF)
+    _check_frame(f, ex, camera, img, u16, F32(0.001), 1250, got, 6)
+
+
+# ------------------------------------------------------------------------------------------------ has_uright
+def _queries(kun, desc, ur, seed):
+    """Map points that project near the frame's features: half of them with a right coordinate consistent with mvuRight,
+    the others 12 px off it (the stereo gates must reject those where the frame has a depth)."""
+    rng = np.random.default_rng(seed)
+    n = len(kun)
+    sel = rng.choice(n, size=min(n, 600), replace=False)
+    x = (kun["x"][sel] + rng.normal(0, 1.0, len(sel))).astype(np.float32)
+    y = (kun["y"][sel] + rng.normal(0, 1.0, len(sel))).astype(np.float32)
+    off = np.where(np.arange(len(sel)) % 2 == 0, 0.5, 12.0).astype(np.float32)
+    xr = np.where(ur[sel] > 0, ur[sel] + off, x - 5.0).astype(np.float32)
+    q = desc[sel].copy()
+    flip = rng.integers(0, 256, q.shape, dtype=np.uint8) & rng.integers(0, 256, q.shape, dtype=np.uint8) & \
+        rng.integers(0, 256, q.shape, dtype=np.uint8) & rng.integers(0, 256, q.shape, dtype=np.uint8)
+    return sel, x, y, xr, q ^ flip
+
+
+def test_resident_rgbd_frame_applies_the_stereo_gates(camera):
+    K4, dist, bounds = _cam(camera)
+    img = _image(7)
+    ex = orb.ORBextractor(1000, 1.2, 8, 20, 7)
+    f, g = orb.Frame(ex.capacity(H, W)), orb.Frame(ex.capacity(H, W))
+    plane = rr.depth_plane(13, H, W, np.uint16)
+    scale = rr.depth_map_scale(1000.0)
+    got = f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, scale, MBF)
+    kun, ur = _check_frame(f, ex, camera, img, plane, scale, 1000, got, 7)
+    g.extract_into(ex, img, bounds, K4, dist)  # the same frame without depth
+    desc = got[2]
+    o = ol.OracleFrame(kun, desc, bounds, u_right=ur)
+    o_mono = ol.OracleFrame(kun, desc, bounds)
+    sel, x, y, xr, q = _queries(kun, desc, ur, 7)
+    nq = len(sel)
+    lvl = kun["octave"][sel].astype(np.int32)
+    blocked = np.zeros(len(kun), np.uint8)
+    differs = []
+    # SearchByProjection(F, vpMapPoints) with mTrackProjXR (ORBmatcher.cc:92-102)
+    mp = dict(desc=q, observed=np.ones(nq, np.uint8), in_view=np.ones(nq, np.uint8), proj_x=x, proj_y=y, proj_xr=xr,
+              scale_level=lvl, view_cos=np.ones(nq, np.float32))
+    a = f.SearchByProjection(mp, 1.0, 0.8, sc.SCALE_FACTORS, blocked)
+    b = o.search_by_projection(mp, 1.0, 0.8, sc.SCALE_FACTORS, blocked)
+    assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    differs.append(a[0] != g.SearchByProjection(mp, 1.0, 0.8, sc.SCALE_FACTORS, blocked)[0])
+    # SearchByProjection(CurrentFrame, LastFrame) with the last frame's right coordinates (:1742-1745)
+    args = (q, np.ones(nq, np.uint8), x, y, xr, lvl, kun["angle"][sel].astype(np.float32), 4.0, 0, sc.SCALE_FACTORS,
+            False, blocked)
+    a = f.SearchByProjection_Last(*args)
+    b = o.search_by_projection_last(*args)
+    assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    differs.append(a[0] != g.SearchByProjection_Last(*args)[0])
+    # Fuse: the chi-square gate with mvuRight (:1269-1274)
+    radius = np.full(nq, 6.0, np.float32)
+    qmp = np.arange(nq, dtype=np.int32)
+    slot = np.full(len(kun), -1, np.int32)
+    obs, bad = np.ones(nq + len(kun), np.int32), np.zeros(nq + len(kun), np.uint8)
+    a = f.Fuse(q, x, y, xr, radius, lvl, sc.INV_SIGMA2)
+    b = o.fuse(qmp, q, x, y, xr, radius, lvl, sc.INV_SIGMA2, slot, obs, bad)
+    assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    c = o_mono.fuse(qmp, q, x, y, xr, radius, lvl, sc.INV_SIGMA2, slot, obs, bad)
+    differs.append(a[0] != c[0] or not np.array_equal(a[1], c[1]))
+    assert any(differs), "mvuRight changed no answer"
+
+
+# ------------------------------------------------------------------------------------------------ repeated calls, threads
+def test_repeated_calls_sizes_and_empty_image(camera):
+    ex = orb.ORBextractor(1000, 1.2, 8, 20, 7)
+    f = orb.Frame(ex.capacity(H, W))
+    for t, (w, h, seed) in enumerate([(640, 480, 3), (320, 240, 4), (640, 480, 5), (320, 240, None)]):
+        K4, dist, bounds = _cam(camera, w, h)
+        img = synth.sequence_frame(w, h, seed, 0) if seed is not None else np.full((h, w), 90, np.uint8)
+        plane = rr.depth_plane(20 + t, h, w, np.uint16)
+        mono, k, d, ur, dep = f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, F32(0.001), MBF)
+        rm, rk, rd = ol.OracleExtractor(1000, 1.2, 8, 20, 7)(img)
+        assert mono == rm and k.tobytes() == rk.tobytes() and np.array_equal(d, rd), t
+        cam = None if camera == "image" else ol.scaled_camera(camera, w, h)
+        kun = rk if cam is None else ol.undistort_keypoints(rk, cam)
+        wu, wd = rr.rgbd_frame(rk, kun, plane, F32(0.001), MBF)
+        assert ur.tobytes() == wu.tobytes() and dep.tobytes() == wd.tobytes(), t
+        assert f.N == len(rk)
+    assert len(k) == 0  # the featureless image
+    # an empty image: operator() returns -1 and the frame is empty
+    with pytest.raises(orb.VsgError) as e:
+        f.extract_into_rgbd(ex, np.zeros((0, 0), np.uint8), np.zeros((0, 0), np.uint16), (0, 0, 1, 1), None, None, 1.0, MBF)
+    assert e.value.code == -1 and f.N == 0
+
+
+def test_two_host_threads_each_with_its_own_frame(camera):
+    K4, dist, bounds = _cam(camera)
+    errors = []
+
+    def work(seed):
+        try:
+            ex = orb.ORBextractor(1000, 1.2, 8, 20, 7)
+            f = orb.Frame(ex.capacity(H, W))
+            for t in range(4):
+                img = synth.sequence_frame(W, H, seed, t)
+                plane = rr.depth_plane(seed * 10 + t, H, W, np.uint16)
+                mono, k, d, ur, dep = f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, F32(0.001), MBF)
+                _, want_ur, want_d = _expected(k, camera, plane, F32(0.001))
+                assert ur.tobytes() == want_ur.tobytes() and dep.tobytes() == want_d.tobytes()
+        except Exception as ex_:  # noqa: BLE001
+            errors.append(repr(ex_))
+
+    th = [threading.Thread(target=work, args=(s,)) for s in (31, 32)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert errors == []
+
+
+def test_steady_state_allocates_nothing(camera):
+    K4, dist, bounds = _cam(camera)
+    ex = orb.ORBextractor(1250, 1.2, 8, 20, 7)
+    f = orb.Frame(ex.capacity(H, W))
+    img = _image(8)
+    plane = rr.depth_plane(8, H, W, np.uint16)
+    pinned = orb.PinnedArray(plane.shape, np.uint16)
+    pinned.a[:] = plane
+    first = f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, F32(0.001), MBF)
+    f.extract_into_rgbd(ex, img, pinned.a, bounds, K4, dist, F32(0.001), MBF)
+    g0 = orb.thread_arena_growths(0)
+    for i in range(10):
+        again = f.extract_into_rgbd(ex, img, plane if i % 2 else pinned.a, bounds, K4, dist, F32(0.001), MBF)
+    assert orb.thread_arena_growths(0) == g0
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first[1:], again[1:]))
+
+
+def test_error_codes(camera):
+    K4, dist, bounds = _cam(camera)
+    ex = orb.ORBextractor(1000, 1.2, 8, 20, 7)
+    f = orb.Frame(ex.capacity(H, W))
+    img = _image(9)
+    plane = rr.depth_plane(9, H, W, np.uint16)
+    f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, F32(0.001), MBF)
+    assert f.N > 0
+    import torch
+    with pytest.raises(ValueError, match="host memory"):  # a device tensor is never passed on as a host pointer
+        f.extract_into_rgbd(ex, img, torch.from_numpy(plane.astype(np.float32)).cuda(), bounds, K4, dist, F32(1.0), MBF)
+    for depth, code in ((plane[:-1], -6), (plane[:, :-2], -6), (plane.astype(np.int32), -3), (None, -6)):
+        with pytest.raises(orb.VsgError) as e:
+            f.extract_into_rgbd(ex, img, depth, bounds, K4, dist, F32(0.001), MBF)
+        assert e.value.code == code
+        assert f.N == 0  # on failure the frame is empty
+        f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, F32(0.001), MBF)
+
+
+# ------------------------------------------------------------------------------------------------ switches
+_CHILD = r"""
+import sys, numpy as np
+sys.path[:0] = [{root!r}, {tests!r}]
+import rgbd_reference as rr, oracle_lib as ol
+from visual_sgraphs_amd import orb, synth
+W, H = 640, 480
+camera = {camera!r}
+K4, dist, bounds = (None, None, (0.0, 0.0, W, H)) if camera == "image" else \
+    (lambda c: (c["K4"], c["dist"], ol.image_bounds(c)))(ol.scaled_camera(camera, W, H))
+ex = orb.ORBextractor(1000, 1.2, 8, 20, 7)
+f = orb.Frame(ex.capacity(H, W))
+out = []
+for t in range(4):  # VSG_GRAPH=1: the first call per key runs eagerly, the second records, later ones replay
+    img = synth.sequence_frame(W, H, 3, t % 2)
+    plane = rr.depth_plane(t, H, W, np.uint16)
+    r = f.extract_into_rgbd(ex, img, plane, bounds, K4, dist, np.float32(0.001), np.float32(40))
+    out.append(b"".join(a.tobytes() for a in r[1:]))
+sys.stdout.buffer.write(b"".join(out))
+"""
+
+
+def _child(camera, env_extra):
+    env = dict(os.environ, **env_extra)
+    code = _CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), camera=camera)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+    return r.stdout
+
+
+def test_identical_under_graph_and_no_overlap(camera):
+    base = _child(camera, {})
+    assert len(base) > 1000
+    assert _child(camera, {"VSG_GRAPH": "1"}) == base
+    assert _child(camera, {"VSG_NO_OVERLAP": "1"}) == base
+
+
+# ------------------------------------------------------------------------------------------------ batched form
+_BATCH_REF = {}
+
+
+def _batch_oracle(cfg, uniq_key, uniq, cap):
+    key = (cfg, uniq_key)
+    if key not in _BATCH_REF:
+        w, h, nf = cfg
+        _BATCH_REF[key] = ol.extract_batch(uniq, nf, cap, 1.2, 8, 20, 7, (0, 0))
+    return _BATCH_REF[key]
+
+
+@pytest.mark.parametrize("B", [1, 9, 12, 48])
+@pytest.mark.parametrize("cfg", [(640, 480, 1000), (1280, 720, 2000)], ids=["C2", "C4"])
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+def test_batch_device_equals_reference(camera, B, cfg, dtype):
+    import torch
+    w, h, nf = cfg
+    K4, dist, _ = _cam(camera, w, h)
+    uniq = np.stack([synth.sequence_frame(w, h, 40 + i, 0) for i in range(3)])
+    idx = np.arange(B) % len(uniq)
+    frames = np.ascontiguousarray(uniq[idx])
+    ex = orb.ORBextractor(nf, 1.2, 8, 20, 7, max_batch=B)
+    cap = ex.capacity(h, w)
+    dev = torch.device("cuda", 0)
+    pitch = w + (24 if dtype == np.uint16 else 8)  # padded depth rows
+    planes = np.zeros((B, h, pitch), dtype)
+    for b in range(B):
+        planes[b, :, :w] = rr.depth_plane(100 + b, h, w, dtype)
+    scale = rr.depth_map_scale(1000.0) if dtype == np.uint16 else F32(1.0)
+    d_gray = torch.from_numpy(frames).to(dev)
+    d_depth = torch.from_numpy(planes.view(np.int16) if dtype == np.uint16 else planes).to(dev)
+    d_kps = torch.zeros((B, cap, 28), dtype=torch.uint8, device=dev)
+    d_desc = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+    d_counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    d_ur = torch.full((B, cap), 123.0, dtype=torch.float32, device=dev)
+    d_dep = torch.full((B, cap), 123.0, dtype=torch.float32, device=dev)
+    st = torch.cuda.Stream(device=dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    esz = planes.itemsize
+    with torch.cuda.stream(st):
+        ex.extract_batch_device(d_gray.data_ptr(), B, h * w, h, w, w, d_kps.data_ptr(), d_desc.data_ptr(),
+                                d_counts.data_ptr(), cap, (0, 0), st.cuda_stream)
+        orb.rgbd_depth_batch_device(d_depth.data_ptr(), orb.VSG_DEPTH_U16 if dtype == np.uint16 else orb.VSG_DEPTH_F32,
+                                    B, h * pitch * esz, pitch * esz, h, w, scale, MBF, K4 if K4 is not None else
+                                    (500.0, 500.0, w / 2, h / 2), dist, d_kps.data_ptr(), d_counts.data_ptr(), cap,
+                                    d_ur.data_ptr(), d_dep.data_ptr(), st.cuda_stream)
+    torch.cuda.synchronize(dev)
+    counts, kps = d_counts.cpu().numpy(), d_kps.cpu().numpy().view(orb.KP_DTYPE).reshape(B, cap)
+    ur, dep = d_ur.cpu().numpy(), d_dep.cpu().numpy()
+    want = _batch_oracle(cfg, 40, uniq, cap)
+    # the input records are the oracle's
+    assert ol.compare_batch(counts, kps, d_desc.cpu().numpy(), want[0][idx], want[1][idx], want[2][idx]) == []
+    cam = None if camera == "image" else ol.scaled_camera(camera, w, h)
+    for b in range(B):
+        n = counts[b, 0]
+        rk = kps[b, :n]
+        kun = rk if cam is None else ol.undistort_keypoints(rk, cam)
+        wu, wd = rr.rgbd_frame(rk, kun, planes[b, :, :w], scale, MBF)
+        assert ur[b, :n].tobytes() == wu.tobytes() and dep[b, :n].tobytes() == wd.tobytes(), b
+        assert np.all(ur[b, n:] == -1) and np.all(dep[b, n:] == -1), b
+
+
+def test_batch_device_out_of_plane_and_nan_records(camera):
+    """Planted records: outside the plane on every side, NaN coordinates, huge values -- -1 / -1 and no fault."""
+    import torch
+    K4, dist, _ = _cam(camera)
+    dev = torch.device("cuda", 0)
+    cap, B = 16, 2
+    k = np.zeros((B, cap), orb.KP_DTYPE)
+    xs = [-1.0, -0.5, 639.999, 640.0, 3e9, -3e9, np.nan, 5.0, np.inf, -np.inf, 10.99, 320.0, 1e-30, 0.0, 100.0, 200.0]
+    ys = [5.0, -0.99, 479.5, 10.0, 10.0, 10.0, 10.0, np.nan, 1.0, 1.0, 2.7, 480.0, 0.0, 479.999, -1.0, 1e20]
+    k["x"], k["y"] = xs, ys
+    plane = rr.depth_plane(3, H, W, np.uint16)
+    planes = np.stack([plane, plane])
+    counts = np.array([[cap, 0], [cap // 2, 0]], np.int32)
+    d_k = torch.from_numpy(k.view(np.uint8).reshape(B, cap, 28).copy()).to(dev)
+    d_c = torch.from_numpy(counts).to(dev)
+    d_p = torch.from_numpy(planes.view(np.int16)).to(dev)
+    d_ur = torch.zeros((B, cap), dtype=torch.float32, device=dev)
+    d_dep = torch.zeros((B, cap), dtype=torch.float32, device=dev)
+    orb.rgbd_depth_batch_device(d_p.data_ptr(), orb.VSG_DEPTH_U16, B, H * W * 2, W * 2, H, W, F32(0.001), MBF,
+                                K4 if K4 is not None else (500.0, 500.0, 320.0, 240.0), dist, d_k.data_ptr(),
+                                d_c.data_ptr(), cap, d_ur.data_ptr(), d_dep.data_ptr(), None)
+    torch.cuda.synchronize(dev)
+    ur, dep = d_ur.cpu().numpy(), d_dep.cpu().numpy()
+    cam = None if camera == "image" else ol.scaled_camera(camera, W, H)
+    for b in range(B):
+        n = counts[b, 0]
+        rk = k[b, :n]
+        kun = rk if cam is None else ol.undistort_keypoints(rk, cam)
+        wu, wd = rr.rgbd_frame(rk, kun, plane, F32(0.001), MBF)
+        assert ur[b, :n].tobytes() == wu.tobytes() and dep[b, :n].tobytes() == wd.tobytes()
+        assert np.all(ur[b, n:] == -1) and np.all(dep[b, n:] == -1)
+    outside = [0, 3, 4, 5, 6, 8, 9, 11, 14, 15]
+    assert np.all(dep[0, outside] == -1) and np.all(dep[0, [1, 2, 10, 12, 13]] > 0)
+
+
+def test_cpp_adaptor_rgbd_equals_reference(tmp_path):
+    """tests/_adaptor_rgbd/rgbd_check.cpp: ResidentFrame::ExtractIntoRGBD from plain C++ (padded uint16 depth, D435i)."""
+    d = ROOT / "tests" / "_adaptor_rgbd"
+    subprocess.check_call(["make", "-C", str(d)], stdout=subprocess.DEVNULL)
+    out = tmp_path / "rgbd.bin"
+    r = subprocess.run([str(d / "rgbd_check"), str(out)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    buf, pos, parts = out.read_bytes(), 0, []
+    while pos < len(buf):
+        n = int(np.frombuffer(buf, np.int32, 1, pos)[0])
+        pos += 4
+        parts.append((pos, n))
+        pos += n * {0: 4, 1: 4, 2: 28, 3: 28, 4: 4, 5: 4, 6: 2}[len(parts) - 1]
+    get = lambda i, dt: np.frombuffer(buf, dt, parts[i][1], parts[i][0])  # noqa: E731
+    mono, N, w, h, ds = get(0, np.int32)
+    factor, mbf = get(1, np.float32)
+    keys, keys_un = get(2, orb.KP_DTYPE), get(3, orb.KP_DTYPE)
+    ur, dep = get(4, np.float32), get(5, np.float32)
+    plane = get(6, np.uint16).reshape(h, ds)[:, :w]
+    assert factor == rr.depth_map_scale(1000.0) and N == len(keys) > 100
+    rm, rk, _ = ol.OracleExtractor(1000, 1.2, 8, 20, 7)(synth.sequence_frame(w, h, 5, 0))
+    assert mono == rm and keys.tobytes() == rk.tobytes()
+    assert keys_un.tobytes() == ol.undistort_keypoints(rk, ol.scaled_camera("d435i", w, h)).tobytes()
+    wu, wd = rr.rgbd_frame(keys, keys_un, plane, factor, mbf)
+    assert ur.tobytes() == wu.tobytes() and dep.tobytes() == wd.tobytes()

@@ -419,6 +419,34 @@ static Camera cam_tum1() {
           {0.262383f, -0.953104f, -0.005358f, 0.002628f, 1.163314f}, 5, {0, 0, 0, 0}};
 }
 
+// ------------------------------------------------------------------------------------------------ RGB-D depth
+// A seeded uint16 depth plane (millimetre-like values, 10 % holes = 0), what a RealSense or a TUM PNG delivers.
+static void seeded_depth(int seed, int W, int H, uint16_t *d) {
+  uint64_t s = 0x9E3779B97F4A7C15ull * (uint64_t)(seed + 1);
+  for (size_t i = 0; i < (size_t)W * H; i++) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    const uint32_t r = (uint32_t)(s >> 33);
+    d[i] = (r % 10 == 0) ? 0 : (uint16_t)(500 + r % 4500);
+  }
+}
+
+// Frame::ComputeStereoFromRGBD (Frame.cc:1129-1150) on the host, after Tracking::GrabImageRGBD's convertTo of a uint16
+// plane (Tracking.cc:1610-1611): the reference's ten lines, float arithmetic, no contraction
+static void cpu_rgbd(const uint16_t *depth, int W, int H, float scale, float mbf, const vsg_keypoint *kp,
+                     const vsg_keypoint *kpun, int n, float *ur, float *dep) {
+  for (int i = 0; i < n; i++) {
+    ur[i] = dep[i] = -1;
+    const float x = kp[i].x, y = kp[i].y;
+    if (!(x > -1.f && y > -1.f && x < (float)W && y < (float)H)) continue;
+    const volatile float d = (float)depth[(size_t)(int)y * W + (int)x] * scale;
+    if (d > 0) {
+      dep[i] = d;
+      const volatile float q = mbf / d;
+      ur[i] = kpun[i].x - q;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ C5
 static const int W5 = 640, H5 = 480, NF5 = 1250, NSTREAM = 5 - 1;
 
@@ -427,22 +455,31 @@ struct TrackResult {
   std::vector<vsg_keypoint> kp, kpun;  // mvKeys, mvKeysUn
   std::vector<uint8_t> ds, tb;
   std::vector<int32_t> tm_last, tm_local;
+  std::vector<float> ur, dep;  // mvuRight, mvDepth (RGB-D frames)
   void size_for(int cap) {
     kp.resize(cap), kpun.resize(cap), ds.resize((size_t)cap * 32), tb.resize(cap), tm_last.resize(cap), tm_local.resize(cap);
+    ur.assign(cap, -1.f), dep.assign(cap, -1.f);
   }
 };
 
 // the projections of the previous frame's features into the current one: the scene moves by (-3, -2) px per frame
 struct Queries {
-  std::vector<float> u, v, ang, vc;
+  std::vector<float> u, v, ur, ang, vc;
   std::vector<int32_t> oct;
   std::vector<uint8_t> obs;
-  void from(const TrackResult &P) {
-    u.resize(P.n), v.resize(P.n), ang.resize(P.n), vc.assign(P.n, 0.9f), oct.resize(P.n), obs.assign(P.n, 1);
-    for (int i = 0; i < P.n; i++)  // projected from the previous frame's UNDISTORTED keypoints, like the reference's geometry
+  // ur: the projected right coordinate (uv(0) - mbf * invz, ORBmatcher.cc:1742; mTrackProjXR, :92-94): the previous
+  // frame's mvuRight moved with the scene where it has a depth, a point 2 m away where it has none
+  void from(const TrackResult &P, float mbf = 0.f) {
+    u.resize(P.n), v.resize(P.n), ur.resize(P.n), ang.resize(P.n), vc.assign(P.n, 0.9f), oct.resize(P.n), obs.assign(P.n, 1);
+    for (int i = 0; i < P.n; i++) {  // projected from the previous frame's UNDISTORTED keypoints, like the reference's geometry
       u[i] = P.kpun[i].x - 3.f, v[i] = P.kpun[i].y - 2.f, ang[i] = P.kpun[i].angle, oct[i] = P.kpun[i].octave;
+      ur[i] = P.ur[i] > 0 ? P.ur[i] - 3.f : u[i] - mbf / 2.f;
+    }
   }
 };
+
+// RealSense_D435i.yaml: RGBD.DepthMapFactor 1000, Stereo.b 0.0745 (mbf = b * fx, Settings.cc)
+static const float kDepthFactor5 = 1000.f, kBaseline5 = 0.0745f;
 
 struct C5Gpu {
   vsg_orb *ex = nullptr;
@@ -464,24 +501,35 @@ struct C5Gpu {
       res[i].size_for(cap);
     }
   }
-  void frame(const uint8_t *img, int t, bool have_prev) {
+  // depth != nullptr: the RGB-D Frame (vsg_orb_extract_to_frame_rgbd, uint16 depth, D435i's DepthMapFactor and bf); the
+  // resident frame then has mvuRight and both searches apply their stereo gates
+  void frame(const uint8_t *img, int t, bool have_prev, const uint16_t *depth = nullptr) {
     TrackResult &R = res[t & 1], &P = res[(t + 1) & 1];
+    const float mbf = kBaseline5 * cam.K4[0];
     // the Frame constructor's front end in one call and one wait: operator() -> UndistortKeyPoints on the device (inside the
     // launch that builds the grid, right behind the extractor's chain) -> resident frame; mvKeysUn comes back for the host
-    CHECK(vsg_orb_extract_to_frame(ex, img, H5, W5, W5, 0, 0, R.kp.data(), R.ds.data(), cap, &R.n, F[t & 1], cam.K4, cam.dist,
-                                   cam.ndist, cam.bounds[0], cam.bounds[1], cam.bounds[2], cam.bounds[3], R.kpun.data()) >= 0);
+    if (depth) {
+      CHECK(vsg_orb_extract_to_frame_rgbd(ex, img, H5, W5, W5, 0, 0, R.kp.data(), R.ds.data(), cap, &R.n, F[t & 1], cam.K4,
+                                          cam.dist, cam.ndist, cam.bounds[0], cam.bounds[1], cam.bounds[2], cam.bounds[3],
+                                          R.kpun.data(), depth, VSG_DEPTH_U16, (size_t)W5 * 2, H5, W5,
+                                          vsg_depth_map_scale(kDepthFactor5), mbf, R.ur.data(), R.dep.data()) >= 0);
+    } else {
+      CHECK(vsg_orb_extract_to_frame(ex, img, H5, W5, W5, 0, 0, R.kp.data(), R.ds.data(), cap, &R.n, F[t & 1], cam.K4, cam.dist,
+                                     cam.ndist, cam.bounds[0], cam.bounds[1], cam.bounds[2], cam.bounds[3], R.kpun.data()) >= 0);
+    }
     R.n_last = R.n_local = 0;
     if (have_prev) {
-      q.from(P);
+      q.from(P, mbf);
       std::fill(R.tb.begin(), R.tb.begin() + R.n, 0), std::fill(R.tm_last.begin(), R.tm_last.begin() + R.n, -1);
-      R.n_last = vsg_frame_search_by_projection_last(F[t & 1], P.n, P.ds.data(), q.obs.data(), q.u.data(), q.v.data(), nullptr,
-                                                     nullptr, nullptr, q.oct.data(), q.ang.data(), 15.f, 0, sf, 8, 1,
-                                                     R.tb.data(), R.tm_last.data());
+      R.n_last = vsg_frame_search_by_projection_last(F[t & 1], P.n, P.ds.data(), q.obs.data(), q.u.data(), q.v.data(),
+                                                     depth ? q.ur.data() : nullptr, nullptr, nullptr, q.oct.data(),
+                                                     q.ang.data(), 15.f, 0, sf, 8, 1, R.tb.data(), R.tm_last.data());
       CHECK(R.n_last >= 0);
       std::fill(R.tb.begin(), R.tb.begin() + R.n, 0), std::fill(R.tm_local.begin(), R.tm_local.begin() + R.n, -1);
       R.n_local = vsg_frame_search_by_projection(F[t & 1], P.n, P.ds.data(), q.obs.data(), q.obs.data(), q.u.data(), q.v.data(),
-                                                 q.u.data(), q.oct.data(), q.vc.data(), nullptr, nullptr, nullptr, nullptr,
-                                                 nullptr, 1.f, 0.8f, sf, 8, nullptr, nullptr, R.tb.data(), R.tm_local.data());
+                                                 depth ? q.ur.data() : q.u.data(), q.oct.data(), q.vc.data(), nullptr, nullptr,
+                                                 nullptr, nullptr, nullptr, 1.f, 0.8f, sf, 8, nullptr, nullptr, R.tb.data(),
+                                                 R.tm_local.data());
       CHECK(R.n_local >= 0);
     }
     frames++;
@@ -506,21 +554,25 @@ struct C5Cpu {
     or_get_tables(ex, sf, nullptr, nullptr, nullptr, nullptr, nullptr);
     res[0].size_for(cap), res[1].size_for(cap);
   }
-  void frame(const uint8_t *img, int t, bool have_prev) {
+  void frame(const uint8_t *img, int t, bool have_prev, const uint16_t *depth = nullptr) {
     TrackResult &R = res[t & 1], &P = res[(t + 1) & 1];
+    const float mbf = kBaseline5 * cam.K4[0];
     or_extract(ex, img, H5, W5, W5, 0, 0, (OrKeyPoint *)R.kp.data(), R.ds.data(), cap, &R.n);
     or_undistort_keypoints((const OrKeyPoint *)R.kp.data(), R.n, cam.K4, cam.dist, cam.ndist, (OrKeyPoint *)R.kpun.data());
-    OrFrame *f = or_frame_create((const OrKeyPoint *)R.kpun.data(), R.ds.data(), nullptr, R.n, -1, cam.bounds[0], cam.bounds[1],
-                                 cam.bounds[2], cam.bounds[3]);
+    if (depth)
+      cpu_rgbd(depth, W5, H5, 1.f / kDepthFactor5, mbf, R.kp.data(), R.kpun.data(), R.n, R.ur.data(), R.dep.data());
+    OrFrame *f = or_frame_create((const OrKeyPoint *)R.kpun.data(), R.ds.data(), depth ? R.ur.data() : nullptr, R.n, -1,
+                                 cam.bounds[0], cam.bounds[1], cam.bounds[2], cam.bounds[3]);
     R.n_last = R.n_local = 0;
     if (have_prev) {
-      q.from(P);
+      q.from(P, mbf);
+      const float *qur = depth ? q.ur.data() : q.u.data();
       std::fill(R.tb.begin(), R.tb.begin() + R.n, 0), std::fill(R.tm_last.begin(), R.tm_last.begin() + R.n, -1);
-      R.n_last = or_frame_search_by_projection_last(f, P.n, P.ds.data(), q.obs.data(), q.u.data(), q.v.data(), q.u.data(), nullptr,
+      R.n_last = or_frame_search_by_projection_last(f, P.n, P.ds.data(), q.obs.data(), q.u.data(), q.v.data(), qur, nullptr,
                                                     nullptr, q.oct.data(), q.ang.data(), 15.f, 0, 0, sf, 1, R.tb.data(),
                                                     R.tm_last.data());
       std::fill(R.tb.begin(), R.tb.begin() + R.n, 0), std::fill(R.tm_local.begin(), R.tm_local.begin() + R.n, -1);
-      R.n_local = or_frame_search_by_projection(f, P.n, P.ds.data(), q.obs.data(), q.obs.data(), q.u.data(), q.v.data(), q.u.data(),
+      R.n_local = or_frame_search_by_projection(f, P.n, P.ds.data(), q.obs.data(), q.obs.data(), q.u.data(), q.v.data(), qur,
                                                 q.oct.data(), q.vc.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, 0.8f,
                                                 sf, nullptr, nullptr, R.tb.data(), R.tm_local.data());
     }
@@ -534,19 +586,26 @@ static bool same_track(const TrackResult &a, const TrackResult &b) {
   return a.n == b.n && a.n_last == b.n_last && a.n_local == b.n_local && !memcmp(a.kp.data(), b.kp.data(), (size_t)a.n * 28) &&
          !memcmp(a.kpun.data(), b.kpun.data(), (size_t)a.n * 28) &&
          !memcmp(a.ds.data(), b.ds.data(), (size_t)a.n * 32) && !memcmp(a.tm_last.data(), b.tm_last.data(), (size_t)a.n * 4) &&
-         !memcmp(a.tm_local.data(), b.tm_local.data(), (size_t)a.n * 4);
+         !memcmp(a.tm_local.data(), b.tm_local.data(), (size_t)a.n * 4) && !memcmp(a.ur.data(), b.ur.data(), (size_t)a.n * 4) &&
+         !memcmp(a.dep.data(), b.dep.data(), (size_t)a.n * 4);
 }
 
-static std::string run_c5(double seconds) {
+// rgbd: the same streams as RGB-D Frames -- a seeded uint16 depth plane with holes per frame, pageable host memory as a
+// driver delivers it; the host side restates ComputeStereoFromRGBD and searches with mvuRight (key "C5_rgbd")
+static std::string run_c5(double seconds, bool rgbd = false) {
   const int T = 6;
   int ndev = vsg_device_count();
   CHECK(ndev > 0);
   std::vector<std::vector<std::vector<uint8_t>>> img(NSTREAM);
+  std::vector<std::vector<std::vector<uint16_t>>> depth(NSTREAM);
   for (int s = 0; s < NSTREAM; s++)
     for (int t = 0; t < T; t++) {
       img[s].emplace_back((size_t)W5 * H5);
       CHECK(vsg_synth_sequence_frame(W5, H5, 500 + s, t, 1, 6, img[s].back().data(), W5) == 0);
+      depth[s].emplace_back((size_t)W5 * H5);
+      seeded_depth(100 * s + t, W5, H5, depth[s].back().data());
     }
+  auto dp = [&](int s, int t) -> const uint16_t * { return rgbd ? depth[s][t % T].data() : nullptr; };
   std::vector<C5Gpu> g(NSTREAM);
   for (int s = 0; s < NSTREAM; s++) g[s].init(s % ndev);  // per-stream GPU pinning
   // ---- parity, every stream, every frame
@@ -560,8 +619,8 @@ static std::string run_c5(double seconds) {
       th.emplace_back([&, s] {
         C5Cpu c(g[s].cap);
         for (int t = 0; t < T; t++) {
-          g[s].frame(img[s][t].data(), t, t > 0);
-          c.frame(img[s][t].data(), t, t > 0);
+          g[s].frame(img[s][t].data(), t, t > 0, dp(s, t));
+          c.frame(img[s][t].data(), t, t > 0, dp(s, t));
           ok[s] &= same_track(g[s].res[t & 1], c.res[t & 1]);
           ml[s] += c.res[t & 1].n_last, mo[s] += c.res[t & 1].n_local, kk[s] += c.res[t & 1].n;
         }
@@ -578,7 +637,7 @@ static std::string run_c5(double seconds) {
       th.emplace_back([&, s] {
         int t = T;
         long n = 0;
-        while (now_ms() - t0 < seconds * 1e3) g[s].frame(img[s][t % T].data(), t, true), t++, n++;
+        while (now_ms() - t0 < seconds * 1e3) g[s].frame(img[s][t % T].data(), t, true, dp(s, t)), t++, n++;
         total += n;
       });
     for (auto &x : th) x.join();
@@ -596,7 +655,7 @@ static std::string run_c5(double seconds) {
         C5Cpu c(g[s].cap);
         int t = 0;
         long n = 0;
-        while (now_ms() - t0 < seconds * 1e3) c.frame(img[s][t % T].data(), t, t > 0), t++, n++;
+        while (now_ms() - t0 < seconds * 1e3) c.frame(img[s][t % T].data(), t, t > 0, dp(s, t)), t++, n++;
         total += n;
       });
     for (auto &x : th) x.join();
@@ -605,13 +664,18 @@ static std::string run_c5(double seconds) {
   char b[3072];
   snprintf(b, sizeof b,
            "{\"workload\": \"C5: %d concurrent 640x480 camera streams, nFeatures=1250, one extractor + one host thread per "
-           "stream, camera = %s: per frame vsg_orb_extract_to_frame (operator() -> UndistortKeyPoints on the device + resident frame, one wait) on the grid bounds "
+           "stream, camera = %s: per frame %s on the grid bounds "
            "(%.3f, %.3f, %.3f, %.3f) of ComputeImageBounds -> SearchByProjection(Cur, Last) -> SearchByProjection(F, local "
            "map points); stream s on device s mod %d\", \"unit\": \"frames/s\", \"frames_per_s\": %.1f, "
            "\"frames_per_s_one_stream\": %.1f, \"ms_per_frame_one_stream\": %.4f, \"streams\": %d, \"devices\": %d, "
            "\"parity\": %s, \"frames_checked\": %d, \"per_frame\": {\"keypoints\": %.1f, \"matches_last_frame\": %.1f, "
            "\"matches_local_map\": %.1f}, \"cpu_oracle\": {\"frames_per_s\": %.2f, \"threads\": %d, \"kind\": \"port\"}}",
-           NSTREAM, g[0].cam.name, g[0].cam.bounds[0], g[0].cam.bounds[1], g[0].cam.bounds[2], g[0].cam.bounds[3], ndev, fps4, fps1,
+           NSTREAM, g[0].cam.name,
+           rgbd ? "vsg_orb_extract_to_frame_rgbd (operator() -> UndistortKeyPoints on the device -> depth conversion + "
+                  "ComputeStereoFromRGBD from a 640x480 uint16 depth plane with 10 % holes in pageable memory, DepthMapFactor "
+                  "1000, bf = 0.0745 * fx -> resident frame with mvuRight, one wait); the searches apply their stereo gates"
+                : "vsg_orb_extract_to_frame (operator() -> UndistortKeyPoints on the device + resident frame, one wait)",
+           g[0].cam.bounds[0], g[0].cam.bounds[1], g[0].cam.bounds[2], g[0].cam.bounds[3], ndev, fps4, fps1,
            1e3 / fps1, NSTREAM, ndev, parity ? "true" : "false", NSTREAM * T,
            (double)kps / (NSTREAM * T), (double)m_last / (NSTREAM * (T - 1)), (double)m_local / (NSTREAM * (T - 1)), cpu_fps,
            NSTREAM);
@@ -739,6 +803,147 @@ static std::string run_latency(double seconds) {
   return b;
 }
 
+// frame_latency's one-frame chains (C1: TUM1 camera, 640x480 / 1000), gray-only against RGB-D in the same run: a seeded
+// uint16 depth plane with holes (TUM's PNG convention, depth = value / 5000; bf 40 = TUM1.yaml's Stereo.b * fx).  The front
+// end alone takes the depth from pageable memory (staged by the post-chain hook behind the extractor's kernels) and from
+// vsg_host_alloc memory (read in place); the tracking chain (front end -> SearchByProjection(Cur, Last) ->
+// SearchByProjection(F, local map points)) runs on the gray frame and on the RGB-D frame with its stereo gates active
+// (projected right coordinates from the previous frame's mvuRight).  Parity: every RGB-D call's mvuRight / mvDepth
+// against the host loop cpu_rgbd; the RGB-D tracking searches against the oracle's routines on a frame with mvuRight.
+static std::string run_rgbd_latency(double seconds) {
+  const int W = 640, H = 480, T = 6;
+  std::vector<std::vector<uint8_t>> img;
+  std::vector<std::vector<uint16_t>> dpage;
+  for (int t = 0; t < T; t++) {
+    img.emplace_back((size_t)W * H);
+    CHECK(vsg_synth_sequence_frame(W, H, 1000, t, 1, 6, img.back().data(), W) == 0);
+    dpage.emplace_back((size_t)W * H);
+    seeded_depth(t, W, H, dpage.back().data());
+  }
+  uint16_t *dpin = nullptr;
+  CHECK(vsg_host_alloc((size_t)T * W * H * 2, (void **)&dpin) == VSG_OK);
+  for (int t = 0; t < T; t++) memcpy(dpin + (size_t)t * W * H, dpage[t].data(), (size_t)W * H * 2);
+  vsg_orb *ex = nullptr;
+  CHECK(vsg_orb_create(1000, 1.2f, 8, 20, 7, 0, 1, &ex) == VSG_OK);
+  const int cap = vsg_orb_capacity(ex, H, W);
+  OrExtractor *oe = or_create(1000, 1.2f, 8, 20, 7);
+  float sf[8];
+  vsg_orb_get_tables(ex, sf, nullptr, nullptr, nullptr, nullptr, nullptr);
+  vsg_frame *F[2];
+  TrackResult R[2], O[2];
+  for (int i = 0; i < 2; i++) {
+    CHECK(vsg_frame_create(0, cap, &F[i]) == VSG_OK);
+    R[i].size_for(cap), O[i].size_for(cap);
+  }
+  Camera cam = cam_tum1();
+  cam.init(W, H);
+  const float scale = vsg_depth_map_scale(5000.0f), mbf = 40.0f;
+  Queries q;
+  // mode 0: gray front end; 1: RGB-D front end, pageable depth; 2: RGB-D front end, vsg_host_alloc depth;
+  // 3: gray tracking chain; 4: RGB-D tracking chain (pageable depth)
+  auto one = [&](int t, int mode) {
+    TrackResult &C = R[t & 1], &P = R[(t + 1) & 1];
+    const uint8_t *g = img[t % T].data();
+    const bool rgbd = mode == 1 || mode == 2 || mode == 4;
+    if (!rgbd) {
+      CHECK(vsg_orb_extract_to_frame(ex, g, H, W, W, 0, 0, C.kp.data(), C.ds.data(), cap, &C.n, F[t & 1], cam.K4, cam.dist,
+                                     cam.ndist, cam.bounds[0], cam.bounds[1], cam.bounds[2], cam.bounds[3], C.kpun.data()) >= 0);
+      std::fill(C.ur.begin(), C.ur.end(), -1.f);
+    } else {
+      const uint16_t *d = mode == 2 ? dpin + (size_t)(t % T) * W * H : dpage[t % T].data();
+      CHECK(vsg_orb_extract_to_frame_rgbd(ex, g, H, W, W, 0, 0, C.kp.data(), C.ds.data(), cap, &C.n, F[t & 1], cam.K4,
+                                          cam.dist, cam.ndist, cam.bounds[0], cam.bounds[1], cam.bounds[2], cam.bounds[3],
+                                          C.kpun.data(), d, VSG_DEPTH_U16, (size_t)W * 2, H, W, scale, mbf, C.ur.data(),
+                                          C.dep.data()) >= 0);
+    }
+    if (mode < 3 || P.n == 0) return;
+    q.from(P, mbf);
+    std::fill(C.tb.begin(), C.tb.begin() + C.n, 0), std::fill(C.tm_last.begin(), C.tm_last.begin() + C.n, -1);
+    C.n_last = vsg_frame_search_by_projection_last(F[t & 1], P.n, P.ds.data(), q.obs.data(), q.u.data(), q.v.data(),
+                                                   rgbd ? q.ur.data() : nullptr, nullptr, nullptr, q.oct.data(), q.ang.data(),
+                                                   15.f, 0, sf, 8, 1, C.tb.data(), C.tm_last.data());
+    std::fill(C.tb.begin(), C.tb.begin() + C.n, 0), std::fill(C.tm_local.begin(), C.tm_local.begin() + C.n, -1);
+    C.n_local = vsg_frame_search_by_projection(F[t & 1], P.n, P.ds.data(), q.obs.data(), q.obs.data(), q.u.data(), q.v.data(),
+                                               rgbd ? q.ur.data() : q.u.data(), q.oct.data(), q.vc.data(), nullptr, nullptr,
+                                               nullptr, nullptr, nullptr, 1.f, 0.8f, sf, 8, nullptr, nullptr, C.tb.data(),
+                                               C.tm_local.data());
+    CHECK(C.n_last >= 0 && C.n_local >= 0);
+  };
+  // the oracle's RGB-D chain (the host restatement of the depth step, the routines on a frame with mvuRight)
+  Queries qc;
+  auto cpu = [&](int t) {
+    TrackResult &C = O[t & 1], &P = O[(t + 1) & 1];
+    or_extract(oe, img[t % T].data(), H, W, W, 0, 0, (OrKeyPoint *)C.kp.data(), C.ds.data(), cap, &C.n);
+    or_undistort_keypoints((const OrKeyPoint *)C.kp.data(), C.n, cam.K4, cam.dist, cam.ndist, (OrKeyPoint *)C.kpun.data());
+    cpu_rgbd(dpage[t % T].data(), W, H, 1.f / 5000.f, mbf, C.kp.data(), C.kpun.data(), C.n, C.ur.data(), C.dep.data());
+    OrFrame *f = or_frame_create((const OrKeyPoint *)C.kpun.data(), C.ds.data(), C.ur.data(), C.n, -1, cam.bounds[0],
+                                 cam.bounds[1], cam.bounds[2], cam.bounds[3]);
+    C.n_last = C.n_local = 0;
+    if (P.n > 0) {
+      qc.from(P, mbf);
+      std::fill(C.tb.begin(), C.tb.begin() + C.n, 0), std::fill(C.tm_last.begin(), C.tm_last.begin() + C.n, -1);
+      C.n_last = or_frame_search_by_projection_last(f, P.n, P.ds.data(), qc.obs.data(), qc.u.data(), qc.v.data(), qc.ur.data(),
+                                                    nullptr, nullptr, qc.oct.data(), qc.ang.data(), 15.f, 0, 0, sf, 1,
+                                                    C.tb.data(), C.tm_last.data());
+      std::fill(C.tb.begin(), C.tb.begin() + C.n, 0), std::fill(C.tm_local.begin(), C.tm_local.begin() + C.n, -1);
+      C.n_local = or_frame_search_by_projection(f, P.n, P.ds.data(), qc.obs.data(), qc.obs.data(), qc.u.data(), qc.v.data(),
+                                                qc.ur.data(), qc.oct.data(), qc.vc.data(), nullptr, nullptr, nullptr, nullptr,
+                                                nullptr, 1.f, 0.8f, sf, nullptr, nullptr, C.tb.data(), C.tm_local.data());
+    }
+    or_frame_destroy(f);
+  };
+  bool parity = true;
+  for (int t = 0; t < 3 * T; t++) {  // the RGB-D tracking chain (pageable), then the front end from vsg_host_alloc depth
+    one(t, t < 2 * T ? 4 : 2);
+    if (t < 2 * T) {
+      cpu(t);
+      parity = parity && same_track(R[t & 1], O[t & 1]);
+    } else {
+      std::vector<float> ur(cap), dep(cap);
+      or_undistort_keypoints((const OrKeyPoint *)R[t & 1].kp.data(), R[t & 1].n, cam.K4, cam.dist, cam.ndist,
+                             (OrKeyPoint *)O[0].kpun.data());
+      cpu_rgbd(dpage[t % T].data(), W, H, 1.f / 5000.f, mbf, R[t & 1].kp.data(), O[0].kpun.data(), R[t & 1].n, ur.data(),
+               dep.data());
+      parity = parity && !memcmp(ur.data(), R[t & 1].ur.data(), (size_t)R[t & 1].n * 4) &&
+               !memcmp(dep.data(), R[t & 1].dep.data(), (size_t)R[t & 1].n * 4);
+    }
+  }
+  long m_last = 0, m_local = 0, gm_last = 0, gm_local = 0;
+  for (int t = 1; t <= 2 * T; t++) one(t, 4), m_last += R[t & 1].n_last, m_local += R[t & 1].n_local;
+  for (int t = 1; t <= 2 * T; t++) one(t, 3), gm_last += R[t & 1].n_last, gm_local += R[t & 1].n_local;
+  // interleaved rounds of 20 calls: every mode sees the same clocks and the same thermal state
+  double ms[5] = {0, 0, 0, 0, 0};
+  int cnt[5] = {0, 0, 0, 0, 0}, t = 0;
+  for (int w = 0; w < 20; w++) one(t++, w % 5);
+  const double t_end = now_ms() + seconds * 1000;
+  while (now_ms() < t_end)
+    for (int m = 0; m < 5; m++) {
+      one(t++, m);  // the previous frame of this round's first search comes from the same mode
+      const double t0 = now_ms();
+      for (int k = 0; k < 20; k++) one(t++, m);
+      ms[m] += now_ms() - t0, cnt[m] += 20;
+    }
+  for (int m = 0; m < 5; m++) ms[m] /= cnt[m];
+  char b[3072];
+  snprintf(b, sizeof b,
+           "{\"workload\": \"frame_latency's one-frame chains (TUM1 camera, 640x480 / 1000) per blocking call, gray-only "
+           "against RGB-D (vsg_orb_extract_to_frame_rgbd, 640x480 uint16 depth with 10 %% holes, depth = value / 5000, bf 40), "
+           "interleaved in one run; track chain = front end -> SearchByProjection(Cur, Last) -> SearchByProjection(F, local map "
+           "points), on the RGB-D frame with the stereo gates active\", \"gray_ms\": %.4f, \"rgbd_pageable_ms\": %.4f, "
+           "\"rgbd_host_alloc_ms\": %.4f, \"pageable_increment_ms\": %.4f, \"host_alloc_increment_ms\": %.4f, "
+           "\"track_chain_gray_ms\": %.4f, \"track_chain_rgbd_ms\": %.4f, \"track_chain_increment_ms\": %.4f, "
+           "\"per_frame\": {\"matches_last_frame_gray\": %.1f, \"matches_local_map_gray\": %.1f, \"matches_last_frame_rgbd\": %.1f, "
+           "\"matches_local_map_rgbd\": %.1f}, \"frames_per_mode\": %d, \"parity\": %s, \"frames_checked\": %d}",
+           ms[0], ms[1], ms[2], ms[1] - ms[0], ms[2] - ms[0], ms[3], ms[4], ms[4] - ms[3], (double)gm_last / (2 * T),
+           (double)gm_local / (2 * T), (double)m_last / (2 * T), (double)m_local / (2 * T), cnt[0], parity ? "true" : "false",
+           3 * T);
+  for (int i = 0; i < 2; i++) vsg_frame_destroy(F[i]);
+  vsg_orb_destroy(ex);
+  or_destroy(oe);
+  vsg_host_free(dpin);
+  return b;
+}
+
 // VSG_CRASH_MAPS=1: on SIGSEGV write the faulting address, the raw return addresses and /proc/self/maps to stderr (async-
 // signal-safe calls only), then die by the default action -- tells WHICH libraries the frames under a crash belong to
 // (profiles/r05_q_rocprofv3_kernel_trace_c5_segfault.txt: rocprofv3's own handler prints addresses without names).
@@ -775,10 +980,15 @@ int main(int argc, char **argv) {
   }
   const double seconds = argc > 1 ? atof(argv[1]) : 2.0;
   const int npipes = argc > 2 ? atoi(argv[2]) : 4;
-  const std::string only = argc > 3 ? argv[3] : "";  // "c5": that configuration alone (kernel traces of the four streams)
+  // "c5": that configuration alone (kernel traces of the four streams); "c5_rgbd": C5 as RGB-D Frames alone; "rgbd": the
+  // RGB-D A/B of the one-frame chains alone
+  const std::string only = argc > 3 ? argv[3] : "";
   const std::string c3 = only.empty() || only == "c3" ? run_c3(seconds, npipes) : "null";
   const std::string c5 = only.empty() || only == "c5" ? run_c5(seconds) : "null";
+  const std::string c5r = only.empty() || only == "c5_rgbd" ? run_c5(seconds, true) : "null";
   const std::string lat = only.empty() || only == "latency" ? run_latency(seconds) : "null";
-  printf("{\"C3\": %s, \"C5\": %s, \"frame_latency\": %s}\n", c3.c_str(), c5.c_str(), lat.c_str());
+  const std::string rgbd = only.empty() || only == "rgbd" ? run_rgbd_latency(seconds) : "null";
+  printf("{\"C3\": %s, \"C5\": %s, \"C5_rgbd\": %s, \"frame_latency\": %s, \"frame_latency_rgbd\": %s}\n", c3.c_str(),
+         c5.c_str(), c5r.c_str(), lat.c_str(), rgbd.c_str());
   return 0;
 }

@@ -49,6 +49,53 @@ struct WinLaunch {
   float inv_sigma2[16];
 };
 
+// ---- Tracking::GrabImageRGBD's depth conversion (Tracking.cc:1610-1611) + Frame::ComputeStereoFromRGBD (Frame.cc:1129-1150)
+// A depth plane as the device reads it.  base == nullptr: no RGB-D step.
+struct DepthPlane {
+  const uint8_t *base;
+  size_t stride;        // bytes per row
+  int type, rows, cols;  // VSG_DEPTH_U16 / VSG_DEPTH_F32
+  int convert;          // fabs(mDepthMapFactor - 1.0f) > 1e-5 || type != CV_32F: convertTo(CV_32F, scale)
+  float scale, mbf;
+};
+
+// d = imDepth.at<float>((int)kp.pt.y, (int)kp.pt.x) (kp = mvKeys[i], the DISTORTED keypoint); d > 0: {d, kpU.x - mbf / d},
+// otherwise {-1, -1}.  A truncated pixel outside the plane, or a NaN coordinate, is {-1, -1} (the reference reads out of
+// bounds there).  Float arithmetic, correctly rounded division, no contraction: convertTo's cvt_32f is x * scale + 0.
+__device__ __forceinline__ void rgbd_depth(const DepthPlane &P, float kx, float ky, float kux, float *depth, float *ur) {
+  float d = -1.0f, u = -1.0f;
+  if (kx > -1.0f && ky > -1.0f && kx < (float)P.cols && ky < (float)P.rows) {  // (NaN fails every comparison)
+    const uint8_t *row = P.base + (size_t)(int)ky * P.stride;
+    const int col = (int)kx;
+    float z = P.type == VSG_DEPTH_U16 ? (float)((const uint16_t *)row)[col] : ((const float *)row)[col];
+    if (P.convert) z = fmul(z, P.scale);
+    if (z > 0) d = z, u = fsub(kux, fdiv(P.mbf, z));
+  }
+  *depth = d, *ur = u;
+}
+
+// Batched form (vsg_rgbd_depth_batch_device): one thread per [frame][record] of the extractor's device outputs -- read the
+// record, undistort it (the source k_frame_grid_build runs), sample, write.  Writes are coalesced [nframes][capacity].
+__global__ __launch_bounds__(256) void k_rgbd_batch(const KeyPointPOD *__restrict__ kps, const int *__restrict__ counts,
+                                                    int capacity, int nframes, size_t frame_stride, DepthPlane P,
+                                                    CamModel cam, float *__restrict__ u_right,
+                                                    float *__restrict__ depth_out) {
+  const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= (size_t)nframes * capacity) return;
+  const int f = (int)(r / (size_t)capacity), i = (int)(r - (size_t)f * capacity);
+  float d = -1.0f, u = -1.0f;
+  if (i < counts[2 * f]) {
+    const KeyPointPOD kp = kps[r];
+    float ux = kp.x, uy;
+    if (cam.distorted) undistort_point(cam, kp.x, kp.y, &ux, &uy);
+    DepthPlane Pf = P;
+    Pf.base = P.base + (size_t)f * frame_stride;
+    rgbd_depth(Pf, kp.x, kp.y, ux, &d, &u);
+  }
+  u_right[r] = u;
+  depth_out[r] = d;
+}
+
 // ---- Frame::AssignFeaturesToGrid (Frame.cc:521-553) for keypoints [i0, i0 + n) -> CSR (cell_start, ent) with the
 // entries of every cell in ascending keypoint order (= the push_back order of the reference), index = i - i0.
 // One workgroup: per-cell counts by LDS atomics, one block scan, an unordered atomic append, then every cell's
@@ -61,7 +108,9 @@ __global__ __launch_bounds__(1024) void k_frame_grid_build(const KeyPointPOD *__
                                                             uint8_t *__restrict__ desc_copy,
                                                             int *__restrict__ zero_cells, CamModel cam,
                                                             KeyPointPOD *__restrict__ kps_un_host,
-                                                            const int *__restrict__ n_dev, int n_cap) {
+                                                            const int *__restrict__ n_dev, int n_cap, DepthPlane dp,
+                                                            float *__restrict__ uright, float *__restrict__ uright_host,
+                                                            float *__restrict__ depth_host) {
   // n_dev: the keypoint count where the extractor's chain left it ({n, monoIndex} of the frame) -- the launch that rides
   // behind operator()'s chain (vsg_orb_extract_to_frame) is enqueued before the host knows it
   if (n_dev) n = min(*n_dev, n_cap);
@@ -74,15 +123,28 @@ __global__ __launch_bounds__(1024) void k_frame_grid_build(const KeyPointPOD *__
   // Frame::UndistortKeyPoints (Frame.cc:891-921) on the way: with a distorted camera the frame's keypoints are mvKeysUn
   // -- every pt through cv::undistortPoints' five double-precision iterations (vsg_undistort.h) -- and the grid below is
   // built from THEM; the host's copy of mvKeysUn is written to pinned memory by the same threads
+  // An RGB-D frame (dp.base) samples its depth plane in the same loop: Frame::ComputeStereoFromRGBD (Frame.cc:1129-1150)
+  // reads the depth at mvKeys[i] and subtracts from mvKeysUn[i].x -- both are in hand here
   const bool undist = kps_copy && cam.distorted;
-  if (undist) {
+  if (undist || dp.base) {
     for (int i = tid; i < n; i += 1024) {
       KeyPointPOD kp = kps[i0 + i];
-      undistort_point(cam, kp.x, kp.y, &kp.x, &kp.y);
-      kps_copy[i] = kp;
-      if (kps_un_host) kps_un_host[i] = kp;
+      const float kx = kp.x, ky = kp.y;
+      if (undist) {
+        undistort_point(cam, kp.x, kp.y, &kp.x, &kp.y);
+        kps_copy[i] = kp;
+        if (kps_un_host) kps_un_host[i] = kp;
+      }
+      if (dp.base) {
+        float d, u;
+        rgbd_depth(dp, kx, ky, kp.x, &d, &u);
+        uright[i] = u;
+        if (uright_host) uright_host[i] = u;
+        if (depth_host) depth_host[i] = d;
+      }
     }
-  } else if (kps_copy) {
+  }
+  if (!undist && kps_copy) {
     for (int i = tid; i < n * 7; i += 1024) ((uint32_t *)kps_copy)[i] = ((const uint32_t *)(kps + i0))[i];
   }
   if (desc_copy)
@@ -658,7 +720,8 @@ static int frame_from_extractor(vsg_frame *f, vsg_orb *h, int index, const vsg_k
   if (v.done) F_TRY(hipStreamWaitEvent(c->stream, v.done, 0));
   hipLaunchKernelGGL(k_frame_grid_build, dim3(1), dim3(1024), 0, c->stream, v.d_kps, 0, n, f->minX, f->minY, f->invW,
                      f->invH, f->d_cell_start[0], f->d_ent[0], f->d_kps, v.d_desc, f->d_desc, f->d_cell_start[1], cam,
-                     un_dev, (const int *)nullptr, 0);
+                     un_dev, (const int *)nullptr, 0, DepthPlane(), (float *)nullptr, (float *)nullptr,
+                     (float *)nullptr);
   F_TRY(hipGetLastError());
   if (!cam.distorted) f->h_kps.assign(kps_host, kps_host + n);  // beside the kernel
   F_TRY(hipStreamSynchronize(c->stream));
@@ -683,41 +746,116 @@ int vsg_frame_from_extractor(vsg_frame *f, vsg_orb *h, int index, const vsg_keyp
 // reads the keypoint count from the device -- so the blocking call's single wait covers both, instead of
 // operator() [wait] -> vsg_frame_from_extractor* [launch, wait].
 namespace {
+// the depth plane of an RGB-D call as the caller passed it, and where the hook puts it when it has to be staged
+struct RgbdIn {
+  const uint8_t *src;
+  size_t stride, row_bytes;
+  DepthPlane plane;        // base = the device alias of pinned caller memory, or of the staging area
+  uint8_t *stage_host;     // non-null: copy the plane here (packed rows) before the launch
+  float *ur_dev, *ur_pin, *depth_pin;
+};
 struct ToFrameHook {
   vsg_frame *f;
   CamModel cam;
   KeyPointPOD *un_dev;
+  const RgbdIn *rgbd;  // nullptr: gray only
 };
 int to_frame_hook(void *ctx, hipStream_t s, const OrbOutputView &v) {
   const ToFrameHook *H = (const ToFrameHook *)ctx;
   vsg_frame *f = H->f;
+  DepthPlane dp = DepthPlane();
+  float *ur = nullptr, *ur_pin = nullptr, *depth_pin = nullptr;
+  if (const RgbdIn *R = H->rgbd) {
+    // pageable (or registered) depth is copied into the pinned arena HERE: the extractor's chain is already enqueued, so
+    // this copy runs while the device works through it instead of in front of it
+    if (R->stage_host)
+      for (int y = 0; y < R->plane.rows; y++)
+        memcpy(R->stage_host + (size_t)y * R->plane.stride, R->src + (size_t)y * R->stride, R->row_bytes);
+    dp = R->plane, ur = R->ur_dev, ur_pin = R->ur_pin, depth_pin = R->depth_pin;
+  }
   hipLaunchKernelGGL(k_frame_grid_build, dim3(1), dim3(1024), 0, s, v.d_kps, 0, 0, f->minX, f->minY, f->invW, f->invH,
                      f->d_cell_start[0], f->d_ent[0], f->d_kps, v.d_desc, f->d_desc, f->d_cell_start[1], H->cam, H->un_dev,
-                     v.d_counts, f->capacity);
+                     v.d_counts, f->capacity, dp, ur, ur_pin, depth_pin);
   return hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
 }
-}  // namespace
 
-int vsg_orb_extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols, int stride, int lap0, int lap1,
-                             vsg_keypoint *kps, uint8_t *desc, int capacity, int *n, vsg_frame *f, const float K4[4],
-                             const float *dist, int ndist, float min_x, float min_y, float max_x, float max_y,
-                             vsg_keypoint *keys_un_out) {
+void frame_clear(vsg_frame *f) {
+  f->n = 0, f->nleft = -1, f->has_uright = false, f->fv_valid = false;
+  f->h_kps.clear();
+}
+
+// the depth arguments of vsg_orb_extract_to_frame_rgbd / vsg_rgbd_depth_batch_device -> a DepthPlane without its base
+int depth_plane(int type, size_t stride, int rows, int cols, float scale, float mbf, DepthPlane *P) {
+  if (type != VSG_DEPTH_U16 && type != VSG_DEPTH_F32) return VSG_ERR_UNSUPPORTED;
+  const size_t elem = type == VSG_DEPTH_U16 ? 2 : 4;
+  if (rows < 1 || cols < 1 || stride < (size_t)cols * elem || stride % elem) return VSG_ERR_INVALID;
+  P->base = nullptr, P->stride = stride, P->type = type, P->rows = rows, P->cols = cols;
+  // if((fabs(mDepthMapFactor-1.0f)>1e-5) || imDepth.type()!=CV_32F)  (Tracking.cc:1610): float difference, double compare
+  P->convert = ((double)fabsf(scale - 1.0f) > 1e-5 || type != VSG_DEPTH_F32) ? 1 : 0;
+  P->scale = scale, P->mbf = mbf;
+  return VSG_OK;
+}
+
+struct RgbdArgs {
+  const void *depth;
+  int type;
+  size_t stride;
+  int rows, cols;
+  float scale, mbf;
+  float *u_right, *depth_out;
+};
+
+int extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols, int stride, int lap0, int lap1,
+                     vsg_keypoint *kps, uint8_t *desc, int capacity, int *n, vsg_frame *f, const float K4[4],
+                     const float *dist, int ndist, float min_x, float min_y, float max_x, float max_y,
+                     vsg_keypoint *keys_un_out, const RgbdArgs *A) {
   if (n) *n = 0;
   if (frame_check(f) != VSG_OK || !h || !kps || !desc || !n) return VSG_ERR_INVALID;
   // the hook launches on the extractor's stream with the frame's device pointers: one device for both
   if (vsg_orb_device_of(h) != f->device) return VSG_ERR_INVALID;
   ToFrameHook H;
-  H.f = f, H.un_dev = nullptr;
+  H.f = f, H.un_dev = nullptr, H.rgbd = nullptr;
   H.cam = CamModel();
   if (K4 && !make_cam_model(K4, dist, ndist, &H.cam)) return VSG_ERR_INVALID;
+  RgbdIn R = {};
+  if (!gray || rows <= 0 || cols <= 0) A = nullptr;  // operator() returns -1 for an empty image: nothing to sample
+  if (A) {
+    int rc = depth_plane(A->type, A->stride, A->rows, A->cols, A->scale, A->mbf, &R.plane);
+    if (rc == VSG_OK && (!A->depth || A->rows != rows || A->cols != cols || (uintptr_t)A->depth % (A->type == VSG_DEPTH_U16 ? 2 : 4)))
+      rc = VSG_ERR_INVALID;
+    if (rc != VSG_OK) {
+      frame_clear(f);
+      return rc;
+    }
+  }
   int rc = VSG_OK;
   ThreadCtx *c = thread_ctx(f->device, &rc);
   if (!c) return rc;
-  KeyPointPOD *un_pin = nullptr;
-  if (H.cam.distorted) {
-    rc = ctx_reserve(c, (size_t)(f->capacity + 1) * sizeof(KeyPointPOD), 0);
+  // the calling thread's pinned arena: [mvKeysUn | mvuRight | mvDepth | staged depth plane]
+  Stage st;
+  const size_t C1 = (size_t)f->capacity + 1;
+  const size_t oUn = st.add(H.cam.distorted ? C1 * sizeof(KeyPointPOD) : 0);
+  const size_t oUr = st.add(A ? C1 * 4 : 0), oDp = st.add(A ? C1 * 4 : 0);
+  void *alias = nullptr;
+  const size_t row_bytes = A ? (size_t)A->cols * (A->type == VSG_DEPTH_U16 ? 2 : 4) : 0;
+  const size_t span = A ? (size_t)(A->rows - 1) * A->stride + row_bytes : 0;
+  const bool direct = A && vsg_orb_host_direct(h, A->depth, span, &alias);
+  const size_t oPl = st.add(A && !direct ? (size_t)A->rows * row_bytes : 0);
+  if (st.total) {
+    rc = ctx_reserve(c, st.total, 0);
     if (rc != VSG_OK) return rc;
-    un_pin = (KeyPointPOD *)c->h_pin, H.un_dev = (KeyPointPOD *)c->d_pin;
+  }
+  KeyPointPOD *un_pin = nullptr;
+  if (H.cam.distorted) un_pin = (KeyPointPOD *)(c->h_pin + oUn), H.un_dev = (KeyPointPOD *)(c->d_pin + oUn);
+  if (A) {
+    R.src = (const uint8_t *)A->depth, R.stride = A->stride, R.row_bytes = row_bytes;
+    if (direct) {
+      R.plane.base = (const uint8_t *)alias;
+    } else {
+      R.stage_host = c->h_pin + oPl, R.plane.base = c->d_pin + oPl, R.plane.stride = row_bytes;
+    }
+    R.ur_dev = f->d_uright, R.ur_pin = (float *)(c->d_pin + oUr), R.depth_pin = (float *)(c->d_pin + oDp);
+    H.rgbd = &R;
   }
   set_bounds(f, min_x, min_y, max_x, max_y);
   vsg_orb_set_post_chain(h, to_frame_hook, &H);
@@ -726,11 +864,10 @@ int vsg_orb_extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols
   if (mono < 0 || *n > f->capacity) {
     // the bounds are already the new ones and the hook may have rewritten the device arrays: the frame holds nothing
     // searchable any more, and says so
-    f->n = 0, f->nleft = -1, f->has_uright = false, f->fv_valid = false;
-    f->h_kps.clear();
+    frame_clear(f);
     return mono < 0 ? mono : VSG_ERR_CAPACITY;
   }
-  f->n = *n, f->nleft = -1, f->has_uright = false, f->fv_valid = false;
+  f->n = *n, f->nleft = -1, f->has_uright = A != nullptr, f->fv_valid = false;
   if (H.cam.distorted) {
     f->h_kps.assign((const vsg_keypoint *)un_pin, (const vsg_keypoint *)un_pin + *n);
     if (keys_un_out && *n) memcpy(keys_un_out, un_pin, (size_t)*n * sizeof(vsg_keypoint));
@@ -738,7 +875,63 @@ int vsg_orb_extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols
     f->h_kps.assign(kps, kps + *n);
     if (keys_un_out && *n && keys_un_out != kps) memcpy(keys_un_out, kps, (size_t)*n * sizeof(vsg_keypoint));
   }
+  if (A && A->u_right && *n) memcpy(A->u_right, c->h_pin + oUr, (size_t)*n * 4);
+  if (A && A->depth_out && *n) memcpy(A->depth_out, c->h_pin + oDp, (size_t)*n * 4);
   return mono;
+}
+}  // namespace
+
+int vsg_orb_extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols, int stride, int lap0, int lap1,
+                             vsg_keypoint *kps, uint8_t *desc, int capacity, int *n, vsg_frame *f, const float K4[4],
+                             const float *dist, int ndist, float min_x, float min_y, float max_x, float max_y,
+                             vsg_keypoint *keys_un_out) {
+  return extract_to_frame(h, gray, rows, cols, stride, lap0, lap1, kps, desc, capacity, n, f, K4, dist, ndist, min_x,
+                          min_y, max_x, max_y, keys_un_out, nullptr);
+}
+
+int vsg_orb_extract_to_frame_rgbd(vsg_orb *h, const uint8_t *gray, int rows, int cols, int stride, int lap0, int lap1,
+                                  vsg_keypoint *kps, uint8_t *desc, int capacity, int *n, vsg_frame *f,
+                                  const float K4[4], const float *dist, int ndist, float min_x, float min_y, float max_x,
+                                  float max_y, vsg_keypoint *keys_un_out, const void *depth, int depth_type,
+                                  size_t depth_stride, int depth_rows, int depth_cols, float depth_scale, float mbf,
+                                  float *u_right, float *depth_out) {
+  const RgbdArgs A = {depth, depth_type, depth_stride, depth_rows, depth_cols, depth_scale, mbf, u_right, depth_out};
+  return extract_to_frame(h, gray, rows, cols, stride, lap0, lap1, kps, desc, capacity, n, f, K4, dist, ndist, min_x,
+                          min_y, max_x, max_y, keys_un_out, &A);
+}
+
+float vsg_depth_map_scale(float yaml_value) {
+  // mDepthMapFactor = fSettings["RGBD.DepthMapFactor"]; if(fabs(mDepthMapFactor)<1e-5) mDepthMapFactor=1;
+  // else mDepthMapFactor = 1.0f/mDepthMapFactor;  (Tracking.cc:638-642)
+  if ((double)fabsf(yaml_value) < 1e-5) return 1.0f;
+  return 1.0f / yaml_value;
+}
+
+int vsg_rgbd_depth_batch_device(int device, const void *d_depth, int depth_type, int nframes, size_t frame_stride,
+                                size_t depth_stride, int rows, int cols, float depth_scale, float mbf, const float K4[4],
+                                const float *dist, int ndist, const vsg_keypoint *d_kps, const int *d_counts,
+                                int capacity, float *d_u_right, float *d_depth_out, void *stream) {
+  DepthPlane P;
+  const int rc = depth_plane(depth_type, depth_stride, rows, cols, depth_scale, mbf, &P);
+  if (rc != VSG_OK) return rc;
+  const size_t elem = depth_type == VSG_DEPTH_U16 ? 2 : 4;
+  if (!d_depth || !d_kps || !d_counts || !d_u_right || !d_depth_out || nframes < 1 || capacity < 1 ||
+      (nframes > 1 && frame_stride < (size_t)(rows - 1) * depth_stride + (size_t)cols * elem) ||
+      frame_stride % elem || (uintptr_t)d_depth % elem)
+    return VSG_ERR_INVALID;
+  CamModel cam;
+  if (!make_cam_model(K4, dist, ndist, &cam)) return VSG_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
+  F_TRY(hipSetDevice(device));
+  P.base = (const uint8_t *)d_depth;
+  const size_t recs = (size_t)nframes * capacity;
+  // stream == NULL is the caller's NULL stream: the launch is ordered on both sides of it
+  hipLaunchKernelGGL(k_rgbd_batch, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const KeyPointPOD *)d_kps, d_counts, capacity, nframes, frame_stride, P, cam, d_u_right,
+                     d_depth_out);
+  F_TRY(hipGetLastError());
+  return VSG_OK;
 }
 
 int vsg_camera_image_bounds(int cols, int rows, const float K4[4], const float *dist, int ndist, float out[4]) {

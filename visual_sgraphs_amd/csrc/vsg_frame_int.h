@@ -139,6 +139,9 @@ struct OrbOutputView {
 
 int vsg_orb_output_view(vsg_orb *h, int index, vsg::OrbOutputView *v);
 int vsg_orb_device_of(const vsg_orb *h);  // the device the handle lives on
+// May the device read [p, p + bytes) of caller host memory in place on behalf of h?  The image path's fail-closed
+// classification (vsg_orb.hip, "caller host memory the device may touch IN PLACE"); *dev_alias = the device address.
+bool vsg_orb_host_direct(const vsg_orb *h, const void *p, size_t bytes, void **dev_alias);
 // Work a blocking extract call enqueues on the handle's stream BEHIND its stage chain and in front of the completion event
 // the call waits for (vsg_orb_extract_to_frame: the resident frame's grid launch rides in operator()'s one wait).  The
 // hook is consumed by the next submit; `v` = frame 0 of that call's outputs.

@@ -1548,6 +1548,10 @@ void vsg_orb_set_post_chain(vsg_orb *h, vsg_post_chain_fn fn, void *ctx) {
 
 int vsg_orb_device_of(const vsg_orb *h) { return h ? h->device : -1; }
 
+bool vsg_orb_host_direct(const vsg_orb *h, const void *p, size_t bytes, void **dev_alias) {
+  return h && host_direct(h, p, bytes, dev_alias);
+}
+
 int vsg_orb_output_view(vsg_orb *h, int index, OrbOutputView *v) {
   if (!h || !v || !h->have_last || index < 0 || index >= h->last_frames) return VSG_ERR_INVALID;
   v->d_kps = h->last_kps + (size_t)index * h->last_cap;

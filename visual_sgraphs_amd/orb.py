@@ -63,6 +63,8 @@ EXPORTS = [
     # round 4
     "vsg_orb_set_pyramid_tiling", "vsg_shard_rank", "vsg_camera_image_bounds", "vsg_frame_from_extractor_undistort",
     "vsg_orb_extract_to_frame",
+    # RGB-D frames: Tracking::GrabImageRGBD's depth conversion + Frame::ComputeStereoFromRGBD
+    "vsg_orb_extract_to_frame_rgbd", "vsg_depth_map_scale", "vsg_rgbd_depth_batch_device",
     # round 5
     "vsg_host_kind", "vsg_orb_set_direct_registered",
     # TemplatedVocabulary::score and the device-resident KeyFrameDatabase
@@ -241,6 +243,12 @@ def load_library():
     L.vsg_camera_image_bounds.argtypes = [ci, ci, _f32p, _f32p, ci, _f32p]
     L.vsg_orb_extract_to_frame.argtypes = [vp, _u8p, ci, ci, ci, ci, ci, vp, _u8p, ci, _i32p, vp, _f32p, _f32p, ci, cf, cf,
                                            cf, cf, vp]
+    L.vsg_orb_extract_to_frame_rgbd.argtypes = [vp, _u8p, ci, ci, ci, ci, ci, vp, _u8p, ci, _i32p, vp, _f32p, _f32p, ci,
+                                                cf, cf, cf, cf, vp, vp, ci, C.c_size_t, ci, ci, cf, cf, _f32p, _f32p]
+    L.vsg_depth_map_scale.argtypes = [cf]
+    L.vsg_depth_map_scale.restype = cf
+    L.vsg_rgbd_depth_batch_device.argtypes = [ci, vp, ci, ci, C.c_size_t, C.c_size_t, ci, ci, cf, cf, _f32p, _f32p, ci,
+                                              vp, vp, ci, vp, vp, vp]
     L.vsg_frame_size.argtypes = [vp]
     L.vsg_frame_copy_grid.argtypes = [vp, ci, _i32p, _i32p]
     L.vsg_frame_features_in_area.argtypes = [vp, _f32p, _f32p, _f32p, _i32p, _i32p, ci, ci, _i32p, _i32p, ci]
@@ -1077,6 +1085,52 @@ def _opt(a, t, conv):
     return (None, None) if a is None else (lambda x: (x, _p(x, t)))(conv(a))
 
 
+VSG_DEPTH_U16, VSG_DEPTH_F32 = 0, 1
+
+
+def depth_map_scale(yaml_value):
+    """Tracking's mDepthMapFactor from RGBD.DepthMapFactor (Tracking.cc:638-642): 1 when |yaml| < 1e-5, else 1.0f / yaml."""
+    return load_library().vsg_depth_map_scale(float(np.float32(yaml_value)))
+
+
+def _depth_type(dtype):
+    """VSG_DEPTH_* of a numpy / torch element type; anything else is passed as -1 (the library answers
+    VSG_ERR_UNSUPPORTED)."""
+    name = str(dtype).replace("torch.", "")
+    return {"uint16": VSG_DEPTH_U16, "float32": VSG_DEPTH_F32}.get(name, -1)
+
+
+def _depth_view(depth):
+    """(pointer, VSG_DEPTH_*, rows, cols, row stride in bytes, owner) of a depth plane without copying it: the library
+    classifies the memory itself (pinned memory is read in place).  None -> a NULL plane."""
+    if depth is None:
+        return 0, VSG_DEPTH_U16, 0, 0, 0, None
+    if hasattr(depth, "data_ptr"):  # torch tensor: host memory only (pinned or not)
+        if depth.device.type != "cpu":
+            raise ValueError(f"depth must be in host memory, not on {depth.device} (device planes: rgbd_depth_batch_device)")
+        if depth.dim() != 2 or depth.stride(1) != 1:
+            raise ValueError("depth must be a 2-D tensor with contiguous rows")
+        return depth.data_ptr(), _depth_type(depth.dtype), depth.shape[0], depth.shape[1], \
+            depth.stride(0) * depth.element_size(), depth
+    a = np.asarray(depth)
+    if a.ndim != 2 or a.strides[1] != a.itemsize or a.strides[0] < 0:
+        a = np.ascontiguousarray(a)
+    return a.ctypes.data, _depth_type(a.dtype), a.shape[0], a.shape[1], a.strides[0], a
+
+
+def rgbd_depth_batch_device(d_depth, depth_type, nframes, frame_stride, depth_stride, rows, cols, depth_scale, mbf, K4,
+                            dist, d_kps, d_counts, capacity, d_u_right, d_depth_out, stream=None, device=0):
+    """vsg_rgbd_depth_batch_device on raw device pointers (ints / torch .data_ptr()): mvuRight / mvDepth
+    [nframes][capacity] of the records vsg_orb_extract_batch_device wrote; asynchronous on `stream`."""
+    k4 = _f32(np.asarray(K4))
+    d = _f32(np.asarray(dist)) if dist is not None else None
+    _check(load_library().vsg_rgbd_depth_batch_device(
+        int(device), C.c_void_p(d_depth), int(depth_type), int(nframes), int(frame_stride), int(depth_stride), int(rows),
+        int(cols), float(depth_scale), float(mbf), _p(k4, _f32p), _p(d, _f32p) if d is not None else None,
+        len(d) if d is not None else 0, C.c_void_p(d_kps), C.c_void_p(d_counts), int(capacity), C.c_void_p(d_u_right),
+        C.c_void_p(d_depth_out), C.c_void_p(stream) if stream else None), "vsg_rgbd_depth_batch_device")
+
+
 class Frame:
     """What the searches read of a VS_GRAPHS::Frame / KeyFrame, resident on the device (include/vsg_orb.h: vsg_frame):
     mvKeysUn (or mvKeys || mvKeysRight with Nleft), mDescriptors, mvuRight, mGrid / mGridRight (Frame.h:280-290)."""
@@ -1156,6 +1210,32 @@ class Frame:
             un.ctypes.data_as(C.c_void_p)), "vsg_orb_extract_to_frame")
         self.kps, self.nleft = un[:n.value].copy(), -1
         return mono, kps[:n.value].copy(), desc[:n.value].copy()
+
+    def extract_into_rgbd(self, ex, image, depth, bounds, K4, dist, depth_scale, mbf, vLappingArea=(0, 0)):
+        """RGB-D Frame front end in one call and one wait (vsg_orb_extract_to_frame_rgbd): operator() ->
+        UndistortKeyPoints -> GrabImageRGBD's depth conversion + ComputeStereoFromRGBD -> AssignFeaturesToGrid.
+        depth: [rows, cols] uint16 or float32 (numpy -- pageable or a PinnedArray's .a -- or a CPU torch tensor; row
+        strides may be padded); depth_scale = mDepthMapFactor (depth_map_scale); K4 / dist may be None (no distortion).
+        Returns (monoIndex, mvKeys, descriptors, mvuRight, mvDepth); self.kps = mvKeysUn."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = img.shape
+        ptr, dtype, drows, dcols, dstride, keep = _depth_view(depth)
+        cap = ex.capacity(rows, cols)
+        kps, desc, un = np.zeros(cap, KP_DTYPE), np.zeros((cap, 32), np.uint8), np.zeros(cap, KP_DTYPE)
+        ur, dep = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        n = C.c_int32(0)
+        k4 = _f32(np.asarray(K4)) if K4 is not None else None
+        d = _f32(np.asarray(dist)) if dist is not None else None
+        mono = _check(self._L.vsg_orb_extract_to_frame_rgbd(
+            ex.handle, _p(img, _u8p), rows, cols, img.strides[0], int(vLappingArea[0]), int(vLappingArea[1]),
+            kps.ctypes.data_as(C.c_void_p), _p(desc, _u8p), cap, C.byref(n), self._h, _p(k4, _f32p) if k4 is not None else None,
+            _p(d, _f32p) if d is not None else None, len(d) if d is not None else 0, *[float(b) for b in bounds],
+            un.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), dtype, dstride, drows, dcols, float(depth_scale), float(mbf),
+            _p(ur, _f32p), _p(dep, _f32p)), "vsg_orb_extract_to_frame_rgbd")
+        del keep
+        k = n.value
+        self.kps, self.nleft = un[:k].copy(), -1
+        return mono, kps[:k].copy(), desc[:k].copy(), ur[:k].copy(), dep[:k].copy()
 
     def grid(self, right=False):
         cs, en = np.zeros(64 * 48 + 1, np.int32), np.zeros(max(self.N, 1), np.int32)
