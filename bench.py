@@ -8,9 +8,12 @@ match of every frame against its predecessor (the inner search of ORBmatcher::Se
 With N > 1 ranks (torchrun) every rank processes its own `--batch` frames per step (frame sharding, weak
 scaling) and the keypoint/descriptor records are exchanged with one RCCL all-gather per step.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel by ALGORITHMIC bytes over
-its HIP-event duration; `cpu_baseline` is the CPU oracle (a port of the reference algorithm, not the
-reference binary) timed on this box's host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run does what the headline figure needs and no more: set up, ramp and warm up,
+time the K steps, write `--dump-outputs`, print the line.  `--full` adds everything else after the timed steps: a
+serialized pass of the same steps for the per-kernel durations, whose `roofline` prices the dominant kernel by
+ALGORITHMIC bytes over its HIP-event duration; the `parity` gate of every frame and match row against the
+CPU oracle; `cpu_baseline`, the CPU oracle (a port of the reference algorithm, not the reference binary) timed on the
+host's cores on a bounded sample; and the legs outside the timed region (tools/bench_extras.py).
 """
 import argparse
 import json
@@ -98,10 +101,15 @@ def main():
     ap.add_argument("--sync-gather", action="store_true",
                     help="make every step wait for its own all-gather (default: the exchange of batch k overlaps the "
                          "kernels of batch k+1, two record buffers in flight)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="budget per CPU baseline leg (0 = skip)")
-    ap.add_argument("--no-stage-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the serialized per-kernel pass (roofline), the parity gate "
+                         "against the CPU oracle, the CPU baselines and the legs outside the timed region; off: the "
+                         "headline figure only")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: budget per CPU baseline leg (0 = skip)")
+    ap.add_argument("--no-stage-timing", action="store_true",
+                    help="no HIP events around the dominant kernel in the timed region, and with --full no serialized pass")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the legs outside the timed region (host API, matcher latency, C4 rate)")
+                    help="--full: skip the legs outside the timed region (host API, matcher latency, C4 rate)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) for real runs; gloo for dry runs")
     ap.add_argument("--torch-gather", action="store_true",
                     help="exchange the records through torch.distributed instead of the library's own RCCL communicator")
@@ -428,9 +436,9 @@ def main():
                  "input": in_state["last"], "steps_done": steps_done}
     # Per-kernel durations for the roofline: the same K steps once more with every kernel on ONE stream, so a
     # kernel's HIP-event span is its own duration (in the timed region the blur runs beside FAST/octree and the
-    # spans stretch each other).  Not part of `value`.
+    # spans stretch each other).  Not part of `value`: --full only.
     stage_ms = {}
-    if not args.no_stage_timing:
+    if args.full and not args.no_stage_timing:
         ex.set_serialize(True)
         ex.enable_timing(True)
         for _ in range(K):
@@ -443,10 +451,10 @@ def main():
 
     # Parity gate on rank 0: EVERY frame and EVERY match row of the last timed step's batch against the CPU oracle, bit for
     # bit (the oracle runs on all host threads; the reference's contract is per frame, Frame.cc:555-563); then the same for
-    # the last step of the serialized pass (the other launch forms).
+    # the last step of the serialized pass (the other launch forms).  --full only.
     n_kp = float(timed_out["set"][2][1:, 0].float().mean().item())
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import oracle_lib as ol
         chk = BatchOracle(frames, nfeat, cap)
 
@@ -608,7 +616,7 @@ def main():
 
     cpu = None
     extra = {}
-    if args.cpu_seconds > 0 and world > 1:
+    if args.full and args.cpu_seconds > 0 and world > 1:
         # N > 1 lines carry the same baseline on a short budget (rank 0's host, one thread; the other ranks are done)
         sample = [frames[i] for i in range(min(B, 16))]
         budget = min(3.0, args.cpu_seconds)
@@ -616,7 +624,7 @@ def main():
         cpu = {"value": round(v1, 2), "unit": "frames/s", "cores": 1, "kind": "port",
                "sample": f"{n1} frames of the same {W}x{H}/{nfeat} workload, extract + brute-force match, "
                          f"{budget:.0f} s on rank 0's host, CPU oracle (port of the reference algorithm)"}
-    if args.cpu_seconds > 0 and world == 1:
+    if args.full and args.cpu_seconds > 0 and world == 1:
         sample = [frames[i] for i in range(min(B, 16))]
         v1, n1 = cpu_baseline(W, H, nfeat, sample, args.cpu_seconds, 1)
         cpu = {"value": round(v1, 2), "unit": "frames/s", "cores": 1, "kind": "port",
@@ -660,7 +668,8 @@ def main():
                    "keypoints_per_frame": round(n_kp, 1),
                    "content": ("rectangles (synth.sequence_frame: rectangles + uniform noise, translated per frame); the other "
                                "nine generated classes and three real photographs: `content_sweep`, the natural-image stand-ins "
-                               "also as `value_value_noise` / `value_defocus`, the slowest photograph as `value_photo`")
+                               "also as `value_value_noise` / `value_defocus`, the slowest photograph as `value_photo` "
+                               "(--full)")
                    if args.content == "rectangles" else
                    f"{args.content} (synth.content_frame, --content: NOT the content `value` is quoted on)",
                    "clock_ramp": f"{max(args.ramp_steps, 0)} untimed steps before the {Wu} warm-up steps (the GPU reaches its "
@@ -668,11 +677,11 @@ def main():
                    "inputs": "resident in HBM" + (": two batches (the frames in forward / reverse order) alternate from step to "
                                                   "step" if rotate else "")},
         **({"outputs_dumped": dumped} if dumped else {}),
-        "parity": parity,
-        "roofline": roofline, "cpu_baseline": cpu,
+        "full": args.full,
+        **({"parity": parity, "roofline": roofline, "cpu_baseline": cpu} if args.full else {}),
     }
     out.update(extra)
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # claims the driver cannot otherwise see (host API, matcher latency, the other BASELINE configurations, the content
         # sweep incl. real photographs, single-frame latency), each behind a short budget, all OUTSIDE the timed region:
         # tools/bench_extras.py

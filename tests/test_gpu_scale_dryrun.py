@@ -20,7 +20,7 @@ def test_two_ranks_on_one_device(exchange):
     port = 29500 + random.randrange(2000)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--one-device",
+           "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--one-device", "--full",
            "--dist-backend", "gloo", "--exchange", exchange, "--batch", "16", "--steps", "3", "--warmup", "3",
            "--cpu-seconds", "1", "--no-stage-timing"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
@@ -38,7 +38,7 @@ def test_four_ranks_on_one_device():
     all-gather is 4 wide, rank 0's boundary predecessor is rank 3 of the previous step."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--one-device", "--dist-backend", "gloo", "--batch", "8",
-           "--steps", "3", "--warmup", "2", "--ramp-steps", "2", "--cpu-seconds", "1", "--no-stage-timing"]
+           "--full", "--steps", "3", "--warmup", "2", "--ramp-steps", "2", "--cpu-seconds", "1", "--no-stage-timing"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-1500:]
     d = json.loads([x for x in r.stdout.strip().splitlines() if x.startswith("{")][-1])
@@ -66,7 +66,7 @@ def test_gpus_flag_starts_the_ranks_itself():
     touches the GPU and relays rank 0's line (VERDICT r3 #3: --gpus used to be parsed and never read)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--one-device", "--dist-backend", "gloo", "--exchange",
-           "boundary", "--batch", "16", "--steps", "3", "--warmup", "2", "--ramp-steps", "2", "--cpu-seconds", "1",
+           "boundary", "--full", "--batch", "16", "--steps", "3", "--warmup", "2", "--ramp-steps", "2", "--cpu-seconds", "1",
            "--no-stage-timing"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-1500:]

@@ -3,7 +3,7 @@
 # must be compared inside ONE gpurun call).  The variant is loaded through the VSG_LIB override of
 # visual_sgraphs_amd/orb.py: the in-tree library is never touched.  "cur" = the in-tree build.
 # Usage on the GPU box: tools/ab_lib.sh "<bench args>" name1 name2 ...
-args="$1"; shift
+args="--full $1"; shift  # the lines are read for roofline.stage_ms and parity
 mkdir -p gpurun_out
 for v in "$@"; do
   if [ "$v" = cur ]; then unset VSG_LIB; else export VSG_LIB="$PWD/tools/_bin/libvsg_$v.so"; fi

@@ -1,6 +1,6 @@
 #!/bin/bash
 # In-run A/B of cells per FAST workgroup (VSG_FAST_K; 0 = the launcher's own choice): tools/abk.sh "<bench args>" K1 K2 ...
-args="$1"; shift
+args="--full $1"; shift  # the lines are read for roofline.stage_ms and parity
 for k in "$@"; do
   for rep in 1 2; do
     VSG_FAST_K=$k python bench.py --cpu-seconds 0 --no-extras $args 2>>gpurun_out/ab.err | python -c "

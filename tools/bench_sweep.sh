@@ -1,5 +1,5 @@
 # workload sweep + PCIe-inclusive host-API rate (numbers for DESIGN.md section 8)
-run() { python bench.py --cpu-seconds 0 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(d['config']['workload'][:2], 'fps', d['value'], 'ms/step', d['ms_per_step'], 'parity', d['parity']['bit_exact_vs_oracle'], 'kp', d['config']['keypoints_per_frame'], 'dom', r['kernel'], r['achieved'], r['stage_ms'])"; }
+run() { python bench.py --full --cpu-seconds 0 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(d['config']['workload'][:2], 'fps', d['value'], 'ms/step', d['ms_per_step'], 'parity', d['parity']['bit_exact_vs_oracle'], 'kp', d['config']['keypoints_per_frame'], 'dom', r['kernel'], r['achieved'], r['stage_ms'])"; }
 run --workload C2
 run --workload C3
 run --workload C4 --batch 128

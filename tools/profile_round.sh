@@ -90,7 +90,7 @@ python3 tools/pmc_summary.py $OUT/c3_pmc_fetch $OUT/c3_pmc_write $OUT/c3_pmc_sq 
 # traffic file whose source hash is the hash of the sources it runs on): the copies under profiles/ on this box are scratch
 cp $OUT/traffic.json profiles/traffic_r06.json
 python3 tools/isa_mix.py > $OUT/isa_mix.json 2>> $OUT/rocprof.err && cp $OUT/isa_mix.json profiles/r06_isa_mix.json
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_abi -- tools/_bin/abi_latency 300 > $OUT/abi_latency.json 2>> $OUT/rocprof.err
 cp $OUT/stats_abi/*/*kernel_stats.csv $OUT/abi_kernel_stats.csv 2>/dev/null
 tools/_bin/config_chain 2 4 > $OUT/config_chain.json 2>> $OUT/rocprof.err

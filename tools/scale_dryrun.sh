@@ -8,7 +8,7 @@ rc=0
 for ex in allgather boundary; do
   port=$((29500 + RANDOM % 2000))
   out=$(python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $port \
-        bench.py --gpus 2 --one-device --dist-backend gloo --exchange $ex --batch 32 --steps 4 --warmup 3 \
+        bench.py --gpus 2 --full --one-device --dist-backend gloo --exchange $ex --batch 32 --steps 4 --warmup 3 \
         --cpu-seconds 1 --no-stage-timing "$@" 2>gpurun_out/scale_dryrun_$ex.err | tail -1)
   echo "$out" | python -c "
 import json, sys
