@@ -603,8 +603,11 @@ int vsg_frame_search_for_initialization(vsg_frame *f1, vsg_frame *f2, const floa
 /* SearchByBoW(KeyFrame*, Frame&) / (KeyFrame*, KeyFrame*) (ORBmatcher.cc:226-428, 758-900) on resident descriptors:
  * only the FeatureVectors and the validity flags go up.  Same outputs as vsg_search_by_bow_kf_f_stereo / _kf_kf.
  * With ALL FeatureVector arrays NULL the FeatureVectors both frames keep resident since their vsg_frame_bow_transform
- * (Frame::mFeatVec; frames of at most 2048 features) are joined on the device and only the flags go up;
- * VSG_ERR_INVALID when either frame never had its ComputeBoW since its features were last written. */
+ * (Frame::mFeatVec, any number of features) are joined on the device and only the flags go up.  An empty frame, or a
+ * ComputeBoW with an empty vocabulary, gives 0 matches and every output -1, as in the reference; otherwise
+ * VSG_ERR_INVALID when either frame never had its ComputeBoW since its features were last written (nothing is left
+ * running on the calling thread's stream when this or any other error is returned).  The flag and match arrays of an empty
+ * frame may be NULL. */
 int vsg_frame_search_by_bow_kf_f(vsg_frame *kf, const uint8_t *kf_valid, const int32_t *kf_node_id,
                                  const int32_t *kf_off, const int32_t *kf_idx, int kf_nodes, vsg_frame *f,
                                  const int32_t *f_node_id, const int32_t *f_off, const int32_t *f_idx, int f_nodes,
@@ -636,7 +639,10 @@ int vsg_frame_stereo_matches(vsg_orb *hl, int frame_l, vsg_orb *hr, int frame_r,
  * frames shares a stream round trip instead of paying three.  Arguments as vsg_frame_stereo_matches (fl / fr = the resident
  * left / right eye; *n_stereo = matches kept by the median cut), vsg_frame_bow_transform (of fl; its FeatureVector also
  * stays resident in fl) and vsg_frame_search_by_bow_kf_f with NULL FeatureVector arrays (kf = a frame whose own ComputeBoW
- * ran earlier; kf == NULL: no search, match_f / n_match are not touched).  Results are those of the three blocking calls. */
+ * ran earlier; kf == NULL: no search, match_f / n_match are not touched).  Results are those of the three blocking calls.
+ * A kf with features that never had its ComputeBoW is refused (VSG_ERR_INVALID) before anything is enqueued; an error after
+ * the first enqueue waits for the stream before it returns.  An fl of more than 2048 features has its FeatureVector
+ * assembled on the host after the wait and the search follows behind a second wait; smaller frames take exactly one. */
 int vsg_frame_stereo_bow_search(vsg_orb *hl, int frame_l, vsg_orb *hr, int frame_r, vsg_frame *fl, vsg_frame *fr, float mb,
                                 float mbf, float *u_right, float *depth, int *n_stereo, vsg_vocab *voc, int levelsup,
                                 int32_t *bow_ids, double *bow_vals, int bow_cap, int *n_bow, int32_t *fv_node,

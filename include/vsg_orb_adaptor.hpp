@@ -780,8 +780,9 @@ class ResidentMatcher {
     check(rc, "vsg_frame_search_by_bow_kf_f");
     return rc;
   }
-  // The same two with the FeatureVectors both frames keep resident since their ComputeBoW (ORBVocabulary::ComputeBoW):
-  // the join runs on the device, only the "has a map point" flags go up
+  // The same two with the FeatureVectors both frames keep resident since their ComputeBoW (ORBVocabulary::ComputeBoW), of
+  // any number of features: the join runs on the device, only the "has a map point" flags go up.  An empty frame gives 0
+  // matches; a non-empty frame whose features changed after its last ComputeBoW is refused (check() throws)
   int SearchByBoW(ResidentFrame &pKF, const uint8_t *kfValid, ResidentFrame &F, std::vector<int32_t> &matchF) const {
     matchF.assign(F.N(), -1);
     int rc = vsg_frame_search_by_bow_kf_f(pKF.handle(), kfValid, nullptr, nullptr, nullptr, 0, F.handle(), nullptr, nullptr,

@@ -2,6 +2,7 @@
 // -> vsg::ORBextractor -> vsg::FrameGrid -> vsg::ORBmatcher::SearchWindow / SearchByBoW (with vsg::ORBVocabulary).
 // Every output is dumped to a flat binary file that tests/test_gpu_adaptor.py compares with the CPU oracle.
 //   usage: adaptor_check <vocab.bin> <out.bin>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -131,8 +132,67 @@ int main(int argc, char **argv) {
       }
     }
 
+    // the NULL-FeatureVector overloads on frames of more than 2048 features (FeatureVector assembled on the host, then copied
+    // into the frame) and on an empty frame: equal to the host-array overloads here, to the oracle in the Python test
+    const int NB = 3000;
+    std::vector<vsg_keypoint> gk[2] = {std::vector<vsg_keypoint>(NB), std::vector<vsg_keypoint>(NB)};
+    std::vector<uint8_t> gd[2] = {std::vector<uint8_t>(NB * 32), std::vector<uint8_t>(NB * 32)};
+    std::vector<int32_t> gMatchF, gMatch12;
+    int ngF = 0, ngKK = 0, neF = 0, neKF = 0, neKK = 0;
+    {
+      uint64_t s = 0x9E3779B97F4A7C15ull;
+      auto rnd = [&]() {
+        s ^= s << 13, s ^= s >> 7, s ^= s << 17;
+        return s;
+      };
+      for (int i = 0; i < NB; ++i) {
+        for (int b = 0; b < 32; ++b) gd[0][i * 32 + b] = (uint8_t)rnd();
+        gk[0][i] = vsg_keypoint{(float)(rnd() % 640), (float)(rnd() % 480), 31.f, (float)(rnd() % 3600) * 0.1f, 1.f, i % 8, -1};
+      }
+      for (int i = 0; i < NB; ++i) {  // the Frame: feature (7 i) mod NB of the KeyFrame with up to 8 bits flipped, turned 20 deg
+        const int j = (int)((7ull * i) % NB);
+        std::copy(gd[0].begin() + j * 32, gd[0].begin() + j * 32 + 32, gd[1].begin() + i * 32);
+        for (int r = (int)(rnd() % 9); r > 0; --r) {
+          const int bit = (int)(rnd() % 256);
+          gd[1][i * 32 + bit / 8] ^= (uint8_t)(1u << (bit % 8));
+        }
+        gk[1][i] = gk[0][j];
+        gk[1][i].angle = std::fmod(gk[0][j].angle + 20.f, 360.f);
+      }
+      vsg::ResidentFrame G0(NB), G1(NB), E(1);
+      G0.Upload(gk[0].data(), gd[0].data(), nullptr, NB, -1, 0.f, 0.f, (float)W, (float)H);
+      G1.Upload(gk[1].data(), gd[1].data(), nullptr, NB, -1, 0.f, 0.f, (float)W, (float)H);
+      E.Upload(nullptr, nullptr, nullptr, 0, -1, 0.f, 0.f, (float)W, (float)H);
+      std::map<unsigned, double> gbow[3];
+      vsg::FeatureVectorCSR gfv[3];
+      voc.ComputeBoW(G0.handle(), gbow[0], gfv[0], 2);
+      voc.ComputeBoW(G1.handle(), gbow[1], gfv[1], 2);
+      voc.ComputeBoW(E.handle(), gbow[2], gfv[2], 2);
+      std::vector<uint8_t> gv0(NB, 1), gv1(NB, 1);
+      for (int i = 0; i < NB; i += 4) gv0[i] = 0;
+      for (int i = 0; i < NB; i += 9) gv1[i] = 0;
+      std::vector<int32_t> hF, hKK, eF, eKF, eKK;
+      const int nhF = rm.SearchByBoW(G0, gv0.data(), gfv[0], G1, gfv[1], hF);
+      const int nhKK = rm.SearchByBoW(G0, gv0.data(), gfv[0], G1, gv1.data(), gfv[1], hKK);
+      ngF = rm.SearchByBoW(G0, gv0.data(), G1, gMatchF);
+      ngKK = rm.SearchByBoW(G0, gv0.data(), G1, gv1.data(), gMatch12);
+      if (ngF != nhF || gMatchF != hF || ngKK != nhKK || gMatch12 != hKK) {
+        printf("resident SearchByBoW above 2048 features differs from the host-array form (%d vs %d, %d vs %d)\n", ngF, nhF,
+               ngKK, nhKK);
+        return 4;
+      }
+      neF = rm.SearchByBoW(G0, gv0.data(), E, eF);                 // empty Frame
+      neKF = rm.SearchByBoW(E, gv0.data(), G1, eKF);               // empty KeyFrame
+      neKK = rm.SearchByBoW(E, gv0.data(), G1, gv1.data(), eKK);  // empty KF1
+      if (gfv[2].nodes() != 0 || !eF.empty() || !eKK.empty() || eKF != std::vector<int32_t>(NB, -1)) {
+        printf("resident SearchByBoW with an empty frame left outputs\n");
+        return 4;
+      }
+    }
+
     std::ofstream f(argv[2], std::ios::binary);
-    std::vector<int32_t> head{mono[0], mono[1], nwin, nbow, ninit, d01, ntri, nlast, nsim3, nfuse, nrinit};
+    std::vector<int32_t> head{mono[0], mono[1], nwin, nbow, ninit, d01, ntri, nlast, nsim3, nfuse, nrinit, ngF, ngKK,
+                              neF, neKF, neKK};
     dump(f, head);
     for (int t = 0; t < 2; ++t) dump(f, kps[t]), dump(f, desc[t]);
     dump(f, cand.off), dump(f, cand.idx), dump(f, bestIdx), dump(f, bestDist), dump(f, trainMatch), dump(f, matchF);
@@ -143,6 +203,8 @@ int main(int argc, char **argv) {
     dump(f, bow_ids), dump(f, bow_vals);
     dump(f, tri_flat);
     dump(f, rLast), dump(f, rSim3), dump(f, rFuseIdx), dump(f, rFuseDist), dump(f, rInit);
+    for (int t = 0; t < 2; ++t) dump(f, gk[t]), dump(f, gd[t]);
+    dump(f, gMatchF), dump(f, gMatch12);
     printf("OK %zu %zu win=%d bow=%d init=%d\n", kps[0].size(), kps[1].size(), nwin, nbow, ninit);
     return 0;
   } catch (const std::exception &e) {

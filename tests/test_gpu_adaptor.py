@@ -35,6 +35,11 @@ def _read(path):
     out["tri"] = take(np.int32).reshape(-1, 2)
     for k in ("r_last", "r_sim3", "r_fuse_idx", "r_fuse_dist", "r_init"):
         out[k] = take(np.int32)
+    for t in range(2):
+        out[f"big_kps{t}"] = take(orb.KP_DTYPE)
+        out[f"big_desc{t}"] = take(np.uint8).reshape(-1, 32)
+    for k in ("big_match_f", "big_match12"):
+        out[k] = take(np.int32)
     assert pos == len(raw)
     return out
 
@@ -133,3 +138,16 @@ def test_cpp_adaptor_end_to_end_equals_oracle(tmp_path):
     assert np.array_equal(got["r_fuse_idx"], r[1]) and np.array_equal(got["r_fuse_dist"], r[2])
     ni2, mi = o0.search_for_initialization(o1, k0["x"], k0["y"], 100, 0.7, True)
     assert int(got["head"][10]) == ni2 > 50 and np.array_equal(got["r_init"], mi)
+
+    # NULL-FeatureVector SearchByBoW above 2048 features (host-assembled FeatureVectors in the frames) and with empty frames
+    gk0, gd0, gk1, gd1 = got["big_kps0"], got["big_desc0"], got["big_kps1"], got["big_desc1"]
+    assert len(gd0) == len(gd1) == 3000
+    g0, g1 = voc.transform(gd0, 2)["fv"], voc.transform(gd1, 2)["fv"]
+    gv0, gv1 = np.ones(3000, np.uint8), np.ones(3000, np.uint8)
+    gv0[::4] = 0
+    gv1[::9] = 0
+    nb, mf = ol.search_by_bow_kf_f(gd0, gk0["angle"], gv0, g0, gd1, gk1["angle"], g1, 0.7, True)
+    assert int(got["head"][11]) == nb > 300 and np.array_equal(got["big_match_f"], mf)
+    nk, m12 = ol.search_by_bow_kf_kf(gd0, gk0["angle"], gv0, g0, gd1, gk1["angle"], gv1, g1, 0.7, True)
+    assert int(got["head"][12]) == nk > 300 and np.array_equal(got["big_match12"], m12)
+    assert got["head"][13:16].tolist() == [0, 0, 0]

@@ -462,8 +462,18 @@ void bow_sizes(int n, bool host_desc, size_t *pin_bytes, size_t *dev_bytes) {
 int bow_enqueue(BowCall *b, vsg_vocab *voc, const uint8_t *desc, const uint8_t *d_desc, int n, int levelsup,
                 vsg_frame *resident, ThreadCtx *c, size_t pin_base, size_t dev_base) {
   b->voc = voc, b->n = n, b->c = c, b->pin_base = pin_base, b->active = false, b->device_assembly = false;
-  if (resident) resident->fv_valid = false;
-  if (n == 0 || voc->nnodes <= 1) return VSG_OK;  // empty() vocabulary: v and fv stay empty (:1147-1150)
+  b->uploaded = false;
+  b->resident = resident && resident->capacity >= n ? resident : nullptr;
+  if (resident) resident->fv_valid = false, resident->fv_empty = false;
+  if (n == 0 || voc->nnodes <= 1) {  // empty() vocabulary: v and fv stay empty (:1147-1150)
+    if (b->resident) b->resident->fv_valid = true, b->resident->fv_empty = true;  // a searchable FeatureVector of no node
+    return VSG_OK;
+  }
+  {  // the joins of the SearchByBoW kernels launch one workgroup per POSSIBLE node of the FeatureVector's level
+    long bound = 1;
+    for (int l = 0; l < voc->L - levelsup && bound < n; l++) bound *= voc->max_children;
+    b->fv_bound = (int)(bound < n ? bound : n);
+  }
   Stage p, d;
   const size_t N = (size_t)n;
   const size_t oD = p.add(d_desc ? 0 : 32 * N);
@@ -495,22 +505,16 @@ int bow_enqueue(BowCall *b, vsg_vocab *voc, const uint8_t *desc, const uint8_t *
     BowOut o;
     o.hdr = (int *)(dp + b->oHdr), o.bow_ids = (int *)(dp + b->oBowId), o.bow_vals = (double *)(dp + b->oBowVal);
     o.fv_node = (int *)(dp + b->oFvNode), o.fv_off = (int *)(dp + b->oFvOff), o.fv_idx = (int *)(dp + b->oFvIdx);
-    const bool res = resident && resident->capacity >= n;
-    o.r_hdr = res ? resident->d_fv_hdr : nullptr, o.r_fv_node = res ? resident->d_fv_node : nullptr;
-    o.r_fv_off = res ? resident->d_fv_off : nullptr, o.r_fv_idx = res ? resident->d_fv_idx : nullptr;
+    vsg_frame *res = b->resident;
+    o.r_hdr = res ? res->d_fv_hdr : nullptr, o.r_fv_node = res ? res->d_fv_node : nullptr;
+    o.r_fv_off = res ? res->d_fv_off : nullptr, o.r_fv_idx = res ? res->d_fv_idx : nullptr;
     const int tf = voc->weighting == 0 || voc->weighting == 1;  // TF_IDF, TF: addWeight; IDF, BINARY: addIfNotExist
     uint64_t *s_sw = (uint64_t *)(dv + dSortW), *s_sn = (uint64_t *)(dv + dSortN);
     hipLaunchKernelGGL(k_bow_rank, dim3((n + 63) / 64), dim3(kAsmThreads), 0, c->stream, s_word, s_node, s_w, n, s_sw, s_sn);
     B_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bow_assemble, dim3(2), dim3(kAsmThreads), 0, c->stream, s_sw, s_sn, s_w, n, tf, o);
     B_TRY(hipGetLastError());
-    if (res) {
-      // the joins of the SearchByBoW kernels launch one wavefront per POSSIBLE node of the FeatureVector's level
-      long bound = 1;
-      for (int l = 0; l < voc->L - levelsup && bound < n; l++) bound *= voc->max_children;
-      resident->fv_bound = (int)(bound < n ? bound : n);
-      resident->fv_valid = true;
-    }
+    if (res) res->fv_bound = b->fv_bound, res->fv_valid = true;
   }
   return VSG_OK;
 }
@@ -544,7 +548,37 @@ int bow_finish(BowCall *b, int32_t *bow_ids, double *bow_vals, int bow_cap, int 
     }
     return (nb > bow_cap || nf > fv_cap) ? VSG_ERR_CAPACITY : VSG_OK;
   }
-  return bow_assemble_host(b->voc, n, word, node, w, bow_ids, bow_vals, bow_cap, n_bow, fv_node, fv_off, fv_idx, fv_cap, n_fv);
+  vsg_frame *res = b->resident;
+  if (!res)
+    return bow_assemble_host(b->voc, n, word, node, w, bow_ids, bow_vals, bow_cap, n_bow, fv_node, fv_off, fv_idx, fv_cap,
+                             n_fv);
+  // Frame::mFeatVec of more than kAsmMax features: assembled into the arena's FeatureVector blocks (room for n nodes), handed
+  // out from there, and copied up into the frame's resident arrays (capacity + 1 entries) behind the work already on the
+  // stream.  The caller waits for the stream before the arena is written again (b->uploaded).
+  uint8_t *hw = b->c->h_pin + b->pin_base;
+  int *pn = (int *)(hw + b->oFvNode), *po = (int *)(hw + b->oFvOff), *pi = (int *)(hw + b->oFvIdx), *hdr = (int *)(hw + b->oHdr);
+  po[0] = 0;
+  int nf = 0;
+  const int rc = bow_assemble_host(b->voc, n, word, node, w, bow_ids, bow_vals, bow_cap, n_bow, pn, po, pi, n, &nf);
+  *n_fv = nf;
+  if (fv_node && fv_idx) {  // as many nodes as the caller has room for (the host assembly's partial fill)
+    const int k = nf < fv_cap ? nf : fv_cap;
+    memcpy(fv_node, pn, 4 * (size_t)k);
+    memcpy(fv_off + 1, po + 1, 4 * (size_t)k);
+    memcpy(fv_idx, pi, 4 * (size_t)po[k]);
+  }
+  const int m = po[nf];
+  hdr[0] = nf, hdr[1] = m;
+  hipStream_t s = b->c->stream;
+  b->uploaded = true;
+  if (hipMemcpyAsync(res->d_fv_hdr, hdr, 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(res->d_fv_node, pn, 4 * (size_t)nf, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(res->d_fv_off, po, 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(res->d_fv_idx, pi, 4 * (size_t)m, hipMemcpyHostToDevice, s) != hipSuccess)
+    return VSG_ERR_HIP;
+  res->fv_bound = b->fv_bound, res->fv_valid = true;
+  if (rc != VSG_OK) return rc;
+  return nf > fv_cap ? VSG_ERR_CAPACITY : VSG_OK;
 }
 
 }  // namespace vsg
@@ -565,10 +599,15 @@ static int bow_transform(vsg_vocab *voc, const uint8_t *desc, vsg_frame *f, int 
   if (rc != VSG_OK) return rc;
   vsg::BowCall b;
   rc = vsg::bow_enqueue(&b, voc, desc, f ? f->d_desc : nullptr, n, levelsup, f, c, 0, 0);
-  if (rc != VSG_OK) return rc;
+  if (rc != VSG_OK) {
+    hipStreamSynchronize(c->stream);  // nothing this call launched outlives it (the next call rewrites the arena)
+    return rc;
+  }
   if (b.active) B_TRY(hipStreamSynchronize(c->stream));
-  return vsg::bow_finish(&b, bow_ids, bow_vals, bow_cap, n_bow, fv_node, fv_off, fv_idx, fv_cap, n_fv, word_of, node_of,
-                         weight_of);
+  rc = vsg::bow_finish(&b, bow_ids, bow_vals, bow_cap, n_bow, fv_node, fv_off, fv_idx, fv_cap, n_fv, word_of, node_of,
+                       weight_of);
+  if (b.uploaded) B_TRY(hipStreamSynchronize(c->stream));  // the host-assembled FeatureVector's copies read the arena
+  return rc;
 }
 
 

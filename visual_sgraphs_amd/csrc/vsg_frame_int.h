@@ -36,10 +36,12 @@ struct vsg_frame {
   int *d_cell_start[2] = {nullptr, nullptr};  // [0] mGrid, [1] mGridRight: CSR over cells ix * 48 + iy
   vsg::GridEnt *d_ent[2] = {nullptr, nullptr};
   std::vector<vsg_keypoint> h_kps;  // host mirror (angle / octave for the ordered host passes)
-  // Frame::mFeatVec (Frame.h:196), resident since round 6: written by the assembly kernel of ComputeBoW (vsg_bow.hip), joined
-  // with another frame's by the SearchByBoW kernels without a host round trip.  hdr = {nodes, features listed}
+  // Frame::mFeatVec (Frame.h:196), resident since round 6: written by the assembly kernel of ComputeBoW (vsg_bow.hip), or for
+  // frames of more than kAsmMax features copied up after the host assembly; joined with another frame's by the SearchByBoW
+  // kernels without a host round trip.  hdr = {nodes, features listed}
   int *d_fv_hdr = nullptr, *d_fv_node = nullptr, *d_fv_off = nullptr, *d_fv_idx = nullptr;
   bool fv_valid = false;  // a ComputeBoW of the CURRENT features has been enqueued on the owning thread's stream
+  bool fv_empty = false;  // ... and it left no node (no features, or an empty() vocabulary): the device copy is not written
   int fv_bound = 0;       // upper bound of the FeatureVector's node count (what the join kernels launch for)
 };
 
@@ -102,8 +104,10 @@ struct WindowCall {
 struct BowCall {
   vsg_vocab *voc = nullptr;
   ThreadCtx *c = nullptr;
-  int n = 0;
+  vsg_frame *resident = nullptr;  // the frame whose FeatureVector this call writes (nullptr: none)
+  int n = 0, fv_bound = 0;
   bool active = false, device_assembly = false;
+  bool uploaded = false;  // finish() enqueued copies of a host-assembled FeatureVector: wait for the stream before the arena is reused
   size_t pin_base = 0, oW = 0, oWord = 0, oNode = 0, oHdr = 0, oBowId = 0, oBowVal = 0, oFvNode = 0, oFvOff = 0, oFvIdx = 0;
 };
 void bow_sizes(int n, bool host_desc, size_t *pin_bytes, size_t *dev_bytes);

@@ -740,8 +740,10 @@ int bow_search_enqueue(BowSearchCall *s, int mode, vsg_frame *A, const uint8_t *
                        float nnratio, ThreadCtx *c, size_t pin_base, size_t dev_base) {
   s->c = c, s->mode = mode, s->A = A, s->B = B, s->active = false, s->pin_base = pin_base;
   s->nOut = mode == 0 ? B->n : A->n;
-  if (!A->fv_valid || !B->fv_valid) return VSG_ERR_INVALID;  // ComputeBoW first (Frame.cc:882-889)
+  // an empty frame has an empty FeatureVector whatever ComputeBoW left: no shared node, 0 matches (ORBmatcher.cc:247)
   if (A->n == 0 || B->n == 0) return VSG_OK;
+  if (!A->fv_valid || !B->fv_valid) return VSG_ERR_INVALID;  // ComputeBoW first (Frame.cc:882-889)
+  if (A->fv_empty || B->fv_empty) return VSG_OK;             // ComputeBoW with an empty() vocabulary left no node
   const int nA = A->n, nB = B->n;
   Stage p;
   const size_t oVA = p.add((size_t)nA), oVB = p.add(mode == 1 ? (size_t)nB : 0);
@@ -786,7 +788,10 @@ static int search_by_bow_resident(int mode, vsg_frame *A, const uint8_t *validA,
   if (rc != VSG_OK) return rc;
   vsg::BowSearchCall s;
   rc = vsg::bow_search_enqueue(&s, mode, A, validA, B, validB, nnratio, c, 0, 0);
-  if (rc != VSG_OK) return rc;
+  if (rc != VSG_OK) {
+    hipStreamSynchronize(c->stream);  // nothing this call launched outlives it (the next call rewrites the arena)
+    return rc;
+  }
   if (s.active) M_TRY(hipStreamSynchronize(c->stream));
   return vsg::bow_search_finish(&s, check_orientation, out);
 }
@@ -988,7 +993,8 @@ int vsg_frame_search_by_bow_kf_f(vsg_frame *kf, const uint8_t *kf_valid, const i
                                  const int32_t *kf_off, const int32_t *kf_idx, int kf_nodes, vsg_frame *f,
                                  const int32_t *f_node_id, const int32_t *f_off, const int32_t *f_idx, int f_nodes,
                                  float nnratio, int check_orientation, int32_t *match_f) {
-  if (!kf || !f || !match_f || kf->device != f->device || !kf_valid) return VSG_ERR_INVALID;
+  // an empty frame's arrays may be NULL (std::vector::data() of an empty vector)
+  if (!kf || !f || (!match_f && f->n > 0) || kf->device != f->device || (!kf_valid && kf->n > 0)) return VSG_ERR_INVALID;
   if (!kf_node_id && !f_node_id)  // both FeatureVectors resident (ComputeBoW ran on both frames): nothing goes up but the flags
     return search_by_bow_resident(0, kf, kf_valid, f, nullptr, nnratio, check_orientation, match_f);
   if (!kf_node_id || !f_node_id || !kf_off || !f_off || !kf_idx || !f_idx) return VSG_ERR_INVALID;
@@ -1002,7 +1008,9 @@ int vsg_frame_search_by_bow_kf_kf(vsg_frame *kf1, const uint8_t *valid1, const i
                                   const int32_t *idx1, int nodes1, vsg_frame *kf2, const uint8_t *valid2,
                                   const int32_t *node_id2, const int32_t *off2, const int32_t *idx2, int nodes2,
                                   float nnratio, int check_orientation, int32_t *matches12) {
-  if (!kf1 || !kf2 || !matches12 || kf1->device != kf2->device || !valid1 || !valid2) return VSG_ERR_INVALID;
+  if (!kf1 || !kf2 || (!matches12 && kf1->n > 0) || kf1->device != kf2->device || (!valid1 && kf1->n > 0) ||
+      (!valid2 && kf2->n > 0))
+    return VSG_ERR_INVALID;
   if (!node_id1 && !node_id2) return search_by_bow_resident(1, kf1, valid1, kf2, valid2, nnratio, check_orientation, matches12);
   if (!node_id1 || !node_id2 || !off1 || !off2 || !idx1 || !idx2) return VSG_ERR_INVALID;
   const vsg_keypoint *ka = kf1->h_kps.data(), *kb = kf2->h_kps.data();

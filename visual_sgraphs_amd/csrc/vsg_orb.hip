@@ -1694,27 +1694,40 @@ int vsg_frame_stereo_bow_search(vsg_orb *hl, int frame_l, vsg_orb *hr, int frame
   const size_t pin_stereo = (12 * (size_t)n_l + 127) & ~(size_t)63;
   rc = ctx_reserve(c, pin_stereo + pinB + pinS, devB + devS);
   if (rc != VSG_OK) return rc;
+  // everything that can refuse is checked before the first enqueue: an error return leaves no work in flight
+  if (kf && kf->n > 0 && n_l > 0 && !kf->fv_valid) return VSG_ERR_INVALID;  // the KeyFrame never had its ComputeBoW
+  auto fail = [&](int e) {  // an error after an enqueue: the kernels still write the arena and fl -- wait for them first
+    hipStreamSynchronize(c->stream);
+    return e;
+  };
   const bool do_stereo = n_l > 0 && n_r > 0;
   if (do_stereo) {
     rc = stereo_enqueue(hl, frame_l, hr, frame_r, fl->d_kps, fl->d_desc, n_l, fr->d_kps, fr->d_desc, n_r, mb, mbf, c, 0);
-    if (rc != VSG_OK) return rc;
+    if (rc != VSG_OK) return fail(rc);
   }
   vsg::BowCall b;
   rc = vsg::bow_enqueue(&b, voc, nullptr, fl->d_desc, n_l, levelsup, fl, c, pin_stereo, 0);
-  if (rc != VSG_OK) return rc;
+  if (rc != VSG_OK) return fail(rc);
+  // fl's FeatureVector is resident once the assembly kernel has run (or it is empty): the search queues up behind it.  A frame
+  // of more than kAsmMax features is assembled on the host after the wait; its search follows behind a second one.
   vsg::BowSearchCall sc;
-  const bool do_search = kf != nullptr && kf->fv_valid && fl->fv_valid;
-  if (kf && !do_search && kf->n > 0 && n_l > 0 && b.active) return VSG_ERR_INVALID;  // the KeyFrame never had its ComputeBoW
-  if (do_search) {
+  const bool search_now = kf != nullptr && fl->fv_valid;
+  if (search_now) {
     rc = vsg::bow_search_enqueue(&sc, 0, kf, kf_valid, fl, nullptr, nnratio, c, pin_stereo + pinB, devB);
-    if (rc != VSG_OK) return rc;
+    if (rc != VSG_OK) return fail(rc);
   }
   HIP_TRY(hipStreamSynchronize(c->stream));  // the ONE wait
   if (do_stereo) *n_stereo = stereo_finish(c, 0, n_l, u_right, depth);
   rc = vsg::bow_finish(&b, bow_ids, bow_vals, bow_cap, n_bow, fv_node, fv_off, fv_idx, fv_cap, n_fv, nullptr, nullptr, nullptr);
+  if (rc != VSG_OK && rc != VSG_ERR_CAPACITY) return b.uploaded ? fail(rc) : rc;
+  if (kf && !search_now) {  // behind the copies of the host-assembled FeatureVector (bow_finish)
+    const int rs = vsg::bow_search_enqueue(&sc, 0, kf, kf_valid, fl, nullptr, nnratio, c, pin_stereo + pinB, devB);
+    if (rs != VSG_OK) return fail(rs);
+  }
+  if (b.uploaded) HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait (more than kAsmMax features only)
   if (kf) {
     for (int i = 0; i < n_l; i++) match_f[i] = -1;
-    if (do_search) *n_match = vsg::bow_search_finish(&sc, check_orientation, match_f);
+    if (sc.active) *n_match = vsg::bow_search_finish(&sc, check_orientation, match_f);
   }
   return rc;
 }
