@@ -521,6 +521,68 @@ int vsg_frame_search_by_projection(vsg_frame *F, int n_mp, const uint8_t *mp_des
                                    const float *scale_factors, int nlevels, const int32_t *left_to_right,
                                    const int32_t *right_to_left, uint8_t *train_blocked, int32_t *train_match);
 
+/* ---- The local map's MapPoints, resident on the device: what Frame::isInFrustum (Frame.cc:656-719) and
+ * SearchByProjection(F, vpMapPoints) (ORBmatcher.cc:42-216) read of a MapPoint.  Slots 0 .. capacity-1 are the caller's
+ * own index of a MapPoint*.  Per slot: world_pos[3] = GetWorldPos(), normal[3] = GetNormal(), min_dist / max_dist = the
+ * MEMBERS mfMinDistance / mfMaxDistance (MapPoint.h; set at MapPoint.cc:106-107, 509-510), not the scaled values of
+ * GetMinDistanceInvariance() / GetMaxDistanceInvariance(): isInFrustum compares with 0.8f * mfMinDistance and
+ * 1.2f * mfMaxDistance (the library applies the getters' factors, MapPoint.cc:521-531) but PredictScale divides the
+ * unscaled mfMaxDistance (MapPoint.cc:555), and 1.2f * x cannot be undone exactly.  desc[32] = GetDescriptor(),
+ * observed = Observations() > 0.  A new store is
+ * all zeros.  update and read run on the calling thread's stream and return when the device copy is written / read, so
+ * a search that another thread starts afterwards sees the update; an update must not run WHILE another thread's call
+ * reads the same store (the reference holds mMutexPos / mMutexFeatures for that). */
+typedef struct vsg_mappoints vsg_mappoints;
+int vsg_mappoints_create(int device, int capacity, vsg_mappoints **out);
+void vsg_mappoints_destroy(vsg_mappoints *mp);
+int vsg_mappoints_capacity(const vsg_mappoints *mp);
+/* SetWorldPos / AddObservation / ComputeDistinctiveDescriptors / UpdateNormalAndDepth of n slots (MapPoint.cc:116,
+ * 141, 340, 440): entry i of every non-NULL field array goes to slot slots[i]; a NULL field keeps what the slots
+ * hold.  A slot listed more than once takes its LAST entry.  A slot outside [0, capacity): VSG_ERR_INVALID and nothing
+ * is written.  One scatter kernel, no copy per field. */
+int vsg_mappoints_update(vsg_mappoints *mp, int n, const int32_t *slots, const float *world_pos, const float *normal,
+                         const float *min_dist, const float *max_dist, const uint8_t *desc, const uint8_t *observed);
+/* test / debug read-back of n slots (any out pointer may be NULL) */
+int vsg_mappoints_read(vsg_mappoints *mp, int n, const int32_t *slots, float *world_pos, float *normal, float *min_dist,
+                       float *max_dist, uint8_t *desc, uint8_t *observed);
+
+/* The camera of one Frame as isInFrustum uses it (Frame.h:203-204, 316-318; set by Frame::UpdatePoseMatrices,
+ * Frame.cc:612-619): Rcw = mRcw row-major, tcw = mtcw, Ow = mOw (passed, not derived: the reference stores it),
+ * fx, fy, cx, cy = Pinhole::mvParameters, mbf, log_scale_factor = mfLogScaleFactor, n_levels = mnScaleLevels.  The image
+ * bounds mnMinX .. mnMaxY are the vsg_frame's own. */
+typedef struct vsg_frame_pose {
+  float Rcw[9], tcw[3], Ow[3];
+  float fx, fy, cx, cy, mbf, log_scale_factor;
+  int32_t n_levels;
+} vsg_frame_pose;
+
+/* bool Frame::isInFrustum(MapPoint *pMP, float viewingCosLimit) (Frame.h:130, Frame.cc:656-719: the Nleft == -1 branch
+ * with Pinhole::project, Pinhole.cpp:46-53, and MapPoint::PredictScale, MapPoint.cc:550-565) for the n map points in
+ * slots[i] (slots == NULL: slots 0 .. n-1).  Outs (any may be NULL): in_view = the return value = mbTrackInView,
+ * proj_x / proj_y = mTrackProjX / Y (-1 for a point rejected before Frame.cc:684, u / v after), and for in-view points
+ * proj_xr = mTrackProjXR, depth = mTrackDepth, scale_level = mnTrackScaleLevel, view_cos = mTrackViewCos (unspecified
+ * for the others).  Float arithmetic in a fixed order, one rounding per operation, glibc's logf.
+ * A frame with Nleft != -1 (isInFrustumChecks on a KannalaBrandt8 pair, Frame.cc:721-800): VSG_ERR_UNSUPPORTED. */
+int vsg_frame_is_in_frustum(vsg_frame *F, vsg_mappoints *mp, int n, const int32_t *slots, const vsg_frame_pose *pose,
+                            float viewing_cos_limit, uint8_t *in_view, float *proj_x, float *proj_y, float *proj_xr,
+                            float *depth, int32_t *scale_level, float *view_cos);
+
+/* void Tracking::SearchLocalPoints() (Tracking.cc:3423-3495), its second loop (:3446-3466) and the
+ * SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th, bFarPoints, thFarPoints) it ends with (ORBmatcher.cc:42-143),
+ * in one enqueue and one wait.  Map point i = slot slots[i] (NULL: slot i).  skip[i] != 0 (NULL: none) = the point
+ * is never projected (mnLastFrameSeen == mCurrentFrame.mnId || isBad(), :3450-3453); its mbTrackInView is false.
+ * viewing_cos_limit = 0.5 at :3455.  th, nnratio, scale_factors, nlevels, train_blocked, train_match and the return
+ * value are those of vsg_frame_search_by_projection; far_points / th_far_points = bFarPoints / thFarPoints
+ * (ORBmatcher.cc:53-54: an in-view point with mTrackDepth > thFarPoints is not searched).  pose->n_levels <= nlevels <= 16.
+ * Optional outs: in_view[i], proj_x[i], proj_y[i] as above (what mmProjectPoints takes, :3462-3465), *n_to_match =
+ * nToMatch (:3460).  The reference searches only when nToMatch > 0; with none in view nothing matches here either.
+ * Nleft != -1: VSG_ERR_UNSUPPORTED. */
+int vsg_frame_search_local_points(vsg_frame *F, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                                  const vsg_frame_pose *pose, float viewing_cos_limit, float th, float nnratio,
+                                  int far_points, float th_far_points, const float *scale_factors, int nlevels,
+                                  uint8_t *train_blocked, int32_t *train_match, uint8_t *in_view, float *proj_x,
+                                  float *proj_y, int *n_to_match);
+
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (ORBmatcher.h:50,
  * ORBmatcher.cc:1667-1878), both blocks (right camera :1786-1853 when CurrentFrame.Nleft != -1).  One entry per
  * LastFrame map point that projects into the image (:1690-1711):  u, v = uv;  ur = uv(0) - mbf * invzc (stereo gate

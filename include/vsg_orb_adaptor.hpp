@@ -526,6 +526,52 @@ inline std::vector<int32_t> ComputeDistinctiveDescriptors(const uint8_t *desc, c
 // GPU between calls.  A maintainer adds one `std::shared_ptr<vsg::ResidentFrame> mpResident` to Frame and KeyFrame
 // (KeyFrame's constructor copies the pointer from the Frame it is built from, like it copies mGrid, KeyFrame.cc:37-60)
 // and fills it at the end of the Frame constructors, after UndistortKeyPoints / ComputeStereo* / AssignFeaturesToGrid.
+// The camera of one Frame as isInFrustum uses it (vsg_frame_pose): Rcw = mRcw row-major, tcw = mtcw, Ow = mOw,
+// fx .. cy = Pinhole::mvParameters, mbf, log_scale_factor = mfLogScaleFactor, n_levels = mnScaleLevels.  Filled per call
+// from the Frame's members after SetPose (Frame::UpdatePoseMatrices, Frame.cc:612-619); nothing of it is resident.
+typedef vsg_frame_pose FramePose;
+
+// What isInFrustum and SearchByProjection(F, vpMapPoints) read of the local map's MapPoints, resident on the device
+// (vsg_mappoints).  A slot is the maintainer's own index of a MapPoint*.  minDist / maxDist are the MEMBERS mfMinDistance /
+// mfMaxDistance (PredictScale divides the unscaled one, MapPoint.cc:555), not the getters' 0.8f / 1.2f multiples.
+class ResidentMapPoints {
+ public:
+  explicit ResidentMapPoints(int capacity, int device = 0) {
+    check(vsg_mappoints_create(device, capacity, &mp_), "vsg_mappoints_create");
+  }
+  ~ResidentMapPoints() { vsg_mappoints_destroy(mp_); }
+  ResidentMapPoints(const ResidentMapPoints &) = delete;
+  ResidentMapPoints &operator=(const ResidentMapPoints &) = delete;
+  int capacity() const { return vsg_mappoints_capacity(mp_); }
+  // entry i of every non-null array goes to slot slots[i]; nullptr keeps what the slots hold; a slot listed twice takes
+  // its last entry.  worldPos / normal: 3 floats per entry, desc: 32 bytes, observed: Observations() > 0.
+  void update(const std::vector<int32_t> &slots, const float *worldPos, const float *normal, const float *minDist,
+              const float *maxDist, const uint8_t *desc, const uint8_t *observed) {
+    check(vsg_mappoints_update(mp_, (int)slots.size(), slots.data(), worldPos, normal, minDist, maxDist, desc, observed),
+          "vsg_mappoints_update");
+  }
+  vsg_mappoints *handle() const { return mp_; }
+
+ private:
+  vsg_mappoints *mp_ = nullptr;
+};
+
+// mbTrackInView, mTrackProjX / Y / XR, mTrackDepth, mnTrackScaleLevel, mTrackViewCos of the queried map points
+struct FrustumResult {
+  std::vector<uint8_t> inView;
+  std::vector<float> projX, projY, projXR, depth, viewCos;
+  std::vector<int32_t> scaleLevel;
+};
+
+// What Tracking::SearchLocalPoints leaves behind: the matches (feature -> index into the queried map points, -1 = none),
+// nToMatch, and per map point mbTrackInView with the projection mmProjectPoints takes (Tracking.cc:3462-3465)
+struct LocalPointsResult {
+  std::vector<int32_t> trainMatch;
+  std::vector<uint8_t> inView;
+  std::vector<float> projX, projY;
+  int nToMatch = 0;
+};
+
 class ResidentFrame {
  public:
   explicit ResidentFrame(int capacity, int device = 0) {
@@ -623,6 +669,42 @@ class ResidentFrame {
     }
     c.idx.resize(total);
     return c;
+  }
+
+  // bool Frame::isInFrustum(MapPoint *pMP, float viewingCosLimit) (Frame.cc:656-719) for the map points in `slots`
+  // (nullptr: slots 0 .. n-1).  Nleft != -1 frames throw (VSG_ERR_UNSUPPORTED).
+  void isInFrustum(const ResidentMapPoints &mp, int n, const int32_t *slots, const FramePose &pose, float viewingCosLimit,
+                   FrustumResult &out) const {
+    const size_t m = n > 0 ? n : 1;
+    out.inView.assign(m, 0), out.projX.assign(m, -1.f), out.projY.assign(m, -1.f), out.projXR.assign(m, 0.f);
+    out.depth.assign(m, 0.f), out.viewCos.assign(m, 0.f), out.scaleLevel.assign(m, 0);
+    check(vsg_frame_is_in_frustum(f_, mp.handle(), n, slots, &pose, viewingCosLimit, out.inView.data(), out.projX.data(),
+                                  out.projY.data(), out.projXR.data(), out.depth.data(), out.scaleLevel.data(),
+                                  out.viewCos.data()),
+          "vsg_frame_is_in_frustum");
+    out.inView.resize(n), out.projX.resize(n), out.projY.resize(n), out.projXR.resize(n), out.depth.resize(n);
+    out.viewCos.resize(n), out.scaleLevel.resize(n);
+  }
+
+  // Tracking::SearchLocalPoints' second loop and its SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th, bFarPoints,
+  // thFarPoints) (Tracking.cc:3446-3493) in one call and one wait.  skip[i] != 0 = mnLastFrameSeen == mnId || isBad()
+  // (nullptr: none); trainBlocked[i] = mvpMapPoints[i] && Observations() > 0 (in / out).  Returns nmatches.
+  int SearchLocalPoints(const ResidentMapPoints &mp, int n, const int32_t *slots, const uint8_t *skip, const FramePose &pose,
+                        float th, float nnratio, bool bFarPoints, float thFarPoints,
+                        const std::vector<float> &mvScaleFactors, std::vector<uint8_t> &trainBlocked,
+                        LocalPointsResult &out, float viewingCosLimit = 0.5f) const {
+    const size_t m = n > 0 ? n : 1;
+    out.trainMatch.assign(N() > 0 ? N() : 1, -1);
+    trainBlocked.resize(out.trainMatch.size(), 0);
+    out.inView.assign(m, 0), out.projX.assign(m, -1.f), out.projY.assign(m, -1.f);
+    const int rc = vsg_frame_search_local_points(f_, mp.handle(), n, slots, skip, &pose, viewingCosLimit, th, nnratio,
+                                                 bFarPoints ? 1 : 0, thFarPoints, mvScaleFactors.data(),
+                                                 (int)mvScaleFactors.size(), trainBlocked.data(), out.trainMatch.data(),
+                                                 out.inView.data(), out.projX.data(), out.projY.data(), &out.nToMatch);
+    check(rc, "vsg_frame_search_local_points");
+    out.trainMatch.resize(N()), trainBlocked.resize(N());
+    out.inView.resize(n), out.projX.resize(n), out.projY.resize(n);
+    return rc;
   }
 
  private:

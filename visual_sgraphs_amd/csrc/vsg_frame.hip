@@ -31,8 +31,6 @@ using namespace vsg;
 
 namespace {
 
-enum { VSG_RETRY = -100 };  // internal: candidate lists overflowed the compact array; the entry point runs again
-
 __device__ __forceinline__ int wave_incl_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);   // row_shr:1
   v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);   // row_shr:2
@@ -480,7 +478,7 @@ size_t WindowCall::bytes() const {
 }
 
 int WindowCall::launch(const vsg_frame *f, int gate_mode_, int best_init_, const float *inv_sigma2_, int nlevels,
-                       const uint8_t *qdesc_dev) {
+                       const uint8_t *qdesc_dev, const WinQuery *q_dev) {
   frame = f;
   gate_mode = gate_mode_, best_init = best_init_;
   const double tl = now_us();
@@ -492,7 +490,7 @@ int WindowCall::launch(const vsg_frame *f, int gate_mode_, int best_init_, const
   for (int l = 0; l < 16; l++) W.inv_sigma2[l] = (inv_sigma2_ && l < nlevels) ? inv_sigma2_[l] : 0.f;
   uint8_t *d = c->d_pin + base;
   hipLaunchKernelGGL(k_window_search, dim3((nq + 3) / 4), dim3(256), 0, c->stream, frame_dev(f),
-                     (const WinQuery *)(d + oQ),
+                     q_dev ? q_dev : (const WinQuery *)(d + oQ),
                      qdesc_dev ? qdesc_dev : with_desc ? (const uint8_t *)(d + oD) : (const uint8_t *)nullptr, W,
                      (int *)(d + oOff), (int *)(d + oCnt), (uint32_t *)(d + oOut), (int *)(d + oOut), c->d_counter);
   t_prof.launch = now_us() - tl;
@@ -514,6 +512,8 @@ int WindowCall::finish() {
   t_cap_hint = (int)(per > t_cap_hint ? per : 2 * t_cap_hint);  // sticky: room for windows like these from now on
   return VSG_RETRY;
 }
+
+void window_call_done() { t_prof.total = now_us() - t_prof.t0; }
 
 walk::CandView WindowCall::lists() const {
   walk::CandView cv;
@@ -584,19 +584,6 @@ void set_bounds(vsg_frame *f, float min_x, float min_y, float max_x, float max_y
   // mfGridElementWidthInv = FRAME_GRID_COLS / (mnMaxX - mnMinX)   (Frame.cc:378-379)
   f->invW = (float)kGridCols / (max_x - min_x);
   f->invH = (float)kGridRows / (max_y - min_y);
-}
-
-// retry loop around a window-search entry point body
-template <class Body>
-int with_retry(Body body) {
-  for (int attempt = 0; attempt < 8; attempt++) {
-    const int rc = body();
-    if (rc != VSG_RETRY) {
-      t_prof.total = now_us() - t_prof.t0;
-      return rc;
-    }
-  }
-  return VSG_ERR_CAPACITY;
 }
 
 inline float radius_by_viewing_cos(float viewCos) {  // ORBmatcher::RadiusByViewingCos (ORBmatcher.cc:218-224)

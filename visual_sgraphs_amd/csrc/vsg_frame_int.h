@@ -71,6 +71,7 @@ struct WinQuery {
 static_assert(sizeof(WinQuery) == 48, "WinQuery layout");
 
 enum { kWinList = 0, kWinBest = 1 };
+enum { VSG_RETRY = -100 };  // internal: candidate lists overflowed the compact array; the entry point runs again
 enum { kGateNone = 0, kGateUr = 1, kGateChi2 = 2 };
 
 // One window-search call on the calling thread's stream: begin() lays the pinned arena out and returns host pointers
@@ -93,12 +94,29 @@ struct WindowCall {
   WinQuery *queries() const { return (WinQuery *)(c->h_pin + base + oQ); }
   uint8_t *desc() const { return c->h_pin + base + oD; }
   int launch(const vsg_frame *f, int gate_mode, int best_init, const float *inv_sigma2, int nlevels,
-             const uint8_t *qdesc_dev = nullptr);  // qdesc_dev: query descriptors already on the device
+             const uint8_t *qdesc_dev = nullptr,   // qdesc_dev: query descriptors already on the device
+             const WinQuery *q_dev = nullptr);     // q_dev: queries a kernel in front of this one wrote on the device
   int finish();  // completion (pinned flag written by the kernel's last wave, or the stream) + overflow handling
   size_t bytes() const;
   walk::CandView lists() const;
   const int32_t *best() const { return (const int32_t *)(c->h_pin + base + oOut); }  // pairs {idx, dist}
 };
+
+// Retry loop around a window-search entry point body: a body whose WindowCall::finish() returned VSG_RETRY runs again
+// with the larger stride finish() left behind.  window_call_done() closes the thread's call profile
+// (vsg_debug_call_profile: the whole entry point's wall time).
+void window_call_done();
+template <class Body>
+int with_retry(Body body) {
+  for (int attempt = 0; attempt < 8; attempt++) {
+    const int rc = body();
+    if (rc != VSG_RETRY) {
+      window_call_done();
+      return rc;
+    }
+  }
+  return VSG_ERR_CAPACITY;
+}
 
 // One ComputeBoW in flight on a thread's arena (vsg_bow.hip): enqueue -> [other work of the same Frame] -> ONE wait -> finish
 struct BowCall {

@@ -7,6 +7,7 @@
 //   fastAtan2                  [OCV] mathfuncs_core.simd.hpp atan_f32, used at ORBextractor.cc:99
 //   cosf/sinf of angle*factorPI  glibc >= 2.28 s_sincosf.h kernels, used at ORBextractor.cc:107-108
 //   x*b + y*a, x*a - y*b       ORBextractor.cc:113-115
+//   logf                       glibc >= 2.27 e_logf.c, used by MapPoint::PredictScale (MapPoint.cc:558)
 #pragma once
 #include <stdint.h>
 
@@ -191,6 +192,73 @@ VSG_HD void sincos_pair(float y, float *cos_out, float *sin_out) {
   if (K::abstop12(y) < K::abstop12(0x1p-12f)) sv = y, cv = 1.0f;
   *cos_out = cv, *sin_out = sv;
 }
+
+// ---- glibc (>= 2.27) logf: 16-entry table {1/c, log(c)} + a degree-3 polynomial of r = z/c - 1, evaluated in double, the
+// result rounded to float once (sysdeps/ieee754/flt-32/e_logf.c, e_logf_data.c).  MapPoint::PredictScale (MapPoint.cc:558)
+// takes log(ratio) of a float.  USE_FMA as for SinCosF: true = the contraction pattern of x86-64's `__logf_fma` ifunc
+// variant, false = `__logf_sse2`.  tests/test_frustum_hostmath.py runs both over every float of [2^-6, 2^8) against the
+// host's libm.  Zero is -inf, negative / NaN is NaN, +inf is +inf, as in glibc (no errno).
+template <bool USE_FMA>
+VSG_HD float logf_glibc(float x) {
+  uint32_t ix = f2u(x);
+  if (ix == 0x3f800000u) return 0.0f;
+  if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {  // x < 0x1p-126, inf or NaN
+    if (ix * 2 == 0) return -__builtin_inff();
+    if (ix == 0x7f800000u) return x;
+    if ((ix & 0x80000000u) || ix * 2 >= 0xff000000u) return __builtin_nanf("");
+    ix = f2u(fmul(x, 0x1p23f));  // subnormal: normalise
+    ix -= 23u << 23;
+  }
+  // x = 2^k z with z in [OFF, 2 OFF); the table's subinterval i holds z, c is near its centre
+  const uint32_t tmp = ix - 0x3f330000u;
+  const int i = (int)((tmp >> 19) & 15u);
+  const int k = (int32_t)tmp >> 23;
+  const uint32_t iz = ix - (tmp & (0x1ffu << 23));
+  double invc, logc;
+  switch (i) {  // selects, not an indexed table: nothing of this lives in memory (no scratch, no constant loads per lane)
+    case 0: invc = 0x1.661ec79f8f3bep+0, logc = -0x1.57bf7808caadep-2; break;
+    case 1: invc = 0x1.571ed4aaf883dp+0, logc = -0x1.2bef0a7c06ddbp-2; break;
+    case 2: invc = 0x1.49539f0f010bp+0, logc = -0x1.01eae7f513a67p-2; break;
+    case 3: invc = 0x1.3c995b0b80385p+0, logc = -0x1.b31d8a68224e9p-3; break;
+    case 4: invc = 0x1.30d190c8864a5p+0, logc = -0x1.6574f0ac07758p-3; break;
+    case 5: invc = 0x1.25e227b0b8eap+0, logc = -0x1.1aa2bc79c81p-3; break;
+    case 6: invc = 0x1.1bb4a4a1a343fp+0, logc = -0x1.a4e76ce8c0e5ep-4; break;
+    case 7: invc = 0x1.12358f08ae5bap+0, logc = -0x1.1973c5a611cccp-4; break;
+    case 8: invc = 0x1.0953f419900a7p+0, logc = -0x1.252f438e10c1ep-5; break;
+    case 9: invc = 0x1p+0, logc = 0x0p+0; break;
+    case 10: invc = 0x1.e608cfd9a47acp-1, logc = 0x1.aa5aa5df25984p-5; break;
+    case 11: invc = 0x1.ca4b31f026aap-1, logc = 0x1.c5e53aa362eb4p-4; break;
+    case 12: invc = 0x1.b2036576afce6p-1, logc = 0x1.526e57720db08p-3; break;
+    case 13: invc = 0x1.9c2d163a1aa2dp-1, logc = 0x1.bc2860d22477p-3; break;
+    case 14: invc = 0x1.886e6037841edp-1, logc = 0x1.1058bc8a07ee1p-2; break;
+    default: invc = 0x1.767dcf5534862p-1, logc = 0x1.4043057b6ee09p-2; break;
+  }
+  const double ln2 = 0x1.62e42fefa39efp-1;
+  const double A0 = -0x1.00ea348b88334p-2, A1 = 0x1.5575b0be00b6ap-2, A2 = -0x1.ffffef20a4123p-2;
+  union {
+    uint32_t u;
+    float f;
+  } zc;
+  zc.u = iz;
+  const double z = (double)zc.f;
+  // log(x) = log1p(z/c - 1) + log(c) + k ln2
+  const double r = USE_FMA ? dfma(z, invc, -1.0) : dsub(dmul(z, invc), 1.0);
+  const double y0 = USE_FMA ? dfma((double)k, ln2, logc) : dadd(logc, dmul((double)k, ln2));
+  const double r2 = dmul(r, r);
+  double y = USE_FMA ? dfma(A1, r, A2) : dadd(dmul(A1, r), A2);
+  y = USE_FMA ? dfma(A0, r2, y) : dadd(dmul(A0, r2), y);
+  y = USE_FMA ? dfma(y, r2, dadd(y0, r)) : dadd(dmul(y, r2), dadd(y0, r));
+  return (float)y;
+}
+
+// the form the library uses: both variants agree with each other and with libm for every float of [2^-6, 2^8) (the range of
+// max_dist / dist that PredictScale can turn into a level other than 0 or n-1), so the uncontracted one it is
+VSG_HD float log_f32(float x) { return logf_glibc<false>(x); }
+
+// sqrtf, correctly rounded on both sides.  NOT __fsqrt_rn: HIP defines that as the native (approximate) square root
+// unless OCML_BASIC_ROUNDED_OPERATIONS is set; sqrtf is IEEE under hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt, which is also what makes the `/` behind __fdiv_rn exact.
+VSG_HD float fsqrt(float a) { return __builtin_sqrtf(a); }
 
 // fast_atan2_deg without the two-sided branch (both sides are the same polynomial of min / max); bit-identical: when
 // ax == ay both forms divide the same values

@@ -71,6 +71,9 @@ EXPORTS = [
     "vsg_vocab_score", "vsg_kfdb_create", "vsg_kfdb_destroy", "vsg_kfdb_add", "vsg_kfdb_erase", "vsg_kfdb_clear",
     "vsg_kfdb_clear_map", "vsg_kfdb_set_map", "vsg_kfdb_set_covisibility", "vsg_kfdb_detect_relocalization_candidates",
     "vsg_kfdb_detect_n_best_candidates",
+    # resident map points: Frame::isInFrustum and Tracking::SearchLocalPoints
+    "vsg_mappoints_create", "vsg_mappoints_destroy", "vsg_mappoints_capacity", "vsg_mappoints_update",
+    "vsg_mappoints_read", "vsg_frame_is_in_frustum", "vsg_frame_search_local_points",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -85,6 +88,24 @@ OCT_BLUR_MEMBATCH, OCT_BLUR_MEMBATCH_FUSED, OCT_FEW_MEMBATCH, OCT_FEW_MEMBATCH_F
 
 class _LaunchForms(C.Structure):
     _fields_ = [(n, C.c_int) for n in LAUNCH_FORM_FIELDS]
+
+
+class FramePose(C.Structure):
+    """include/vsg_orb.h vsg_frame_pose: the camera of one Frame as Frame::isInFrustum uses it (mRcw row-major, mtcw, mOw,
+    Pinhole::mvParameters, mbf, mfLogScaleFactor, mnScaleLevels)."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+    @classmethod
+    def make(cls, Rcw, tcw, Ow, fx, fy, cx, cy, mbf, log_scale_factor, n_levels):
+        p = cls()
+        p.Rcw[:] = [float(v) for v in np.asarray(Rcw, np.float32).reshape(9)]
+        p.tcw[:] = [float(v) for v in np.asarray(tcw, np.float32).reshape(3)]
+        p.Ow[:] = [float(v) for v in np.asarray(Ow, np.float32).reshape(3)]
+        p.fx, p.fy, p.cx, p.cy, p.mbf = float(fx), float(fy), float(cx), float(cy), float(mbf)
+        p.log_scale_factor, p.n_levels = float(log_scale_factor), int(n_levels)
+        return p
 
 
 class VsgError(RuntimeError):
@@ -296,6 +317,16 @@ def load_library():
     u64, i32 = C.c_uint64, C.c_int32
     _u64p = C.POINTER(C.c_uint64)
     L.vsg_vocab_score.argtypes = [vp, _i32p, _f64p, ci, _i32p, _i32p, _f64p, ci, _f64p]
+    L.vsg_mappoints_create.argtypes = [ci, ci, C.POINTER(vp)]
+    L.vsg_mappoints_destroy.argtypes = [vp]
+    L.vsg_mappoints_destroy.restype = None
+    L.vsg_mappoints_capacity.argtypes = [vp]
+    L.vsg_mappoints_update.argtypes = [vp, ci, _i32p, _f32p, _f32p, _f32p, _f32p, _u8p, _u8p]
+    L.vsg_mappoints_read.argtypes = [vp, ci, _i32p, _f32p, _f32p, _f32p, _f32p, _u8p, _u8p]
+    L.vsg_frame_is_in_frustum.argtypes = [vp, vp, ci, _i32p, C.POINTER(FramePose), cf, _u8p, _f32p, _f32p, _f32p, _f32p,
+                                          _i32p, _f32p]
+    L.vsg_frame_search_local_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, cf, cf, ci, cf, _f32p,
+                                                ci, _u8p, _i32p, _u8p, _f32p, _f32p, C.POINTER(ci)]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -968,6 +999,67 @@ class KeyFrameDatabase:
         return [int(x) for x in lo[:nl.value]], [int(x) for x in me[:nm.value]]
 
 
+class MapPoints:
+    """The local map's MapPoints resident on the device (include/vsg_orb.h: vsg_mappoints): per slot GetWorldPos(),
+    GetNormal(), the members mfMinDistance / mfMaxDistance (unscaled: PredictScale divides mfMaxDistance itself),
+    GetDescriptor(), Observations() > 0.  Slots are the caller's own index of a MapPoint."""
+
+    def __init__(self, capacity, device=0):
+        self._L = load_library()
+        self._h = C.c_void_p()
+        self.device = int(device)
+        _check(self._L.vsg_mappoints_create(self.device, int(capacity), C.byref(self._h)), "vsg_mappoints_create")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._L.vsg_mappoints_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def capacity(self):
+        return self._L.vsg_mappoints_capacity(self._h)
+
+    def update(self, slots, world_pos=None, normal=None, min_dist=None, max_dist=None, desc=None, observed=None):
+        """Scatter update of len(slots) slots; a field left None keeps what the slots hold; a slot listed twice takes its
+        last entry."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(sl)
+
+        def f(a, conv, t, width):
+            if a is None:
+                return None, None
+            if np.asarray(a).size != n * width:
+                raise ValueError("field length does not match the slot list")
+            a = conv(a)
+            return a, _p(a, t)
+        keep = [f(world_pos, _f32, _f32p, 3), f(normal, _f32, _f32p, 3), f(min_dist, _f32, _f32p, 1),
+                f(max_dist, _f32, _f32p, 1), f(desc, _u8, _u8p, 32), f(observed, _u8, _u8p, 1)]
+        _check(self._L.vsg_mappoints_update(self._h, n, _p(_i32(sl), _i32p), *[k[1] for k in keep]),
+               "vsg_mappoints_update")
+
+    def read(self, slots):
+        """dict of the fields of the listed slots (test / debug)."""
+        sl = _i32(slots)
+        n = len(np.asarray(slots))
+        out = {"world_pos": np.zeros((max(n, 1), 3), np.float32), "normal": np.zeros((max(n, 1), 3), np.float32),
+               "min_dist": np.zeros(max(n, 1), np.float32), "max_dist": np.zeros(max(n, 1), np.float32),
+               "desc": np.zeros((max(n, 1), 32), np.uint8), "observed": np.zeros(max(n, 1), np.uint8)}
+        _check(self._L.vsg_mappoints_read(self._h, n, _p(sl, _i32p), _p(out["world_pos"], _f32p), _p(out["normal"], _f32p),
+                                          _p(out["min_dist"], _f32p), _p(out["max_dist"], _f32p), _p(out["desc"], _u8p),
+                                          _p(out["observed"], _u8p)), "vsg_mappoints_read")
+        return {k: v[:n] for k, v in out.items()}
+
+
 def ComputeDistinctiveDescriptors(desc, off, device=0):
     """MapPoint::ComputeDistinctiveDescriptors for many map points: returns the chosen row index per group."""
     d, o = _u8(desc).reshape(-1, 32), _i32(off)
@@ -1282,6 +1374,47 @@ class Frame:
             len(scale_factors), o(ltr, _i32p), o(rtl, _i32p), _p(tb, _u8p), _p(tm, _i32p)),
             "vsg_frame_search_by_projection")
         return nm, tm[:len(tb)], tb
+
+    # ---- Frame::isInFrustum (Frame.cc:656-719) on resident map points
+    def isInFrustum(self, mp, pose, n=None, slots=None, viewing_cos_limit=0.5):
+        """mp: MapPoints, pose: FramePose.  Map point i = slot slots[i] (None: slots 0 .. n-1, n defaulting to the store's
+        capacity).  Returns a dict: in_view, proj_x, proj_y, proj_xr, depth, scale_level, view_cos."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32) if slots is not None else None
+        n = len(sl) if sl is not None else (mp.capacity if n is None else int(n))
+        m = max(n, 1)
+        out = {"in_view": np.zeros(m, np.uint8), "proj_x": np.zeros(m, np.float32), "proj_y": np.zeros(m, np.float32),
+               "proj_xr": np.zeros(m, np.float32), "depth": np.zeros(m, np.float32),
+               "scale_level": np.zeros(m, np.int32), "view_cos": np.zeros(m, np.float32)}
+        _check(self._L.vsg_frame_is_in_frustum(
+            self._h, mp.handle, n, _p(_i32(sl), _i32p) if sl is not None else None, C.byref(pose),
+            float(np.float32(viewing_cos_limit)), _p(out["in_view"], _u8p), _p(out["proj_x"], _f32p),
+            _p(out["proj_y"], _f32p), _p(out["proj_xr"], _f32p), _p(out["depth"], _f32p), _p(out["scale_level"], _i32p),
+            _p(out["view_cos"], _f32p)), "vsg_frame_is_in_frustum")
+        return {k: v[:n] for k, v in out.items()}
+
+    # ---- Tracking::SearchLocalPoints (Tracking.cc:3423-3495): isInFrustum + SearchByProjection(F, vpMapPoints)
+    def SearchLocalPoints(self, mp, pose, th, nnratio, scale_factors, train_blocked, n=None, slots=None, skip=None,
+                          viewing_cos_limit=0.5, far_points=False, th_far_points=0.0):
+        """skip[i] != 0: mnLastFrameSeen == mnId or isBad() (never projected).  Returns (nmatches, train_match,
+        train_blocked, in_view, proj_x, proj_y, n_to_match)."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32) if slots is not None else None
+        n = len(sl) if sl is not None else (mp.capacity if n is None else int(n))
+        sk = _u8(skip) if skip is not None else None
+        if sk is not None and len(sk) != n:
+            raise ValueError("skip length does not match the map points")
+        m = max(n, 1)
+        sf = _f32(scale_factors)
+        tb = _u8(train_blocked).copy()
+        tm = np.full(max(len(tb), 1), -1, np.int32)
+        inv, px, py = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        ntm = C.c_int(0)
+        nm = _check(self._L.vsg_frame_search_local_points(
+            self._h, mp.handle, n, _p(_i32(sl), _i32p) if sl is not None else None,
+            _p(sk, _u8p) if sk is not None and n else None, C.byref(pose), float(np.float32(viewing_cos_limit)), float(th),
+            float(np.float32(nnratio)), int(bool(far_points)), float(np.float32(th_far_points)), _p(sf, _f32p),
+            len(scale_factors), _p(tb, _u8p), _p(tm, _i32p), _p(inv, _u8p), _p(px, _f32p), _p(py, _f32p), C.byref(ntm)),
+            "vsg_frame_search_local_points")
+        return nm, tm[:len(tb)], tb, inv[:n], px[:n], py[:n], ntm.value
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono)  (ORBmatcher.cc:1667-1878)
     def SearchByProjection_Last(self, desc, observed, u, v, ur, last_octave, last_angle, th, direction, scale_factors,
