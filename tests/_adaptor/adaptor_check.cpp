@@ -190,6 +190,77 @@ int main(int argc, char **argv) {
       }
     }
 
+    // ---- resident frames at the window search's size edges (oracle values in the Python test)
+    // (1) a frame of more than 4096 keypoints straight out of the extractor: above that count the grid launch orders its
+    //     cells in global memory instead of LDS
+    const int WB = 1280, HB = 720;
+    std::vector<vsg_keypoint> bk;
+    std::vector<uint8_t> bd;
+    std::vector<int32_t> bOff, bIdx, bSim3, bLast;
+    int nbSim3 = 0, nbLast = 0;
+    {
+      std::vector<uint8_t> imb((size_t)WB * HB);
+      if (vsg_synth_sequence_frame(WB, HB, 21, 0, 1, 6, imb.data(), WB)) return 2;
+      vsg::ORBextractor exb(6000, 1.2f, 8, 20, 7);
+      exb(imb.data(), HB, WB, WB, bk, bd, lap);
+      vsg::ResidentFrame B(exb.capacity(HB, WB));
+      B.FromExtractor(exb, bk, 0.f, 0.f, (float)WB, (float)HB);
+      vsg::ProjectedPoints Q;   // every third keypoint searched for in its own frame, one pixel off, 12 * scale wide
+      for (size_t i = 0; i < bk.size(); i += 3) {
+        const vsg_keypoint &k = bk[i];
+        Q.u.push_back(k.x + 1.0f), Q.v.push_back(k.y - 1.0f), Q.level.push_back(k.octave), Q.angle.push_back(k.angle);
+        Q.radius.push_back(12.0f * scale[k.octave]), Q.observed.push_back(1);
+        Q.desc.insert(Q.desc.end(), bd.begin() + i * 32, bd.begin() + i * 32 + 32);
+      }
+      Q.ur = Q.u;
+      const vsg::Candidates c = B.GetFeaturesInArea(Q.u.data(), Q.v.data(), Q.radius.data(), nullptr, nullptr, Q.n());
+      bOff = c.off, bIdx = c.idx;
+      bSim3.assign(bk.size(), -1);
+      nbSim3 = rm.SearchByProjection(B, Q, 1.0f, bSim3);
+      std::vector<uint8_t> blk;
+      nbLast = rm.SearchByProjection(B, Q, 12.0f, 0, scale, blk, bLast);
+    }
+    // (2) an uploaded frame whose cells hold 1, 32, 33 and 150 entries: a window chunk with a cell of more than 32 entries
+    //     filters twice, every other one through a 32-bit survivor mask
+    std::vector<vsg_keypoint> ck;
+    std::vector<uint8_t> cd, cqd;
+    std::vector<float> cqx, cqy, cqr;
+    std::vector<int32_t> cql, cOff, cIdx, cSim3, cFuseIdx, cFuseDist;
+    int ncSim3 = 0, ncFuse = 0;
+    {
+      uint64_t s = 0xD1B54A32D192ED03ull;
+      auto rnd = [&]() {
+        s ^= s << 13, s ^= s >> 7, s ^= s << 17;
+        return s;
+      };
+      const int cellsX[4] = {10, 20, 30, 40}, count[4] = {1, 32, 33, 150};   // cells (x, 12) of the 64 x 48 grid on 640x480
+      for (int c = 0; c < 4; ++c)
+        for (int j = 0; j < count[c]; ++j)   // cell px collects x in [10 px - 5, 10 px + 5)
+          ck.push_back(vsg_keypoint{cellsX[c] * 10.0f + (float)(rnd() % 900) * 0.01f - 4.5f,
+                                    120.0f + (float)(rnd() % 900) * 0.01f - 4.5f, 31.f, (float)(rnd() % 3600) * 0.1f, 1.f,
+                                    (int)(rnd() % 3), -1});
+      for (size_t i = ck.size(); i > 1; --i) std::swap(ck[i - 1], ck[rnd() % i]);   // cell members spread over the indices
+      cd.resize(ck.size() * 32);
+      for (auto &b : cd) b = (uint8_t)rnd();
+      vsg::ResidentFrame Cf((int)ck.size());
+      Cf.Upload(ck.data(), cd.data(), nullptr, (int)ck.size(), -1, 0.f, 0.f, (float)W, (float)H);
+      vsg::ProjectedPoints Q;
+      for (int c = 0; c < 4; ++c)
+        for (int j = 0; j < 6; ++j) {   // radii 4 .. 9 px around the cell centre; the last covers the whole cell
+          const int src = (int)(rnd() % ck.size());
+          Q.u.push_back(cellsX[c] * 10.0f), Q.v.push_back(120.0f), Q.radius.push_back(4.0f + j);
+          Q.level.push_back(1 + j % 2), Q.angle.push_back(0.f), Q.observed.push_back(1);
+          Q.desc.insert(Q.desc.end(), cd.begin() + src * 32, cd.begin() + src * 32 + 32);
+        }
+      Q.ur = Q.u;
+      cqx = Q.u, cqy = Q.v, cqr = Q.radius, cqd = Q.desc, cql = Q.level;
+      const vsg::Candidates c = Cf.GetFeaturesInArea(Q.u.data(), Q.v.data(), Q.radius.data(), nullptr, nullptr, Q.n());
+      cOff = c.off, cIdx = c.idx;
+      cSim3.assign(ck.size(), -1);
+      ncSim3 = rm.SearchByProjection(Cf, Q, 3.0f, cSim3);
+      ncFuse = rm.Fuse(Cf, Q, cFuseIdx, cFuseDist);
+    }
+
     std::ofstream f(argv[2], std::ios::binary);
     std::vector<int32_t> head{mono[0], mono[1], nwin, nbow, ninit, d01, ntri, nlast, nsim3, nfuse, nrinit, ngF, ngKK,
                               neF, neKF, neKK};
@@ -205,6 +276,10 @@ int main(int argc, char **argv) {
     dump(f, rLast), dump(f, rSim3), dump(f, rFuseIdx), dump(f, rFuseDist), dump(f, rInit);
     for (int t = 0; t < 2; ++t) dump(f, gk[t]), dump(f, gd[t]);
     dump(f, gMatchF), dump(f, gMatch12);
+    dump(f, std::vector<int32_t>{nbSim3, nbLast, ncSim3, ncFuse});
+    dump(f, bk), dump(f, bd), dump(f, bOff), dump(f, bIdx), dump(f, bSim3), dump(f, bLast);
+    dump(f, ck), dump(f, cd), dump(f, cqx), dump(f, cqy), dump(f, cqr), dump(f, cqd), dump(f, cql), dump(f, cOff), dump(f, cIdx), dump(f, cSim3);
+    dump(f, cFuseIdx), dump(f, cFuseDist);
     printf("OK %zu %zu win=%d bow=%d init=%d\n", kps[0].size(), kps[1].size(), nwin, nbow, ninit);
     return 0;
   } catch (const std::exception &e) {

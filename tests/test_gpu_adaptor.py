@@ -40,6 +40,16 @@ def _read(path):
         out[f"big_desc{t}"] = take(np.uint8).reshape(-1, 32)
     for k in ("big_match_f", "big_match12"):
         out[k] = take(np.int32)
+    out["edge_head"] = take(np.int32)
+    out["b_kps"], out["b_desc"] = take(orb.KP_DTYPE), take(np.uint8).reshape(-1, 32)
+    for k in ("b_off", "b_idx", "b_sim3", "b_last"):
+        out[k] = take(np.int32)
+    out["c_kps"], out["c_desc"] = take(orb.KP_DTYPE), take(np.uint8).reshape(-1, 32)
+    for k in ("c_x", "c_y", "c_r"):
+        out[k] = take(np.float32)
+    out["c_qdesc"] = take(np.uint8).reshape(-1, 32)
+    for k in ("c_level", "c_off", "c_idx", "c_sim3", "c_fuse_idx", "c_fuse_dist"):
+        out[k] = take(np.int32)
     assert pos == len(raw)
     return out
 
@@ -151,3 +161,47 @@ def test_cpp_adaptor_end_to_end_equals_oracle(tmp_path):
     nk, m12 = ol.search_by_bow_kf_kf(gd0, gk0["angle"], gv0, g0, gd1, gk1["angle"], gv1, g1, 0.7, True)
     assert int(got["head"][12]) == nk > 300 and np.array_equal(got["big_match12"], m12)
     assert got["head"][13:16].tolist() == [0, 0, 0]
+
+    # ---- resident frames at the window search's size edges
+    # (1) more than 4096 device-built features (the grid launch orders its cells in global memory): the extractor's output,
+    # every list of GetFeaturesInArea and two matcher routines equal the oracle's
+    bk, bd = got["b_kps"], got["b_desc"]
+    _, wk, wd = ol.OracleExtractor(6000, 1.2, 8, 20, 7)(synth.sequence_frame(1280, 720, 21, 0))
+    assert len(wk) > 4200 and bk.tobytes() == wk.tobytes() and np.array_equal(bd, wd)
+    ob = ol.OracleFrame(wk, wd, (0.0, 0.0, 1280.0, 720.0))
+    occ = np.diff(ob.grid()[0])
+    assert (occ >= 2).sum() >= 30 and occ.max() >= 8   # unsorted cells would show
+    qs = np.arange(0, len(wk), 3)
+    qu, qv = (wk["x"][qs] + np.float32(1)).astype(np.float32), (wk["y"][qs] - np.float32(1)).astype(np.float32)
+    qo = wk["octave"][qs].astype(np.int32)
+    qr = (np.float32(12) * scale[qo]).astype(np.float32)
+    off, idx = [0], []
+    for i in range(len(qs)):
+        idx.extend(ob.features_in_area(qu[i], qv[i], qr[i], kf_form=True).tolist())
+        off.append(len(idx))
+    assert np.array_equal(got["b_off"], off) and np.array_equal(got["b_idx"], idx) and len(idx) > 10 * len(qs)
+    ns, m = ob.search_by_projection_sim3(wd[qs], qu, qv, qr, qo, 1.0, np.full(len(wk), -1, np.int32))
+    assert int(got["edge_head"][0]) == ns > 1000 and np.array_equal(got["b_sim3"], m)
+    nl, tm, _ = ob.search_by_projection_last(wd[qs], np.ones(len(qs), np.uint8), qu, qv, qu, qo,
+                                             wk["angle"][qs].astype(np.float32), 12.0, 0, scale, True,
+                                             np.zeros(len(wk), np.uint8))
+    assert int(got["edge_head"][1]) == nl > 1000 and np.array_equal(got["b_last"], tm)
+    # (2) cells of 1, 32, 33 and 150 entries: the full 32-entry cell goes through the last bit of the kernel's survivor mask,
+    # the larger ones through its two-pass filter
+    ck, cd = got["c_kps"], got["c_desc"]
+    oc = ol.OracleFrame(ck, cd, b)
+    assert sorted(np.diff(oc.grid()[0])[np.diff(oc.grid()[0]) > 0].tolist()) == [1, 32, 33, 150]
+    cx, cy, cr = got["c_x"], got["c_y"], got["c_r"]
+    off, idx = [0], []
+    for i in range(len(cx)):
+        idx.extend(oc.features_in_area(cx[i], cy[i], cr[i], kf_form=True).tolist())
+        off.append(len(idx))
+    assert np.array_equal(got["c_off"], off) and np.array_equal(got["c_idx"], idx)
+    assert {32, 33, 150} <= set(np.diff(off).tolist())   # whole cells are listed
+    cq, cl = got["c_qdesc"], got["c_level"]
+    ns, m = oc.search_by_projection_sim3(cq, cx, cy, cr, cl, 3.0, np.full(len(ck), -1, np.int32))
+    assert int(got["edge_head"][2]) == ns >= 10 and np.array_equal(got["c_sim3"], m)
+    z = np.zeros(len(cx) + len(ck), np.int32)
+    r = oc.fuse_sim3(np.arange(len(cx)), cq, cx, cy, cr, cl, np.full(len(ck), -1, np.int32), z, z.astype(np.uint8))
+    assert int(got["edge_head"][3]) == r[0]
+    assert np.array_equal(got["c_fuse_idx"], r[1]) and np.array_equal(got["c_fuse_dist"], r[2]) and (r[1] >= 0).sum() >= 10

@@ -1259,18 +1259,19 @@ class Frame:
         self.kps, self.nleft = k, int(nleft)
         return self
 
-    def from_extractor(self, ex, index, kps, bounds):
-        """Device-to-device from frame `index` of the extractor's last call; kps = the records that call returned."""
-        k = np.ascontiguousarray(kps, dtype=KP_DTYPE)
+    def from_extractor(self, ex, index, kps, bounds, n=None):
+        """Device-to-device from frame `index` of the extractor's last call; kps = the records that call returned
+        (n: only the first n of them)."""
+        k = np.ascontiguousarray(kps, dtype=KP_DTYPE)[:n]
         _check(self._L.vsg_frame_from_extractor(self._h, ex.handle, int(index), k.ctypes.data_as(C.c_void_p), len(k),
                                                 *[float(b) for b in bounds]), "vsg_frame_from_extractor")
         self.kps, self.nleft = k, -1
         return self
 
-    def from_extractor_undistort(self, ex, index, kps, K4, dist, bounds):
+    def from_extractor_undistort(self, ex, index, kps, K4, dist, bounds, n=None):
         """The same for a distorted pinhole camera: Frame::UndistortKeyPoints (Frame.cc:891-921) on the device inside the
         grid launch.  self.kps = mvKeysUn afterwards."""
-        k = np.ascontiguousarray(kps, dtype=KP_DTYPE)
+        k = np.ascontiguousarray(kps, dtype=KP_DTYPE)[:n]
         K4, dist = _f32(np.asarray(K4)), _f32(np.asarray(dist))
         un = np.zeros(len(k), KP_DTYPE)
         _check(self._L.vsg_frame_from_extractor_undistort(
