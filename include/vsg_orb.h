@@ -266,7 +266,13 @@ int vsg_distinctive_descriptors(int device, const uint8_t *desc, const int32_t *
 
 /* ---- Frame grid: Frame::AssignFeaturesToGrid / PosInGrid (Frame.cc:521-553, 870-880) and
  * Frame::GetFeaturesInArea / KeyFrame::GetFeaturesInArea (Frame.cc:802-868, KeyFrame.cc:834-874) on the device.
- * 64 x 48 cells (Frame.h:49-50).  kps = the (undistorted) keypoints the reference indexes (host pointer). */
+ * 64 x 48 cells (Frame.h:49-50).  kps = the (undistorted) keypoints the reference indexes (host pointer).
+ * A vsg_grid is the left grid of a resident frame (vsg_frame, below) without descriptors, mvuRight or FeatureVector:
+ * the same upload builds it and the same kernel answers vsg_grid_query and vsg_frame_features_in_area.  n <= 32767
+ * (VSG_ERR_INVALID above); n == 0 builds a grid whose every query is empty.  Octaves are compared whole and may be
+ * anything an int16 holds (a resident frame's: 0..15); outside of that: VSG_ERR_UNSUPPORTED.  Device memory per grid:
+ * one allocation of 12 bytes per keypoint (the grid entry: x, y, index | octave -- the keypoint records themselves stay
+ * on the host) + two cell tables of 12 KB (the right-camera one is empty). */
 typedef struct vsg_grid vsg_grid;
 int vsg_grid_build(int device, const vsg_keypoint *kps, int n, float min_x, float min_y, float max_x, float max_y,
                    vsg_grid **out);
@@ -498,8 +504,9 @@ int vsg_frame_size(const vsg_frame *f);
 int vsg_frame_copy_grid(vsg_frame *f, int right, int32_t *cell_start, int32_t *entries);
 
 /* Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel, bRight) (Frame.cc:802-868) / KeyFrame::GetFeaturesInArea
- * (KeyFrame.cc:834-874; pass min_level = max_level = NULL) for nq windows on the resident grid; CSR out like
- * vsg_grid_query.  Indices are grid-local (right grid: i - Nleft), exactly what the reference's vectors hold. */
+ * (KeyFrame.cc:834-874; pass min_level = max_level = NULL) for nq windows on the resident grid; CSR out, return value
+ * and cap as vsg_grid_query, which is this call on a grid's frame with right = 0.  Indices are grid-local (right grid:
+ * i - Nleft), exactly what the reference's vectors hold. */
 int vsg_frame_features_in_area(vsg_frame *f, const float *x, const float *y, const float *r, const int32_t *min_level,
                                const int32_t *max_level, int right, int nq, int32_t *cand_off, int32_t *cand_idx,
                                int cap);

@@ -179,6 +179,7 @@ struct Candidates {
 };
 
 // Frame::mGrid (Frame.h:290) on the device: AssignFeaturesToGrid + GetFeaturesInArea (Frame.cc:521-553, 802-868).
+// The grid of a ResidentFrame on its own (no descriptors): same host build, same kernel, same candidate order.
 class FrameGrid {
  public:
   FrameGrid(const vsg_keypoint *keysUn, int n, float mnMinX, float mnMinY, float mnMaxX, float mnMaxY, int device = 0) {

@@ -259,6 +259,110 @@ def test_device_grid_edge_cases(camera):
         assert idx.tolist() == ref.query(*q).tolist()
 
 
+def test_device_grid_octaves_above_15():
+    """A grid compares the whole octave (a resident frame's packed candidates carry 4 bits of it; a grid's do not)."""
+    rng = np.random.default_rng(7)
+    octaves = [0, 7, 16, 20, 300]
+    kp = np.zeros(800, orb.KP_DTYPE)
+    kp["x"], kp["y"] = rng.uniform(0, 640, len(kp)), rng.uniform(0, 480, len(kp))
+    kp["octave"] = rng.choice(octaves, len(kp))
+    bounds = (0.0, 0.0, 640.0, 480.0)
+    g, ref = orb.FrameGrid(kp, *bounds), ol.OracleGrid(kp, *bounds)
+    x, y = rng.uniform(0, 640, 40).astype(np.float32), rng.uniform(0, 480, 40).astype(np.float32)
+    r = np.full(40, 50.0, np.float32)
+    # (minLevel, maxLevel) -> the octaves GetFeaturesInArea lets through (Frame.cc:836-843)
+    for (lo, hi), passing in {(-1, -1): octaves, (0, 0): [0], (-1, 15): [0, 7], (1, 7): [7], (8, 16): [16],
+                              (16, -1): [16, 20, 300], (17, 20): [20], (17, 299): [20], (21, 299): [],
+                              (21, 300): [300], (300, -1): [300], (301, -1): []}.items():
+        off, idx = g.GetFeaturesInArea(x, y, r, np.full(40, lo, np.int32), np.full(40, hi, np.int32))
+        for q in range(40):
+            assert np.array_equal(idx[off[q]:off[q + 1]], ref.query(x[q], y[q], r[q], lo, hi)), (lo, hi, q)
+        assert sorted(set(kp["octave"][idx].tolist())) == passing, (lo, hi)
+
+
+def _grid_query_raw(g, x, y, r, idx, cap):
+    """vsg_grid_query as the C caller sees it: (return value, cand_off); idx (None = NULL) is written in place."""
+    off = np.full(len(x) + 1, -1, np.int32)
+    rc = orb._lib.vsg_grid_query(g._h, orb._p(x, orb._f32p), orb._p(y, orb._f32p), orb._p(r, orb._f32p), None, None,
+                                 len(x), orb._p(off, orb._i32p), orb._p(idx, orb._i32p) if idx is not None else None, cap)
+    return rc, off
+
+
+def test_device_grid_query_cap_below_total_and_count_only(frames):
+    (k0, d0), (k1, d1) = frames
+    bounds = (0.0, 0.0, 640.0, 480.0)
+    g, ref = orb.FrameGrid(k1, *bounds), ol.OracleGrid(k1, *bounds)
+    x, y = (k0["x"][:60] + 3).astype(np.float32), (k0["y"][:60] + 2).astype(np.float32)
+    r = np.full(60, 30.0, np.float32)
+    want = [ref.query(x[q], y[q], r[q]) for q in range(60)]
+    want_off = np.concatenate([[0], np.cumsum([len(w) for w in want])]).astype(np.int32)
+    want_idx = np.concatenate(want)
+    total = int(want_off[-1])
+    assert total > 200
+    GUARD = -7
+    for cap in (total // 2, 1, total - 1, total):
+        idx = np.full(total + 8, GUARD, np.int32)
+        rc, off = _grid_query_raw(g, x, y, r, idx, cap)
+        assert rc == total, cap  # the return value is the total even when it exceeds cap
+        assert np.array_equal(off, want_off), cap  # cand_off is complete
+        assert np.array_equal(idx[:cap], want_idx[:cap]), cap
+        assert (idx[cap:] == GUARD).all(), cap  # nothing is written behind cap
+    # count-only calls: cand_idx == NULL (whatever cap says), or cap == 0
+    for idx, cap in ((None, 0), (None, total), (np.full(total, GUARD, np.int32), 0)):
+        rc, off = _grid_query_raw(g, x, y, r, idx, cap)
+        assert rc == total and np.array_equal(off, want_off)
+        assert idx is None or (idx == GUARD).all()
+    rc, off = _grid_query_raw(g, x[:0], y[:0], r[:0], None, 0)  # nq == 0
+    assert rc == 0 and off[0] == 0
+
+
+def test_device_grid_built_on_one_thread_queried_from_another(frames):
+    import threading
+    (k0, d0), (k1, d1) = frames
+    bounds = (0.0, 0.0, 640.0, 480.0)
+    ref = ol.OracleGrid(k1, *bounds)
+    x, y = (k0["x"] + 3).astype(np.float32), (k0["y"] + 2).astype(np.float32)
+    # r = 5 lists fit the kernel's 16 inline slots per query; r = 60 lists go to its overflow segment
+    want = {rad: [ref.query(x[q], y[q], rad) for q in range(len(x))] for rad in (5.0, 60.0)}
+    assert max(len(w) for w in want[5.0]) <= 16 and sum(len(w) for w in want[5.0]) > 100
+    assert sum(len(w) > 16 for w in want[60.0]) > len(x) // 2
+    box = {}
+
+    def run(name, fn):
+        def body():
+            try:
+                box[name] = fn()
+            except BaseException as e:  # noqa: BLE001 -- re-raised on the test's thread below
+                box[name] = e
+        t = threading.Thread(target=body)
+        t.start()
+        t.join()
+        if isinstance(box[name], BaseException):
+            raise box[name]
+        return box[name]
+
+    g = run("build", lambda: orb.FrameGrid(k1, *bounds))
+    for rad in (5.0, 60.0):
+        off, idx = run("query", lambda: g.GetFeaturesInArea(x, y, np.full(len(x), rad, np.float32)))
+        for q in range(len(x)):
+            assert np.array_equal(idx[off[q]:off[q + 1]], want[rad][q]), (rad, q)
+    off, idx = g.GetFeaturesInArea(x, y, np.full(len(x), 60.0, np.float32))  # and from a third (this) thread
+    assert np.array_equal(idx, np.concatenate(want[60.0]))
+
+
+def test_device_grid_rejects_octave_outside_int16():
+    kp = np.zeros(3, orb.KP_DTYPE)
+    kp["x"], kp["y"], kp["octave"] = [5.0, 50.0, 100.0], [5.0, 50.0, 100.0], [0, 40000, 1]
+    with pytest.raises(orb.VsgError) as e:
+        orb.FrameGrid(kp, 0.0, 0.0, 640.0, 480.0)
+    assert e.value.code == -3  # VSG_ERR_UNSUPPORTED
+    kp["octave"] = [-32768, 32767, 1]  # the int16 range itself is exact
+    g, ref = orb.FrameGrid(kp, 0.0, 0.0, 640.0, 480.0), ol.OracleGrid(kp, 0.0, 0.0, 640.0, 480.0)
+    for lo, hi in ((-1, -1), (2, -1), (-1, 40), (32767, 32767)):
+        off, idx = g.GetFeaturesInArea([50.0], [50.0], [60.0], [lo], [hi])
+        assert idx.tolist() == ref.query(50.0, 50.0, 60.0, lo, hi).tolist(), (lo, hi)
+
+
 @pytest.mark.parametrize("seed,blocking", [(0, True), (1, False), (2, None)])
 def test_search_window_generic(frames, seed, blocking):
     """Common core of the Sim3 / relocalisation projection searches, SearchBySim3 and Fuse (per-query best)."""

@@ -249,11 +249,6 @@ struct vsg_vocab {
   double *d_weight = nullptr;  // same order
 };
 
-#define B_TRY(expr)                               \
-  do {                                            \
-    if ((expr) != hipSuccess) return VSG_ERR_HIP; \
-  } while (0)
-
 extern "C" {
 
 void vsg_vocab_destroy(vsg_vocab *v) {
@@ -266,8 +261,8 @@ void vsg_vocab_destroy(vsg_vocab *v) {
 int vsg_vocab_load(int device, const uint8_t *blob, size_t size, vsg_vocab **out) {
   if (!out || !blob) return VSG_ERR_INVALID;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
+  const int drc = vsg::use_device(device);
+  if (drc != VSG_OK) return drc;
   // parse like loadFromBinFile (:1478-1552)
   size_t pos = 0;
   auto rd = [&](void *dst, size_t n) {
@@ -322,7 +317,6 @@ int vsg_vocab_load(int device, const uint8_t *blob, size_t size, vsg_vocab **out
     r.node_id = i, r.word = word[i], r.pad = 0;
     wpos[posn[i]] = weight[i];
   }
-  B_TRY(hipSetDevice(device));
   vsg_vocab *v = new vsg_vocab();
   v->device = device, v->k = k, v->L = L, v->scoring = n1, v->weighting = n2, v->nnodes = nn, v->nwords = nwords;
   v->max_children = max_children;
@@ -485,7 +479,7 @@ int bow_enqueue(BowCall *b, vsg_vocab *voc, const uint8_t *desc, const uint8_t *
   uint8_t *hp = c->h_pin + pin_base, *dp = c->d_pin + pin_base, *dv = c->d_buf + dev_base;
   if (!d_desc) {
     memcpy(hp + oD, desc, 32 * N);
-    B_TRY(hipMemcpyAsync(dv + dD, hp + oD, 32 * N, hipMemcpyHostToDevice, c->stream));
+    TRY_HIP(hipMemcpyAsync(dv + dD, hp + oD, 32 * N, hipMemcpyHostToDevice, c->stream));
     d_desc = dv + dD;
   }
   int *s_word = (int *)(dv + dWord), *s_node = (int *)(dv + dNode);
@@ -498,7 +492,7 @@ int bow_enqueue(BowCall *b, vsg_vocab *voc, const uint8_t *desc, const uint8_t *
     hipLaunchKernelGGL(k_bow_descend<32>, dim3((n * 32 + 255) / 256), dim3(256), 0, c->stream, voc->d_rec, voc->d_weight,
                        voc->root_link, d_desc, n, voc->L - levelsup, s_word, s_node, s_w, (int *)(dp + b->oWord),
                        (int *)(dp + b->oNode), (double *)(dp + b->oW));
-  B_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   b->active = true;
   b->device_assembly = n <= kAsmMax;
   if (b->device_assembly) {
@@ -511,9 +505,9 @@ int bow_enqueue(BowCall *b, vsg_vocab *voc, const uint8_t *desc, const uint8_t *
     const int tf = voc->weighting == 0 || voc->weighting == 1;  // TF_IDF, TF: addWeight; IDF, BINARY: addIfNotExist
     uint64_t *s_sw = (uint64_t *)(dv + dSortW), *s_sn = (uint64_t *)(dv + dSortN);
     hipLaunchKernelGGL(k_bow_rank, dim3((n + 63) / 64), dim3(kAsmThreads), 0, c->stream, s_word, s_node, s_w, n, s_sw, s_sn);
-    B_TRY(hipGetLastError());
+    TRY_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_bow_assemble, dim3(2), dim3(kAsmThreads), 0, c->stream, s_sw, s_sn, s_w, n, tf, o);
-    B_TRY(hipGetLastError());
+    TRY_HIP(hipGetLastError());
     if (res) res->fv_bound = b->fv_bound, res->fv_valid = true;
   }
   return VSG_OK;
@@ -603,10 +597,10 @@ static int bow_transform(vsg_vocab *voc, const uint8_t *desc, vsg_frame *f, int 
     hipStreamSynchronize(c->stream);  // nothing this call launched outlives it (the next call rewrites the arena)
     return rc;
   }
-  if (b.active) B_TRY(hipStreamSynchronize(c->stream));
+  if (b.active) TRY_HIP(hipStreamSynchronize(c->stream));
   rc = vsg::bow_finish(&b, bow_ids, bow_vals, bow_cap, n_bow, fv_node, fv_off, fv_idx, fv_cap, n_fv, word_of, node_of,
                        weight_of);
-  if (b.uploaded) B_TRY(hipStreamSynchronize(c->stream));  // the host-assembled FeatureVector's copies read the arena
+  if (b.uploaded) TRY_HIP(hipStreamSynchronize(c->stream));  // the host-assembled FeatureVector's copies read the arena
   return rc;
 }
 

@@ -16,7 +16,19 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/vsg_orb.h"
+
+// a HIP call of an entry point: anything but hipSuccess ends the entry point with VSG_ERR_HIP
+#define TRY_HIP(expr)                             \
+  do {                                            \
+    if ((expr) != hipSuccess) return VSG_ERR_HIP; \
+  } while (0)
+
 namespace vsg {
+
+// hipSetDevice(device) behind a check of the ordinal: VSG_OK, VSG_ERR_NO_DEVICE (no such device) or VSG_ERR_HIP
+// (hidden: the library's exported symbols stay what they were)
+__attribute__((visibility("hidden"))) int use_device(int device);
 
 struct ThreadCtx {
   int device = -1;

@@ -21,14 +21,15 @@ std::mutex g_lds_mutex;
 size_t g_lds_limit[8][kMaxDevices];  // zero-initialised: "64 KB default" is applied on read
 }  // namespace
 
+int use_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
+  return hipSetDevice(device) == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+}
+
 ThreadCtx *thread_ctx(int device, int *rc) {
   if (rc) *rc = VSG_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    if (rc) *rc = VSG_ERR_NO_DEVICE;
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
+  if (use_device(device) != VSG_OK) {
     if (rc) *rc = VSG_ERR_NO_DEVICE;
     return nullptr;
   }
@@ -158,9 +159,7 @@ int vsg_thread_release(void) {
 // records of vsg_shard_record, bench.py's boundary state) need no second HIP runtime binding for it
 int vsg_copy_d2d_async(int device, void *dst, const void *src, size_t bytes, void *stream) {
   if (!dst || !src) return VSG_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return VSG_ERR_NO_DEVICE;
+  if (vsg::use_device(device) != VSG_OK) return VSG_ERR_NO_DEVICE;
   if (bytes == 0) return VSG_OK;
   return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? VSG_OK : VSG_ERR_HIP;
 }

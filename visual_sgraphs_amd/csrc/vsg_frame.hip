@@ -12,6 +12,10 @@
 // SGPRs, v_xor + v_bcnt).  Inputs are read from, and results written to, the calling thread's pinned arena straight
 // over PCIe: a call is  fill -> ONE launch -> sync -> ordered host pass (vsg_walks.h).  Nothing is allocated and
 // nothing runs on the NULL stream.
+//
+// The stand-alone Frame grid (vsg_grid_build / vsg_grid_query / vsg_grid_destroy) lives here too: a
+// vsg_grid is a frame block with the left grid alone, filled by the upload path (host_grid is the one
+// host build of the CSR) and searched by k_window_search in list mode (the one GetFeaturesInArea window walk).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -527,25 +531,23 @@ walk::CandView WindowCall::lists() const {
 
 namespace {
 
-#define F_TRY(expr)                               \
-  do {                                            \
-    if ((expr) != hipSuccess) return VSG_ERR_HIP; \
-  } while (0)
-
-// device layout of a frame for `cap` features
+// device layout of a frame for `cap` features.  grid_only: the block behind a vsg_grid -- the left grid and an (empty)
+// right cell table, which is all a list-mode window search without descriptors reads (GridEnt carries the keypoint
+// fields it tests); the blocks a grid never has are zero bytes long
 struct FrameLayout {
   size_t oK, oD, oU, oCS0, oE0, oCS1, oE1, oFvH, oFvN, oFvO, oFvI, total;
-  explicit FrameLayout(int cap) {
+  bool grid_only;
+  explicit FrameLayout(int cap, bool grid_only_ = false) : grid_only(grid_only_) {
     Stage st;
-    const size_t C = (size_t)cap + 1;
-    oK = st.add(C * sizeof(KeyPointPOD));
-    oD = st.add(C * 32);
-    oU = st.add(C * 4);
+    const size_t C = (size_t)cap + 1, X = grid_only ? 0 : C;
+    oK = st.add(X * sizeof(KeyPointPOD));
+    oD = st.add(X * 32);
+    oU = st.add(X * 4);
     oCS0 = st.add((kGridCells + 1) * 4);
     oE0 = st.add(C * sizeof(GridEnt));
     oCS1 = st.add((kGridCells + 1) * 4);
-    oE1 = st.add(C * sizeof(GridEnt));
-    oFvH = st.add(64), oFvN = st.add(C * 4), oFvO = st.add((C + 1) * 4), oFvI = st.add(C * 4);  // Frame::mFeatVec
+    oE1 = st.add(X * sizeof(GridEnt));
+    oFvH = st.add(X ? 64 : 0), oFvN = st.add(X * 4), oFvO = st.add(X ? (C + 1) * 4 : 0), oFvI = st.add(X * 4);  // Frame::mFeatVec
     total = st.total;
   }
 };
@@ -586,6 +588,65 @@ void set_bounds(vsg_frame *f, float min_x, float min_y, float max_x, float max_y
   f->invH = (float)kGridRows / (max_y - min_y);
 }
 
+// The device block of a frame for `capacity` features on `device`.  zero_fill: a frame that was created but never
+// uploaded has n = 0 AND all-zero cell_start arrays, so a search on it walks empty [0, 0) entry ranges instead of whatever
+// the allocation held.  The fill runs on the calling thread's own stream and is WAITED for: uploads and searches use
+// non-blocking streams, which the NULL stream's hipMemset is not ordered against (it could land after an upload and wipe
+// it).  A grid is uploaded by the call that creates it and skips the fill.  *ctx = the calling thread's context.
+int frame_alloc(int device, int capacity, const FrameLayout &L, bool zero_fill, vsg_frame *f, ThreadCtx **ctx) {
+  // (thread_ctx below checks the device again, but reports a failed hipSetDevice as VSG_ERR_NO_DEVICE; creating a
+  // frame or a grid has always answered VSG_ERR_HIP there, hence the check of its own)
+  const int drc = use_device(device);
+  if (drc != VSG_OK) return drc;
+  f->device = device;
+  f->capacity = capacity;
+  int rc = VSG_OK;
+  ThreadCtx *c = *ctx = thread_ctx(device, &rc);
+  if (!c) return rc;
+  if (hipMalloc((void **)&f->d_block, L.total) != hipSuccess) return VSG_ERR_HIP;
+  if (zero_fill &&
+      (hipMemsetAsync(f->d_block, 0, L.total, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) {
+    hipFree(f->d_block);
+    f->d_block = nullptr;
+    return VSG_ERR_HIP;
+  }
+  f->d_kps = (KeyPointPOD *)(f->d_block + L.oK);
+  f->d_desc = f->d_block + L.oD;
+  f->d_uright = (float *)(f->d_block + L.oU);
+  f->d_cell_start[0] = (int *)(f->d_block + L.oCS0);
+  f->d_ent[0] = (GridEnt *)(f->d_block + L.oE0);
+  f->d_cell_start[1] = (int *)(f->d_block + L.oCS1);
+  f->d_ent[1] = (GridEnt *)(f->d_block + L.oE1);
+  f->d_fv_hdr = (int *)(f->d_block + L.oFvH), f->d_fv_node = (int *)(f->d_block + L.oFvN);
+  f->d_fv_off = (int *)(f->d_block + L.oFvO), f->d_fv_idx = (int *)(f->d_block + L.oFvI);
+  return VSG_OK;
+}
+
+// What vsg_frame_upload and vsg_grid_build share: bounds and grid(s) [, keypoints, descriptors, mvuRight] of a frame
+// laid out as L.  The whole device image is assembled in the calling thread's pinned arena and goes up in ONE DMA.
+int frame_put(vsg_frame *f, ThreadCtx *c, const FrameLayout &L, const vsg_keypoint *keys, const uint8_t *desc,
+              const float *u_right, int n, int nleft, float min_x, float min_y, float max_x, float max_y) {
+  const int rc = ctx_reserve(c, L.total, 0);
+  if (rc != VSG_OK) return rc;
+  set_bounds(f, min_x, min_y, max_x, max_y);
+  f->n = n, f->nleft = nleft, f->has_uright = u_right != nullptr, f->fv_valid = false;
+  uint8_t *h = c->h_pin;
+  if (n && !L.grid_only) memcpy(h + L.oK, keys, (size_t)n * sizeof(vsg_keypoint));
+  if (desc && n) memcpy(h + L.oD, desc, (size_t)n * 32);
+  if (u_right && n) memcpy(h + L.oU, u_right, (size_t)n * 4);
+  const int nl = nleft == -1 ? n : nleft;
+  host_grid(keys, 0, nl, f->minX, f->minY, f->invW, f->invH, (int *)(h + L.oCS0), (GridEnt *)(h + L.oE0));
+  if (nleft != -1)
+    host_grid(keys, nleft, n - nleft, f->minX, f->minY, f->invW, f->invH, (int *)(h + L.oCS1), (GridEnt *)(h + L.oE1));
+  else
+    memset(h + L.oCS1, 0, (kGridCells + 1) * 4);
+  // only the used part of every block travels: [keys | desc | uright | grid] are contiguous up to the right grid
+  const size_t used = nleft != -1 ? L.oE1 + (size_t)(n - nleft + 1) * sizeof(GridEnt) : L.oCS1 + (kGridCells + 1) * 4;
+  TRY_HIP(hipMemcpyAsync(f->d_block, h, used, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipStreamSynchronize(c->stream));  // the frame may be searched from any thread from now on
+  return VSG_OK;
+}
+
 inline float radius_by_viewing_cos(float viewCos) {  // ORBmatcher::RadiusByViewingCos (ORBmatcher.cc:218-224)
   if (viewCos > 0.998) return 2.5f;
   return 4.0f;
@@ -606,38 +667,13 @@ int vsg_debug_call_profile(float us[4]) {
 int vsg_frame_create(int device, int capacity, vsg_frame **out) {
   if (!out || capacity < 1 || capacity > 32767) return VSG_ERR_INVALID;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
-  F_TRY(hipSetDevice(device));
   vsg_frame *f = new vsg_frame();
-  f->device = device;
-  f->capacity = capacity;
-  const FrameLayout L(capacity);
-  // zeroed: a frame that was created but never uploaded has n = 0 AND all-zero cell_start arrays, so a search on it
-  // walks empty [0, 0) entry ranges instead of whatever the allocation held.  The fill runs on the calling thread's own
-  // stream and is WAITED for: uploads and searches use non-blocking streams, which the NULL stream's hipMemset is not
-  // ordered against (it could land after an upload and wipe it).
-  int rc = VSG_OK;
-  ThreadCtx *c = thread_ctx(device, &rc);
-  if (!c) {
+  ThreadCtx *c = nullptr;
+  const int rc = frame_alloc(device, capacity, FrameLayout(capacity), true, f, &c);
+  if (rc != VSG_OK) {
     delete f;
     return rc;
   }
-  if (hipMalloc((void **)&f->d_block, L.total) != hipSuccess ||
-      hipMemsetAsync(f->d_block, 0, L.total, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-    if (f->d_block) hipFree(f->d_block);
-    delete f;
-    return VSG_ERR_HIP;
-  }
-  f->d_kps = (KeyPointPOD *)(f->d_block + L.oK);
-  f->d_desc = f->d_block + L.oD;
-  f->d_uright = (float *)(f->d_block + L.oU);
-  f->d_cell_start[0] = (int *)(f->d_block + L.oCS0);
-  f->d_ent[0] = (GridEnt *)(f->d_block + L.oE0);
-  f->d_cell_start[1] = (int *)(f->d_block + L.oCS1);
-  f->d_ent[1] = (GridEnt *)(f->d_block + L.oE1);
-  f->d_fv_hdr = (int *)(f->d_block + L.oFvH), f->d_fv_node = (int *)(f->d_block + L.oFvN);
-  f->d_fv_off = (int *)(f->d_block + L.oFvO), f->d_fv_idx = (int *)(f->d_block + L.oFvI);
   *out = f;
   return VSG_OK;
 }
@@ -661,28 +697,47 @@ int vsg_frame_upload(vsg_frame *f, const vsg_keypoint *keys, const uint8_t *desc
   int rc = VSG_OK;
   ThreadCtx *c = thread_ctx(f->device, &rc);
   if (!c) return rc;
-  const FrameLayout L(f->capacity);
-  rc = ctx_reserve(c, L.total, 0);
-  if (rc != VSG_OK) return rc;
-  set_bounds(f, min_x, min_y, max_x, max_y);
-  f->n = n, f->nleft = nleft, f->has_uright = u_right != nullptr, f->fv_valid = false;
-  f->h_kps.assign(keys, keys + n);
-  // the whole device image of the frame is assembled in the pinned arena and goes up in ONE DMA
-  uint8_t *h = c->h_pin;
-  if (n) memcpy(h + L.oK, keys, (size_t)n * sizeof(vsg_keypoint));
-  if (n) memcpy(h + L.oD, desc, (size_t)n * 32);
-  if (u_right && n) memcpy(h + L.oU, u_right, (size_t)n * 4);
-  const int nl = nleft == -1 ? n : nleft;
-  host_grid(keys, 0, nl, f->minX, f->minY, f->invW, f->invH, (int *)(h + L.oCS0), (GridEnt *)(h + L.oE0));
-  if (nleft != -1)
-    host_grid(keys, nleft, n - nleft, f->minX, f->minY, f->invW, f->invH, (int *)(h + L.oCS1), (GridEnt *)(h + L.oE1));
-  else
-    memset(h + L.oCS1, 0, (kGridCells + 1) * 4);
-  // only the used part of every block travels: [keys | desc | uright | grid] are contiguous up to the right grid
-  const size_t used = nleft != -1 ? L.oE1 + (size_t)(n - nleft + 1) * sizeof(GridEnt) : L.oCS1 + (kGridCells + 1) * 4;
-  F_TRY(hipMemcpyAsync(f->d_block, h, used, hipMemcpyHostToDevice, c->stream));
-  F_TRY(hipStreamSynchronize(c->stream));  // the frame may be searched from any thread from now on
+  rc = frame_put(f, c, FrameLayout(f->capacity), keys, desc, u_right, n, nleft, min_x, min_y, max_x, max_y);
+  if (rc == VSG_OK) f->h_kps.assign(keys, keys + n);
+  return rc;
+}
+
+// ---- the stand-alone Frame grid (include/vsg_orb.h: vsg_grid): a frame block that holds the left grid alone, built by
+// the upload path and searched by the list mode of k_window_search
+// (the handle is a vsg_frame behind an opaque name: nothing but these three entry points ever sees one)
+static vsg_frame *grid_frame(vsg_grid *g) { return (vsg_frame *)g; }
+
+void vsg_grid_destroy(vsg_grid *g) { vsg_frame_destroy(grid_frame(g)); }
+
+int vsg_grid_build(int device, const vsg_keypoint *kps, int n, float min_x, float min_y, float max_x, float max_y,
+                   vsg_grid **out) {
+  if (!out || n < 0 || (n > 0 && !kps) || n > 32767) return VSG_ERR_INVALID;
+  *out = nullptr;
+  // GridEnt carries the level in 16 bits; the queries compare it whole, so (unlike a frame's) it need not fit 0..15
+  for (int i = 0; i < n; i++)
+    if (kps[i].octave < INT16_MIN || kps[i].octave > INT16_MAX) return VSG_ERR_UNSUPPORTED;
+  const int cap = n > 0 ? n : 1;
+  const FrameLayout L(cap, true);
+  vsg_frame *g = new vsg_frame();
+  ThreadCtx *c = nullptr;
+  // no zero fill: the upload below writes everything a search reads (both cell tables and the entries they index),
+  // and the fill is a memset and a second stream wait inside a call whose whole cost is one small DMA and one wait
+  int rc = frame_alloc(device, cap, L, false, g, &c);
+  if (rc == VSG_OK) rc = frame_put(g, c, L, kps, nullptr, nullptr, n, -1, min_x, min_y, max_x, max_y);
+  if (rc != VSG_OK) {
+    vsg_frame_destroy(g);
+    return rc;
+  }
+  *out = (vsg_grid *)g;
   return VSG_OK;
+}
+
+int vsg_grid_query(vsg_grid *g, const float *x, const float *y, const float *r, const int32_t *min_level,
+                   const int32_t *max_level, int nq, int32_t *cand_off, int32_t *cand_idx, int cap) {
+  // A grid's block has no keypoint, descriptor or mvuRight arrays (FrameLayout's grid_only: those pointers alias the
+  // cell table).  This call never reads them: list mode, no query descriptors, kGateNone, left grid.  A search that
+  // does must not be pointed at a grid.
+  return vsg_frame_features_in_area(grid_frame(g), x, y, r, min_level, max_level, 0, nq, cand_off, cand_idx, cap);
 }
 
 // one launch: [undistortion +] grid from the keypoints where they already are (the extractor's output) + the two record
@@ -704,14 +759,14 @@ static int frame_from_extractor(vsg_frame *f, vsg_orb *h, int index, const vsg_k
   }
   set_bounds(f, min_x, min_y, max_x, max_y);
   f->n = n, f->nleft = -1, f->has_uright = false, f->fv_valid = false;
-  if (v.done) F_TRY(hipStreamWaitEvent(c->stream, v.done, 0));
+  if (v.done) TRY_HIP(hipStreamWaitEvent(c->stream, v.done, 0));
   hipLaunchKernelGGL(k_frame_grid_build, dim3(1), dim3(1024), 0, c->stream, v.d_kps, 0, n, f->minX, f->minY, f->invW,
                      f->invH, f->d_cell_start[0], f->d_ent[0], f->d_kps, v.d_desc, f->d_desc, f->d_cell_start[1], cam,
                      un_dev, (const int *)nullptr, 0, DepthPlane(), (float *)nullptr, (float *)nullptr,
                      (float *)nullptr);
-  F_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   if (!cam.distorted) f->h_kps.assign(kps_host, kps_host + n);  // beside the kernel
-  F_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipStreamSynchronize(c->stream));
   if (cam.distorted) {
     f->h_kps.assign((const vsg_keypoint *)un_pin, (const vsg_keypoint *)un_pin + n);
     if (keys_un_out && n) memcpy(keys_un_out, un_pin, (size_t)n * sizeof(vsg_keypoint));
@@ -908,16 +963,15 @@ int vsg_rgbd_depth_batch_device(int device, const void *d_depth, int depth_type,
     return VSG_ERR_INVALID;
   CamModel cam;
   if (!make_cam_model(K4, dist, ndist, &cam)) return VSG_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
-  F_TRY(hipSetDevice(device));
+  const int drc = use_device(device);
+  if (drc != VSG_OK) return drc;
   P.base = (const uint8_t *)d_depth;
   const size_t recs = (size_t)nframes * capacity;
   // stream == NULL is the caller's NULL stream: the launch is ordered on both sides of it
   hipLaunchKernelGGL(k_rgbd_batch, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const KeyPointPOD *)d_kps, d_counts, capacity, nframes, frame_stride, P, cam, d_u_right,
                      d_depth_out);
-  F_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   return VSG_OK;
 }
 
@@ -958,9 +1012,9 @@ int vsg_frame_copy_grid(vsg_frame *f, int right, int32_t *cell_start, int32_t *e
   if (rc != VSG_OK) return rc;
   int *hcs = (int *)c->h_pin;
   GridEnt *he = (GridEnt *)(c->h_pin + (((kGridCells + 1) * 4 + 63) & ~63));
-  F_TRY(hipMemcpyAsync(hcs, f->d_cell_start[right], (kGridCells + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-  F_TRY(hipMemcpyAsync(he, f->d_ent[right], (size_t)f->capacity * sizeof(GridEnt), hipMemcpyDeviceToHost, c->stream));
-  F_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipMemcpyAsync(hcs, f->d_cell_start[right], (kGridCells + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+  TRY_HIP(hipMemcpyAsync(he, f->d_ent[right], (size_t)f->capacity * sizeof(GridEnt), hipMemcpyDeviceToHost, c->stream));
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(cell_start, hcs, (kGridCells + 1) * 4);
   const int ne = hcs[kGridCells];
   if (ne < 0 || ne > f->capacity) return VSG_ERR_HIP;

@@ -285,18 +285,13 @@ int grid_for(long items_per_block_4waves, long cap) {
   return (int)std::max(1L, std::min(g, cap));
 }
 
-#define K_TRY(expr)                               \
-  do {                                            \
-    if ((expr) != hipSuccess) return VSG_ERR_HIP; \
-  } while (0)
-
 // a device array that grows by 1.5x: the first `used` elements are kept, the new tail is filled with `fill` bytes
 template <class T>
 int grow(T **p, size_t *cap, size_t need, size_t used, int fill, hipStream_t st) {
   if (need <= *cap) return VSG_OK;
   size_t nc = std::max(need, std::max(*cap + *cap / 2, (size_t)1024));
   T *np = nullptr;
-  K_TRY(hipMalloc((void **)&np, nc * sizeof(T)));
+  TRY_HIP(hipMalloc((void **)&np, nc * sizeof(T)));
   hipError_t e = hipSuccess;
   if (used) e = hipMemcpyAsync(np, *p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(np + used, fill, (nc - used) * sizeof(T), st);
@@ -379,8 +374,8 @@ struct vsg_kfdb {
     const int n = (int)std::max(tomb.size(), dead.size());
     hipLaunchKernelGGL(k_kfdb_mark, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)(c->d_pin + oT),
                        (int)tomb.size(), d_ent_word, (const int *)(c->d_pin + oD), (int)dead.size(), d_slot_dead);
-    K_TRY(hipGetLastError());
-    K_TRY(hipStreamSynchronize(c->stream));
+    TRY_HIP(hipGetLastError());
+    TRY_HIP(hipStreamSynchronize(c->stream));
     return VSG_OK;
   }
 
@@ -429,29 +424,29 @@ static int kfdb_query(vsg_kfdb *db, int kind, uint64_t qid, const int32_t *ids, 
   double *qv = (double *)(dv + dV);
   unsigned long long *key = (unsigned long long *)(dv + dKey);
   hipStream_t st = c->stream;
-  K_TRY(hipMemcpyAsync(q, hp + pQ, 4 * N, hipMemcpyHostToDevice, st));
-  K_TRY(hipMemcpyAsync(qv, hp + pV, 8 * N, hipMemcpyHostToDevice, st));
-  if (!conn.empty()) K_TRY(hipMemcpyAsync(cn, hp + pC, 4 * conn.size(), hipMemcpyHostToDevice, st));
-  K_TRY(hipMemsetAsync(cnt, 0, 4 * NI, st));
-  K_TRY(hipMemsetAsync(key, 0xFF, 8 * NI, st));
-  K_TRY(hipMemsetAsync(ctrl, 0, 64, st));
+  TRY_HIP(hipMemcpyAsync(q, hp + pQ, 4 * N, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(qv, hp + pV, 8 * N, hipMemcpyHostToDevice, st));
+  if (!conn.empty()) TRY_HIP(hipMemcpyAsync(cn, hp + pC, 4 * conn.size(), hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemsetAsync(cnt, 0, 4 * NI, st));
+  TRY_HIP(hipMemsetAsync(key, 0xFF, 8 * NI, st));
+  TRY_HIP(hipMemsetAsync(ctrl, 0, 64, st));
   const size_t lds = 4 * N;
   const int gi = (nidx + 255) / 256;
   hipLaunchKernelGGL(k_kfdb_count, dim3(grid_for(n_slots, 2048)), dim3(256), lds, st, q, n, db->d_slot_off,
                      db->d_slot_len, db->d_slot_kf, db->d_slot_dead, n_slots, db->d_ent_word, cnt, key);
-  K_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_kfdb_words, dim3(gi), dim3(256), 0, st, nidx, kind, (unsigned long long)qid, cn, (int)conn.size(),
                      cnt, key, db->d_st, ctrl);
-  K_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_kfdb_select, dim3(gi), dim3(256), 0, st, nidx, cnt, key, ctrl, cand);
-  K_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_kfdb_score, dim3(grid_for(nidx, 1024)), dim3(256), lds, st, q, qv, n, db->scoring, kind, ctrl, cand,
                      db->d_kf_bow, db->d_slot_off, db->d_slot_len, db->d_ent_word, db->d_ent_val, db->d_st);
-  K_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_kfdb_covis, dim3(gi), dim3(256), 0, st, kind, (unsigned long long)qid, ctrl, cand, key, db->d_cov,
                      db->d_st, (int *)(dp + pH), (CandRec *)(dp + pO));
-  K_TRY(hipGetLastError());
-  K_TRY(hipStreamSynchronize(st));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(st));
   const int nc = *(const int *)(hp + pH);
   if (nc < 0 || nc > nidx) return VSG_ERR_HIP;
   const CandRec *r = (const CandRec *)(hp + pO);
@@ -500,12 +495,12 @@ int vsg_vocab_score(vsg_vocab *voc, const int32_t *ids, const double *vals, int 
   memcpy(hp + pQ, ids, 4 * N), memcpy(hp + pV, vals, 8 * N), memcpy(hp + pOff, off, 4 * (M + 1));
   memcpy(hp + pI, m_ids, 4 * E), memcpy(hp + pW, m_vals, 8 * E);
   // one copy of the whole staged block (the device layout mirrors the pinned one up to the output)
-  K_TRY(hipMemcpyAsync(dv, hp, pOut, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(dv, hp, pOut, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_vocab_score, dim3(grid_for(m, 1024)), dim3(256), 4 * N, c->stream, (const int *)(dv + dQ),
                      (const double *)(dv + dV), n, scoring, (const int *)(dv + dOff), (const int *)(dv + dI),
                      (const double *)(dv + dW), m, (double *)(c->d_pin + pOut));
-  K_TRY(hipGetLastError());
-  K_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(out, hp + pOut, 8 * M);
   return VSG_OK;
 }
@@ -554,13 +549,13 @@ int vsg_kfdb_add(vsg_kfdb *db, uint64_t kf_id, int32_t map_id, const int32_t *bo
   if ((rc = vsg::ctx_reserve(c, p.total, 0)) != VSG_OK) return rc;
   if (n > 0) {
     memcpy(c->h_pin + pI, bow_ids, 4 * N), memcpy(c->h_pin + pV, bow_vals, 8 * N);
-    K_TRY(hipMemcpyAsync(db->d_ent_word + ne, c->h_pin + pI, 4 * N, hipMemcpyHostToDevice, st));
-    K_TRY(hipMemcpyAsync(db->d_ent_val + ne, c->h_pin + pV, 8 * N, hipMemcpyHostToDevice, st));
+    TRY_HIP(hipMemcpyAsync(db->d_ent_word + ne, c->h_pin + pI, 4 * N, hipMemcpyHostToDevice, st));
+    TRY_HIP(hipMemcpyAsync(db->d_ent_val + ne, c->h_pin + pV, 8 * N, hipMemcpyHostToDevice, st));
   }
   hipLaunchKernelGGL(k_kfdb_new_slot, dim3(1), dim3(64), 0, st, db->d_slot_off, db->d_slot_len, db->d_slot_kf,
                      db->d_slot_dead, db->d_kf_bow, (int)s, (uint32_t)ne, n, i);
-  K_TRY(hipGetLastError());
-  K_TRY(hipStreamSynchronize(st));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(st));
   vsg_kfdb::Slot sl;
   sl.kf = i, sl.off = (uint32_t)ne, sl.live = n;
   sl.ids.assign(bow_ids, bow_ids + n), sl.alive.assign(N, 1);
@@ -680,8 +675,8 @@ int vsg_kfdb_set_covisibility(vsg_kfdb *db, const uint64_t *kf_ids, const int32_
   memcpy(c->h_pin + oR, rows.data(), 4 * rows.size());
   hipLaunchKernelGGL(k_kfdb_set_cov, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const int *)(c->d_pin + oR), n,
                      db->d_cov);
-  K_TRY(hipGetLastError());
-  K_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(c->stream));
   return VSG_OK;
 }
 

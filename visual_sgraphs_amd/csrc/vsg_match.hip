@@ -567,21 +567,9 @@ __global__ __launch_bounds__(128) void k_distinctive(const uint8_t *desc, const 
 // out in the pinned arena and go up in ONE DMA into the device arena (they are read many times by the kernels),
 // results come back through the pinned arena.  No allocation, no NULL-stream launch in steady state.
 
-#define M_TRY(expr)                      \
-  do {                                   \
-    hipError_t _e = (expr);              \
-    if (_e != hipSuccess) return VSG_ERR_HIP; \
-  } while (0)
-
 using vsg::ThreadCtx;
 using vsg::Stage;
 namespace walk = vsg::walk;
-
-int use_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return VSG_ERR_NO_DEVICE;
-  return hipSetDevice(device) == hipSuccess ? VSG_OK : VSG_ERR_NO_DEVICE;
-}
 
 // merge-join of two FeatureVectors (ORBmatcher.cc:247-405 loop skeleton incl. lower_bound jumps)
 void join_nodes(const int *idA, const int *offA, int nA, const int *idB, const int *offB, int nB,
@@ -629,13 +617,13 @@ static int candidate_entries(int device, const uint8_t *q_desc, int n_q, const i
   for (int q = 0; q < n_q; q++)
     for (int k = cand_off[q]; k < cand_off[q + 1]; k++) qof[k] = q;
   memcpy(h + oIdx, cand_idx, (size_t)ncand * 4);
-  M_TRY(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
   const uint8_t *d = c->d_buf;
   hipLaunchKernelGGL(k_cand_dist, dim3((ncand + 255) / 256), dim3(256), 0, c->stream, d + oQ, (const int *)(d + oOf),
                      (const int *)(d + oIdx), d + oT, t_octave ? d + oOct : (const uint8_t *)nullptr, ncand,
                      (uint32_t *)(c->d_pin + oEnt));
-  M_TRY(hipGetLastError());
-  M_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(c->stream));
   *ent = (const uint32_t *)(h + oEnt);
   return VSG_OK;
 }
@@ -703,18 +691,18 @@ static int search_by_bow(int device, int mode, int nleftB, const uint8_t *descA,
   memcpy(h + oIB, idxB, (size_t)nIdxB * 4);
   if (!dDescA) memcpy(h + oDA, descA, (size_t)nA * 32);
   if (!dDescB) memcpy(h + oDB, descB, (size_t)nB * 32);
-  M_TRY(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
   uint8_t *d = c->d_buf;
   int *dMA = (int *)(d + oMA), *dMB = (int *)(d + oMB);  // mode 0: dMB = match_f, dMA = the claim scratch; mode 1: the reverse
-  M_TRY(hipMemsetAsync(mode == 0 ? dMB : dMA, 0xFF, (size_t)(mode == 0 ? nB : nA) * 4, c->stream));  // -1
+  TRY_HIP(hipMemsetAsync(mode == 0 ? dMB : dMA, 0xFF, (size_t)(mode == 0 ? nB : nA) * 4, c->stream));  // -1
   hipLaunchKernelGGL(k_search_by_bow, dim3(npairs), dim3(256), 0, c->stream, (const NodePair *)(d + oP), npairs,
                      FvDev{}, FvDev{}, dDescA ? dDescA : d + oDA, d + oVA, (const int *)(d + oIA), dDescB ? dDescB : d + oDB, d + oVB,
                      (const int *)(d + oIB), nnratio, mode, nleftB, dMA, mode == 0 ? dMB : (int *)nullptr,
                      mode == 0 ? dMA : dMB);
-  M_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   int *hOut = (int *)(h + in_bytes);
-  M_TRY(hipMemcpyAsync(hOut, mode == 0 ? dMB : dMA, (size_t)nOut * 4, hipMemcpyDeviceToHost, c->stream));
-  M_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipMemcpyAsync(hOut, mode == 0 ? dMB : dMA, (size_t)nOut * 4, hipMemcpyDeviceToHost, c->stream));
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(out, hOut, (size_t)nOut * 4);
   // rotation consistency (:407-425 / :879-897)
   return bow_rotation_filter(out, nOut, mode, angleA, angleB, checkOri != 0);
@@ -759,7 +747,7 @@ int bow_search_enqueue(BowSearchCall *s, int mode, vsg_frame *A, const uint8_t *
                      A->d_desc, dp + oVA, (const int *)nullptr, B->d_desc, dp + oVB, (const int *)nullptr, nnratio, mode,
                      mode == 0 ? B->nleft : -1, mode == 1 ? out : (int *)nullptr, mode == 0 ? out : (int *)nullptr,
                      (int *)(c->d_buf + dev_base));
-  M_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   s->active = true;
   return VSG_OK;
 }
@@ -792,7 +780,7 @@ static int search_by_bow_resident(int mode, vsg_frame *A, const uint8_t *validA,
     hipStreamSynchronize(c->stream);  // nothing this call launched outlives it (the next call rewrites the arena)
     return rc;
   }
-  if (s.active) M_TRY(hipStreamSynchronize(c->stream));
+  if (s.active) TRY_HIP(hipStreamSynchronize(c->stream));
   return vsg::bow_search_finish(&s, check_orientation, out);
 }
 
@@ -836,16 +824,16 @@ static int search_triangulation(int device, const uint8_t *desc1, const uint8_t 
     memcpy(h + oOk, pair_ok, ok_words * 4);
     memcpy(h + oOff, pair_off, (size_t)(npairs + 1) * 4);
   }
-  M_TRY(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
   uint8_t *d = c->d_buf;
-  M_TRY(hipMemsetAsync(d + oM, 0xFF, (size_t)n1 * 4, c->stream));
+  TRY_HIP(hipMemsetAsync(d + oM, 0xFF, (size_t)n1 * 4, c->stream));
   hipLaunchKernelGGL(k_search_triangulation, dim3((npairs + 3) / 4), dim3(256), 0, c->stream, (const NodePair *)(d + oP),
                      npairs, dDesc1 ? dDesc1 : d + oD1, d + oE1, (const int *)(d + oI1), dDesc2 ? dDesc2 : d + oD2, d + oE2,
                      (const int *)(d + oI2), pair_ok ? (const uint32_t *)(d + oOk) : (const uint32_t *)nullptr,
                      pair_ok ? (const int *)(d + oOff) : (const int *)nullptr, (int *)(d + oM));
-  M_TRY(hipGetLastError());
-  M_TRY(hipMemcpyAsync(h + oM, d + oM, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
-  M_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipMemcpyAsync(h + oM, d + oM, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(matches12, h + oM, (size_t)n1 * 4);
   return bow_rotation_filter(matches12, n1, 1, angle1, angle2, check_orientation != 0);
 }
@@ -873,12 +861,12 @@ int vsg_hamming_pairs(int device, const uint8_t *a, int na, const uint8_t *b, in
   memcpy(h + oB, b, (size_t)nb * 32);
   memcpy(h + oIA, ia, (size_t)npairs * 4);
   memcpy(h + oIB, ib, (size_t)npairs * 4);
-  M_TRY(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
   const uint8_t *d = c->d_buf;
   hipLaunchKernelGGL(k_hamming_pairs, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, d + oA, d + oB,
                      (const int *)(d + oIA), (const int *)(d + oIB), npairs, (int *)(c->d_pin + oD));
-  M_TRY(hipGetLastError());
-  M_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(dist, h + oD, (size_t)npairs * 4);
   return VSG_OK;
 }
@@ -888,14 +876,13 @@ int vsg_hamming_block_best2_device(int device, const uint8_t *d_a, const uint8_t
                                    int nblocks, int max_rows, int32_t *d_best, int32_t *d_second,
                                    int32_t *d_argbest, void *stream) {
   if (!d_a || !d_b || !d_best || !d_second || !d_argbest || nblocks < 1 || max_rows < 1) return VSG_ERR_INVALID;
-  int rc = use_device(device);
-  if (rc != VSG_OK) return rc;
+  if (vsg::use_device(device) != VSG_OK) return VSG_ERR_NO_DEVICE;
   dim3 grid((max_rows + kBest2Rows - 1) / kBest2Rows, nblocks);
   // stream == NULL is the caller's NULL stream (see vsg_orb_extract_batch_device for how the extractor orders itself
   // against it)
   hipLaunchKernelGGL(k_block_best2_mfma, grid, dim3(256), 0, (hipStream_t)stream, d_a, d_b, block_stride_bytes,
                      d_counts_a, d_counts_b, count_stride, max_rows, max_rows, max_rows, d_best, d_second, d_argbest);
-  M_TRY(hipGetLastError());
+  TRY_HIP(hipGetLastError());
   return VSG_OK;
 }
 
@@ -915,14 +902,14 @@ int vsg_hamming_block_best2(int device, const uint8_t *a, int na, const uint8_t 
   uint8_t *h = c->h_pin;
   memcpy(h + oA, a, (size_t)na * 32);
   if (nb) memcpy(h + oB, b, (size_t)nb * 32);
-  M_TRY(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
   const uint8_t *d = c->d_buf;
   int *d1 = (int *)(c->d_pin + o1), *d2 = (int *)(c->d_pin + o2), *d3 = (int *)(c->d_pin + o3);
   const dim3 grid((na + kBest2Rows - 1) / kBest2Rows, 1);
   hipLaunchKernelGGL(k_block_best2_mfma, grid, dim3(256), 0, c->stream, d + oA, d + oB, (size_t)0,
                      (const int *)nullptr, (const int *)nullptr, 0, na, nb, na, d1, d2, d3);
-  M_TRY(hipGetLastError());
-  M_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(best, h + o1, (size_t)na * 4);
   memcpy(second, h + o2, (size_t)na * 4);
   memcpy(argbest, h + o3, (size_t)na * 4);
@@ -1025,7 +1012,7 @@ int vsg_search_by_projection_last(int device, const uint8_t *q_desc, const float
                                   uint8_t *train_blocked, int n_t, int th_high, int check_orientation,
                                   int32_t *train_match) {
   if (!cand_off || !train_blocked || !train_match || n_q < 0 || n_t < 0) return VSG_ERR_INVALID;
-  if (n_q == 0 || n_t == 0) return use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
+  if (n_q == 0 || n_t == 0) return vsg::use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
   const uint32_t *ent = nullptr;
   int rc = candidate_entries(device, q_desc, n_q, cand_off, cand_idx, t_desc, nullptr, n_t, &ent);
   if (rc != VSG_OK) return rc;
@@ -1039,7 +1026,7 @@ int vsg_search_by_projection_local(int device, const uint8_t *q_desc, const uint
                                    const int32_t *t_octave, uint8_t *train_blocked, int n_t, float nnratio,
                                    int32_t *train_match) {
   if (!cand_off || !train_blocked || !train_match || !t_octave || n_q < 0 || n_t < 0) return VSG_ERR_INVALID;
-  if (n_q == 0 || n_t == 0) return use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
+  if (n_q == 0 || n_t == 0) return vsg::use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
   const uint32_t *ent = nullptr;
   int rc = candidate_entries(device, q_desc, n_q, cand_off, cand_idx, t_desc, t_octave, n_t, &ent);
   if (rc != VSG_OK) return rc;
@@ -1067,11 +1054,11 @@ int vsg_distinctive_descriptors(int device, const uint8_t *desc, const int32_t *
   uint8_t *h = c->h_pin;
   if (n) memcpy(h + oD, desc, (size_t)n * 32);
   memcpy(h + oOff, off, (size_t)(ngroups + 1) * 4);
-  M_TRY(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_distinctive, dim3(ngroups), dim3(128), 0, c->stream, c->d_buf + oD, (const int *)(c->d_buf + oOff),
                      (int *)(c->d_pin + oB));
-  M_TRY(hipGetLastError());
-  M_TRY(hipStreamSynchronize(c->stream));
+  TRY_HIP(hipGetLastError());
+  TRY_HIP(hipStreamSynchronize(c->stream));
   memcpy(best, h + oB, (size_t)ngroups * 4);
   return VSG_OK;
 }
@@ -1081,7 +1068,7 @@ int vsg_search_window(int device, const uint8_t *q_desc, const uint8_t *query_bl
                       int n_t, int th_high, int32_t *q_best_idx, int32_t *q_best_dist, int32_t *train_match) {
   if (!cand_off || !q_best_idx || !q_best_dist || n_q < 0 || n_t < 0) return VSG_ERR_INVALID;
   for (int q = 0; q < n_q; q++) q_best_idx[q] = -1, q_best_dist[q] = 256;
-  if (n_q == 0 || n_t == 0) return use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
+  if (n_q == 0 || n_t == 0) return vsg::use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
   const uint32_t *ent = nullptr;
   int rc = candidate_entries(device, q_desc, n_q, cand_off, cand_idx, t_desc, nullptr, n_t, &ent);
   if (rc != VSG_OK) return rc;
@@ -1108,7 +1095,7 @@ int vsg_search_for_initialization(int device, const uint8_t *desc1, const float 
                                   int32_t *matches12) {
   if (!cand_off || !matches12 || !octave1 || n1 < 0 || n2 < 0) return VSG_ERR_INVALID;
   for (int i = 0; i < n1; i++) matches12[i] = -1;
-  if (n1 == 0 || n2 == 0) return use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
+  if (n1 == 0 || n2 == 0) return vsg::use_device(device) == VSG_OK ? 0 : VSG_ERR_NO_DEVICE;
   const uint32_t *ent = nullptr;
   int rc = candidate_entries(device, desc1, n1, cand_off, cand_idx, desc2, nullptr, n2, &ent);
   if (rc != VSG_OK) return rc;

@@ -22,6 +22,7 @@
 
 #include "../../include/vsg_orb.h"
 #include "vsg_common.h"
+#include "vsg_ctx.h"
 
 namespace {
 
@@ -167,9 +168,9 @@ int vsg_shard_create(int device, int rank, int world, const uint8_t id[128], int
     t_serr = "RCCL (librccl.so.1) could not be loaded";
     return VSG_ERR_UNSUPPORTED;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VSG_ERR_NO_DEVICE;
-  S_HIP(hipSetDevice(device));
+  const int drc = vsg::use_device(device);
+  if (drc == VSG_ERR_HIP) t_serr = std::string("hipSetDevice(device): ") + hipGetErrorString(hipGetLastError());
+  if (drc != VSG_OK) return drc;
   vsg_shard *s = new vsg_shard();
   s->device = device, s->rank = rank, s->world = world, s->cap = capacity, s->frames = frames_per_rank;
   s->rec = vsg_shard_record_bytes(capacity);
