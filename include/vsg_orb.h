@@ -622,6 +622,45 @@ int vsg_frame_search_by_projection_kf(vsg_frame *cur, int n_q, const uint8_t *mp
                                       const float *radius, const int32_t *predicted_level, const float *kf_angle,
                                       int orb_dist, int check_orientation, uint8_t *occupied, int32_t *train_match);
 
+/* The two searches above with their geometry on the device: the map points are those of a vsg_mappoints store, the
+ * projection loop runs as a kernel in front of the window search (one enqueue, one wait), and only poses and slot lists
+ * cross to the device.  Float arithmetic in a fixed order, one rounding per operation.  Frames with
+ * Nleft != -1: VSG_ERR_UNSUPPORTED.  pose->n_levels <= nlevels <= 16.
+ *
+ * int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (ORBmatcher.cc:1667-1878)
+ * as Tracking::TrackWithMotionModel calls it (Tracking.cc:2945-2965).  last = the resident LastFrame (its octaves are read
+ * on the device, its angles from the host mirror); last_slots[i], one entry per feature of last, = the slot of
+ * LastFrame.mvpMapPoints[i], or < 0 for "no map point, or mvbOutlier[i]" (:1688-1691).  cur_pose / last_pose =
+ * CurrentFrame / LastFrame.GetPose() with the current camera's intrinsics; mb = CurrentFrame.mb, mono = bMono: bForward /
+ * bBackward (:1677-1684) are derived here.  The invzc < 0 test, Pinhole::project, the bounds (:1699-1709), the radius
+ * th * mvScaleFactors[nLastOctave] (:1715), the level window (:1719-1724) and ur = uv(0) - mbf * invzc (:1744) follow.
+ * Return value, train_blocked and the rotation filter are those of vsg_frame_search_by_projection_last given the
+ * projected points in order; train_match[i2] = index of the LAST-FRAME FEATURE whose map point feature i2 takes.
+ * Optional outs: *direction (0 neither, 1 bForward, 2 bBackward); per last-frame feature projected[i] (reached
+ * GetFeaturesInArea), u[i], v[i], ur[i] (0 where not projected).  A retry with 2 * th (Tracking.cc:2956-2961) is the
+ * same call with another th: nothing else is sent again.  A slot >= capacity, last_slots == NULL, or a feature with a
+ * slot whose octave lies outside [0, nlevels): VSG_ERR_INVALID, before anything is enqueued. */
+int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *mp, const int32_t *last_slots,
+                                const vsg_frame_pose *cur_pose, const vsg_frame_pose *last_pose, float mb, int mono,
+                                float th, const float *scale_factors, int nlevels, int check_orientation,
+                                uint8_t *train_blocked, int32_t *train_match, int *direction, uint8_t *projected, float *u,
+                                float *v, float *ur);
+
+/* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, th,
+ * ORBdist) (ORBmatcher.cc:1880-2000) as Tracking::Relocalization calls it (Tracking.cc:3805, :3819).  Query i = slot
+ * slots[i] = pKF->GetMapPointMatches()[i] for the n entries that hold a map point; skip[i] != 0 (NULL:
+ * none) = isBad() || sAlreadyFound.count(pMP) (:1901).  Projection WITHOUT a sign test on the depth, the bounds, the band
+ * 0.8f * mfMinDistance .. 1.2f * mfMaxDistance, PredictScale and radius = th * mvScaleFactors[nPredictedLevel]
+ * (:1904-1930) follow.  kf_angle[i] = pKF->mvKeysUn[i].angle of query i (may be NULL when check_orientation == 0).
+ * Return value, occupied and train_match (= query index) are those of vsg_frame_search_by_projection_kf given the
+ * projected points in order.  Optional outs per query: projected[i], u[i], v[i], predicted_level[i] (0 where not
+ * projected).  slots == NULL or a slot outside [0, capacity): VSG_ERR_INVALID, before anything is enqueued. */
+int vsg_frame_search_keyframe_points(vsg_frame *cur, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                                     const vsg_frame_pose *pose, float th, int orb_dist, const float *scale_factors,
+                                     int nlevels, int check_orientation, const float *kf_angle, uint8_t *occupied,
+                                     int32_t *train_match, uint8_t *projected, float *u, float *v,
+                                     int32_t *predicted_level);
+
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, S12, th) (ORBmatcher.h:76,
  * ORBmatcher.cc:1448-1665).  Direction 1 (:1489-1565): for each KF1 feature i1 with a usable, not yet matched map
  * point that projects into KF2: idx1[k] = i1, its descriptor, (u, v, radius, predicted level) in KF2; direction 2

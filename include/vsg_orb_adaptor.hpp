@@ -804,6 +804,70 @@ class ResidentMatcher {
     return rc;
   }
 
+  // int SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th, const bool bMono)
+  // (ORBmatcher.h:50, ORBmatcher.cc:1667-1878) with the geometry on the device (vsg_frame_search_last_frame): LastFrame is
+  // resident, lastSlots[i] = the slot of LastFrame.mvpMapPoints[i] in mp, or -1 for "no map point, or mvbOutlier[i]".
+  // curPose / lastPose = the two frames' GetPose() as FramePose; mb = CurrentFrame.mb.  trainMatch[i2] = the LAST-FRAME
+  // feature whose map point CurrentFrame's feature i2 takes.  The retry of Tracking.cc:2956-2961 is the same call with
+  // 2 * th.  out (optional): bForward / bBackward as 1 / 2, and per last-frame feature projected, u, v, ur.
+  struct LastFrameProjection {
+    int direction = 0;
+    std::vector<uint8_t> projected;
+    std::vector<float> u, v, ur;
+  };
+  int SearchByProjection(ResidentFrame &CurrentFrame, ResidentFrame &LastFrame, const ResidentMapPoints &mp,
+                         const std::vector<int32_t> &lastSlots, const FramePose &curPose, const FramePose &lastPose, float mb,
+                         float th, bool bMono, const std::vector<float> &mvScaleFactors, std::vector<uint8_t> &trainBlocked,
+                         std::vector<int32_t> &trainMatch, LastFrameProjection *out = nullptr) const {
+    const int n = LastFrame.N();
+    if ((int)lastSlots.size() != n) check(VSG_ERR_INVALID, "vsg_frame_search_last_frame");
+    trainMatch.assign(CurrentFrame.N() > 0 ? CurrentFrame.N() : 1, -1);
+    trainBlocked.resize(trainMatch.size(), 0);
+    const size_t m = n > 0 ? n : 1;
+    if (out) out->projected.assign(m, 0), out->u.assign(m, 0.f), out->v.assign(m, 0.f), out->ur.assign(m, 0.f);
+    std::vector<int32_t> none(1, -1);
+    const int rc = vsg_frame_search_last_frame(
+        CurrentFrame.handle(), LastFrame.handle(), mp.handle(), n ? lastSlots.data() : none.data(), &curPose, &lastPose, mb,
+        bMono ? 1 : 0, th, mvScaleFactors.data(), (int)mvScaleFactors.size(), mbCheckOrientation, trainBlocked.data(),
+        trainMatch.data(), out ? &out->direction : nullptr, out ? out->projected.data() : nullptr,
+        out ? out->u.data() : nullptr, out ? out->v.data() : nullptr, out ? out->ur.data() : nullptr);
+    check(rc, "vsg_frame_search_last_frame");
+    trainMatch.resize(CurrentFrame.N()), trainBlocked.resize(CurrentFrame.N());
+    if (out) out->projected.resize(n), out->u.resize(n), out->v.resize(n), out->ur.resize(n);
+    return rc;
+  }
+
+  // int SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint *> &sAlreadyFound, const float th,
+  // const int ORBdist) (ORBmatcher.h:54, ORBmatcher.cc:1880-2000) with the geometry on the device
+  // (vsg_frame_search_keyframe_points): slots[i] = the slot of the i-th map point of pKF->GetMapPointMatches(), kfAngle[i] =
+  // pKF->mvKeysUn[.].angle of its feature, skip[i] != 0 = isBad() || sAlreadyFound.count(pMP) (nullptr: none).
+  // occupied[i2] = CurrentFrame.mvpMapPoints[i2] != NULL (in / out); trainMatch[i2] = query index.
+  struct KeyFrameProjection {
+    std::vector<uint8_t> projected;
+    std::vector<float> u, v;
+    std::vector<int32_t> level;
+  };
+  int SearchByProjection(ResidentFrame &CurrentFrame, const ResidentMapPoints &mp, const std::vector<int32_t> &slots,
+                         const std::vector<float> &kfAngle, const uint8_t *skip, const FramePose &pose, float th, int ORBdist,
+                         const std::vector<float> &mvScaleFactors, std::vector<uint8_t> &occupied,
+                         std::vector<int32_t> &trainMatch, KeyFrameProjection *out = nullptr) const {
+    const int n = (int)slots.size();
+    if (mbCheckOrientation && (int)kfAngle.size() != n) check(VSG_ERR_INVALID, "vsg_frame_search_keyframe_points");
+    trainMatch.assign(CurrentFrame.N() > 0 ? CurrentFrame.N() : 1, -1);
+    occupied.resize(trainMatch.size(), 0);
+    const size_t m = n > 0 ? n : 1;
+    if (out) out->projected.assign(m, 0), out->u.assign(m, 0.f), out->v.assign(m, 0.f), out->level.assign(m, 0);
+    const int rc = vsg_frame_search_keyframe_points(
+        CurrentFrame.handle(), mp.handle(), n, slots.data(), skip, &pose, th, ORBdist, mvScaleFactors.data(),
+        (int)mvScaleFactors.size(), mbCheckOrientation, kfAngle.empty() ? nullptr : kfAngle.data(), occupied.data(),
+        trainMatch.data(), out ? out->projected.data() : nullptr, out ? out->u.data() : nullptr,
+        out ? out->v.data() : nullptr, out ? out->level.data() : nullptr);
+    check(rc, "vsg_frame_search_keyframe_points");
+    trainMatch.resize(CurrentFrame.N()), occupied.resize(CurrentFrame.N());
+    if (out) out->projected.resize(n), out->u.resize(n), out->v.resize(n), out->level.resize(n);
+    return rc;
+  }
+
   // SearchBySim3(pKF1, pKF2, vpMatches12, S12, th)  (ORBmatcher.cc:1448-1665): idx1 / idx2 = feature index of every
   // projected point in its own KeyFrame; matches12[i1] = i2 where both directions agree
   int SearchBySim3(ResidentFrame &pKF1, ResidentFrame &pKF2, const std::vector<int32_t> &idx1,

@@ -10,12 +10,17 @@
 // GATHERED by k_frustum rather than read by the window kernel through the slot index: the window kernel is the one
 // every search routine shares and stays as it is, a wavefront of it reads its query's 32 bytes once either way, and
 // only the points that are searched (in view, not far) are copied -- 13-19 % of a local map.
+//
+// k_project_points does the same for the two other searches of Tracking that project map points through a Frame's
+// pose (vsg_project.h): SearchByProjection(CurrentFrame, LastFrame) with the last frame resident (its octaves are read
+// on the device) and SearchByProjection(CurrentFrame, pKF, sAlreadyFound) for relocalisation.
 #include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "vsg_frame_int.h"
 #include "vsg_frustum.h"
+#include "vsg_project.h"
 
 using namespace vsg;
 
@@ -145,6 +150,71 @@ __global__ __launch_bounds__(64) void k_frustum(StoreDev S, const int32_t *__res
   }
 }
 
+struct ProjectArgs {
+  vsg_frame_pose cam;
+  ImageBounds bounds;
+  int n;
+  float th;
+  int direction;  // last-frame form: 0 neither, 1 bForward, 2 bBackward
+  float scale_factors[16];
+};
+
+struct ProjectOutDev {
+  uint8_t *valid;     // the point reaches GetFeaturesInArea
+  float *u, *v;
+  float *ur;          // last-frame form
+  int32_t *level;     // KeyFrame form
+  uint8_t *observed;  // last-frame form: Observations() > 0 of query i's point, for the ordered host pass
+};
+
+// The projection loops of SearchByProjection(CurrentFrame, LastFrame) (kLast, ORBmatcher.cc:1686-1724) and of
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound) (ORBmatcher.cc:1895-1930), one lane per query, 64 lanes per
+// workgroup like k_frustum.  kLast: query i = feature i of the resident last frame, slots[i] < 0 = no map point or an
+// outlier, the octave is the last frame's own.  Otherwise query i = slot slots[i], skip[i] = isBad() or
+// in sAlreadyFound.  A query that is not searched gets the inactive flag and no descriptor (see k_frustum).
+template <bool kLast>
+__global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t *__restrict__ slots,
+                                                       const uint8_t *__restrict__ skip,
+                                                       const KeyPointPOD *__restrict__ last_kps, ProjectArgs A,
+                                                       ProjectOutDev O, WinQuery *__restrict__ Q,
+                                                       uint8_t *__restrict__ qdesc) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.n) return;
+  const int s = slots[i];
+  ProjectOut o = {0, 0.0f, 0.0f, 0.0f, 0};
+  WinQuery w = {0, 0, 0, -1, -1, 0, -1, 0.f, 0.f, 2, 0, 0};
+  uint8_t observed = 0;
+  if (s >= 0 && !(skip && skip[i])) {
+    const float *P = S.pos + 3 * (size_t)s;
+    if (kLast) {
+      const int oct = last_kps[i].octave;  // nLastOctave (:1711); the host refused octaves outside the pyramid
+      o = project_last_point(A.cam, A.bounds, P);
+      if ((unsigned)oct >= 16u) o.valid = 0;
+      if (o.valid) {
+        const float radius = fmul(A.th, A.scale_factors[oct]);  // :1715
+        // level window (:1719-1724): forward -> (nLastOctave, -1), backward -> (0, nLastOctave), else +-1
+        const int minL = A.direction == 1 ? oct : A.direction == 2 ? 0 : oct - 1;
+        const int maxL = A.direction == 1 ? -1 : A.direction == 2 ? oct : oct + 1;
+        w = {o.u, o.v, radius, minL, maxL, 0, -1, o.ur, radius, 0, 0, 0};
+      }
+      observed = S.observed[s];
+    } else {
+      o = project_kf_point(A.cam, A.bounds, P, S.min_dist[s], S.max_dist[s]);
+      if (o.valid) {
+        const float radius = fmul(A.th, A.scale_factors[o.level]);  // :1928
+        w = {o.u, o.v, radius, o.level - 1, o.level + 1, 0, -1, 0.f, 0.f, 0, 0, 0};  // :1930
+      }
+    }
+    if (o.valid) copy_desc(qdesc + 32 * (size_t)i, S.desc + 32 * (size_t)s);
+  }
+  O.valid[i] = (uint8_t)o.valid;
+  O.u[i] = o.u, O.v[i] = o.v;
+  if (O.ur) O.ur[i] = o.ur;
+  if (O.level) O.level[i] = o.level;
+  if (O.observed) O.observed[i] = observed;
+  Q[i] = w;
+}
+
 int store_check(const vsg_mappoints *mp) { return mp && mp->d_block ? VSG_OK : VSG_ERR_INVALID; }
 
 // n slots of the caller into the arena at `dst` (nullptr list: nothing to copy, the kernel uses i); VSG_ERR_INVALID for
@@ -201,6 +271,84 @@ int copy_begin(vsg_mappoints *mp, int n, const int32_t *slots, const CopyLayout 
 int copy_end(ThreadCtx *c) {
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
   return e1 == hipSuccess && e2 == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+}
+
+// What the two projection searches share: the window call with this call's own blocks behind it in both arenas, the
+// projection kernel and the window kernel enqueued back to back, one wait.
+struct ProjectCall {
+  WindowCall wc;
+  size_t oS = 0, oK = 0, oV = 0, oO = 0, oU = 0, oVv = 0, oA = 0;  // slots, skip, valid, observed, u, v, ur / level
+  uint8_t *hp = nullptr;
+
+  // kLast: `slots` has one entry per feature of `last` (< 0: inactive); else n slots and skip
+  template <bool kLast>
+  int run(const vsg_frame *cur, const vsg_mappoints *mp, const vsg_frame *last, int n, const int32_t *slots,
+          const uint8_t *skip, const ProjectArgs &A) {
+    const size_t N = (size_t)n;
+    Stage st;
+    oS = st.add(N * 4), oK = st.add(skip ? N : 0), oV = st.add(N), oO = st.add(kLast ? N : 0);
+    oU = st.add(N * 4), oVv = st.add(N * 4), oA = st.add(N * 4);
+    int rc = wc.begin(cur->device, n, kWinList, false, 0, st.total);
+    if (rc != VSG_OK) return rc;
+    ThreadCtx *c = wc.c;
+    Stage sd;
+    const size_t dQ = sd.add(N * sizeof(WinQuery)), dD = sd.add(N * 32);
+    rc = ctx_reserve(c, 0, sd.total);
+    if (rc != VSG_OK) return rc;
+    const size_t base = wc.bytes();
+    hp = c->h_pin + base;
+    uint8_t *dp = c->d_pin + base;
+    memcpy(hp + oS, slots, N * 4);
+    if (skip) memcpy(hp + oK, skip, N);
+    const ProjectOutDev O = {dp + oV,
+                             (float *)(dp + oU),
+                             (float *)(dp + oVv),
+                             kLast ? (float *)(dp + oA) : nullptr,
+                             kLast ? nullptr : (int32_t *)(dp + oA),
+                             kLast ? dp + oO : nullptr};
+    WinQuery *Q = (WinQuery *)(c->d_buf + dQ);
+    uint8_t *D = c->d_buf + dD;
+    hipLaunchKernelGGL(k_project_points<kLast>, dim3((n + 63) / 64), dim3(64), 0, c->stream, store_dev(mp),
+                       (const int32_t *)(dp + oS),
+                       skip ? (const uint8_t *)(dp + oK) : (const uint8_t *)nullptr,
+                       kLast ? (const KeyPointPOD *)last->d_kps : (const KeyPointPOD *)nullptr, A, O, Q, D);
+    rc = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+    // the stereo gate of :1742-1748 applies to frames with mvuRight (Nleft == -1 here); the KeyFrame form has none
+    if (rc == VSG_OK) rc = wc.launch(cur, kLast && cur->has_uright ? kGateUr : kGateNone, 256, nullptr, 0, D, Q);
+    if (rc != VSG_OK) {
+      hipStreamSynchronize(c->stream);  // nothing of this call may still write the arena when the next one fills it
+      return rc;
+    }
+    return wc.finish();  // VSG_RETRY: the lists overflowed their array; the whole call runs again
+  }
+  void outs(int n, uint8_t *projected, float *u, float *v, void *ur_or_level) const {
+    const size_t N = (size_t)n;
+    if (projected) memcpy(projected, hp + oV, N);
+    if (u) memcpy(u, hp + oU, N * 4);
+    if (v) memcpy(v, hp + oVv, N * 4);
+    if (ur_or_level) memcpy(ur_or_level, hp + oA, N * 4);
+  }
+};
+
+// the checks the two projection searches share, in the order of pose_check
+int project_check(const vsg_frame *cur, const vsg_mappoints *mp, const vsg_frame_pose *pose, const float *scale_factors,
+                  int nlevels, const uint8_t *blocked, const int32_t *train_match) {
+  const int rc = pose_check(cur, mp, pose);
+  if (rc != VSG_OK) return rc;
+  if (!scale_factors || !blocked || !train_match || nlevels < 1 || nlevels > 16 || pose->n_levels > nlevels)
+    return VSG_ERR_INVALID;
+  return VSG_OK;
+}
+
+ProjectArgs project_args(const vsg_frame *cur, const vsg_frame_pose *pose, int n, float th, const float *scale_factors,
+                         int nlevels) {
+  ProjectArgs A;
+  memset(&A, 0, sizeof(A));
+  A.cam = *pose;
+  A.bounds = {cur->minX, cur->maxX, cur->minY, cur->maxY};
+  A.n = n, A.th = th;
+  for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
+  return A;
 }
 
 }  // namespace
@@ -421,6 +569,69 @@ int vsg_frame_search_local_points(vsg_frame *F, vsg_mappoints *mp, int n, const 
     // a point that is in view but too far has an empty list: the pass does nothing for it, as :53-54
     return walk::search_local(wc.lists(), n, -1, hv, nullptr, nullptr, hp + oO, nnratio, nullptr, nullptr,
                               train_blocked, train_match);
+  });
+}
+
+int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *mp, const int32_t *last_slots,
+                                const vsg_frame_pose *cur_pose, const vsg_frame_pose *last_pose, float mb, int mono,
+                                float th, const float *scale_factors, int nlevels, int check_orientation,
+                                uint8_t *train_blocked, int32_t *train_match, int *direction, uint8_t *projected, float *u,
+                                float *v, float *ur) {
+  if (!last || !last->d_block || !last_pose || !last_slots) return VSG_ERR_INVALID;
+  int rc = project_check(cur, mp, cur_pose, scale_factors, nlevels, train_blocked, train_match);
+  if (rc != VSG_OK) return rc;
+  if (last->nleft != -1) return VSG_ERR_UNSUPPORTED;  // the right-camera block (ORBmatcher.cc:1785-1853)
+  if (last->device != cur->device) return VSG_ERR_INVALID;
+  const int dir = motion_direction(*cur_pose, *last_pose, mb, mono ? 1 : 0);  // :1677-1684
+  const int n = last->n;
+  const vsg_keypoint *lk = last->h_kps.data();
+  for (int i = 0; i < n; i++) {  // before the first enqueue
+    if (last_slots[i] >= mp->capacity) return VSG_ERR_INVALID;
+    if (last_slots[i] >= 0 && (lk[i].octave < 0 || lk[i].octave >= nlevels)) return VSG_ERR_INVALID;
+  }
+  if (direction) *direction = dir;  // after the checks: an invalid call writes nothing
+  if (n == 0) return 0;
+  ProjectArgs A = project_args(cur, cur_pose, n, th, scale_factors, nlevels);
+  A.direction = dir;
+  std::vector<float> last_angle;  // kpLF.angle (:1768)
+  if (check_orientation) {
+    last_angle.resize((size_t)n);
+    for (int i = 0; i < n; i++) last_angle[i] = lk[i].angle;
+  }
+  return with_retry([&]() -> int {
+    ProjectCall pc;
+    rc = pc.run<true>(cur, mp, last, n, last_slots, nullptr, A);
+    if (rc != VSG_OK) return rc;
+    pc.outs(n, projected, u, v, ur);
+    const vsg_keypoint *hk = cur->h_kps.data();
+    // a feature without a map point, an outlier and a point that does not project have empty lists: the pass does nothing
+    // for them, as the `continue`s of :1689-1709
+    return walk::search_last(pc.wc.lists(), n, -1, last_angle.data(), pc.hp + pc.oO, [&](int i) { return hk[i].angle; },
+                             walk::TH_HIGH, check_orientation != 0, train_blocked, train_match);
+  });
+}
+
+int vsg_frame_search_keyframe_points(vsg_frame *cur, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                                     const vsg_frame_pose *pose, float th, int orb_dist, const float *scale_factors,
+                                     int nlevels, int check_orientation, const float *kf_angle, uint8_t *occupied,
+                                     int32_t *train_match, uint8_t *projected, float *u, float *v,
+                                     int32_t *predicted_level) {
+  int rc = project_check(cur, mp, pose, scale_factors, nlevels, occupied, train_match);
+  if (rc != VSG_OK) return rc;
+  if (n < 0 || (check_orientation && n > 0 && !kf_angle)) return VSG_ERR_INVALID;
+  if (n == 0) return 0;
+  if (!slots) return VSG_ERR_INVALID;
+  for (int i = 0; i < n; i++)
+    if (slots[i] < 0 || slots[i] >= mp->capacity) return VSG_ERR_INVALID;  // before the first enqueue
+  const ProjectArgs A = project_args(cur, pose, n, th, scale_factors, nlevels);
+  return with_retry([&]() -> int {
+    ProjectCall pc;
+    rc = pc.run<false>(cur, mp, nullptr, n, slots, skip, A);
+    if (rc != VSG_OK) return rc;
+    pc.outs(n, projected, u, v, predicted_level);
+    const vsg_keypoint *hk = cur->h_kps.data();
+    return walk::search_kf_projection(pc.wc.lists(), n, kf_angle, [&](int i) { return hk[i].angle; }, orb_dist,
+                                      check_orientation != 0, occupied, train_match);
   });
 }
 

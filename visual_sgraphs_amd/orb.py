@@ -74,6 +74,8 @@ EXPORTS = [
     # resident map points: Frame::isInFrustum and Tracking::SearchLocalPoints
     "vsg_mappoints_create", "vsg_mappoints_destroy", "vsg_mappoints_capacity", "vsg_mappoints_update",
     "vsg_mappoints_read", "vsg_frame_is_in_frustum", "vsg_frame_search_local_points",
+    # the motion-model and relocalisation projection searches on resident map points
+    "vsg_frame_search_last_frame", "vsg_frame_search_keyframe_points",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -327,6 +329,10 @@ def load_library():
                                           _i32p, _f32p]
     L.vsg_frame_search_local_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, cf, cf, ci, cf, _f32p,
                                                 ci, _u8p, _i32p, _u8p, _f32p, _f32p, C.POINTER(ci)]
+    L.vsg_frame_search_last_frame.argtypes = [vp, vp, vp, _i32p, C.POINTER(FramePose), C.POINTER(FramePose), cf, ci, cf,
+                                              _f32p, ci, ci, _u8p, _i32p, C.POINTER(ci), _u8p, _f32p, _f32p, _f32p]
+    L.vsg_frame_search_keyframe_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, ci, _f32p, ci, ci,
+                                                   _f32p, _u8p, _i32p, _u8p, _f32p, _f32p, _i32p]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1416,6 +1422,53 @@ class Frame:
             len(scale_factors), _p(tb, _u8p), _p(tm, _i32p), _p(inv, _u8p), _p(px, _f32p), _p(py, _f32p), C.byref(ntm)),
             "vsg_frame_search_local_points")
         return nm, tm[:len(tb)], tb, inv[:n], px[:n], py[:n], ntm.value
+
+    # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono) on resident map points  (ORBmatcher.cc:1667-1878)
+    def SearchLastFrame(self, last, mp, last_slots, cur_pose, last_pose, mb, mono, th, scale_factors, train_blocked,
+                        check_orientation=True):
+        """last: the resident LastFrame; last_slots[i] = slot of its feature i's map point (< 0: none, or an outlier).
+        Returns (nmatches, train_match, train_blocked, direction, projected, u, v, ur); train_match[i2] = index of the
+        last-frame feature, the last four per last-frame feature."""
+        sl = np.ascontiguousarray(last_slots, dtype=np.int32) if last_slots is not None else None
+        n = len(last.kps)
+        if sl is not None and len(sl) != n:
+            raise ValueError("last_slots length does not match the last frame's features")
+        m = max(n, 1)
+        sf = _f32(scale_factors)
+        tb = _u8(train_blocked).copy()
+        tm = np.full(max(len(tb), 1), -1, np.int32)
+        pr, u, v, ur = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        direction = C.c_int(0)
+        nm = _check(self._L.vsg_frame_search_last_frame(
+            self._h, last.handle, mp.handle, _p(_i32(sl), _i32p) if sl is not None else None, C.byref(cur_pose), C.byref(last_pose), float(np.float32(mb)),
+            int(bool(mono)), float(th), _p(sf, _f32p), len(scale_factors), int(bool(check_orientation)), _p(tb, _u8p),
+            _p(tm, _i32p), C.byref(direction), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(ur, _f32p)),
+            "vsg_frame_search_last_frame")
+        return nm, tm[:len(tb)], tb, direction.value, pr[:n], u[:n], v[:n], ur[:n]
+
+    # ---- SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) on resident map points  (ORBmatcher.cc:1880-2000)
+    def SearchKeyFramePoints(self, mp, slots, pose, th, orb_dist, scale_factors, occupied, kf_angle=None, skip=None,
+                             check_orientation=True):
+        """slots[i] = slot of the KeyFrame's i-th map point, kf_angle[i] = pKF->mvKeysUn[i].angle, skip[i] != 0 = isBad() or
+        in sAlreadyFound.  Returns (nmatches, train_match, occupied, projected, u, v, predicted_level); train_match[i2] =
+        query index."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(sl)
+        sk = _u8(skip) if skip is not None else None
+        ka = _f32(kf_angle) if kf_angle is not None else None
+        if (sk is not None and len(sk) != n) or (ka is not None and len(ka) != n):
+            raise ValueError("skip / kf_angle length does not match the slots")
+        m = max(n, 1)
+        sf = _f32(scale_factors)
+        oc = _u8(occupied).copy()
+        tm = np.full(max(len(oc), 1), -1, np.int32)
+        pr, u, v, lvl = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
+        nm = _check(self._L.vsg_frame_search_keyframe_points(
+            self._h, mp.handle, n, _p(_i32(sl), _i32p), _p(sk, _u8p) if sk is not None and n else None, C.byref(pose),
+            float(th), int(orb_dist), _p(sf, _f32p), len(scale_factors), int(bool(check_orientation)),
+            _p(ka, _f32p) if ka is not None and n else None, _p(oc, _u8p), _p(tm, _i32p), _p(pr, _u8p), _p(u, _f32p),
+            _p(v, _f32p), _p(lvl, _i32p)), "vsg_frame_search_keyframe_points")
+        return nm, tm[:len(oc)], oc, pr[:n], u[:n], v[:n], lvl[:n]
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono)  (ORBmatcher.cc:1667-1878)
     def SearchByProjection_Last(self, desc, observed, u, v, ur, last_octave, last_angle, th, direction, scale_factors,
