@@ -1,4 +1,5 @@
-"""The resident-frame kernels (k_frame_grid_build, k_window_search: visual_sgraphs_amd/csrc/vsg_frame.hip) at their edges
+"""The resident-frame kernels (k_frame_grid_build: visual_sgraphs_amd/csrc/vsg_frame.hip, k_window_search:
+csrc/vsg_window.hip) at their edges
 instead of at their typical shape: device-built grids across kGridLdsMax, cells of more than 32 entries under every gate,
 windows of more than 64 cells, candidate lists around the inline slot, the overflow retry from a fresh thread, the packed
 candidate word at its field limits, degenerate stereo splits, query-count tails, one frame rewritten at changing sizes,

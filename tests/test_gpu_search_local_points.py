@@ -11,7 +11,11 @@ import numpy as np
 import pytest
 
 import frustum_reference as fr
+import projection_reference as pr
 import rgbd_reference as rr
+import scenarios as sc
+from frame_edge_routines import S16, resident
+from test_gpu_frame_edges import in_thread
 from visual_sgraphs_amd import orb, synth
 
 pytestmark = pytest.mark.gpu
@@ -86,15 +90,16 @@ def existing_path(F, ref, f, th, sf, blocked, th_far=None):
     return F.SearchByProjection(fr.search_fields(ref, f["desc"], f["observed"], th_far), th, NNRATIO, sf, blocked)
 
 
-def compare(F, mp, pose, f, bounds, th, sf, blocked, slots=None, skip=None, far=None, min_share=0.10):
+def compare(F, mp, pose, f, bounds, th, sf, blocked, slots=None, skip=None, far=None, min_share=0.10, run=lambda call: call()):
+    """run: how the call under test is made (the reference call always runs on the calling thread)"""
     ref = fr.is_in_frustum(pose, bounds, f["world_pos"], f["normal"], f["min_dist"], f["max_dist"], skip=skip)
     want = existing_path(F, ref, f, th, sf, blocked, far)
     n_in = int(ref["in_view"].sum())
     print(f"n={len(ref['in_view'])} in view {n_in} nmatches {want[0]} th {th} far {far}")
     if min_share is not None:
         assert want[0] >= min_share * n_in, (want[0], n_in)  # a real share matches (condition on the existing path)
-    got = F.SearchLocalPoints(mp, orb.FramePose.make(**pose), th, NNRATIO, sf, blocked, n=len(ref["in_view"]), slots=slots,
-                              skip=skip, far_points=far is not None, th_far_points=far or 0.0)
+    got = run(lambda: F.SearchLocalPoints(mp, orb.FramePose.make(**pose), th, NNRATIO, sf, blocked, n=len(ref["in_view"]),
+                                          slots=slots, skip=skip, far_points=far is not None, th_far_points=far or 0.0))
     assert got[0] == want[0]
     assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
     assert np.array_equal(got[3], ref["in_view"]) and got[6] == n_in
@@ -227,3 +232,70 @@ def test_two_threads_two_frames_one_store(ex):
         assert len(gs) == calls
         for g in gs:
             assert g[0] == w[0] and all(np.array_equal(a, b) for a, b in zip(g[1:6], w[1:6])) and g[6] == w[6]
+
+
+def dense_windows_case(th_local, th_kf, n_points=65):
+    """A frame packed as in test_dense_cells_left_grid (clustered cells of up to 200 entries; without mvuRight, so that
+    every list is GetFeaturesInArea's own and the oracle can count it) and n_points map points above its cluster cells whose
+    windows hold more than the kernel's 16 inline entries in BOTH searches.  Returns (frame dict, pose, fields, isInFrustum
+    reference, KeyFrame-projection reference, overflow total of the local search, of the KeyFrame search)."""
+    fd = dict(sc.dense_case(False)[0], u_right=None)
+    o = sc.oracle_of(fd)
+    cs, en = o.grid(False)
+    occ = np.diff(cs)
+    cof = sc.cell_of_features(cs, en, len(fd["keys"]))
+    # the keypoints of the cluster cells whose own octave a predicted level of the 8-level pose can reach
+    cand = np.flatnonzero((cof >= 0) & (occ[np.maximum(cof, 0)] >= 100) & (fd["keys"]["octave"] <= 6))
+    pose, f = local_map(type("K", (), dict(kps=fd["keys"][cand]))(), fd["desc"][cand], None, 51, n_other=0)
+    ref = fr.is_in_frustum(pose, fd["bounds"], f["world_pos"], f["normal"], f["min_dist"], f["max_dist"])
+    kf = pr.project_kf_points(pose, fd["bounds"], f["world_pos"], f["min_dist"], f["max_dist"])
+    keep, n_local, n_kf = [], [], []
+    for i in np.flatnonzero((ref["in_view"] != 0) & (kf["valid"] != 0)):
+        # ORBmatcher.cc:64-70 and :1928-1934 in float, as the product rounds them
+        r = np.float32(2.5 if float(ref["view_cos"][i]) > 0.998 else 4.0) * np.float32(th_local)
+        lvl, lk = int(ref["scale_level"][i]), int(kf["level"][i])
+        a = len(o.features_in_area(ref["proj_x"][i], ref["proj_y"][i], np.float32(r * S16[lvl]), lvl - 1, lvl))
+        b = len(o.features_in_area(kf["u"][i], kf["v"][i], np.float32(np.float32(th_kf) * S16[lk]), lk - 1, lk + 1))
+        if a > 16 and b > 16:
+            keep.append(i), n_local.append(a), n_kf.append(b)
+        if len(keep) == n_points:
+            break
+    assert len(keep) == n_points
+    keep = np.array(keep)
+    f = {k: np.ascontiguousarray(v[keep]) for k, v in f.items()}
+    ref = {k: v[keep] for k, v in ref.items()}
+    kf = {k: v[keep] for k, v in kf.items()}
+    return fd, pose, f, ref, kf, sum(n_local), sum(n_kf)
+
+
+def test_overflow_retry_on_a_fresh_thread_through_the_resident_call():
+    """SearchLocalPoints and SearchKeyFramePoints, each as the FIRST window search of a freshly started thread: the
+    thread's candidate capacity is at its floor of 4 entries per query, 65 points (two workgroups of the projection kernel,
+    the second with one live lane; 17 of the window kernel, the last with one live wave) whose lists all go to the overflow
+    area need more than 4 x 65, so the first attempt ends in the retry and the whole chain -- projection kernel, window
+    kernel, wait -- runs twice.  Results as the host-array SearchByProjection / SearchByProjection_KF on the same inputs."""
+    th, th_kf, orb_dist = 15, 60, 100
+    fd, pose, f, ref, kf, total_local, total_kf = dense_windows_case(th, th_kf)
+    n = len(f["desc"])
+    assert n == 65 and total_local > 4 * n and total_kf > 4 * n, (total_local, total_kf)   # every list is an overflow list
+    F, _ = resident(fd)
+    mp = store_of(f)
+    blocked = np.zeros(len(fd["keys"]), np.uint8)
+    ref2, _ = compare(F, mp, pose, f, fd["bounds"], th, S16, blocked, run=in_thread)
+    assert all(np.array_equal(ref2[k], ref[k]) for k in ("in_view", "scale_level")) and ref["in_view"].all()
+    # the KeyFrame form, as tests/test_gpu_search_keyframe_points.py compares it
+    slots = np.arange(n, dtype=np.int32)
+    kf_angle = np.random.default_rng(52).uniform(0, 360, n).astype(np.float32)
+    a = pr.keyframe_fields(kf, slots, f["desc"], kf_angle, th_kf, S16)
+    want = F.SearchByProjection_KF(a["desc"], a["u"], a["v"], a["radius"], a["predicted_level"], a["kf_angle"], orb_dist, True,
+                                   blocked)
+    want = (want[0], pr.map_back(want[1], a["index"]), want[2])
+    print(f"kf n={n} overflow entries {total_kf} nmatches {want[0]}")
+    assert want[0] >= 5   # the rotation histogram keeps matches under random observer angles (condition on the existing path)
+    got = in_thread(lambda: F.SearchKeyFramePoints(mp, slots, orb.FramePose.make(**pose), th_kf, orb_dist, S16, blocked,
+                                                   kf_angle, None, True))
+    assert got[0] == want[0]
+    assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
+    assert np.array_equal(got[3], kf["valid"])
+    for x, k in ((got[4], "u"), (got[5], "v"), (got[6], "level")):
+        assert x.dtype == kf[k].dtype and x.tobytes() == kf[k].tobytes(), k

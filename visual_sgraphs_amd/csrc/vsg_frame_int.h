@@ -1,5 +1,6 @@
 // vsg_frame_int.h -- internal layout of a device-resident Frame / KeyFrame feature set (include/vsg_orb.h: vsg_frame)
-// and the window-search launcher shared by vsg_frame.hip, vsg_match.hip, vsg_bow.hip and vsg_orb.hip.
+// and the window-search launcher (vsg_window.hip), shared by vsg_frame.hip, vsg_window.hip, vsg_mappoints.hip,
+// vsg_match.hip, vsg_bow.hip and vsg_orb.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +11,7 @@
 #include "vsg_common.h"
 #include "vsg_ctx.h"
 #include "vsg_walks.h"
+#include "vsg_windows.h"
 
 enum { kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows };  // FRAME_GRID_COLS / ROWS (Frame.h:49-50)
 enum { kGridLdsMax = 4096 };  // keypoints per frame up to which k_frame_grid_build orders the cells in LDS
@@ -58,34 +60,34 @@ struct FrameDev {
   float minX, minY, invW, invH;
 };
 FrameDev frame_dev(const vsg_frame *f);
+inline int frame_check(const vsg_frame *f) { return f && f->d_block ? VSG_OK : VSG_ERR_INVALID; }
+// a vsg_grid (include/vsg_orb.h) is a vsg_frame behind an opaque name
+inline vsg_frame *grid_frame(vsg_grid *g) { return (vsg_frame *)g; }
 
-// One GetFeaturesInArea window + the static candidate filters of a search routine.
-struct WinQuery {
-  float x, y, r;    // Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel, bRight)   (Frame.cc:802-868)
-  int minL, maxL;   //   (-1, -1 = KeyFrame::GetFeaturesInArea, KeyFrame.cc:834-874)
-  int lo, hi;       // kpLevel < lo || kpLevel > hi -> skip (hi < 0: no such filter)       e.g. ORBmatcher.cc:506-509
-  float ur, gate;   // projected right coordinate + threshold of the stereo gates           e.g. ORBmatcher.cc:97-102
-  int flags;        // bit 0: bRight (mGridRight, indices + Nleft); bit 1: inactive query (empty list)
-  int pad0, pad1;
-};
-static_assert(sizeof(WinQuery) == 48, "WinQuery layout");
+// inclusive prefix sum over the 64 lanes of a wavefront (k_frame_grid_build, k_window_search)
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);   // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);   // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);   // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);   // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
+  return v;
+}
 
 enum { kWinList = 0, kWinBest = 1 };
 enum { VSG_RETRY = -100 };  // internal: candidate lists overflowed the compact array; the entry point runs again
 enum { kGateNone = 0, kGateUr = 1, kGateChi2 = 2 };
 
 // One window-search call on the calling thread's stream: begin() lays the pinned arena out and returns host pointers
-// for the caller to fill (queries, descriptors); launch() enqueues the kernel; finish() syncs and, for lists that
-// overflowed their stride, re-runs with a larger one.
+// for the caller to fill (queries, descriptors); launch() enqueues the kernel; finish() waits for the stream and, when
+// the lists overflowed the compact array, raises the thread's capacity hint and returns VSG_RETRY: the entry point's
+// body runs again from begin() (with_retry below).
 struct WindowCall {
   ThreadCtx *c = nullptr;
   int nq = 0, mode = kWinList, cap = 0;  // cap: entries the compact candidate array holds (list mode)
   size_t oQ = 0, oD = 0, oOff = 0, oCnt = 0, oOut = 0;
   bool with_desc = true;
-  // launch parameters remembered for the overflow re-run
-  const vsg_frame *frame = nullptr;
-  int gate_mode = kGateNone, best_init = 256;
-  float inv_sigma2[16] = {};
   size_t base = 0;  // offset of this call's blocks inside the arena (several calls can share one arena)
   bool range_open = false;  // a roctx range pushed by begin() and not yet popped (every exit path pops exactly once)
   ~WindowCall();
@@ -96,7 +98,13 @@ struct WindowCall {
   int launch(const vsg_frame *f, int gate_mode, int best_init, const float *inv_sigma2, int nlevels,
              const uint8_t *qdesc_dev = nullptr,   // qdesc_dev: query descriptors already on the device
              const WinQuery *q_dev = nullptr);     // q_dev: queries a kernel in front of this one wrote on the device
-  int finish();  // completion (pinned flag written by the kernel's last wave, or the stream) + overflow handling
+  int finish();  // waits for the stream; VSG_RETRY when the lists overflowed (list mode)
+  // launch() then finish(): what an entry point with ONE window kernel does between its fill and its host pass
+  int run(const vsg_frame *f, int gate_mode, int best_init = 256, const float *inv_sigma2 = nullptr, int nlevels = 0,
+          const uint8_t *qdesc_dev = nullptr) {
+    const int rc = launch(f, gate_mode, best_init, inv_sigma2, nlevels, qdesc_dev);
+    return rc != VSG_OK ? rc : finish();
+  }
   size_t bytes() const;
   walk::CandView lists() const;
   const int32_t *best() const { return (const int32_t *)(c->h_pin + base + oOut); }  // pairs {idx, dist}

@@ -67,7 +67,4 @@ VSG_HD FrustumOut frustum_point(const vsg_frame_pose &cam, float minX, float max
   return o;
 }
 
-// ORBmatcher::RadiusByViewingCos (ORBmatcher.cc:218-224); the comparison is with the double 0.998
-VSG_HD float radius_by_viewing_cos(float viewCos) { return (double)viewCos > 0.998 ? 2.5f : 4.0f; }
-
 }  // namespace vsg

@@ -135,15 +135,10 @@ __global__ __launch_bounds__(64) void k_frustum(StoreDev S, const int32_t *__res
   if (O.view_cos) O.view_cos[i] = o.view_cos;
   if (O.observed) O.observed[i] = S.observed[s];
   if (Q) {
-    WinQuery w = {0, 0, 0, -1, -1, 0, -1, 0.f, 0.f, 2, 0, 0};
+    WinQuery w = win_inactive(false);
     // :50-54: !mbTrackInView -> continue; bFarPoints && mTrackDepth > thFarPoints -> continue
     if (o.in_view && !(A.far_points && o.depth > A.th_far_points)) {
-      float r = radius_by_viewing_cos(o.view_cos);  // :64
-      if (A.b_factor) r = fmul(r, A.th);            // :66-67
-      const float win = fmul(r, A.scale_factors[o.scale_level]);
-      // GetFeaturesInArea(mTrackProjX, mTrackProjY, r * mvScaleFactors[level], level - 1, level)  (:69-70); ur and the
-      // gate of :97-102 as vsg_frame_search_by_projection builds them
-      w = {o.proj_x, o.proj_y, win, o.scale_level - 1, o.scale_level, 0, -1, o.proj_xr, win, 0, 0, 0};
+      w = win_local(o.proj_x, o.proj_y, o.proj_xr, o.scale_level, o.view_cos, A.th, A.b_factor, A.scale_factors);
       copy_desc(qdesc + 32 * (size_t)i, S.desc + 32 * (size_t)s);
     }
     Q[i] = w;
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t
   if (i >= A.n) return;
   const int s = slots[i];
   ProjectOut o = {0, 0.0f, 0.0f, 0.0f, 0};
-  WinQuery w = {0, 0, 0, -1, -1, 0, -1, 0.f, 0.f, 2, 0, 0};
+  WinQuery w = win_inactive(false);
   uint8_t observed = 0;
   if (s >= 0 && !(skip && skip[i])) {
     const float *P = S.pos + 3 * (size_t)s;
@@ -190,20 +185,11 @@ __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t
       const int oct = last_kps[i].octave;  // nLastOctave (:1711); the host refused octaves outside the pyramid
       o = project_last_point(A.cam, A.bounds, P);
       if ((unsigned)oct >= 16u) o.valid = 0;
-      if (o.valid) {
-        const float radius = fmul(A.th, A.scale_factors[oct]);  // :1715
-        // level window (:1719-1724): forward -> (nLastOctave, -1), backward -> (0, nLastOctave), else +-1
-        const int minL = A.direction == 1 ? oct : A.direction == 2 ? 0 : oct - 1;
-        const int maxL = A.direction == 1 ? -1 : A.direction == 2 ? oct : oct + 1;
-        w = {o.u, o.v, radius, minL, maxL, 0, -1, o.ur, radius, 0, 0, 0};
-      }
+      if (o.valid) w = win_last(o.u, o.v, o.ur, oct, A.th, A.direction, A.scale_factors);
       observed = S.observed[s];
     } else {
       o = project_kf_point(A.cam, A.bounds, P, S.min_dist[s], S.max_dist[s]);
-      if (o.valid) {
-        const float radius = fmul(A.th, A.scale_factors[o.level]);  // :1928
-        w = {o.u, o.v, radius, o.level - 1, o.level + 1, 0, -1, 0.f, 0.f, 0, 0, 0};  // :1930
-      }
+      if (o.valid) w = win_kf(o.u, o.v, fmul(A.th, A.scale_factors[o.level]), o.level);  // radius: :1928
     }
     if (o.valid) copy_desc(qdesc + 32 * (size_t)i, S.desc + 32 * (size_t)s);
   }
@@ -217,15 +203,13 @@ __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t
 
 int store_check(const vsg_mappoints *mp) { return mp && mp->d_block ? VSG_OK : VSG_ERR_INVALID; }
 
-// n slots of the caller into the arena at `dst` (nullptr list: nothing to copy, the kernel uses i); VSG_ERR_INVALID for
-// a slot outside the store.  Runs BEFORE anything is enqueued: an error return leaves no kernel behind.
-int stage_slots(const vsg_mappoints *mp, int n, const int32_t *slots, int32_t *dst) {
-  if (!slots) return n <= mp->capacity ? VSG_OK : VSG_ERR_INVALID;
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= mp->capacity) return VSG_ERR_INVALID;
-    dst[i] = slots[i];
-  }
-  return VSG_OK;
+// Does every slot of a caller's list lie inside the store (nullptr list: the kernel uses slot i)?  Every entry point asks
+// BEFORE anything is enqueued: an error return leaves no kernel behind.
+bool slots_in_store(const vsg_mappoints *mp, int n, const int32_t *slots) {
+  if (!slots) return n <= mp->capacity;
+  for (int i = 0; i < n; i++)
+    if (slots[i] < 0 || slots[i] >= mp->capacity) return false;
+  return true;
 }
 
 int pose_check(const vsg_frame *F, const vsg_mappoints *mp, const vsg_frame_pose *pose) {
@@ -258,8 +242,7 @@ struct CopyLayout {
 
 // arguments every update / read checks BEFORE anything is staged or enqueued; the thread's context with the arena reserved
 int copy_begin(vsg_mappoints *mp, int n, const int32_t *slots, const CopyLayout &L, ThreadCtx **c) {
-  for (int i = 0; i < n; i++)
-    if (slots[i] < 0 || slots[i] >= mp->capacity) return VSG_ERR_INVALID;
+  if (!slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
   int rc = VSG_OK;
   *c = thread_ctx(mp->device, &rc);
   if (!*c) return rc;
@@ -273,62 +256,73 @@ int copy_end(ThreadCtx *c) {
   return e1 == hipSuccess && e2 == hipSuccess ? VSG_OK : VSG_ERR_HIP;
 }
 
-// What the two projection searches share: the window call with this call's own blocks behind it in both arenas, the
-// projection kernel and the window kernel enqueued back to back, one wait.
-struct ProjectCall {
+// What the three searches on resident map points share: a projection kernel that writes every point's WinQuery and
+// gathers its descriptor, k_window_search right behind it on the same stream, one wait.  The call's own blocks
+// [slots? | skip? | valid | observed? | x | y | aux?] sit behind the window call's in the pinned arena, [WinQuery |
+// descriptors] in the device arena.
+struct ResidentDev {  // what the projection kernel is launched with: the device side of those blocks and the stream
+  const int32_t *slots;
+  const uint8_t *skip;
+  uint8_t *valid, *observed;
+  float *x, *y;
+  void *aux;  // one more 4-byte value per point: ur (last-frame form) / level (KeyFrame form)
+  WinQuery *Q;
+  uint8_t *qdesc;
+  hipStream_t stream;
+};
+struct ResidentCall {
   WindowCall wc;
-  size_t oS = 0, oK = 0, oV = 0, oO = 0, oU = 0, oVv = 0, oA = 0;  // slots, skip, valid, observed, u, v, ur / level
-  uint8_t *hp = nullptr;
+  size_t oS = 0, oK = 0, oV = 0, oO = 0, oX = 0, oY = 0, oA = 0;
+  uint8_t *hp = nullptr;  // the call's blocks, host side
 
-  // kLast: `slots` has one entry per feature of `last` (< 0: inactive); else n slots and skip
-  template <bool kLast>
-  int run(const vsg_frame *cur, const vsg_mappoints *mp, const vsg_frame *last, int n, const int32_t *slots,
-          const uint8_t *skip, const ProjectArgs &A) {
+  // launch(ResidentDev) enqueues the projection kernel.  VSG_RETRY: the lists overflowed, the whole call runs again
+  template <class Launch>
+  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, bool observed, bool aux, int gate_mode,
+          Launch launch) {
     const size_t N = (size_t)n;
-    Stage st;
-    oS = st.add(N * 4), oK = st.add(skip ? N : 0), oV = st.add(N), oO = st.add(kLast ? N : 0);
-    oU = st.add(N * 4), oVv = st.add(N * 4), oA = st.add(N * 4);
-    int rc = wc.begin(cur->device, n, kWinList, false, 0, st.total);
+    Stage st, sd;
+    oS = st.add(slots ? N * 4 : 0), oK = st.add(skip ? N : 0), oV = st.add(N), oO = st.add(observed ? N : 0);
+    oX = st.add(N * 4), oY = st.add(N * 4), oA = st.add(aux ? N * 4 : 0);
+    const size_t dQ = sd.add(N * sizeof(WinQuery)), dD = sd.add(N * 32);
+    int rc = wc.begin(F->device, n, kWinList, false, 0, st.total);
     if (rc != VSG_OK) return rc;
     ThreadCtx *c = wc.c;
-    Stage sd;
-    const size_t dQ = sd.add(N * sizeof(WinQuery)), dD = sd.add(N * 32);
     rc = ctx_reserve(c, 0, sd.total);
     if (rc != VSG_OK) return rc;
-    const size_t base = wc.bytes();
-    hp = c->h_pin + base;
-    uint8_t *dp = c->d_pin + base;
-    memcpy(hp + oS, slots, N * 4);
+    // both reserves first, pointers after: either reserve may move its arena
+    hp = c->h_pin + wc.bytes();
+    uint8_t *dp = c->d_pin + wc.bytes();
+    if (slots) memcpy(hp + oS, slots, N * 4);
     if (skip) memcpy(hp + oK, skip, N);
-    const ProjectOutDev O = {dp + oV,
-                             (float *)(dp + oU),
-                             (float *)(dp + oVv),
-                             kLast ? (float *)(dp + oA) : nullptr,
-                             kLast ? nullptr : (int32_t *)(dp + oA),
-                             kLast ? dp + oO : nullptr};
-    WinQuery *Q = (WinQuery *)(c->d_buf + dQ);
-    uint8_t *D = c->d_buf + dD;
-    hipLaunchKernelGGL(k_project_points<kLast>, dim3((n + 63) / 64), dim3(64), 0, c->stream, store_dev(mp),
-                       (const int32_t *)(dp + oS),
-                       skip ? (const uint8_t *)(dp + oK) : (const uint8_t *)nullptr,
-                       kLast ? (const KeyPointPOD *)last->d_kps : (const KeyPointPOD *)nullptr, A, O, Q, D);
+    const ResidentDev R = {slots ? (const int32_t *)(dp + oS) : nullptr, skip ? dp + oK : nullptr, dp + oV,
+                           observed ? dp + oO : nullptr, (float *)(dp + oX), (float *)(dp + oY),
+                           aux ? dp + oA : nullptr, (WinQuery *)(c->d_buf + dQ), c->d_buf + dD, c->stream};
+    launch(R);
     rc = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
-    // the stereo gate of :1742-1748 applies to frames with mvuRight (Nleft == -1 here); the KeyFrame form has none
-    if (rc == VSG_OK) rc = wc.launch(cur, kLast && cur->has_uright ? kGateUr : kGateNone, 256, nullptr, 0, D, Q);
+    if (rc == VSG_OK) rc = wc.launch(F, gate_mode, 256, nullptr, 0, R.qdesc, R.Q);
     if (rc != VSG_OK) {
       hipStreamSynchronize(c->stream);  // nothing of this call may still write the arena when the next one fills it
       return rc;
     }
-    return wc.finish();  // VSG_RETRY: the lists overflowed their array; the whole call runs again
+    return wc.finish();
   }
-  void outs(int n, uint8_t *projected, float *u, float *v, void *ur_or_level) const {
+  // copy-out of the per-point results the caller asked for
+  void outs(int n, uint8_t *valid, float *x, float *y, void *aux) const {
     const size_t N = (size_t)n;
-    if (projected) memcpy(projected, hp + oV, N);
-    if (u) memcpy(u, hp + oU, N * 4);
-    if (v) memcpy(v, hp + oVv, N * 4);
-    if (ur_or_level) memcpy(ur_or_level, hp + oA, N * 4);
+    if (valid) memcpy(valid, hp + oV, N);
+    if (x) memcpy(x, hp + oX, N * 4);
+    if (y) memcpy(y, hp + oY, N * 4);
+    if (aux) memcpy(aux, hp + oA, N * 4);
   }
 };
+
+template <bool kLast>
+void launch_project(const ResidentDev &R, const vsg_mappoints *mp, const vsg_frame *last, const ProjectArgs &A) {
+  const ProjectOutDev O = {R.valid, R.x, R.y, kLast ? (float *)R.aux : nullptr, kLast ? nullptr : (int32_t *)R.aux,
+                           R.observed};
+  hipLaunchKernelGGL(k_project_points<kLast>, dim3((A.n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
+                     R.skip, kLast ? (const KeyPointPOD *)last->d_kps : (const KeyPointPOD *)nullptr, A, O, R.Q, R.qdesc);
+}
 
 // the checks the two projection searches share, in the order of pose_check
 int project_check(const vsg_frame *cur, const vsg_mappoints *mp, const vsg_frame_pose *pose, const float *scale_factors,
@@ -481,8 +475,8 @@ int vsg_frame_is_in_frustum(vsg_frame *F, vsg_mappoints *mp, int n, const int32_
   rc = ctx_reserve(c, st.total, 0);
   if (rc != VSG_OK) return rc;
   uint8_t *hp = c->h_pin, *dp = c->d_pin;
-  rc = stage_slots(mp, n, slots, (int32_t *)(hp + oS));
-  if (rc != VSG_OK) return rc;
+  if (!slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
+  if (slots) memcpy(hp + oS, slots, N * 4);
   const FrustumOutDev O = {dp + oV,
                            (float *)(dp + oX),
                            (float *)(dp + oY),
@@ -518,56 +512,27 @@ int vsg_frame_search_local_points(vsg_frame *F, vsg_mappoints *mp, int n, const 
     return VSG_ERR_INVALID;
   if (n_to_match) *n_to_match = 0;
   if (n == 0) return 0;
-  if (!slots && n > mp->capacity) return VSG_ERR_INVALID;
-  if (slots)
-    for (int i = 0; i < n; i++)
-      if (slots[i] < 0 || slots[i] >= mp->capacity) return VSG_ERR_INVALID;  // before the first enqueue
+  if (!slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
   FrustumArgs A = frustum_args(F, pose, viewing_cos_limit, n);
   A.b_factor = th != 1.0;  // ORBmatcher.cc:46
   A.th = th, A.far_points = far_points ? 1 : 0, A.th_far_points = th_far_points;
   for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
-  const size_t N = (size_t)n;
   return with_retry([&]() -> int {
-    WindowCall wc;
-    // this call's own blocks sit behind the window call's in both arenas
-    Stage st;
-    const size_t oS = st.add(slots ? N * 4 : 0), oK = st.add(skip ? N : 0), oV = st.add(N), oO = st.add(N),
-                 oX = st.add(N * 4), oY = st.add(N * 4);
-    rc = wc.begin(F->device, n, kWinList, false, 0, st.total);
-    if (rc != VSG_OK) return rc;
-    ThreadCtx *c = wc.c;
-    Stage sd;
-    const size_t dQ = sd.add(N * sizeof(WinQuery)), dD = sd.add(N * 32);
-    rc = ctx_reserve(c, 0, sd.total);
-    if (rc != VSG_OK) return rc;
-    const size_t base = wc.bytes();
-    uint8_t *hp = c->h_pin + base, *dp = c->d_pin + base;
-    if (slots) memcpy(hp + oS, slots, N * 4);
-    if (skip) memcpy(hp + oK, skip, N);
-    const FrustumOutDev O = {dp + oV, (float *)(dp + oX), (float *)(dp + oY), nullptr, nullptr, nullptr, nullptr, dp + oO};
-    WinQuery *Q = (WinQuery *)(c->d_buf + dQ);
-    uint8_t *D = c->d_buf + dD;
-    hipLaunchKernelGGL(k_frustum, dim3((n + 63) / 64), dim3(64), 0, c->stream, store_dev(mp),
-                       slots ? (const int32_t *)(dp + oS) : (const int32_t *)nullptr,
-                       skip ? (const uint8_t *)(dp + oK) : (const uint8_t *)nullptr, A, O, Q, D);
-    rc = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+    ResidentCall call;
     // the stereo gate of :97-102 applies to frames with mvuRight (Nleft == -1 here)
-    if (rc == VSG_OK) rc = wc.launch(F, F->has_uright ? kGateUr : kGateNone, 256, nullptr, 0, D, Q);
-    if (rc != VSG_OK) {
-      hipStreamSynchronize(c->stream);  // nothing of this call may still write the arena when the next one fills it
-      return rc;
-    }
-    rc = wc.finish();
-    if (rc != VSG_OK) return rc;  // VSG_RETRY: the lists overflowed their array; the whole call runs again
-    const uint8_t *hv = hp + oV;
+    rc = call.run(F, n, slots, skip, true, false, F->has_uright ? kGateUr : kGateNone, [&](const ResidentDev &R) {
+      const FrustumOutDev O = {R.valid, R.x, R.y, nullptr, nullptr, nullptr, nullptr, R.observed};
+      hipLaunchKernelGGL(k_frustum, dim3((n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots, R.skip, A, O,
+                         R.Q, R.qdesc);
+    });
+    if (rc != VSG_OK) return rc;
+    const uint8_t *hv = call.hp + call.oV;
     int to_match = 0;
     for (int i = 0; i < n; i++) to_match += hv[i];
     if (n_to_match) *n_to_match = to_match;
-    if (in_view) memcpy(in_view, hv, N);
-    if (proj_x) memcpy(proj_x, hp + oX, N * 4);
-    if (proj_y) memcpy(proj_y, hp + oY, N * 4);
+    call.outs(n, in_view, proj_x, proj_y, nullptr);
     // a point that is in view but too far has an empty list: the pass does nothing for it, as :53-54
-    return walk::search_local(wc.lists(), n, -1, hv, nullptr, nullptr, hp + oO, nnratio, nullptr, nullptr,
+    return walk::search_local(call.wc.lists(), n, -1, hv, nullptr, nullptr, call.hp + call.oO, nnratio, nullptr, nullptr,
                               train_blocked, train_match);
   });
 }
@@ -599,15 +564,18 @@ int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *
     for (int i = 0; i < n; i++) last_angle[i] = lk[i].angle;
   }
   return with_retry([&]() -> int {
-    ProjectCall pc;
-    rc = pc.run<true>(cur, mp, last, n, last_slots, nullptr, A);
+    ResidentCall call;
+    // the stereo gate of :1742-1748 applies to frames with mvuRight (Nleft == -1 here)
+    rc = call.run(cur, n, last_slots, nullptr, true, true, cur->has_uright ? kGateUr : kGateNone,
+                  [&](const ResidentDev &R) { launch_project<true>(R, mp, last, A); });
     if (rc != VSG_OK) return rc;
-    pc.outs(n, projected, u, v, ur);
+    call.outs(n, projected, u, v, ur);
     const vsg_keypoint *hk = cur->h_kps.data();
     // a feature without a map point, an outlier and a point that does not project have empty lists: the pass does nothing
     // for them, as the `continue`s of :1689-1709
-    return walk::search_last(pc.wc.lists(), n, -1, last_angle.data(), pc.hp + pc.oO, [&](int i) { return hk[i].angle; },
-                             walk::TH_HIGH, check_orientation != 0, train_blocked, train_match);
+    return walk::search_last(call.wc.lists(), n, -1, last_angle.data(), call.hp + call.oO,
+                             [&](int i) { return hk[i].angle; }, walk::TH_HIGH, check_orientation != 0, train_blocked,
+                             train_match);
   });
 }
 
@@ -620,17 +588,16 @@ int vsg_frame_search_keyframe_points(vsg_frame *cur, vsg_mappoints *mp, int n, c
   if (rc != VSG_OK) return rc;
   if (n < 0 || (check_orientation && n > 0 && !kf_angle)) return VSG_ERR_INVALID;
   if (n == 0) return 0;
-  if (!slots) return VSG_ERR_INVALID;
-  for (int i = 0; i < n; i++)
-    if (slots[i] < 0 || slots[i] >= mp->capacity) return VSG_ERR_INVALID;  // before the first enqueue
+  if (!slots || !slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
   const ProjectArgs A = project_args(cur, pose, n, th, scale_factors, nlevels);
   return with_retry([&]() -> int {
-    ProjectCall pc;
-    rc = pc.run<false>(cur, mp, nullptr, n, slots, skip, A);
+    ResidentCall call;  // (this search has no stereo gate)
+    rc = call.run(cur, n, slots, skip, false, true, kGateNone,
+                  [&](const ResidentDev &R) { launch_project<false>(R, mp, nullptr, A); });
     if (rc != VSG_OK) return rc;
-    pc.outs(n, projected, u, v, predicted_level);
+    call.outs(n, projected, u, v, predicted_level);
     const vsg_keypoint *hk = cur->h_kps.data();
-    return walk::search_kf_projection(pc.wc.lists(), n, kf_angle, [&](int i) { return hk[i].angle; }, orb_dist,
+    return walk::search_kf_projection(call.wc.lists(), n, kf_angle, [&](int i) { return hk[i].angle; }, orb_dist,
                                       check_orientation != 0, occupied, train_match);
   });
 }

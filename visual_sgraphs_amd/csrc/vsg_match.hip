@@ -502,7 +502,7 @@ __global__ __launch_bounds__(256) void k_search_triangulation(const NodePair *pa
 // (vsg_walks.h: index | distance << 15 | octave << 24).  The walk over the queries that follows is inherently
 // sequential (a claimed feature blocks later queries) and touches a dozen candidates per query: it runs on the host
 // over these entries, like the reference's own loop -- the first version walked the queries with a single wavefront
-// on the device and took 1.3 ms for 1000 queries, 25x the CPU.  (Resident frames: k_window_search, vsg_frame.hip.)
+// on the device and took 1.3 ms for 1000 queries, 25x the CPU.  (Resident frames: k_window_search, vsg_window.hip.)
 __global__ __launch_bounds__(256) void k_cand_dist(const uint8_t *qDesc, const int *qOf, const int *candIdx,
                                                    const uint8_t *tDesc, const uint8_t *tOct, int ncand,
                                                    uint32_t *ent) {
