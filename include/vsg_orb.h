@@ -661,6 +661,52 @@ int vsg_frame_search_keyframe_points(vsg_frame *cur, vsg_mappoints *mp, int n, c
                                      int32_t *train_match, uint8_t *projected, float *u, float *v,
                                      int32_t *predicted_level);
 
+/* The back end's routines that project map points into ONE KeyFrame, with their geometry on the device: the points are
+ * those of a vsg_mappoints store, the per-point loop runs as a kernel in front of the window search (one enqueue, one
+ * wait), and only the pose, the slot list and the skip flags cross to the device.  The four loops (ORBmatcher.cc:452-486,
+ * :559-595, :1194-1241, :1360-1395) are one: p3Dc = Tcw * p3Dw, p3Dc(2) < 0 rejects, Pinhole::project,
+ * KeyFrame::IsInImage (KeyFrame.cc:880-883: maximum exclusive, a NaN rejected) on the KeyFrame's `const int` bounds
+ * (KeyFrame.h:419-422, the resident frame's own truncated toward zero as at KeyFrame.cc:52), the band 0.8f * mfMinDistance ..
+ * 1.2f * mfMaxDistance, PO.dot(Pn) < 0.5 * dist3D rejects, PredictScale, radius = th * mvScaleFactors[nPredictedLevel].
+ * Float arithmetic in a fixed order, one rounding per operation.  Query i = slot slots[i];
+ * skip[i] != 0 (NULL: none) = the routine `continue`s before GetWorldPos().  pose = Tcw / Ow with the KeyFrame's
+ * intrinsics: pKF->GetPose() / GetCameraCenter(), or for the Sim3 routines the caller's decomposition
+ * Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()), Ow = Tcw.inverse().translation() (:433-434,
+ * :1340-1341).  pose->n_levels <= nlevels <= 16.  Optional outs per query: projected[i] (reached GetFeaturesInArea), u[i],
+ * v[i], ur[i], predicted_level[i] (0 where not projected).  Checked before anything is enqueued: NULL handles, frame and
+ * store on different devices, nlevels outside 1..16, pose->n_levels > nlevels, n < 0, slots == NULL or a slot outside
+ * [0, capacity): VSG_ERR_INVALID; a KeyFrame with Nleft != -1 (bRight, mpCamera2: :1154-1159): VSG_ERR_UNSUPPORTED; n == 0
+ * returns 0.  One target KeyFrame per call, as in the reference.
+ *
+ * int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, th, false) (ORBmatcher.cc:1148-1335) as
+ * LocalMapping::SearchInNeighbors calls it for every neighbour (LocalMapping.cc:770, :800): the search.  skip[i] =
+ * !pMP || isBad() || IsInKeyFrame(pKF) (:1177-1192).  Chi-square gate with inv_level_sigma2 = pKF->mvInvLevelSigma2
+ * (:1269-1293), scan from 256.  best_idx / best_dist per QUERY, -1 / 256 when nothing qualifies; returns the count with
+ * bestDist <= TH_LOW (:1310).  Results are those of vsg_frame_fuse given the projected points in order; the replace / add
+ * walk stays vsg_fuse_decide. */
+int vsg_frame_fuse_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                          const vsg_frame_pose *pose, float th, const float *scale_factors,
+                          const float *inv_level_sigma2, int nlevels, int32_t *best_idx, int32_t *best_dist,
+                          uint8_t *projected, float *u, float *v, float *ur, int32_t *predicted_level);
+/* int ORBmatcher::Fuse(KeyFrame *pKF, Sim3f &Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1337-1446) as
+ * LoopClosing::SearchAndFuse calls it (LoopClosing.cc:2012, :2054).  skip[i] = isBad() || spAlreadyFound.count(pMP)
+ * (:1356; the set is pKF->GetMapPoints(), :1344).  No gate, scan from INT_MAX (:1406): best_dist is INT_MAX when nothing
+ * qualifies.  Results are those of vsg_frame_fuse_sim3 given the projected points in order. */
+int vsg_frame_fuse_points_sim3(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                               const vsg_frame_pose *pose, float th, const float *scale_factors, int nlevels,
+                               int32_t *best_idx, int32_t *best_dist, uint8_t *projected, float *u, float *v,
+                               int32_t *predicted_level);
+/* int ORBmatcher::SearchByProjection(KeyFrame *pKF, Sim3f &Scw, vpPoints, vpMatched, th, ratioHamming)
+ * (ORBmatcher.cc:430-528) as LoopClosing calls it (LoopClosing.cc:735, :757, :944); the twin with vpPointsKFs (:530-641)
+ * goes through the adaptor as for vsg_frame_search_by_projection_sim3.  skip[i] = isBad() || spAlreadyFound.count(pMP)
+ * (:448).  matched (one entry per KeyFrame feature, -1 = vpMatched[i] not set, in / out), the accept rule
+ * bestDist <= TH_LOW * ratioHamming (:520) and the return value are those of vsg_frame_search_by_projection_sim3 given the
+ * projected points in order; a new entry holds the QUERY index. */
+int vsg_frame_search_sim3_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                                 const vsg_frame_pose *pose, float th, float ratio_hamming, const float *scale_factors,
+                                 int nlevels, int32_t *matched, uint8_t *projected, float *u, float *v,
+                                 int32_t *predicted_level);
+
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, S12, th) (ORBmatcher.h:76,
  * ORBmatcher.cc:1448-1665).  Direction 1 (:1489-1565): for each KF1 feature i1 with a usable, not yet matched map
  * point that projects into KF2: idx1[k] = i1, its descriptor, (u, v, radius, predicted level) in KF2; direction 2

@@ -906,6 +906,81 @@ class ResidentMatcher {
     return rc;
   }
 
+  // The three routines below project the points of a ResidentMapPoints store into ONE KeyFrame on the device
+  // (vsg_frame_fuse_points, vsg_frame_fuse_points_sim3, vsg_frame_search_sim3_points): slots[i] = the slot of the i-th
+  // point of the routine's list, skip[i] != 0 = the routine `continue`s before GetWorldPos() (nullptr: none).  pose = Tcw /
+  // Ow with pKF's intrinsics: pKF->GetPose() / GetCameraCenter(), or the decomposition of Scw the Sim3 routines start with
+  // (ORBmatcher.cc:433-434, :1340-1341).  out (optional): per point projected, u, v, ur, level.
+  struct IntoKeyFrameProjection {
+    std::vector<uint8_t> projected;
+    std::vector<float> u, v, ur;
+    std::vector<int32_t> level;
+    void assign(size_t m) { projected.assign(m, 0), u.assign(m, 0.f), v.assign(m, 0.f), ur.assign(m, 0.f), level.assign(m, 0); }
+    void resize(size_t n) { projected.resize(n), u.resize(n), v.resize(n), ur.resize(n), level.resize(n); }
+  };
+  // int Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const float th = 3.0, const bool bRight = false)
+  // (ORBmatcher.h:84, ORBmatcher.cc:1148-1335; LocalMapping.cc:770, :800) with bRight == false: the search.  skip[i] =
+  // !pMP || isBad() || IsInKeyFrame(pKF).  bestIdx / bestDist per point (-1 / 256 when nothing qualifies); the caller then
+  // walks them as for the Fuse above.  Returns the count with bestDist <= TH_LOW.
+  int Fuse(ResidentFrame &pKF, const ResidentMapPoints &mp, const std::vector<int32_t> &slots, const uint8_t *skip,
+           const FramePose &pose, float th, const std::vector<float> &mvScaleFactors,
+           const std::vector<float> &mvInvLevelSigma2, std::vector<int32_t> &bestIdx, std::vector<int32_t> &bestDist,
+           IntoKeyFrameProjection *out = nullptr) const {
+    const int n = (int)slots.size();
+    if (mvInvLevelSigma2.size() != mvScaleFactors.size()) check(VSG_ERR_INVALID, "vsg_frame_fuse_points");
+    const size_t m = n > 0 ? n : 1;
+    bestIdx.assign(m, -1), bestDist.assign(m, 256);
+    if (out) out->assign(m);
+    const int rc = vsg_frame_fuse_points(
+        pKF.handle(), mp.handle(), n, slots.data(), skip, &pose, th, mvScaleFactors.data(), mvInvLevelSigma2.data(),
+        (int)mvScaleFactors.size(), bestIdx.data(), bestDist.data(), out ? out->projected.data() : nullptr,
+        out ? out->u.data() : nullptr, out ? out->v.data() : nullptr, out ? out->ur.data() : nullptr,
+        out ? out->level.data() : nullptr);
+    check(rc, "vsg_frame_fuse_points");
+    bestIdx.resize(n), bestDist.resize(n);
+    if (out) out->resize(n);
+    return rc;
+  }
+  // int Fuse(KeyFrame *pKF, Sophus::Sim3f &Scw, const vector<MapPoint *> &vpPoints, float th, vector<MapPoint *>
+  // &vpReplacePoint) (ORBmatcher.h:87, ORBmatcher.cc:1337-1446; LoopClosing.cc:2012, :2054): the search.  skip[i] = isBad() ||
+  // spAlreadyFound.count(pMP) (:1356; the set is pKF->GetMapPoints(), :1344).  bestDist is INT_MAX when nothing
+  // qualifies.
+  int Fuse(ResidentFrame &pKF, const ResidentMapPoints &mp, const std::vector<int32_t> &slots, const uint8_t *skip,
+           const FramePose &pose, float th, const std::vector<float> &mvScaleFactors, std::vector<int32_t> &bestIdx,
+           std::vector<int32_t> &bestDist, IntoKeyFrameProjection *out = nullptr) const {
+    const int n = (int)slots.size();
+    const size_t m = n > 0 ? n : 1;
+    bestIdx.assign(m, -1), bestDist.assign(m, 0x7FFFFFFF);
+    if (out) out->assign(m);
+    const int rc = vsg_frame_fuse_points_sim3(
+        pKF.handle(), mp.handle(), n, slots.data(), skip, &pose, th, mvScaleFactors.data(), (int)mvScaleFactors.size(),
+        bestIdx.data(), bestDist.data(), out ? out->projected.data() : nullptr, out ? out->u.data() : nullptr,
+        out ? out->v.data() : nullptr, out ? out->level.data() : nullptr);
+    check(rc, "vsg_frame_fuse_points_sim3");
+    bestIdx.resize(n), bestDist.resize(n);
+    if (out) out->resize(n);
+    return rc;
+  }
+  // int SearchByProjection(KeyFrame *pKF, Sophus::Sim3f &Scw, const vector<MapPoint *> &vpPoints, vector<MapPoint *>
+  // &vpMatched, int th, float ratioHamming = 1.0) (ORBmatcher.h:58, ORBmatcher.cc:430-528; LoopClosing.cc:735, :757, :944).
+  // skip[i] = isBad() || spAlreadyFound.count(pMP).  matched[i] != -1 = vpMatched[i] is set; new entries = index into slots.
+  int SearchByProjection(ResidentFrame &pKF, const ResidentMapPoints &mp, const std::vector<int32_t> &slots,
+                         const uint8_t *skip, const FramePose &pose, int th, float ratioHamming,
+                         const std::vector<float> &mvScaleFactors, std::vector<int32_t> &matched,
+                         IntoKeyFrameProjection *out = nullptr) const {
+    const int n = (int)slots.size();
+    matched.resize(pKF.N() > 0 ? pKF.N() : 1, -1);
+    if (out) out->assign(n > 0 ? n : 1);
+    const int rc = vsg_frame_search_sim3_points(
+        pKF.handle(), mp.handle(), n, slots.data(), skip, &pose, (float)th, ratioHamming, mvScaleFactors.data(),
+        (int)mvScaleFactors.size(), matched.data(), out ? out->projected.data() : nullptr, out ? out->u.data() : nullptr,
+        out ? out->v.data() : nullptr, out ? out->level.data() : nullptr);
+    check(rc, "vsg_frame_search_sim3_points");
+    matched.resize(pKF.N());
+    if (out) out->resize(n);
+    return rc;
+  }
+
   // SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)  (ORBmatcher.cc:643-756)
   int SearchForInitialization(ResidentFrame &F1, ResidentFrame &F2, const std::vector<float> &prevX,
                               const std::vector<float> &prevY, int windowSize, std::vector<int32_t> &vnMatches12) const {

@@ -13,7 +13,9 @@
 //
 // k_project_points does the same for the two other searches of Tracking that project map points through a Frame's
 // pose (vsg_project.h): SearchByProjection(CurrentFrame, LastFrame) with the last frame resident (its octaves are read
-// on the device) and SearchByProjection(CurrentFrame, pKF, sAlreadyFound) for relocalisation.
+// on the device) and SearchByProjection(CurrentFrame, pKF, sAlreadyFound) for relocalisation; and for the back end's
+// routines that project into ONE KeyFrame: the two Fuse and SearchByProjection(pKF, Scw, ...), whose Sim3 the caller
+// has decomposed into a pose as the routines themselves do on entry.
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -157,17 +159,20 @@ struct ProjectArgs {
 struct ProjectOutDev {
   uint8_t *valid;     // the point reaches GetFeaturesInArea
   float *u, *v;
-  float *ur;          // last-frame form
-  int32_t *level;     // KeyFrame form
+  float *ur;          // last-frame form, into-KeyFrame form
+  int32_t *level;     // relocalisation form, into-KeyFrame form
   uint8_t *observed;  // last-frame form: Observations() > 0 of query i's point, for the ordered host pass
 };
 
 // The projection loops of SearchByProjection(CurrentFrame, LastFrame) (kLast, ORBmatcher.cc:1686-1724) and of
 // SearchByProjection(CurrentFrame, pKF, sAlreadyFound) (ORBmatcher.cc:1895-1930), one lane per query, 64 lanes per
-// workgroup like k_frustum.  kLast: query i = feature i of the resident last frame, slots[i] < 0 = no map point or an
-// outlier, the octave is the last frame's own.  Otherwise query i = slot slots[i], skip[i] = isBad() or
-// in sAlreadyFound.  A query that is not searched gets the inactive flag and no descriptor (see k_frustum).
-template <bool kLast>
+// workgroup like k_frustum.  kProjLast: query i = feature i of the resident last frame, slots[i] < 0 = no map point or an
+// outlier, the octave is the last frame's own.  kProjReloc: query i = slot slots[i], skip[i] = isBad() or
+// in sAlreadyFound.  kProjKeyFrame: the loop of Fuse x2 and SearchByProjection(pKF, Scw, ...) (ORBmatcher.cc:1194-1241,
+// :1360-1395, :452-486), query i = slot slots[i], skip[i] = isBad(), IsInKeyFrame(pKF) or in spAlreadyFound; A.bounds
+// are the KeyFrame's truncated ones.  A query that is not searched gets the inactive flag and no descriptor (see k_frustum).
+enum { kProjLast = 0, kProjReloc = 1, kProjKeyFrame = 2 };
+template <int kForm>
 __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t *__restrict__ slots,
                                                        const uint8_t *__restrict__ skip,
                                                        const KeyPointPOD *__restrict__ last_kps, ProjectArgs A,
@@ -181,15 +186,19 @@ __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t
   uint8_t observed = 0;
   if (s >= 0 && !(skip && skip[i])) {
     const float *P = S.pos + 3 * (size_t)s;
-    if (kLast) {
+    if (kForm == kProjLast) {
       const int oct = last_kps[i].octave;  // nLastOctave (:1711); the host refused octaves outside the pyramid
       o = project_last_point(A.cam, A.bounds, P);
       if ((unsigned)oct >= 16u) o.valid = 0;
       if (o.valid) w = win_last(o.u, o.v, o.ur, oct, A.th, A.direction, A.scale_factors);
       observed = S.observed[s];
-    } else {
+    } else if (kForm == kProjReloc) {
       o = project_kf_point(A.cam, A.bounds, P, S.min_dist[s], S.max_dist[s]);
       if (o.valid) w = win_kf(o.u, o.v, fmul(A.th, A.scale_factors[o.level]), o.level);  // radius: :1928
+    } else {
+      o = project_keyframe_point(A.cam, A.bounds, P, S.normal + 3 * (size_t)s, S.min_dist[s], S.max_dist[s]);
+      // radius: :1241 / :1395 / :486; the level window [l - 1, l] and Fuse's ur ride in the query
+      if (o.valid) w = win_keyframe_area(o.u, o.v, fmul(A.th, A.scale_factors[o.level]), o.level, o.ur, false);
     }
     if (o.valid) copy_desc(qdesc + 32 * (size_t)i, S.desc + 32 * (size_t)s);
   }
@@ -256,35 +265,44 @@ int copy_end(ThreadCtx *c) {
   return e1 == hipSuccess && e2 == hipSuccess ? VSG_OK : VSG_ERR_HIP;
 }
 
-// What the three searches on resident map points share: a projection kernel that writes every point's WinQuery and
+// What the six searches on resident map points share: a projection kernel that writes every point's WinQuery and
 // gathers its descriptor, k_window_search right behind it on the same stream, one wait.  The call's own blocks
-// [slots? | skip? | valid | observed? | x | y | aux?] sit behind the window call's in the pinned arena, [WinQuery |
-// descriptors] in the device arena.
+// [slots? | skip? | valid | observed? | x | y | aux? | aux2?] sit behind the window call's in the pinned arena,
+// [WinQuery | descriptors] in the device arena.
 struct ResidentDev {  // what the projection kernel is launched with: the device side of those blocks and the stream
   const int32_t *slots;
   const uint8_t *skip;
   uint8_t *valid, *observed;
   float *x, *y;
-  void *aux;  // one more 4-byte value per point: ur (last-frame form) / level (KeyFrame form)
+  void *aux;   // one more 4-byte value per point: ur (last-frame form, into-KeyFrame form) / level (relocalisation form)
+  void *aux2;  // and another: level (into-KeyFrame form)
   WinQuery *Q;
   uint8_t *qdesc;
   hipStream_t stream;
 };
+// How the window kernel behind the projection runs: candidate lists for an ordered host pass, or the best candidate per
+// query (Fuse) with its scan's start value and, for the chi-square gate, pKF->mvInvLevelSigma2.
+struct ResidentMode {
+  int mode, gate_mode, best_init;
+  const float *inv_sigma2;
+  int nlevels;
+};
+ResidentMode resident_lists(int gate_mode) { return {kWinList, gate_mode, 256, nullptr, 0}; }
 struct ResidentCall {
   WindowCall wc;
-  size_t oS = 0, oK = 0, oV = 0, oO = 0, oX = 0, oY = 0, oA = 0;
+  size_t oS = 0, oK = 0, oV = 0, oO = 0, oX = 0, oY = 0, oA = 0, oA2 = 0;
   uint8_t *hp = nullptr;  // the call's blocks, host side
 
   // launch(ResidentDev) enqueues the projection kernel.  VSG_RETRY: the lists overflowed, the whole call runs again
   template <class Launch>
-  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, bool observed, bool aux, int gate_mode,
-          Launch launch) {
+  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, bool observed, bool aux, bool aux2,
+          const ResidentMode &M, Launch launch) {
     const size_t N = (size_t)n;
     Stage st, sd;
     oS = st.add(slots ? N * 4 : 0), oK = st.add(skip ? N : 0), oV = st.add(N), oO = st.add(observed ? N : 0);
-    oX = st.add(N * 4), oY = st.add(N * 4), oA = st.add(aux ? N * 4 : 0);
+    oX = st.add(N * 4), oY = st.add(N * 4), oA = st.add(aux ? N * 4 : 0), oA2 = st.add(aux2 ? N * 4 : 0);
     const size_t dQ = sd.add(N * sizeof(WinQuery)), dD = sd.add(N * 32);
-    int rc = wc.begin(F->device, n, kWinList, false, 0, st.total);
+    int rc = wc.begin(F->device, n, M.mode, false, 0, st.total);
     if (rc != VSG_OK) return rc;
     ThreadCtx *c = wc.c;
     rc = ctx_reserve(c, 0, sd.total);
@@ -296,10 +314,11 @@ struct ResidentCall {
     if (skip) memcpy(hp + oK, skip, N);
     const ResidentDev R = {slots ? (const int32_t *)(dp + oS) : nullptr, skip ? dp + oK : nullptr, dp + oV,
                            observed ? dp + oO : nullptr, (float *)(dp + oX), (float *)(dp + oY),
-                           aux ? dp + oA : nullptr, (WinQuery *)(c->d_buf + dQ), c->d_buf + dD, c->stream};
+                           aux ? dp + oA : nullptr, aux2 ? dp + oA2 : nullptr, (WinQuery *)(c->d_buf + dQ),
+                           c->d_buf + dD, c->stream};
     launch(R);
     rc = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
-    if (rc == VSG_OK) rc = wc.launch(F, gate_mode, 256, nullptr, 0, R.qdesc, R.Q);
+    if (rc == VSG_OK) rc = wc.launch(F, M.gate_mode, M.best_init, M.inv_sigma2, M.nlevels, R.qdesc, R.Q);
     if (rc != VSG_OK) {
       hipStreamSynchronize(c->stream);  // nothing of this call may still write the arena when the next one fills it
       return rc;
@@ -307,20 +326,22 @@ struct ResidentCall {
     return wc.finish();
   }
   // copy-out of the per-point results the caller asked for
-  void outs(int n, uint8_t *valid, float *x, float *y, void *aux) const {
+  void outs(int n, uint8_t *valid, float *x, float *y, void *aux, void *aux2 = nullptr) const {
     const size_t N = (size_t)n;
     if (valid) memcpy(valid, hp + oV, N);
     if (x) memcpy(x, hp + oX, N * 4);
     if (y) memcpy(y, hp + oY, N * 4);
     if (aux) memcpy(aux, hp + oA, N * 4);
+    if (aux2) memcpy(aux2, hp + oA2, N * 4);
   }
 };
 
-template <bool kLast>
+template <int kForm>
 void launch_project(const ResidentDev &R, const vsg_mappoints *mp, const vsg_frame *last, const ProjectArgs &A) {
-  const ProjectOutDev O = {R.valid, R.x, R.y, kLast ? (float *)R.aux : nullptr, kLast ? nullptr : (int32_t *)R.aux,
-                           R.observed};
-  hipLaunchKernelGGL(k_project_points<kLast>, dim3((A.n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
+  const bool kLast = kForm == kProjLast;
+  const ProjectOutDev O = {R.valid, R.x, R.y, kForm != kProjReloc ? (float *)R.aux : nullptr,
+                           (int32_t *)(kForm == kProjReloc ? R.aux : kForm == kProjKeyFrame ? R.aux2 : nullptr), R.observed};
+  hipLaunchKernelGGL(k_project_points<kForm>, dim3((A.n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
                      R.skip, kLast ? (const KeyPointPOD *)last->d_kps : (const KeyPointPOD *)nullptr, A, O, R.Q, R.qdesc);
 }
 
@@ -343,6 +364,50 @@ ProjectArgs project_args(const vsg_frame *cur, const vsg_frame_pose *pose, int n
   A.n = n, A.th = th;
   for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
   return A;
+}
+
+// What the three routines that project into one KeyFrame check, in the order of project_check, BEFORE anything is
+// enqueued; outs_ok: the entry's own required arrays are there.  VSG_OK with *go == false: n == 0, the entry returns 0.
+int keyframe_check(const vsg_frame *kf, const vsg_mappoints *mp, int n, const int32_t *slots, const vsg_frame_pose *pose,
+                   const float *scale_factors, int nlevels, bool outs_ok, bool *go) {
+  *go = false;
+  const int rc = pose_check(kf, mp, pose);  // Nleft != -1: bRight / mpCamera2 (ORBmatcher.cc:1154-1159)
+  if (rc != VSG_OK) return rc;
+  if (!scale_factors || !outs_ok || nlevels < 1 || nlevels > 16 || pose->n_levels > nlevels || n < 0)
+    return VSG_ERR_INVALID;
+  if (n == 0) return VSG_OK;
+  if (!slots || !slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
+  *go = true;
+  return VSG_OK;
+}
+
+// ... and their projection arguments: the bounds are KeyFrame::mnMinX .. mnMaxY, the Frame's truncated to int
+ProjectArgs keyframe_args(const vsg_frame *kf, const vsg_frame_pose *pose, int n, float th, const float *scale_factors,
+                          int nlevels) {
+  ProjectArgs A = project_args(kf, pose, n, th, scale_factors, nlevels);
+  A.bounds = keyframe_bounds(A.bounds);
+  return A;
+}
+
+// Fuse's search on resident points: the projection kernel, then k_window_search in best mode; one wait
+int fuse_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                const vsg_frame_pose *pose, float th, const float *scale_factors, int nlevels, const ResidentMode &M,
+                int32_t *best_idx, int32_t *best_dist, uint8_t *projected, float *u, float *v, float *ur,
+                int32_t *predicted_level) {
+  const ProjectArgs A = keyframe_args(kf, pose, n, th, scale_factors, nlevels);
+  ResidentCall call;
+  const int rc = call.run(kf, n, slots, skip, false, true, true, M,
+                          [&](const ResidentDev &R) { launch_project<kProjKeyFrame>(R, mp, nullptr, A); });
+  if (rc != VSG_OK) return rc;
+  call.outs(n, projected, u, v, ur, predicted_level);
+  const int32_t *b = call.wc.best();
+  int nfused = 0;
+  for (int k = 0; k < n; k++) {
+    best_idx[k] = b[2 * k];
+    best_dist[k] = b[2 * k] >= 0 ? b[2 * k + 1] : M.best_init;
+    if (b[2 * k] >= 0 && b[2 * k + 1] <= walk::TH_LOW) nfused++;  // :1310 / :1428
+  }
+  return nfused;
 }
 
 }  // namespace
@@ -520,11 +585,12 @@ int vsg_frame_search_local_points(vsg_frame *F, vsg_mappoints *mp, int n, const 
   return with_retry([&]() -> int {
     ResidentCall call;
     // the stereo gate of :97-102 applies to frames with mvuRight (Nleft == -1 here)
-    rc = call.run(F, n, slots, skip, true, false, F->has_uright ? kGateUr : kGateNone, [&](const ResidentDev &R) {
-      const FrustumOutDev O = {R.valid, R.x, R.y, nullptr, nullptr, nullptr, nullptr, R.observed};
-      hipLaunchKernelGGL(k_frustum, dim3((n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots, R.skip, A, O,
-                         R.Q, R.qdesc);
-    });
+    rc = call.run(F, n, slots, skip, true, false, false, resident_lists(F->has_uright ? kGateUr : kGateNone),
+                  [&](const ResidentDev &R) {
+                    const FrustumOutDev O = {R.valid, R.x, R.y, nullptr, nullptr, nullptr, nullptr, R.observed};
+                    hipLaunchKernelGGL(k_frustum, dim3((n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
+                                       R.skip, A, O, R.Q, R.qdesc);
+                  });
     if (rc != VSG_OK) return rc;
     const uint8_t *hv = call.hp + call.oV;
     int to_match = 0;
@@ -566,8 +632,8 @@ int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *
   return with_retry([&]() -> int {
     ResidentCall call;
     // the stereo gate of :1742-1748 applies to frames with mvuRight (Nleft == -1 here)
-    rc = call.run(cur, n, last_slots, nullptr, true, true, cur->has_uright ? kGateUr : kGateNone,
-                  [&](const ResidentDev &R) { launch_project<true>(R, mp, last, A); });
+    rc = call.run(cur, n, last_slots, nullptr, true, true, false, resident_lists(cur->has_uright ? kGateUr : kGateNone),
+                  [&](const ResidentDev &R) { launch_project<kProjLast>(R, mp, last, A); });
     if (rc != VSG_OK) return rc;
     call.outs(n, projected, u, v, ur);
     const vsg_keypoint *hk = cur->h_kps.data();
@@ -592,13 +658,62 @@ int vsg_frame_search_keyframe_points(vsg_frame *cur, vsg_mappoints *mp, int n, c
   const ProjectArgs A = project_args(cur, pose, n, th, scale_factors, nlevels);
   return with_retry([&]() -> int {
     ResidentCall call;  // (this search has no stereo gate)
-    rc = call.run(cur, n, slots, skip, false, true, kGateNone,
-                  [&](const ResidentDev &R) { launch_project<false>(R, mp, nullptr, A); });
+    rc = call.run(cur, n, slots, skip, false, true, false, resident_lists(kGateNone),
+                  [&](const ResidentDev &R) { launch_project<kProjReloc>(R, mp, nullptr, A); });
     if (rc != VSG_OK) return rc;
     call.outs(n, projected, u, v, predicted_level);
     const vsg_keypoint *hk = cur->h_kps.data();
     return walk::search_kf_projection(call.wc.lists(), n, kf_angle, [&](int i) { return hk[i].angle; }, orb_dist,
                                       check_orientation != 0, occupied, train_match);
+  });
+}
+
+int vsg_frame_fuse_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                          const vsg_frame_pose *pose, float th, const float *scale_factors,
+                          const float *inv_level_sigma2, int nlevels, int32_t *best_idx, int32_t *best_dist,
+                          uint8_t *projected, float *u, float *v, float *ur, int32_t *predicted_level) {
+  bool go;
+  const int rc = keyframe_check(kf, mp, n, slots, pose, scale_factors, nlevels,
+                                best_idx && best_dist && inv_level_sigma2, &go);
+  if (rc != VSG_OK) return rc;
+  if (!go) return 0;
+  // the chi-square gate of :1269-1293 reads mvuRight where the KeyFrame has it; bestDist starts at 256 (:1255)
+  return fuse_points(kf, mp, n, slots, skip, pose, th, scale_factors, nlevels,
+                     {kWinBest, kGateChi2, 256, inv_level_sigma2, nlevels}, best_idx, best_dist, projected, u, v, ur,
+                     predicted_level);
+}
+
+int vsg_frame_fuse_points_sim3(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                               const vsg_frame_pose *pose, float th, const float *scale_factors, int nlevels,
+                               int32_t *best_idx, int32_t *best_dist, uint8_t *projected, float *u, float *v,
+                               int32_t *predicted_level) {
+  bool go;
+  const int rc = keyframe_check(kf, mp, n, slots, pose, scale_factors, nlevels, best_idx && best_dist, &go);
+  if (rc != VSG_OK) return rc;
+  if (!go) return 0;
+  // no gate; bestDist starts at INT_MAX (:1406)
+  return fuse_points(kf, mp, n, slots, skip, pose, th, scale_factors, nlevels,
+                     {kWinBest, kGateNone, 0x7FFFFFFF, nullptr, 0}, best_idx, best_dist, projected, u, v, nullptr,
+                     predicted_level);
+}
+
+int vsg_frame_search_sim3_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                                 const vsg_frame_pose *pose, float th, float ratio_hamming, const float *scale_factors,
+                                 int nlevels, int32_t *matched, uint8_t *projected, float *u, float *v,
+                                 int32_t *predicted_level) {
+  bool go;
+  int rc = keyframe_check(kf, mp, n, slots, pose, scale_factors, nlevels, matched != nullptr, &go);
+  if (rc != VSG_OK) return rc;
+  if (!go) return 0;
+  const ProjectArgs A = keyframe_args(kf, pose, n, th, scale_factors, nlevels);
+  return with_retry([&]() -> int {
+    ResidentCall call;
+    rc = call.run(kf, n, slots, skip, false, true, true, resident_lists(kGateNone),
+                  [&](const ResidentDev &R) { launch_project<kProjKeyFrame>(R, mp, nullptr, A); });
+    if (rc != VSG_OK) return rc;
+    call.outs(n, projected, u, v, nullptr, predicted_level);
+    // a point that does not pass :446-483 has an empty list: the pass does nothing for it (:490-491)
+    return walk::search_sim3_projection(call.wc.lists(), n, ratio_hamming, matched);
   });
 }
 

@@ -1,9 +1,13 @@
-// vsg_project.h -- the geometry of the two ORBmatcher searches of Tracking that project map points through the current
-// pose of a Frame, for ONE map point, host and device from one source:
+// vsg_project.h -- the geometry of the ORBmatcher routines that project map points through a pose, for ONE map point,
+// host and device from one source.  Tracking's two searches through the current pose of a Frame:
 //   SearchByProjection(CurrentFrame, LastFrame, th, bMono)                   ORBmatcher.cc:1667-1748
 //   SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)        ORBmatcher.cc:1880-1930
-// k_project_points (vsg_mappoints.hip) runs them one lane per query; tests/_projectcore and the latency probe's
-// caller-side loop compile them for the host.  As in vsg_frustum.h the order is fixed and nothing contracts: every
+// and the back end's four routines that project into a KeyFrame (project_keyframe_point: one loop, written four times):
+//   SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) x2   ORBmatcher.cc:452-486, :559-595
+//   Fuse(pKF, vpMapPoints, th, bRight)                                       ORBmatcher.cc:1194-1241
+//   Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)                             ORBmatcher.cc:1360-1395
+// k_project_points (vsg_mappoints.hip) runs them one lane per query; tests/_projectcore, tests/_keyframecore and the
+// latency probes' caller-side loops compile them for the host.  As in vsg_frustum.h the order is fixed and nothing contracts: every
 // operation is one vsg::f* call = one rounding.
 #pragma once
 #include "vsg_frustum.h"
@@ -17,8 +21,8 @@ struct ImageBounds {
 struct ProjectOut {
   int valid;       // the point reaches GetFeaturesInArea
   float u, v;      // uv                          (meaningful only when valid)
-  float ur;        // uv(0) - mbf * invzc         (last-frame form)
-  int level;       // nPredictedLevel             (KeyFrame form)
+  float ur;        // uv(0) - mbf * invzc         (last-frame form, project_keyframe_point)
+  int level;       // nPredictedLevel             (the two KeyFrame forms)
 };
 
 // x3Dc = Tcw * x3Dw (:1695, :1905), the rows in the order of frustum_point
@@ -65,6 +69,41 @@ VSG_HD ProjectOut project_kf_point(const vsg_frame_pose &cam, const ImageBounds 
   if (dist3D < minDistance || dist3D > maxDistance) return o;                                    // :1922-1923
   o.valid = 1, o.u = u, o.v = v;
   o.level = predict_scale(mfMaxDistance, dist3D, cam.log_scale_factor, cam.n_levels);  // :1925
+  return o;
+}
+
+// KeyFrame::mnMinX .. mnMaxY are `const int` (KeyFrame.h:419-422) initialised from the Frame's floats (KeyFrame.cc:52):
+// truncation toward zero.  IsInImage compares a float with them, i.e. with the int converted back to float.
+VSG_HD ImageBounds keyframe_bounds(const ImageBounds &frame) {
+  return {(float)cvt_int_x86(frame.minX), (float)cvt_int_x86(frame.maxX), (float)cvt_int_x86(frame.minY),
+          (float)cvt_int_x86(frame.maxY)};
+}
+
+// The per-point loop of Fuse(pKF, vpMapPoints, th) (:1194-1238), which is also that of Fuse(pKF, Scw, ...) (:1360-1392)
+// and of the two SearchByProjection(pKF, Scw, ...) (:452-483, :559-592) once those have decomposed Scw into Tcw / Ow
+// (:433-434, :1340-1341); only Fuse's pose form reads ur.  kf = keyframe_bounds() of the resident frame's bounds.
+VSG_HD ProjectOut project_keyframe_point(const vsg_frame_pose &cam, const ImageBounds &kf, const float *P, const float *Pn,
+                                         float mfMinDistance, float mfMaxDistance) {
+  ProjectOut o = {0, 0.0f, 0.0f, 0.0f, 0};
+  float X, Y, Z;
+  camera_point(cam, P, &X, &Y, &Z);  // :1195
+  if (Z < 0.0f) return o;            // :1198 (0 and NaN go on)
+  const float invz = fdiv(1.0f, Z);  // :1204
+  // Pinhole::project (Pinhole.cpp:46-53): fx * X / Z + cx
+  const float u = fadd(fdiv(fmul(cam.fx, X), Z), cam.cx);  // :1206
+  const float v = fadd(fdiv(fmul(cam.fy, Y), Z), cam.cy);
+  // KeyFrame::IsInImage (KeyFrame.cc:880-883): the maximum is exclusive and a NaN is rejected
+  if (!(u >= kf.minX && u < kf.maxX && v >= kf.minY && v < kf.maxY)) return o;  // :1209
+  const float ur = fsub(u, fmul(cam.mbf, invz));                                 // :1215
+  const float PO0 = fsub(P[0], cam.Ow[0]), PO1 = fsub(P[1], cam.Ow[1]), PO2 = fsub(P[2], cam.Ow[2]);  // :1219
+  const float dist3D = fsqrt(dot3(PO0, PO1, PO2, PO0, PO1, PO2));                                       // :1220
+  // GetMaxDistanceInvariance() = 1.2f * mfMaxDistance, GetMinDistanceInvariance() = 0.8f * mfMinDistance (MapPoint.cc:521-531)
+  const float maxDistance = fmul(1.2f, mfMaxDistance), minDistance = fmul(0.8f, mfMinDistance);  // :1217-1218
+  if (dist3D < minDistance || dist3D > maxDistance) return o;                                    // :1223
+  // :1232 `PO.dot(Pn) < 0.5 * dist3D`: the float dot product against a double product (exact: a halving)
+  if ((double)dot3(PO0, PO1, PO2, Pn[0], Pn[1], Pn[2]) < dmul(0.5, (double)dist3D)) return o;
+  o.valid = 1, o.u = u, o.v = v, o.ur = ur;
+  o.level = predict_scale(mfMaxDistance, dist3D, cam.log_scale_factor, cam.n_levels);  // :1238
   return o;
 }
 

@@ -76,6 +76,8 @@ EXPORTS = [
     "vsg_mappoints_read", "vsg_frame_is_in_frustum", "vsg_frame_search_local_points",
     # the motion-model and relocalisation projection searches on resident map points
     "vsg_frame_search_last_frame", "vsg_frame_search_keyframe_points",
+    # Fuse x2 and the Sim3 projection search on resident map points
+    "vsg_frame_fuse_points", "vsg_frame_fuse_points_sim3", "vsg_frame_search_sim3_points",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -333,6 +335,12 @@ def load_library():
                                               _f32p, ci, ci, _u8p, _i32p, C.POINTER(ci), _u8p, _f32p, _f32p, _f32p]
     L.vsg_frame_search_keyframe_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, ci, _f32p, ci, ci,
                                                    _f32p, _u8p, _i32p, _u8p, _f32p, _f32p, _i32p]
+    L.vsg_frame_fuse_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, _f32p, _f32p, ci, _i32p, _i32p,
+                                        _u8p, _f32p, _f32p, _f32p, _i32p]
+    L.vsg_frame_fuse_points_sim3.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, _f32p, ci, _i32p, _i32p,
+                                             _u8p, _f32p, _f32p, _i32p]
+    L.vsg_frame_search_sim3_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, cf, _f32p, ci, _i32p,
+                                               _u8p, _f32p, _f32p, _i32p]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1469,6 +1477,59 @@ class Frame:
             _p(ka, _f32p) if ka is not None and n else None, _p(oc, _u8p), _p(tm, _i32p), _p(pr, _u8p), _p(u, _f32p),
             _p(v, _f32p), _p(lvl, _i32p)), "vsg_frame_search_keyframe_points")
         return nm, tm[:len(oc)], oc, pr[:n], u[:n], v[:n], lvl[:n]
+
+    # ---- Fuse x2 and SearchByProjection(pKF, Scw, ...) on resident map points  (ORBmatcher.cc:1148-1446, :430-528)
+    def _keyframe_points(self, slots, skip):
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(sl)
+        sk = _u8(skip) if skip is not None else None
+        if sk is not None and len(sk) != n:
+            raise ValueError("skip length does not match the slots")
+        m = max(n, 1)
+        outs = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
+        return sl, n, _p(sl, _i32p), _p(sk, _u8p) if sk is not None and n else None, outs
+
+    def FusePoints(self, mp, slots, pose, th, scale_factors, inv_level_sigma2, skip=None):
+        """Fuse(pKF, vpMapPoints, th, false) with self = pKF: slots[i] = slot of vpMapPoints[i], skip[i] != 0 = NULL, isBad()
+        or IsInKeyFrame(pKF), pose = pKF's.  Returns (nFused, best_idx, best_dist, projected, u, v, ur, predicted_level),
+        every array per query."""
+        sl, n, slp, skp, (pr, u, v, lvl) = self._keyframe_points(slots, skip)
+        sf, s2 = _f32(scale_factors), _f32(inv_level_sigma2)
+        if len(s2) != len(sf):
+            raise ValueError("inv_level_sigma2 length does not match the scale factors")
+        bi, bd, ur = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        nf = _check(self._L.vsg_frame_fuse_points(
+            self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), _p(sf, _f32p), _p(s2, _f32p), len(sf),
+            _p(bi, _i32p), _p(bd, _i32p), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(ur, _f32p), _p(lvl, _i32p)),
+            "vsg_frame_fuse_points")
+        return nf, bi[:n], bd[:n], pr[:n], u[:n], v[:n], ur[:n], lvl[:n]
+
+    def FusePoints_Sim3(self, mp, slots, pose, th, scale_factors, skip=None):
+        """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) with self = pKF and pose = the decomposed Scw.  Returns (nFused,
+        best_idx, best_dist, projected, u, v, predicted_level)."""
+        sl, n, slp, skp, (pr, u, v, lvl) = self._keyframe_points(slots, skip)
+        sf = _f32(scale_factors)
+        bi, bd = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        nf = _check(self._L.vsg_frame_fuse_points_sim3(
+            self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), _p(sf, _f32p), len(sf), _p(bi, _i32p),
+            _p(bd, _i32p), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(lvl, _i32p)), "vsg_frame_fuse_points_sim3")
+        return nf, bi[:n], bd[:n], pr[:n], u[:n], v[:n], lvl[:n]
+
+    def SearchSim3Points(self, mp, slots, pose, th, ratio_hamming, scale_factors, matched, skip=None):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) with self = pKF and pose = the decomposed
+        Scw; matched[i] != -1 = vpMatched[i] is set.  Returns (nmatches, matched, projected, u, v, predicted_level); a new
+        entry of matched holds the query index."""
+        sl, n, slp, skp, (pr, u, v, lvl) = self._keyframe_points(slots, skip)
+        sf = _f32(scale_factors)
+        if len(matched) != self.N:
+            raise ValueError("matched length does not match the KeyFrame's features")
+        m = np.full(max(len(matched), 1), -1, np.int32)
+        m[:len(matched)] = matched
+        nm = _check(self._L.vsg_frame_search_sim3_points(
+            self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), float(np.float32(ratio_hamming)), _p(sf, _f32p),
+            len(sf), _p(m, _i32p), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(lvl, _i32p)),
+            "vsg_frame_search_sim3_points")
+        return nm, m[:len(matched)], pr[:n], u[:n], v[:n], lvl[:n]
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono)  (ORBmatcher.cc:1667-1878)
     def SearchByProjection_Last(self, desc, observed, u, v, ur, last_octave, last_angle, th, direction, scale_factors,
