@@ -1,0 +1,70 @@
+// What a caller of the library does per call WITHOUT resident map points, for tools/resident_points_probe.py's side A:
+// the routine's per-point loop on the host (the kernels' own arithmetic, visual_sgraphs_amd/csrc/vsg_frustum.h and
+// vsg_project.h, compiled -O2, one thread) and the gather of what the host-array entry point takes.
+#include <string.h>
+
+#include "vsg_project.h"
+
+extern "C" {
+
+// Tracking::SearchLocalPoints' loop: Frame::isInFrustum per local map point, for vsg_frame_search_by_projection
+void lp_host_side(const vsg_frame_pose *pose, const float *bounds /* minX, minY, maxX, maxY */, float viewing_cos_limit,
+                  int n, const int32_t *slots, const float *world_pos, const float *normal, const float *min_dist,
+                  const float *max_dist, const uint8_t *desc, const uint8_t *observed, uint8_t *in_view, float *proj_x,
+                  float *proj_y, float *proj_xr, int32_t *scale_level, float *view_cos, uint8_t *q_desc,
+                  uint8_t *q_observed) {
+  for (int i = 0; i < n; i++) {
+    const int s = slots[i];
+    const float *P = world_pos + 3 * s, *N = normal + 3 * s;
+    const vsg::FrustumOut o = vsg::frustum_point(*pose, bounds[0], bounds[2], bounds[1], bounds[3], viewing_cos_limit,
+                                                 P[0], P[1], P[2], N[0], N[1], N[2], min_dist[s], max_dist[s]);
+    in_view[i] = (uint8_t)o.in_view, proj_x[i] = o.proj_x, proj_y[i] = o.proj_y, proj_xr[i] = o.proj_xr;
+    scale_level[i] = o.scale_level, view_cos[i] = o.view_cos;
+    memcpy(q_desc + 32 * (size_t)i, desc + 32 * (size_t)s, 32);
+    q_observed[i] = observed[s];
+  }
+}
+
+// the projection loop of SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:1686-1715), compacted to the
+// projected points, for vsg_frame_search_by_projection_last
+int tl_host_side(const vsg_frame_pose *pose, const float *bounds, int n, const int32_t *slots,
+                 const vsg_keypoint *last_kps, const float *world_pos, const uint8_t *desc, const uint8_t *observed,
+                 int32_t *index, uint8_t *q_desc, uint8_t *q_observed, float *u, float *v, float *ur, int32_t *octave,
+                 float *angle) {
+  const vsg::ImageBounds b = {bounds[0], bounds[2], bounds[1], bounds[3]};
+  int m = 0;
+  for (int i = 0; i < n; i++) {
+    const int s = slots[i];
+    if (s < 0) continue;  // no map point, or an outlier
+    const vsg::ProjectOut o = vsg::project_last_point(*pose, b, world_pos + 3 * (size_t)s);
+    if (!o.valid) continue;
+    index[m] = i, u[m] = o.u, v[m] = o.v, ur[m] = o.ur;
+    octave[m] = last_kps[i].octave, angle[m] = last_kps[i].angle;
+    memcpy(q_desc + 32 * (size_t)m, desc + 32 * (size_t)s, 32);
+    q_observed[m] = observed[s];
+    m++;
+  }
+  return m;
+}
+
+// the per-point loop of Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:1194-1241), compacted likewise, for vsg_frame_fuse
+int kp_host_side(const vsg_frame_pose *pose, const float *bounds, int n, const uint8_t *skip, const float *world_pos,
+                 const float *normal, const float *min_dist, const float *max_dist, const uint8_t *desc, float th,
+                 const float *scale_factors, int32_t *index, uint8_t *q_desc, float *u, float *v, float *ur,
+                 float *radius, int32_t *level) {
+  const vsg::ImageBounds kf = vsg::keyframe_bounds({bounds[0], bounds[2], bounds[1], bounds[3]});
+  int m = 0;
+  for (int i = 0; i < n; i++) {
+    if (skip[i]) continue;  // isBad() or IsInKeyFrame(pKF)
+    const vsg::ProjectOut o = vsg::project_keyframe_point(*pose, kf, world_pos + 3 * (size_t)i, normal + 3 * (size_t)i,
+                                                          min_dist[i], max_dist[i]);
+    if (!o.valid) continue;
+    index[m] = i, u[m] = o.u, v[m] = o.v, ur[m] = o.ur, level[m] = o.level;
+    radius[m] = vsg::fmul(th, scale_factors[o.level]);
+    memcpy(q_desc + 32 * (size_t)m, desc + 32 * (size_t)i, 32);
+    m++;
+  }
+  return m;
+}
+
+}  // extern "C"

@@ -1,0 +1,367 @@
+#!/usr/bin/env python3
+"""Warm latency of the searches on device-resident map points, next to what a caller does without them.  Runs on the GPU
+box; every run is a fresh child process, the variants alternating call by call inside it.  Three cases, each a resident
+1000-feature frame (640x480, TUM1 intrinsics) whose features sit where a subset of the points projects, with slightly
+changed descriptors, so that the search matches a real share:
+
+  local     Tracking::SearchLocalPoints, local maps of 1000 / 2000 / 4000 points (tests/frustum_reference.py's scenario)
+            A = Frame::isInFrustum per point on the host + vsg_frame_search_by_projection
+            B = vsg_frame_search_local_points;  B5 = B with 5 % of the slots updated before each call: a keyframe's churn
+  last      SearchByProjection(CurrentFrame, LastFrame, th, bMono), last frames whose features carry 500 / 1000 / 2000
+            slots (a quarter more features carry none)
+            A = the projection loop of ORBmatcher.cc:1686-1715 on the host + vsg_frame_search_by_projection_last
+            B = vsg_frame_search_last_frame, last frame and store resident
+  keyframe  Fuse(pKF, vpMapPoints, th), 500 / 1000 / 2000 candidate points, a tenth flagged isBad() / IsInKeyFrame(pKF)
+            A = the per-point loop of ORBmatcher.cc:1194-1241 on the host + vsg_frame_fuse
+            B = vsg_frame_fuse_points (LocalMapping::SearchInNeighbors fuses one list into 20-30 neighbours, one pose each)
+
+A is the caller-side path: the host loop (tools/resident_points_cpu.cpp, the kernel's own arithmetic compiled -O2, one
+thread) + the gather of descriptors + the host-array entry point; A2 is A again, the run's own A-vs-A spread.  For B only
+the pose changes (a small rotation per call, the same for every variant).  Host clock around the blocking calls, straight
+through ctypes with preallocated arrays on both sides.  Every call asserts that A and B compute the same result.
+
+usage: resident_points_probe.py <local|last|keyframe> [calls] [out.json]  -> runs the child, writes the record (default
+                                  profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json)
+       resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
+       resident_points_probe.py local trace           -> a few B calls at 4000 points, for rocprofv3 --kernel-trace --stats"""
+import ctypes as C
+import json
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+
+_f32p, _u8p, _i32p = (C.POINTER(t) for t in (C.c_float, C.c_uint8, C.c_int32))
+NFEAT = 1000
+FIELDS = ("world_pos", "normal", "min_dist", "max_dist", "desc", "observed")
+
+
+def host_side(orb):
+    out = ROOT / "tools" / "_bin"
+    out.mkdir(exist_ok=True)
+    so = out / "libresident_points_cpu.so"
+    csrc = ROOT / "visual_sgraphs_amd" / "csrc"
+    src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h"]
+    if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
+                               str(src[0])])
+    H = C.CDLL(str(so))
+    pose = C.POINTER(orb.FramePose)
+    H.lp_host_side.restype = None
+    H.lp_host_side.argtypes = [pose, _f32p, C.c_float, C.c_int, _i32p, _f32p, _f32p, _f32p, _f32p, _u8p, _u8p, _u8p, _f32p,
+                               _f32p, _f32p, _i32p, _f32p, _u8p, _u8p]
+    H.tl_host_side.argtypes = [pose, _f32p, C.c_int, _i32p, C.c_void_p, _f32p, _u8p, _u8p, _i32p, _u8p, _u8p, _f32p, _f32p,
+                               _f32p, _i32p, _f32p]
+    H.kp_host_side.argtypes = [pose, _f32p, C.c_int, _u8p, _f32p, _f32p, _f32p, _f32p, _u8p, C.c_float, _f32p, _i32p, _u8p,
+                               _f32p, _f32p, _f32p, _f32p, _i32p]
+    return H
+
+
+def p(a, t):
+    return a.ctypes.data_as(t)
+
+
+def stats(us):
+    a = np.sort(np.asarray(us))
+    return {"median_us": round(float(np.median(a)), 1), "p10_us": round(float(a[int(0.1 * len(a))]), 1),
+            "p90_us": round(float(a[int(0.9 * len(a))]), 1)}
+
+
+class Case:
+    """What the three cases share.  A case provides SIZES, TH, DEST, its scene (__init__(orb, fr, n): self.pose and
+    self.bounds first), A(L, H, P) and B(L, P) -> the result to compare (computed inside the clock), and facts()."""
+    VARIANTS = ("A", "B", "A2")
+
+    def start(self, orb, fr, n):
+        self.orb, self.fr, self.n = orb, fr, n
+        self.sf = (np.float32(1.2) ** np.arange(8, dtype=np.float32)).astype(np.float32)
+        self.b = np.array(self.bounds, np.float32)
+        return np.random.default_rng(n)
+
+    def cloud(self, rng):
+        """n points in front of the camera, a tenth of them outside the image: (px, py) and self.pos"""
+        po, n = self.pose, self.n
+        R, t = po["Rcw"].astype(np.float64), po["tcw"].astype(np.float64)
+        px, py, z = rng.uniform(-40, 680, n), rng.uniform(-30, 510, n), rng.uniform(1, 8, n)
+        Pc = np.stack([(px - po["cx"]) / po["fx"] * z, (py - po["cy"]) / po["fy"] * z, z], 1)
+        self.pos = np.ascontiguousarray(((Pc - t) @ R).astype(np.float32))
+        return px, py
+
+    def frame(self, x, y, octave, desc, rng, angle=False):
+        """The resident frame: NFEAT features at (x, y) with two changed descriptor bytes each"""
+        keys = np.zeros(NFEAT, self.orb.KP_DTYPE)
+        keys["x"], keys["y"], keys["octave"] = x, y, octave
+        if angle:
+            keys["angle"] = rng.uniform(0, 360, NFEAT)
+        d = desc.copy()
+        d[:, :2] ^= rng.integers(0, 256, (NFEAT, 2), dtype=np.uint8)
+        self.F = self.orb.Frame(NFEAT + 1)
+        self.F.upload(keys, d, self.bounds)
+
+    def pose_at(self, k):
+        """The camera turned by a small angle about its y axis: the pose of call k."""
+        a = 0.002 * (k % 50)
+        Ry = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+        po = self.pose
+        R = (Ry @ po["Rcw"].astype(np.float64)).astype(np.float32)
+        t = (Ry @ po["tcw"].astype(np.float64)).astype(np.float32)
+        return self.orb.FramePose.make(**self.fr.make_pose(R, t, po["fx"], po["fy"], po["cx"], po["cy"], po["mbf"]))
+
+    def reset(self):
+        pass
+
+    def run(self, name, L, H, P):
+        return self.A(L, H, P) if name[0] == "A" else self.B(L, P)
+
+
+class Local(Case):
+    SIZES, TH, NNRATIO, DEST = (1000, 2000, 4000), 3.0, 0.8, "local_points_latency.json"
+    VARIANTS = ("A", "B", "A2", "B5")
+
+    def __init__(self, orb, fr, n):
+        self.pose, self.bounds, f = fr.scenario(3, "tum1", n=n)
+        rng = self.start(orb, fr, n)
+        self.f = {k: np.ascontiguousarray(v) for k, v in f.items()}
+        ref = fr.is_in_frustum(self.pose, self.bounds, f["world_pos"], f["normal"], f["min_dist"], f["max_dist"])
+        iv = np.flatnonzero(ref["in_view"])
+        src = iv[rng.integers(0, len(iv), NFEAT)]
+        x = ref["proj_x"][src] + rng.normal(0, 2.0, NFEAT).astype(np.float32)
+        y = ref["proj_y"][src] + rng.normal(0, 2.0, NFEAT).astype(np.float32)
+        self.frame(x, y, np.maximum(ref["scale_level"][src] - rng.integers(0, 2, NFEAT), 0), f["desc"][src], rng)
+        self.mp = orb.MapPoints(n)
+        self.slots = np.arange(n, dtype=np.int32)
+        self.mp.update(self.slots, **{k: self.f[k] for k in FIELDS})
+        z = np.zeros
+        self.in_view, self.px, self.py, self.pxr = z(n, np.uint8), z(n, np.float32), z(n, np.float32), z(n, np.float32)
+        self.lvl, self.vc, self.qd, self.qo = z(n, np.int32), z(n, np.float32), z((n, 32), np.uint8), z(n, np.uint8)
+        self.tb, self.tm, self.ntm = z(NFEAT, np.uint8), z(NFEAT, np.int32), C.c_int(0)
+        # the churn: 5 % of the slots rewritten with the values they hold
+        self.churn = rng.choice(n, max(n // 20, 1), replace=False).astype(np.int32)
+        self.u = [np.ascontiguousarray(self.f[k][self.churn]) for k in FIELDS[:5]]
+
+    def reset(self):
+        self.tb[:] = 0
+        self.tm[:] = -1
+
+    def A(self, L, H, P):
+        f = self.f
+        H.lp_host_side(C.byref(P), p(self.b, _f32p), 0.5, self.n, p(self.slots, _i32p), p(f["world_pos"], _f32p),
+                       p(f["normal"], _f32p), p(f["min_dist"], _f32p), p(f["max_dist"], _f32p), p(f["desc"], _u8p),
+                       p(f["observed"], _u8p), p(self.in_view, _u8p), p(self.px, _f32p), p(self.py, _f32p),
+                       p(self.pxr, _f32p), p(self.lvl, _i32p), p(self.vc, _f32p), p(self.qd, _u8p), p(self.qo, _u8p))
+        return L.vsg_frame_search_by_projection(
+            self.F.handle, self.n, p(self.qd, _u8p), p(self.qo, _u8p), p(self.in_view, _u8p), p(self.px, _f32p),
+            p(self.py, _f32p), p(self.pxr, _f32p), p(self.lvl, _i32p), p(self.vc, _f32p), None, None, None, None, None,
+            self.TH, self.NNRATIO, p(self.sf, _f32p), 8, None, None, p(self.tb, _u8p), p(self.tm, _i32p))
+
+    def B(self, L, P):
+        return L.vsg_frame_search_local_points(
+            self.F.handle, self.mp.handle, self.n, p(self.slots, _i32p), None, C.byref(P), 0.5, self.TH, self.NNRATIO, 0,
+            0.0, p(self.sf, _f32p), 8, p(self.tb, _u8p), p(self.tm, _i32p), p(self.in_view, _u8p), p(self.px, _f32p),
+            p(self.py, _f32p), C.byref(self.ntm))
+
+    def run(self, name, L, H, P):
+        if name == "B5":
+            u = self.u
+            assert L.vsg_mappoints_update(self.mp.handle, len(self.churn), p(self.churn, _i32p), p(u[0], _f32p),
+                                          p(u[1], _f32p), p(u[2], _f32p), p(u[3], _f32p), p(u[4], _u8p), None) == 0
+        return Case.run(self, name, L, H, P)
+
+    def result(self, name, r):
+        return r, self.tm.copy()
+
+    def facts(self, last):
+        return {"nmatches_last": int(last["B"][0]), "n_to_match_last": int(self.ntm.value)}
+
+
+class Last(Case):
+    SIZES, TH, DEST = (500, 1000, 2000), 7.0, "track_last_latency.json"
+
+    def __init__(self, orb, fr, n):
+        self.pose, self.bounds = fr.scenario(3, "tum1", n=1)[0], (0.0, 0.0, 640.0, 480.0)
+        rng = self.start(orb, fr, n)
+        px, py = self.cloud(rng)
+        self.desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        self.observed = (rng.random(n) < 0.8).astype(np.uint8)
+        src = rng.integers(0, n, NFEAT)
+        x, y = px[src] + rng.normal(0, 2, NFEAT), py[src] + rng.normal(0, 2, NFEAT)
+        oct_of = rng.integers(0, 8, n)
+        self.frame(x, y, oct_of[src], self.desc[src], rng, angle=True)
+        # the last frame: one feature per point plus a quarter without a map point, shuffled
+        nl = n + n // 4
+        self.slots = np.concatenate([np.arange(n), np.full(n // 4, -1)]).astype(np.int32)
+        rng.shuffle(self.slots)
+        self.lk = np.zeros(nl, orb.KP_DTYPE)
+        self.lk["x"], self.lk["y"] = rng.uniform(1, 639, nl), rng.uniform(1, 479, nl)
+        self.lk["octave"] = np.where(self.slots >= 0, oct_of[np.maximum(self.slots, 0)], rng.integers(0, 8, nl))
+        self.lk["angle"] = rng.uniform(0, 360, nl)
+        self.L = orb.Frame(nl + 1)
+        self.L.upload(self.lk, rng.integers(0, 256, (nl, 32), dtype=np.uint8), self.bounds)
+        self.mp = orb.MapPoints(n)
+        self.mp.update(np.arange(n), world_pos=self.pos, desc=self.desc, observed=self.observed)
+        self.mb = float(self.pose["mbf"] / self.pose["fx"])
+        z_ = np.zeros
+        self.index, self.qd, self.qo = z_(nl, np.int32), z_((nl, 32), np.uint8), z_(nl, np.uint8)
+        self.u, self.v, self.ur, self.oc, self.an = (z_(nl, np.float32), z_(nl, np.float32), z_(nl, np.float32),
+                                                     z_(nl, np.int32), z_(nl, np.float32))
+        self.tb, self.tm, self.dir = z_(NFEAT, np.uint8), z_(NFEAT, np.int32), C.c_int(0)
+        self.last_pose = orb.FramePose.make(**self.pose)
+        self.nproj = 0
+
+    def reset(self):
+        self.tb[:] = 0
+        self.tm[:] = -1
+
+    def A(self, L, H, P):
+        m = H.tl_host_side(C.byref(P), p(self.b, _f32p), len(self.slots), p(self.slots, _i32p), self.lk.ctypes.data_as(C.c_void_p),
+                           p(self.pos, _f32p), p(self.desc, _u8p), p(self.observed, _u8p), p(self.index, _i32p),
+                           p(self.qd, _u8p), p(self.qo, _u8p), p(self.u, _f32p), p(self.v, _f32p), p(self.ur, _f32p),
+                           p(self.oc, _i32p), p(self.an, _f32p))
+        self.nproj = m
+        return L.vsg_frame_search_by_projection_last(
+            self.F.handle, m, p(self.qd, _u8p), p(self.qo, _u8p), p(self.u, _f32p), p(self.v, _f32p), p(self.ur, _f32p), None,
+            None, p(self.oc, _i32p), p(self.an, _f32p), self.TH, 0, p(self.sf, _f32p), 8, 1, p(self.tb, _u8p), p(self.tm, _i32p))
+
+    def B(self, L, P):
+        return L.vsg_frame_search_last_frame(
+            self.F.handle, self.L.handle, self.mp.handle, p(self.slots, _i32p), C.byref(P), C.byref(self.last_pose), self.mb, 1,
+            self.TH, p(self.sf, _f32p), 8, 1, p(self.tb, _u8p), p(self.tm, _i32p), C.byref(self.dir), None, None, None, None)
+
+    def result(self, name, r):
+        tm = self.tm.copy()
+        if name[0] == "A":  # compacted indices -> last-frame features
+            tm[tm >= 0] = self.index[tm[tm >= 0]]
+        return r, tm
+
+    def facts(self, last):
+        return {"last_features": len(self.slots), "projected_last": int(self.nproj), "nmatches_last": int(last["B"][0])}
+
+
+class KeyFrame(Case):
+    SIZES, TH, DEST = (500, 1000, 2000), 3.0, "keyframe_points_latency.json"
+
+    def __init__(self, orb, fr, n):
+        self.pose, self.bounds = fr.scenario(3, "tum1", n=1)[0], (0.0, 0.0, 640.0, 480.0)
+        rng = self.start(orb, fr, n)
+        px, py = self.cloud(rng)
+        PO = self.pos.astype(np.float64) - self.pose["Ow"]  # normals along the viewing rays
+        dist = np.linalg.norm(PO, axis=1)
+        self.normal = np.ascontiguousarray((PO / dist[:, None]).astype(np.float32))
+        oct_of = rng.integers(0, 8, n)
+        self.max_dist = (dist * 1.2 ** (oct_of - 0.5)).astype(np.float32)  # the predicted level is the feature's octave
+        self.min_dist = (self.max_dist / np.float32(1.2) ** np.float32(7)).astype(np.float32)
+        self.desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        self.skip = (rng.random(n) < 0.1).astype(np.uint8)
+        src = rng.integers(0, n, NFEAT)
+        x, y = px[src] + rng.normal(0, 0.7, NFEAT), py[src] + rng.normal(0, 0.7, NFEAT)
+        self.frame(x, y, oct_of[src], self.desc[src], rng, angle=True)
+        self.slots = np.arange(n, dtype=np.int32)
+        self.mp = orb.MapPoints(n)
+        self.mp.update(self.slots, world_pos=self.pos, normal=self.normal, min_dist=self.min_dist, max_dist=self.max_dist,
+                       desc=self.desc)
+        self.inv2 = (np.float32(1) / (self.sf * self.sf)).astype(np.float32)
+        z_ = np.zeros
+        self.index, self.qd = z_(n, np.int32), z_((n, 32), np.uint8)
+        self.u, self.v, self.ur, self.rad, self.lvl = (z_(n, np.float32), z_(n, np.float32), z_(n, np.float32),
+                                                       z_(n, np.float32), z_(n, np.int32))
+        self.bi, self.bd = z_(n, np.int32), z_(n, np.int32)
+        self.nproj = 0
+
+    # (both sides hand back copies inside the clock: A's are the scatter of its compacted results back to the queries)
+    def A(self, L, H, P):
+        m = H.kp_host_side(C.byref(P), p(self.b, _f32p), self.n, p(self.skip, _u8p), p(self.pos, _f32p), p(self.normal, _f32p),
+                           p(self.min_dist, _f32p), p(self.max_dist, _f32p), p(self.desc, _u8p), self.TH, p(self.sf, _f32p),
+                           p(self.index, _i32p), p(self.qd, _u8p), p(self.u, _f32p), p(self.v, _f32p), p(self.ur, _f32p),
+                           p(self.rad, _f32p), p(self.lvl, _i32p))
+        self.nproj = m
+        r = L.vsg_frame_fuse(self.F.handle, m, p(self.qd, _u8p), p(self.u, _f32p), p(self.v, _f32p), p(self.ur, _f32p),
+                             p(self.rad, _f32p), p(self.lvl, _i32p), 0, p(self.inv2, _f32p), 8, p(self.bi, _i32p),
+                             p(self.bd, _i32p))
+        bi, bd = np.full(self.n, -1, np.int32), np.full(self.n, 256, np.int32)
+        bi[self.index[:m]], bd[self.index[:m]] = self.bi[:m], self.bd[:m]
+        return r, bi, bd
+
+    def B(self, L, P):
+        r = L.vsg_frame_fuse_points(self.F.handle, self.mp.handle, self.n, p(self.slots, _i32p), p(self.skip, _u8p), C.byref(P),
+                                    self.TH, p(self.sf, _f32p), p(self.inv2, _f32p), 8, p(self.bi, _i32p), p(self.bd, _i32p), None,
+                                    None, None, None, None)
+        return r, self.bi.copy(), self.bd.copy()
+
+    def result(self, name, got):
+        return got
+
+    def facts(self, last):
+        return {"projected_last": int(self.nproj), "fused_last": int(last["B"][0])}
+
+
+CASES = {"local": Local, "last": Last, "keyframe": KeyFrame}
+
+
+def child(case, calls):
+    import frustum_reference as fr
+    from visual_sgraphs_amd import orb
+    L, H, K = orb.load_library(), host_side(orb), CASES[case]
+    out = {"calls": calls, "features": NFEAT, "th": K.TH, "sizes": {}}
+    for n in K.SIZES:
+        c = K(orb, fr, n)
+        t = {k: [] for k in K.VARIANTS}
+        last = {}
+        for k in range(calls + 20):
+            P = c.pose_at(k)
+            for name in K.VARIANTS:
+                c.reset()
+                t0 = time.perf_counter()
+                r = c.run(name, L, H, P)
+                dt = (time.perf_counter() - t0) * 1e6
+                last[name] = c.result(name, r)
+                assert last[name][0] >= 0, (name, last[name][0])
+                if k >= 20:
+                    t[name].append(dt)
+            for name in K.VARIANTS[1:]:  # the variants compute the same thing
+                assert all(np.array_equal(a, b) for a, b in zip(last["A"], last[name])), name
+        res = {k: stats(v) for k, v in t.items()}
+        res.update(c.facts(last))
+        res["a_vs_a_median_gap_us"] = round(abs(res["A"]["median_us"] - res["A2"]["median_us"]), 1)
+        # the resident call is "not slower" when its 10-90 % range does not lie wholly above the caller-side path's
+        res["resident_not_slower"] = bool(res["B"]["p10_us"] <= max(res["A"]["p90_us"], res["A2"]["p90_us"]))
+        res["resident_faster"] = bool(res["B"]["p90_us"] < min(res["A"]["p10_us"], res["A2"]["p10_us"]))
+        out["sizes"][str(n)] = res
+    print(json.dumps(out))
+
+
+def trace():
+    import frustum_reference as fr
+    from visual_sgraphs_amd import orb
+    L, c = orb.load_library(), Local(orb, fr, 4000)
+    for k in range(10):
+        c.reset()
+        assert c.B(L, c.pose_at(k)) >= 0
+    print({"n": 4000, "nmatches": int((c.tm >= 0).sum()), "n_to_match": c.ntm.value})
+
+
+def main(argv):
+    if argv[0] == "child":
+        return child(argv[1], int(argv[2]) if len(argv) > 2 else 200)
+    if argv[1:] == ["trace"]:
+        return trace()
+    calls = int(argv[1]) if len(argv) > 1 else 200
+    dest = Path(argv[2]) if len(argv) > 2 else ROOT / "profiles" / CASES[argv[0]].DEST
+    r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "child", argv[0], str(calls)], capture_output=True,
+                       text=True, timeout=900)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        return r.returncode
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    dest.parent.mkdir(parents=True, exist_ok=True)
+    dest.write_text(json.dumps(rec, indent=1) + "\n")
+    print(json.dumps(rec))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

@@ -108,6 +108,18 @@ struct WindowCall {
   size_t bytes() const;
   walk::CandView lists() const;
   const int32_t *best() const { return (const int32_t *)(c->h_pin + base + oOut); }  // pairs {idx, dist}
+  // Fuse's copy-out of best mode: bestIdx / bestDist per query (no candidate: -1 / the scan's start value); returns
+  // how many are within TH_LOW (ORBmatcher.cc:1310 / :1428)
+  int best_out(int best_init, int32_t *best_idx, int32_t *best_dist) const {
+    const int32_t *b = best();
+    int nfused = 0;
+    for (int k = 0; k < nq; k++) {
+      best_idx[k] = b[2 * k];
+      best_dist[k] = b[2 * k] >= 0 ? b[2 * k + 1] : best_init;
+      if (b[2 * k] >= 0 && b[2 * k + 1] <= walk::TH_LOW) nfused++;
+    }
+    return nfused;
+  }
 };
 
 // Retry loop around a window-search entry point body: a body whose WindowCall::finish() returned VSG_RETRY runs again

@@ -1,6 +1,6 @@
 // vsg_frustum.h -- Frame::isInFrustum (Frame.cc:656-719, the Nleft == -1 branch) for ONE map point, host and device
 // from one source: k_frustum (vsg_mappoints.hip) runs it one lane per point, tests/_frustumcore and the latency probe's
-// caller-side loop compile it for the host.
+// caller-side loop (tools/resident_points_cpu.cpp) compile it for the host.
 //
 // The reference evaluates this in Eigen float under -O3 -march=native, so its bits follow the compiler's contraction;
 // here the order is fixed and nothing contracts: every operation is one vsg::f* call = one rounding.

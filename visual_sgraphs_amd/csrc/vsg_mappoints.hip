@@ -92,23 +92,38 @@ __global__ __launch_bounds__(256) void k_mappoints_gather(StoreDev S, FieldsOut 
   if (A.observed) A.observed[i] = S.observed[s];
 }
 
-struct FrustumArgs {
+// What both projection kernels are launched with: the pose, the image bounds and a search's th and scale table, then the
+// few scalars that one form reads.
+struct PointArgs {
   vsg_frame_pose cam;
-  float minX, maxX, minY, maxY, viewing_cos_limit;
+  ImageBounds bounds;  // the Frame's; the into-KeyFrame form: keyframe_bounds() of them
   int n;
-  // the search half (Q == nullptr: isInFrustum alone)
-  int b_factor, far_points;
-  float th, th_far_points;
+  float th;
   float scale_factors[16];
+  float viewing_cos_limit;   // k_frustum
+  int b_factor, far_points;  // k_frustum's search half (Q != nullptr)
+  float th_far_points;
+  int direction;  // last-frame form: 0 neither, 1 bForward, 2 bBackward
 };
 
-struct FrustumOutDev {
-  uint8_t *in_view;
-  float *proj_x, *proj_y, *proj_xr, *depth;  // proj_xr, depth, scale_level, view_cos: nullptr when not wanted
-  int32_t *scale_level;
-  float *view_cos;
-  uint8_t *observed;  // Observations() > 0 of point i, for the ordered host pass (nullptr when not wanted)
+// The per-point results of both kernels, one array per field; nullptr = the call does not want the field.
+struct PointOut {
+  uint8_t *valid;     // mbTrackInView / the point reaches GetFeaturesInArea
+  float *x, *y;       // mTrackProjX / Y, uv
+  float *xr, *depth;  // mTrackProjXR, uv(0) - mbf * invzc; mTrackDepth
+  int32_t *level;     // mnTrackScaleLevel / nPredictedLevel
+  float *view_cos;    // mTrackViewCos
+  uint8_t *observed;  // Observations() > 0 of point i, for the ordered host pass
 };
+// valid, x and y are part of every call; a call names the others it wants with these bits
+enum { kXr = 1, kDepth = 2, kLevel = 4, kViewCos = 8, kObserved = 16, kEveryCall = 32 };
+// f(member, its bit) for every field of PointOut, in the order of the blocks in the arena
+template <class Fn>
+void point_fields(Fn f) {
+  f(&PointOut::valid, kEveryCall), f(&PointOut::x, kEveryCall), f(&PointOut::y, kEveryCall), f(&PointOut::xr, kXr);
+  f(&PointOut::depth, kDepth), f(&PointOut::level, kLevel), f(&PointOut::view_cos, kViewCos);
+  f(&PointOut::observed, kObserved);
+}
 
 // Frame::isInFrustum, one lane per map point i = slot slots[i] (nullptr: slot i).  skip[i]: never projected (in_view 0,
 // proj -1).  With Q: the window of SearchByProjection(F, vpMapPoints) (ORBmatcher.cc:59-70) as a WinQuery and the
@@ -118,7 +133,7 @@ struct FrustumOutDev {
 // query has no candidates to compare it with.  Not a value to rely on, and not a read for a checker to flag.
 // 64 lanes per workgroup: 4000 points are 63 workgroups on 63 CUs, each running the fp64 logf once.
 __global__ __launch_bounds__(64) void k_frustum(StoreDev S, const int32_t *__restrict__ slots,
-                                                const uint8_t *__restrict__ skip, FrustumArgs A, FrustumOutDev O,
+                                                const uint8_t *__restrict__ skip, PointArgs A, PointOut O,
                                                 WinQuery *__restrict__ Q, uint8_t *__restrict__ qdesc) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= A.n) return;
@@ -126,14 +141,14 @@ __global__ __launch_bounds__(64) void k_frustum(StoreDev S, const int32_t *__res
   FrustumOut o = {0, -1.0f, -1.0f, 0.0f, 0.0f, 0, 0.0f};
   if (!(skip && skip[i])) {
     const float *P = S.pos + 3 * (size_t)s, *N = S.normal + 3 * (size_t)s;
-    o = frustum_point(A.cam, A.minX, A.maxX, A.minY, A.maxY, A.viewing_cos_limit, P[0], P[1], P[2], N[0], N[1], N[2],
-                      S.min_dist[s], S.max_dist[s]);
+    o = frustum_point(A.cam, A.bounds.minX, A.bounds.maxX, A.bounds.minY, A.bounds.maxY, A.viewing_cos_limit, P[0], P[1],
+                      P[2], N[0], N[1], N[2], S.min_dist[s], S.max_dist[s]);
   }
-  O.in_view[i] = (uint8_t)o.in_view;
-  O.proj_x[i] = o.proj_x, O.proj_y[i] = o.proj_y;
-  if (O.proj_xr) O.proj_xr[i] = o.proj_xr;
+  O.valid[i] = (uint8_t)o.in_view;
+  O.x[i] = o.proj_x, O.y[i] = o.proj_y;
+  if (O.xr) O.xr[i] = o.proj_xr;
   if (O.depth) O.depth[i] = o.depth;
-  if (O.scale_level) O.scale_level[i] = o.scale_level;
+  if (O.level) O.level[i] = o.scale_level;
   if (O.view_cos) O.view_cos[i] = o.view_cos;
   if (O.observed) O.observed[i] = S.observed[s];
   if (Q) {
@@ -147,23 +162,6 @@ __global__ __launch_bounds__(64) void k_frustum(StoreDev S, const int32_t *__res
   }
 }
 
-struct ProjectArgs {
-  vsg_frame_pose cam;
-  ImageBounds bounds;
-  int n;
-  float th;
-  int direction;  // last-frame form: 0 neither, 1 bForward, 2 bBackward
-  float scale_factors[16];
-};
-
-struct ProjectOutDev {
-  uint8_t *valid;     // the point reaches GetFeaturesInArea
-  float *u, *v;
-  float *ur;          // last-frame form, into-KeyFrame form
-  int32_t *level;     // relocalisation form, into-KeyFrame form
-  uint8_t *observed;  // last-frame form: Observations() > 0 of query i's point, for the ordered host pass
-};
-
 // The projection loops of SearchByProjection(CurrentFrame, LastFrame) (kLast, ORBmatcher.cc:1686-1724) and of
 // SearchByProjection(CurrentFrame, pKF, sAlreadyFound) (ORBmatcher.cc:1895-1930), one lane per query, 64 lanes per
 // workgroup like k_frustum.  kProjLast: query i = feature i of the resident last frame, slots[i] < 0 = no map point or an
@@ -171,12 +169,13 @@ struct ProjectOutDev {
 // in sAlreadyFound.  kProjKeyFrame: the loop of Fuse x2 and SearchByProjection(pKF, Scw, ...) (ORBmatcher.cc:1194-1241,
 // :1360-1395, :452-486), query i = slot slots[i], skip[i] = isBad(), IsInKeyFrame(pKF) or in spAlreadyFound; A.bounds
 // are the KeyFrame's truncated ones.  A query that is not searched gets the inactive flag and no descriptor (see k_frustum).
+// Of O it can fill valid, x, y, xr (last-frame and into-KeyFrame form), level (the two KeyFrame forms) and observed.
 enum { kProjLast = 0, kProjReloc = 1, kProjKeyFrame = 2 };
 template <int kForm>
 __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t *__restrict__ slots,
                                                        const uint8_t *__restrict__ skip,
-                                                       const KeyPointPOD *__restrict__ last_kps, ProjectArgs A,
-                                                       ProjectOutDev O, WinQuery *__restrict__ Q,
+                                                       const KeyPointPOD *__restrict__ last_kps, PointArgs A,
+                                                       PointOut O, WinQuery *__restrict__ Q,
                                                        uint8_t *__restrict__ qdesc) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= A.n) return;
@@ -203,8 +202,8 @@ __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t
     if (o.valid) copy_desc(qdesc + 32 * (size_t)i, S.desc + 32 * (size_t)s);
   }
   O.valid[i] = (uint8_t)o.valid;
-  O.u[i] = o.u, O.v[i] = o.v;
-  if (O.ur) O.ur[i] = o.ur;
+  O.x[i] = o.u, O.y[i] = o.v;
+  if (O.xr) O.xr[i] = o.ur;
   if (O.level) O.level[i] = o.level;
   if (O.observed) O.observed[i] = observed;
   Q[i] = w;
@@ -221,20 +220,31 @@ bool slots_in_store(const vsg_mappoints *mp, int n, const int32_t *slots) {
   return true;
 }
 
-int pose_check(const vsg_frame *F, const vsg_mappoints *mp, const vsg_frame_pose *pose) {
+// What the seven entry points on resident points check first, in this order (the codes differ): the handles and the
+// pose are there; no second camera; one device, a pyramid, n, the entry's own required arrays (entry_ok); and for a
+// search (levels) its scale table against the pose.  An entry adds its slot list's test and what only it knows.
+int resident_check(const vsg_frame *F, const vsg_mappoints *mp, const vsg_frame_pose *pose, int n, bool entry_ok,
+                   bool levels, const float *scale_factors, int nlevels) {
   if (!F || !F->d_block || store_check(mp) != VSG_OK || !pose) return VSG_ERR_INVALID;
-  if (F->nleft != -1) return VSG_ERR_UNSUPPORTED;  // isInFrustumChecks with KannalaBrandt8 (Frame.cc:721-800)
-  if (F->device != mp->device || pose->n_levels < 1) return VSG_ERR_INVALID;
+  // isInFrustumChecks with KannalaBrandt8 (Frame.cc:721-800), bRight / mpCamera2 (ORBmatcher.cc:1154-1159)
+  if (F->nleft != -1) return VSG_ERR_UNSUPPORTED;
+  if (F->device != mp->device || pose->n_levels < 1 || n < 0 || !entry_ok) return VSG_ERR_INVALID;
+  if (levels && (!scale_factors || nlevels < 1 || nlevels > 16 || pose->n_levels > nlevels)) return VSG_ERR_INVALID;
   return VSG_OK;
 }
 
-FrustumArgs frustum_args(const vsg_frame *F, const vsg_frame_pose *pose, float viewing_cos_limit, int n) {
-  FrustumArgs A;
+// The kernels' arguments for F's camera at `pose`; a search adds its th and scale table.  kKeyFrameBounds: the bounds are
+// KeyFrame::mnMinX .. mnMaxY, the Frame's truncated to int.  The scalars of one form are the caller's to set by name.
+enum BoundsForm { kFrameBounds, kKeyFrameBounds };
+PointArgs point_args(const vsg_frame *F, const vsg_frame_pose *pose, int n, BoundsForm form = kFrameBounds, float th = 0.0f,
+                     const float *scale_factors = nullptr, int nlevels = 0) {
+  PointArgs A;
   memset(&A, 0, sizeof(A));
   A.cam = *pose;
-  A.minX = F->minX, A.maxX = F->maxX, A.minY = F->minY, A.maxY = F->maxY;
-  A.viewing_cos_limit = viewing_cos_limit;
-  A.n = n;
+  A.bounds = {F->minX, F->maxX, F->minY, F->maxY};
+  if (form == kKeyFrameBounds) A.bounds = keyframe_bounds(A.bounds);
+  A.n = n, A.th = th;
+  for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
   return A;
 }
 
@@ -265,21 +275,64 @@ int copy_end(ThreadCtx *c) {
   return e1 == hipSuccess && e2 == hipSuccess ? VSG_OK : VSG_ERR_HIP;
 }
 
-// What the six searches on resident map points share: a projection kernel that writes every point's WinQuery and
-// gathers its descriptor, k_window_search right behind it on the same stream, one wait.  The call's own blocks
-// [slots? | skip? | valid | observed? | x | y | aux? | aux2?] sit behind the window call's in the pinned arena,
-// [WinQuery | descriptors] in the device arena.
-struct ResidentDev {  // what the projection kernel is launched with: the device side of those blocks and the stream
+// The pinned-arena blocks of one call on resident points, [slots? | skip? | the fields of PointOut the call wants]:
+// lay_out() says how many bytes to reserve, bind() (after the reserve: it may move the arena) copies the caller's slots
+// and skip flags in and takes both sides' pointers, copy_out() hands the caller the fields it gave an array for.
+struct PointStage {
+  size_t N = 0, oSlots = 0, oSkip = 0, off[8] = {}, total = 0;
+  unsigned want = 0;
+  const int32_t *src_slots = nullptr, *slots = nullptr;  // the caller's, and where the kernel reads them (nullptr: slot i)
+  const uint8_t *src_skip = nullptr, *skip = nullptr;
+  PointOut host = {}, dev = {};
+
+  void lay_out(int n, const int32_t *slots_, const uint8_t *skip_, unsigned want_) {
+    N = (size_t)n, src_slots = slots_, src_skip = skip_, want = want_ | kEveryCall;
+    Stage st;
+    oSlots = st.add(src_slots ? N * 4 : 0), oSkip = st.add(src_skip ? N : 0);
+    int k = 0;
+    point_fields([&](auto m, unsigned bit) { off[k++] = st.add(want & bit ? N * sizeof(*(host.*m)) : 0); });
+    total = st.total;
+  }
+  template <class T>
+  static void at(T *&p, uint8_t *block) { p = (T *)block; }
+  void bind(uint8_t *hp, uint8_t *dp) {
+    if (src_slots) memcpy(hp + oSlots, src_slots, N * 4), slots = (const int32_t *)(dp + oSlots);
+    if (src_skip) memcpy(hp + oSkip, src_skip, N), skip = dp + oSkip;
+    int k = 0;
+    point_fields([&](auto m, unsigned bit) {
+      if (want & bit) at(host.*m, hp + off[k]), at(dev.*m, dp + off[k]);
+      k++;
+    });
+  }
+  // dst names the caller's arrays (nullptr: not asked for); only a field the call wanted may be asked for
+  void copy_out(const PointOut &dst) const {
+    point_fields([&](auto m, unsigned) {
+      if (dst.*m) memcpy(dst.*m, host.*m, N * sizeof(*(dst.*m)));
+    });
+  }
+};
+
+// What a projection kernel is launched with besides its arguments: the device side of a PointStage, where the search's
+// queries and descriptors go (nullptr: isInFrustum alone), and the stream.
+struct ResidentDev {
   const int32_t *slots;
   const uint8_t *skip;
-  uint8_t *valid, *observed;
-  float *x, *y;
-  void *aux;   // one more 4-byte value per point: ur (last-frame form, into-KeyFrame form) / level (relocalisation form)
-  void *aux2;  // and another: level (into-KeyFrame form)
+  PointOut out;
   WinQuery *Q;
   uint8_t *qdesc;
   hipStream_t stream;
 };
+void launch_frustum(const ResidentDev &R, const vsg_mappoints *mp, const PointArgs &A) {
+  hipLaunchKernelGGL(k_frustum, dim3((A.n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots, R.skip, A, R.out, R.Q,
+                     R.qdesc);
+}
+template <int kForm>
+void launch_project(const ResidentDev &R, const vsg_mappoints *mp, const vsg_frame *last, const PointArgs &A) {
+  const bool kLast = kForm == kProjLast;
+  hipLaunchKernelGGL(k_project_points<kForm>, dim3((A.n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
+                     R.skip, kLast ? (const KeyPointPOD *)last->d_kps : (const KeyPointPOD *)nullptr, A, R.out, R.Q, R.qdesc);
+}
+
 // How the window kernel behind the projection runs: candidate lists for an ordered host pass, or the best candidate per
 // query (Fuse) with its scan's start value and, for the chi-square gate, pKF->mvInvLevelSigma2.
 struct ResidentMode {
@@ -288,34 +341,30 @@ struct ResidentMode {
   int nlevels;
 };
 ResidentMode resident_lists(int gate_mode) { return {kWinList, gate_mode, 256, nullptr, 0}; }
+
+// What the six searches on resident map points share: a projection kernel that writes every point's WinQuery and
+// gathers its descriptor, k_window_search right behind it on the same stream, one wait.  The call's PointStage sits
+// behind the window call's blocks in the pinned arena, [WinQuery | descriptors] in the device arena.
 struct ResidentCall {
   WindowCall wc;
-  size_t oS = 0, oK = 0, oV = 0, oO = 0, oX = 0, oY = 0, oA = 0, oA2 = 0;
-  uint8_t *hp = nullptr;  // the call's blocks, host side
+  PointStage st;
 
-  // launch(ResidentDev) enqueues the projection kernel.  VSG_RETRY: the lists overflowed, the whole call runs again
+  // want: the optional fields of PointOut the projection kernel is to write; launch(ResidentDev) enqueues it.
+  // VSG_RETRY: the lists overflowed, the whole call runs again
   template <class Launch>
-  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, bool observed, bool aux, bool aux2,
-          const ResidentMode &M, Launch launch) {
-    const size_t N = (size_t)n;
-    Stage st, sd;
-    oS = st.add(slots ? N * 4 : 0), oK = st.add(skip ? N : 0), oV = st.add(N), oO = st.add(observed ? N : 0);
-    oX = st.add(N * 4), oY = st.add(N * 4), oA = st.add(aux ? N * 4 : 0), oA2 = st.add(aux2 ? N * 4 : 0);
-    const size_t dQ = sd.add(N * sizeof(WinQuery)), dD = sd.add(N * 32);
+  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, unsigned want, const ResidentMode &M,
+          Launch launch) {
+    st.lay_out(n, slots, skip, want);
+    Stage sd;
+    const size_t dQ = sd.add(st.N * sizeof(WinQuery)), dD = sd.add(st.N * 32);
     int rc = wc.begin(F->device, n, M.mode, false, 0, st.total);
     if (rc != VSG_OK) return rc;
     ThreadCtx *c = wc.c;
     rc = ctx_reserve(c, 0, sd.total);
     if (rc != VSG_OK) return rc;
     // both reserves first, pointers after: either reserve may move its arena
-    hp = c->h_pin + wc.bytes();
-    uint8_t *dp = c->d_pin + wc.bytes();
-    if (slots) memcpy(hp + oS, slots, N * 4);
-    if (skip) memcpy(hp + oK, skip, N);
-    const ResidentDev R = {slots ? (const int32_t *)(dp + oS) : nullptr, skip ? dp + oK : nullptr, dp + oV,
-                           observed ? dp + oO : nullptr, (float *)(dp + oX), (float *)(dp + oY),
-                           aux ? dp + oA : nullptr, aux2 ? dp + oA2 : nullptr, (WinQuery *)(c->d_buf + dQ),
-                           c->d_buf + dD, c->stream};
+    st.bind(c->h_pin + wc.bytes(), c->d_pin + wc.bytes());
+    const ResidentDev R = {st.slots, st.skip, st.dev, (WinQuery *)(c->d_buf + dQ), c->d_buf + dD, c->stream};
     launch(R);
     rc = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
     if (rc == VSG_OK) rc = wc.launch(F, M.gate_mode, M.best_init, M.inv_sigma2, M.nlevels, R.qdesc, R.Q);
@@ -325,89 +374,38 @@ struct ResidentCall {
     }
     return wc.finish();
   }
-  // copy-out of the per-point results the caller asked for
-  void outs(int n, uint8_t *valid, float *x, float *y, void *aux, void *aux2 = nullptr) const {
-    const size_t N = (size_t)n;
-    if (valid) memcpy(valid, hp + oV, N);
-    if (x) memcpy(x, hp + oX, N * 4);
-    if (y) memcpy(y, hp + oY, N * 4);
-    if (aux) memcpy(aux, hp + oA, N * 4);
-    if (aux2) memcpy(aux2, hp + oA2, N * 4);
-  }
 };
 
-template <int kForm>
-void launch_project(const ResidentDev &R, const vsg_mappoints *mp, const vsg_frame *last, const ProjectArgs &A) {
-  const bool kLast = kForm == kProjLast;
-  const ProjectOutDev O = {R.valid, R.x, R.y, kForm != kProjReloc ? (float *)R.aux : nullptr,
-                           (int32_t *)(kForm == kProjReloc ? R.aux : kForm == kProjKeyFrame ? R.aux2 : nullptr), R.observed};
-  hipLaunchKernelGGL(k_project_points<kForm>, dim3((A.n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
-                     R.skip, kLast ? (const KeyPointPOD *)last->d_kps : (const KeyPointPOD *)nullptr, A, O, R.Q, R.qdesc);
+// The caller's arrays of the three routines that project into one KeyFrame, by name (ur: Fuse's pose form alone)
+PointOut keyframe_outs(uint8_t *projected, float *u, float *v, float *ur, int32_t *predicted_level) {
+  PointOut dst = {};
+  dst.valid = projected, dst.x = u, dst.y = v, dst.xr = ur, dst.level = predicted_level;
+  return dst;
 }
 
-// the checks the two projection searches share, in the order of pose_check
-int project_check(const vsg_frame *cur, const vsg_mappoints *mp, const vsg_frame_pose *pose, const float *scale_factors,
-                  int nlevels, const uint8_t *blocked, const int32_t *train_match) {
-  const int rc = pose_check(cur, mp, pose);
-  if (rc != VSG_OK) return rc;
-  if (!scale_factors || !blocked || !train_match || nlevels < 1 || nlevels > 16 || pose->n_levels > nlevels)
-    return VSG_ERR_INVALID;
-  return VSG_OK;
-}
-
-ProjectArgs project_args(const vsg_frame *cur, const vsg_frame_pose *pose, int n, float th, const float *scale_factors,
-                         int nlevels) {
-  ProjectArgs A;
-  memset(&A, 0, sizeof(A));
-  A.cam = *pose;
-  A.bounds = {cur->minX, cur->maxX, cur->minY, cur->maxY};
-  A.n = n, A.th = th;
-  for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
-  return A;
-}
-
-// What the three routines that project into one KeyFrame check, in the order of project_check, BEFORE anything is
-// enqueued; outs_ok: the entry's own required arrays are there.  VSG_OK with *go == false: n == 0, the entry returns 0.
+// What those three check BEFORE anything is enqueued, resident_check first.  VSG_OK with *go == false: n == 0, the entry
+// returns 0.
 int keyframe_check(const vsg_frame *kf, const vsg_mappoints *mp, int n, const int32_t *slots, const vsg_frame_pose *pose,
-                   const float *scale_factors, int nlevels, bool outs_ok, bool *go) {
+                   const float *scale_factors, int nlevels, bool entry_ok, bool *go) {
   *go = false;
-  const int rc = pose_check(kf, mp, pose);  // Nleft != -1: bRight / mpCamera2 (ORBmatcher.cc:1154-1159)
-  if (rc != VSG_OK) return rc;
-  if (!scale_factors || !outs_ok || nlevels < 1 || nlevels > 16 || pose->n_levels > nlevels || n < 0)
-    return VSG_ERR_INVALID;
-  if (n == 0) return VSG_OK;
+  const int rc = resident_check(kf, mp, pose, n, entry_ok, true, scale_factors, nlevels);
+  if (rc != VSG_OK || n == 0) return rc;
   if (!slots || !slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
   *go = true;
   return VSG_OK;
 }
 
-// ... and their projection arguments: the bounds are KeyFrame::mnMinX .. mnMaxY, the Frame's truncated to int
-ProjectArgs keyframe_args(const vsg_frame *kf, const vsg_frame_pose *pose, int n, float th, const float *scale_factors,
-                          int nlevels) {
-  ProjectArgs A = project_args(kf, pose, n, th, scale_factors, nlevels);
-  A.bounds = keyframe_bounds(A.bounds);
-  return A;
-}
-
 // Fuse's search on resident points: the projection kernel, then k_window_search in best mode; one wait
 int fuse_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
                 const vsg_frame_pose *pose, float th, const float *scale_factors, int nlevels, const ResidentMode &M,
-                int32_t *best_idx, int32_t *best_dist, uint8_t *projected, float *u, float *v, float *ur,
-                int32_t *predicted_level) {
-  const ProjectArgs A = keyframe_args(kf, pose, n, th, scale_factors, nlevels);
+                int32_t *best_idx, int32_t *best_dist, const PointOut &dst) {
+  const PointArgs A = point_args(kf, pose, n, kKeyFrameBounds, th, scale_factors, nlevels);
   ResidentCall call;
-  const int rc = call.run(kf, n, slots, skip, false, true, true, M,
+  const int rc = call.run(kf, n, slots, skip, kXr | kLevel, M,
                           [&](const ResidentDev &R) { launch_project<kProjKeyFrame>(R, mp, nullptr, A); });
   if (rc != VSG_OK) return rc;
-  call.outs(n, projected, u, v, ur, predicted_level);
-  const int32_t *b = call.wc.best();
-  int nfused = 0;
-  for (int k = 0; k < n; k++) {
-    best_idx[k] = b[2 * k];
-    best_dist[k] = b[2 * k] >= 0 ? b[2 * k + 1] : M.best_init;
-    if (b[2 * k] >= 0 && b[2 * k + 1] <= walk::TH_LOW) nfused++;  // :1310 / :1428
-  }
-  return nfused;
+  call.st.copy_out(dst);
+  return call.wc.best_out(M.best_init, best_idx, best_dist);
 }
 
 }  // namespace
@@ -527,41 +525,25 @@ int vsg_mappoints_read(vsg_mappoints *mp, int n, const int32_t *slots, float *wo
 int vsg_frame_is_in_frustum(vsg_frame *F, vsg_mappoints *mp, int n, const int32_t *slots, const vsg_frame_pose *pose,
                             float viewing_cos_limit, uint8_t *in_view, float *proj_x, float *proj_y, float *proj_xr,
                             float *depth, int32_t *scale_level, float *view_cos) {
-  int rc = pose_check(F, mp, pose);
-  if (rc != VSG_OK) return rc;
-  if (n < 0) return VSG_ERR_INVALID;
-  if (n == 0) return VSG_OK;
+  int rc = resident_check(F, mp, pose, n, true, false, nullptr, 0);
+  if (rc != VSG_OK || n == 0) return rc;
   ThreadCtx *c = thread_ctx(F->device, &rc);
   if (!c) return rc;
-  const size_t N = (size_t)n;
-  Stage st;
-  const size_t oS = st.add(slots ? N * 4 : 0), oV = st.add(N), oX = st.add(N * 4), oY = st.add(N * 4),
-               oXR = st.add(N * 4), oDp = st.add(N * 4), oL = st.add(N * 4), oC = st.add(N * 4);
+  PointStage st;
+  st.lay_out(n, slots, nullptr, kXr | kDepth | kLevel | kViewCos);
   rc = ctx_reserve(c, st.total, 0);
   if (rc != VSG_OK) return rc;
-  uint8_t *hp = c->h_pin, *dp = c->d_pin;
   if (!slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
-  if (slots) memcpy(hp + oS, slots, N * 4);
-  const FrustumOutDev O = {dp + oV,
-                           (float *)(dp + oX),
-                           (float *)(dp + oY),
-                           (float *)(dp + oXR),
-                           (float *)(dp + oDp),
-                           (int32_t *)(dp + oL),
-                           (float *)(dp + oC),
-                           nullptr};
-  hipLaunchKernelGGL(k_frustum, dim3((n + 63) / 64), dim3(64), 0, c->stream, store_dev(mp),
-                     slots ? (const int32_t *)(dp + oS) : (const int32_t *)nullptr, (const uint8_t *)nullptr,
-                     frustum_args(F, pose, viewing_cos_limit, n), O, (WinQuery *)nullptr, (uint8_t *)nullptr);
+  st.bind(c->h_pin, c->d_pin);
+  PointArgs A = point_args(F, pose, n);
+  A.viewing_cos_limit = viewing_cos_limit;
+  launch_frustum({st.slots, st.skip, st.dev, nullptr, nullptr, c->stream}, mp, A);
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
   if (e1 != hipSuccess || e2 != hipSuccess) return VSG_ERR_HIP;
-  if (in_view) memcpy(in_view, hp + oV, N);
-  if (proj_x) memcpy(proj_x, hp + oX, N * 4);
-  if (proj_y) memcpy(proj_y, hp + oY, N * 4);
-  if (proj_xr) memcpy(proj_xr, hp + oXR, N * 4);
-  if (depth) memcpy(depth, hp + oDp, N * 4);
-  if (scale_level) memcpy(scale_level, hp + oL, N * 4);
-  if (view_cos) memcpy(view_cos, hp + oC, N * 4);
+  PointOut dst = {};
+  dst.valid = in_view, dst.x = proj_x, dst.y = proj_y, dst.xr = proj_xr, dst.depth = depth;
+  dst.level = scale_level, dst.view_cos = view_cos;
+  st.copy_out(dst);
   return VSG_OK;
 }
 
@@ -570,35 +552,30 @@ int vsg_frame_search_local_points(vsg_frame *F, vsg_mappoints *mp, int n, const 
                                   int far_points, float th_far_points, const float *scale_factors, int nlevels,
                                   uint8_t *train_blocked, int32_t *train_match, uint8_t *in_view, float *proj_x,
                                   float *proj_y, int *n_to_match) {
-  int rc = pose_check(F, mp, pose);
+  int rc = resident_check(F, mp, pose, n, train_blocked && train_match, true, scale_factors, nlevels);
   if (rc != VSG_OK) return rc;
-  if (n < 0 || !train_blocked || !train_match || !scale_factors || nlevels < 1 || nlevels > 16 ||
-      pose->n_levels > nlevels)
-    return VSG_ERR_INVALID;
   if (n_to_match) *n_to_match = 0;
   if (n == 0) return 0;
   if (!slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
-  FrustumArgs A = frustum_args(F, pose, viewing_cos_limit, n);
+  PointArgs A = point_args(F, pose, n, kFrameBounds, th, scale_factors, nlevels);
+  A.viewing_cos_limit = viewing_cos_limit;
   A.b_factor = th != 1.0;  // ORBmatcher.cc:46
-  A.th = th, A.far_points = far_points ? 1 : 0, A.th_far_points = th_far_points;
-  for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
+  A.far_points = far_points ? 1 : 0, A.th_far_points = th_far_points;
+  PointOut dst = {};
+  dst.valid = in_view, dst.x = proj_x, dst.y = proj_y;
   return with_retry([&]() -> int {
     ResidentCall call;
     // the stereo gate of :97-102 applies to frames with mvuRight (Nleft == -1 here)
-    rc = call.run(F, n, slots, skip, true, false, false, resident_lists(F->has_uright ? kGateUr : kGateNone),
-                  [&](const ResidentDev &R) {
-                    const FrustumOutDev O = {R.valid, R.x, R.y, nullptr, nullptr, nullptr, nullptr, R.observed};
-                    hipLaunchKernelGGL(k_frustum, dim3((n + 63) / 64), dim3(64), 0, R.stream, store_dev(mp), R.slots,
-                                       R.skip, A, O, R.Q, R.qdesc);
-                  });
+    rc = call.run(F, n, slots, skip, kObserved, resident_lists(F->has_uright ? kGateUr : kGateNone),
+                  [&](const ResidentDev &R) { launch_frustum(R, mp, A); });
     if (rc != VSG_OK) return rc;
-    const uint8_t *hv = call.hp + call.oV;
+    const PointOut &h = call.st.host;
     int to_match = 0;
-    for (int i = 0; i < n; i++) to_match += hv[i];
+    for (int i = 0; i < n; i++) to_match += h.valid[i];
     if (n_to_match) *n_to_match = to_match;
-    call.outs(n, in_view, proj_x, proj_y, nullptr);
+    call.st.copy_out(dst);
     // a point that is in view but too far has an empty list: the pass does nothing for it, as :53-54
-    return walk::search_local(call.wc.lists(), n, -1, hv, nullptr, nullptr, call.hp + call.oO, nnratio, nullptr, nullptr,
+    return walk::search_local(call.wc.lists(), n, -1, h.valid, nullptr, nullptr, h.observed, nnratio, nullptr, nullptr,
                               train_blocked, train_match);
   });
 }
@@ -609,12 +586,12 @@ int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *
                                 uint8_t *train_blocked, int32_t *train_match, int *direction, uint8_t *projected, float *u,
                                 float *v, float *ur) {
   if (!last || !last->d_block || !last_pose || !last_slots) return VSG_ERR_INVALID;
-  int rc = project_check(cur, mp, cur_pose, scale_factors, nlevels, train_blocked, train_match);
+  const int n = last->n;
+  int rc = resident_check(cur, mp, cur_pose, n, train_blocked && train_match, true, scale_factors, nlevels);
   if (rc != VSG_OK) return rc;
   if (last->nleft != -1) return VSG_ERR_UNSUPPORTED;  // the right-camera block (ORBmatcher.cc:1785-1853)
   if (last->device != cur->device) return VSG_ERR_INVALID;
   const int dir = motion_direction(*cur_pose, *last_pose, mb, mono ? 1 : 0);  // :1677-1684
-  const int n = last->n;
   const vsg_keypoint *lk = last->h_kps.data();
   for (int i = 0; i < n; i++) {  // before the first enqueue
     if (last_slots[i] >= mp->capacity) return VSG_ERR_INVALID;
@@ -622,8 +599,10 @@ int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *
   }
   if (direction) *direction = dir;  // after the checks: an invalid call writes nothing
   if (n == 0) return 0;
-  ProjectArgs A = project_args(cur, cur_pose, n, th, scale_factors, nlevels);
+  PointArgs A = point_args(cur, cur_pose, n, kFrameBounds, th, scale_factors, nlevels);
   A.direction = dir;
+  PointOut dst = {};
+  dst.valid = projected, dst.x = u, dst.y = v, dst.xr = ur;
   std::vector<float> last_angle;  // kpLF.angle (:1768)
   if (check_orientation) {
     last_angle.resize((size_t)n);
@@ -632,14 +611,14 @@ int vsg_frame_search_last_frame(vsg_frame *cur, vsg_frame *last, vsg_mappoints *
   return with_retry([&]() -> int {
     ResidentCall call;
     // the stereo gate of :1742-1748 applies to frames with mvuRight (Nleft == -1 here)
-    rc = call.run(cur, n, last_slots, nullptr, true, true, false, resident_lists(cur->has_uright ? kGateUr : kGateNone),
+    rc = call.run(cur, n, last_slots, nullptr, kXr | kObserved, resident_lists(cur->has_uright ? kGateUr : kGateNone),
                   [&](const ResidentDev &R) { launch_project<kProjLast>(R, mp, last, A); });
     if (rc != VSG_OK) return rc;
-    call.outs(n, projected, u, v, ur);
+    call.st.copy_out(dst);
     const vsg_keypoint *hk = cur->h_kps.data();
     // a feature without a map point, an outlier and a point that does not project have empty lists: the pass does nothing
     // for them, as the `continue`s of :1689-1709
-    return walk::search_last(call.wc.lists(), n, -1, last_angle.data(), call.hp + call.oO,
+    return walk::search_last(call.wc.lists(), n, -1, last_angle.data(), call.st.host.observed,
                              [&](int i) { return hk[i].angle; }, walk::TH_HIGH, check_orientation != 0, train_blocked,
                              train_match);
   });
@@ -650,18 +629,18 @@ int vsg_frame_search_keyframe_points(vsg_frame *cur, vsg_mappoints *mp, int n, c
                                      int nlevels, int check_orientation, const float *kf_angle, uint8_t *occupied,
                                      int32_t *train_match, uint8_t *projected, float *u, float *v,
                                      int32_t *predicted_level) {
-  int rc = project_check(cur, mp, pose, scale_factors, nlevels, occupied, train_match);
-  if (rc != VSG_OK) return rc;
-  if (n < 0 || (check_orientation && n > 0 && !kf_angle)) return VSG_ERR_INVALID;
-  if (n == 0) return 0;
+  int rc = resident_check(cur, mp, pose, n, occupied && train_match && !(check_orientation && n > 0 && !kf_angle), true,
+                          scale_factors, nlevels);
+  if (rc != VSG_OK || n == 0) return rc;
   if (!slots || !slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
-  const ProjectArgs A = project_args(cur, pose, n, th, scale_factors, nlevels);
+  const PointArgs A = point_args(cur, pose, n, kFrameBounds, th, scale_factors, nlevels);
+  const PointOut dst = keyframe_outs(projected, u, v, nullptr, predicted_level);
   return with_retry([&]() -> int {
     ResidentCall call;  // (this search has no stereo gate)
-    rc = call.run(cur, n, slots, skip, false, true, false, resident_lists(kGateNone),
+    rc = call.run(cur, n, slots, skip, kLevel, resident_lists(kGateNone),
                   [&](const ResidentDev &R) { launch_project<kProjReloc>(R, mp, nullptr, A); });
     if (rc != VSG_OK) return rc;
-    call.outs(n, projected, u, v, predicted_level);
+    call.st.copy_out(dst);
     const vsg_keypoint *hk = cur->h_kps.data();
     return walk::search_kf_projection(call.wc.lists(), n, kf_angle, [&](int i) { return hk[i].angle; }, orb_dist,
                                       check_orientation != 0, occupied, train_match);
@@ -675,12 +654,11 @@ int vsg_frame_fuse_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t
   bool go;
   const int rc = keyframe_check(kf, mp, n, slots, pose, scale_factors, nlevels,
                                 best_idx && best_dist && inv_level_sigma2, &go);
-  if (rc != VSG_OK) return rc;
-  if (!go) return 0;
+  if (rc != VSG_OK || !go) return rc;
   // the chi-square gate of :1269-1293 reads mvuRight where the KeyFrame has it; bestDist starts at 256 (:1255)
   return fuse_points(kf, mp, n, slots, skip, pose, th, scale_factors, nlevels,
-                     {kWinBest, kGateChi2, 256, inv_level_sigma2, nlevels}, best_idx, best_dist, projected, u, v, ur,
-                     predicted_level);
+                     {kWinBest, kGateChi2, 256, inv_level_sigma2, nlevels}, best_idx, best_dist,
+                     keyframe_outs(projected, u, v, ur, predicted_level));
 }
 
 int vsg_frame_fuse_points_sim3(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
@@ -689,12 +667,11 @@ int vsg_frame_fuse_points_sim3(vsg_frame *kf, vsg_mappoints *mp, int n, const in
                                int32_t *predicted_level) {
   bool go;
   const int rc = keyframe_check(kf, mp, n, slots, pose, scale_factors, nlevels, best_idx && best_dist, &go);
-  if (rc != VSG_OK) return rc;
-  if (!go) return 0;
+  if (rc != VSG_OK || !go) return rc;
   // no gate; bestDist starts at INT_MAX (:1406)
   return fuse_points(kf, mp, n, slots, skip, pose, th, scale_factors, nlevels,
-                     {kWinBest, kGateNone, 0x7FFFFFFF, nullptr, 0}, best_idx, best_dist, projected, u, v, nullptr,
-                     predicted_level);
+                     {kWinBest, kGateNone, 0x7FFFFFFF, nullptr, 0}, best_idx, best_dist,
+                     keyframe_outs(projected, u, v, nullptr, predicted_level));
 }
 
 int vsg_frame_search_sim3_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
@@ -703,15 +680,15 @@ int vsg_frame_search_sim3_points(vsg_frame *kf, vsg_mappoints *mp, int n, const 
                                  int32_t *predicted_level) {
   bool go;
   int rc = keyframe_check(kf, mp, n, slots, pose, scale_factors, nlevels, matched != nullptr, &go);
-  if (rc != VSG_OK) return rc;
-  if (!go) return 0;
-  const ProjectArgs A = keyframe_args(kf, pose, n, th, scale_factors, nlevels);
+  if (rc != VSG_OK || !go) return rc;
+  const PointArgs A = point_args(kf, pose, n, kKeyFrameBounds, th, scale_factors, nlevels);
+  const PointOut dst = keyframe_outs(projected, u, v, nullptr, predicted_level);
   return with_retry([&]() -> int {
     ResidentCall call;
-    rc = call.run(kf, n, slots, skip, false, true, true, resident_lists(kGateNone),
+    rc = call.run(kf, n, slots, skip, kXr | kLevel, resident_lists(kGateNone),
                   [&](const ResidentDev &R) { launch_project<kProjKeyFrame>(R, mp, nullptr, A); });
     if (rc != VSG_OK) return rc;
-    call.outs(n, projected, u, v, nullptr, predicted_level);
+    call.st.copy_out(dst);
     // a point that does not pass :446-483 has an empty list: the pass does nothing for it (:490-491)
     return walk::search_sim3_projection(call.wc.lists(), n, ratio_hamming, matched);
   });

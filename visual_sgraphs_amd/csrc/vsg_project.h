@@ -7,7 +7,7 @@
 //   Fuse(pKF, vpMapPoints, th, bRight)                                       ORBmatcher.cc:1194-1241
 //   Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)                             ORBmatcher.cc:1360-1395
 // k_project_points (vsg_mappoints.hip) runs them one lane per query; tests/_projectcore, tests/_keyframecore and the
-// latency probes' caller-side loops compile them for the host.  As in vsg_frustum.h the order is fixed and nothing contracts: every
+// latency probe's caller-side loops (tools/resident_points_cpu.cpp) compile them for the host.  As in vsg_frustum.h the order is fixed and nothing contracts: every
 // operation is one vsg::f* call = one rounding.
 #pragma once
 #include "vsg_frustum.h"

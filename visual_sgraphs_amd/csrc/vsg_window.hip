@@ -554,15 +554,7 @@ static int fuse_search(vsg_frame *kf, int n_q, const uint8_t *mp_desc, const flo
   if (rc != VSG_OK) return rc;
   fill_keyframe_area(wc, n_q, mp_desc, u, v, ur, radius, predicted_level, right != 0);
   rc = wc.run(kf, gate, init, inv_level_sigma2, nlevels);
-  if (rc != VSG_OK) return rc;
-  const int32_t *b = wc.best();
-  int nfused = 0;
-  for (int k = 0; k < n_q; k++) {
-    best_idx[k] = b[2 * k];
-    best_dist[k] = b[2 * k] >= 0 ? b[2 * k + 1] : init;
-    if (b[2 * k] >= 0 && b[2 * k + 1] <= walk::TH_LOW) nfused++;
-  }
-  return nfused;
+  return rc != VSG_OK ? rc : wc.best_out(init, best_idx, best_dist);
 }
 
 int vsg_frame_fuse(vsg_frame *kf, int n_q, const uint8_t *mp_desc, const float *u, const float *v, const float *ur,

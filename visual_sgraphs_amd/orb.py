@@ -1390,46 +1390,49 @@ class Frame:
             "vsg_frame_search_by_projection")
         return nm, tm[:len(tb)], tb
 
+    # ---- the entries on resident map points (MapPoints): what they share on this side
+    @staticmethod
+    def _resident_points(slots, skip, fields, n=None, of="the slots"):
+        """slots (None: slots 0 .. n-1), skip flags of the same length (or None), and one output array of max(n, 1) entries
+        per dtype of `fields`.  Returns (n, slots pointer, skip pointer, the outputs' pointers in that order, trimmed) with
+        trimmed() = the outputs cut to n."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32) if slots is not None else None
+        n = len(sl) if sl is not None else int(n)
+        sk = _u8(skip) if skip is not None else None
+        if sk is not None and len(sk) != n:
+            raise ValueError(f"skip length does not match {of}")
+        outs = [np.zeros(max(n, 1), dt) for dt in fields]
+        ptr = {np.uint8: _u8p, np.int32: _i32p, np.float32: _f32p}
+        return (n, _p(_i32(sl), _i32p) if sl is not None else None, _p(sk, _u8p) if sk is not None and n else None,
+                [_p(a, ptr[dt]) for a, dt in zip(outs, fields)], lambda: tuple(a[:n] for a in outs))
+
     # ---- Frame::isInFrustum (Frame.cc:656-719) on resident map points
     def isInFrustum(self, mp, pose, n=None, slots=None, viewing_cos_limit=0.5):
         """mp: MapPoints, pose: FramePose.  Map point i = slot slots[i] (None: slots 0 .. n-1, n defaulting to the store's
         capacity).  Returns a dict: in_view, proj_x, proj_y, proj_xr, depth, scale_level, view_cos."""
-        sl = np.ascontiguousarray(slots, dtype=np.int32) if slots is not None else None
-        n = len(sl) if sl is not None else (mp.capacity if n is None else int(n))
-        m = max(n, 1)
-        out = {"in_view": np.zeros(m, np.uint8), "proj_x": np.zeros(m, np.float32), "proj_y": np.zeros(m, np.float32),
-               "proj_xr": np.zeros(m, np.float32), "depth": np.zeros(m, np.float32),
-               "scale_level": np.zeros(m, np.int32), "view_cos": np.zeros(m, np.float32)}
-        _check(self._L.vsg_frame_is_in_frustum(
-            self._h, mp.handle, n, _p(_i32(sl), _i32p) if sl is not None else None, C.byref(pose),
-            float(np.float32(viewing_cos_limit)), _p(out["in_view"], _u8p), _p(out["proj_x"], _f32p),
-            _p(out["proj_y"], _f32p), _p(out["proj_xr"], _f32p), _p(out["depth"], _f32p), _p(out["scale_level"], _i32p),
-            _p(out["view_cos"], _f32p)), "vsg_frame_is_in_frustum")
-        return {k: v[:n] for k, v in out.items()}
+        u8, f32, i32 = np.uint8, np.float32, np.int32
+        n, slp, _, o, trimmed = self._resident_points(slots, None, (u8, f32, f32, f32, f32, i32, f32),
+                                                      mp.capacity if n is None else n)
+        _check(self._L.vsg_frame_is_in_frustum(self._h, mp.handle, n, slp, C.byref(pose),
+                                               float(np.float32(viewing_cos_limit)), *o), "vsg_frame_is_in_frustum")
+        return dict(zip(("in_view", "proj_x", "proj_y", "proj_xr", "depth", "scale_level", "view_cos"), trimmed()))
 
     # ---- Tracking::SearchLocalPoints (Tracking.cc:3423-3495): isInFrustum + SearchByProjection(F, vpMapPoints)
     def SearchLocalPoints(self, mp, pose, th, nnratio, scale_factors, train_blocked, n=None, slots=None, skip=None,
                           viewing_cos_limit=0.5, far_points=False, th_far_points=0.0):
         """skip[i] != 0: mnLastFrameSeen == mnId or isBad() (never projected).  Returns (nmatches, train_match,
         train_blocked, in_view, proj_x, proj_y, n_to_match)."""
-        sl = np.ascontiguousarray(slots, dtype=np.int32) if slots is not None else None
-        n = len(sl) if sl is not None else (mp.capacity if n is None else int(n))
-        sk = _u8(skip) if skip is not None else None
-        if sk is not None and len(sk) != n:
-            raise ValueError("skip length does not match the map points")
-        m = max(n, 1)
+        n, slp, skp, o, trimmed = self._resident_points(slots, skip, (np.uint8, np.float32, np.float32),
+                                                        mp.capacity if n is None else n, "the map points")
         sf = _f32(scale_factors)
         tb = _u8(train_blocked).copy()
         tm = np.full(max(len(tb), 1), -1, np.int32)
-        inv, px, py = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32)
         ntm = C.c_int(0)
         nm = _check(self._L.vsg_frame_search_local_points(
-            self._h, mp.handle, n, _p(_i32(sl), _i32p) if sl is not None else None,
-            _p(sk, _u8p) if sk is not None and n else None, C.byref(pose), float(np.float32(viewing_cos_limit)), float(th),
+            self._h, mp.handle, n, slp, skp, C.byref(pose), float(np.float32(viewing_cos_limit)), float(th),
             float(np.float32(nnratio)), int(bool(far_points)), float(np.float32(th_far_points)), _p(sf, _f32p),
-            len(scale_factors), _p(tb, _u8p), _p(tm, _i32p), _p(inv, _u8p), _p(px, _f32p), _p(py, _f32p), C.byref(ntm)),
-            "vsg_frame_search_local_points")
-        return nm, tm[:len(tb)], tb, inv[:n], px[:n], py[:n], ntm.value
+            len(scale_factors), _p(tb, _u8p), _p(tm, _i32p), *o, C.byref(ntm)), "vsg_frame_search_local_points")
+        return (nm, tm[:len(tb)], tb, *trimmed(), ntm.value)
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono) on resident map points  (ORBmatcher.cc:1667-1878)
     def SearchLastFrame(self, last, mp, last_slots, cur_pose, last_pose, mb, mono, th, scale_factors, train_blocked,
@@ -1437,22 +1440,19 @@ class Frame:
         """last: the resident LastFrame; last_slots[i] = slot of its feature i's map point (< 0: none, or an outlier).
         Returns (nmatches, train_match, train_blocked, direction, projected, u, v, ur); train_match[i2] = index of the
         last-frame feature, the last four per last-frame feature."""
-        sl = np.ascontiguousarray(last_slots, dtype=np.int32) if last_slots is not None else None
-        n = len(last.kps)
-        if sl is not None and len(sl) != n:
+        if last_slots is not None and len(last_slots) != len(last.kps):
             raise ValueError("last_slots length does not match the last frame's features")
-        m = max(n, 1)
+        _, slp, _, o, trimmed = self._resident_points(last_slots, None, (np.uint8, np.float32, np.float32, np.float32),
+                                                      len(last.kps))
         sf = _f32(scale_factors)
         tb = _u8(train_blocked).copy()
         tm = np.full(max(len(tb), 1), -1, np.int32)
-        pr, u, v, ur = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32)
         direction = C.c_int(0)
         nm = _check(self._L.vsg_frame_search_last_frame(
-            self._h, last.handle, mp.handle, _p(_i32(sl), _i32p) if sl is not None else None, C.byref(cur_pose), C.byref(last_pose), float(np.float32(mb)),
+            self._h, last.handle, mp.handle, slp, C.byref(cur_pose), C.byref(last_pose), float(np.float32(mb)),
             int(bool(mono)), float(th), _p(sf, _f32p), len(scale_factors), int(bool(check_orientation)), _p(tb, _u8p),
-            _p(tm, _i32p), C.byref(direction), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(ur, _f32p)),
-            "vsg_frame_search_last_frame")
-        return nm, tm[:len(tb)], tb, direction.value, pr[:n], u[:n], v[:n], ur[:n]
+            _p(tm, _i32p), C.byref(direction), *o), "vsg_frame_search_last_frame")
+        return (nm, tm[:len(tb)], tb, direction.value, *trimmed())
 
     # ---- SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) on resident map points  (ORBmatcher.cc:1880-2000)
     def SearchKeyFramePoints(self, mp, slots, pose, th, orb_dist, scale_factors, occupied, kf_angle=None, skip=None,
@@ -1460,66 +1460,48 @@ class Frame:
         """slots[i] = slot of the KeyFrame's i-th map point, kf_angle[i] = pKF->mvKeysUn[i].angle, skip[i] != 0 = isBad() or
         in sAlreadyFound.  Returns (nmatches, train_match, occupied, projected, u, v, predicted_level); train_match[i2] =
         query index."""
-        sl = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(sl)
-        sk = _u8(skip) if skip is not None else None
+        n, slp, skp, o, trimmed = self._resident_points(slots, skip, (np.uint8, np.float32, np.float32, np.int32))
         ka = _f32(kf_angle) if kf_angle is not None else None
-        if (sk is not None and len(sk) != n) or (ka is not None and len(ka) != n):
-            raise ValueError("skip / kf_angle length does not match the slots")
-        m = max(n, 1)
+        if ka is not None and len(ka) != n:
+            raise ValueError("kf_angle length does not match the slots")
         sf = _f32(scale_factors)
         oc = _u8(occupied).copy()
         tm = np.full(max(len(oc), 1), -1, np.int32)
-        pr, u, v, lvl = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
         nm = _check(self._L.vsg_frame_search_keyframe_points(
-            self._h, mp.handle, n, _p(_i32(sl), _i32p), _p(sk, _u8p) if sk is not None and n else None, C.byref(pose),
-            float(th), int(orb_dist), _p(sf, _f32p), len(scale_factors), int(bool(check_orientation)),
-            _p(ka, _f32p) if ka is not None and n else None, _p(oc, _u8p), _p(tm, _i32p), _p(pr, _u8p), _p(u, _f32p),
-            _p(v, _f32p), _p(lvl, _i32p)), "vsg_frame_search_keyframe_points")
-        return nm, tm[:len(oc)], oc, pr[:n], u[:n], v[:n], lvl[:n]
+            self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), int(orb_dist), _p(sf, _f32p), len(scale_factors),
+            int(bool(check_orientation)), _p(ka, _f32p) if ka is not None and n else None, _p(oc, _u8p), _p(tm, _i32p), *o),
+            "vsg_frame_search_keyframe_points")
+        return (nm, tm[:len(oc)], oc, *trimmed())
 
     # ---- Fuse x2 and SearchByProjection(pKF, Scw, ...) on resident map points  (ORBmatcher.cc:1148-1446, :430-528)
-    def _keyframe_points(self, slots, skip):
-        sl = np.ascontiguousarray(slots, dtype=np.int32)
-        n = len(sl)
-        sk = _u8(skip) if skip is not None else None
-        if sk is not None and len(sk) != n:
-            raise ValueError("skip length does not match the slots")
-        m = max(n, 1)
-        outs = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
-        return sl, n, _p(sl, _i32p), _p(sk, _u8p) if sk is not None and n else None, outs
-
     def FusePoints(self, mp, slots, pose, th, scale_factors, inv_level_sigma2, skip=None):
         """Fuse(pKF, vpMapPoints, th, false) with self = pKF: slots[i] = slot of vpMapPoints[i], skip[i] != 0 = NULL, isBad()
         or IsInKeyFrame(pKF), pose = pKF's.  Returns (nFused, best_idx, best_dist, projected, u, v, ur, predicted_level),
         every array per query."""
-        sl, n, slp, skp, (pr, u, v, lvl) = self._keyframe_points(slots, skip)
+        u8, f32, i32 = np.uint8, np.float32, np.int32
+        n, slp, skp, o, trimmed = self._resident_points(slots, skip, (i32, i32, u8, f32, f32, f32, i32))
         sf, s2 = _f32(scale_factors), _f32(inv_level_sigma2)
         if len(s2) != len(sf):
             raise ValueError("inv_level_sigma2 length does not match the scale factors")
-        bi, bd, ur = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
-        nf = _check(self._L.vsg_frame_fuse_points(
-            self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), _p(sf, _f32p), _p(s2, _f32p), len(sf),
-            _p(bi, _i32p), _p(bd, _i32p), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(ur, _f32p), _p(lvl, _i32p)),
-            "vsg_frame_fuse_points")
-        return nf, bi[:n], bd[:n], pr[:n], u[:n], v[:n], ur[:n], lvl[:n]
+        nf = _check(self._L.vsg_frame_fuse_points(self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), _p(sf, _f32p),
+                                                  _p(s2, _f32p), len(sf), *o), "vsg_frame_fuse_points")
+        return (nf, *trimmed())
 
     def FusePoints_Sim3(self, mp, slots, pose, th, scale_factors, skip=None):
         """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) with self = pKF and pose = the decomposed Scw.  Returns (nFused,
         best_idx, best_dist, projected, u, v, predicted_level)."""
-        sl, n, slp, skp, (pr, u, v, lvl) = self._keyframe_points(slots, skip)
+        u8, f32, i32 = np.uint8, np.float32, np.int32
+        n, slp, skp, o, trimmed = self._resident_points(slots, skip, (i32, i32, u8, f32, f32, i32))
         sf = _f32(scale_factors)
-        bi, bd = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-        nf = _check(self._L.vsg_frame_fuse_points_sim3(
-            self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), _p(sf, _f32p), len(sf), _p(bi, _i32p),
-            _p(bd, _i32p), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(lvl, _i32p)), "vsg_frame_fuse_points_sim3")
-        return nf, bi[:n], bd[:n], pr[:n], u[:n], v[:n], lvl[:n]
+        nf = _check(self._L.vsg_frame_fuse_points_sim3(self._h, mp.handle, n, slp, skp, C.byref(pose), float(th),
+                                                       _p(sf, _f32p), len(sf), *o), "vsg_frame_fuse_points_sim3")
+        return (nf, *trimmed())
 
     def SearchSim3Points(self, mp, slots, pose, th, ratio_hamming, scale_factors, matched, skip=None):
         """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) with self = pKF and pose = the decomposed
         Scw; matched[i] != -1 = vpMatched[i] is set.  Returns (nmatches, matched, projected, u, v, predicted_level); a new
         entry of matched holds the query index."""
-        sl, n, slp, skp, (pr, u, v, lvl) = self._keyframe_points(slots, skip)
+        n, slp, skp, o, trimmed = self._resident_points(slots, skip, (np.uint8, np.float32, np.float32, np.int32))
         sf = _f32(scale_factors)
         if len(matched) != self.N:
             raise ValueError("matched length does not match the KeyFrame's features")
@@ -1527,9 +1509,8 @@ class Frame:
         m[:len(matched)] = matched
         nm = _check(self._L.vsg_frame_search_sim3_points(
             self._h, mp.handle, n, slp, skp, C.byref(pose), float(th), float(np.float32(ratio_hamming)), _p(sf, _f32p),
-            len(sf), _p(m, _i32p), _p(pr, _u8p), _p(u, _f32p), _p(v, _f32p), _p(lvl, _i32p)),
-            "vsg_frame_search_sim3_points")
-        return nm, m[:len(matched)], pr[:n], u[:n], v[:n], lvl[:n]
+            len(sf), _p(m, _i32p), *o), "vsg_frame_search_sim3_points")
+        return (nm, m[:len(matched)], *trimmed())
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono)  (ORBmatcher.cc:1667-1878)
     def SearchByProjection_Last(self, desc, observed, u, v, ur, last_octave, last_angle, th, direction, scale_factors,
