@@ -775,6 +775,37 @@ int vsg_frame_search_for_triangulation(vsg_frame *kf1, const uint8_t *eligible1,
                                        const uint8_t *eligible2, const int32_t *node_id2, const int32_t *off2,
                                        const int32_t *idx2, int nodes2, const uint32_t *pair_ok, const int32_t *pair_off,
                                        int check_orientation, int32_t *matches12);
+/* SearchForTriangulation(KeyFrame*, KeyFrame*, ...) (ORBmatcher.cc:902-1146) on two resident KeyFrames with the geometric
+ * predicate evaluated on the device too: no caller-side loop over the pairs and no bitmask.  LocalMapping::
+ * CreateNewMapPoints calls it for the new keyframe against each of its best covisible neighbours (LocalMapping.cc:389-460);
+ * one neighbour per call, as in the reference.  no_mpX[i] = !pKFX->GetMapPoint(i) (:969-973, :1001-1002) is the only
+ * per-feature state that goes up; everything else the predicate reads per keypoint is resident (mvKeysUn x, y, octave,
+ * mvuRight: a frame uploaded without mvuRight counts as all -1).  Per pair, in float, a fixed order and one rounding per
+ * operation (csrc/vsg_epipolar.h):
+ *   bOnlyStereo with a mono keypoint on either side: no candidate (:976-980, :1004-1008);
+ *   both keypoints mono: distex = ep[0] - x2, distey = ep[1] - y2, distex * distex + distey * distey <
+ *     100 * scale_factors2[octave2] rejects (:1023-1031; also under bCoarse);
+ *   unless bCoarse, Pinhole::epipolarConstrain (Pinhole.cpp:118-141): a = x1 * F12(0,0) + y1 * F12(1,0) + F12(2,0), b and c
+ *     with columns 1 and 2, num = a * x2 + b * y2 + c, den = a * a + b * b, den == 0 rejects, dsqr = num * num / den, accept
+ *     iff (double)dsqr < 3.84 * (double)level_sigma2_2[octave2] (a double comparison, as in the reference).
+ * F12 (row-major) = K1.transpose().inverse() * hat(t12) * R12 * K2.inverse() (Pinhole.cpp:121-124) and ep =
+ * pKF2->mpCamera->project(T2w * Cw) (:913-915) depend on the two keyframes only: the caller computes them once per call with
+ * the reference's own expressions.  scale_factors2 / level_sigma2_2 = pKF2->mvScaleFactors / mvLevelSigma2, nlevels entries.
+ * With ALL six FeatureVector arrays NULL the FeatureVectors both frames keep resident since their vsg_frame_bow_transform are
+ * joined on the device, under the rules of vsg_frame_search_by_bow_kf_kf: an empty frame or an empty vocabulary gives 0
+ * matches, a frame that never had its ComputeBoW VSG_ERR_INVALID.  matches12 and the return value (nmatches after the
+ * rotation-histogram filter) are those of vsg_frame_search_for_triangulation given eligible = no_mp (&& stereo under
+ * bOnlyStereo) and the bitmask of this predicate.  Checked before anything is enqueued: NULL handles, inputs or outputs,
+ * frames on different devices, nlevels outside 1..16, a keypoint of kf2 whose octave lies outside [0, nlevels), only SOME of
+ * the FeatureVector arrays NULL, and in the host-FeatureVector form offsets that do not ascend from 0 or an idx outside
+ * [0, n): VSG_ERR_INVALID; a frame with Nleft != -1 (mpCamera2: :929-937, :1033-1071): VSG_ERR_UNSUPPORTED.  An error after
+ * the enqueue waits for the stream before it returns. */
+int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *no_mp1, const int32_t *node_id1,
+                                                const int32_t *off1, const int32_t *idx1, int nodes1, vsg_frame *kf2,
+                                                const uint8_t *no_mp2, const int32_t *node_id2, const int32_t *off2,
+                                                const int32_t *idx2, int nodes2, const float F12[9], const float ep[2],
+                                                const float *scale_factors2, const float *level_sigma2_2, int nlevels,
+                                                int only_stereo, int coarse, int check_orientation, int32_t *matches12);
 /* Frame::ComputeBoW (Frame.cc:882-889) on the resident descriptors; outputs as vsg_bow_transform. */
 int vsg_frame_bow_transform(vsg_vocab *voc, vsg_frame *f, int levelsup, int32_t *bow_ids, double *bow_vals,
                             int bow_cap, int *n_bow, int32_t *fv_node, int32_t *fv_off, int32_t *fv_idx, int fv_cap,

@@ -1072,6 +1072,35 @@ class ResidentMatcher {
     return rc;
   }
 
+  // int SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, vector<pair<size_t, size_t>> &vMatchedPairs, const bool
+  // bOnlyStereo, const bool bCoarse) (ORBmatcher.h:72, ORBmatcher.cc:902-1146; LocalMapping.cc:389-460) with the predicate of
+  // :976-1073 on the device too (vsg_frame_search_for_triangulation_epipolar): no loop over the pairs here and no bitmask.
+  // noMpX[i] = !pKFX->GetMapPoint(i).  F12 (row-major) and ep are the caller's, once per pair of keyframes, with the
+  // reference's own expressions: F12 = K1.transpose().inverse() * Sophus::SO3f::hat(t12) * R12 * K2.inverse()
+  // (Pinhole.cpp:121-124), ep = pKF2->mpCamera->project(T2w * Cw) (:913-915).  mvScaleFactors2 / mvLevelSigma2_2 are pKF2's.
+  // fv1 / fv2 == nullptr: the FeatureVectors both frames keep resident since their ComputeBoW are joined on the device.
+  int SearchForTriangulation(ResidentFrame &pKF1, const uint8_t *noMp1, ResidentFrame &pKF2, const uint8_t *noMp2,
+                             const float F12[9], const float ep[2], const std::vector<float> &mvScaleFactors2,
+                             const std::vector<float> &mvLevelSigma2_2, bool bOnlyStereo, bool bCoarse,
+                             std::vector<std::pair<size_t, size_t>> &vMatchedPairs, const FeatureVectorCSR *fv1 = nullptr,
+                             const FeatureVectorCSR *fv2 = nullptr) const {
+    if (mvLevelSigma2_2.size() != mvScaleFactors2.size() || !fv1 != !fv2)
+      check(VSG_ERR_INVALID, "vsg_frame_search_for_triangulation_epipolar");
+    vMatchedPairs.clear();
+    if (fv1 && (fv1->nodes() == 0 || fv2->nodes() == 0)) return 0;  // no shared node (their data() may be NULL)
+    std::vector<int32_t> m12(pKF1.N() > 0 ? pKF1.N() : 1, -1);
+    const int rc = vsg_frame_search_for_triangulation_epipolar(
+        pKF1.handle(), noMp1, fv1 ? fv1->node.data() : nullptr, fv1 ? fv1->off.data() : nullptr,
+        fv1 ? fv1->idx.data() : nullptr, fv1 ? fv1->nodes() : 0, pKF2.handle(), noMp2, fv2 ? fv2->node.data() : nullptr,
+        fv2 ? fv2->off.data() : nullptr, fv2 ? fv2->idx.data() : nullptr, fv2 ? fv2->nodes() : 0, F12, ep,
+        mvScaleFactors2.data(), mvLevelSigma2_2.data(), (int)mvScaleFactors2.size(), bOnlyStereo, bCoarse,
+        mbCheckOrientation, m12.data());
+    check(rc, "vsg_frame_search_for_triangulation_epipolar");
+    for (int i = 0; i < pKF1.N(); i++)
+      if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1131-1141: pairs in idx1 order
+    return rc;
+  }
+
  protected:
   float mfNNratio;
   bool mbCheckOrientation;

@@ -16,6 +16,7 @@
 #include "../include/vsg_orb_debug.h"
 #include "../include/vsg_synth.h"
 #include "../oracle/orb_oracle.h"
+#include "../visual_sgraphs_amd/csrc/vsg_epipolar.h"
 
 static double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -268,6 +269,106 @@ int main(int argc, char **argv) {
       CHECK(a == b && a > 50 && m12 == m12o);
       snprintf(extra, sizeof extra, ", \"matches\": %d", a);
       emit("SearchForTriangulation_resident_k10_L6", time_ms([&]() { tg(); }, N), time_ms([&]() { to(); }, N / 4), extra);
+    }
+    // ---- the same search with the epipolar predicate of :976-1073: the caller-side loop (host predicate over every pair
+    // of every shared node -> bitmask -> vsg_frame_search_for_triangulation) against ONE call that evaluates it on the device
+    // and joins the resident FeatureVectors there (vsg_frame_search_for_triangulation_epipolar), at 1000- and 2000-feature
+    // keyframes.  F12 = a sideways translation along the sequence's shift, the epipole at the image centre.
+    {
+      float sig2[8];
+      vsg_orb_get_tables(ex, nullptr, nullptr, sig2, nullptr, nullptr, nullptr);
+      const double f = 500.0, cx = 320.0, cy = 240.0, t0 = 0.3, t1 = 0.2;
+      // K^-T [t]x K^-1 for t = (t0, t1, 0), R = I
+      const float F12[9] = {0.f, 0.f, (float)(t1 / f), 0.f, 0.f, (float)(-t0 / f), (float)(-t1 / f), (float)(t0 / f),
+                            0.f};
+      (void)cx, (void)cy;  // the principal point cancels in F12(2, 2)
+      const float ep[2] = {320.f, 240.f};
+      auto run = [&](const char *name, vsg_frame *Fa, vsg_frame *Fb, const vsg_keypoint *ka, const vsg_keypoint *kb, int na,
+                     int nb, const uint8_t *da, const uint8_t *db, FV &ga, FV &gb) -> int {
+        std::vector<uint8_t> m1(na, 1), m2(nb, 1);
+        for (int i = 0; i < na; i += 5) m1[i] = 0;
+        for (int i = 0; i < nb; i += 7) m2[i] = 0;
+        std::vector<int32_t> me(na), mc(na), mo(na), off;
+        std::vector<uint32_t> bits;
+        std::vector<float> aa(na), ab(nb);
+        for (int i = 0; i < na; i++) aa[i] = ka[i].angle;
+        for (int i = 0; i < nb; i++) ab[i] = kb[i].angle;
+        long long npairs = 0;
+        auto caller = [&]() {  // what ResidentMatcher::SearchForTriangulation(..., Pred, ...) does
+          bits.assign(1, 0u), off.assign(1, 0);
+          int a = 0, b = 0;
+          while (a < ga.n && b < gb.n) {
+            if (ga.node[a] == gb.node[b]) {
+              const int n2 = gb.off[b + 1] - gb.off[b];
+              for (int i1 = ga.off[a]; i1 < ga.off[a + 1]; i1++)
+                for (int i2 = gb.off[b]; i2 < gb.off[b + 1]; i2++) {
+                  const long long bit = (long long)off.back() + (long long)(i1 - ga.off[a]) * n2 + (i2 - gb.off[b]);
+                  if ((size_t)(bit >> 5) >= bits.size()) bits.resize((size_t)(bit >> 5) + 64, 0u);
+                  const vsg_keypoint &p = ka[ga.idx[i1]], &q = kb[gb.idx[i2]];
+                  if (m1[ga.idx[i1]] && m2[gb.idx[i2]] &&
+                      vsg::epipolar_reason_pair(F12, ep, p.x, p.y, -1.f, q.x, q.y, -1.f, sf[q.octave], sig2[q.octave], 0, 0) ==
+                          vsg::kEpiPass)
+                    bits[bit >> 5] |= 1u << (bit & 31);
+                }
+              off.push_back(off.back() + (ga.off[a + 1] - ga.off[a]) * n2);
+              a++, b++;
+            } else if (ga.node[a] < gb.node[b]) {
+              a++;
+            } else {
+              b++;
+            }
+          }
+          npairs = off.back();
+          bits.resize((size_t)(off.back() >> 5) + 2, 0u);
+          return vsg_frame_search_for_triangulation(Fa, m1.data(), ga.node.data(), ga.off.data(), ga.idx.data(), ga.n, Fb,
+                                                    m2.data(), gb.node.data(), gb.off.data(), gb.idx.data(), gb.n, bits.data(),
+                                                    off.data(), 1, mc.data());
+        };
+        auto device = [&]() {
+          return vsg_frame_search_for_triangulation_epipolar(Fa, m1.data(), nullptr, nullptr, nullptr, 0, Fb, m2.data(), nullptr,
+                                                             nullptr, nullptr, 0, F12, ep, sf, sig2, 8, 0, 0, 1, me.data());
+        };
+        const int c = caller(), e = device();
+        const int o = or_search_for_triangulation(da, aa.data(), m1.data(), na, ga.node.data(), ga.off.data(), ga.idx.data(), ga.n,
+                                                  db, ab.data(), m2.data(), nb, gb.node.data(), gb.off.data(), gb.idx.data(),
+                                                  gb.n, bits.data(), off.data(), 1, mo.data());
+        CHECK(c == e && c == o && c > 20 && me == mc && me == mo);
+        char extra2[192];
+        snprintf(extra2, sizeof extra2, ", \"caller_side_loop_ms\": %.4f, \"matches\": %d, \"pairs\": %lld, \"features\": %d",
+                 time_ms([&]() { caller(); }, N / 4), c, npairs, na);
+        const double oracle_ms = time_ms([&]() {  // the search alone, given the bits
+          or_search_for_triangulation(da, aa.data(), m1.data(), na, ga.node.data(), ga.off.data(), ga.idx.data(), ga.n, db,
+                                      ab.data(), m2.data(), nb, gb.node.data(), gb.off.data(), gb.idx.data(), gb.n, bits.data(),
+                                      off.data(), 1, mo.data());
+        }, N / 4);
+        emit(name, time_ms([&]() { device(); }, N), oracle_ms, extra2);
+        return 0;
+      };
+      if (run("SearchForTriangulation_epipolar_resident_k10_L6", F[0], F[1], kp[0].data(), kp[1].data(), nq, nt, ds[0].data(),
+              ds[1].data(), g0, g1))
+        return 1;
+      // 2000-feature keyframes of the same two images
+      vsg_orb *ex2 = nullptr;
+      CHECK(vsg_orb_create(2000, 1.2f, 8, 20, 7, 0, 1, &ex2) == VSG_OK);
+      const int cap2 = vsg_orb_capacity(ex2, H, W);
+      std::vector<vsg_keypoint> kq[2] = {std::vector<vsg_keypoint>(cap2), std::vector<vsg_keypoint>(cap2)};
+      std::vector<uint8_t> dq[2] = {std::vector<uint8_t>(cap2 * 32), std::vector<uint8_t>(cap2 * 32)};
+      int n2k[2];
+      vsg_frame *G[2];
+      FV h0(cap2), h1(cap2);
+      FV *hh[2] = {&h0, &h1};
+      for (int t = 0; t < 2; t++) {
+        CHECK(vsg_orb_extract(ex2, img[t].data(), H, W, W, 0, 0, kq[t].data(), dq[t].data(), cap2, &n2k[t]) >= 0);
+        CHECK(vsg_frame_create(0, cap2, &G[t]) == VSG_OK);
+        CHECK(vsg_frame_from_extractor(G[t], ex2, 0, kq[t].data(), n2k[t], 0.f, 0.f, (float)W, (float)H) == VSG_OK);
+        CHECK(vsg_frame_bow_transform(voc, G[t], 4, hh[t]->bid.data(), hh[t]->bval.data(), cap2, &hh[t]->nb, hh[t]->node.data(),
+                                      hh[t]->off.data(), hh[t]->idx.data(), cap2, &hh[t]->n, nullptr, nullptr, nullptr) == VSG_OK);
+      }
+      if (run("SearchForTriangulation_epipolar_resident_k10_L6_2000", G[0], G[1], kq[0].data(), kq[1].data(), n2k[0], n2k[1],
+              dq[0].data(), dq[1].data(), h0, h1))
+        return 1;
+      for (int t = 0; t < 2; t++) vsg_frame_destroy(G[t]);
+      vsg_orb_destroy(ex2);
     }
     vsg_vocab_destroy(voc);
     or_vocab_destroy(ovoc);

@@ -44,7 +44,7 @@ def needs_build():
     if not LIB.exists():
         return True
     deps = list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + \
-        [PKG.parent / "include" / "vsg_orb.h", PKG.parent / "include" / "vsg_orb_debug.h"]
+        [PKG.parent / "include" / n for n in ("vsg_orb.h", "vsg_orb_debug.h", "vsg_orb_debug_epipolar.h")]
     return any(d.stat().st_mtime > LIB.stat().st_mtime for d in deps)
 
 
@@ -65,7 +65,8 @@ def build(force=False, verbose=False):
     obj_dir.mkdir(parents=True, exist_ok=True)
     hipcc = _hipcc()
     headers = list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + [PKG.parent / "include" / "vsg_orb.h",
-                                                                    PKG.parent / "include" / "vsg_orb_debug.h", Path(__file__)]
+                                                                    PKG.parent / "include" / "vsg_orb_debug.h",
+                                                                    PKG.parent / "include" / "vsg_orb_debug_epipolar.h", Path(__file__)]
     hdr_time = max(h.stat().st_mtime for h in headers)
 
     def compile_one(src):

@@ -19,7 +19,9 @@
 #include <algorithm>
 
 #include "../../include/vsg_orb.h"
+#include "../../include/vsg_orb_debug_epipolar.h"
 #include "vsg_ctx.h"
+#include "vsg_epipolar.h"
 #include "vsg_frame_int.h"
 #include "vsg_math.h"
 #include "vsg_walks.h"
@@ -497,6 +499,140 @@ __global__ __launch_bounds__(256) void k_search_triangulation(const NodePair *pa
   }
 }
 
+// ---- SearchForTriangulation with the geometric predicate of :976-1073 evaluated HERE (vsg_epipolar.h) instead of read as
+// one caller-made bit per pair.  The predicate is a pure function of the pair and the reference never sets vbMatched2, so KF1
+// features are independent: one WORKGROUP per shared vocabulary node, joined on the host (pairs) or -- pairs == nullptr -- in
+// the kernel on the two resident FeatureVectors, exactly as k_search_by_bow does.
+//   * The node's KF2 side goes to LDS once per tile of kEpiTile rows: descriptor, x, y, the level's gate radius and chi-square
+//     bound (two 16-entry tables made by the host with the header's own functions) and the flags (stereo; has a map point).
+//   * Waves take the KF1 rows round-robin; (a, b, c, den) of the row's epipolar line are wave-uniform, the lanes stride the
+//     tile's KF2 rows, run the geometry first and the Hamming distance for the survivors; wave_min over
+//     (dist << 20) | (0xFFFFF - j), j = the position in the node's KF2 list ACROSS tiles: the later of equal distances wins.
+//   * KF1 rows are taken kEpiRows at a time, staged the same way (one round of loads instead of a dependent chain per row); a
+//     row's running minimum over the tiles lives in LDS (s_key), owned by the wave that walks the row.  A node of any size
+//     on either side is walked with the same 14 KB of LDS; a node whose KF2 side fits one tile (every node of a real
+//     FeatureVector) is staged once.
+// matches12 is WRITE-ONLY (pre-filled with -1 by the host: pinned memory); a KF1 feature belongs to one node.
+struct EpiParams {
+  float F12[9], ep[2];
+  float gate[16];    // epipole_gate_radius(mvScaleFactors2[level]); 0 above nlevels
+  double bound[16];  // chi_square_bound(mvLevelSigma2_2[level])
+  int only_stereo, coarse;
+};
+struct EpiFrame {
+  const vsg::KeyPointPOD *kps;
+  const uint8_t *desc;
+  const float *uright;  // nullptr: every mvuRight is -1
+  const uint8_t *no_mp;  // !pKF->GetMapPoint(i)
+};
+enum { kEpiTile = 128, kEpiRows = 128, kEpiStereo = 1, kEpiHasMp = 2 };
+
+__global__ __launch_bounds__(256) void k_triangulation_epipolar(const NodePair *pairs, int npairs, FvDev fa, FvDev fb,
+                                                                const int *idxA, const int *idxB, EpiFrame A, EpiFrame B,
+                                                                EpiParams P, int *matches12) {
+  const int node = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  NodePair np;
+  if (pairs) {
+    if (node >= npairs) return;
+    np = pairs[node];
+  } else {  // the join of k_search_by_bow
+    __shared__ int s_pos;
+    const int nA_nodes = fa.hdr[0], nB_nodes = fb.hdr[0];
+    const int id = node < nA_nodes ? fa.node[node] : -1;
+    if (tid == 0) s_pos = -1;
+    __syncthreads();
+    for (int base = 0; base < nB_nodes; base += 256)
+      if (base + tid < nB_nodes && fb.node[base + tid] == id) s_pos = base + tid;  // ids are unique: at most one writer
+    __syncthreads();
+    const int lo = s_pos;
+    if (node >= nA_nodes || lo < 0) return;
+    np.a_begin = fa.off[node], np.a_end = fa.off[node + 1], np.b_begin = fb.off[lo], np.b_end = fb.off[lo + 1];
+    idxA = fa.idx, idxB = fb.idx;
+  }
+  const int na = np.a_end - np.a_begin, nb = np.b_end - np.b_begin;
+  __shared__ uint4 s_d[kEpiTile][2], s_da[kEpiRows][2];
+  __shared__ double s_bound[kEpiTile];
+  __shared__ float s_x[kEpiTile], s_y[kEpiTile], s_gate[kEpiTile], s_ax[kEpiRows], s_ay[kEpiRows];
+  __shared__ int s_flag[kEpiTile], s_ra[kEpiRows], s_aflag[kEpiRows];
+  __shared__ uint32_t s_key[kEpiRows];
+  const int sr = tid >> 1, sh = tid & 1;  // staging: thread = (row, descriptor half)
+  int staged = -1;                        // first KF2 row of the tile in LDS (block-uniform)
+  for (int a0 = 0; a0 < na; a0 += kEpiRows) {
+    const int rows = min(kEpiRows, na - a0);
+    __syncthreads();  // every wave is done with the chunk before
+    if (sr < rows) {  // the chunk's KF1 side in one round of loads
+      const int ra = idxA[np.a_begin + a0 + sr];
+      s_da[sr][sh] = ((const uint4 *)(A.desc + (size_t)ra * 32))[sh];
+      if (sh == 0) {
+        const vsg::KeyPointPOD kp = A.kps[ra];
+        const bool stereo1 = A.uright && A.uright[ra] >= 0;
+        // -1: has a map point (:969-973), or mono under bOnlyStereo (:976-980): the row is not walked
+        s_ra[sr] = ra, s_ax[sr] = kp.x, s_ay[sr] = kp.y, s_key[sr] = KEY_NONE;
+        s_aflag[sr] = (!A.no_mp[ra] || (P.only_stereo && !stereo1)) ? -1 : (stereo1 ? kEpiStereo : 0);
+      }
+    }
+    __syncthreads();
+    for (int t0 = 0; t0 < nb; t0 += kEpiTile) {
+      const int nt = min(kEpiTile, nb - t0);
+      if (staged != t0) {
+        if (staged >= 0) __syncthreads();  // every wave is done with the tile before
+        if (sr < nt) {
+          const int rb = idxB[np.b_begin + t0 + sr];
+          s_d[sr][sh] = ((const uint4 *)(B.desc + (size_t)rb * 32))[sh];
+          if (sh == 0) {
+            const vsg::KeyPointPOD kp = B.kps[rb];
+            const int lv = kp.octave & 15;  // the host checked [0, nlevels) on its mirror; the tables have 16 entries
+            s_x[sr] = kp.x, s_y[sr] = kp.y, s_gate[sr] = P.gate[lv], s_bound[sr] = P.bound[lv];
+            s_flag[sr] = ((B.uright && B.uright[rb] >= 0) ? kEpiStereo : 0) | (B.no_mp[rb] ? 0 : kEpiHasMp);
+          }
+        }
+        staged = t0;
+        __syncthreads();
+      }
+      for (int r = wave; r < rows; r += 4) {  // wave-uniform; row r belongs to wave r & 3
+        const int af = s_aflag[r];
+        if (af < 0) continue;
+        const bool stereo1 = af != 0;
+        vsg::EpipolarLine line = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (!P.coarse) line = vsg::epipolar_line(P.F12, s_ax[r], s_ay[r]);
+        const uint4 d0 = s_da[r][0], d1 = s_da[r][1];
+        uint32_t k = KEY_NONE;
+        for (int j = lane; j < nt; j += 64) {
+          const int fl = s_flag[j];
+          if (fl & kEpiHasMp) continue;  // :1001-1002
+          if (vsg::epipolar_reason(line, stereo1, s_x[j], s_y[j], (fl & kEpiStereo) != 0, P.ep[0], P.ep[1], s_gate[j],
+                                   s_bound[j], P.only_stereo, P.coarse) != vsg::kEpiPass)
+            continue;
+          const int dist = hamming256(d0, d1, s_d[j][0], s_d[j][1]);
+          if (dist > TH_LOW) continue;  // :1014
+          k = min(k, ((uint32_t)dist << 20) | (0xFFFFFu - (uint32_t)(t0 + j)));
+        }
+        k = wave_min(k);
+        if (lane == 0) s_key[r] = min(s_key[r], k);  // the owner wave's own entry: no other wave reads or writes it
+      }
+    }
+    // the chunk's matches: a wave writes the rows it owns (what its lane 0 left in s_key: same wave, program order)
+    for (int r = wave + 4 * lane; r < rows; r += 256) {
+      const uint32_t k = s_key[r];
+      if (k != KEY_NONE) matches12[s_ra[r]] = idxB[np.b_begin + (int)(0xFFFFFu - (k & 0xFFFFFu))];
+    }
+  }
+}
+
+// test hook (vsg_debug_epipolar_pairs): the device predicate on listed pairs, one lane per pair
+__global__ __launch_bounds__(256) void k_epipolar_pairs(int n, const int *i1, const int *i2, EpiFrame A, EpiFrame B,
+                                                        EpiParams P, uint8_t *reason) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int ra = i1[p], rb = i2[p];
+  const vsg::KeyPointPOD k1 = A.kps[ra], k2 = B.kps[rb];
+  vsg::EpipolarLine line = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!P.coarse) line = vsg::epipolar_line(P.F12, k1.x, k1.y);
+  const int lv = k2.octave & 15;
+  reason[p] = (uint8_t)vsg::epipolar_reason(line, A.uright && A.uright[ra] >= 0, k2.x, k2.y, B.uright && B.uright[rb] >= 0,
+                                            P.ep[0], P.ep[1], P.gate[lv], P.bound[lv], P.only_stereo, P.coarse);
+}
+
 // ---- windowed searches on HOST candidate lists (the caller ran GetFeaturesInArea itself): every candidate entry's
 // Hamming distance in ONE data-parallel pass, written as the packed entry the ordered host passes read
 // (vsg_walks.h: index | distance << 15 | octave << 24).  The walk over the queries that follows is inherently
@@ -838,9 +974,138 @@ static int search_triangulation(int device, const uint8_t *desc1, const uint8_t 
   return bow_rotation_filter(matches12, n1, 1, angle1, angle2, check_orientation != 0);
 }
 
+// the per-call constants of the epipolar predicate: F12, ep and the two per-level tables of pKF2 (vsg_epipolar.h)
+static EpiParams epi_params(const float *F12, const float *ep, const float *scale_factors2, const float *level_sigma2_2,
+                            int nlevels, int only_stereo, int coarse) {
+  EpiParams P;
+  memset(&P, 0, sizeof P);
+  memcpy(P.F12, F12, sizeof P.F12);
+  P.ep[0] = ep[0], P.ep[1] = ep[1];
+  for (int l = 0; l < nlevels; l++)
+    P.gate[l] = vsg::epipole_gate_radius(scale_factors2[l]), P.bound[l] = vsg::chi_square_bound(level_sigma2_2[l]);
+  P.only_stereo = only_stereo != 0, P.coarse = coarse != 0;
+  return P;
+}
+static bool octaves_within(const vsg_frame *f, int nlevels) {
+  for (const vsg_keypoint &k : f->h_kps)
+    if (k.octave < 0 || k.octave >= nlevels) return false;
+  return true;
+}
+// a FeatureVector given as host arrays: ascending offsets from 0 and feature indices inside the frame
+static bool fv_within(const int32_t *off, const int32_t *idx, int nodes, int n) {
+  if (nodes < 0 || (nodes > 0 && off[0] != 0)) return false;
+  for (int k = 0; k < nodes; k++)
+    if (off[k + 1] < off[k]) return false;
+  for (int k = 0, e = nodes > 0 ? off[nodes] : 0; k < e; k++)
+    if (idx[k] < 0 || idx[k] >= n) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *no_mp1, const int32_t *node_id1,
+                                                const int32_t *off1, const int32_t *idx1, int nodes1, vsg_frame *kf2,
+                                                const uint8_t *no_mp2, const int32_t *node_id2, const int32_t *off2,
+                                                const int32_t *idx2, int nodes2, const float F12[9], const float ep[2],
+                                                const float *scale_factors2, const float *level_sigma2_2, int nlevels,
+                                                int only_stereo, int coarse, int check_orientation, int32_t *matches12) {
+  // ---- everything that can be refused is refused here, before anything is enqueued
+  if (vsg::frame_check(kf1) != VSG_OK || vsg::frame_check(kf2) != VSG_OK || kf1->device != kf2->device || !F12 || !ep ||
+      !scale_factors2 || !level_sigma2_2 || nlevels < 1 || nlevels > 16 || (!matches12 && kf1->n > 0) ||
+      (!no_mp1 && kf1->n > 0) || (!no_mp2 && kf2->n > 0))
+    return VSG_ERR_INVALID;
+  if (kf1->nleft != -1 || kf2->nleft != -1) return VSG_ERR_UNSUPPORTED;  // mpCamera2 (:929-937, :1033-1071)
+  if (!octaves_within(kf2, nlevels)) return VSG_ERR_INVALID;
+  const bool resident_fv = !node_id1 && !off1 && !idx1 && !node_id2 && !off2 && !idx2;
+  if (!resident_fv) {
+    if (!node_id1 || !off1 || !idx1 || !node_id2 || !off2 || !idx2) return VSG_ERR_INVALID;
+    // the kernel indexes the frames with these: an index outside a frame never reaches the device
+    if (!fv_within(off1, idx1, nodes1, kf1->n) || !fv_within(off2, idx2, nodes2, kf2->n)) return VSG_ERR_INVALID;
+  }
+  const int n1 = kf1->n, n2 = kf2->n;
+  // ComputeBoW first (Frame.cc:882-889); an empty frame has an empty FeatureVector whatever ComputeBoW left
+  if (resident_fv && n1 > 0 && n2 > 0 && (!kf1->fv_valid || !kf2->fv_valid)) return VSG_ERR_INVALID;
+  for (int i = 0; i < n1; i++) matches12[i] = -1;  // no output is touched before the last refusal
+  if (n1 == 0 || n2 == 0) return 0;  // no shared node, 0 matches (ORBmatcher.cc:961)
+  std::vector<NodePair> pairs;
+  if (resident_fv) {
+    if (kf1->fv_empty || kf2->fv_empty) return 0;  // ComputeBoW with an empty() vocabulary left no node
+  } else {
+    join_nodes(node_id1, off1, nodes1, node_id2, off2, nodes2, pairs);
+    if (pairs.empty()) return 0;
+  }
+  int rc = VSG_OK;
+  ThreadCtx *c = vsg::thread_ctx(kf1->device, &rc);
+  if (!c) return rc;
+  // ONE launch and nothing else on the stream (as bow_search_enqueue): the flags and lists are read and the matches written
+  // where they lie in the pinned arena
+  const int npairs = (int)pairs.size(), nI1 = resident_fv ? 0 : off1[nodes1], nI2 = resident_fv ? 0 : off2[nodes2];
+  Stage st;
+  const size_t oF1 = st.add((size_t)n1), oF2 = st.add((size_t)n2), oP = st.add(pairs.size() * sizeof(NodePair)),
+               oI1 = st.add((size_t)nI1 * 4), oI2 = st.add((size_t)nI2 * 4), oM = st.add((size_t)n1 * 4);
+  rc = vsg::ctx_reserve(c, st.total, 0);
+  if (rc != VSG_OK) return rc;
+  uint8_t *h = c->h_pin, *d = c->d_pin;
+  memcpy(h + oF1, no_mp1, (size_t)n1);
+  memcpy(h + oF2, no_mp2, (size_t)n2);
+  if (!resident_fv) {
+    memcpy(h + oP, pairs.data(), pairs.size() * sizeof(NodePair));
+    memcpy(h + oI1, idx1, (size_t)nI1 * 4);
+    memcpy(h + oI2, idx2, (size_t)nI2 * 4);
+  }
+  memset(h + oM, 0xFF, (size_t)n1 * 4);  // -1: the kernel only writes matches
+  const EpiParams P = epi_params(F12, ep, scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse);
+  const EpiFrame A{kf1->d_kps, kf1->d_desc, kf1->has_uright ? kf1->d_uright : (const float *)nullptr, d + oF1};
+  const EpiFrame B{kf2->d_kps, kf2->d_desc, kf2->has_uright ? kf2->d_uright : (const float *)nullptr, d + oF2};
+  FvDev fa{}, fb{};
+  if (resident_fv)
+    fa = FvDev{kf1->d_fv_hdr, kf1->d_fv_node, kf1->d_fv_off, kf1->d_fv_idx},
+    fb = FvDev{kf2->d_fv_hdr, kf2->d_fv_node, kf2->d_fv_off, kf2->d_fv_idx};
+  const int blocks = resident_fv ? (kf1->fv_bound > 0 ? kf1->fv_bound : 1) : npairs;
+  hipLaunchKernelGGL(k_triangulation_epipolar, dim3(blocks), dim3(256), 0, c->stream,
+                     resident_fv ? (const NodePair *)nullptr : (const NodePair *)(d + oP), npairs, fa, fb,
+                     (const int *)(d + oI1), (const int *)(d + oI2), A, B, P, (int *)(d + oM));
+  const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(c->stream);  // an error still waits
+  if (launched != hipSuccess || waited != hipSuccess) return VSG_ERR_HIP;
+  memcpy(matches12, h + oM, (size_t)n1 * 4);
+  const vsg_keypoint *ka = kf1->h_kps.data(), *kb = kf2->h_kps.data();
+  return bow_rotation_filter(matches12, n1, 1, [&](int i) { return ka[i].angle; }, [&](int i) { return kb[i].angle; },
+                             check_orientation != 0);
+}
+
+int vsg_debug_epipolar_pairs(vsg_frame *kf1, vsg_frame *kf2, int n, const int32_t *i1, const int32_t *i2,
+                             const float F12[9], const float ep[2], const float *scale_factors2,
+                             const float *level_sigma2_2, int nlevels, int only_stereo, int coarse, uint8_t *reason) {
+  if (vsg::frame_check(kf1) != VSG_OK || vsg::frame_check(kf2) != VSG_OK || kf1->device != kf2->device || n < 0 ||
+      (n > 0 && (!i1 || !i2 || !reason)) || !F12 || !ep || !scale_factors2 || !level_sigma2_2 || nlevels < 1 || nlevels > 16)
+    return VSG_ERR_INVALID;
+  if (kf1->nleft != -1 || kf2->nleft != -1) return VSG_ERR_UNSUPPORTED;
+  if (!octaves_within(kf2, nlevels)) return VSG_ERR_INVALID;
+  for (int p = 0; p < n; p++)
+    if (i1[p] < 0 || i1[p] >= kf1->n || i2[p] < 0 || i2[p] >= kf2->n) return VSG_ERR_INVALID;
+  if (n == 0) return VSG_OK;
+  int rc = VSG_OK;
+  ThreadCtx *c = vsg::thread_ctx(kf1->device, &rc);
+  if (!c) return rc;
+  Stage st;
+  const size_t o1 = st.add((size_t)n * 4), o2 = st.add((size_t)n * 4), oR = st.add((size_t)n);
+  rc = vsg::ctx_reserve(c, st.total, 0);
+  if (rc != VSG_OK) return rc;
+  uint8_t *h = c->h_pin, *d = c->d_pin;
+  memcpy(h + o1, i1, (size_t)n * 4);
+  memcpy(h + o2, i2, (size_t)n * 4);
+  const EpiParams P = epi_params(F12, ep, scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse);
+  const EpiFrame A{kf1->d_kps, kf1->d_desc, kf1->has_uright ? kf1->d_uright : (const float *)nullptr, nullptr};
+  const EpiFrame B{kf2->d_kps, kf2->d_desc, kf2->has_uright ? kf2->d_uright : (const float *)nullptr, nullptr};
+  hipLaunchKernelGGL(k_epipolar_pairs, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, (const int *)(d + o1),
+                     (const int *)(d + o2), A, B, P, d + oR);
+  const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(c->stream);
+  if (launched != hipSuccess || waited != hipSuccess) return VSG_ERR_HIP;
+  memcpy(reason, h + oR, (size_t)n);
+  return VSG_OK;
+}
 
 int vsg_hamming_pairs(int device, const uint8_t *a, int na, const uint8_t *b, int nb, const int32_t *ia,
                       const int32_t *ib, int npairs, int32_t *dist) {

@@ -78,6 +78,9 @@ EXPORTS = [
     "vsg_frame_search_last_frame", "vsg_frame_search_keyframe_points",
     # Fuse x2 and the Sim3 projection search on resident map points
     "vsg_frame_fuse_points", "vsg_frame_fuse_points_sim3", "vsg_frame_search_sim3_points",
+    # SearchForTriangulation with the epipolar test on the device (its test hook, vsg_debug_epipolar_pairs of
+    # include/vsg_orb_debug_epipolar.h, is bound below but is no part of the two headers this list mirrors)
+    "vsg_frame_search_for_triangulation_epipolar",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -295,6 +298,9 @@ def load_library():
                                                 cf, ci, _i32p]
     L.vsg_frame_search_for_triangulation.argtypes = [vp, _u8p, _i32p, _i32p, _i32p, ci, vp, _u8p, _i32p, _i32p, _i32p,
                                                      ci, vp, vp, ci, _i32p]
+    L.vsg_frame_search_for_triangulation_epipolar.argtypes = [vp, _u8p, _i32p, _i32p, _i32p, ci, vp, _u8p, _i32p, _i32p,
+                                                              _i32p, ci, _f32p, _f32p, _f32p, _f32p, ci, ci, ci, ci, _i32p]
+    L.vsg_debug_epipolar_pairs.argtypes = [vp, vp, ci, _i32p, _i32p, _f32p, _f32p, _f32p, _f32p, ci, ci, ci, _u8p]
     L.vsg_frame_bow_transform.argtypes = [vp, vp, ci, _i32p, _f64p, ci, _i32p, _i32p, _i32p, _i32p, ci, _i32p, _i32p,
                                           _i32p, _f64p]
     L.vsg_frame_stereo_matches.argtypes = [vp, ci, vp, ci, vp, vp, cf, cf, _f32p, _f32p]
@@ -1628,6 +1634,32 @@ class Frame:
             "vsg_frame_search_for_triangulation")
         return nm, out[:self.N]
 
+    def SearchForTriangulationEpipolar(self, no_mp1, kf2, no_mp2, F12, ep, scale_factors2, level_sigma2_2, only_stereo,
+                                       coarse, check_orientation, fv1=None, fv2=None):
+        """ORBmatcher::SearchForTriangulation (ORBmatcher.cc:902-1146), self = pKF1, kf2 = pKF2, both resident, with the
+        epipole gate and Pinhole::epipolarConstrain evaluated on the device (vsg_frame_search_for_triangulation_epipolar).
+        no_mpX[i] = !pKFX->GetMapPoint(i); F12 = the 3 x 3 fundamental matrix (row-major), ep = the epipole in kf2;
+        scale_factors2 / level_sigma2_2 = pKF2's mvScaleFactors / mvLevelSigma2.  fv1 = fv2 = None: the FeatureVectors both
+        frames keep resident since their ComputeBoW are joined on the device.  Returns (nmatches, matches12)."""
+        m1, m2 = _u8(no_mp1), _u8(no_mp2)
+        F, e = _f32(np.asarray(F12).reshape(9)), _f32(np.asarray(ep).reshape(2))
+        sf, s2 = _f32(scale_factors2), _f32(level_sigma2_2)
+        assert len(sf) == len(s2)
+        if (fv1 is None) != (fv2 is None):
+            raise ValueError("fv1 and fv2: both or neither")
+        a1 = a2 = (None, None, None)
+        keep = []
+        if fv1 is not None:
+            keep = [_i32(x) for x in fv1] + [_i32(x) for x in fv2]
+            a1, a2 = tuple(_p(x, _i32p) for x in keep[:3]), tuple(_p(x, _i32p) for x in keep[3:])
+        out = np.full(max(self.N, 1), -1, np.int32)
+        nm = _check(self._L.vsg_frame_search_for_triangulation_epipolar(
+            self._h, _p(m1, _u8p), *a1, len(fv1[0]) if fv1 is not None else 0, kf2.handle, _p(m2, _u8p), *a2,
+            len(fv2[0]) if fv2 is not None else 0, _p(F, _f32p), _p(e, _f32p), _p(sf, _f32p), _p(s2, _f32p), len(sf),
+            int(bool(only_stereo)), int(bool(coarse)), int(bool(check_orientation)), _p(out, _i32p)),
+            "vsg_frame_search_for_triangulation_epipolar")
+        return nm, out[:self.N]
+
     def ComputeBoW(self, voc, levelsup=4):
         """Frame::ComputeBoW on the resident descriptors; same dict as ORBVocabulary.transform."""
         n = self.N
@@ -1644,6 +1676,21 @@ class Frame:
         return dict(bow_ids=bi[:nb.value].copy(), bow_vals=bv[:nb.value].copy(),
                     fv=(fn[:nf.value].copy(), fo[:nf.value + 1].copy(), fi[:fo[nf.value]].copy()),
                     word=w_of[:n].copy(), node=n_of[:n].copy(), weight=wt[:n].copy())
+
+
+def debug_epipolar_pairs(kf1, kf2, i1, i2, F12, ep, scale_factors2, level_sigma2_2, only_stereo, coarse):
+    """Test hook (include/vsg_orb_debug_epipolar.h): the reason code the DEVICE predicate of SearchForTriangulationEpipolar gives
+    each listed pair (feature i1[p] of kf1, i2[p] of kf2): 0 pass, 1 not stereo under only_stereo, 2 epipole gate,
+    3 den == 0, 4 chi-square."""
+    a, b = _i32(i1), _i32(i2)
+    assert len(a) == len(b)
+    F, e = _f32(np.asarray(F12).reshape(9)), _f32(np.asarray(ep).reshape(2))
+    sf, s2 = _f32(scale_factors2), _f32(level_sigma2_2)
+    out = np.zeros(max(len(a), 1), np.uint8)
+    _check(load_library().vsg_debug_epipolar_pairs(
+        kf1.handle, kf2.handle, len(a), _p(a, _i32p), _p(b, _i32p), _p(F, _f32p), _p(e, _f32p), _p(sf, _f32p), _p(s2, _f32p),
+        len(sf), int(bool(only_stereo)), int(bool(coarse)), _p(out, _u8p)), "vsg_debug_epipolar_pairs")
+    return out[:len(a)]
 
 
 def SearchBySim3(kf1, kf2, q1, q2):
