@@ -2225,7 +2225,13 @@ __global__ __launch_bounds__(256) void k_stereo(PyrView pl, PyrView pr, StereoPa
     const int ily = (int)fsub(scaledvL, (float)w), ilx = (int)fsub(scaleduL, (float)w);
     const float iniu = fsub(fadd(scaleduR0, (float)L), (float)w);
     const float endu = fadd(fadd(fadd(scaleduR0, (float)L), (float)w), 1.0f);
-    if (!(iniu < 0 || endu >= (float)pr.w[levelL])) {
+    // The levels carry no 19 px border (mvImagePyramid does): a keypoint whose left 11 x 11 window or right 11 x 21 strip
+    // (columns scaleduR0 - 10 .. scaleduR0 + 10) leaves level levelL gets no match.  Every operand is wave-uniform and no
+    // pixel has been loaded yet; ORBextractor keypoints (x, y >= 19 on their level) never come here.
+    const int iur = (int)scaleduR0;
+    const int wl = min(pl.w[levelL], pr.w[levelL]), hl = min(pl.h[levelL], pr.h[levelL]);
+    const bool inside = ily >= 0 && ily <= hl - 11 && ilx >= 0 && ilx <= wl - 11 && iur >= 10 && iur <= wl - 11;
+    if (inside && !(iniu < 0 || endu >= (float)pr.w[levelL])) {
       const uint8_t *PL = pl.lvl[levelL], *PR = pr.lvl[levelL];
       const int pL = pl.pitch[levelL], pR = pr.pitch[levelL];
       // this lane's pixels of the 11x11 window: p = lane and lane + 64

@@ -1412,6 +1412,24 @@ static int stereo_median_cut(const int *sad, int n_l, float *u_right, float *dep
   return kept;
 }
 
+// What k_stereo indexes without a test: sp.scale[] / PyrView::lvl[] by every keypoint's octave, and the right pyramid by the
+// LEFT keypoint's level.  An octave outside [0, nlevels) of the left extractor, or a right extractor whose levels are not the
+// left one's, is refused by every entry point before anything is enqueued.
+static bool stereo_octaves_within(const vsg_keypoint *k, int n, int nlevels) {
+  for (int i = 0; i < n; i++)
+    if (k[i].octave < 0 || k[i].octave >= nlevels) return false;
+  return true;
+}
+static int stereo_check(const vsg_orb *hl, const vsg_orb *hr, const vsg_keypoint *kl, int n_l, const vsg_keypoint *kr,
+                        int n_r) {
+  const FrameGeom &gl = hl->G.fg, &gr = hr->G.fg;
+  if (hl->T.nlevels != hr->T.nlevels || gl.nlevels != gr.nlevels || gl.nlevels != hl->T.nlevels) return VSG_ERR_INVALID;
+  for (int l = 0; l < gl.nlevels; l++)
+    if (gl.lv[l].w != gr.lv[l].w || gl.lv[l].h != gr.lv[l].h) return VSG_ERR_INVALID;
+  if (!stereo_octaves_within(kl, n_l, hl->T.nlevels) || !stereo_octaves_within(kr, n_r, hl->T.nlevels)) return VSG_ERR_INVALID;
+  return VSG_OK;
+}
+
 // Frame::ComputeStereoMatches on device-resident keypoints / descriptors: one launch on the calling thread's stream,
 // results through its pinned arena.  d_kps* / d_desc* are device pointers.  Two halves (round 6): enqueue, and -- after the
 // stream has been waited for, possibly together with other work of the same Frame -- the copy-out and the median cut.
@@ -1458,7 +1476,12 @@ int vsg_stereo_matches(vsg_orb *hl, int frame_l, vsg_orb *hr, int frame_r, const
   if (!hl || !hr || !u_right || !depth || n_l < 0 || n_r < 0 || hl->device != hr->device) return VSG_ERR_INVALID;
   for (int i = 0; i < n_l; i++) u_right[i] = -1.0f, depth[i] = -1.0f;
   if (n_l == 0 || n_r == 0) return 0;
-  int rc = VSG_OK;
+  if (!kps_l || !kps_r || !desc_l || !desc_r) return VSG_ERR_INVALID;
+  PyrView pv;
+  int rc = pyr_view(hl, frame_l, pv);
+  if (rc == VSG_OK) rc = pyr_view(hr, frame_r, pv);
+  if (rc == VSG_OK) rc = stereo_check(hl, hr, kps_l, n_l, kps_r, n_r);
+  if (rc != VSG_OK) return rc;  // refused before the upload below is enqueued
   ThreadCtx *c = thread_ctx(hl->device, &rc);
   if (!c) return rc;
   // keypoints and descriptors of both eyes go up through the pinned arena (one DMA into the device arena)
@@ -1486,7 +1509,9 @@ int vsg_frame_stereo_matches(vsg_orb *hl, int frame_l, vsg_orb *hr, int frame_r,
   const int n_l = fl->n, n_r = fr->n;
   for (int i = 0; i < n_l; i++) u_right[i] = -1.0f, depth[i] = -1.0f;
   if (n_l == 0 || n_r == 0) return 0;
-  int rc = VSG_OK;
+  if ((int)fl->h_kps.size() != n_l || (int)fr->h_kps.size() != n_r) return VSG_ERR_INVALID;
+  int rc = stereo_check(hl, hr, fl->h_kps.data(), n_l, fr->h_kps.data(), n_r);  // on the frames' host mirrors
+  if (rc != VSG_OK) return rc;
   ThreadCtx *c = thread_ctx(hl->device, &rc);
   if (!c) return rc;
   rc = ctx_reserve(c, 12 * (size_t)n_l + 64, 0);
@@ -1516,6 +1541,14 @@ int vsg_frame_stereo_bow_search(vsg_orb *hl, int frame_l, vsg_orb *hr, int frame
   *n_stereo = 0;
   if (n_match) *n_match = 0;
   int rc = VSG_OK;
+  if (n_l > 0 && n_r > 0) {  // the stereo half runs: its refusals, on the frames' host mirrors
+    if ((int)fl->h_kps.size() != n_l || (int)fr->h_kps.size() != n_r) return VSG_ERR_INVALID;
+    PyrView pv;
+    rc = pyr_view(hl, frame_l, pv);
+    if (rc == VSG_OK) rc = pyr_view(hr, frame_r, pv);
+    if (rc == VSG_OK) rc = stereo_check(hl, hr, fl->h_kps.data(), n_l, fr->h_kps.data(), n_r);
+    if (rc != VSG_OK) return rc;
+  }
   ThreadCtx *c = thread_ctx(hl->device, &rc);
   if (!c) return rc;
   // one arena layout for the three calls, reserved BEFORE anything is enqueued (growing an arena frees the old one)
