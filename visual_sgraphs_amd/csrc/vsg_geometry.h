@@ -99,7 +99,7 @@ struct PyrTiling {
   std::vector<Short4> tab;
   int ldsA = 0, ldsB = 0;  // LDS bytes for even / odd levels of the ping-pong
   int tabMax = 0;          // max over tiles of staged table entries
-  bool ok = false;         // usable by k_pyramid (16-bit LDS row offsets, column span)
+  bool ok = false;         // usable by k_pyramid (16-bit LDS row offsets, column span, weight ranges)
   int lds_bytes() const { return ((ldsA + 15) & ~15) + ((ldsB + 15) & ~15) + 8 * (tabMax + 1); }
 };
 
@@ -288,6 +288,14 @@ inline int build_geometry(Geometry &G, const ExtractorTables &T, int rows, int c
       const int x3 = x + 3 < D.w ? x + 3 : D.w - 1;
       if (tabx[x3].a - tabx[x].a > 6) spanOk = false;
     }
+    // Operand ranges of its row loop: the x weights are kept times 16 in 16 bits and a horizontal sum times 4096 in 32
+    // (weights <= 2048 with a0 + a1 <= 2049 keep S <= 255 * 2049 < 2^19), the y weights are 16-bit multiply-add operands
+    // whose sum of two products (+ rounding) stays below 2^28; every table resize_axis_table makes is inside.
+    const Short4 *taby = &G.resizeTab[D.tab_y_off];
+    for (int x = 0; x < D.w; x++)
+      if (tabx[x].b < 0 || tabx[x].b > 2048 || tabx[x].c < 0 || tabx[x].c > 2048 || tabx[x].b + tabx[x].c > 2049) spanOk = false;
+    for (int y = 0; y < D.h; y++)
+      if (taby[y].c < 0 || taby[y].c > 2048 || taby[y].d < 0 || taby[y].d > 2048) spanOk = false;
   }
   for (int ti = 0; ti < kPyrTilings; ti++) {
     PyrTiling &PT = G.pyr[ti];

@@ -185,6 +185,9 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
     //    (sx, sx+1) byte pair of each column is picked with a per-thread v_perm selector; the horizontal 11-bit
     //    interpolation of a pair is then ONE v_dot2_u32_u16 (weights a0 | a1 << 16).  Where the reference clamps
     //    sx1 to sx (image edge) its weight a1 is 0, so reading sx + 1 instead changes nothing.
+    //    The selector puts each pixel into the HIGH byte of its 16-bit half (p << 8) and the weights are kept times 16
+    //    (<= 32768: vsg_geometry.h checks the range), so the dot product is S << 12 (< 2^31) and the reference's
+    //    truncated S >> 4 is its high half as it lies -- the vertical pass reads that half, nothing shifts it.
     //  * consecutive destination rows share a source row 5 times out of 6 (scale 1.2): the horizontal sums of the
     //    lower row are kept in registers and reused as the upper row of the next destination row.
     //  * the dword goes to the LDS image (source of the next level) and, where this tile OWNS it, straight to HBM.
@@ -209,22 +212,19 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
         const Short4 tx = {(int16_t)(tw.x & 0xFFFFu), (int16_t)(tw.x >> 16), (int16_t)(tw.y & 0xFFFFu), 0};
         if (k == 0) o = tx.a;
         const uint32_t f = (uint32_t)(tx.a - o);  // 0..6 (vsg_geometry.h checks the span)
-        sel[k] = f | (0x0Cu << 8) | ((f + 1) << 16) | (0x0Cu << 24);
-        wgt[k] = (u16x2){(unsigned short)tx.b, (unsigned short)tx.c};
+        sel[k] = 0x0Cu | (f << 8) | (0x0Cu << 16) | ((f + 1) << 24);
+        wgt[k] = (u16x2){(unsigned short)(tx.b << 4), (unsigned short)(tx.c << 4)};
       }
       const uint8_t *swin = src + (o & ~3);
       const uint32_t sh = (uint32_t)(o & 3);
-      auto hrow = [&](int off, uint32_t (&H)[4]) {
+      auto hrow = [&](uint32_t off, uint32_t (&H)[4]) {
         const uint32_t *q = (const uint32_t *)(swin + off);
         const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
         const uint32_t A = __builtin_amdgcn_alignbyte(w1, w0, sh), B = __builtin_amdgcn_alignbyte(w2, w1, sh);
 #pragma unroll
         for (int k = 0; k < 4; k++)
         {
-          H[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(B, A, sel[k])), wgt[k], 0u,
-                                        false) >> 4;
-          asm volatile("" : "+v"(H[k]));  // the shifted sum is THE value: otherwise the compiler carries the un-shifted one
-                                          // across rows and shifts it again where it is reused
+          H[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(B, A, sel[k])), wgt[k], 0u, false);
         }
       };
       // ownership of this column group: all 4 bytes, some (a seam between tiles), or none
@@ -234,52 +234,76 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
       // Two destination rows per trip with the roles of the two horizontal-sum sets swapped (the lower source row of one
       // destination row is the upper one of the next 5 times out of 6: no register copies), the next row's table entry
       // requested before the current row is worked on, and the lower row's sums formed unconditionally (where the
-      // reference clamps sy + 1 to sy the same row is summed twice: same value).  Ownership as one unsigned range test
-      // per row, the level's address as a uniform base + a 32-bit lane offset.
+      // reference clamps sy + 1 to sy the same row is summed twice: same value).
+      // Per row nothing is recomputed that can be carried: the LDS and the HBM store offsets are bumped in place (opaque
+      // to the compiler, which otherwise splits each into a row part and a column part and adds them again per row), the
+      // rows left count down, and the ROW ownership test is the range check of a buffer descriptor that covers exactly
+      // the owned rows of the level -- a store to a row above or below them has an offset outside [0, num_records) (a
+      // negative one wraps to a large unsigned one) and is dropped by the address unit.  (Rows the tile does not own hold
+      // the bytes their owner writes, so the check only saves the traffic.)
       uint32_t HA[4] = {0, 0, 0, 0}, HB[4];
-      int offc = -1;  // LDS row offset whose horizontal sums are cached (in the set that is "upper" next)
-      uint8_t *drow = dst + ya * dpitch + 4 * cg;
-      uint8_t *gbase = frame_base + D.img_off;
-      uint32_t goff = (uint32_t)((dy0 + ya) * D.pitch + gx);
+      typedef __attribute__((address_space(3))) uint32_t lds_u32;
+      uint32_t doff = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)dst +
+                      (uint32_t)(ya * dpitch + 4 * cg);  // LDS address of this row's dword
       const uint32_t gpitch = (uint32_t)D.pitch;
-      const int own_lo = oy0 - dy0;
-      const uint32_t own_n = (uint32_t)max(oy1 - oy0, 0);
-      auto emit = [&](int y, const Short4 &ty, const uint32_t (&H0)[4], const uint32_t (&H1)[4]) {
-        uint32_t out = 0;
+      const int own_rows = max(oy1 - oy0, 0);
+      const __amdgpu_buffer_rsrc_t own_img = __builtin_amdgcn_make_buffer_rsrc(
+          frame_base + D.img_off + (size_t)oy0 * gpitch, 0, own_rows * (int)gpitch, 0x00020000);
+      uint32_t goff = (uint32_t)((dy0 + ya - oy0) * (int)gpitch + gx);  // offset in the owned rows' image
+      // Vertical pass of one destination row from the horizontal sums of its two source rows (H = S >> 4, the high halves):
+      //   v = (((b0 * H0) >> 16) + ((b1 * H1) >> 16) + 2) >> 2            ([OCV] resize.cpp, VResizeLinear 8U)
+      // The two products are truncated SEPARATELY.  With P0 = b0 * H0 + (2 << 16) and its low 16 bits cleared,
+      //   Q = b1 * H1 + (P0 & 0xFFFF0000)   has   Q >> 16 = (b0 * H0 >> 16) + (b1 * H1 >> 16) + 2   exactly
+      // (what is added to b1 * H1 is a multiple of 2^16; all of it < 2^28): two multiply-adds that read the weights as the
+      // 16-bit halves of the table word where it lies and one full-rate AND per pixel.  The sums of pixels (0, 2) and
+      // (1, 3) are then byte-picked into the halves of one dword each (each <= 1023: the result is a byte), shifted
+      // together, and the four bytes picked into the output dword.
+      const uint32_t kRound = 2u << 16;
+      auto emit = [&](uint32_t wy, const uint32_t (&H0)[4], const uint32_t (&H1)[4]) {
+        uint32_t Q[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-          const uint32_t v = ((__umul24((uint32_t)ty.c, H0[k]) >> 16) + (__umul24((uint32_t)ty.d, H1[k]) >> 16) + 2u) >> 2;
-          out |= v << (8 * k);
+          uint32_t p;
+          asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[0,1,0,0]" : "=v"(p) : "v"(wy), "v"(H0[k]), "v"(kRound));
+          p &= 0xFFFF0000u;
+          asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,1,0,0]" : "=v"(Q[k]) : "v"(wy), "v"(H1[k]), "v"(p));
         }
-        *(uint32_t *)drow = out;
-        if ((uint32_t)(y - own_lo) < own_n) {
-          if (full) {
-            *(uint32_t *)(gbase + goff) = out;
-          } else if (part) {
+        const uint32_t t = __builtin_amdgcn_perm(Q[2], Q[0], 0x07060302u), u = __builtin_amdgcn_perm(Q[3], Q[1], 0x07060302u);
+        const uint32_t out = __builtin_amdgcn_perm(u >> 2, t >> 2, 0x06020400u);
+        *(lds_u32 *)(uintptr_t)doff = out;
+        if (full) {
+          __builtin_amdgcn_raw_buffer_store_b32(out, own_img, (int)goff, 0, 0);
+        } else if (part) {
 #pragma unroll
-            for (int j = 0; j < 4; j++)
-              if (gx + j >= ox0 && gx + j < ox1) gbase[goff + j] = (uint8_t)(out >> (8 * j));
-          }
+          for (int j = 0; j < 4; j++)
+            if (gx + j >= ox0 && gx + j < ox1)
+              __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(out >> (8 * j)), own_img, (int)goff + j, 0, 0);
         }
-        drow += dpitch;
+        doff += (uint32_t)dpitch;
         goff += gpitch;
+        asm volatile("" : "+v"(doff), "+v"(goff));
       };
+      // A y entry is {LDS offset of the upper source row, of the lower one} | {b0, b1}, 16 bits each; the offset whose sums
+      // are cached (in the set that is "upper" next) is the high half of the previous entry's first word.
       // (the entry after a chunk's last row is read and not used: within the table, or the one entry of padding the
       // launch allocates after it)
-      const Short4 *typ = tyv + ya;
-      Short4 ty = typ[0];
-      for (int y = ya; y < yb; y += 2, typ += 2) {
-        const Short4 ty1 = typ[1];
-        if (ty.a != offc) hrow(ty.a, HA);
-        hrow(ty.b, HB);
-        emit(y, ty, HA, HB);
-        offc = ty.b;
-        if (y + 1 >= yb) break;
-        ty = typ[2];
-        if (ty1.a != offc) hrow(ty1.a, HB);
-        hrow(ty1.b, HA);
-        emit(y + 1, ty1, HB, HA);
-        offc = ty1.b;
+      const uint2 *typ = (const uint2 *)(tyv + ya);
+      uint2 e0 = typ[0];
+      uint2 e1 = {0xFFFFFFFFu, 0};  // no row offset is 0xFFFF
+      for (int n = yb - ya;; typ += 2) {
+        const bool up0 = (e0.x & 0xFFFFu) != (e1.x >> 16);
+        e1 = typ[1];
+        if (up0) hrow(e0.x & 0xFFFFu, HA);
+        hrow(e0.x >> 16, HB);
+        emit(e0.y, HA, HB);
+        if (n < 2) break;
+        const bool up1 = (e1.x & 0xFFFFu) != (e0.x >> 16);
+        e0 = typ[2];
+        if (up1) hrow(e1.x & 0xFFFFu, HB);
+        hrow(e1.x >> 16, HA);
+        emit(e1.y, HB, HA);
+        n -= 2;
+        if (n <= 0) break;
       }
     }
     __syncthreads();
