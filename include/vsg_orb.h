@@ -181,7 +181,14 @@ int vsg_hamming_block_best2_device(int device, const uint8_t *d_a, const uint8_t
 /* int ORBmatcher::SearchByBoW(KeyFrame *pKF, Frame &F, vpMapPointMatches) (ORBmatcher.h:64,
  * ORBmatcher.cc:226-428), F.Nleft == -1.  FeatureVectors (DBoW2 std::map<NodeId, vector<unsigned>>)
  * are CSR: node ids ascending, offsets[nodes+1], indices.  kf_valid[i] = (pMP && !pMP->isBad()).
- * match_f[i] = KF feature index whose MapPoint F feature i received, or -1.  Returns nmatches. */
+ * match_f[i] = KF feature index whose MapPoint F feature i received, or -1.  Returns nmatches.
+ * Checked before anything is enqueued, in this and in every other call that takes FeatureVectors as host arrays
+ * (vsg_search_by_bow_*, vsg_search_for_triangulation and their vsg_frame_* forms): a NULL output; NULL descriptors, angles
+ * or flags of a side with n > 0; and per FeatureVector with nodes > 0 a NULL array, node ids that do not strictly ascend,
+ * offsets that do not ascend from 0 or an idx outside [0, n): VSG_ERR_INVALID, and the output is not written.  These checks
+ * come before the device is looked at: on a machine without a device a bad argument reports VSG_ERR_INVALID, not
+ * VSG_ERR_NO_DEVICE.  A feature listed under two nodes is NOT detected and stays the caller's contract (a DBoW2
+ * FeatureVector cannot hold one). */
 int vsg_search_by_bow_kf_f(int device, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_valid,
                            int n_kf, const int32_t *kf_node_id, const int32_t *kf_off, const int32_t *kf_idx,
                            int kf_nodes, const uint8_t *f_desc, const float *f_angle, int n_f,
@@ -192,7 +199,7 @@ int vsg_search_by_bow_kf_f(int device, const uint8_t *kf_desc, const float *kf_a
  * from the left camera, [f_nleft, n_f) from the right (descriptors vconcat'ed, Frame.cc:296).  Left and right
  * candidates keep separate best / second-best pairs; the right best is accepted at dist <= TH_LOW without a ratio
  * test, but only when the left best also is <= TH_LOW (the reference nests the block).  f_nleft = -1 is the call
- * above. */
+ * above.  Checked before anything is enqueued: as above, and f_nleft outside [-1, n_f]: VSG_ERR_INVALID. */
 int vsg_search_by_bow_kf_f_stereo(int device, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_valid,
                                   int n_kf, const int32_t *kf_node_id, const int32_t *kf_off, const int32_t *kf_idx,
                                   int kf_nodes, const uint8_t *f_desc, const float *f_angle, int n_f, int f_nleft,
@@ -200,7 +207,8 @@ int vsg_search_by_bow_kf_f_stereo(int device, const uint8_t *kf_desc, const floa
                                   float nnratio, int check_orientation, int32_t *match_f);
 
 /* int ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12) (ORBmatcher.h:65,
- * ORBmatcher.cc:758-900), NLeft == -1.  matches12[idx1] = idx2 or -1. */
+ * ORBmatcher.cc:758-900), NLeft == -1.  matches12[idx1] = idx2 or -1.  Checked before anything is enqueued: as for
+ * vsg_search_by_bow_kf_f, with the flags of both sides: VSG_ERR_INVALID. */
 int vsg_search_by_bow_kf_kf(int device, const uint8_t *desc1, const float *angle1, const uint8_t *valid1, int n1,
                             const int32_t *node_id1, const int32_t *off1, const int32_t *idx1, int nodes1,
                             const uint8_t *desc2, const float *angle2, const uint8_t *valid2, int n2,
@@ -216,7 +224,10 @@ int vsg_search_by_bow_kf_kf(int device, const uint8_t *desc1, const float *angle
  * pair_off has (shared nodes + 1) entries; pair_ok == NULL means every pair passes.  Among the passing candidates
  * with dist <= TH_LOW the smallest distance wins, the LATER one on ties (`dist > bestDist` skips, :1015).
  * matches12[idx1] = idx2 or -1 (vMatchedPairs = the non-negative entries in index order).  Returns nmatches after
- * the rotation-histogram filter. */
+ * the rotation-histogram filter.  Checked before anything is enqueued: as for vsg_search_by_bow_kf_kf, and pair_ok without
+ * pair_off, pair_off[0] < 0, or a shared node s whose range pair_off[s + 1] - pair_off[s] holds fewer than n1(s) * n2(s)
+ * bits (so a node whose bit count does not fit the int32 offsets): VSG_ERR_INVALID.  pair_ok is read up to word
+ * (pair_off[shared nodes] + 31) / 32, exclusive. */
 int vsg_search_for_triangulation(int device, const uint8_t *desc1, const float *angle1, const uint8_t *eligible1,
                                  int n1, const int32_t *node_id1, const int32_t *off1, const int32_t *idx1, int nodes1,
                                  const uint8_t *desc2, const float *angle2, const uint8_t *eligible2, int n2,
@@ -757,7 +768,10 @@ int vsg_frame_search_for_initialization(vsg_frame *f1, vsg_frame *f2, const floa
  * ComputeBoW with an empty vocabulary, gives 0 matches and every output -1, as in the reference; otherwise
  * VSG_ERR_INVALID when either frame never had its ComputeBoW since its features were last written (nothing is left
  * running on the calling thread's stream when this or any other error is returned).  The flag and match arrays of an empty
- * frame may be NULL. */
+ * frame may be NULL.  Checked before anything is enqueued: NULL handles, inputs or outputs, frames on different devices, only
+ * SOME of the FeatureVector arrays NULL, and in the host-FeatureVector form what vsg_search_by_bow_kf_f checks of a
+ * FeatureVector (node ids that do not strictly ascend, offsets that do not ascend from 0, an idx outside [0, n)):
+ * VSG_ERR_INVALID. */
 int vsg_frame_search_by_bow_kf_f(vsg_frame *kf, const uint8_t *kf_valid, const int32_t *kf_node_id,
                                  const int32_t *kf_off, const int32_t *kf_idx, int kf_nodes, vsg_frame *f,
                                  const int32_t *f_node_id, const int32_t *f_off, const int32_t *f_idx, int f_nodes,
@@ -769,7 +783,9 @@ int vsg_frame_search_by_bow_kf_kf(vsg_frame *kf1, const uint8_t *valid1, const i
 /* SearchForTriangulation(KeyFrame*, KeyFrame*, ...) (ORBmatcher.cc:902-1146) with both KeyFrames resident (LocalMapping::
  * CreateNewMapPoints calls it for the current keyframe against each of its 10-20 best covisible neighbours,
  * LocalMapping.cc:389: the current keyframe's descriptors go up once, not once per neighbour).  Arguments and result as
- * vsg_search_for_triangulation; angles come from the frames' host mirrors. */
+ * vsg_search_for_triangulation; angles come from the frames' host mirrors.  Checked before anything is enqueued: NULL
+ * handles, flags or output, frames on different devices, and what vsg_search_for_triangulation checks of the FeatureVectors
+ * and of pair_ok / pair_off: VSG_ERR_INVALID. */
 int vsg_frame_search_for_triangulation(vsg_frame *kf1, const uint8_t *eligible1, const int32_t *node_id1,
                                        const int32_t *off1, const int32_t *idx1, int nodes1, vsg_frame *kf2,
                                        const uint8_t *eligible2, const int32_t *node_id2, const int32_t *off2,
@@ -797,8 +813,8 @@ int vsg_frame_search_for_triangulation(vsg_frame *kf1, const uint8_t *eligible1,
  * rotation-histogram filter) are those of vsg_frame_search_for_triangulation given eligible = no_mp (&& stereo under
  * bOnlyStereo) and the bitmask of this predicate.  Checked before anything is enqueued: NULL handles, inputs or outputs,
  * frames on different devices, nlevels outside 1..16, a keypoint of kf2 whose octave lies outside [0, nlevels), only SOME of
- * the FeatureVector arrays NULL, and in the host-FeatureVector form offsets that do not ascend from 0 or an idx outside
- * [0, n): VSG_ERR_INVALID; a frame with Nleft != -1 (mpCamera2: :929-937, :1033-1071): VSG_ERR_UNSUPPORTED.  An error after
+ * the FeatureVector arrays NULL, and in the host-FeatureVector form node ids that do not strictly ascend, offsets that do not
+ * ascend from 0 or an idx outside [0, n): VSG_ERR_INVALID; a frame with Nleft != -1 (mpCamera2: :929-937, :1033-1071): VSG_ERR_UNSUPPORTED.  An error after
  * the enqueue waits for the stream before it returns. */
 int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *no_mp1, const int32_t *node_id1,
                                                 const int32_t *off1, const int32_t *idx1, int nodes1, vsg_frame *kf2,

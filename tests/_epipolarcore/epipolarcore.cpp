@@ -1,5 +1,5 @@
 // Host build of the epipolar predicate of SearchForTriangulation (vsg_epipolar.h), for tests/test_epipolar_reference.py:
-// the same source k_triangulation_epipolar compiles, against the NumPy restatement.
+// the same source k_triangulation_walk<EpipolarPred> compiles, against the NumPy restatement.
 #include "vsg_epipolar.h"
 
 extern "C" {

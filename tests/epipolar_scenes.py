@@ -22,7 +22,7 @@ from visual_sgraphs_amd import synth
 F32 = np.float32
 W, H, SHIFT = 320, 240, (-3.0, -2.0)
 BOUNDS = (0.0, 0.0, float(W), float(H))
-TILE = 128  # kEpiTile = kEpiRows of k_triangulation_epipolar
+TILE = 128  # kEpiTile = kEpiRows of k_triangulation_walk
 
 
 def fundamental_sideways(f, cx, cy, t):

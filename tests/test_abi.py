@@ -139,3 +139,51 @@ def test_stream_to_rank_honours_more_ranks_than_streams():
     # a world that is not a multiple of the stream count: the spare ranks share the first streams
     ranks = {sharding.stream_to_rank(s, 4, 6, f) for s in range(4) for f in range(4)}
     assert ranks == set(range(6))
+
+
+def _bad_feature_vectors(n):
+    """(name, FeatureVector) of a frame of n features: an idx that holds n, and offsets that descend."""
+    ids, off = np.array([2, 5, 9], np.int32), np.array([0, 3, 6, 8], np.int32)
+    idx = np.arange(8, dtype=np.int32)
+    bad_idx = idx.copy()
+    bad_idx[4] = n
+    bad_off = off.copy()
+    bad_off[1] = 7
+    return (ids, off, idx), [("idx_holds_n", (ids, off, bad_idx)), ("offsets_descend", (ids, bad_off, idx))]
+
+
+def test_bad_feature_vectors_are_refused_before_the_device_is_touched(lib):
+    """VSG_ERR_INVALID (-6), not VSG_ERR_NO_DEVICE, on a machine without a device, and the output array as it was: the
+    FeatureVector and predicate-bit checks of csrc/vsg_fv.h run before thread_ctx, before anything is enqueued and before the
+    output is written.  With a device present the same calls are refused the same way."""
+    from visual_sgraphs_amd import orb
+    p, n = orb._p, 10
+    desc, angle, flags = np.zeros((n, 32), np.uint8), np.zeros(n, np.float32), np.ones(n, np.uint8)
+    good, bad = _bad_feature_vectors(n)
+    side = lambda fv, with_flags=True: ([p(desc, orb._u8p), p(angle, orb._f32p)] + ([p(flags, orb._u8p)] if with_flags else []) +
+                                        [n] + [p(a, orb._i32p) for a in fv] + [len(fv[0])])
+    exact = np.array([0, 9, 18, 22], np.int32)      # the three shared nodes hold 3 x 3, 3 x 3 and 2 x 2 pairs
+    short = exact - np.array([0, 0, 0, 1], np.int32)
+    bits = np.full(2, 0xFFFFFFFF, np.uint32)
+    calls = []
+    for name, fv in bad:
+        for where in (0, 1):
+            a, b = (fv, good) if where == 0 else (good, fv)
+            calls.append((name, "vsg_search_by_bow_kf_f_stereo",
+                          lambda out, a=a, b=b: [0] + side(a) + side(b, False)[:3] + [-1] + side(b, False)[3:] + [0.7, 1, out]))
+            calls.append((name, "vsg_search_by_bow_kf_kf", lambda out, a=a, b=b: [0] + side(a) + side(b) + [0.7, 1, out]))
+            calls.append((name, "vsg_search_for_triangulation",
+                          lambda out, a=a, b=b: [0] + side(a) + side(b) + [bits.ctypes.data, exact.ctypes.data, 1, out]))
+    calls.append(("pair_off_one_bit_short", "vsg_search_for_triangulation",
+                  lambda out: [0] + side(good) + side(good) + [bits.ctypes.data, short.ctypes.data, 1, out]))
+    assert len(calls) == 13
+    for name, fn, args in calls:
+        out = np.full(n, 12345, np.int32)
+        assert getattr(lib, fn)(*args(p(out, orb._i32p))) == -6, (fn, name)
+        assert (out == 12345).all(), (fn, name)
+    if lib.vsg_device_count() <= 0:   # the same calls with valid arguments get as far as the device
+        for fn, args in (("vsg_search_by_bow_kf_kf", lambda out: [0] + side(good) + side(good) + [0.7, 1, out]),
+                         ("vsg_search_for_triangulation",
+                          lambda out: [0] + side(good) + side(good) + [bits.ctypes.data, exact.ctypes.data, 1, out])):
+            out = np.full(n, 12345, np.int32)
+            assert getattr(lib, fn)(*args(p(out, orb._i32p))) == -4 and (out == 12345).all(), fn

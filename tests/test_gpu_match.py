@@ -521,3 +521,122 @@ def test_search_by_bow_kf_f_fisheye_stereo(frames, seed, n_nodes, ratio, ori):
     n_m, got_m = m.SearchByBoW_KF_F(d0, k0["angle"], kf_valid, kf_fv, f_desc, f_angle, f_fv)
     n_w, want_m = ol.search_by_bow_kf_f(d0, k0["angle"], kf_valid, kf_fv, f_desc, f_angle, f_fv, ratio, ori)
     assert n_m == n_w and np.array_equal(got_m, want_m) and not np.array_equal(want_m, want)
+
+
+# ---- the vocabulary-node searches on FeatureVectors given as host arrays: what they refuse, and the caller-bits walk of
+# SearchForTriangulation at its tile edges
+NODE_FORMS = ["frame_kf_f", "frame_kf_kf", "frame_triangulation", "host_kf_f", "host_kf_kf", "host_triangulation"]
+
+
+@pytest.fixture(scope="module")
+def node_scene():
+    """Two uploaded frames of about 300 features (the parity scene of tests/epipolar_scenes.py) with FeatureVectors of 8
+    nodes: a KF1 feature lies in the node of its true correspondence, so every search finds matches."""
+    import epipolar_scenes as es
+    s = dict(es.frames())
+    rng = np.random.default_rng(77)
+    n1, n2 = len(s["k1"]), len(s["k2"])
+    node2 = rng.integers(0, 8, n2)
+    node1 = np.where(s["match"] >= 0, node2[np.maximum(s["match"], 0)], rng.integers(0, 8, n1))
+    fv = lambda node: es._fv({int(i) * 5 + 2: np.flatnonzero(node == i).astype(np.int32) for i in range(8)})
+    s["fv1"], s["fv2"] = fv(node1), fv(node2)
+    assert len(s["fv1"][0]) == len(s["fv2"][0]) == 8 and 200 <= n1 <= 400 and 200 <= n2 <= 400
+    s["F1"] = orb.Frame(n1 + 1).upload(s["k1"], s["d1"], es.BOUNDS)
+    s["F2"] = orb.Frame(n2 + 1).upload(s["k2"], s["d2"], es.BOUNDS)
+    s["v1"], s["v2"] = (rng.random(n1) > 0.2).astype(np.uint8), (rng.random(n2) > 0.2).astype(np.uint8)
+    s["bits"] = shared_pair_bits(s["fv1"], s["fv2"], rng, 0.7)
+    return s
+
+
+def _node_search(form, s, fv1, fv2, pair_off=None):
+    """The raw call of one form: (return code, output array pre-filled with 12345).  An entry of fv1 / fv2 may be None."""
+    L = orb.load_library()
+    p = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    n1, n2 = len(s["k1"]), len(s["k2"])
+    a1, a2 = np.ascontiguousarray(s["k1"]["angle"]), np.ascontiguousarray(s["k2"]["angle"])
+    u8, f32, i32 = orb._u8p, orb._f32p, orb._i32p
+    fa, fb = [p(x, i32) for x in fv1] + [8], [p(x, i32) for x in fv2] + [8]
+    ok, off = s["bits"][0], s["bits"][1] if pair_off is None else pair_off
+    out = np.full(n2 if form.endswith("kf_f") else n1, 12345, np.int32)
+    tail = [0.7, 1, p(out, i32)]
+    tri = [ok.ctypes.data, off.ctypes.data, 1, p(out, i32)]
+    h1, h2 = [p(s["d1"], u8), p(a1, f32), p(s["v1"], u8), n1], [p(s["d2"], u8), p(a2, f32), p(s["v2"], u8), n2]
+    if form == "frame_kf_f":
+        rc = L.vsg_frame_search_by_bow_kf_f(s["F1"].handle, p(s["v1"], u8), *fa, s["F2"].handle, *fb, *tail)
+    elif form == "frame_kf_kf":
+        rc = L.vsg_frame_search_by_bow_kf_kf(s["F1"].handle, p(s["v1"], u8), *fa, s["F2"].handle, p(s["v2"], u8), *fb, *tail)
+    elif form == "frame_triangulation":
+        rc = L.vsg_frame_search_for_triangulation(s["F1"].handle, p(s["v1"], u8), *fa, s["F2"].handle, p(s["v2"], u8), *fb, *tri)
+    elif form == "host_kf_f":
+        rc = L.vsg_search_by_bow_kf_f_stereo(0, *h1, *fa, p(s["d2"], u8), p(a2, f32), n2, -1, *fb, *tail)
+    elif form == "host_kf_kf":
+        rc = L.vsg_search_by_bow_kf_kf(0, *h1, *fa, *h2, *fb, *tail)
+    else:
+        rc = L.vsg_search_for_triangulation(0, *h1, *fa, *h2, *fb, *tri)
+    return rc, out
+
+
+@pytest.mark.parametrize("form", NODE_FORMS)
+def test_node_searches_refuse_bad_feature_vectors_and_bits_then_equal_the_oracle(node_scene, form):
+    """idx outside [0, n), a descending offset, only some arrays NULL and (triangulation) a pair_off one bit short are
+    VSG_ERR_INVALID with the output untouched: none of them reaches the device.  The same call with valid arguments equals the
+    CPU oracle."""
+    s = node_scene
+    n1, n2 = len(s["k1"]), len(s["k2"])
+    (ids1, off1, idx1), (ids2, off2, idx2) = s["fv1"], s["fv2"]
+    bad = []
+    for v in (n1, -1, 1 << 30):
+        b = idx1.copy()
+        b[len(b) // 2] = v
+        bad.append(((ids1, off1, b), s["fv2"], None))
+    b = idx2.copy()
+    b[-1] = n2
+    bad.append((s["fv1"], (ids2, off2, b), None))
+    b = off1.copy()
+    b[2] = b[3] + 1
+    bad.append(((ids1, b, idx1), s["fv2"], None))
+    bad += [((ids1, None, idx1), s["fv2"], None), (s["fv1"], (ids2, off2, None), None), ((None, off1, idx1), s["fv2"], None)]
+    if form.endswith("triangulation"):
+        short = s["bits"][1].copy()
+        short[-1] -= 1
+        bad.append((s["fv1"], s["fv2"], short))
+    for fv1, fv2, pair_off in bad:
+        rc, out = _node_search(form, s, fv1, fv2, pair_off)
+        assert rc == -6 and (out == 12345).all()
+    rc, out = _node_search(form, s, s["fv1"], s["fv2"])
+    a1, a2 = s["k1"]["angle"], s["k2"]["angle"]
+    if form.endswith("kf_f"):
+        want = ol.search_by_bow_kf_f(s["d1"], a1, s["v1"], s["fv1"], s["d2"], a2, s["fv2"], 0.7, True)
+    elif form.endswith("kf_kf"):
+        want = ol.search_by_bow_kf_kf(s["d1"], a1, s["v1"], s["fv1"], s["d2"], a2, s["v2"], s["fv2"], 0.7, True)
+    else:
+        want = ol.search_for_triangulation(s["d1"], a1, s["v1"], s["fv1"], s["d2"], a2, s["v2"], s["fv2"], *s["bits"], True)
+    assert rc == want[0] > 10 and np.array_equal(out, want[1])
+
+
+@pytest.fixture(scope="module")
+def edge_frames():
+    import triangulation_edges as te
+    s = te.scene()
+    k1, k2 = te.keypoints(s["a1"], orb.KP_DTYPE), te.keypoints(s["a2"], orb.KP_DTYPE)
+    bounds = (0.0, 0.0, 640.0, 480.0)
+    return orb.Frame(len(k1)).upload(k1, s["d1"], bounds), orb.Frame(len(k2)).upload(k2, s["d2"], bounds)
+
+
+@pytest.mark.parametrize("flags", ["all_one", "every_third_zero"])
+@pytest.mark.parametrize("pattern", ["none", "ones", "zeros", "last_bit_of_every_node"])
+def test_search_for_triangulation_caller_bits_at_the_tile_edges(edge_frames, pattern, flags):
+    """Nodes of (1, 1) ... (257, 130) rows around the 128-row chunks and tiles of the walk, a tie across the tile edge, four
+    bit patterns, two flag settings (tests/triangulation_edges.py; the oracle's side is checked in
+    tests/test_triangulation_edges.py): host-descriptor and resident form equal the CPU oracle."""
+    import triangulation_edges as te
+    s = te.scene()
+    ok, off = te.pair_bits(pattern)
+    e1, e2 = s["flags"][flags]
+    want = ol.search_for_triangulation(s["d1"], s["a1"], e1, s["fv1"], s["d2"], s["a2"], e2, s["fv2"], ok, off, True)
+    te.check_counts(s, pattern, flags, *want)
+    host = orb.ORBmatcher(0.6, True).SearchForTriangulation(s["d1"], s["a1"], e1, s["fv1"], s["d2"], s["a2"], e2, s["fv2"], ok, off)
+    assert host[0] == want[0] and np.array_equal(host[1], want[1])
+    f1, f2 = edge_frames
+    res = f1.SearchForTriangulation(e1, s["fv1"], f2, e2, s["fv2"], True, ok, off)
+    assert res[0] == want[0] and np.array_equal(res[1], want[1])

@@ -1,5 +1,5 @@
 """SearchForTriangulation with the epipole gate and Pinhole::epipolarConstrain on the device
-(vsg_frame_search_for_triangulation_epipolar, k_triangulation_epipolar) on the parity scene of tests/epipolar_scenes.py: the
+(vsg_frame_search_for_triangulation_epipolar, k_triangulation_walk<EpipolarPred>) on the parity scene of tests/epipolar_scenes.py: the
 restatement's bitmask (tests/epipolar_reference.py) goes into the EXISTING CPU oracle of the triangulation search, and the new
 call -- and the existing resident call fed the same bits -- must return the oracle's matches12 and count.  The device
 predicate is compared pair by pair through vsg_debug_epipolar_pairs, on the scene's largest node and on the directed edge

@@ -1,7 +1,7 @@
 // vsg_epipolar.h -- the geometric predicate of ORBmatcher::SearchForTriangulation (ORBmatcher.cc:976-1073) for ONE pair of
 // keypoints (kp1 of pKF1, kp2 of pKF2), host and device from one source: the stereo test of `bOnlyStereo` (:976-980,
 // :1004-1008), the epipole distance gate (:1023-1031) and `bCoarse || Pinhole::epipolarConstrain` (:1073,
-// Pinhole.cpp:118-141).  k_triangulation_epipolar and k_epipolar_pairs (vsg_match.hip) run it on the device;
+// Pinhole.cpp:118-141).  k_triangulation_walk<EpipolarPred> and k_epipolar_pairs (vsg_match.hip) run it on the device;
 // tests/_epipolarcore, tests/_adaptor_triangulation and the latency probe's caller-side loop (tools/abi_latency.cpp)
 // compile it for the host.  As in vsg_frustum.h / vsg_project.h the order is fixed and nothing contracts: every operation
 // is one vsg::f* / vsg::d* call = one rounding.

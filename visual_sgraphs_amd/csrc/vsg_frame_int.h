@@ -60,6 +60,11 @@ struct FrameDev {
   float minX, minY, invW, invH;
 };
 FrameDev frame_dev(const vsg_frame *f);
+// the frame's resident FeatureVector as the node-search kernels take it (vsg_match.hip): hdr = {nodes, features listed}
+struct FvDev {
+  const int *hdr, *node, *off, *idx;
+};
+inline FvDev fv_dev(const vsg_frame *f) { return FvDev{f->d_fv_hdr, f->d_fv_node, f->d_fv_off, f->d_fv_idx}; }
 inline int frame_check(const vsg_frame *f) { return f && f->d_block ? VSG_OK : VSG_ERR_INVALID; }
 // a vsg_grid (include/vsg_orb.h) is a vsg_frame behind an opaque name
 inline vsg_frame *grid_frame(vsg_grid *g) { return (vsg_frame *)g; }

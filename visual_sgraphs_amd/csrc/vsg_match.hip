@@ -1,28 +1,31 @@
 // vsg_match.hip -- Hamming searches of ORBmatcher (orb_slam3/src/ORBmatcher.cc) on flattened POD views.
 //
-// Integer XOR + popcount work (v_xor_b32 / v_bcnt_u32_b32), no MFMA.  Distances are evaluated lane-parallel;
-// every greedy "already matched" decision of the reference stays ordered:
-//   * SearchByBoW: vocabulary nodes are independent (an F feature belongs to one node), so one wavefront per
-//     shared node walks that node's KF features in order, lanes over the node's F features;
-//   * SearchByProjection / SearchForInitialization: one wavefront walks the queries in order, lanes over the
-//     query's candidate list; the mutable state lives in global memory behind a wave-level fence.
+// Integer XOR + popcount work (v_xor_b32 / v_bcnt_u32_b32); the brute-force best / second-best scan alone runs on the
+// matrix cores (k_block_best2_mfma).
+//   * The vocabulary-node searches: nodes are independent (a feature belongs to one node), so a WORKGROUP takes one node both
+//     FeatureVectors have, joined on the host (vsg_fv.h, after its checks) or, for two resident ones, in the kernel
+//     (block_node).  k_search_by_bow keeps the reference's greedy "already matched" order inside a node as a fixed point over
+//     an LDS distance matrix; k_triangulation_walk has no greedy state and walks a node in LDS tiles, its pair predicate a
+//     template parameter (the epipolar test of vsg_epipolar.h computed in place, or bits the caller made).
+//   * The searches on candidate lists the CALLER made: every candidate's distance in one data-parallel pass (k_cand_dist),
+//     the ordered walk over the queries on the host (vsg_walks.h).  On resident frames: vsg_window.hip.
 // best / second-best follow the reference's strict '<' scan: packed keys (dist << 20 | scan position) make
-// "earliest candidate wins ties" a plain integer minimum.
+// "earliest candidate wins ties" a plain integer minimum (the triangulation walk inverts the position: later wins there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
-#include <string>
+#include <type_traits>
 #include <vector>
-
-#include <algorithm>
 
 #include "../../include/vsg_orb.h"
 #include "../../include/vsg_orb_debug_epipolar.h"
 #include "vsg_ctx.h"
 #include "vsg_epipolar.h"
 #include "vsg_frame_int.h"
+#include "vsg_fv.h"
 #include "vsg_math.h"
 #include "vsg_walks.h"
 
@@ -61,18 +64,6 @@ __device__ __forceinline__ void wave_best2(uint32_t &k1, uint32_t &k2) {
     const uint32_t o1 = __shfl_xor(k1, d), o2 = __shfl_xor(k2, d);
     merge2(k1, k2, o1, o2);
   }
-}
-// the same minimum over the DPP path (row shifts, then the row broadcasts; lanes without a source keep the identity): VALU
-// latency per step instead of an LDS round trip per __shfl_xor -- what the ordered walk of k_search_by_bow is made of
-__device__ __forceinline__ uint32_t wave_min_dpp(uint32_t v) {
-  const int I = -1;
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(I, (int)v, 0x111, 0xF, 0xF, false));  // row_shr:1
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(I, (int)v, 0x112, 0xF, 0xF, false));  // row_shr:2
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(I, (int)v, 0x114, 0xF, 0xF, false));  // row_shr:4
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(I, (int)v, 0x118, 0xF, 0xF, false));  // row_shr:8
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(I, (int)v, 0x142, 0xA, 0xF, false));  // row_bcast:15 -> rows 1, 3
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(I, (int)v, 0x143, 0xC, 0xF, false));  // row_bcast:31 -> rows 2, 3
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 __device__ __forceinline__ uint32_t wave_min(uint32_t k) {
 #pragma unroll
@@ -273,24 +264,45 @@ __global__ __launch_bounds__(256) void k_block_best2_mfma(const uint8_t *a_base,
   }
 }
 
-// ---- SearchByBoW: one wavefront per shared vocabulary node (node pairs merged on the host).
+// ---- the vocabulary-node searches: one WORKGROUP per node both FeatureVectors have.
+using vsg::FvDev;  // a FeatureVector resident on the device (vsg_frame_int.h: Frame::mFeatVec written by k_bow_assemble)
+using vsg::NodePair;
+
+// The node of this block, block-uniform; false: the block has none.  Joined on the host (pairs: block b takes pairs[b]), or
+// -- pairs == nullptr -- BOTH FeatureVectors are resident and the join of ORBmatcher.cc:247-405 happens here: block b takes
+// node b of A and looks the same id up in B's node list (a node is shared or it is not: the merge-join's lower_bound jumps
+// and this lookup name the same pairs; nodes are independent, their order is irrelevant).  idxA / idxB then become the
+// resident lists.
+__device__ __forceinline__ bool block_node(const NodePair *pairs, int npairs, const FvDev &fa, const FvDev &fb, NodePair &np,
+                                           const int *&idxA, const int *&idxB) {
+  const int node = blockIdx.x, tid = threadIdx.x;
+  if (pairs) {
+    if (node >= npairs) return false;
+    np = pairs[node];
+    return true;
+  }
+  // everything the join needs is requested at once (B's node list 256 entries at a time, whatever the headers say: the
+  // arrays hold capacity + 1 entries): ONE memory round trip in front of the offsets instead of a bisection's eight
+  __shared__ int s_pos;
+  const int nA_nodes = fa.hdr[0], nB_nodes = fb.hdr[0];
+  const int id = node < nA_nodes ? fa.node[node] : -1;
+  if (tid == 0) s_pos = -1;
+  __syncthreads();
+  for (int base = 0; base < nB_nodes; base += 256)  // block-uniform; one pass for the reference's ~100 nodes
+    if (base + tid < nB_nodes && fb.node[base + tid] == id) s_pos = base + tid;  // ids are unique: at most one writer
+  __syncthreads();
+  const int lo = s_pos;
+  if (node >= nA_nodes || lo < 0) return false;
+  np.a_begin = fa.off[node], np.a_end = fa.off[node + 1], np.b_begin = fb.off[lo], np.b_end = fb.off[lo + 1];
+  idxA = fa.idx, idxB = fb.idx;
+  return true;
+}
+
+// ---- SearchByBoW
 // mode 0: KF -> Frame  (ORBmatcher.cc:254-392): skip F features already in match_f; accept bestDist1 <= TH_LOW
 // mode 1: KF -> KF     (ORBmatcher.cc:790-864): skip vbMatched2 / invalid; accept bestDist1 <  TH_LOW
-struct NodePair {
-  int a_begin, a_end, b_begin, b_end;
-};
 enum { kBowNodeSide = 128 };  // nodes up to this many features a side are matched on a distance matrix in LDS
 
-// A FeatureVector resident on the device (vsg_frame: Frame::mFeatVec written by k_bow_assemble): hdr = {nodes, features}
-struct FvDev {
-  const int *hdr, *node, *off, *idx;
-};
-
-// One WORKGROUP per shared vocabulary node (round 6; rounds 1-5: one wavefront, whose ordered walk chained three dependent
-// global loads and a fence per KeyFrame feature -- 37 us per call, all of it the largest node's walk).
-//   * pairs == nullptr: BOTH FeatureVectors are resident and the join of ORBmatcher.cc:247-405 happens here -- block b takes
-//     node b of A and finds the same id in B's ascending node list by bisection (a node is shared or it is not: the
-//     merge-join's lower_bound jumps and this lookup name the same pairs; nodes are independent, their order is irrelevant).
 //   * The node's descriptors go to LDS once (na + nb rows, not na x nb row pairs), every distance of the node is computed
 //     from there in one sweep of all 256 lanes.
 //   * The ordered, greedy walk (a KeyFrame feature sees the claims of the ones BEFORE it) as a fixed point, one lane per
@@ -298,36 +310,18 @@ struct FvDev {
 //     By induction feature i is final from round i + 1 on, and a round that changes no decision is the walk's result
 //     (feature 0 never depended on anyone, feature 1 is consistent with feature 0's final claim, ...).  Conflicts between
 //     neighbours are rare, so a node settles in 2-4 rounds of ~nb LDS reads per lane instead of na dependent reductions.
-// matchA / matchB are WRITE-ONLY (pre-filled with -1 by whoever owns them: they may be pinned host memory); every feature
-// belongs to exactly one node, so a node's block is the only writer and the only reader of its claims.
+// `match` is WRITE-ONLY (pre-filled with -1 by whoever owns it: it may be pinned host memory); every feature belongs to
+// exactly one node, so a node's block is the only writer and the only reader of its claims.
 __global__ __launch_bounds__(256) void k_search_by_bow(const NodePair *pairs, int npairs, FvDev fa, FvDev fb,
                                                        const uint8_t *descA,
                                                        const uint8_t *validA, const int *idxA, const uint8_t *descB,
                                                        const uint8_t *validB, const int *idxB, float nnratio, int mode,
                                                        int nleftB /*mode0: F.Nleft or -1*/,
-                                                       int *matchA /*mode1: matches12*/, int *matchB /*mode0: match_f*/,
+                                                       int *match /*mode0: match_f [nB], mode1: matches12 [nA]*/,
                                                        int *claimB /*device scratch [nB]: large nodes only*/) {
-  const int node = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x, lane = tid & 63;
   NodePair np;
-  if (pairs) {
-    if (node >= npairs) return;
-    np = pairs[node];
-  } else {
-    // everything the join needs is requested at once (B's node list 256 entries at a time, whatever the headers say: the
-    // arrays hold capacity + 1 entries): ONE memory round trip in front of the offsets instead of a bisection's eight
-    __shared__ int s_pos;
-    const int nA_nodes = fa.hdr[0], nB_nodes = fb.hdr[0];
-    const int id = node < nA_nodes ? fa.node[node] : -1;
-    if (tid == 0) s_pos = -1;
-    __syncthreads();
-    for (int base = 0; base < nB_nodes; base += 256)  // block-uniform; one pass for the reference's ~100 nodes
-      if (base + tid < nB_nodes && fb.node[base + tid] == id) s_pos = base + tid;  // ids are unique: at most one writer
-    __syncthreads();
-    const int lo = s_pos;
-    if (node >= nA_nodes || lo < 0) return;
-    np.a_begin = fa.off[node], np.a_end = fa.off[node + 1], np.b_begin = fb.off[lo], np.b_end = fb.off[lo + 1];
-    idxA = fa.idx, idxB = fb.idx;
-  }
+  if (!block_node(pairs, npairs, fa, fb, np, idxA, idxB)) return;
   const int nb = np.b_end - np.b_begin, na = np.a_end - np.a_begin;
   __shared__ uint4 s_da[kBowNodeSide][2], s_db[kBowNodeSide][2];
   __shared__ uint16_t s_dist[kBowNodeSide * kBowNodeSide];
@@ -403,10 +397,10 @@ __global__ __launch_bounds__(256) void k_search_by_bow(const NodePair *pairs, in
     }
     if (active) {
       if (mode == 0) {
-        if (decL >= 0) matchB[s_rb[decL]] = ra;  // vpMapPointMatches[bestIdxF] = pMP
-        if (decR >= 0) matchB[s_rb[decR]] = ra;
+        if (decL >= 0) match[s_rb[decL]] = ra;  // vpMapPointMatches[bestIdxF] = pMP
+        if (decR >= 0) match[s_rb[decR]] = ra;
       } else if (decL >= 0) {
-        matchA[ra] = s_rb[decL];                 // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
+        match[ra] = s_rb[decL];                 // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
       }
     }
     return;
@@ -441,7 +435,7 @@ __global__ __launch_bounds__(256) void k_search_by_bow(const NodePair *pairs, in
       r1 = wave_min(r1);
       if ((int)(r1 >> 20) <= TH_LOW) {
         const int rb = idxB[np.b_begin + (int)(r1 & 0xFFFFF)];
-        if (lane == 0) matchB[rb] = ra, claimB[rb] = 1;
+        if (lane == 0) match[rb] = ra, claimB[rb] = 1;
         __threadfence_block();  // later KF features of this node must see the claim
       }
     }
@@ -450,9 +444,9 @@ __global__ __launch_bounds__(256) void k_search_by_bow(const NodePair *pairs, in
       const int rb = idxB[np.b_begin + (int)(k1 & 0xFFFFF)];
       if (lane == 0) {
         if (mode == 0)
-          matchB[rb] = ra;  // vpMapPointMatches[bestIdxF] = pMP
+          match[rb] = ra;  // vpMapPointMatches[bestIdxF] = pMP
         else
-          matchA[ra] = rb;  // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
+          match[ra] = rb;  // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
         claimB[rb] = 1;     // (mode 1: vbMatched2[bestIdx2] = true)
       }
       __threadfence_block();
@@ -460,59 +454,23 @@ __global__ __launch_bounds__(256) void k_search_by_bow(const NodePair *pairs, in
   }
 }
 
-// ---- SearchForTriangulation (ORBmatcher.cc:902-1146): one wavefront per shared vocabulary node.  For every eligible
-// KF1 feature of the node: best KF2 feature of the node with dist <= TH_LOW whose (idx1, idx2) pair passes the
-// caller's geometric predicate bit; the reference's `dist > bestDist -> continue` lets a LATER equal distance win, so
-// keys are (dist << 20 | 0xFFFFF - position) and the wave takes their minimum.  No greedy state (vbMatched2 is never
-// set by the reference), so nodes and features are independent.
-__global__ __launch_bounds__(256) void k_search_triangulation(const NodePair *pairs, int npairs, const uint8_t *descA,
-                                                              const uint8_t *eligA, const int *idxA,
-                                                              const uint8_t *descB, const uint8_t *eligB,
-                                                              const int *idxB, const uint32_t *pairOk,
-                                                              const int *pairOff, int *matches12) {
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (wave >= npairs) return;
-  const NodePair np = pairs[wave];
-  const int nb = np.b_end - np.b_begin;
-  const long long bit0 = pairOk ? (long long)pairOff[wave] : 0;
-  for (int ia = np.a_begin; ia < np.a_end; ia++) {
-    const int ra = idxA[ia];
-    if (!eligA[ra]) continue;
-    uint4 a0, a1;
-    load_desc(descA, ra, a0, a1);
-    uint32_t k = KEY_NONE;
-    for (int j = lane; j < nb; j += 64) {
-      const int rb = idxB[np.b_begin + j];
-      if (!eligB[rb]) continue;
-      if (pairOk) {
-        const long long bit = bit0 + (long long)(ia - np.a_begin) * nb + j;
-        if (!((pairOk[bit >> 5] >> (bit & 31)) & 1u)) continue;
-      }
-      uint4 b0, b1;
-      load_desc(descB, rb, b0, b1);
-      const int dist = hamming256(a0, a1, b0, b1);
-      if (dist > TH_LOW) continue;
-      k = min(k, ((uint32_t)dist << 20) | (0xFFFFFu - (uint32_t)j));
-    }
-    k = wave_min(k);
-    if (lane == 0 && k != KEY_NONE) matches12[ra] = idxB[np.b_begin + (int)(0xFFFFFu - (k & 0xFFFFFu))];
-  }
-}
-
-// ---- SearchForTriangulation with the geometric predicate of :976-1073 evaluated HERE (vsg_epipolar.h) instead of read as
-// one caller-made bit per pair.  The predicate is a pure function of the pair and the reference never sets vbMatched2, so KF1
-// features are independent: one WORKGROUP per shared vocabulary node, joined on the host (pairs) or -- pairs == nullptr -- in
-// the kernel on the two resident FeatureVectors, exactly as k_search_by_bow does.
-//   * The node's KF2 side goes to LDS once per tile of kEpiTile rows: descriptor, x, y, the level's gate radius and chi-square
-//     bound (two 16-entry tables made by the host with the header's own functions) and the flags (stereo; has a map point).
-//   * Waves take the KF1 rows round-robin; (a, b, c, den) of the row's epipolar line are wave-uniform, the lanes stride the
-//     tile's KF2 rows, run the geometry first and the Hamming distance for the survivors; wave_min over
-//     (dist << 20) | (0xFFFFF - j), j = the position in the node's KF2 list ACROSS tiles: the later of equal distances wins.
-//   * KF1 rows are taken kEpiRows at a time, staged the same way (one round of loads instead of a dependent chain per row); a
-//     row's running minimum over the tiles lives in LDS (s_key), owned by the wave that walks the row.  A node of any size
-//     on either side is walked with the same 14 KB of LDS; a node whose KF2 side fits one tile (every node of a real
-//     FeatureVector) is staged once.
-// matches12 is WRITE-ONLY (pre-filled with -1 by the host: pinned memory); a KF1 feature belongs to one node.
+// ---- SearchForTriangulation (ORBmatcher.cc:902-1146).  For every KF1 feature of the node that is walked: the best KF2
+// feature of the node with dist <= TH_LOW whose pair passes the geometric predicate of :976-1073.  The reference's
+// `dist > bestDist -> continue` lets a LATER equal distance win, so keys are (dist << 20) | (0xFFFFF - j), j = the position in
+// the node's KF2 list ACROSS tiles, and the walk takes their minimum.  The predicate is a pure function of the pair and the
+// reference never sets vbMatched2, so KF1 features are independent.  ONE walk; the predicate is the template parameter:
+//   * EpipolarPred: evaluated HERE (vsg_epipolar.h).  (a, b, c, den) of the row's epipolar line are wave-uniform; a KF2 row
+//     brings x, y, the level's gate radius and chi-square bound (two 16-entry tables made by the host with the header's own
+//     functions) and the flags (stereo; has a map point), in LDS arrays only this instantiation keeps;
+//   * CallerBitsPred: one bit per pair made by the caller, bit pair_off[s] + i * nb + j for positions (i, j) of the s-th
+//     shared node's lists (pair_bits_check of vsg_fv.h saw the layout: the sum fits an int); bits == nullptr: every pair
+//     passes.  A row of either side needs its eligible flag.
+// The node's KF2 side goes to LDS once per tile of kEpiTile rows.  Waves take the KF1 rows round-robin; the lanes stride the
+// tile's KF2 rows, run the predicate first and the Hamming distance for the survivors; wave_min over the keys.  KF1 rows are
+// taken kEpiRows at a time, staged the same way (one round of loads instead of a dependent chain per row); a row's running
+// minimum over the tiles lives in LDS (s_key), owned by the wave that walks the row.  A node of any size on either side is
+// walked with the same 14 KB of LDS; a node whose KF2 side fits one tile (every node of a real FeatureVector) is staged once.
+// matches12 is WRITE-ONLY (pre-filled with -1 by the host: it may be pinned memory); a KF1 feature belongs to one node.
 struct EpiParams {
   float F12[9], ep[2];
   float gate[16];    // epipole_gate_radius(mvScaleFactors2[level]); 0 above nlevels
@@ -522,36 +480,35 @@ struct EpiParams {
 struct EpiFrame {
   const vsg::KeyPointPOD *kps;
   const uint8_t *desc;
-  const float *uright;  // nullptr: every mvuRight is -1
+  const float *uright;   // nullptr: every mvuRight is -1
   const uint8_t *no_mp;  // !pKF->GetMapPoint(i)
+};
+struct EpipolarPred {
+  EpiFrame A, B;
+  EpiParams P;
+};
+struct CallerBitsPred {
+  const uint8_t *desc1, *eligible1, *desc2, *eligible2;
+  const uint32_t *bits;
+  const int *pair_off;
 };
 enum { kEpiTile = 128, kEpiRows = 128, kEpiStereo = 1, kEpiHasMp = 2 };
 
-__global__ __launch_bounds__(256) void k_triangulation_epipolar(const NodePair *pairs, int npairs, FvDev fa, FvDev fb,
-                                                                const int *idxA, const int *idxB, EpiFrame A, EpiFrame B,
-                                                                EpiParams P, int *matches12) {
+template <class Pred>
+__global__ __launch_bounds__(256) void k_triangulation_walk(const NodePair *pairs, int npairs, FvDev fa, FvDev fb,
+                                                            const int *idxA, const int *idxB, Pred q, int *matches12) {
+  constexpr bool kEpi = std::is_same<Pred, EpipolarPred>::value;
+  const uint8_t *descA, *descB;
+  if constexpr (kEpi)
+    descA = q.A.desc, descB = q.B.desc;
+  else
+    descA = q.desc1, descB = q.desc2;
   const int node = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   NodePair np;
-  if (pairs) {
-    if (node >= npairs) return;
-    np = pairs[node];
-  } else {  // the join of k_search_by_bow
-    __shared__ int s_pos;
-    const int nA_nodes = fa.hdr[0], nB_nodes = fb.hdr[0];
-    const int id = node < nA_nodes ? fa.node[node] : -1;
-    if (tid == 0) s_pos = -1;
-    __syncthreads();
-    for (int base = 0; base < nB_nodes; base += 256)
-      if (base + tid < nB_nodes && fb.node[base + tid] == id) s_pos = base + tid;  // ids are unique: at most one writer
-    __syncthreads();
-    const int lo = s_pos;
-    if (node >= nA_nodes || lo < 0) return;
-    np.a_begin = fa.off[node], np.a_end = fa.off[node + 1], np.b_begin = fb.off[lo], np.b_end = fb.off[lo + 1];
-    idxA = fa.idx, idxB = fb.idx;
-  }
+  if (!block_node(pairs, npairs, fa, fb, np, idxA, idxB)) return;
   const int na = np.a_end - np.a_begin, nb = np.b_end - np.b_begin;
   __shared__ uint4 s_d[kEpiTile][2], s_da[kEpiRows][2];
-  __shared__ double s_bound[kEpiTile];
+  __shared__ double s_bound[kEpiTile];  // this line and the next: read by the epipolar form alone, gone from the other
   __shared__ float s_x[kEpiTile], s_y[kEpiTile], s_gate[kEpiTile], s_ax[kEpiRows], s_ay[kEpiRows];
   __shared__ int s_flag[kEpiTile], s_ra[kEpiRows], s_aflag[kEpiRows];
   __shared__ uint32_t s_key[kEpiRows];
@@ -562,13 +519,18 @@ __global__ __launch_bounds__(256) void k_triangulation_epipolar(const NodePair *
     __syncthreads();  // every wave is done with the chunk before
     if (sr < rows) {  // the chunk's KF1 side in one round of loads
       const int ra = idxA[np.a_begin + a0 + sr];
-      s_da[sr][sh] = ((const uint4 *)(A.desc + (size_t)ra * 32))[sh];
+      s_da[sr][sh] = ((const uint4 *)(descA + (size_t)ra * 32))[sh];
       if (sh == 0) {
-        const vsg::KeyPointPOD kp = A.kps[ra];
-        const bool stereo1 = A.uright && A.uright[ra] >= 0;
-        // -1: has a map point (:969-973), or mono under bOnlyStereo (:976-980): the row is not walked
-        s_ra[sr] = ra, s_ax[sr] = kp.x, s_ay[sr] = kp.y, s_key[sr] = KEY_NONE;
-        s_aflag[sr] = (!A.no_mp[ra] || (P.only_stereo && !stereo1)) ? -1 : (stereo1 ? kEpiStereo : 0);
+        s_ra[sr] = ra, s_key[sr] = KEY_NONE;
+        if constexpr (kEpi) {
+          const vsg::KeyPointPOD kp = q.A.kps[ra];
+          const bool stereo1 = q.A.uright && q.A.uright[ra] >= 0;
+          s_ax[sr] = kp.x, s_ay[sr] = kp.y;
+          // -1: has a map point (:969-973), or mono under bOnlyStereo (:976-980): the row is not walked
+          s_aflag[sr] = (!q.A.no_mp[ra] || (q.P.only_stereo && !stereo1)) ? -1 : (stereo1 ? kEpiStereo : 0);
+        } else {
+          s_aflag[sr] = q.eligible1[ra] ? 0 : -1;
+        }
       }
     }
     __syncthreads();
@@ -578,12 +540,16 @@ __global__ __launch_bounds__(256) void k_triangulation_epipolar(const NodePair *
         if (staged >= 0) __syncthreads();  // every wave is done with the tile before
         if (sr < nt) {
           const int rb = idxB[np.b_begin + t0 + sr];
-          s_d[sr][sh] = ((const uint4 *)(B.desc + (size_t)rb * 32))[sh];
+          s_d[sr][sh] = ((const uint4 *)(descB + (size_t)rb * 32))[sh];
           if (sh == 0) {
-            const vsg::KeyPointPOD kp = B.kps[rb];
-            const int lv = kp.octave & 15;  // the host checked [0, nlevels) on its mirror; the tables have 16 entries
-            s_x[sr] = kp.x, s_y[sr] = kp.y, s_gate[sr] = P.gate[lv], s_bound[sr] = P.bound[lv];
-            s_flag[sr] = ((B.uright && B.uright[rb] >= 0) ? kEpiStereo : 0) | (B.no_mp[rb] ? 0 : kEpiHasMp);
+            if constexpr (kEpi) {
+              const vsg::KeyPointPOD kp = q.B.kps[rb];
+              const int lv = kp.octave & 15;  // the host checked [0, nlevels) on its mirror; the tables have 16 entries
+              s_x[sr] = kp.x, s_y[sr] = kp.y, s_gate[sr] = q.P.gate[lv], s_bound[sr] = q.P.bound[lv];
+              s_flag[sr] = ((q.B.uright && q.B.uright[rb] >= 0) ? kEpiStereo : 0) | (q.B.no_mp[rb] ? 0 : kEpiHasMp);
+            } else {
+              s_flag[sr] = q.eligible2[rb];
+            }
           }
         }
         staged = t0;
@@ -592,17 +558,26 @@ __global__ __launch_bounds__(256) void k_triangulation_epipolar(const NodePair *
       for (int r = wave; r < rows; r += 4) {  // wave-uniform; row r belongs to wave r & 3
         const int af = s_aflag[r];
         if (af < 0) continue;
-        const bool stereo1 = af != 0;
         vsg::EpipolarLine line = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (!P.coarse) line = vsg::epipolar_line(P.F12, s_ax[r], s_ay[r]);
+        int bit0 = 0;  // the row's first bit
+        if constexpr (kEpi) {
+          if (!q.P.coarse) line = vsg::epipolar_line(q.P.F12, s_ax[r], s_ay[r]);
+        } else if (q.bits) {
+          bit0 = q.pair_off[node] + (a0 + r) * nb + t0;
+        }
         const uint4 d0 = s_da[r][0], d1 = s_da[r][1];
         uint32_t k = KEY_NONE;
         for (int j = lane; j < nt; j += 64) {
           const int fl = s_flag[j];
-          if (fl & kEpiHasMp) continue;  // :1001-1002
-          if (vsg::epipolar_reason(line, stereo1, s_x[j], s_y[j], (fl & kEpiStereo) != 0, P.ep[0], P.ep[1], s_gate[j],
-                                   s_bound[j], P.only_stereo, P.coarse) != vsg::kEpiPass)
-            continue;
+          if constexpr (kEpi) {
+            if (fl & kEpiHasMp) continue;  // :1001-1002
+            if (vsg::epipolar_reason(line, af != 0, s_x[j], s_y[j], (fl & kEpiStereo) != 0, q.P.ep[0], q.P.ep[1], s_gate[j],
+                                     s_bound[j], q.P.only_stereo, q.P.coarse) != vsg::kEpiPass)
+              continue;
+          } else {
+            if (!fl) continue;
+            if (q.bits && !((q.bits[(bit0 + j) >> 5] >> ((bit0 + j) & 31)) & 1u)) continue;
+          }
           const int dist = hamming256(d0, d1, s_d[j][0], s_d[j][1]);
           if (dist > TH_LOW) continue;  // :1014
           k = min(k, ((uint32_t)dist << 20) | (0xFFFFFu - (uint32_t)(t0 + j)));
@@ -707,22 +682,6 @@ using vsg::ThreadCtx;
 using vsg::Stage;
 namespace walk = vsg::walk;
 
-// merge-join of two FeatureVectors (ORBmatcher.cc:247-405 loop skeleton incl. lower_bound jumps)
-void join_nodes(const int *idA, const int *offA, int nA, const int *idB, const int *offB, int nB,
-                std::vector<NodePair> &out) {
-  int i = 0, j = 0;
-  while (i != nA && j != nB) {
-    if (idA[i] == idB[j]) {
-      out.push_back({offA[i], offA[i + 1], offB[j], offB[j + 1]});
-      i++, j++;
-    } else if (idA[i] < idB[j]) {
-      i = (int)(std::lower_bound(idA, idA + nA, idB[j]) - idA);
-    } else {
-      j = (int)(std::lower_bound(idB, idB + nB, idA[i]) - idB);
-    }
-  }
-}
-
 // Packed candidate entries (vsg_walks.h) for host-provided CSR candidate lists.  On return *ent points into the
 // calling thread's pinned arena (valid until its next call).
 static int candidate_entries(int device, const uint8_t *q_desc, int n_q, const int32_t *cand_off,
@@ -792,56 +751,95 @@ static int bow_rotation_filter(int *out, int nOut, int mode, AngleA angleA, Angl
   return nmatches;
 }
 
-// SearchByBoW on descriptors that are either host arrays (descA/descB, staged) or already on the device (dDescA/dDescB)
-template <class AngleA, class AngleB>
-static int search_by_bow(int device, int mode, int nleftB, const uint8_t *descA, const uint8_t *dDescA, AngleA angleA,
-                         const uint8_t *validA, int nA, const int *idA, const int *offA, const int *idxA, int nodesA,
-                         const uint8_t *descB, const uint8_t *dDescB, AngleB angleB, const uint8_t *validB, int nB,
-                         const int *idB, const int *offB, const int *idxB, int nodesB, float nnratio, int checkOri,
-                         int *out) {
+// The buffers of one call in an arena: each is named ONCE, so the size it is laid out with is the size it is copied with
+struct Upload {
+  enum { kMax = 10 };
+  Stage st;
+  const void *src[kMax];
+  size_t bytes[kMax], at[kMax];
+  int n = 0;
+  size_t add(const void *s, size_t b) {  // s == nullptr: laid out and left to the caller
+    if (n == kMax) abort();
+    src[n] = s, bytes[n] = b;
+    return at[n++] = st.add(b);
+  }
+  void fill(uint8_t *base) const {
+    for (int i = 0; i < n; i++)
+      if (src[i] && bytes[i]) memcpy(base + at[i], src[i], bytes[i]);
+  }
+};
+
+// ---- the node searches on FeatureVectors given as HOST arrays.  One side of such a call: its descriptors and angles are
+// host arrays (the descriptors are staged) or those of a resident frame (d_desc, and the angles of its host mirror)
+struct HostSide {
+  int n;
+  const uint8_t *desc, *d_desc;
+  const float *angle;
+  const vsg_keypoint *kps;
+  const uint8_t *flags;  // valid / eligible per feature; nullptr: the side has none (the Frame of KF -> F)
+  vsg::FvView fv;
+  float angle_of(int i) const { return angle ? angle[i] : kps[i].angle; }
+};
+static HostSide frame_side(const vsg_frame *f, const uint8_t *flags, const int32_t *node_id, const int32_t *off,
+                           const int32_t *idx, int nodes) {
+  return HostSide{f->n, nullptr, f->d_desc, nullptr, f->h_kps.data(), flags, {node_id, off, idx, nodes}};
+}
+
+// One such search from the checks to the rotation filter.  mode 0 / 1: SearchByBoW KF -> F (the output is per feature of B:
+// match_f) / KF -> KF (per feature of A: matches12); mode 2: SearchForTriangulation (matches12; pair_ok / pair_off).
+// Everything that can be refused is refused FIRST, with VSG_ERR_INVALID: before thread_ctx is called, before anything is
+// enqueued and before the output is written.  The kernels index the frames with idx and the bits with pair_off: what
+// vsg_fv.h refuses never reaches the device.
+static int node_search(int device, int mode, int nleftB, float nnratio, const HostSide &A, const HostSide &B,
+                       const uint32_t *pair_ok, const int32_t *pair_off, int check_orientation, int32_t *out) {
+  for (const HostSide *s : {&A, &B})
+    if (s->n < 0 || (s->n > 0 && ((!s->desc && !s->d_desc) || (!s->angle && !s->kps))) || !vsg::fv_check(s->fv, s->n))
+      return VSG_ERR_INVALID;
+  if ((A.n > 0 && !A.flags) || (mode != 0 && B.n > 0 && !B.flags) || (pair_ok && !pair_off)) return VSG_ERR_INVALID;
+  std::vector<NodePair> pairs;
+  vsg::join_nodes(A.fv.node_id, A.fv.off, A.fv.nodes, B.fv.node_id, B.fv.off, B.fv.nodes, pairs);
+  if (pair_ok && !vsg::pair_bits_check(pairs, pair_off)) return VSG_ERR_INVALID;
   int rc = VSG_OK;
   ThreadCtx *c = vsg::thread_ctx(device, &rc);
   if (!c) return rc;
-  const int nOut = mode == 0 ? nB : nA;
+  const int nOut = mode == 0 ? B.n : A.n, npairs = (int)pairs.size();
   for (int i = 0; i < nOut; i++) out[i] = -1;
-  std::vector<NodePair> pairs;
-  join_nodes(idA, offA, nodesA, idB, offB, nodesB, pairs);
-  if (pairs.empty() || nA == 0 || nB == 0) return 0;
-  const int nIdxA = offA[nodesA], nIdxB = offB[nodesB], npairs = (int)pairs.size();
-  Stage st;
-  const size_t oP = st.add(pairs.size() * sizeof(NodePair)), oVA = st.add((size_t)nA), oIA = st.add((size_t)nIdxA * 4),
-               oVB = st.add(mode == 1 ? (size_t)nB : 0), oIB = st.add((size_t)nIdxB * 4),
-               oDA = st.add(dDescA ? 0 : (size_t)nA * 32), oDB = st.add(dDescB ? 0 : (size_t)nB * 32);
-  const size_t in_bytes = st.total;
-  Stage dv;  // device-only scratch behind the inputs
-  dv.total = in_bytes;
-  const size_t nAB = (size_t)(nA > nB ? nA : nB);
-  const size_t oMA = dv.add(nAB * 4), oMB = dv.add(nAB * 4);
-  rc = vsg::ctx_reserve(c, in_bytes + (size_t)nOut * 4 + 64, dv.total);
+  if (pairs.empty() || A.n == 0 || B.n == 0) return 0;
+  // The join's pairs, both sides' flags and lists, host descriptors and the predicate bits (the last node's end at
+  // pair_off[npairs]) go up in ONE DMA: the kernels read them many times.  Behind them the output and BoW's claim scratch.
+  Upload up;
+  const size_t oP = up.add(pairs.data(), pairs.size() * sizeof(NodePair)), oFA = up.add(A.flags, (size_t)A.n),
+               oIA = up.add(A.fv.idx, (size_t)A.fv.off[A.fv.nodes] * 4), oFB = up.add(B.flags, B.flags ? (size_t)B.n : 0),
+               oIB = up.add(B.fv.idx, (size_t)B.fv.off[B.fv.nodes] * 4), oDA = up.add(A.desc, A.d_desc ? 0 : (size_t)A.n * 32),
+               oDB = up.add(B.desc, B.d_desc ? 0 : (size_t)B.n * 32),
+               oOk = up.add(pair_ok, pair_ok ? ((size_t)pair_off[npairs] + 31) / 32 * 4 : 0),
+               oOff = up.add(pair_ok ? pair_off : nullptr, pair_ok ? (size_t)(npairs + 1) * 4 : 0);
+  const size_t in_bytes = up.st.total, oOut = up.st.add((size_t)nOut * 4), pin_bytes = up.st.total;
+  const size_t oClaim = up.st.add(mode == 2 ? 0 : (size_t)B.n * 4);
+  rc = vsg::ctx_reserve(c, pin_bytes, up.st.total);
   if (rc != VSG_OK) return rc;
-  uint8_t *h = c->h_pin;
-  memcpy(h + oP, pairs.data(), pairs.size() * sizeof(NodePair));
-  memcpy(h + oVA, validA, (size_t)nA);
-  memcpy(h + oIA, idxA, (size_t)nIdxA * 4);
-  if (mode == 1) memcpy(h + oVB, validB, (size_t)nB);
-  memcpy(h + oIB, idxB, (size_t)nIdxB * 4);
-  if (!dDescA) memcpy(h + oDA, descA, (size_t)nA * 32);
-  if (!dDescB) memcpy(h + oDB, descB, (size_t)nB * 32);
-  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
-  uint8_t *d = c->d_buf;
-  int *dMA = (int *)(d + oMA), *dMB = (int *)(d + oMB);  // mode 0: dMB = match_f, dMA = the claim scratch; mode 1: the reverse
-  TRY_HIP(hipMemsetAsync(mode == 0 ? dMB : dMA, 0xFF, (size_t)(mode == 0 ? nB : nA) * 4, c->stream));  // -1
-  hipLaunchKernelGGL(k_search_by_bow, dim3(npairs), dim3(256), 0, c->stream, (const NodePair *)(d + oP), npairs,
-                     FvDev{}, FvDev{}, dDescA ? dDescA : d + oDA, d + oVA, (const int *)(d + oIA), dDescB ? dDescB : d + oDB, d + oVB,
-                     (const int *)(d + oIB), nnratio, mode, nleftB, dMA, mode == 0 ? dMB : (int *)nullptr,
-                     mode == 0 ? dMA : dMB);
+  uint8_t *h = c->h_pin, *d = c->d_buf;
+  up.fill(h);
+  TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  TRY_HIP(hipMemsetAsync(d + oOut, 0xFF, (size_t)nOut * 4, c->stream));  // -1: the kernels only write matches
+  const uint8_t *dA = A.d_desc ? A.d_desc : d + oDA, *dB = B.d_desc ? B.d_desc : d + oDB;
+  if (mode == 2)
+    hipLaunchKernelGGL(k_triangulation_walk<CallerBitsPred>, dim3(npairs), dim3(256), 0, c->stream, (const NodePair *)(d + oP),
+                       npairs, FvDev{}, FvDev{}, (const int *)(d + oIA), (const int *)(d + oIB),
+                       CallerBitsPred{dA, d + oFA, dB, d + oFB, pair_ok ? (const uint32_t *)(d + oOk) : nullptr,
+                                      (const int *)(d + oOff)},
+                       (int *)(d + oOut));
+  else
+    hipLaunchKernelGGL(k_search_by_bow, dim3(npairs), dim3(256), 0, c->stream, (const NodePair *)(d + oP), npairs, FvDev{},
+                       FvDev{}, dA, d + oFA, (const int *)(d + oIA), dB, d + oFB, (const int *)(d + oIB), nnratio, mode, nleftB,
+                       (int *)(d + oOut), (int *)(d + oClaim));
   TRY_HIP(hipGetLastError());
-  int *hOut = (int *)(h + in_bytes);
-  TRY_HIP(hipMemcpyAsync(hOut, mode == 0 ? dMB : dMA, (size_t)nOut * 4, hipMemcpyDeviceToHost, c->stream));
+  TRY_HIP(hipMemcpyAsync(h + oOut, d + oOut, (size_t)nOut * 4, hipMemcpyDeviceToHost, c->stream));
   TRY_HIP(hipStreamSynchronize(c->stream));
-  memcpy(out, hOut, (size_t)nOut * 4);
+  memcpy(out, h + oOut, (size_t)nOut * 4);
   // rotation consistency (:407-425 / :879-897)
-  return bow_rotation_filter(out, nOut, mode, angleA, angleB, checkOri != 0);
+  return bow_rotation_filter(out, nOut, mode == 0 ? 0 : 1, [&](int i) { return A.angle_of(i); },
+                             [&](int i) { return B.angle_of(i); }, check_orientation != 0);
 }
 
 // ---- SearchByBoW on two frames whose descriptors AND FeatureVectors are resident (round 6): nothing but the KeyFrame's
@@ -869,20 +867,16 @@ int bow_search_enqueue(BowSearchCall *s, int mode, vsg_frame *A, const uint8_t *
   if (!A->fv_valid || !B->fv_valid) return VSG_ERR_INVALID;  // ComputeBoW first (Frame.cc:882-889)
   if (A->fv_empty || B->fv_empty) return VSG_OK;             // ComputeBoW with an empty() vocabulary left no node
   const int nA = A->n, nB = B->n;
-  Stage p;
-  const size_t oVA = p.add((size_t)nA), oVB = p.add(mode == 1 ? (size_t)nB : 0);
-  s->oOut = p.add(4 * (size_t)s->nOut + 64);
+  Upload p;  // the layout of bow_search_sizes
+  const size_t oVA = p.add(validA, (size_t)nA), oVB = p.add(mode == 1 ? validB : nullptr, mode == 1 ? (size_t)nB : 0);
+  s->oOut = p.add(nullptr, 4 * (size_t)s->nOut + 64);
   uint8_t *hp = c->h_pin + pin_base, *dp = c->d_pin + pin_base;
-  memcpy(hp + oVA, validA, (size_t)nA);
-  if (mode == 1) memcpy(hp + oVB, validB, (size_t)nB);
+  p.fill(hp);
   memset(hp + s->oOut, 0xFF, 4 * (size_t)s->nOut);  // -1: the kernel only writes matches
-  const FvDev fa{A->d_fv_hdr, A->d_fv_node, A->d_fv_off, A->d_fv_idx}, fb{B->d_fv_hdr, B->d_fv_node, B->d_fv_off, B->d_fv_idx};
-  const int waves = A->fv_bound > 0 ? A->fv_bound : 1;
-  int *out = (int *)(dp + s->oOut);
-  hipLaunchKernelGGL(k_search_by_bow, dim3(waves), dim3(256), 0, c->stream, (const NodePair *)nullptr, 0, fa, fb,
-                     A->d_desc, dp + oVA, (const int *)nullptr, B->d_desc, dp + oVB, (const int *)nullptr, nnratio, mode,
-                     mode == 0 ? B->nleft : -1, mode == 1 ? out : (int *)nullptr, mode == 0 ? out : (int *)nullptr,
-                     (int *)(c->d_buf + dev_base));
+  const int blocks = A->fv_bound > 0 ? A->fv_bound : 1;
+  hipLaunchKernelGGL(k_search_by_bow, dim3(blocks), dim3(256), 0, c->stream, (const NodePair *)nullptr, 0, vsg::fv_dev(A),
+                     vsg::fv_dev(B), A->d_desc, dp + oVA, (const int *)nullptr, B->d_desc, dp + oVB, (const int *)nullptr,
+                     nnratio, mode, mode == 0 ? B->nleft : -1, (int *)(dp + s->oOut), (int *)(c->d_buf + dev_base));
   TRY_HIP(hipGetLastError());
   s->active = true;
   return VSG_OK;
@@ -920,60 +914,6 @@ static int search_by_bow_resident(int mode, vsg_frame *A, const uint8_t *validA,
   return vsg::bow_search_finish(&s, check_orientation, out);
 }
 
-// SearchForTriangulation on descriptors that are host arrays (desc1/desc2, staged) or already resident (dDesc1/dDesc2)
-template <class Angle1, class Angle2>
-static int search_triangulation(int device, const uint8_t *desc1, const uint8_t *dDesc1, Angle1 angle1,
-                                const uint8_t *eligible1, int n1, const int32_t *node_id1, const int32_t *off1,
-                                const int32_t *idx1, int nodes1, const uint8_t *desc2, const uint8_t *dDesc2,
-                                Angle2 angle2, const uint8_t *eligible2, int n2, const int32_t *node_id2,
-                                const int32_t *off2, const int32_t *idx2, int nodes2, const uint32_t *pair_ok,
-                                const int32_t *pair_off, int check_orientation, int32_t *matches12) {
-  int rc = VSG_OK;
-  ThreadCtx *c = vsg::thread_ctx(device, &rc);
-  if (!c) return rc;
-  for (int i = 0; i < n1; i++) matches12[i] = -1;
-  std::vector<NodePair> pairs;
-  join_nodes(node_id1, off1, nodes1, node_id2, off2, nodes2, pairs);
-  if (pairs.empty() || n1 == 0 || n2 == 0) return 0;
-  const int npairs = (int)pairs.size();
-  const int nI1 = off1[nodes1], nI2 = off2[nodes2];
-  // bits of shared node s start at pair_off[s]; the last node ends at pair_off[npairs]
-  const size_t ok_words = pair_ok ? (size_t)(((long long)pair_off[npairs] + 31) / 32 + 1) : 0;
-  Stage st;
-  const size_t oP = st.add(pairs.size() * sizeof(NodePair)), oD1 = st.add(dDesc1 ? 0 : (size_t)n1 * 32),
-               oE1 = st.add((size_t)n1), oI1 = st.add((size_t)nI1 * 4), oD2 = st.add(dDesc2 ? 0 : (size_t)n2 * 32),
-               oE2 = st.add((size_t)n2), oI2 = st.add((size_t)nI2 * 4), oOk = st.add(ok_words * 4),
-               oOff = st.add(pair_ok ? (size_t)(npairs + 1) * 4 : 0);
-  const size_t in_bytes = st.total;
-  const size_t oM = st.add((size_t)n1 * 4);
-  rc = vsg::ctx_reserve(c, st.total, st.total);
-  if (rc != VSG_OK) return rc;
-  uint8_t *h = c->h_pin;
-  memcpy(h + oP, pairs.data(), pairs.size() * sizeof(NodePair));
-  if (!dDesc1) memcpy(h + oD1, desc1, (size_t)n1 * 32);
-  memcpy(h + oE1, eligible1, (size_t)n1);
-  memcpy(h + oI1, idx1, (size_t)nI1 * 4);
-  if (!dDesc2) memcpy(h + oD2, desc2, (size_t)n2 * 32);
-  memcpy(h + oE2, eligible2, (size_t)n2);
-  memcpy(h + oI2, idx2, (size_t)nI2 * 4);
-  if (pair_ok) {
-    memcpy(h + oOk, pair_ok, ok_words * 4);
-    memcpy(h + oOff, pair_off, (size_t)(npairs + 1) * 4);
-  }
-  TRY_HIP(hipMemcpyAsync(c->d_buf, h, in_bytes, hipMemcpyHostToDevice, c->stream));
-  uint8_t *d = c->d_buf;
-  TRY_HIP(hipMemsetAsync(d + oM, 0xFF, (size_t)n1 * 4, c->stream));
-  hipLaunchKernelGGL(k_search_triangulation, dim3((npairs + 3) / 4), dim3(256), 0, c->stream, (const NodePair *)(d + oP),
-                     npairs, dDesc1 ? dDesc1 : d + oD1, d + oE1, (const int *)(d + oI1), dDesc2 ? dDesc2 : d + oD2, d + oE2,
-                     (const int *)(d + oI2), pair_ok ? (const uint32_t *)(d + oOk) : (const uint32_t *)nullptr,
-                     pair_ok ? (const int *)(d + oOff) : (const int *)nullptr, (int *)(d + oM));
-  TRY_HIP(hipGetLastError());
-  TRY_HIP(hipMemcpyAsync(h + oM, d + oM, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
-  TRY_HIP(hipStreamSynchronize(c->stream));
-  memcpy(matches12, h + oM, (size_t)n1 * 4);
-  return bow_rotation_filter(matches12, n1, 1, angle1, angle2, check_orientation != 0);
-}
-
 // the per-call constants of the epipolar predicate: F12, ep and the two per-level tables of pKF2 (vsg_epipolar.h)
 static EpiParams epi_params(const float *F12, const float *ep, const float *scale_factors2, const float *level_sigma2_2,
                             int nlevels, int only_stereo, int coarse) {
@@ -991,14 +931,8 @@ static bool octaves_within(const vsg_frame *f, int nlevels) {
     if (k.octave < 0 || k.octave >= nlevels) return false;
   return true;
 }
-// a FeatureVector given as host arrays: ascending offsets from 0 and feature indices inside the frame
-static bool fv_within(const int32_t *off, const int32_t *idx, int nodes, int n) {
-  if (nodes < 0 || (nodes > 0 && off[0] != 0)) return false;
-  for (int k = 0; k < nodes; k++)
-    if (off[k + 1] < off[k]) return false;
-  for (int k = 0, e = nodes > 0 ? off[nodes] : 0; k < e; k++)
-    if (idx[k] < 0 || idx[k] >= n) return false;
-  return true;
+static EpiFrame epi_frame(const vsg_frame *f, const uint8_t *no_mp) {
+  return EpiFrame{f->d_kps, f->d_desc, f->has_uright ? f->d_uright : (const float *)nullptr, no_mp};
 }
 
 }  // namespace
@@ -1019,10 +953,11 @@ int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *n
   if (kf1->nleft != -1 || kf2->nleft != -1) return VSG_ERR_UNSUPPORTED;  // mpCamera2 (:929-937, :1033-1071)
   if (!octaves_within(kf2, nlevels)) return VSG_ERR_INVALID;
   const bool resident_fv = !node_id1 && !off1 && !idx1 && !node_id2 && !off2 && !idx2;
+  const vsg::FvView v1{node_id1, off1, idx1, nodes1}, v2{node_id2, off2, idx2, nodes2};
   if (!resident_fv) {
     if (!node_id1 || !off1 || !idx1 || !node_id2 || !off2 || !idx2) return VSG_ERR_INVALID;
     // the kernel indexes the frames with these: an index outside a frame never reaches the device
-    if (!fv_within(off1, idx1, nodes1, kf1->n) || !fv_within(off2, idx2, nodes2, kf2->n)) return VSG_ERR_INVALID;
+    if (!vsg::fv_check(v1, kf1->n) || !vsg::fv_check(v2, kf2->n)) return VSG_ERR_INVALID;
   }
   const int n1 = kf1->n, n2 = kf2->n;
   // ComputeBoW first (Frame.cc:882-889); an empty frame has an empty FeatureVector whatever ComputeBoW left
@@ -1033,7 +968,7 @@ int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *n
   if (resident_fv) {
     if (kf1->fv_empty || kf2->fv_empty) return 0;  // ComputeBoW with an empty() vocabulary left no node
   } else {
-    join_nodes(node_id1, off1, nodes1, node_id2, off2, nodes2, pairs);
+    vsg::join_nodes(node_id1, off1, nodes1, node_id2, off2, nodes2, pairs);
     if (pairs.empty()) return 0;
   }
   int rc = VSG_OK;
@@ -1041,32 +976,24 @@ int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *n
   if (!c) return rc;
   // ONE launch and nothing else on the stream (as bow_search_enqueue): the flags and lists are read and the matches written
   // where they lie in the pinned arena
-  const int npairs = (int)pairs.size(), nI1 = resident_fv ? 0 : off1[nodes1], nI2 = resident_fv ? 0 : off2[nodes2];
-  Stage st;
-  const size_t oF1 = st.add((size_t)n1), oF2 = st.add((size_t)n2), oP = st.add(pairs.size() * sizeof(NodePair)),
-               oI1 = st.add((size_t)nI1 * 4), oI2 = st.add((size_t)nI2 * 4), oM = st.add((size_t)n1 * 4);
-  rc = vsg::ctx_reserve(c, st.total, 0);
+  const int npairs = (int)pairs.size();
+  Upload up;
+  const size_t oF1 = up.add(no_mp1, (size_t)n1), oF2 = up.add(no_mp2, (size_t)n2),
+               oP = up.add(pairs.data(), pairs.size() * sizeof(NodePair)),
+               oI1 = up.add(idx1, resident_fv ? 0 : (size_t)off1[nodes1] * 4),
+               oI2 = up.add(idx2, resident_fv ? 0 : (size_t)off2[nodes2] * 4), oM = up.add(nullptr, (size_t)n1 * 4);
+  rc = vsg::ctx_reserve(c, up.st.total, 0);
   if (rc != VSG_OK) return rc;
   uint8_t *h = c->h_pin, *d = c->d_pin;
-  memcpy(h + oF1, no_mp1, (size_t)n1);
-  memcpy(h + oF2, no_mp2, (size_t)n2);
-  if (!resident_fv) {
-    memcpy(h + oP, pairs.data(), pairs.size() * sizeof(NodePair));
-    memcpy(h + oI1, idx1, (size_t)nI1 * 4);
-    memcpy(h + oI2, idx2, (size_t)nI2 * 4);
-  }
+  up.fill(h);
   memset(h + oM, 0xFF, (size_t)n1 * 4);  // -1: the kernel only writes matches
-  const EpiParams P = epi_params(F12, ep, scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse);
-  const EpiFrame A{kf1->d_kps, kf1->d_desc, kf1->has_uright ? kf1->d_uright : (const float *)nullptr, d + oF1};
-  const EpiFrame B{kf2->d_kps, kf2->d_desc, kf2->has_uright ? kf2->d_uright : (const float *)nullptr, d + oF2};
-  FvDev fa{}, fb{};
-  if (resident_fv)
-    fa = FvDev{kf1->d_fv_hdr, kf1->d_fv_node, kf1->d_fv_off, kf1->d_fv_idx},
-    fb = FvDev{kf2->d_fv_hdr, kf2->d_fv_node, kf2->d_fv_off, kf2->d_fv_idx};
+  const EpipolarPred pred{epi_frame(kf1, d + oF1), epi_frame(kf2, d + oF2),
+                          epi_params(F12, ep, scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse)};
   const int blocks = resident_fv ? (kf1->fv_bound > 0 ? kf1->fv_bound : 1) : npairs;
-  hipLaunchKernelGGL(k_triangulation_epipolar, dim3(blocks), dim3(256), 0, c->stream,
-                     resident_fv ? (const NodePair *)nullptr : (const NodePair *)(d + oP), npairs, fa, fb,
-                     (const int *)(d + oI1), (const int *)(d + oI2), A, B, P, (int *)(d + oM));
+  hipLaunchKernelGGL(k_triangulation_walk<EpipolarPred>, dim3(blocks), dim3(256), 0, c->stream,
+                     resident_fv ? (const NodePair *)nullptr : (const NodePair *)(d + oP), npairs,
+                     resident_fv ? vsg::fv_dev(kf1) : FvDev{}, resident_fv ? vsg::fv_dev(kf2) : FvDev{},
+                     (const int *)(d + oI1), (const int *)(d + oI2), pred, (int *)(d + oM));
   const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(c->stream);  // an error still waits
   if (launched != hipSuccess || waited != hipSuccess) return VSG_ERR_HIP;
   memcpy(matches12, h + oM, (size_t)n1 * 4);
@@ -1097,10 +1024,8 @@ int vsg_debug_epipolar_pairs(vsg_frame *kf1, vsg_frame *kf2, int n, const int32_
   memcpy(h + o1, i1, (size_t)n * 4);
   memcpy(h + o2, i2, (size_t)n * 4);
   const EpiParams P = epi_params(F12, ep, scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse);
-  const EpiFrame A{kf1->d_kps, kf1->d_desc, kf1->has_uright ? kf1->d_uright : (const float *)nullptr, nullptr};
-  const EpiFrame B{kf2->d_kps, kf2->d_desc, kf2->has_uright ? kf2->d_uright : (const float *)nullptr, nullptr};
   hipLaunchKernelGGL(k_epipolar_pairs, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, (const int *)(d + o1),
-                     (const int *)(d + o2), A, B, P, d + oR);
+                     (const int *)(d + o2), epi_frame(kf1, nullptr), epi_frame(kf2, nullptr), P, d + oR);
   const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(c->stream);
   if (launched != hipSuccess || waited != hipSuccess) return VSG_ERR_HIP;
   memcpy(reason, h + oR, (size_t)n);
@@ -1187,10 +1112,10 @@ int vsg_search_for_triangulation(int device, const uint8_t *desc1, const float *
                                  const int32_t *node_id2, const int32_t *off2, const int32_t *idx2, int nodes2,
                                  const uint32_t *pair_ok, const int32_t *pair_off, int check_orientation,
                                  int32_t *matches12) {
-  if (!matches12 || n1 < 0 || n2 < 0 || (pair_ok && !pair_off)) return VSG_ERR_INVALID;
-  return search_triangulation(device, desc1, nullptr, [&](int i) { return angle1[i]; }, eligible1, n1, node_id1, off1, idx1,
-                              nodes1, desc2, nullptr, [&](int i) { return angle2[i]; }, eligible2, n2, node_id2, off2, idx2,
-                              nodes2, pair_ok, pair_off, check_orientation, matches12);
+  if (!matches12) return VSG_ERR_INVALID;
+  return node_search(device, 2, -1, 0.0f, HostSide{n1, desc1, nullptr, angle1, nullptr, eligible1, {node_id1, off1, idx1, nodes1}},
+                     HostSide{n2, desc2, nullptr, angle2, nullptr, eligible2, {node_id2, off2, idx2, nodes2}}, pair_ok, pair_off,
+                     check_orientation, matches12);
 }
 
 // both KeyFrames resident (vsg_frame): only the FeatureVectors, the eligibility flags and the predicate bits go up
@@ -1199,13 +1124,11 @@ int vsg_frame_search_for_triangulation(vsg_frame *kf1, const uint8_t *eligible1,
                                        const uint8_t *eligible2, const int32_t *node_id2, const int32_t *off2,
                                        const int32_t *idx2, int nodes2, const uint32_t *pair_ok, const int32_t *pair_off,
                                        int check_orientation, int32_t *matches12) {
-  if (!kf1 || !kf2 || !matches12 || kf1->device != kf2->device || !eligible1 || !eligible2 || (pair_ok && !pair_off))
+  if (vsg::frame_check(kf1) != VSG_OK || vsg::frame_check(kf2) != VSG_OK || !matches12 || kf1->device != kf2->device ||
+      !eligible1 || !eligible2)
     return VSG_ERR_INVALID;
-  const vsg_keypoint *ka = kf1->h_kps.data(), *kb = kf2->h_kps.data();
-  return search_triangulation(kf1->device, nullptr, kf1->d_desc, [&](int i) { return ka[i].angle; }, eligible1, kf1->n,
-                              node_id1, off1, idx1, nodes1, nullptr, kf2->d_desc, [&](int i) { return kb[i].angle; },
-                              eligible2, kf2->n, node_id2, off2, idx2, nodes2, pair_ok, pair_off, check_orientation,
-                              matches12);
+  return node_search(kf1->device, 2, -1, 0.0f, frame_side(kf1, eligible1, node_id1, off1, idx1, nodes1),
+                     frame_side(kf2, eligible2, node_id2, off2, idx2, nodes2), pair_ok, pair_off, check_orientation, matches12);
 }
 
 int vsg_search_by_bow_kf_f(int device, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_valid,
@@ -1223,10 +1146,11 @@ int vsg_search_by_bow_kf_f_stereo(int device, const uint8_t *kf_desc, const floa
                                   int kf_nodes, const uint8_t *f_desc, const float *f_angle, int n_f, int f_nleft,
                                   const int32_t *f_node_id, const int32_t *f_off, const int32_t *f_idx, int f_nodes,
                                   float nnratio, int check_orientation, int32_t *match_f) {
-  if (!match_f || n_kf < 0 || n_f < 0 || f_nleft < -1 || f_nleft > n_f) return VSG_ERR_INVALID;
-  return search_by_bow(device, 0, f_nleft, kf_desc, nullptr, [&](int i) { return kf_angle[i]; }, kf_valid, n_kf,
-                       kf_node_id, kf_off, kf_idx, kf_nodes, f_desc, nullptr, [&](int i) { return f_angle[i]; }, nullptr,
-                       n_f, f_node_id, f_off, f_idx, f_nodes, nnratio, check_orientation, match_f);
+  if (!match_f || f_nleft < -1 || f_nleft > n_f) return VSG_ERR_INVALID;
+  return node_search(device, 0, f_nleft, nnratio,
+                     HostSide{n_kf, kf_desc, nullptr, kf_angle, nullptr, kf_valid, {kf_node_id, kf_off, kf_idx, kf_nodes}},
+                     HostSide{n_f, f_desc, nullptr, f_angle, nullptr, nullptr, {f_node_id, f_off, f_idx, f_nodes}}, nullptr, nullptr,
+                     check_orientation, match_f);
 }
 
 int vsg_search_by_bow_kf_kf(int device, const uint8_t *desc1, const float *angle1, const uint8_t *valid1, int n1,
@@ -1234,10 +1158,10 @@ int vsg_search_by_bow_kf_kf(int device, const uint8_t *desc1, const float *angle
                             const uint8_t *desc2, const float *angle2, const uint8_t *valid2, int n2,
                             const int32_t *node_id2, const int32_t *off2, const int32_t *idx2, int nodes2,
                             float nnratio, int check_orientation, int32_t *matches12) {
-  if (!matches12 || n1 < 0 || n2 < 0) return VSG_ERR_INVALID;
-  return search_by_bow(device, 1, -1, desc1, nullptr, [&](int i) { return angle1[i]; }, valid1, n1, node_id1, off1, idx1,
-                       nodes1, desc2, nullptr, [&](int i) { return angle2[i]; }, valid2, n2, node_id2, off2, idx2, nodes2,
-                       nnratio, check_orientation, matches12);
+  if (!matches12) return VSG_ERR_INVALID;
+  return node_search(device, 1, -1, nnratio, HostSide{n1, desc1, nullptr, angle1, nullptr, valid1, {node_id1, off1, idx1, nodes1}},
+                     HostSide{n2, desc2, nullptr, angle2, nullptr, valid2, {node_id2, off2, idx2, nodes2}}, nullptr, nullptr,
+                     check_orientation, matches12);
 }
 
 // the same two searches with both descriptor sets resident (vsg_frame): only FeatureVectors + flags go up
@@ -1246,29 +1170,27 @@ int vsg_frame_search_by_bow_kf_f(vsg_frame *kf, const uint8_t *kf_valid, const i
                                  const int32_t *f_node_id, const int32_t *f_off, const int32_t *f_idx, int f_nodes,
                                  float nnratio, int check_orientation, int32_t *match_f) {
   // an empty frame's arrays may be NULL (std::vector::data() of an empty vector)
-  if (!kf || !f || (!match_f && f->n > 0) || kf->device != f->device || (!kf_valid && kf->n > 0)) return VSG_ERR_INVALID;
+  if (vsg::frame_check(kf) != VSG_OK || vsg::frame_check(f) != VSG_OK || (!match_f && f->n > 0) || kf->device != f->device ||
+      (!kf_valid && kf->n > 0))
+    return VSG_ERR_INVALID;
   if (!kf_node_id && !f_node_id)  // both FeatureVectors resident (ComputeBoW ran on both frames): nothing goes up but the flags
     return search_by_bow_resident(0, kf, kf_valid, f, nullptr, nnratio, check_orientation, match_f);
-  if (!kf_node_id || !f_node_id || !kf_off || !f_off || !kf_idx || !f_idx) return VSG_ERR_INVALID;
-  const vsg_keypoint *ka = kf->h_kps.data(), *kb = f->h_kps.data();
-  return search_by_bow(kf->device, 0, f->nleft, nullptr, kf->d_desc, [&](int i) { return ka[i].angle; }, kf_valid, kf->n,
-                       kf_node_id, kf_off, kf_idx, kf_nodes, nullptr, f->d_desc, [&](int i) { return kb[i].angle; },
-                       nullptr, f->n, f_node_id, f_off, f_idx, f_nodes, nnratio, check_orientation, match_f);
+  if (!kf_node_id || !f_node_id || !kf_off || !f_off || !kf_idx || !f_idx) return VSG_ERR_INVALID;  // only SOME of them
+  return node_search(kf->device, 0, f->nleft, nnratio, frame_side(kf, kf_valid, kf_node_id, kf_off, kf_idx, kf_nodes),
+                     frame_side(f, nullptr, f_node_id, f_off, f_idx, f_nodes), nullptr, nullptr, check_orientation, match_f);
 }
 
 int vsg_frame_search_by_bow_kf_kf(vsg_frame *kf1, const uint8_t *valid1, const int32_t *node_id1, const int32_t *off1,
                                   const int32_t *idx1, int nodes1, vsg_frame *kf2, const uint8_t *valid2,
                                   const int32_t *node_id2, const int32_t *off2, const int32_t *idx2, int nodes2,
                                   float nnratio, int check_orientation, int32_t *matches12) {
-  if (!kf1 || !kf2 || (!matches12 && kf1->n > 0) || kf1->device != kf2->device || (!valid1 && kf1->n > 0) ||
-      (!valid2 && kf2->n > 0))
+  if (vsg::frame_check(kf1) != VSG_OK || vsg::frame_check(kf2) != VSG_OK || (!matches12 && kf1->n > 0) ||
+      kf1->device != kf2->device || (!valid1 && kf1->n > 0) || (!valid2 && kf2->n > 0))
     return VSG_ERR_INVALID;
   if (!node_id1 && !node_id2) return search_by_bow_resident(1, kf1, valid1, kf2, valid2, nnratio, check_orientation, matches12);
-  if (!node_id1 || !node_id2 || !off1 || !off2 || !idx1 || !idx2) return VSG_ERR_INVALID;
-  const vsg_keypoint *ka = kf1->h_kps.data(), *kb = kf2->h_kps.data();
-  return search_by_bow(kf1->device, 1, -1, nullptr, kf1->d_desc, [&](int i) { return ka[i].angle; }, valid1, kf1->n,
-                       node_id1, off1, idx1, nodes1, nullptr, kf2->d_desc, [&](int i) { return kb[i].angle; }, valid2,
-                       kf2->n, node_id2, off2, idx2, nodes2, nnratio, check_orientation, matches12);
+  if (!node_id1 || !node_id2 || !off1 || !off2 || !idx1 || !idx2) return VSG_ERR_INVALID;  // only SOME of them
+  return node_search(kf1->device, 1, -1, nnratio, frame_side(kf1, valid1, node_id1, off1, idx1, nodes1),
+                     frame_side(kf2, valid2, node_id2, off2, idx2, nodes2), nullptr, nullptr, check_orientation, matches12);
 }
 
 int vsg_search_by_projection_last(int device, const uint8_t *q_desc, const float *q_angle,
