@@ -557,12 +557,48 @@ int vsg_mappoints_capacity(const vsg_mappoints *mp);
 /* SetWorldPos / AddObservation / ComputeDistinctiveDescriptors / UpdateNormalAndDepth of n slots (MapPoint.cc:116,
  * 141, 340, 440): entry i of every non-NULL field array goes to slot slots[i]; a NULL field keeps what the slots
  * hold.  A slot listed more than once takes its LAST entry.  A slot outside [0, capacity): VSG_ERR_INVALID and nothing
- * is written.  One scatter kernel, no copy per field. */
+ * is written.  One scatter kernel, no copy per field.  desc, normal, min_dist and max_dist are DERIVED from a point's
+ * observations in keyframes: the caller either computes them and sends them here, or sends the observation lists to
+ * vsg_mappoints_refresh_from_observations below, which computes and writes them on the device. */
 int vsg_mappoints_update(vsg_mappoints *mp, int n, const int32_t *slots, const float *world_pos, const float *normal,
                          const float *min_dist, const float *max_dist, const uint8_t *desc, const uint8_t *observed);
 /* test / debug read-back of n slots (any out pointer may be NULL) */
 int vsg_mappoints_read(vsg_mappoints *mp, int n, const int32_t *slots, float *world_pos, float *normal, float *min_dist,
                        float *max_dist, uint8_t *desc, uint8_t *observed);
+
+/* void MapPoint::ComputeDistinctiveDescriptors() (MapPoint.cc:340-417) and void MapPoint::UpdateNormalAndDepth()
+ * (MapPoint.cc:440-513) of n map points from their observations in resident keyframes, written into the slots on the
+ * device: the caller sends a few integers per observation instead of gathering descriptors, computing and uploading.
+ * Point i = slot slots[i]; its observations (mObservations in the std::map's order, one per keyframe: its leftIndex)
+ * are entries [obs_off[i], obs_off[i + 1]) of obs_kf (index into kfs), obs_idx (leftIndex in that keyframe) and obs_bad
+ * (pKF->isBad(); NULL: none); ref_pos[i] = the position of mpRefKF's observation inside that list.  kfs[k] holds
+ * keyframe k's mDescriptors and mvKeysUn, kf_Ow[3 k] = its GetCameraCenter().  scale_factors = mvScaleFactors,
+ * nlevels = mnScaleLevels, in [1, 16].  what = the fields to refresh; fields it does not name stay byte-identical.
+ *   - A bad keyframe's observation is left out of the descriptor candidates (:363); it is still summed into the normal
+ *     (:461-482 has no such test) and may be the reference observation (:484-492).
+ *   - A point with an empty list keeps all four fields (:354, :455); its best is -1, its outs are what the slot holds.
+ *   - A point whose candidates are all bad keeps its descriptor (:379), best -1; its normal and depth are updated.
+ *   - best[i] = the position inside point i's list of the chosen observation: the first row with the least median
+ *     wins (strict '<', :406); the caller copies that row of its own mDescriptors into mDescriptor (:415).  -1 when
+ *     what does not name VSG_REFRESH_DESC.
+ *   - normal / min_dist / max_dist (outs) = mNormalVector, mfMinDistance, mfMaxDistance as the slot holds them after
+ *     the call (:509-511).  Float arithmetic in a fixed order, one rounding per operation, the sum serial in list order
+ *     (csrc/vsg_observations.h).  Pos == a camera centre gives NaN, as in the reference.
+ *   - world_pos is read from the store: the caller has sent SetWorldPos before (vsg_mappoints_update).
+ * Any out may be NULL.  Checked before anything is enqueued (an error leaves no kernel behind and writes nothing):
+ * offsets that do not ascend from 0, an observation outside [0, n_kf) x [0, N of that keyframe), a slot outside
+ * [0, capacity) or listed twice, a ref_pos outside a non-empty list, a reference keypoint whose octave is >= nlevels,
+ * nlevels outside [1, 16], what outside 1 .. 3, a keyframe on another device than the store: VSG_ERR_INVALID; a keyframe
+ * with Nleft != -1 (:475-481, :494-501), or a point with more than 128 observations that are not bad (the cap of
+ * vsg_distinctive_descriptors): VSG_ERR_UNSUPPORTED.  n == 0: VSG_OK, nothing is touched.  One enqueue on the calling
+ * thread's stream and one wait: the call returns when the store is written, as vsg_mappoints_update. */
+#define VSG_REFRESH_DESC 1   /* ComputeDistinctiveDescriptors -> desc */
+#define VSG_REFRESH_NORMAL 2 /* UpdateNormalAndDepth -> normal, min_dist, max_dist */
+int vsg_mappoints_refresh_from_observations(vsg_mappoints *mp, int n, const int32_t *slots, const int32_t *obs_off,
+                                            const int32_t *obs_kf, const int32_t *obs_idx, const uint8_t *obs_bad,
+                                            const int32_t *ref_pos, int n_kf, vsg_frame *const *kfs, const float *kf_Ow,
+                                            const float *scale_factors, int nlevels, int what, int32_t *best,
+                                            float *normal, float *min_dist, float *max_dist);
 
 /* The camera of one Frame as isInFrustum uses it (Frame.h:203-204, 316-318; set by Frame::UpdatePoseMatrices,
  * Frame.cc:612-619): Rcw = mRcw row-major, tcw = mtcw, Ow = mOw (passed, not derived: the reference stores it),

@@ -535,6 +535,14 @@ typedef vsg_frame_pose FramePose;
 // What isInFrustum and SearchByProjection(F, vpMapPoints) read of the local map's MapPoints, resident on the device
 // (vsg_mappoints).  A slot is the maintainer's own index of a MapPoint*.  minDist / maxDist are the MEMBERS mfMinDistance /
 // mfMaxDistance (PredictScale divides the unscaled one, MapPoint.cc:555), not the getters' 0.8f / 1.2f multiples.
+// What ResidentMapPoints::Refresh leaves behind per listed point: best = the position inside the point's observation
+// list of the descriptor ComputeDistinctiveDescriptors chose (-1: mDescriptor is kept), and mNormalVector (3 floats per
+// point), mfMinDistance, mfMaxDistance as the slot holds them after the call
+struct RefreshResult {
+  std::vector<int32_t> best;
+  std::vector<float> normal, minDist, maxDist;
+};
+
 class ResidentMapPoints {
  public:
   explicit ResidentMapPoints(int capacity, int device = 0) {
@@ -550,6 +558,31 @@ class ResidentMapPoints {
               const float *maxDist, const uint8_t *desc, const uint8_t *observed) {
     check(vsg_mappoints_update(mp_, (int)slots.size(), slots.data(), worldPos, normal, minDist, maxDist, desc, observed),
           "vsg_mappoints_update");
+  }
+  // MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth of slots.size() points from their
+  // observations, on the device (vsg_mappoints_refresh_from_observations): point i has the observations
+  // [obsOff[i], obsOff[i + 1]) of obsKf (index into keyFrames = ResidentFrame::handle() of each keyframe), obsIdx
+  // (leftIndex) and obsBad (pKF->isBad(); empty: none); refPos[i] = where mpRefKF's observation sits in that list;
+  // kfOw = GetCameraCenter(), 3 floats per keyframe.  what = VSG_REFRESH_DESC | VSG_REFRESH_NORMAL or one of them.
+  RefreshResult Refresh(const std::vector<int32_t> &slots, const std::vector<int32_t> &obsOff,
+                        const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                        const std::vector<uint8_t> &obsBad, const std::vector<int32_t> &refPos,
+                        const std::vector<vsg_frame *> &keyFrames, const std::vector<float> &kfOw,
+                        const std::vector<float> &mvScaleFactors, int what = VSG_REFRESH_DESC | VSG_REFRESH_NORMAL) {
+    const size_t n = slots.size();
+    if (obsOff.size() != n + 1 || refPos.size() != n || obsKf.size() != obsIdx.size() ||
+        (!obsBad.empty() && obsBad.size() != obsKf.size()) || kfOw.size() != 3 * keyFrames.size() ||
+        (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())))
+      throw std::runtime_error("ResidentMapPoints::Refresh: the arrays' sizes do not match");
+    RefreshResult r;
+    r.best.assign(n, -1), r.normal.assign(3 * n, 0.0f), r.minDist.assign(n, 0.0f), r.maxDist.assign(n, 0.0f);
+    check(vsg_mappoints_refresh_from_observations(mp_, (int)n, slots.data(), obsOff.data(), obsKf.data(), obsIdx.data(),
+                                                  obsBad.empty() ? nullptr : obsBad.data(), refPos.data(),
+                                                  (int)keyFrames.size(), keyFrames.data(), kfOw.data(),
+                                                  mvScaleFactors.data(), (int)mvScaleFactors.size(), what, r.best.data(),
+                                                  r.normal.data(), r.minDist.data(), r.maxDist.data()),
+          "vsg_mappoints_refresh_from_observations");
+    return r;
   }
   vsg_mappoints *handle() const { return mp_; }
 

@@ -1,8 +1,12 @@
 // What a caller of the library does per call WITHOUT resident map points, for tools/resident_points_probe.py's side A:
-// the routine's per-point loop on the host (the kernels' own arithmetic, visual_sgraphs_amd/csrc/vsg_frustum.h and
-// vsg_project.h, compiled -O2, one thread) and the gather of what the host-array entry point takes.
+// the routine's per-point loop on the host (the kernels' own arithmetic, visual_sgraphs_amd/csrc/vsg_frustum.h,
+// vsg_project.h and vsg_observations.h, compiled -O2, one thread) and the gather of what the host-array entry point takes.
 #include <string.h>
 
+#include <algorithm>
+#include <vector>
+
+#include "vsg_observations.h"
 #include "vsg_project.h"
 
 extern "C" {
@@ -65,6 +69,55 @@ int kp_host_side(const vsg_frame_pose *pose, const float *bounds, int n, const u
     m++;
   }
   return m;
+}
+
+// What LocalMapping does for the points of a new keyframe without vsg_mappoints_refresh_from_observations: gather every
+// observation's descriptor (rows [32 off[n]], keyframe k's descriptors at kf_desc + 32 * kf_stride * k), then
+// MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:382-415 as the reference runs it: the N x N distances, then a copy
+// and a std::sort of every row) and MapPoint::UpdateNormalAndDepth (vsg_observations.h), into the arrays of
+// vsg_mappoints_update.  choose == 0: the distinctive descriptor is left to the caller (vsg_distinctive_descriptors on
+// `rows`, then rf_take_rows); the rest is done.  kf_octave: the keypoints' octaves, kf_stride per keyframe.
+void rf_host_side(int n, const int32_t *off, const int32_t *kf, const int32_t *idx, const int32_t *ref_pos,
+                  const uint8_t *kf_desc, const int32_t *kf_octave, int kf_stride, const float *kf_Ow, const float *world_pos,
+                  const float *scale_factors, int nlevels, int choose, uint8_t *rows, int32_t *best, uint8_t *desc,
+                  float *normal, float *min_dist, float *max_dist) {
+  for (int k = 0, e = off[n]; k < e; k++)
+    memcpy(rows + 32 * (size_t)k, kf_desc + 32 * ((size_t)kf[k] * kf_stride + idx[k]), 32);
+  std::vector<int> D, row;
+  for (int i = 0; i < n; i++) {
+    const int o = off[i], N = off[i + 1] - o;
+    if (N == 0) continue;
+    if (choose) {
+      D.assign((size_t)N * N, 0);
+      for (int a = 0; a < N; a++)
+        for (int b = a + 1; b < N; b++) {
+          uint32_t wa[8], wb[8];
+          memcpy(wa, rows + 32 * (size_t)(o + a), 32), memcpy(wb, rows + 32 * (size_t)(o + b), 32);
+          int d = 0;
+          for (int w = 0; w < 8; w++) d += vsg::popc32(wa[w] ^ wb[w]);
+          D[(size_t)a * N + b] = D[(size_t)b * N + a] = d;
+        }
+      int best_median = 0x7FFFFFFF, best_idx = 0;
+      for (int a = 0; a < N; a++) {
+        row.assign(D.begin() + (size_t)a * N, D.begin() + (size_t)(a + 1) * N);
+        std::sort(row.begin(), row.end());
+        const int median = row[(size_t)(0.5 * (N - 1))];
+        if (median < best_median) best_median = median, best_idx = a;
+      }
+      best[i] = best_idx;
+      memcpy(desc + 32 * (size_t)i, rows + 32 * (size_t)(o + best_idx), 32);
+    }
+    const int r = o + ref_pos[i];
+    vsg::update_normal_and_depth(world_pos + 3 * (size_t)i, N, kf + o, kf_Ow, ref_pos[i],
+                                 kf_octave[(size_t)kf[r] * kf_stride + idx[r]], scale_factors, nlevels, normal + 3 * (size_t)i,
+                                 min_dist + i, max_dist + i);
+  }
+}
+
+// mDescriptor = vDescriptors[BestIdx].clone() (:415) for the choices of vsg_distinctive_descriptors
+void rf_take_rows(int n, const int32_t *off, const uint8_t *rows, const int32_t *best, uint8_t *desc) {
+  for (int i = 0; i < n; i++)
+    if (best[i] >= 0) memcpy(desc + 32 * (size_t)i, rows + 32 * (size_t)(off[i] + best[i]), 32);
 }
 
 }  // extern "C"

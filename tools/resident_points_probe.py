@@ -14,16 +14,22 @@ changed descriptors, so that the search matches a real share:
   keyframe  Fuse(pKF, vpMapPoints, th), 500 / 1000 / 2000 candidate points, a tenth flagged isBad() / IsInKeyFrame(pKF)
             A = the per-point loop of ORBmatcher.cc:1194-1241 on the host + vsg_frame_fuse
             B = vsg_frame_fuse_points (LocalMapping::SearchInNeighbors fuses one list into 20-30 neighbours, one pose each)
+  refresh   MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth of 500 / 2000 / 8000 points (a keyframe's
+            points, a local and a large bundle adjustment's) observed in 30 resident keyframes of 1000 features
+            A  = gather of the descriptors + both routines' loops on the host + vsg_mappoints_update of the four fields
+            Ap = A with the descriptor choice by vsg_distinctive_descriptors;  B = vsg_mappoints_refresh_from_observations
 
 A is the caller-side path: the host loop (tools/resident_points_cpu.cpp, the kernel's own arithmetic compiled -O2, one
 thread) + the gather of descriptors + the host-array entry point; A2 is A again, the run's own A-vs-A spread.  For B only
 the pose changes (a small rotation per call, the same for every variant).  Host clock around the blocking calls, straight
 through ctypes with preallocated arrays on both sides.  Every call asserts that A and B compute the same result.
 
-usage: resident_points_probe.py <local|last|keyframe> [calls] [out.json]  -> runs the child, writes the record (default
-                                  profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json)
+usage: resident_points_probe.py <local|last|keyframe|refresh> [calls] [out.json]  -> runs the child, writes the record (default
+                                  profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
+                                  mappoints_refresh_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
-       resident_points_probe.py local trace           -> a few B calls at 4000 points, for rocprofv3 --kernel-trace --stats"""
+       resident_points_probe.py local trace           -> a few B calls at 4000 points, for rocprofv3 --kernel-trace --stats
+       resident_points_probe.py refresh trace         -> the same for refresh at 8000 points"""
 import ctypes as C
 import json
 import subprocess
@@ -46,7 +52,8 @@ def host_side(orb):
     out.mkdir(exist_ok=True)
     so = out / "libresident_points_cpu.so"
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
-    src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h"]
+    src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
+           csrc / "vsg_observations.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
                                str(src[0])])
@@ -59,6 +66,10 @@ def host_side(orb):
                                _f32p, _i32p, _f32p]
     H.kp_host_side.argtypes = [pose, _f32p, C.c_int, _u8p, _f32p, _f32p, _f32p, _f32p, _u8p, C.c_float, _f32p, _i32p, _u8p,
                                _f32p, _f32p, _f32p, _f32p, _i32p]
+    H.rf_host_side.restype = H.rf_take_rows.restype = None
+    H.rf_host_side.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p, _i32p, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int,
+                               _u8p, _i32p, _u8p, _f32p, _f32p, _f32p]
+    H.rf_take_rows.argtypes = [C.c_int, _i32p, _u8p, _i32p, _u8p]
     return H
 
 
@@ -299,7 +310,87 @@ class KeyFrame(Case):
         return {"projected_last": int(self.nproj), "fused_last": int(last["B"][0])}
 
 
-CASES = {"local": Local, "last": Last, "keyframe": KeyFrame}
+class Refresh(Case):
+    """MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth of n points of the store: 30 keyframes of 1000
+    features with random descriptors, observation counts 2 + Gamma(1.5, 4) rounded and clipped to [2, 40] (mean near 8; a
+    list longer than 30 names some keyframes twice), no keyframe bad.  Before every variant of every call the four fields of
+    the listed slots are zeroed (outside the clock); after it the slots are read back (outside the clock) and compared."""
+    SIZES, TH, DEST = (500, 2000, 8000), 0.0, "mappoints_refresh_latency.json"
+    VARIANTS = ("A", "B", "A2", "Ap")
+    NKF, KFN = 30, 1000
+
+    def __init__(self, orb, fr, n):
+        self.orb, self.n = orb, n
+        rng = np.random.default_rng(n)
+        self.sf = (np.float32(1.2) ** np.arange(8, dtype=np.float32)).astype(np.float32)
+        m = np.clip(np.rint(2 + rng.gamma(1.5, 4.0, n)), 2, 40).astype(np.int64)
+        self.off = np.concatenate([[0], np.cumsum(m)]).astype(np.int32)
+        self.kf = np.concatenate([np.concatenate([rng.permutation(self.NKF), rng.integers(0, self.NKF, 10)])[:k]
+                                  for k in m]).astype(np.int32)
+        self.idx = rng.integers(0, self.KFN, len(self.kf)).astype(np.int32)
+        self.ref = (rng.random(n) * m).astype(np.int32)
+        self.kdesc = rng.integers(0, 256, (self.NKF, self.KFN, 32), dtype=np.uint8)
+        self.koct = rng.integers(0, 8, (self.NKF, self.KFN)).astype(np.int32)
+        self.Ow = rng.normal(0, 2.5, (self.NKF, 3)).astype(np.float32)
+        self.pos = np.ascontiguousarray((rng.uniform(-6, 6, (n, 3)) + [0, 0, 12]).astype(np.float32))
+        self.frames = []
+        for k in range(self.NKF):
+            keys = np.zeros(self.KFN, orb.KP_DTYPE)
+            keys["octave"] = self.koct[k]
+            keys["x"], keys["y"] = rng.uniform(0, 640, self.KFN), rng.uniform(0, 480, self.KFN)
+            self.frames.append(orb.Frame(self.KFN + 1).upload(keys, self.kdesc[k], (0.0, 0.0, 640.0, 480.0)))
+        self.handles = (C.c_void_p * self.NKF)(*[f.handle for f in self.frames])
+        self.slots = rng.permutation(2 * n)[:n].astype(np.int32)  # a store twice the size, the points scattered over it
+        self.mp = orb.MapPoints(2 * n)
+        self.mp.update(self.slots, world_pos=self.pos)
+        z = np.zeros
+        self.rows, self.best, self.desc = z((len(self.kf), 32), np.uint8), z(n, np.int32), z((n, 32), np.uint8)
+        self.nrm, self.mn, self.mx = z((n, 3), np.float32), z(n, np.float32), z(n, np.float32)
+        self.zero = dict(normal=z((n, 3), np.float32), min_dist=z(n, np.float32), max_dist=z(n, np.float32),
+                         desc=z((n, 32), np.uint8))
+        self.m = m
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.mp.update(self.slots, **self.zero)
+        self.best[:] = -1
+
+    def host(self, L, H, choose):
+        H.rf_host_side(self.n, p(self.off, _i32p), p(self.kf, _i32p), p(self.idx, _i32p), p(self.ref, _i32p),
+                       p(self.kdesc, _u8p), p(self.koct, _i32p), self.KFN, p(self.Ow, _f32p), p(self.pos, _f32p),
+                       p(self.sf, _f32p), 8, choose, p(self.rows, _u8p), p(self.best, _i32p), p(self.desc, _u8p),
+                       p(self.nrm, _f32p), p(self.mn, _f32p), p(self.mx, _f32p))
+        if not choose:
+            rc = L.vsg_distinctive_descriptors(0, p(self.rows, _u8p), p(self.off, _i32p), self.n, p(self.best, _i32p))
+            if rc != 0:
+                return rc
+            H.rf_take_rows(self.n, p(self.off, _i32p), p(self.rows, _u8p), p(self.best, _i32p), p(self.desc, _u8p))
+        return L.vsg_mappoints_update(self.mp.handle, self.n, p(self.slots, _i32p), None, p(self.nrm, _f32p), p(self.mn, _f32p),
+                                      p(self.mx, _f32p), p(self.desc, _u8p), None)
+
+    def B(self, L, P=None):
+        return L.vsg_mappoints_refresh_from_observations(
+            self.mp.handle, self.n, p(self.slots, _i32p), p(self.off, _i32p), p(self.kf, _i32p), p(self.idx, _i32p), None,
+            p(self.ref, _i32p), self.NKF, self.handles, p(self.Ow, _f32p), p(self.sf, _f32p), 8, 3, p(self.best, _i32p), None,
+            None, None)
+
+    def run(self, name, L, H, P):
+        return self.B(L) if name == "B" else self.host(L, H, 0 if name == "Ap" else 1)
+
+    def result(self, name, r):
+        s = self.mp.read(self.slots)
+        return (r, self.best.copy(), np.frombuffer(s["desc"].tobytes(), np.uint8), s["normal"].view(np.uint32).copy(),
+                s["min_dist"].view(np.uint32).copy(), s["max_dist"].view(np.uint32).copy())
+
+    def facts(self, last):
+        return {"observations": int(len(self.kf)), "mean_observations": round(float(self.m.mean()), 2),
+                "max_observations": int(self.m.max()), "keyframes": self.NKF, "features_per_keyframe": self.KFN,
+                "best_not_first": int((last["B"][1] != 0).sum())}
+
+
+CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh}
 
 
 def child(case, calls):
@@ -330,13 +421,23 @@ def child(case, calls):
         # the resident call is "not slower" when its 10-90 % range does not lie wholly above the caller-side path's
         res["resident_not_slower"] = bool(res["B"]["p10_us"] <= max(res["A"]["p90_us"], res["A2"]["p90_us"]))
         res["resident_faster"] = bool(res["B"]["p90_us"] < min(res["A"]["p10_us"], res["A2"]["p10_us"]))
+        # ... and its median gain counts when it is larger than the run's own A-vs-A gap
+        res["resident_median_gain_us"] = round(res["A"]["median_us"] - res["B"]["median_us"], 1)
+        res["gain_exceeds_a_vs_a_gap"] = bool(res["resident_median_gain_us"] > res["a_vs_a_median_gap_us"])
         out["sizes"][str(n)] = res
     print(json.dumps(out))
 
 
-def trace():
+def trace(case="local"):
     import frustum_reference as fr
     from visual_sgraphs_amd import orb
+    if case == "refresh":
+        L, c = orb.load_library(), Refresh(orb, fr, 8000)
+        for k in range(10):
+            c.reset()
+            assert c.B(L) == 0
+        print({"n": 8000, "observations": len(c.kf), "best_not_first": int((c.best != 0).sum())})
+        return
     L, c = orb.load_library(), Local(orb, fr, 4000)
     for k in range(10):
         c.reset()
@@ -348,7 +449,7 @@ def main(argv):
     if argv[0] == "child":
         return child(argv[1], int(argv[2]) if len(argv) > 2 else 200)
     if argv[1:] == ["trace"]:
-        return trace()
+        return trace(argv[0])
     calls = int(argv[1]) if len(argv) > 1 else 200
     dest = Path(argv[2]) if len(argv) > 2 else ROOT / "profiles" / CASES[argv[0]].DEST
     r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "child", argv[0], str(calls)], capture_output=True,

@@ -22,6 +22,8 @@
 
 #include "vsg_frame_int.h"
 #include "vsg_frustum.h"
+#include "vsg_obs_args.h"
+#include "vsg_observations.h"
 #include "vsg_project.h"
 
 using namespace vsg;
@@ -207,6 +209,142 @@ __global__ __launch_bounds__(64) void k_project_points(StoreDev S, const int32_t
   if (O.level) O.level[i] = o.level;
   if (O.observed) O.observed[i] = observed;
   Q[i] = w;
+}
+
+// ---- vsg_mappoints_refresh_from_observations: MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:340-417) and
+// MapPoint::UpdateNormalAndDepth (:440-513) of many map points from their observation lists, written into the slots.
+// One entry of the keyframe table per keyframe: where its descriptors and keypoints live on the device (read from the
+// vsg_frame handles by the call itself) and its camera centre.
+struct KfEntry {
+  const uint8_t *desc;
+  const KeyPointPOD *kps;
+  float Ow[3];
+  int32_t pad;
+};
+struct RefreshArgs {
+  const KfEntry *table;
+  const int32_t *order;  // point indices: the launch handles order[first .. first + count)
+  const int32_t *slots, *off, *kf, *idx;
+  const uint8_t *bad;  // nullptr: no observation is bad
+  const int32_t *ref_pos;
+  int first, count, what, nlevels;
+  float scale_factors[16];
+  int32_t *best;  // the outs, by point index, in the pinned arena
+  float *normal, *min_dist, *max_dist;
+};
+
+__device__ __forceinline__ int hamming_u4(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
+  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
+         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// A group of kLanes lanes (one wavefront, or a workgroup of two) per map point, kPts groups per workgroup: real
+// observation counts are 3 to 20, and one workgroup per point would leave most of the chip idle.  The host sends a point
+// to the form whose kLanes holds its observations that are not bad (obs_check: at most 128); every index the kernel forms
+// is one obs_check has bounded.  Every barrier is reached by every lane: nothing returns early.
+//   1. 64 observations at a time: lane j reads observation j's bad flag and computes its unit vector; the ballot of the
+//      flags gives the list positions of the good observations in order (s_good), and the unit vectors are added SERIALLY
+//      in list order (every lane adds the same values: float addition does not associate, vsg_observations.h).
+//   2. lane j fetches good observation j's 32 bytes through the table into the LDS tile; every later pass reads LDS.
+//   3. lane i computes row i of the distance matrix into its own LDS column and finds the element of rank
+//      (int)(0.5 * (N - 1)) by bisection on the VALUE (9 bits: 9 counting passes, not N): the least v with
+//      #{x <= v} > rank.
+//   4. the least (median << 16 | i) over the group: the first row with the least median (strict '<', :406); that row
+//      goes from the tile into the slot as two uint4 stores.
+template <int kLanes, int kPts>
+__global__ __launch_bounds__(kLanes *kPts) void k_refresh(StoreDev S, RefreshArgs A) {
+  constexpr int kWaves = kLanes / 64;
+  __shared__ uint4 s_desc[kPts][kLanes][2];
+  __shared__ uint16_t s_D[kPts][kLanes * kLanes];  // [j][i]: lane i's column, written and read by lane i alone
+  __shared__ int32_t s_good[kPts][kLanes];
+  __shared__ uint32_t s_key[kPts][kWaves];
+  const int g = threadIdx.x / kLanes, t = threadIdx.x % kLanes, lane = threadIdx.x & 63, gw = t >> 6;
+  const int q = blockIdx.x * kPts + g;
+  const bool active = q < A.count;
+  int p = 0, s = 0, o = 0, m = 0;
+  float P[3] = {0.0f, 0.0f, 0.0f};
+  if (active) {
+    p = A.order[A.first + q], s = A.slots[p], o = A.off[p], m = A.off[p + 1] - o;
+    copy3(P, S.pos + 3 * (size_t)s);
+  }
+  const bool do_normal = (A.what & VSG_REFRESH_NORMAL) && gw == 0;
+  int ngood = 0;
+  float sum[3] = {0.0f, 0.0f, 0.0f};
+  for (int c = 0; c < m; c += 64) {
+    const int j = c + lane;
+    bool good = false;
+    float u[3] = {0.0f, 0.0f, 0.0f};
+    if (j < m) {
+      good = !(A.bad && A.bad[o + j]);  // pKF->isBad() (:363); UpdateNormalAndDepth has no such test
+      if (do_normal) observation_unit(P, A.table[A.kf[o + j]].Ow, u);
+    }
+    const unsigned long long mask = __ballot(good);
+    const int pos = ngood + __popcll(mask & ((1ull << lane) - 1ull));
+    if (good && gw == 0 && pos < kLanes) s_good[g][pos] = j;
+    ngood += __popcll(mask);
+    if (do_normal) {
+      const int cnt = min(64, m - c);
+      for (int k = 0; k < cnt; k++) {
+        const float uk[3] = {__shfl(u[0], k), __shfl(u[1], k), __shfl(u[2], k)};
+        observation_add(sum, uk);
+      }
+    }
+  }
+  ngood = min(ngood, kLanes);
+  if (active && t == 0) {
+    float nrm[3], mn = S.min_dist[s], mx = S.max_dist[s];
+    copy3(nrm, S.normal + 3 * (size_t)s);
+    if (do_normal && m > 0) {  // :455: no observation, no change
+      const int r = o + A.ref_pos[p];
+      const KfEntry e = A.table[A.kf[r]];
+      const int level = e.kps[A.idx[r]].octave & 15;  // :492; obs_check saw it below nlevels
+      observation_depth(P, e.Ow, A.scale_factors, level, A.nlevels, &mn, &mx);
+      observation_mean(sum, m, nrm);
+      copy3(S.normal + 3 * (size_t)s, nrm);
+      S.min_dist[s] = mn, S.max_dist[s] = mx;
+    }
+    copy3(A.normal + 3 * (size_t)p, nrm);
+    A.min_dist[p] = mn, A.max_dist[p] = mx;
+  }
+  const bool do_desc = active && (A.what & VSG_REFRESH_DESC) && ngood > 0;  // :354, :379
+  __syncthreads();
+  uint4 d0 = {0, 0, 0, 0}, d1 = {0, 0, 0, 0};
+  if (do_desc && t < ngood) {
+    const int j = o + s_good[g][t];
+    const uint4 *src = (const uint4 *)(A.table[A.kf[j]].desc + 32 * (size_t)A.idx[j]);
+    d0 = src[0], d1 = src[1];
+    s_desc[g][t][0] = d0, s_desc[g][t][1] = d1;
+  }
+  __syncthreads();
+  uint32_t key = 0xFFFFFFFFu;
+  if (do_desc && t < ngood) {
+    uint16_t *D = s_D[g] + t;
+    for (int j = 0; j < ngood; j++) D[j * kLanes] = (uint16_t)hamming_u4(d0, d1, s_desc[g][j][0], s_desc[g][j][1]);
+    const int rank = (ngood - 1) >> 1;  // vDists[0.5 * (N - 1)] (:404)
+    int lo = 0, hi = 256;
+    for (int it = 0; it < 9; it++) {  // [0, 256] holds 257 values: 9 halvings
+      const int mid = (lo + hi) >> 1;
+      int le = 0;
+      for (int j = 0; j < ngood; j++) le += D[j * kLanes] <= mid;
+      if (le > rank)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    key = ((uint32_t)lo << 16) | (uint32_t)t;
+  }
+  for (int d = 32; d > 0; d >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, d));
+  if (lane == 0) s_key[g][gw] = key;
+  __syncthreads();
+  if (do_desc) {
+    uint32_t b = s_key[g][0];
+    for (int w = 1; w < kWaves; w++) b = min(b, s_key[g][w]);
+    const int win = (int)(b & 0xFFFFu);
+    if (t < 2) ((uint4 *)(S.desc + 32 * (size_t)s))[t] = s_desc[g][win][t];
+    if (t == 0) A.best[p] = s_good[g][win];
+  } else if (active && t == 0) {
+    A.best[p] = -1;
+  }
 }
 
 int store_check(const vsg_mappoints *mp) { return mp && mp->d_block ? VSG_OK : VSG_ERR_INVALID; }
@@ -519,6 +657,90 @@ int vsg_mappoints_read(vsg_mappoints *mp, int n, const int32_t *slots, float *wo
   if (max_dist) memcpy(max_dist, hp + L.oMax, N * 4);
   if (desc) memcpy(desc, hp + L.oD, N * 32);
   if (observed) memcpy(observed, hp + L.oO, N);
+  return VSG_OK;
+}
+
+int vsg_mappoints_refresh_from_observations(vsg_mappoints *mp, int n, const int32_t *slots, const int32_t *obs_off,
+                                            const int32_t *obs_kf, const int32_t *obs_idx, const uint8_t *obs_bad,
+                                            const int32_t *ref_pos, int n_kf, vsg_frame *const *kfs, const float *kf_Ow,
+                                            const float *scale_factors, int nlevels, int what, int32_t *best,
+                                            float *normal, float *min_dist, float *max_dist) {
+  if (store_check(mp) != VSG_OK || n < 0 || n_kf < 0 || !scale_factors) return VSG_ERR_INVALID;
+  if (what < 1 || what > (VSG_REFRESH_DESC | VSG_REFRESH_NORMAL)) return VSG_ERR_INVALID;
+  if (n_kf > 0 && (!kfs || !kf_Ow)) return VSG_ERR_INVALID;
+  for (int k = 0; k < n_kf; k++)
+    if (frame_check(kfs[k]) != VSG_OK || kfs[k]->device != mp->device) return VSG_ERR_INVALID;
+  for (int k = 0; k < n_kf; k++)  // GetRightCameraCenter, mvKeysRight (:475-481, :494-501)
+    if (kfs[k]->nleft != -1) return VSG_ERR_UNSUPPORTED;
+  std::vector<int32_t> kf_n((size_t)n_kf), good;
+  std::vector<const vsg_keypoint *> kf_kps((size_t)n_kf);
+  for (int k = 0; k < n_kf; k++) {
+    const size_t have = kfs[k]->h_kps.size();
+    kf_n[(size_t)k] = (int32_t)((size_t)kfs[k]->n < have ? (size_t)kfs[k]->n : have);
+    kf_kps[(size_t)k] = kfs[k]->h_kps.data();
+  }
+  const ObsView view = {n,    slots,       obs_off,       obs_kf,       obs_idx, obs_bad, ref_pos,
+                        n_kf, kf_n.data(), kf_kps.data(), mp->capacity, nlevels};
+  int rc = obs_check(view, &good);
+  if (rc != VSG_OK || n == 0) return rc;
+  // everything the kernels index has been bounded; nothing has been enqueued
+  ThreadCtx *c = thread_ctx(mp->device, &rc);
+  if (!c) return rc;
+  const size_t N = (size_t)n, T = (size_t)obs_off[n], K = (size_t)n_kf;
+  Stage st;
+  const size_t oTab = st.add(K * sizeof(KfEntry)), oS = st.add(N * 4), oOff = st.add((N + 1) * 4), oKf = st.add(T * 4),
+               oIdx = st.add(T * 4), oBad = st.add(obs_bad ? T : 0), oRef = st.add(N * 4), oOrd = st.add(N * 4);
+  const size_t in_bytes = st.total;
+  const size_t oBest = st.add(N * 4), oNrm = st.add(N * 12), oMin = st.add(N * 4), oMax = st.add(N * 4);
+  rc = ctx_reserve(c, st.total, in_bytes);
+  if (rc != VSG_OK) return rc;
+  uint8_t *hp = c->h_pin, *dv = c->d_buf, *dp = c->d_pin;
+  KfEntry *tab = (KfEntry *)(hp + oTab);
+  for (size_t k = 0; k < K; k++) {  // the frames' pointers as they are NOW
+    tab[k].desc = kfs[k]->d_desc, tab[k].kps = kfs[k]->d_kps, tab[k].pad = 0;
+    tab[k].Ow[0] = kf_Ow[3 * k], tab[k].Ow[1] = kf_Ow[3 * k + 1], tab[k].Ow[2] = kf_Ow[3 * k + 2];
+  }
+  memcpy(hp + oS, slots, N * 4);
+  memcpy(hp + oOff, obs_off, (N + 1) * 4);
+  if (T) memcpy(hp + oKf, obs_kf, T * 4), memcpy(hp + oIdx, obs_idx, T * 4);
+  if (T && obs_bad) memcpy(hp + oBad, obs_bad, T);
+  if (ref_pos)
+    memcpy(hp + oRef, ref_pos, N * 4);
+  else
+    memset(hp + oRef, 0, N * 4);
+  // points of at most 64 candidates first (one wavefront each), then those of 65 .. 128 (one workgroup each)
+  static_assert(kObsMaxCandidates == 128, "k_refresh<128, 1> holds the longest list obs_check accepts");
+  int32_t *ord = (int32_t *)(hp + oOrd);
+  int n_small = 0;
+  for (int i = 0; i < n; i++)
+    if (good[(size_t)i] <= 64) ord[n_small++] = i;
+  int n_all = n_small;
+  for (int i = 0; i < n; i++)
+    if (good[(size_t)i] > 64) ord[n_all++] = i;
+  TRY_HIP(hipMemcpyAsync(dv, hp, in_bytes, hipMemcpyHostToDevice, c->stream));
+  RefreshArgs A;
+  memset(&A, 0, sizeof(A));
+  A.table = (const KfEntry *)(dv + oTab), A.order = (const int32_t *)(dv + oOrd), A.slots = (const int32_t *)(dv + oS);
+  A.off = (const int32_t *)(dv + oOff), A.kf = (const int32_t *)(dv + oKf), A.idx = (const int32_t *)(dv + oIdx);
+  A.bad = obs_bad ? dv + oBad : nullptr, A.ref_pos = (const int32_t *)(dv + oRef);
+  A.what = what, A.nlevels = nlevels;
+  for (int l = 0; l < nlevels; l++) A.scale_factors[l] = scale_factors[l];
+  A.best = (int32_t *)(dp + oBest), A.normal = (float *)(dp + oNrm);
+  A.min_dist = (float *)(dp + oMin), A.max_dist = (float *)(dp + oMax);
+  if (n_small > 0) {
+    A.first = 0, A.count = n_small;
+    hipLaunchKernelGGL((k_refresh<64, 4>), dim3((n_small + 3) / 4), dim3(256), 0, c->stream, store_dev(mp), A);
+  }
+  if (n_all > n_small) {
+    A.first = n_small, A.count = n_all - n_small;
+    hipLaunchKernelGGL((k_refresh<128, 1>), dim3(n_all - n_small), dim3(128), 0, c->stream, store_dev(mp), A);
+  }
+  rc = copy_end(c);
+  if (rc != VSG_OK) return rc;
+  if (best) memcpy(best, hp + oBest, N * 4);
+  if (normal) memcpy(normal, hp + oNrm, N * 12);
+  if (min_dist) memcpy(min_dist, hp + oMin, N * 4);
+  if (max_dist) memcpy(max_dist, hp + oMax, N * 4);
   return VSG_OK;
 }
 

@@ -81,6 +81,8 @@ EXPORTS = [
     # SearchForTriangulation with the epipolar test on the device (its test hook, vsg_debug_epipolar_pairs of
     # include/vsg_orb_debug_epipolar.h, is bound below but is no part of the two headers this list mirrors)
     "vsg_frame_search_for_triangulation_epipolar",
+    # ComputeDistinctiveDescriptors and UpdateNormalAndDepth of resident map points from their observation lists
+    "vsg_mappoints_refresh_from_observations",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -333,6 +335,8 @@ def load_library():
     L.vsg_mappoints_capacity.argtypes = [vp]
     L.vsg_mappoints_update.argtypes = [vp, ci, _i32p, _f32p, _f32p, _f32p, _f32p, _u8p, _u8p]
     L.vsg_mappoints_read.argtypes = [vp, ci, _i32p, _f32p, _f32p, _f32p, _f32p, _u8p, _u8p]
+    L.vsg_mappoints_refresh_from_observations.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, _u8p, _i32p, ci, C.POINTER(vp),
+                                                          _f32p, _f32p, ci, ci, _i32p, _f32p, _f32p, _f32p]
     L.vsg_frame_is_in_frustum.argtypes = [vp, vp, ci, _i32p, C.POINTER(FramePose), cf, _u8p, _f32p, _f32p, _f32p, _f32p,
                                           _i32p, _f32p]
     L.vsg_frame_search_local_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, cf, cf, ci, cf, _f32p,
@@ -1019,6 +1023,9 @@ class KeyFrameDatabase:
         return [int(x) for x in lo[:nl.value]], [int(x) for x in me[:nm.value]]
 
 
+REFRESH_DESC, REFRESH_NORMAL = 1, 2  # include/vsg_orb.h VSG_REFRESH_*
+
+
 class MapPoints:
     """The local map's MapPoints resident on the device (include/vsg_orb.h: vsg_mappoints): per slot GetWorldPos(),
     GetNormal(), the members mfMinDistance / mfMaxDistance (unscaled: PredictScale divides mfMaxDistance itself),
@@ -1077,6 +1084,37 @@ class MapPoints:
         _check(self._L.vsg_mappoints_read(self._h, n, _p(sl, _i32p), _p(out["world_pos"], _f32p), _p(out["normal"], _f32p),
                                           _p(out["min_dist"], _f32p), _p(out["max_dist"], _f32p), _p(out["desc"], _u8p),
                                           _p(out["observed"], _u8p)), "vsg_mappoints_read")
+        return {k: v[:n] for k, v in out.items()}
+
+    def refresh(self, slots, obs_off, obs_kf, obs_idx, ref_pos, keyframes, kf_Ow, scale_factors, obs_bad=None,
+                what=REFRESH_DESC | REFRESH_NORMAL):
+        """MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth of len(slots) points from their
+        observation lists (vsg_mappoints_refresh_from_observations): point i has the observations
+        [obs_off[i], obs_off[i + 1]) of obs_kf (index into `keyframes`, a list of orb.Frame), obs_idx (leftIndex) and
+        obs_bad (pKF->isBad(), None: none); ref_pos[i] = where mpRefKF's observation sits in that list; kf_Ow =
+        GetCameraCenter() per keyframe.  Returns dict(best, normal, min_dist, max_dist): best = the chosen observation's
+        position in the point's list (-1: descriptor kept), the others = what the slots hold after the call."""
+        n, nobs = int(np.asarray(slots).size), int(np.asarray(obs_kf).size)
+        sl, off, kf, idx, ref = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx), _i32(ref_pos)
+        if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != nobs or np.asarray(ref_pos).size != n:
+            raise ValueError("observation arrays do not match the slot list")
+        if nobs < int(off[-1]):
+            raise ValueError("obs_off runs past the observation arrays")
+        bad = _u8(obs_bad) if obs_bad is not None else None
+        if bad is not None and bad.size != nobs:
+            raise ValueError("obs_bad does not match the observation arrays")
+        ow, sf = _f32(kf_Ow).reshape(-1), _f32(scale_factors)
+        if np.asarray(kf_Ow).size != 3 * len(keyframes):
+            raise ValueError("kf_Ow needs 3 floats per keyframe")
+        handles = (C.c_void_p * max(len(keyframes), 1))(*[f.handle for f in keyframes])
+        out = {"best": np.full(max(n, 1), -1, np.int32), "normal": np.zeros((max(n, 1), 3), np.float32),
+               "min_dist": np.zeros(max(n, 1), np.float32), "max_dist": np.zeros(max(n, 1), np.float32)}
+        _check(self._L.vsg_mappoints_refresh_from_observations(
+            self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p),
+            _p(bad, _u8p) if bad is not None and nobs else None, _p(ref, _i32p), len(keyframes), handles, _p(ow, _f32p),
+            _p(sf, _f32p), int(np.asarray(scale_factors).size), int(what),
+            _p(out["best"], _i32p), _p(out["normal"], _f32p), _p(out["min_dist"], _f32p), _p(out["max_dist"], _f32p)),
+            "vsg_mappoints_refresh_from_observations")
         return {k: v[:n] for k, v in out.items()}
 
 
