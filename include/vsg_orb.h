@@ -754,6 +754,52 @@ int vsg_frame_search_sim3_points(vsg_frame *kf, vsg_mappoints *mp, int n, const 
                                  int nlevels, int32_t *matched, uint8_t *projected, float *u, float *v,
                                  int32_t *predicted_level);
 
+/* int Optimizer::PoseOptimization(Frame *pFrame) (Optimizer.h, Optimizer.cc:1063-1452: the !mpCamera2 branches
+ * :1115-1180, the round loop :1254-1442, the pose recovery :1444-1451) on a resident frame and resident map points: the
+ * link between the resident searches above, which project through the pose this routine produces.  One persistent
+ * workgroup runs all four rounds (g2o's OptimizationAlgorithmLevenberg::solve, optimization_algorithm_levenberg.cpp:
+ * 61-194, ten iterations of at most ten trials each; EdgeSE3ProjectXYZOnlyPose, OptimizableTypes.cpp:47-62, and
+ * EdgeStereoSE3ProjectXYZOnlyPose, types_six_dof_expmap.cpp:365-437; Huber, robust_kernel_impl.cpp:78) in double, in one
+ * enqueue and one wait; only the slot of each feature and a pose cross to the device.  The arithmetic is
+ * csrc/vsg_pose_opt.h, which a host build reproduces bit for bit.
+ *   - feat_slots[i], one per feature of F, = the slot of pFrame->mvpMapPoints[i], or < 0 for none.  A feature is stereo
+ *     when the frame's u_right[i] >= 0 (:1118); a frame without u_right is all monocular.
+ *   - Tcw = pFrame->GetPose(): unit_quaternion() as x y z w, translation().  EVERY round starts from it (:1263).
+ *   - fx .. bf = the Frame's floats; inv_level_sigma2 = mvInvLevelSigma2, nlevels entries, nlevels in [1, 16].
+ *   - Returns nInitialCorrespondences - nBad (:1451).  outlier = the storage of mvbOutlier: entry i is written ONLY for
+ *     features with a slot (:1121, :1149, :1361-1367), the others keep their bytes.  chi2 (may be NULL): the float that
+ *     was compared at the last classification that compared feature i (:1357).  res->q / t = vSE3_recov->estimate()
+ *     (:1446; the caller narrows it to the Sophus::SE3f of :1447), n_initial, n_bad, rounds_run.
+ *   - Fewer than 3 features with a slot (:1251): their outlier flags are cleared, res holds the input pose, returns 0,
+ *     nothing is enqueued.  Fewer than 10 edges end the loop after one round (:1440).
+ *   - hold_round = -1 runs everything.  hold_round = 2 runs rounds 0 and 1, then round 2's optimize(), and returns 0
+ *     with res->held = 1, res->q / t = the estimate the host's plane step reads (:1296-1298) and outlier as after round
+ *     1: the vS-Graphs refine_map_points step (:1270-1335) runs on the host HERE, and
+ *     vsg_frame_pose_optimization_resume(F, removed, ...) finishes round 2's classification and round 3, with
+ *     removed[i] != 0 (NULL: none) for the features whose map point that step dropped (mvpMapPoints[j] = NULL,
+ *     mvbOutlier[j] = true): they stay flagged and are counted in nBad in both rounds (:1348-1353), and they leave
+ *     optimizer.edges() (:1440).  If the loop ended before round 2, held = 0 and the call is complete.  The held state
+ *     lives in a device buffer of the frame.  _resume with nothing held, after a call that rewrote the frame's features
+ *     (vsg_frame_upload, vsg_frame_from_extractor*, vsg_orb_extract_to_frame*), or a second time: VSG_ERR_INVALID.
+ * Checked before anything is enqueued (an error leaves no kernel behind and writes nothing): a NULL F, mp, feat_slots,
+ * Tcw, inv_level_sigma2, outlier or res, a slot >= capacity, nlevels outside [1, 16], a feature with a slot whose octave
+ * is >= nlevels, a hold_round other than -1 or 2, store and frame on different devices: VSG_ERR_INVALID; Nleft != -1
+ * (EdgeSE3ProjectXYZOnlyPoseToBody :1182-1246, KannalaBrandt8): VSG_ERR_UNSUPPORTED.
+ * Future work: a chain "search -> optimise" in one enqueue (the search's matches feeding feat_slots on the device). */
+typedef struct vsg_pose_se3 {
+  float q[4]; /* Tcw.unit_quaternion() as x y z w */
+  float t[3]; /* Tcw.translation() */
+} vsg_pose_se3;
+typedef struct vsg_pose_result {
+  double q[4], t[3];
+  int32_t n_initial, n_bad, rounds_run, held;
+} vsg_pose_result;
+int vsg_frame_pose_optimization(vsg_frame *F, vsg_mappoints *mp, const int32_t *feat_slots, const vsg_pose_se3 *Tcw,
+                                float fx, float fy, float cx, float cy, float bf, const float *inv_level_sigma2,
+                                int nlevels, int hold_round, uint8_t *outlier, float *chi2, vsg_pose_result *res);
+int vsg_frame_pose_optimization_resume(vsg_frame *F, const uint8_t *removed, uint8_t *outlier, float *chi2,
+                                       vsg_pose_result *res);
+
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, S12, th) (ORBmatcher.h:76,
  * ORBmatcher.cc:1448-1665).  Direction 1 (:1489-1565): for each KF1 feature i1 with a usable, not yet matched map
  * point that projects into KF2: idx1[k] = i1, its descriptor, (u, v, radius, predicted level) in KF2; direction 2

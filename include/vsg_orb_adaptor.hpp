@@ -741,7 +741,57 @@ class ResidentFrame {
     return rc;
   }
 
+  // int Optimizer::PoseOptimization(Frame *pFrame) (Optimizer.cc:1063-1452) in one call and one wait
+  // (vsg_frame_pose_optimization).  featSlots[i] = the slot of pFrame->mvpMapPoints[i] or < 0, one per feature; Tcw =
+  // pFrame->GetPose() (unit_quaternion() as x y z w, translation()); camera = fx, fy, cx, cy, mbf; outlier = mvbOutlier,
+  // written only for features with a slot.  out.q / out.t make the Sophus::SE3f of :1447 for pFrame->SetPose.  Returns
+  // nInitialCorrespondences - nBad.  holdForPlaneStep: stop after round 2's optimize() (out.held: run the
+  // refine_map_points step of :1270-1335 on out.qd / out.td, then PoseOptimizationResume with the features it dropped;
+  // not held: fewer than 10 edges, the call is complete).
+  struct PoseOptResult {
+    float q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0};   // SE3quat_recov.rotation().cast<float>(), translation().cast<float>()
+    double qd[4] = {0, 0, 0, 1}, td[3] = {0, 0, 0};  // vSE3_recov->estimate()
+    int nInitialCorrespondences = 0, nBad = 0, roundsRun = 0;
+    bool held = false;
+  };
+  int PoseOptimization(const ResidentMapPoints &mp, const std::vector<int32_t> &featSlots, const vsg_pose_se3 &Tcw,
+                       const float camera[5], const std::vector<float> &invLevelSigma2, std::vector<uint8_t> &outlier,
+                       PoseOptResult &out, bool holdForPlaneStep = false, std::vector<float> *chi2 = nullptr) const {
+    if ((int)featSlots.size() != N()) throw std::runtime_error("PoseOptimization: one slot per feature");
+    outlier.resize(featSlots.size() ? featSlots.size() : 1, 0);
+    if (chi2) chi2->resize(outlier.size(), 0.f);
+    vsg_pose_result res;
+    const int rc = vsg_frame_pose_optimization(f_, mp.handle(), featSlots.data(), &Tcw, camera[0], camera[1], camera[2],
+                                               camera[3], camera[4], invLevelSigma2.data(), (int)invLevelSigma2.size(),
+                                               holdForPlaneStep ? 2 : -1, outlier.data(), chi2 ? chi2->data() : nullptr, &res);
+    check(rc, "vsg_frame_pose_optimization");
+    return poseResult(rc, res, featSlots.size(), outlier, chi2, out);
+  }
+  // removed[i] != 0: the plane step set mvpMapPoints[i] = NULL and mvbOutlier[i] = true (nullptr: none)
+  int PoseOptimizationResume(const std::vector<uint8_t> *removed, std::vector<uint8_t> &outlier, PoseOptResult &out,
+                             std::vector<float> *chi2 = nullptr) const {
+    const size_t n = (size_t)N();
+    if (removed && removed->size() != n) throw std::runtime_error("PoseOptimizationResume: one flag per feature");
+    outlier.resize(n ? n : 1, 0);
+    if (chi2) chi2->resize(outlier.size(), 0.f);
+    vsg_pose_result res;
+    const int rc = vsg_frame_pose_optimization_resume(f_, removed ? removed->data() : nullptr, outlier.data(),
+                                                      chi2 ? chi2->data() : nullptr, &res);
+    check(rc, "vsg_frame_pose_optimization_resume");
+    return poseResult(rc, res, n, outlier, chi2, out);
+  }
+
  private:
+  static int poseResult(int rc, const vsg_pose_result &res, size_t n, std::vector<uint8_t> &outlier,
+                        std::vector<float> *chi2, PoseOptResult &out) {
+    for (int k = 0; k < 4; ++k) out.qd[k] = res.q[k], out.q[k] = (float)res.q[k];
+    for (int k = 0; k < 3; ++k) out.td[k] = res.t[k], out.t[k] = (float)res.t[k];
+    out.nInitialCorrespondences = res.n_initial, out.nBad = res.n_bad, out.roundsRun = res.rounds_run;
+    out.held = res.held != 0;
+    outlier.resize(n);
+    if (chi2) chi2->resize(n);
+    return rc;
+  }
   vsg_frame *f_ = nullptr;
 };
 

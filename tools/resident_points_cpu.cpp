@@ -1,12 +1,13 @@
 // What a caller of the library does per call WITHOUT resident map points, for tools/resident_points_probe.py's side A:
 // the routine's per-point loop on the host (the kernels' own arithmetic, visual_sgraphs_amd/csrc/vsg_frustum.h,
-// vsg_project.h and vsg_observations.h, compiled -O2, one thread) and the gather of what the host-array entry point takes.
+// vsg_project.h, vsg_observations.h and vsg_pose_opt.h, compiled -O2, one thread) and the gather of what the host-array entry point takes.
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "vsg_observations.h"
+#include "vsg_pose_opt.h"
 #include "vsg_project.h"
 
 extern "C" {
@@ -118,6 +119,27 @@ void rf_host_side(int n, const int32_t *off, const int32_t *kf, const int32_t *i
 void rf_take_rows(int n, const int32_t *off, const uint8_t *rows, const int32_t *best, uint8_t *desc) {
   for (int i = 0; i < n; i++)
     if (best[i] >= 0) memcpy(desc + 32 * (size_t)i, rows + 32 * (size_t)(off[i] + best[i]), 32);
+}
+
+// Optimizer::PoseOptimization on one host thread: the host build of vsg_pose_opt.h given the arrays the caller holds
+// anyway (mvKeysUn, mvuRight, the map points' positions by slot).  NOT g2o: the same arithmetic as the kernel with its
+// reduction tree replayed serially, no virtual calls, no sparse block structure -- it likely flatters the host.
+// Returns nInitialCorrespondences - nBad; qt[7] = the estimate (q x y z w, t), ri = {n_bad, rounds_run}.
+int po_host_side(int n, const int32_t *feat_slots, const float *world_pos, const float *kx, const float *ky,
+                 const int32_t *octave, const float *u_right, const float *pose7, const float *cam5,
+                 const float *inv_level_sigma2, int nlevels, uint8_t *outlier, float *chi2, double *qt, int32_t *ri) {
+  using namespace vsg;
+  static thread_local pose::HostCall call;  // its vectors keep their capacity from call to call
+  const pose::Est input = pose::est_from_pose(pose7, pose7 + 4);
+  const pose::Cam cam = {(double)cam5[0], (double)cam5[1], (double)cam5[2], (double)cam5[3], (double)cam5[4]};
+  call.gather(n, feat_slots, world_pos, kx, ky, octave, u_right, inv_level_sigma2, nlevels, cam, input);
+  if (call.edges.size() < 3) return 0;
+  call.rounds(pose::kModeAll);
+  call.copy_out(outlier, chi2);
+  for (int k = 0; k < 4; k++) qt[k] = pose::canon(call.ctl.est.q[k]);
+  for (int k = 0; k < 3; k++) qt[4 + k] = pose::canon(call.ctl.est.t[k]);
+  ri[0] = call.ctl.n_bad, ri[1] = call.ctl.rounds_run;
+  return (int)call.edges.size() - call.ctl.n_bad;
 }
 
 }  // extern "C"

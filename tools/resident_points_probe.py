@@ -18,15 +18,21 @@ changed descriptors, so that the search matches a real share:
             points, a local and a large bundle adjustment's) observed in 30 resident keyframes of 1000 features
             A  = gather of the descriptors + both routines' loops on the host + vsg_mappoints_update of the four fields
             Ap = A with the descriptor choice by vsg_distinctive_descriptors;  B = vsg_mappoints_refresh_from_observations
+  pose      Optimizer::PoseOptimization of a 1000-feature frame with 100 / 300 / 1000 correspondences (20 % outliers,
+            half of the features stereo, the start pose a constant-velocity guess 2 cm and 1 degree off)
+            A  = the host build of csrc/vsg_pose_opt.h on one thread, given the same arrays: the caller-side path as far as
+                 it can be built here.  It is NOT g2o (no Eigen here) and likely flatters the host: same arithmetic, no
+                 virtual calls, no sparse block solver.  B = vsg_frame_pose_optimization;  B2 = B again, the device
+                 call's own A-vs-A repeat.  Every call asserts A and B equal bit for bit (pose, chi2, flags)
 
 A is the caller-side path: the host loop (tools/resident_points_cpu.cpp, the kernel's own arithmetic compiled -O2, one
 thread) + the gather of descriptors + the host-array entry point; A2 is A again, the run's own A-vs-A spread.  For B only
 the pose changes (a small rotation per call, the same for every variant).  Host clock around the blocking calls, straight
 through ctypes with preallocated arrays on both sides.  Every call asserts that A and B compute the same result.
 
-usage: resident_points_probe.py <local|last|keyframe|refresh> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
-                                  mappoints_refresh_latency.json)
+                                  mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
        resident_points_probe.py local trace           -> a few B calls at 4000 points, for rocprofv3 --kernel-trace --stats
        resident_points_probe.py refresh trace         -> the same for refresh at 8000 points"""
@@ -53,7 +59,7 @@ def host_side(orb):
     so = out / "libresident_points_cpu.so"
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
-           csrc / "vsg_observations.h"]
+           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
                                str(src[0])])
@@ -70,6 +76,8 @@ def host_side(orb):
     H.rf_host_side.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p, _i32p, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                _u8p, _i32p, _u8p, _f32p, _f32p, _f32p]
     H.rf_take_rows.argtypes = [C.c_int, _i32p, _u8p, _i32p, _u8p]
+    H.po_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, C.c_int, _u8p, _f32p,
+                               C.POINTER(C.c_double), _i32p]
     return H
 
 
@@ -390,7 +398,62 @@ class Refresh(Case):
                 "best_not_first": int((last["B"][1] != 0).sum())}
 
 
-CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh}
+class Pose(Case):
+    """Optimizer::PoseOptimization: n correspondences among the 1000 features of one frame (tests/pose_scenes.py's scene
+    generator: uniform inlier noise within 0.8 sigma, 20 % outliers displaced by 20 px or more)."""
+    SIZES, TH, DEST = (100, 300, 1000), 0.0, "pose_optimization_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+
+    def __init__(self, orb, fr, n):
+        import pose_scenes as ps
+        self.orb, self.n = orb, n
+        s = self.s = ps.make(7000 + n, NFEAT, n, "mixed", outliers=0.2, start=(0.02, 1.0), capacity=2 * NFEAT)
+        keys = np.zeros(NFEAT, orb.KP_DTYPE)
+        keys["x"], keys["y"], keys["octave"] = s["kx"], s["ky"], s["octave"]
+        self.frame = orb.Frame(NFEAT + 1).upload(keys, np.zeros((NFEAT, 32), np.uint8), (0.0, 0.0, 640.0, 480.0),
+                                                 u_right=s["u_right"])
+        self.mp = orb.MapPoints(s["capacity"])
+        self.mp.update(np.arange(s["capacity"]), world_pos=s["world_pos"])
+        c = np.ascontiguousarray
+        self.slots, self.pos = c(s["feat_slots"], np.int32), c(s["world_pos"], np.float32)
+        self.kx, self.ky, self.oct = c(s["kx"], np.float32), c(s["ky"], np.float32), c(s["octave"], np.int32)
+        self.ur, self.sig = c(s["u_right"], np.float32), c(s["inv_sigma2"], np.float32)
+        self.pose7, self.cam = np.concatenate([s["q"], s["t"]]).astype(np.float32), np.array(s["cam"], np.float32)
+        self.tcw = orb.PoseSE3()
+        self.tcw.q[:], self.tcw.t[:] = [float(v) for v in s["q"]], [float(v) for v in s["t"]]
+        self.res = orb.PoseResult()
+        self.out, self.chi2 = np.zeros(NFEAT, np.uint8), np.zeros(NFEAT, np.float32)
+        self.qt, self.ri = np.zeros(7), np.zeros(2, np.int32)
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.out[:], self.chi2[:], self.qt[:], self.ri[:] = 0, 0, 0, 0
+
+    def run(self, name, L, H, P):
+        if name.startswith("A"):
+            return H.po_host_side(NFEAT, p(self.slots, _i32p), p(self.pos, _f32p), p(self.kx, _f32p), p(self.ky, _f32p),
+                                  p(self.oct, _i32p), p(self.ur, _f32p), p(self.pose7, _f32p), p(self.cam, _f32p),
+                                  p(self.sig, _f32p), 8, p(self.out, _u8p), p(self.chi2, _f32p),
+                                  self.qt.ctypes.data_as(C.POINTER(C.c_double)), p(self.ri, _i32p))
+        rc = L.vsg_frame_pose_optimization(self.frame.handle, self.mp.handle, p(self.slots, _i32p), C.byref(self.tcw),
+                                           *[float(v) for v in self.cam], p(self.sig, _f32p), 8, -1, p(self.out, _u8p),
+                                           p(self.chi2, _f32p), C.byref(self.res))
+        self.qt[:4], self.qt[4:] = self.res.q[:], self.res.t[:]
+        self.ri[:] = self.res.n_bad, self.res.rounds_run
+        return rc
+
+    def result(self, name, r):
+        return (r, self.out.copy(), self.chi2.view(np.uint32).copy(), self.qt.view(np.uint64).copy(), self.ri.copy())
+
+    def facts(self, last):
+        return {"correspondences": self.n, "inliers_returned": int(last["B"][0]), "n_bad": int(last["B"][4][0]),
+                "rounds_run": int(last["B"][4][1]), "stereo_share": round(float((self.ur[self.slots >= 0] >= 0).mean()), 2),
+                "host_side": "host build of csrc/vsg_pose_opt.h, one thread; NOT g2o, likely flatters the host"}
+
+
+CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose}
 
 
 def child(case, calls):
@@ -418,6 +481,8 @@ def child(case, calls):
         res = {k: stats(v) for k, v in t.items()}
         res.update(c.facts(last))
         res["a_vs_a_median_gap_us"] = round(abs(res["A"]["median_us"] - res["A2"]["median_us"]), 1)
+        if "B2" in t:  # the resident call timed twice: its own repeat gap
+            res["b_vs_b_median_gap_us"] = round(abs(res["B"]["median_us"] - res["B2"]["median_us"]), 1)
         # the resident call is "not slower" when its 10-90 % range does not lie wholly above the caller-side path's
         res["resident_not_slower"] = bool(res["B"]["p10_us"] <= max(res["A"]["p90_us"], res["A2"]["p90_us"]))
         res["resident_faster"] = bool(res["B"]["p90_us"] < min(res["A"]["p10_us"], res["A2"]["p10_us"]))

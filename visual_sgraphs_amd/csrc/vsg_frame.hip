@@ -309,7 +309,7 @@ int frame_put(vsg_frame *f, ThreadCtx *c, const FrameLayout &L, const vsg_keypoi
   const int rc = ctx_reserve(c, L.total, 0);
   if (rc != VSG_OK) return rc;
   set_bounds(f, min_x, min_y, max_x, max_y);
-  f->n = n, f->nleft = nleft, f->has_uright = u_right != nullptr, f->fv_valid = false;
+  f->n = n, f->nleft = nleft, f->has_uright = u_right != nullptr, f->fv_valid = false, f->pose_held = false;
   uint8_t *h = c->h_pin;
   if (n && !L.grid_only) memcpy(h + L.oK, keys, (size_t)n * sizeof(vsg_keypoint));
   if (desc && n) memcpy(h + L.oD, desc, (size_t)n * 32);
@@ -349,6 +349,7 @@ void vsg_frame_destroy(vsg_frame *f) {
   if (!f) return;
   hipSetDevice(f->device);
   hipFree(f->d_block);
+  hipFree(f->d_pose);
   delete f;
 }
 
@@ -414,7 +415,7 @@ static int frame_from_extractor(vsg_frame *f, vsg_orb *h, int index, const vsg_k
     un_pin = (KeyPointPOD *)c->h_pin, un_dev = (KeyPointPOD *)c->d_pin;
   }
   set_bounds(f, min_x, min_y, max_x, max_y);
-  f->n = n, f->nleft = -1, f->has_uright = false, f->fv_valid = false;
+  f->n = n, f->nleft = -1, f->has_uright = false, f->fv_valid = false, f->pose_held = false;
   if (v.done) TRY_HIP(hipStreamWaitEvent(c->stream, v.done, 0));
   hipLaunchKernelGGL(k_frame_grid_build, dim3(1), dim3(1024), 0, c->stream, v.d_kps, 0, n, f->minX, f->minY, f->invW,
                      f->invH, f->d_cell_start[0], f->d_ent[0], f->d_kps, v.d_desc, f->d_desc, f->d_cell_start[1], cam,
@@ -478,7 +479,7 @@ int to_frame_hook(void *ctx, hipStream_t s, const OrbOutputView &v) {
 }
 
 void frame_clear(vsg_frame *f) {
-  f->n = 0, f->nleft = -1, f->has_uright = false, f->fv_valid = false;
+  f->n = 0, f->nleft = -1, f->has_uright = false, f->fv_valid = false, f->pose_held = false;
   f->h_kps.clear();
 }
 
@@ -565,7 +566,7 @@ int extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols, int st
     frame_clear(f);
     return mono < 0 ? mono : VSG_ERR_CAPACITY;
   }
-  f->n = *n, f->nleft = -1, f->has_uright = A != nullptr, f->fv_valid = false;
+  f->n = *n, f->nleft = -1, f->has_uright = A != nullptr, f->fv_valid = false, f->pose_held = false;
   if (H.cam.distorted) {
     f->h_kps.assign((const vsg_keypoint *)un_pin, (const vsg_keypoint *)un_pin + *n);
     if (keys_un_out && *n) memcpy(keys_un_out, un_pin, (size_t)*n * sizeof(vsg_keypoint));

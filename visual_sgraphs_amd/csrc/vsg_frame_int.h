@@ -45,6 +45,12 @@ struct vsg_frame {
   bool fv_valid = false;  // a ComputeBoW of the CURRENT features has been enqueued on the owning thread's stream
   bool fv_empty = false;  // ... and it left no node (no features, or an empty() vocabulary): the device copy is not written
   int fv_bound = 0;       // upper bound of the FeatureVector's node count (what the join kernels launch for)
+  // Optimizer::PoseOptimization (vsg_pose.hip): the compacted edges, their last errors, the estimate and the flags of a
+  // call, allocated on first use.  pose_held: a call stopped after round 2's optimize and the CURRENT features are still
+  // the ones its edges were gathered from; pose_feat[e] = the feature of edge e.
+  uint8_t *d_pose = nullptr;
+  bool pose_held = false;
+  std::vector<int32_t> pose_feat;
 };
 
 namespace vsg {
@@ -65,6 +71,12 @@ struct FvDev {
   const int *hdr, *node, *off, *idx;
 };
 inline FvDev fv_dev(const vsg_frame *f) { return FvDev{f->d_fv_hdr, f->d_fv_node, f->d_fv_off, f->d_fv_idx}; }
+// what another translation unit may read of a vsg_mappoints store (vsg_mappoints.hip): false = no store
+struct StoreView {
+  const float *pos;  // GetWorldPos(), [3 * capacity]
+  int device, capacity;
+};
+bool store_view(const vsg_mappoints *mp, StoreView *v);
 inline int frame_check(const vsg_frame *f) { return f && f->d_block ? VSG_OK : VSG_ERR_INVALID; }
 // a vsg_grid (include/vsg_orb.h) is a vsg_frame behind an opaque name
 inline vsg_frame *grid_frame(vsg_grid *g) { return (vsg_frame *)g; }

@@ -40,6 +40,12 @@ struct vsg_mappoints {
   uint32_t epoch = 0;
 };
 
+bool vsg::store_view(const vsg_mappoints *mp, StoreView *v) {
+  if (!mp || !mp->d_block) return false;
+  *v = {mp->d_pos, mp->device, mp->capacity};
+  return true;
+}
+
 namespace {
 
 struct StoreDev {

@@ -83,6 +83,8 @@ EXPORTS = [
     "vsg_frame_search_for_triangulation_epipolar",
     # ComputeDistinctiveDescriptors and UpdateNormalAndDepth of resident map points from their observation lists
     "vsg_mappoints_refresh_from_observations",
+    # Optimizer::PoseOptimization on a resident frame and resident map points
+    "vsg_frame_pose_optimization", "vsg_frame_pose_optimization_resume",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -115,6 +117,17 @@ class FramePose(C.Structure):
         p.fx, p.fy, p.cx, p.cy, p.mbf = float(fx), float(fy), float(cx), float(cy), float(mbf)
         p.log_scale_factor, p.n_levels = float(log_scale_factor), int(n_levels)
         return p
+
+
+class PoseSE3(C.Structure):
+    """include/vsg_orb.h vsg_pose_se3: Tcw.unit_quaternion() as x y z w, Tcw.translation()."""
+    _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3)]
+
+
+class PoseResult(C.Structure):
+    """include/vsg_orb.h vsg_pose_result."""
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("n_initial", C.c_int32), ("n_bad", C.c_int32),
+                ("rounds_run", C.c_int32), ("held", C.c_int32)]
 
 
 class VsgError(RuntimeError):
@@ -351,6 +364,9 @@ def load_library():
                                              _u8p, _f32p, _f32p, _i32p]
     L.vsg_frame_search_sim3_points.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, cf, _f32p, ci, _i32p,
                                                _u8p, _f32p, _f32p, _i32p]
+    L.vsg_frame_pose_optimization.argtypes = [vp, vp, _i32p, C.POINTER(PoseSE3), cf, cf, cf, cf, cf, _f32p, ci, ci, _u8p,
+                                              _f32p, C.POINTER(PoseResult)]
+    L.vsg_frame_pose_optimization_resume.argtypes = [vp, _u8p, _u8p, _f32p, C.POINTER(PoseResult)]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1477,6 +1493,50 @@ class Frame:
             float(np.float32(nnratio)), int(bool(far_points)), float(np.float32(th_far_points)), _p(sf, _f32p),
             len(scale_factors), _p(tb, _u8p), _p(tm, _i32p), *o, C.byref(ntm)), "vsg_frame_search_local_points")
         return (nm, tm[:len(tb)], tb, *trimmed(), ntm.value)
+
+    # ---- Optimizer::PoseOptimization(pFrame) on resident map points  (Optimizer.cc:1063-1452)
+    @staticmethod
+    def _pose_result(ret, res, outlier, chi2):
+        return dict(ret=ret, q=np.array(res.q[:], np.float64), t=np.array(res.t[:], np.float64), n_initial=res.n_initial,
+                    n_bad=res.n_bad, rounds_run=res.rounds_run, held=res.held, outlier=outlier, chi2=chi2)
+
+    def pose_optimization(self, mp, feat_slots, q, t, camera, inv_level_sigma2, outlier, hold_round=-1, chi2=None):
+        """feat_slots[i] = slot of mvpMapPoints[i] (< 0: none), one per feature; q (x y z w), t = pFrame->GetPose();
+        camera = (fx, fy, cx, cy, mbf); outlier = mvbOutlier, updated IN A COPY for the features with a slot; chi2 (an
+        optional float array of the same length) likewise.  hold_round = 2 stops after round 2's optimize() (held = 1: run
+        the plane step on q / t, then pose_optimization_resume).  Returns a dict: ret, q, t (float64), n_initial, n_bad,
+        rounds_run, held, outlier, chi2."""
+        if len(feat_slots) != len(self.kps):
+            raise ValueError("feat_slots length does not match the frame's features")
+        sl, sig = _i32(feat_slots), _f32(inv_level_sigma2)
+        out = _u8(outlier).copy()
+        if len(out) != len(self.kps):
+            raise ValueError("outlier length does not match the frame's features")
+        out = out if out.size else np.zeros(1, np.uint8)
+        c2 = np.zeros(max(len(self.kps), 1), np.float32) if chi2 is None else _f32(chi2).copy()
+        pose, res = PoseSE3(), PoseResult()
+        pose.q[:] = [float(v) for v in np.asarray(q, np.float32).reshape(4)]
+        pose.t[:] = [float(v) for v in np.asarray(t, np.float32).reshape(3)]
+        ret = _check(self._L.vsg_frame_pose_optimization(
+            self._h, mp.handle, _p(sl, _i32p), C.byref(pose), *[float(np.float32(c)) for c in camera], _p(sig, _f32p),
+            len(inv_level_sigma2), int(hold_round), _p(out, _u8p), _p(c2, _f32p), C.byref(res)),
+            "vsg_frame_pose_optimization")
+        return self._pose_result(ret, res, out[:len(self.kps)], c2[:len(self.kps)])
+
+    def pose_optimization_resume(self, outlier, removed=None, chi2=None):
+        """Round 2's classification and round 3 of a held pose_optimization.  removed[i] != 0: the plane step set
+        mvpMapPoints[i] = NULL.  outlier / chi2 = the arrays the held call returned."""
+        out = _u8(outlier).copy()
+        out = out if out.size else np.zeros(1, np.uint8)
+        c2 = np.zeros(max(len(self.kps), 1), np.float32) if chi2 is None else _f32(chi2).copy()
+        rem = None if removed is None else _u8(removed)
+        if rem is not None and len(rem) != len(self.kps):
+            raise ValueError("removed length does not match the frame's features")
+        res = PoseResult()
+        ret = _check(self._L.vsg_frame_pose_optimization_resume(
+            self._h, _p(rem, _u8p) if rem is not None else None, _p(out, _u8p), _p(c2, _f32p), C.byref(res)),
+            "vsg_frame_pose_optimization_resume")
+        return self._pose_result(ret, res, out[:len(self.kps)], c2[:len(self.kps)])
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono) on resident map points  (ORBmatcher.cc:1667-1878)
     def SearchLastFrame(self, last, mp, last_slots, cur_pose, last_pose, mb, mono, th, scale_factors, train_blocked,
