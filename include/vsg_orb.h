@@ -433,7 +433,11 @@ int vsg_orb_wait(vsg_orb *h, int ticket, int *n, int *mono_index);
  * grid indexes (mvKeysUn; mvKeys || mvKeysRight when Nleft != -1), mDescriptors, mvuRight and the 64 x 48 mGrid (+
  * mGridRight) as CSR -- so that a search uploads only the projected positions and the map points' descriptors.
  * A small host mirror of the keypoints serves the ordered host-side passes (rotation histogram, level ratio test).
- * Frames are immutable after upload and may be searched concurrently from several threads. */
+ * Frames are immutable after upload and may be searched concurrently from several threads.  The one thing that may be
+ * added to an uploaded frame is the per-keyframe stereo attachment of vsg_frame_set_stereo_points (below, at
+ * vsg_frame_triangulate_matches): it is set once per keyframe, before the first call that reads it and not while another
+ * thread's call does, and the next vsg_frame_upload / vsg_frame_from_extractor* / vsg_orb_extract_to_frame* into the
+ * frame drops it. */
 typedef struct vsg_frame vsg_frame;
 /* Limits (the packed candidate entries are index : 15 | distance : 9 | octave : 4 bits): capacity <= 32767 features per
  * frame (vsg_frame_create returns VSG_ERR_INVALID beyond, the host-candidate forms vsg_search_* return
@@ -904,6 +908,92 @@ int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *n
                                                 const int32_t *idx2, int nodes2, const float F12[9], const float ep[2],
                                                 const float *scale_factors2, const float *level_sigma2_2, int nlevels,
                                                 int only_stereo, int coarse, int check_orientation, int32_t *matches12);
+/* ---- LocalMapping::CreateNewMapPoints on resident keyframes (LocalMapping.cc:382-710) -------------------------------
+ * The loop over one neighbour's matches (:475-708): per matched pair (idx1 of mpCurrentKeyFrame = kf1, idx2 of pKF2 = kf2)
+ * the parallax test, GeometricTools::Triangulate (GeometricTools.cc:47-66) or KeyFrame::UnprojectStereo (KeyFrame.cc:
+ * 885-902), the two depth signs, the two reprojection gates, the scale-consistency gate, and for an accepted pair the new
+ * MapPoint written straight into a resident store: SetWorldPos, ComputeDistinctiveDescriptors and UpdateNormalAndDepth of a
+ * point with exactly two observations.  Both keyframes have Nleft == -1 and the Pinhole camera.  One source for host and
+ * device (csrc/vsg_triangulate.h): float arithmetic in the reference's order, one rounding per
+ * operation, comparisons as the reference writes them (a NaN takes the reference's branch), with these quirks kept:
+ *   - cosParallaxStereo2 is taken only when kf1's keypoint is mono (the `else if (bStereo2)` of :570);
+ *   - the float cosParallaxRays is compared with the DOUBLE literals 0.9996 (inertial) / 0.9998 (:582), the squared
+ *     reprojection errors with 5.991 * sigma2 / 7.8 * sigma2 in double (:632, :643), invz = (float)(1.0 / z) (:624);
+ *   - kf2's u2_r uses the CURRENT keyframe's mbf (:663): kf1.mbf is read, kf2.mbf never;
+ *   - Triangulate's right singular vector comes from a one-sided Jacobi in DOUBLE (6 sweeps) on the float A of :50-53, not
+ *     from Eigen's float JacobiSVD: a deviation of arithmetic class, recorded in DESIGN.md beside the pose solve's LDL^T.
+ * Reason codes (uint8 per feature of kf1) and source codes (what countStereo counts, :693): */
+#define VSG_TRI_ACCEPTED 0
+#define VSG_TRI_LOW_PARALLAX 1  /* :600-603 */
+#define VSG_TRI_W_ZERO 2        /* GeometricTools.cc:59 */
+#define VSG_TRI_STEREO_DEPTH 3  /* KeyFrame.cc:888: mvDepth <= 0 */
+#define VSG_TRI_Z1 4            /* :613 */
+#define VSG_TRI_Z2 5            /* :617 */
+#define VSG_TRI_REPROJ1 6       /* :632 / :643 */
+#define VSG_TRI_REPROJ2 7       /* :657 / :668 */
+#define VSG_TRI_DIST_ZERO 8     /* :679 */
+#define VSG_TRI_FAR 9           /* :682 */
+#define VSG_TRI_SCALE_RATIO 10  /* :688 */
+#define VSG_TRI_NO_FREE_SLOT 11 /* accepted by every gate, but free_slots was used up: nothing is written for it */
+#define VSG_TRI_NO_MATCH 255    /* matches12[idx1] < 0 */
+#define VSG_TRI_FROM_TRIANGULATE 0
+#define VSG_TRI_FROM_STEREO1 1 /* mpCurrentKeyFrame->UnprojectStereo(idx1) (:592) */
+#define VSG_TRI_FROM_STEREO2 2 /* pKF2->UnprojectStereo(idx2) (:598) */
+/* kf1 / kf2 = the two cameras (Rcw, tcw, Ow, fx, fy, cx, cy and kf1's mbf are read; log_scale_factor and n_levels are not);
+ * ratio_factor = 1.5f * mpCurrentKeyFrame->mfScaleFactor (:422); inertial = mbInertial; far_points / th_far_points =
+ * mbFarPoints / mThFarPoints; kf2_first = std::less<KeyFrame *>()(pKF2, mpCurrentKeyFrame): the new point's
+ * mObservations is a std::map<KeyFrame *, ...>, with two observations both rows of ComputeDistinctiveDescriptors have
+ * median 0 and the FIRST in the map's order wins (MapPoint.cc:406), and UpdateNormalAndDepth sums in that order. */
+typedef struct vsg_triangulation_params {
+  vsg_frame_pose kf1, kf2;
+  float ratio_factor, th_far_points;
+  int32_t inertial, far_points, kf2_first;
+} vsg_triangulation_params;
+/* The per-keyframe inputs of the stereo branches, attached to a resident frame once per keyframe: xyz_c[3 i ..] = x3Dc of
+ * KeyFrame::UnprojectStereo(i) (KeyFrame.cc:887-894: z = mvDepth[i], x = (mvKeys[i].pt.x - cx) * z * invfx, y likewise --
+ * mvKeys, the RAW keypoints, which the frame does not hold), cos_parallax[i] = cos(2 * atan2(mb / 2, mvDepth[i])) (:569),
+ * both computed by the caller with the reference's own expressions (as F12 and the epipole of the search).  Entries of
+ * features with mvuRight < 0 are never read.  The two calls below return VSG_ERR_INVALID before they enqueue anything when
+ * a frame that was given an mvuRight with any entry >= 0 (or filled by vsg_orb_extract_to_frame_rgbd) has nothing
+ * attached; a frame without mvuRight needs nothing.  Dropped by the next upload into the frame.  NULL frame or array, or
+ * a frame never uploaded: VSG_ERR_INVALID.  One copy on the calling thread's stream, waited for. */
+int vsg_frame_set_stereo_points(vsg_frame *f, const float *xyz_c, const float *cos_parallax);
+/* The loop :475-708 for a match list the caller holds: matches12[n1] as the searches return it (-1: none), walked in
+ * ascending idx1 as the reference walks vMatchedIndices.  scale_factorsX / level_sigma2_X = mvScaleFactors / mvLevelSigma2
+ * of kfX, nlevels entries each (nlevels = mnScaleLevels in 1..16).  Outputs, each n1 entries (x3d 3 n1), all required:
+ * reason / source as above (a feature without a match: 255 / 0), x3d = x3D as far as the reference assigned it (zeros
+ * before), new_slot = the slot of the point the pair created or -1, *n_created = how many.
+ *   mp == NULL: geometry only; free_slots / n_free are not read, nothing is created, an accepted pair has reason 0.
+ *   mp != NULL: the k-th accepted pair in ascending idx1 takes free_slots[k]; the device writes that slot's world_pos = x3D,
+ *     desc (row idx1 of kf1, or row idx2 of kf2 under kf2_first), normal, min_dist, max_dist (UpdateNormalAndDepth with
+ *     mpRefKF = mpCurrentKeyFrame: csrc/vsg_observations.h on the two-entry list) and observed = 1.  Accepted pairs beyond
+ *     n_free get VSG_TRI_NO_FREE_SLOT and write nothing.  Slots that are not assigned stay byte-identical.
+ * Checked before anything is enqueued (outputs untouched): NULL handles, params, tables or outputs, frames and store on
+ * different devices, nlevels outside 1..16, a keypoint of EITHER frame whose octave lies outside [0, nlevels), a match
+ * outside [0, n2), n_free < 0, a free_slots entry outside [0, capacity) or listed twice, a frame with stereo keypoints and
+ * no attachment: VSG_ERR_INVALID; Nleft != -1 on either frame (:482-554): VSG_ERR_UNSUPPORTED.  One enqueue on the
+ * calling thread's stream and one wait; an error after the enqueue waits for the stream before it returns.  The caller
+ * clears no_mp1[idx1] / no_mp2[idx2] for created points between neighbours (:699-700). */
+int vsg_frame_triangulate_matches(vsg_frame *kf1, vsg_frame *kf2, const int32_t *matches12,
+                                  const vsg_triangulation_params *params, const float *scale_factors1,
+                                  const float *level_sigma2_1, const float *scale_factors2, const float *level_sigma2_2,
+                                  int nlevels, vsg_mappoints *mp, const int32_t *free_slots, int n_free, uint8_t *reason,
+                                  uint8_t *source, float *x3d, int32_t *new_slot, int32_t *n_created);
+/* One neighbour of CreateNewMapPoints (:456-708) in ONE enqueue and ONE wait: vsg_frame_search_for_triangulation_epipolar
+ * (its arguments, both FeatureVector forms, and its checks), the rotation-consistency filter (ORBmatcher.cc:1100-1118:
+ * rot_bin per match, the 30-bin count and ComputeThreeMaxima, here on the device), then vsg_frame_triangulate_matches on
+ * the filtered matches.  matches12 is the list AFTER the filter and the return value its count; the other outputs, the
+ * store writes and the checks are those of the two calls.  An all-neighbours call is deliberately not offered: the
+ * reference leaves the loop between neighbours (CheckNewKeyFrames, :430) and the caller updates no_mp1 there. */
+int vsg_frame_create_new_map_points(vsg_frame *kf1, const uint8_t *no_mp1, const int32_t *node_id1, const int32_t *off1,
+                                    const int32_t *idx1, int nodes1, vsg_frame *kf2, const uint8_t *no_mp2,
+                                    const int32_t *node_id2, const int32_t *off2, const int32_t *idx2, int nodes2,
+                                    const float F12[9], const float ep[2], int only_stereo, int coarse,
+                                    int check_orientation, const vsg_triangulation_params *params,
+                                    const float *scale_factors1, const float *level_sigma2_1, const float *scale_factors2,
+                                    const float *level_sigma2_2, int nlevels, vsg_mappoints *mp, const int32_t *free_slots,
+                                    int n_free, int32_t *matches12, uint8_t *reason, uint8_t *source, float *x3d,
+                                    int32_t *new_slot, int32_t *n_created);
 /* Frame::ComputeBoW (Frame.cc:882-889) on the resident descriptors; outputs as vsg_bow_transform. */
 int vsg_frame_bow_transform(vsg_vocab *voc, vsg_frame *f, int levelsup, int32_t *bow_ids, double *bow_vals,
                             int bow_cap, int *n_bow, int32_t *fv_node, int32_t *fv_off, int32_t *fv_idx, int fv_cap,

@@ -8,6 +8,7 @@
 // and a `mvImagePyramid` refresh for Frame::ComputeStereoMatches (Frame.cc:964,1054-1069).
 // See INTEGRATION.md for the three-line change in Tracking.cc / Frame.cc that swaps the extractor.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -686,6 +687,15 @@ class ResidentFrame {
   }
   int N() const { return vsg_frame_size(f_); }
   vsg_frame *handle() const { return f_; }
+  // The per-keyframe inputs of CreateNewMapPoints' stereo branches (vsg_frame_set_stereo_points), once per keyframe:
+  // x3Dc[3 i ..] = x3Dc of KeyFrame::UnprojectStereo(i) (KeyFrame.cc:887-894, from mvKeys and mvDepth), cosParallax[i] =
+  // cos(2 * atan2(mb / 2, mvDepth[i])) (LocalMapping.cc:569); entries of keypoints with mvuRight < 0 are never read.
+  void SetStereoPoints(const std::vector<float> &x3Dc, const std::vector<float> &cosParallax) {
+    if (x3Dc.size() < 3 * (size_t)N() || cosParallax.size() < (size_t)N()) check(VSG_ERR_INVALID, "vsg_frame_set_stereo_points");
+    static const float none[3] = {0.0f, 0.0f, 0.0f};
+    check(vsg_frame_set_stereo_points(f_, x3Dc.empty() ? none : x3Dc.data(), cosParallax.empty() ? none : cosParallax.data()),
+          "vsg_frame_set_stereo_points");
+  }
 
   // Frame::GetFeaturesInArea / KeyFrame::GetFeaturesInArea for many windows at once
   Candidates GetFeaturesInArea(const float *x, const float *y, const float *r, const int32_t *minLevel,
@@ -842,6 +852,23 @@ struct ProjectedPoints {
 
 // The remaining ORBmatcher searches on resident frames (ORBmatcher.h:44-87).  Outputs are feature -> query-index maps;
 // the maintainer's glue writes the MapPoint* assignments back.
+// What one neighbour of LocalMapping::CreateNewMapPoints leaves behind (vsg_frame_triangulate_matches /
+// vsg_frame_create_new_map_points): per feature of mpCurrentKeyFrame the reason (VSG_TRI_*), the source (VSG_TRI_FROM_*: what
+// countStereo counts), x3D and the slot of the point it created (-1: none); vMatchedIndices after the rotation filter.
+struct NewMapPointsResult {
+  std::vector<uint8_t> reason, source;
+  std::vector<float> x3D;  // 3 per feature
+  std::vector<int32_t> newSlot;
+  std::vector<std::pair<size_t, size_t>> vMatchedIndices;
+  int nCreated = 0, nMatches = 0;
+  void resize(int n) {
+    const size_t m = n > 0 ? (size_t)n : 1;
+    reason.assign(m, 0), source.assign(m, 0), x3D.assign(3 * m, 0.0f), newSlot.assign(m, -1);
+    vMatchedIndices.clear();
+    nCreated = nMatches = 0;
+  }
+};
+
 class ResidentMatcher {
  public:
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;
@@ -1182,6 +1209,62 @@ class ResidentMatcher {
     for (int i = 0; i < pKF1.N(); i++)
       if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1131-1141: pairs in idx1 order
     return rc;
+  }
+
+  // The loop over one neighbour's matches of LocalMapping::CreateNewMapPoints (LocalMapping.cc:475-708) for a match list the
+  // caller holds (matches12[idx1] = idx2 or -1), mpCurrentKeyFrame = pKF1 (vsg_frame_triangulate_matches).  mp == nullptr:
+  // geometry only; otherwise the k-th accepted pair in ascending idx1 is written into freeSlots[k] on the device.
+  void TriangulateMatches(ResidentFrame &pKF1, ResidentFrame &pKF2, const std::vector<int32_t> &matches12,
+                          const vsg_triangulation_params &params, const std::vector<float> &mvScaleFactors1,
+                          const std::vector<float> &mvLevelSigma2_1, const std::vector<float> &mvScaleFactors2,
+                          const std::vector<float> &mvLevelSigma2_2, ResidentMapPoints *mp,
+                          const std::vector<int32_t> &freeSlots, NewMapPointsResult &out) const {
+    const size_t nl = mvScaleFactors1.size();
+    if (mvLevelSigma2_1.size() != nl || mvScaleFactors2.size() != nl || mvLevelSigma2_2.size() != nl ||
+        matches12.size() < (size_t)pKF1.N())
+      check(VSG_ERR_INVALID, "vsg_frame_triangulate_matches");
+    out.resize(pKF1.N());
+    static const int32_t none = -1;
+    check(vsg_frame_triangulate_matches(pKF1.handle(), pKF2.handle(), matches12.empty() ? &none : matches12.data(), &params,
+                                        mvScaleFactors1.data(), mvLevelSigma2_1.data(), mvScaleFactors2.data(),
+                                        mvLevelSigma2_2.data(), (int)nl, mp ? mp->handle() : nullptr, freeSlots.data(),
+                                        (int)freeSlots.size(), out.reason.data(), out.source.data(), out.x3D.data(),
+                                        out.newSlot.data(), &out.nCreated),
+          "vsg_frame_triangulate_matches");
+    for (int i = 0; i < pKF1.N(); i++)
+      if (matches12[i] >= 0) out.vMatchedIndices.emplace_back((size_t)i, (size_t)matches12[i]), out.nMatches++;
+  }
+
+  // One neighbour of LocalMapping::CreateNewMapPoints (LocalMapping.cc:456-708) in one enqueue and one wait
+  // (vsg_frame_create_new_map_points): the search of SearchForTriangulation above (F12, ep, noMpX, fv1 / fv2 as there), the
+  // rotation filter, the triangulation and the store writes.  Returns nmatches after the filter.
+  int CreateNewMapPoints(ResidentFrame &pKF1, const uint8_t *noMp1, ResidentFrame &pKF2, const uint8_t *noMp2,
+                         const float F12[9], const float ep[2], bool bOnlyStereo, bool bCoarse,
+                         const vsg_triangulation_params &params, const std::vector<float> &mvScaleFactors1,
+                         const std::vector<float> &mvLevelSigma2_1, const std::vector<float> &mvScaleFactors2,
+                         const std::vector<float> &mvLevelSigma2_2, ResidentMapPoints *mp,
+                         const std::vector<int32_t> &freeSlots, NewMapPointsResult &out, const FeatureVectorCSR *fv1 = nullptr,
+                         const FeatureVectorCSR *fv2 = nullptr) const {
+    const size_t nl = mvScaleFactors1.size();
+    if (mvLevelSigma2_1.size() != nl || mvScaleFactors2.size() != nl || mvLevelSigma2_2.size() != nl || !fv1 != !fv2)
+      check(VSG_ERR_INVALID, "vsg_frame_create_new_map_points");
+    out.resize(pKF1.N());
+    std::vector<int32_t> m12(pKF1.N() > 0 ? pKF1.N() : 1, -1);
+    if (fv1 && (fv1->nodes() == 0 || fv2->nodes() == 0)) {  // no shared node (their data() may be NULL): no match, no point
+      std::fill(out.reason.begin(), out.reason.end(), (uint8_t)VSG_TRI_NO_MATCH);
+      return 0;
+    }
+    const int rc = vsg_frame_create_new_map_points(
+        pKF1.handle(), noMp1, fv1 ? fv1->node.data() : nullptr, fv1 ? fv1->off.data() : nullptr,
+        fv1 ? fv1->idx.data() : nullptr, fv1 ? fv1->nodes() : 0, pKF2.handle(), noMp2, fv2 ? fv2->node.data() : nullptr,
+        fv2 ? fv2->off.data() : nullptr, fv2 ? fv2->idx.data() : nullptr, fv2 ? fv2->nodes() : 0, F12, ep, bOnlyStereo, bCoarse,
+        mbCheckOrientation, &params, mvScaleFactors1.data(), mvLevelSigma2_1.data(), mvScaleFactors2.data(),
+        mvLevelSigma2_2.data(), (int)nl, mp ? mp->handle() : nullptr, freeSlots.data(), (int)freeSlots.size(), m12.data(),
+        out.reason.data(), out.source.data(), out.x3D.data(), out.newSlot.data(), &out.nCreated);
+    check(rc, "vsg_frame_create_new_map_points");
+    for (int i = 0; i < pKF1.N(); i++)
+      if (m12[i] >= 0) out.vMatchedIndices.emplace_back((size_t)i, (size_t)m12[i]);
+    return out.nMatches = rc;
   }
 
  protected:

@@ -9,6 +9,7 @@
 #include "vsg_observations.h"
 #include "vsg_pose_opt.h"
 #include "vsg_project.h"
+#include "vsg_triangulate.h"
 
 extern "C" {
 
@@ -140,6 +141,33 @@ int po_host_side(int n, const int32_t *feat_slots, const float *world_pos, const
   for (int k = 0; k < 3; k++) qt[4 + k] = pose::canon(call.ctl.est.t[k]);
   ri[0] = call.ctl.n_bad, ri[1] = call.ctl.rounds_run;
   return (int)call.edges.size() - call.ctl.n_bad;
+}
+
+// The caller-side loop of LocalMapping::CreateNewMapPoints (LocalMapping.cc:475-708) on one neighbour's matches: the header's
+// geometry for every match, then what a caller gathers for vsg_mappoints_update and vsg_mappoints_refresh_from_observations:
+// the k-th accepted pair takes free_slots[k]; slots[k], pos[3 k], obs_idx[2 k] = {idx1, idx2}.  frame tables f1 / f2 = {x, y,
+// uright, stereo (4 per feature), scale_factors, level_sigma2}.  Returns the number of accepted pairs (<= n_free).
+int np_host_side(const vsg_triangulation_params *P, int n1, const float *const *f1, const int32_t *octave1, int n2,
+                 const float *const *f2, const int32_t *octave2, const int32_t *matches12, int nlevels, const int32_t *free_slots,
+                 int n_free, uint8_t *reason, uint8_t *source, float *x3d, int32_t *new_slot, int32_t *slots, float *pos,
+                 int32_t *obs_idx) {
+  const vsg::TriFrameHost A{n1, f1[0], f1[1], octave1, f1[2], f1[3], nullptr, f1[4], f1[5]};
+  const vsg::TriFrameHost B{n2, f2[0], f2[1], octave2, f2[2], f2[3], nullptr, f2[4], f2[5]};
+  const vsg::TriStoreHost none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  vsg::new_points_loop(*P, A, B, matches12, nlevels, none, nullptr, 0, reason, source, x3d, new_slot);
+  int k = 0;
+  for (int i = 0; i < n1; i++) {
+    if (matches12[i] < 0 || reason[i] != vsg::kTriAccepted) continue;
+    if (k == n_free) {
+      reason[i] = vsg::kTriNoFreeSlot;
+      continue;
+    }
+    new_slot[i] = slots[k] = free_slots[k];
+    for (int c = 0; c < 3; c++) pos[3 * k + c] = x3d[3 * i + c];
+    obs_idx[2 * k] = i, obs_idx[2 * k + 1] = matches12[i];
+    k++;
+  }
+  return k;
 }
 
 }  // extern "C"

@@ -30,7 +30,13 @@ thread) + the gather of descriptors + the host-array entry point; A2 is A again,
 the pose changes (a small rotation per call, the same for every variant).  Host clock around the blocking calls, straight
 through ctypes with preallocated arrays on both sides.  Every call asserts that A and B compute the same result.
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose> [calls] [out.json]  -> runs the child, writes the record (default
+  newpoints one neighbour of LocalMapping::CreateNewMapPoints on two resident keyframes of 1000 / 2000 features, a store of 8000
+            slots, resident FeatureVectors
+            A  = vsg_frame_search_for_triangulation_epipolar + the host build of csrc/vsg_triangulate.h over its matches on one
+                 thread (NOT Eigen: the header's own arithmetic) + vsg_mappoints_update + vsg_mappoints_refresh_from_observations
+            B  = vsg_frame_create_new_map_points;  A2 / B2 = both again.  Every call asserts equal outputs and store
+
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -59,7 +65,7 @@ def host_side(orb):
     so = out / "libresident_points_cpu.so"
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
-           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h"]
+           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
                                str(src[0])])
@@ -76,6 +82,8 @@ def host_side(orb):
     H.rf_host_side.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p, _i32p, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                _u8p, _i32p, _u8p, _f32p, _f32p, _f32p]
     H.rf_take_rows.argtypes = [C.c_int, _i32p, _u8p, _i32p, _u8p]
+    H.np_host_side.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _i32p, C.c_int, C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int,
+                               _u8p, _u8p, _f32p, _i32p, _i32p, _f32p, _i32p]
     H.po_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, C.c_int, _u8p, _f32p,
                                C.POINTER(C.c_double), _i32p]
     return H
@@ -453,7 +461,108 @@ class Pose(Case):
                 "host_side": "host build of csrc/vsg_pose_opt.h, one thread; NOT g2o, likely flatters the host"}
 
 
-CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose}
+class NewPoints(Case):
+    """One neighbour of LocalMapping::CreateNewMapPoints: two resident keyframes of n features each (tests/
+    triangulation_scenes.py's generator: 30 % of the features see a shared point, depths 0.4 .. 40, a third stereo), the
+    k = 10 / L = 6 vocabulary's resident FeatureVectors, a store of 8000 slots."""
+    SIZES, TH, DEST = (1000, 2000), 0.0, "create_new_map_points_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+    CAP = 8000
+
+    def __init__(self, orb, fr, n):
+        import triangulation_scenes as ts
+        import triangulation_hostcore as hc
+        from visual_sgraphs_amd import synth
+        self.orb, self.n = orb, n
+        rng = np.random.default_rng(9000 + n)
+        npts = int(0.3 * n)
+        s = self.s = ts.build(ts.cloud(rng, npts, 0.4, 40.0), *ts.cameras(), rng, extra=n - npts)
+        voc = orb.ORBVocabulary(synth.synthetic_vocabulary(10, 6, seed=17, stop_fraction=0.05))
+        self.f = []
+        for t in ("1", "2"):
+            f = orb.Frame(n).upload(s["k" + t], s["d" + t], ts.BOUNDS, u_right=s["ur" + t])
+            f.SetStereoPoints(s["stereo" + t][:, :3], s["stereo" + t][:, 3])
+            f.ComputeBoW(voc)
+            self.f.append(f)
+        self.mp = orb.MapPoints(self.CAP)
+        c = np.ascontiguousarray
+        self.free = np.arange(self.CAP, dtype=np.int32)
+        self.P = orb.TriangulationParams.make(*[orb.FramePose.make(k["Rcw"], k["tcw"], k["Ow"], k["fx"], k["fy"], k["cx"], k["cy"],
+                                                                  k["mbf"], 0.0, 0) for k in (s["P"]["kf1"], s["P"]["kf2"])],
+                                            s["P"]["ratio_factor"])
+        self.pb = hc.params_blob(s["P"])
+        assert bytes(self.pb) == bytes(self.P)
+        self.keep = []
+        self.tab, self.oct = [], []
+        for t in ("1", "2"):
+            arr = [c(s["k" + t]["x"], np.float32), c(s["k" + t]["y"], np.float32), c(s["ur" + t], np.float32),
+                   c(s["stereo" + t], np.float32), c(s["sf" + t], np.float32), c(s["sigma2_" + t], np.float32)]
+            self.keep.append(arr)
+            self.tab.append((C.c_void_p * 6)(*[a.ctypes.data for a in arr]))
+            self.oct.append(c(s["k" + t]["octave"], np.int32))
+        self.sf, self.sig = self.keep[0][4], self.keep[0][5]
+        self.no_mp = [np.ones(n, np.uint8), np.ones(n, np.uint8)]
+        self.F12, self.ep = c(s["F12"].reshape(9), np.float32), c(s["ep"], np.float32)
+        self.m12, self.reason, self.source = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        self.x3d, self.new_slot, self.created = np.zeros(3 * n, np.float32), np.zeros(n, np.int32), C.c_int32(0)
+        self.slots, self.pos, self.obs_idx = np.zeros(n, np.int32), np.zeros(3 * n, np.float32), np.zeros(2 * n, np.int32)
+        self.obs_off, self.obs_kf = np.arange(0, 2 * n + 1, 2, dtype=np.int32), np.tile(np.array([0, 1], np.int32), n)
+        self.ref_pos, self.ones = np.zeros(n, np.int32), np.ones(n, np.uint8)
+        self.kfs = (C.c_void_p * 2)(self.f[0].handle, self.f[1].handle)
+        self.Ow = np.concatenate([s["P"]["kf1"]["Ow"], s["P"]["kf2"]["Ow"]]).astype(np.float32)
+        self.best, self.o_n, self.o_mn, self.o_mx = (np.zeros(n, np.int32), np.zeros(3 * n, np.float32), np.zeros(n, np.float32),
+                                                     np.zeros(n, np.float32))
+        self.zero = dict(world_pos=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), min_dist=np.zeros(n, np.float32),
+                         max_dist=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8), observed=np.zeros(n, np.uint8))
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):  # outside the clock: the slots a call may write are cleared, so that every variant has to write them
+        self.mp.update(self.free[:self.n], **self.zero)
+        self.m12[:], self.reason[:], self.source[:], self.x3d[:], self.new_slot[:] = 0, 0, 0, 0, 0
+
+    def run(self, name, L, H, P):
+        f1, f2, n = self.f[0].handle, self.f[1].handle, self.n
+        if name.startswith("B"):
+            return L.vsg_frame_create_new_map_points(
+                f1, p(self.no_mp[0], _u8p), None, None, None, 0, f2, p(self.no_mp[1], _u8p), None, None, None, 0, p(self.F12, _f32p),
+                p(self.ep, _f32p), 0, 0, 1, C.byref(self.P), p(self.sf, _f32p), p(self.sig, _f32p), p(self.sf, _f32p),
+                p(self.sig, _f32p), 4, self.mp.handle, p(self.free, _i32p), self.CAP, p(self.m12, _i32p), p(self.reason, _u8p),
+                p(self.source, _u8p), p(self.x3d, _f32p), p(self.new_slot, _i32p), C.byref(self.created))
+        nm = L.vsg_frame_search_for_triangulation_epipolar(
+            f1, p(self.no_mp[0], _u8p), None, None, None, 0, f2, p(self.no_mp[1], _u8p), None, None, None, 0, p(self.F12, _f32p),
+            p(self.ep, _f32p), p(self.sf, _f32p), p(self.sig, _f32p), 4, 0, 0, 1, p(self.m12, _i32p))
+        k = H.np_host_side(C.byref(self.P), n, self.tab[0], p(self.oct[0], _i32p), n, self.tab[1], p(self.oct[1], _i32p),
+                           p(self.m12, _i32p), 4, p(self.free, _i32p), self.CAP, p(self.reason, _u8p), p(self.source, _u8p),
+                           p(self.x3d, _f32p), p(self.new_slot, _i32p), p(self.slots, _i32p), p(self.pos, _f32p),
+                           p(self.obs_idx, _i32p))
+        self.created.value = k
+        if k:
+            assert L.vsg_mappoints_update(self.mp.handle, k, p(self.slots, _i32p), p(self.pos, _f32p), None, None, None, None,
+                                          p(self.ones, _u8p)) == 0
+            assert L.vsg_mappoints_refresh_from_observations(
+                self.mp.handle, k, p(self.slots, _i32p), p(self.obs_off, _i32p), p(self.obs_kf, _i32p), p(self.obs_idx, _i32p), None,
+                p(self.ref_pos, _i32p), 2, self.kfs, p(self.Ow, _f32p), p(self.sf, _f32p), 4, 3, p(self.best, _i32p),
+                p(self.o_n, _f32p), p(self.o_mn, _f32p), p(self.o_mx, _f32p)) == 0
+        return nm
+
+    def result(self, name, r):
+        st = self.mp.read(self.free[:self.n])
+        return (r, self.m12.copy(), self.reason.copy(), self.source.copy(), self.x3d.view(np.uint32).copy(), self.new_slot.copy(),
+                np.array([self.created.value]), st["world_pos"].view(np.uint32).copy(), st["normal"].view(np.uint32).copy(),
+                st["min_dist"].view(np.uint32).copy(), st["max_dist"].view(np.uint32).copy(), st["desc"].copy(), st["observed"].copy())
+
+    def facts(self, last):
+        b = last["B"]
+        return {"features_per_keyframe": self.n, "matches_after_rotation_filter": int(b[0]), "points_created": int(b[6][0]),
+                "from_unproject_stereo": int(((b[2] == 0) & (b[3] > 0)).sum()), "store_slots": self.CAP,
+                "host_side": "A = vsg_frame_search_for_triangulation_epipolar + the host build of csrc/vsg_triangulate.h on one "
+                             "thread (tools/resident_points_cpu.cpp; NOT Eigen: the double Jacobi of the header, no JacobiSVD) + "
+                             "vsg_mappoints_update + vsg_mappoints_refresh_from_observations; B = vsg_frame_create_new_map_points"}
+
+
+CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints}
 
 
 def child(case, calls):

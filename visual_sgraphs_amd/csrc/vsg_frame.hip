@@ -310,6 +310,8 @@ int frame_put(vsg_frame *f, ThreadCtx *c, const FrameLayout &L, const vsg_keypoi
   if (rc != VSG_OK) return rc;
   set_bounds(f, min_x, min_y, max_x, max_y);
   f->n = n, f->nleft = nleft, f->has_uright = u_right != nullptr, f->fv_valid = false, f->pose_held = false;
+  f->stereo_attached = f->any_stereo = false;
+  for (int i = 0; u_right && i < n; i++) f->any_stereo |= u_right[i] >= 0;
   uint8_t *h = c->h_pin;
   if (n && !L.grid_only) memcpy(h + L.oK, keys, (size_t)n * sizeof(vsg_keypoint));
   if (desc && n) memcpy(h + L.oD, desc, (size_t)n * 32);
@@ -350,6 +352,7 @@ void vsg_frame_destroy(vsg_frame *f) {
   hipSetDevice(f->device);
   hipFree(f->d_block);
   hipFree(f->d_pose);
+  hipFree(f->d_stereo);
   delete f;
 }
 
@@ -416,6 +419,7 @@ static int frame_from_extractor(vsg_frame *f, vsg_orb *h, int index, const vsg_k
   }
   set_bounds(f, min_x, min_y, max_x, max_y);
   f->n = n, f->nleft = -1, f->has_uright = false, f->fv_valid = false, f->pose_held = false;
+  f->stereo_attached = f->any_stereo = false;
   if (v.done) TRY_HIP(hipStreamWaitEvent(c->stream, v.done, 0));
   hipLaunchKernelGGL(k_frame_grid_build, dim3(1), dim3(1024), 0, c->stream, v.d_kps, 0, n, f->minX, f->minY, f->invW,
                      f->invH, f->d_cell_start[0], f->d_ent[0], f->d_kps, v.d_desc, f->d_desc, f->d_cell_start[1], cam,
@@ -480,6 +484,7 @@ int to_frame_hook(void *ctx, hipStream_t s, const OrbOutputView &v) {
 
 void frame_clear(vsg_frame *f) {
   f->n = 0, f->nleft = -1, f->has_uright = false, f->fv_valid = false, f->pose_held = false;
+  f->stereo_attached = f->any_stereo = false;
   f->h_kps.clear();
 }
 
@@ -567,6 +572,7 @@ int extract_to_frame(vsg_orb *h, const uint8_t *gray, int rows, int cols, int st
     return mono < 0 ? mono : VSG_ERR_CAPACITY;
   }
   f->n = *n, f->nleft = -1, f->has_uright = A != nullptr, f->fv_valid = false, f->pose_held = false;
+  f->stereo_attached = false, f->any_stereo = f->has_uright;  // mvuRight is computed on the device: assume some are >= 0
   if (H.cam.distorted) {
     f->h_kps.assign((const vsg_keypoint *)un_pin, (const vsg_keypoint *)un_pin + *n);
     if (keys_un_out && *n) memcpy(keys_un_out, un_pin, (size_t)*n * sizeof(vsg_keypoint));

@@ -51,6 +51,11 @@ struct vsg_frame {
   uint8_t *d_pose = nullptr;
   bool pose_held = false;
   std::vector<int32_t> pose_feat;
+  // CreateNewMapPoints (vsg_triangulate.hip): any_stereo = some mvuRight of the CURRENT features may be >= 0 (known for an
+  // uploaded array, assumed for one the device computed); d_stereo = {x3Dc, cos parallax} per feature, allocated by the
+  // first vsg_frame_set_stereo_points; stereo_attached: it holds the current features' values (every upload drops it)
+  bool any_stereo = false, stereo_attached = false;
+  float4 *d_stereo = nullptr;
 };
 
 namespace vsg {
@@ -77,6 +82,13 @@ struct StoreView {
   int device, capacity;
 };
 bool store_view(const vsg_mappoints *mp, StoreView *v);
+// every field of a store, for the one kernel outside vsg_mappoints.hip that WRITES points (k_new_points)
+struct StoreFields {
+  float *pos, *normal, *min_dist, *max_dist;
+  uint8_t *desc, *observed;
+  int device, capacity;
+};
+bool store_fields(vsg_mappoints *mp, StoreFields *v);
 inline int frame_check(const vsg_frame *f) { return f && f->d_block ? VSG_OK : VSG_ERR_INVALID; }
 // a vsg_grid (include/vsg_orb.h) is a vsg_frame behind an opaque name
 inline vsg_frame *grid_frame(vsg_grid *g) { return (vsg_frame *)g; }
@@ -184,6 +196,29 @@ void bow_search_sizes(int nA, int nB, int mode, size_t *pin_bytes, size_t *dev_b
 int bow_search_enqueue(BowSearchCall *s, int mode, vsg_frame *A, const uint8_t *validA, vsg_frame *B, const uint8_t *validB,
                        float nnratio, ThreadCtx *c, size_t pin_base, size_t dev_base);
 int bow_search_finish(BowSearchCall *s, int check_orientation, int32_t *out);
+
+// vsg_frame_search_for_triangulation_epipolar in two halves (vsg_match.hip): the check, then layout + launch on the calling
+// thread's arena with room for the caller's own blocks behind the search's
+struct EpiSearchArgs {
+  vsg_frame *kf1;
+  const uint8_t *no_mp1;
+  const int32_t *node_id1, *off1, *idx1;
+  int nodes1;
+  vsg_frame *kf2;
+  const uint8_t *no_mp2;
+  const int32_t *node_id2, *off2, *idx2;
+  int nodes2;
+  const float *F12, *ep, *scale_factors2, *level_sigma2_2;
+  int nlevels, only_stereo, coarse;
+};
+struct EpiSearch {
+  ThreadCtx *c = nullptr;
+  int n1 = 0;
+  bool launched = false;      // false: no walk was needed, every match is -1
+  size_t oM = 0, oExtra = 0;  // the matches / the caller's block, offsets into the pinned arena
+};
+int epipolar_search_check(const EpiSearchArgs &a, const int32_t *matches12);
+int epipolar_search_enqueue(EpiSearch *s, const EpiSearchArgs &a, size_t extra_bytes);
 
 // view of the handle's outputs of the last extract call (vsg_orb.hip)
 struct OrbOutputView {

@@ -46,6 +46,12 @@ bool vsg::store_view(const vsg_mappoints *mp, StoreView *v) {
   return true;
 }
 
+bool vsg::store_fields(vsg_mappoints *mp, StoreFields *v) {
+  if (!mp || !mp->d_block) return false;
+  *v = {mp->d_pos, mp->d_normal, mp->d_min, mp->d_max, mp->d_desc, mp->d_observed, mp->device, mp->capacity};
+  return true;
+}
+
 namespace {
 
 struct StoreDev {

@@ -937,6 +937,81 @@ static EpiFrame epi_frame(const vsg_frame *f, const uint8_t *no_mp) {
 
 }  // namespace
 
+// ---- the epipolar search in two halves (vsg_frame_int.h), shared by vsg_frame_search_for_triangulation_epipolar and
+// vsg_frame_create_new_map_points (vsg_triangulate.hip)
+namespace vsg {
+
+// everything that can be refused is refused here, before anything is enqueued
+int epipolar_search_check(const EpiSearchArgs &a, const int32_t *matches12) {
+  vsg_frame *kf1 = a.kf1, *kf2 = a.kf2;
+  if (vsg::frame_check(kf1) != VSG_OK || vsg::frame_check(kf2) != VSG_OK || kf1->device != kf2->device || !a.F12 || !a.ep ||
+      !a.scale_factors2 || !a.level_sigma2_2 || a.nlevels < 1 || a.nlevels > 16 || (!matches12 && kf1->n > 0) ||
+      (!a.no_mp1 && kf1->n > 0) || (!a.no_mp2 && kf2->n > 0))
+    return VSG_ERR_INVALID;
+  if (kf1->nleft != -1 || kf2->nleft != -1) return VSG_ERR_UNSUPPORTED;  // mpCamera2 (:929-937, :1033-1071)
+  if (!octaves_within(kf2, a.nlevels)) return VSG_ERR_INVALID;
+  const bool resident_fv = !a.node_id1 && !a.off1 && !a.idx1 && !a.node_id2 && !a.off2 && !a.idx2;
+  if (!resident_fv) {
+    if (!a.node_id1 || !a.off1 || !a.idx1 || !a.node_id2 || !a.off2 || !a.idx2) return VSG_ERR_INVALID;
+    // the kernel indexes the frames with these: an index outside a frame never reaches the device
+    const vsg::FvView v1{a.node_id1, a.off1, a.idx1, a.nodes1}, v2{a.node_id2, a.off2, a.idx2, a.nodes2};
+    if (!vsg::fv_check(v1, kf1->n) || !vsg::fv_check(v2, kf2->n)) return VSG_ERR_INVALID;
+  }
+  // ComputeBoW first (Frame.cc:882-889); an empty frame has an empty FeatureVector whatever ComputeBoW left
+  if (resident_fv && kf1->n > 0 && kf2->n > 0 && (!kf1->fv_valid || !kf2->fv_valid)) return VSG_ERR_INVALID;
+  return VSG_OK;
+}
+
+// After the check: lays the call out in the calling thread's pinned arena with `extra_bytes` for the caller behind it (at
+// s->oExtra) and enqueues the walk.  s->launched == false: no launch was needed, every match is -1 (and when
+// extra_bytes != 0 the arena still holds the caller's block).  The caller looks at hipGetLastError and waits.
+int epipolar_search_enqueue(EpiSearch *s, const EpiSearchArgs &a, size_t extra_bytes) {
+  vsg_frame *kf1 = a.kf1, *kf2 = a.kf2;
+  const int n1 = kf1->n, n2 = kf2->n;
+  s->n1 = n1, s->launched = false;
+  const bool resident_fv = !a.node_id1;
+  std::vector<NodePair> pairs;
+  bool empty = n1 == 0 || n2 == 0;  // no shared node, 0 matches (ORBmatcher.cc:961)
+  if (!empty) {
+    if (resident_fv) {
+      empty = kf1->fv_empty || kf2->fv_empty;  // ComputeBoW with an empty() vocabulary left no node
+    } else {
+      vsg::join_nodes(a.node_id1, a.off1, a.nodes1, a.node_id2, a.off2, a.nodes2, pairs);
+      empty = pairs.empty();
+    }
+  }
+  if (empty && !extra_bytes) return VSG_OK;
+  int rc = VSG_OK;
+  ThreadCtx *c = s->c = vsg::thread_ctx(kf1->device, &rc);
+  if (!c) return rc;
+  // ONE launch and nothing else on the stream (as bow_search_enqueue): the flags and lists are read and the matches written
+  // where they lie in the pinned arena
+  const int npairs = (int)pairs.size();
+  Upload up;
+  const size_t oF1 = up.add(a.no_mp1, (size_t)n1), oF2 = up.add(a.no_mp2, (size_t)n2),
+               oP = up.add(pairs.data(), pairs.size() * sizeof(NodePair)),
+               oI1 = up.add(a.idx1, resident_fv ? 0 : (size_t)a.off1[a.nodes1] * 4),
+               oI2 = up.add(a.idx2, resident_fv ? 0 : (size_t)a.off2[a.nodes2] * 4), oM = up.add(nullptr, (size_t)n1 * 4);
+  s->oM = oM, s->oExtra = up.st.add(extra_bytes);
+  rc = vsg::ctx_reserve(c, up.st.total, 0);
+  if (rc != VSG_OK) return rc;
+  uint8_t *h = c->h_pin, *d = c->d_pin;
+  up.fill(h);
+  memset(h + oM, 0xFF, (size_t)n1 * 4);  // -1: the kernel only writes matches
+  if (empty) return VSG_OK;
+  const EpipolarPred pred{epi_frame(kf1, d + oF1), epi_frame(kf2, d + oF2),
+                          epi_params(a.F12, a.ep, a.scale_factors2, a.level_sigma2_2, a.nlevels, a.only_stereo, a.coarse)};
+  const int blocks = resident_fv ? (kf1->fv_bound > 0 ? kf1->fv_bound : 1) : npairs;
+  hipLaunchKernelGGL(k_triangulation_walk<EpipolarPred>, dim3(blocks), dim3(256), 0, c->stream,
+                     resident_fv ? (const NodePair *)nullptr : (const NodePair *)(d + oP), npairs,
+                     resident_fv ? vsg::fv_dev(kf1) : FvDev{}, resident_fv ? vsg::fv_dev(kf2) : FvDev{},
+                     (const int *)(d + oI1), (const int *)(d + oI2), pred, (int *)(d + oM));
+  s->launched = true;
+  return VSG_OK;
+}
+
+}  // namespace vsg
+
 extern "C" {
 
 int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *no_mp1, const int32_t *node_id1,
@@ -945,58 +1020,19 @@ int vsg_frame_search_for_triangulation_epipolar(vsg_frame *kf1, const uint8_t *n
                                                 const int32_t *idx2, int nodes2, const float F12[9], const float ep[2],
                                                 const float *scale_factors2, const float *level_sigma2_2, int nlevels,
                                                 int only_stereo, int coarse, int check_orientation, int32_t *matches12) {
-  // ---- everything that can be refused is refused here, before anything is enqueued
-  if (vsg::frame_check(kf1) != VSG_OK || vsg::frame_check(kf2) != VSG_OK || kf1->device != kf2->device || !F12 || !ep ||
-      !scale_factors2 || !level_sigma2_2 || nlevels < 1 || nlevels > 16 || (!matches12 && kf1->n > 0) ||
-      (!no_mp1 && kf1->n > 0) || (!no_mp2 && kf2->n > 0))
-    return VSG_ERR_INVALID;
-  if (kf1->nleft != -1 || kf2->nleft != -1) return VSG_ERR_UNSUPPORTED;  // mpCamera2 (:929-937, :1033-1071)
-  if (!octaves_within(kf2, nlevels)) return VSG_ERR_INVALID;
-  const bool resident_fv = !node_id1 && !off1 && !idx1 && !node_id2 && !off2 && !idx2;
-  const vsg::FvView v1{node_id1, off1, idx1, nodes1}, v2{node_id2, off2, idx2, nodes2};
-  if (!resident_fv) {
-    if (!node_id1 || !off1 || !idx1 || !node_id2 || !off2 || !idx2) return VSG_ERR_INVALID;
-    // the kernel indexes the frames with these: an index outside a frame never reaches the device
-    if (!vsg::fv_check(v1, kf1->n) || !vsg::fv_check(v2, kf2->n)) return VSG_ERR_INVALID;
-  }
-  const int n1 = kf1->n, n2 = kf2->n;
-  // ComputeBoW first (Frame.cc:882-889); an empty frame has an empty FeatureVector whatever ComputeBoW left
-  if (resident_fv && n1 > 0 && n2 > 0 && (!kf1->fv_valid || !kf2->fv_valid)) return VSG_ERR_INVALID;
-  for (int i = 0; i < n1; i++) matches12[i] = -1;  // no output is touched before the last refusal
-  if (n1 == 0 || n2 == 0) return 0;  // no shared node, 0 matches (ORBmatcher.cc:961)
-  std::vector<NodePair> pairs;
-  if (resident_fv) {
-    if (kf1->fv_empty || kf2->fv_empty) return 0;  // ComputeBoW with an empty() vocabulary left no node
-  } else {
-    vsg::join_nodes(node_id1, off1, nodes1, node_id2, off2, nodes2, pairs);
-    if (pairs.empty()) return 0;
-  }
-  int rc = VSG_OK;
-  ThreadCtx *c = vsg::thread_ctx(kf1->device, &rc);
-  if (!c) return rc;
-  // ONE launch and nothing else on the stream (as bow_search_enqueue): the flags and lists are read and the matches written
-  // where they lie in the pinned arena
-  const int npairs = (int)pairs.size();
-  Upload up;
-  const size_t oF1 = up.add(no_mp1, (size_t)n1), oF2 = up.add(no_mp2, (size_t)n2),
-               oP = up.add(pairs.data(), pairs.size() * sizeof(NodePair)),
-               oI1 = up.add(idx1, resident_fv ? 0 : (size_t)off1[nodes1] * 4),
-               oI2 = up.add(idx2, resident_fv ? 0 : (size_t)off2[nodes2] * 4), oM = up.add(nullptr, (size_t)n1 * 4);
-  rc = vsg::ctx_reserve(c, up.st.total, 0);
+  const vsg::EpiSearchArgs a{kf1, no_mp1, node_id1, off1, idx1, nodes1, kf2, no_mp2, node_id2, off2, idx2, nodes2, F12, ep,
+                             scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse};
+  int rc = vsg::epipolar_search_check(a, matches12);
   if (rc != VSG_OK) return rc;
-  uint8_t *h = c->h_pin, *d = c->d_pin;
-  up.fill(h);
-  memset(h + oM, 0xFF, (size_t)n1 * 4);  // -1: the kernel only writes matches
-  const EpipolarPred pred{epi_frame(kf1, d + oF1), epi_frame(kf2, d + oF2),
-                          epi_params(F12, ep, scale_factors2, level_sigma2_2, nlevels, only_stereo, coarse)};
-  const int blocks = resident_fv ? (kf1->fv_bound > 0 ? kf1->fv_bound : 1) : npairs;
-  hipLaunchKernelGGL(k_triangulation_walk<EpipolarPred>, dim3(blocks), dim3(256), 0, c->stream,
-                     resident_fv ? (const NodePair *)nullptr : (const NodePair *)(d + oP), npairs,
-                     resident_fv ? vsg::fv_dev(kf1) : FvDev{}, resident_fv ? vsg::fv_dev(kf2) : FvDev{},
-                     (const int *)(d + oI1), (const int *)(d + oI2), pred, (int *)(d + oM));
-  const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(c->stream);  // an error still waits
+  const int n1 = kf1->n;
+  for (int i = 0; i < n1; i++) matches12[i] = -1;  // no output is touched before the last refusal
+  vsg::EpiSearch s;
+  rc = vsg::epipolar_search_enqueue(&s, a, 0);
+  if (rc != VSG_OK) return rc;
+  if (!s.launched) return 0;
+  const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(s.c->stream);  // an error still waits
   if (launched != hipSuccess || waited != hipSuccess) return VSG_ERR_HIP;
-  memcpy(matches12, h + oM, (size_t)n1 * 4);
+  memcpy(matches12, s.c->h_pin + s.oM, (size_t)n1 * 4);
   const vsg_keypoint *ka = kf1->h_kps.data(), *kb = kf2->h_kps.data();
   return bow_rotation_filter(matches12, n1, 1, [&](int i) { return ka[i].angle; }, [&](int i) { return kb[i].angle; },
                              check_orientation != 0);

@@ -38,6 +38,7 @@ VSG_HD double dmul(double a, double b) { return __dmul_rn(a, b); }
 VSG_HD double dadd(double a, double b) { return __dadd_rn(a, b); }
 VSG_HD double dsub(double a, double b) { return __dsub_rn(a, b); }
 VSG_HD double dfma(double a, double b, double c) { return __fma_rn(a, b, c); }
+VSG_HD double ddiv(double a, double b) { return a / b; }  // IEEE in hipcc's gfx950 lowering (as vsg_pose_opt.h relies on)
 VSG_HD int round_half_even(float v) { return __float2int_rn(v); }
 #else
 VSG_HD float fmul(float a, float b) {
@@ -69,6 +70,10 @@ VSG_HD double dsub(double a, double b) {
   return r;
 }
 VSG_HD double dfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+VSG_HD double ddiv(double a, double b) {
+  volatile double r = a / b;
+  return r;
+}
 VSG_HD int round_half_even(float v) { return (int)__builtin_lrintf(v); }
 #endif
 
@@ -259,6 +264,7 @@ VSG_HD float log_f32(float x) { return logf_glibc<false>(x); }
 // unless OCML_BASIC_ROUNDED_OPERATIONS is set; sqrtf is IEEE under hipcc's default
 // -fhip-fp32-correctly-rounded-divide-sqrt, which is also what makes the `/` behind __fdiv_rn exact.
 VSG_HD float fsqrt(float a) { return __builtin_sqrtf(a); }
+VSG_HD double dsqrt(double a) { return __builtin_sqrt(a); }  // correctly rounded on both sides, as vsg_pose_opt.h's sqrt
 
 // fast_atan2_deg without the two-sided branch (both sides are the same polynomial of min / max); bit-identical: when
 // ax == ay both forms divide the same values

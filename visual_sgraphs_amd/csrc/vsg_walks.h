@@ -11,6 +11,12 @@
 #include <cmath>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define VSG_WALK_HD __host__ __device__ inline
+#else
+#define VSG_WALK_HD inline
+#endif
+
 namespace vsg {
 namespace walk {
 
@@ -36,7 +42,7 @@ struct CandView {
 };
 
 // rotation-consistency bin (e.g. ORBmatcher.cc:351-356, 1771-1777)
-inline int rot_bin(float angle1, float angle2) {
+VSG_WALK_HD int rot_bin(float angle1, float angle2) {
   const float factor = 1.0f / HISTO_LENGTH;
   float rot = angle1 - angle2;
   if (rot < 0.0) rot += 360.0f;
@@ -45,11 +51,13 @@ inline int rot_bin(float angle1, float angle2) {
   return bin;
 }
 
-// ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:2002-2043)
-inline void three_maxima(const std::vector<int> *histo, int L, int &ind1, int &ind2, int &ind3) {
+// ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:2002-2043) on the bins' sizes; size(i) = histo[i].size().  The host
+// passes hand it their vectors, k_new_points (vsg_triangulate.hip) its 30 counts in LDS.
+template <class SizeOf>
+VSG_WALK_HD void three_maxima_of(SizeOf size, int L, int &ind1, int &ind2, int &ind3) {
   int max1 = 0, max2 = 0, max3 = 0;
   for (int i = 0; i < L; i++) {
-    const int s = (int)histo[i].size();
+    const int s = size(i);
     if (s > max1) {
       max3 = max2, max2 = max1, max1 = s;
       ind3 = ind2, ind2 = ind1, ind1 = i;
@@ -66,6 +74,9 @@ inline void three_maxima(const std::vector<int> *histo, int L, int &ind1, int &i
   } else if (max3 < 0.1f * (float)max1) {
     ind3 = -1;
   }
+}
+inline void three_maxima(const std::vector<int> *histo, int L, int &ind1, int &ind2, int &ind3) {
+  three_maxima_of([&](int i) { return (int)histo[i].size(); }, L, ind1, ind2, ind3);
 }
 
 // entries of the losing bins are handed to `drop`

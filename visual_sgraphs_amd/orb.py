@@ -85,6 +85,8 @@ EXPORTS = [
     "vsg_mappoints_refresh_from_observations",
     # Optimizer::PoseOptimization on a resident frame and resident map points
     "vsg_frame_pose_optimization", "vsg_frame_pose_optimization_resume",
+    # LocalMapping::CreateNewMapPoints on resident keyframes: triangulate, gate, write the new points into the store
+    "vsg_frame_set_stereo_points", "vsg_frame_triangulate_matches", "vsg_frame_create_new_map_points",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -117,6 +119,29 @@ class FramePose(C.Structure):
         p.fx, p.fy, p.cx, p.cy, p.mbf = float(fx), float(fy), float(cx), float(cy), float(mbf)
         p.log_scale_factor, p.n_levels = float(log_scale_factor), int(n_levels)
         return p
+
+
+class TriangulationParams(C.Structure):
+    """include/vsg_orb.h vsg_triangulation_params: the two cameras of LocalMapping::CreateNewMapPoints (kf1 =
+    mpCurrentKeyFrame, kf2 = pKF2), ratioFactor, mbInertial, mbFarPoints / mThFarPoints and kf2_first =
+    std::less<KeyFrame *>()(pKF2, mpCurrentKeyFrame)."""
+    _fields_ = [("kf1", FramePose), ("kf2", FramePose), ("ratio_factor", C.c_float), ("th_far_points", C.c_float),
+                ("inertial", C.c_int32), ("far_points", C.c_int32), ("kf2_first", C.c_int32)]
+
+    @classmethod
+    def make(cls, kf1, kf2, ratio_factor, inertial=False, far_points=False, th_far_points=0.0, kf2_first=False):
+        p = cls()
+        p.kf1, p.kf2 = kf1, kf2
+        p.ratio_factor, p.th_far_points = float(ratio_factor), float(th_far_points)
+        p.inertial, p.far_points, p.kf2_first = int(bool(inertial)), int(bool(far_points)), int(bool(kf2_first))
+        return p
+
+
+# vsg_frame_triangulate_matches / vsg_frame_create_new_map_points: reason and source codes (VSG_TRI_* of include/vsg_orb.h)
+TRI_REASONS = ("accepted", "low_parallax", "w_zero", "stereo_depth", "z1", "z2", "reproj1", "reproj2", "dist_zero", "far",
+               "scale_ratio", "no_free_slot")
+TRI_NO_MATCH = 255
+TRI_FROM_TRIANGULATE, TRI_FROM_STEREO1, TRI_FROM_STEREO2 = 0, 1, 2
 
 
 class PoseSE3(C.Structure):
@@ -367,6 +392,12 @@ def load_library():
     L.vsg_frame_pose_optimization.argtypes = [vp, vp, _i32p, C.POINTER(PoseSE3), cf, cf, cf, cf, cf, _f32p, ci, ci, _u8p,
                                               _f32p, C.POINTER(PoseResult)]
     L.vsg_frame_pose_optimization_resume.argtypes = [vp, _u8p, _u8p, _f32p, C.POINTER(PoseResult)]
+    tri_tail = [C.POINTER(TriangulationParams), _f32p, _f32p, _f32p, _f32p, ci, vp, _i32p, ci]
+    tri_outs = [_u8p, _u8p, _f32p, _i32p, _i32p]
+    L.vsg_frame_set_stereo_points.argtypes = [vp, _f32p, _f32p]
+    L.vsg_frame_triangulate_matches.argtypes = [vp, vp, _i32p] + tri_tail + tri_outs
+    L.vsg_frame_create_new_map_points.argtypes = [vp, _u8p, _i32p, _i32p, _i32p, ci, vp, _u8p, _i32p, _i32p, _i32p, ci, _f32p,
+                                                  _f32p, ci, ci, ci] + tri_tail + [_i32p] + tri_outs
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1757,6 +1788,68 @@ class Frame:
             int(bool(only_stereo)), int(bool(coarse)), int(bool(check_orientation)), _p(out, _i32p)),
             "vsg_frame_search_for_triangulation_epipolar")
         return nm, out[:self.N]
+
+    def SetStereoPoints(self, xyz_c, cos_parallax):
+        """vsg_frame_set_stereo_points: per feature x3Dc of KeyFrame::UnprojectStereo (KeyFrame.cc:887-894) and
+        cos(2 * atan2(mb / 2, mvDepth[i])) (LocalMapping.cc:569), computed by the caller; once per keyframe, dropped by
+        the next upload."""
+        x, c = _f32(np.asarray(xyz_c).reshape(-1)), _f32(cos_parallax)
+        assert len(x) >= 3 * self.N and len(c) >= self.N
+        _check(self._L.vsg_frame_set_stereo_points(self._h, _p(x, _f32p), _p(c, _f32p)), "vsg_frame_set_stereo_points")
+        return self
+
+    def _tri_args(self, params, tables, mp, free_slots):
+        sf1, s1, sf2, s2 = (_f32(t) for t in tables)
+        assert len(sf1) == len(s1) == len(sf2) == len(s2)
+        fs = _i32(free_slots if free_slots is not None else [])
+        n_free = 0 if free_slots is None else len(free_slots)
+        n = max(self.N, 1)
+        out = dict(reason=np.zeros(n, np.uint8), source=np.zeros(n, np.uint8), x3d=np.zeros((n, 3), np.float32),
+                   new_slot=np.zeros(n, np.int32))
+        created = C.c_int32(0)
+        tail = [C.byref(params), _p(sf1, _f32p), _p(s1, _f32p), _p(sf2, _f32p), _p(s2, _f32p), len(sf1),
+                mp.handle if mp is not None else None, _p(fs, _i32p), n_free]
+        outs = [_p(out["reason"], _u8p), _p(out["source"], _u8p), _p(out["x3d"], _f32p), _p(out["new_slot"], _i32p),
+                C.byref(created)]
+        return tail, outs, out, created, (sf1, s1, sf2, s2, fs)
+
+    def TriangulateMatches(self, kf2, matches12, params, scale_factors1, level_sigma2_1, scale_factors2, level_sigma2_2,
+                           mp=None, free_slots=None):
+        """The loop over one neighbour's matches of LocalMapping::CreateNewMapPoints (LocalMapping.cc:475-708), self =
+        mpCurrentKeyFrame, kf2 = pKF2, for a match list the caller holds (vsg_frame_triangulate_matches).  mp = a
+        MapPoints store the accepted pairs are written into, in ascending idx1 into free_slots (None: geometry only).
+        Returns dict(reason, source, x3d, new_slot, n_created)."""
+        m = _i32(matches12)
+        assert len(m) >= self.N
+        tail, outs, out, created, keep = self._tri_args(params, (scale_factors1, level_sigma2_1, scale_factors2,
+                                                                 level_sigma2_2), mp, free_slots)
+        _check(self._L.vsg_frame_triangulate_matches(self._h, kf2.handle, _p(m, _i32p), *tail, *outs),
+               "vsg_frame_triangulate_matches")
+        return dict({k: v[:self.N] for k, v in out.items()}, n_created=created.value)
+
+    def CreateNewMapPoints(self, no_mp1, kf2, no_mp2, F12, ep, only_stereo, coarse, check_orientation, params,
+                           scale_factors1, level_sigma2_1, scale_factors2, level_sigma2_2, mp=None, free_slots=None,
+                           fv1=None, fv2=None):
+        """One neighbour of LocalMapping::CreateNewMapPoints (LocalMapping.cc:456-708) in one enqueue and one wait
+        (vsg_frame_create_new_map_points): SearchForTriangulationEpipolar's search, the rotation filter on the device, then
+        TriangulateMatches on what is left.  Returns dict(nmatches, matches12, reason, source, x3d, new_slot, n_created)."""
+        m1, m2 = _u8(no_mp1), _u8(no_mp2)
+        F, e = _f32(np.asarray(F12).reshape(9)), _f32(np.asarray(ep).reshape(2))
+        if (fv1 is None) != (fv2 is None):
+            raise ValueError("fv1 and fv2: both or neither")
+        a1 = a2 = (None, None, None)
+        keep_fv = []
+        if fv1 is not None:
+            keep_fv = [_i32(x) for x in fv1] + [_i32(x) for x in fv2]
+            a1, a2 = tuple(_p(x, _i32p) for x in keep_fv[:3]), tuple(_p(x, _i32p) for x in keep_fv[3:])
+        tail, outs, out, created, keep = self._tri_args(params, (scale_factors1, level_sigma2_1, scale_factors2,
+                                                                 level_sigma2_2), mp, free_slots)
+        m12 = np.full(max(self.N, 1), -1, np.int32)
+        nm = _check(self._L.vsg_frame_create_new_map_points(
+            self._h, _p(m1, _u8p), *a1, len(fv1[0]) if fv1 is not None else 0, kf2.handle, _p(m2, _u8p), *a2,
+            len(fv2[0]) if fv2 is not None else 0, _p(F, _f32p), _p(e, _f32p), int(bool(only_stereo)), int(bool(coarse)),
+            int(bool(check_orientation)), *tail, _p(m12, _i32p), *outs), "vsg_frame_create_new_map_points")
+        return dict({k: v[:self.N] for k, v in out.items()}, nmatches=nm, matches12=m12[:self.N], n_created=created.value)
 
     def ComputeBoW(self, voc, levelsup=4):
         """Frame::ComputeBoW on the resident descriptors; same dict as ORBVocabulary.transform."""
