@@ -994,6 +994,47 @@ int vsg_frame_create_new_map_points(vsg_frame *kf1, const uint8_t *no_mp1, const
                                     const float *level_sigma2_2, int nlevels, vsg_mappoints *mp, const int32_t *free_slots,
                                     int n_free, int32_t *matches12, uint8_t *reason, uint8_t *source, float *x3d,
                                     int32_t *new_slot, int32_t *n_created);
+/* Sim3Solver (Sim3Solver.cc; LoopClosing.cc:678-690) on resident map points: EVERY RANSAC hypothesis in one call.
+ * Hypothesis k depends on its three sampled correspondences alone and iterate's stopping rule (:215-291, called until
+ * bConverge || bNoMore) is a function of the hypotheses' inlier counts c[k]: converged at the FIRST k with
+ * c[k] > min_inliers (mnIterations = k + 1), otherwise bNoMore with the members holding the LAST k that reaches the
+ * maximum.  So the call computes all n_hyp hypotheses side by side and selects.
+ *   Correspondence i (mvpMapPoints1[i], mvpMapPoints2[i]) = slot slots1[i] of mp1 and slot slots2[i] of mp2 (mp2 may be
+ * mp1; a merge candidate lives in another map).  kf1 / kf2 = pKF1 / pKF2: Rcw, tcw, fx, fy, cx, cy are read, nothing else;
+ * X3Dc2 goes through kf2's pose also for a point matched through another keyframe pKFm (:107) -- only the sigma is pKFm's.
+ * max_err1 / max_err2 = mvnMaxError1 / 2 AS THE COMPARISON SEES THEM: 9.210 * sigmaSquare is a double stored into a
+ * std::vector<size_t> (Sim3Solver.h:72-73), so the threshold is truncated toward zero and `err < mvnMaxError[i]` compares
+ * with that integer as a float: pass (float)(size_t)(9.210 * sigma2).  fix_scale = mbFixScale, min_inliers =
+ * mRansacMinInliers, n_hyp = mRansacMaxIts after SetRansacParameters (vsg_sim3_ransac_iterations), samples[3 k .. 3 k + 2] =
+ * the three correspondence indices of hypothesis k in the order they fill columns 0..2 (vsg_sim3_draw_samples).
+ *   Outputs: inlier[i] = mvbInliersi of the returned hypothesis (the caller scatters it to vbInliers[mvnIndices1[i]]);
+ * res as below; hyp_inliers[k] / hyp_T12[16 k ..] (either may be NULL) = mnInliersi / mT12i of every hypothesis.
+ * n < min_inliers (:222-226): no_more = 1, the identity, best_hypothesis -1, flags cleared, nothing is enqueued.
+ *   Arithmetic (csrc/vsg_sim3.h, host and device from one source): float in the reference's order;
+ * the eigenvector of N comes from a double Jacobi instead of Eigen's float EigenSolver and the rotation from the quaternion
+ * directly instead of atan2 + SO3f::exp, both deviations by rounding; a zero imaginary part gives the reference's NaN
+ * rotation and no inlier.  NaNs in res and hyp_T12 are canonical.
+ *   Checked before anything is enqueued (an error writes nothing and leaves no kernel behind), VSG_ERR_INVALID: NULL
+ * handles, poses, res, samples, or (n > 0) arrays; stores on different devices; n < 0; a slot outside [0, capacity) of its
+ * store; n_hyp outside [1, 1024]; min_inliers < 0; and when n >= min_inliers: n < 3, a sample outside [0, n), two equal
+ * samples in one triple.  One enqueue (three kernels) on the calling thread's stream and one wait; only the indices, the
+ * thresholds, two poses and the samples cross to the device. */
+typedef struct vsg_sim3_result {
+  float R12[9], t12[3], s12, T12[16]; /* mBestRotation (row-major), mBestTranslation, mBestScale, mBestT12 (row-major) */
+  int32_t converged, no_more, n_inliers, best_hypothesis, iterations; /* bConverge, bNoMore, mnBestInliers, k, mnIterations */
+} vsg_sim3_result;
+int vsg_mappoints_sim3_ransac(vsg_mappoints *mp1, vsg_mappoints *mp2, int n, const int32_t *slots1, const int32_t *slots2,
+                              const float *max_err1, const float *max_err2, const vsg_frame_pose *kf1,
+                              const vsg_frame_pose *kf2, int fix_scale, int min_inliers, int n_hyp, const int32_t *samples,
+                              uint8_t *inlier, vsg_sim3_result *res, int32_t *hyp_inliers, float *hyp_T12);
+/* Sim3Solver::SetRansacParameters (:120-144): mRansacMaxIts for n correspondences, with the float epsilon and
+ * max(1, min(nIterations, max_iterations)).  Host only.  n < 0 or min_inliers < 0: VSG_ERR_INVALID. */
+int vsg_sim3_ransac_iterations(double probability, int min_inliers, int max_iterations, int n);
+/* The draw of :242-256 for n_hyp hypotheses: per hypothesis a copy of mvAllIndices (0 .. n-1), then three times
+ * randi = random_int(0, size - 1, ctx), the element is taken, back() moves into its place, pop_back().  random_int == NULL:
+ * DUtils::Random::RandomInt's formula over rand() (Random.cpp:47-50).  Host only.  n < 3, n_hyp < 0, NULL samples, or a
+ * random_int result outside its range: VSG_ERR_INVALID. */
+int vsg_sim3_draw_samples(int n, int n_hyp, int (*random_int)(int lo, int hi, void *ctx), void *ctx, int32_t *samples);
 /* Frame::ComputeBoW (Frame.cc:882-889) on the resident descriptors; outputs as vsg_bow_transform. */
 int vsg_frame_bow_transform(vsg_vocab *voc, vsg_frame *f, int levelsup, int32_t *bow_ids, double *bow_vals,
                             int bow_cap, int *n_bow, int32_t *fv_node, int32_t *fv_off, int32_t *fv_idx, int fv_cap,

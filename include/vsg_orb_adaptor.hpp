@@ -1287,4 +1287,129 @@ inline void WaitBatch(const ORBextractor &ex, int ticket, std::vector<int> &n, s
   check(vsg_orb_wait(ex.handle(), ticket, n.data(), monoIndex.data()), "vsg_orb_wait");
 }
 
+// Sim3Solver (Sim3Solver.h, Sim3Solver.cc) on resident map points, with the reference's shape so that the loop of
+// LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:678-690) stays as it is:
+//     vsg::ResidentSim3Solver solver(mp1, mp2, slots1, slots2, maxErr1, maxErr2, mvnIndices1, N1, pose1, pose2, mbFixScale);
+//     solver.SetRansacParameters(0.99, nBoWInliers, 300);
+//     while (!bConverge && !bNoMore) mTcm = solver.iterate(20, bNoMore, vbInliers, nInliers, bConverge);
+// The maintainer's constructor keeps the reference's filter (:68-112: both points exist, neither isBad, both have an index in
+// their keyframe) and hands over what survives it: correspondence i = slot slots1[i] of mp1 (pMP1) against slot slots2[i] of
+// mp2 (pMP2; the same store or another map's), maxErr1 / maxErr2[i] = Sim3MaxError(mvLevelSigma2[kp.octave]) of pKF1 / pKFm,
+// mvnIndices1[i] = i1 and mN1 = vpMatched12.size().  pose1 / pose2 = pKF1's / pKF2's pose and camera (X3Dc2 goes through
+// pKF2's pose also for a point matched through pKFm, :107).  The FIRST iterate (or find) computes every hypothesis in one
+// device call (vsg_mappoints_sim3_ransac); later calls replay the reference's nIterations-at-a-time view of that result.
+// Matrices are row-major arrays (the maintainer maps them: Eigen::Map<Eigen::Matrix<float, 4, 4, Eigen::RowMajor>>).
+// The samples come from vsg_sim3_draw_samples with DUtils::Random::RandomInt's formula over rand(), or from randomInt.
+inline float Sim3MaxError(float sigmaSquare) { return (float)(size_t)(9.210 * sigmaSquare); }  // :96-97, Sim3Solver.h:72-73
+inline float Sim3MaxError(const std::vector<float> &mvLevelSigma2, int octave) { return Sim3MaxError(mvLevelSigma2[(size_t)octave]); }
+
+class ResidentSim3Solver {
+ public:
+  typedef std::vector<float> Matrix;  // row-major
+  ResidentSim3Solver(const ResidentMapPoints &mp1, const ResidentMapPoints &mp2, const std::vector<int32_t> &slots1,
+                     const std::vector<int32_t> &slots2, const std::vector<float> &maxErr1, const std::vector<float> &maxErr2,
+                     const std::vector<size_t> &mvnIndices1, int mN1, const FramePose &pose1, const FramePose &pose2,
+                     bool bFixScale = false, int (*randomInt)(int, int, void *) = nullptr, void *randomCtx = nullptr)
+      : mp1_(mp1.handle()), mp2_(mp2.handle()), slots1_(slots1), slots2_(slots2), maxErr1_(maxErr1), maxErr2_(maxErr2),
+        mvnIndices1_(mvnIndices1), mN1_(mN1), pose1_(pose1), pose2_(pose2), mbFixScale_(bFixScale), randomInt_(randomInt),
+        randomCtx_(randomCtx) {
+    N_ = (int)slots1_.size();
+    if (slots2_.size() != slots1_.size() || maxErr1_.size() != slots1_.size() || maxErr2_.size() != slots1_.size() ||
+        mvnIndices1_.size() != slots1_.size())
+      check(VSG_ERR_INVALID, "vsg::ResidentSim3Solver");
+    for (size_t i1 : mvnIndices1_)
+      if (i1 >= (size_t)(mN1_ > 0 ? mN1_ : 0)) check(VSG_ERR_INVALID, "vsg::ResidentSim3Solver");
+    fill_identity();
+    SetRansacParameters();
+  }
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    mRansacMinInliers_ = minInliers;
+    mRansacMaxIts_ = vsg_sim3_ransac_iterations(probability, minInliers, maxIterations, N_);
+    check(mRansacMaxIts_, "vsg_sim3_ransac_iterations");
+    mnIterations_ = 0, solved_ = false;
+  }
+  // Sim3Solver::iterate (:215-291).  While the solver has not converged the reference returns a stack variable that it may
+  // have left unset (bestSim3, :235, :290); mBestT12 is returned there.
+  Matrix iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, bool &bConverge) {
+    bNoMore = false, bConverge = false;
+    vbInliers.assign((size_t)(mN1_ > 0 ? mN1_ : 0), false);
+    nInliers = 0;
+    if (N_ < mRansacMinInliers_) {  // :222-226
+      bNoMore = true;
+      return identity4();
+    }
+    solve();
+    // the reference's loop: this call walks hypotheses [mnIterations, mnIterations + nIterations) of at most mRansacMaxIts
+    int walked = mRansacMaxIts_ - mnIterations_ < nIterations ? mRansacMaxIts_ - mnIterations_ : nIterations;
+    if (walked < 0) walked = 0;
+    if (res_.converged && res_.iterations > mnIterations_ && res_.iterations <= mnIterations_ + walked) {
+      mnIterations_ = res_.iterations;
+      nInliers = res_.n_inliers;
+      for (int i = 0; i < N_; ++i)
+        if (inlier_[(size_t)i]) vbInliers[mvnIndices1_[(size_t)i]] = true;
+      bConverge = true;
+      return Matrix(res_.T12, res_.T12 + 16);
+    }
+    mnIterations_ += walked;
+    if (mnIterations_ >= mRansacMaxIts_) bNoMore = true;
+    return Matrix(res_.T12, res_.T12 + 16);
+  }
+  // Sim3Solver::iterate without bConverge (:146-213) returns the identity unless it converged
+  Matrix iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers) {
+    bool bConverge = false;
+    Matrix T = iterate(nIterations, bNoMore, vbInliers, nInliers, bConverge);
+    return bConverge ? T : identity4();
+  }
+  Matrix find(std::vector<bool> &vbInliers12, int &nInliers) {  // :293-297
+    bool bFlag;
+    return iterate(mRansacMaxIts_, bFlag, vbInliers12, nInliers);
+  }
+  // mBest* as far as the reference's loop has walked: the device call holds the members of the END of the walk, which is
+  // where the reference's caller reads them (after bConverge or bNoMore)
+  Matrix GetEstimatedTransformation() const { return Matrix(res_.T12, res_.T12 + 16); }
+  Matrix GetEstimatedRotation() const { return Matrix(res_.R12, res_.R12 + 9); }
+  std::vector<float> GetEstimatedTranslation() const { return std::vector<float>(res_.t12, res_.t12 + 3); }
+  float GetEstimatedScale() const { return res_.s12; }
+  int iterations() const { return mnIterations_; }          // mnIterations
+  int maxIterations() const { return mRansacMaxIts_; }      // mRansacMaxIts
+  const vsg_sim3_result &result() const { return res_; }
+  const std::vector<int32_t> &samples() const { return samples_; }
+
+ private:
+  static Matrix identity4() {
+    Matrix I(16, 0.0f);
+    I[0] = I[5] = I[10] = I[15] = 1.0f;
+    return I;
+  }
+  void fill_identity() {
+    memset(&res_, 0, sizeof res_);
+    res_.R12[0] = res_.R12[4] = res_.R12[8] = res_.s12 = res_.T12[0] = res_.T12[5] = res_.T12[10] = res_.T12[15] = 1.0f;
+  }
+  void solve() {
+    if (solved_) return;
+    samples_.assign(3 * (size_t)mRansacMaxIts_, 0);
+    check(vsg_sim3_draw_samples(N_, mRansacMaxIts_, randomInt_, randomCtx_, samples_.data()), "vsg_sim3_draw_samples");
+    inlier_.assign((size_t)(N_ > 0 ? N_ : 1), 0);
+    check(vsg_mappoints_sim3_ransac(mp1_, mp2_, N_, slots1_.data(), slots2_.data(), maxErr1_.data(), maxErr2_.data(), &pose1_,
+                                    &pose2_, mbFixScale_ ? 1 : 0, mRansacMinInliers_, mRansacMaxIts_, samples_.data(),
+                                    inlier_.data(), &res_, nullptr, nullptr),
+          "vsg_mappoints_sim3_ransac");
+    solved_ = true;
+  }
+  vsg_mappoints *mp1_, *mp2_;
+  std::vector<int32_t> slots1_, slots2_;
+  std::vector<float> maxErr1_, maxErr2_;
+  std::vector<size_t> mvnIndices1_;
+  int mN1_, N_ = 0;
+  FramePose pose1_, pose2_;
+  bool mbFixScale_;
+  int (*randomInt_)(int, int, void *);
+  void *randomCtx_;
+  int mRansacMinInliers_ = 6, mRansacMaxIts_ = 300, mnIterations_ = 0;
+  bool solved_ = false;
+  std::vector<int32_t> samples_;
+  std::vector<uint8_t> inlier_;
+  vsg_sim3_result res_;
+};
+
 }  // namespace vsg

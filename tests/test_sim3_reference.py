@@ -1,0 +1,239 @@
+"""csrc/vsg_sim3.h (its host build, tests/_sim3core) against the NumPy restatement of the reference's Sim3Solver
+(tests/sim3_reference.py), the selection rule against iterate's loop transcribed, each kept quirk against a restatement that
+"fixes" it, and the two host-only entry points of the library (no device is touched).
+
+MEASURED (test_header_against_the_restatement_per_hypothesis prints them with -s): over the four scenes -- 60 correspondences,
+30 % gross outliers, 1 cm noise, scale 1.3, rotation 20 degrees, octaves 0..7, 300 hypotheses each -- the restatement's float32
+path (LAPACK sgeev, atan2, Rodrigues) differs from the header (double Jacobi, quaternion -> matrix) by at most
+  max |dR| 5.90e-6, |ds| / s 4.81e-7, |dt| / max(1, |t|) 3.05e-5 (|t| reaches 50 for triples that hold an outlier)
+on the hypotheses compared; 2 / 6 / 0 / 3 of 300 hypotheses per scene are left out by the eigenvalue gap (cap: 15) and 1 / 3 /
+0 / 1 of ~17800 decisions by the threshold margin (cap: 1 %); no compared decision differs, and the call converges at the same
+hypothesis as iterate's loop over the header's counts.  The asserted bounds are
+these figures times 2: the two deviations differ from the reference's own float path by rounding, not by method."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sim3_hostcore as hc
+import sim3_reference as sr
+import sim3_scenes as ss
+from visual_sgraphs_amd import orb
+
+F32, F64, I32 = np.float32, np.float64, np.int32
+TOL_R, TOL_S, TOL_T = 2 * 5.90e-6, 2 * 4.81e-7, 2 * 3.05e-5
+MIN_GAP, MARGIN = 1e-2, 1e-3
+
+
+def _restated(s, fix_scale=False, **kw):
+    X1, X2, p1, p2 = sr.set_up(s["kf1"], s["kf2"], s["Xw1"], s["Xw2"])
+    out = []
+    for tri in s["samples"]:
+        h = sr.compute_sim3(X1[tri].T, X2[tri].T, fix_scale, **kw)
+        h["err"] = sr.errors(h, s["kf1"], s["kf2"], X1, X2, p1, p2)
+        out.append(h)
+    return out
+
+
+@pytest.mark.parametrize("seed", ss.SEEDS)
+def test_header_against_the_restatement_per_hypothesis(seed):
+    s = ss.issue_scene(seed)
+    n, nh = s["n"], len(s["samples"])
+    H = hc.hypotheses(s, hc.points(s), s["samples"])
+    ref = _restated(s)
+    compared = [k for k in range(nh) if ref[k]["gap"] >= MIN_GAP]
+    assert nh - len(compared) <= 0.05 * nh
+    dR = max(np.abs(H["R"][k].astype(F64) - ref[k]["R"]).max() for k in compared)
+    ds = max(abs(float(H["s"][k]) - float(ref[k]["s"])) / float(ref[k]["s"]) for k in compared)
+    dt = max(np.abs(H["t"][k].astype(F64) - ref[k]["t"]).max() / max(1.0, np.abs(ref[k]["t"]).max()) for k in compared)
+    left_out = differing = total = 0
+    for k in compared:
+        e1, e2 = ref[k]["err"]
+        with np.errstate(invalid="ignore"):
+            clear = (np.abs(e1 - s["max_err1"]) > MARGIN * s["max_err1"]) & (np.abs(e2 - s["max_err2"]) > MARGIN * s["max_err2"])
+        want = sr.inliers(e1, e2, s["max_err1"], s["max_err2"])
+        total += n
+        left_out += int((~clear).sum())
+        differing += int((want[clear] != H["inlier"][k][clear]).sum())
+    print("seed %d: left out %d of %d hypotheses, %d of %d decisions; max |dR| %.2e  |ds|/s %.2e  |dt|/max(1,|t|) %.2e (|t| <= %.1f); "
+          "%d decisions differ" % (seed, nh - len(compared), nh, left_out, total, dR, ds, dt,
+                                   max(np.abs(ref[k]["t"]).max() for k in compared), differing))
+    assert left_out <= 0.01 * total
+    assert differing == 0
+    assert dR <= TOL_R and ds <= TOL_S and dt <= TOL_T
+    # the call as a whole: the header's counts through the header's selection = iterate's loop over the same counts, and
+    # the true similarity is found
+    r = hc.ransac(s)
+    counts = H["inlier"].sum(1)
+    assert (r["hyp_inliers"] == counts).all()
+    best, conv, no_more, its, nbest = sr.iterate_transcribed(counts, 15, nh)
+    res = r["res"]
+    assert (res["best_hypothesis"], res["converged"], res["no_more"], res["iterations"], res["n_inliers"]) == \
+        (best, int(conv), int(no_more), its, nbest)
+    assert conv and (r["inlier"].astype(bool) == H["inlier"][best]).all() and not r["inlier"].astype(bool)[s["outlier"]].any()
+    assert abs(float(res["s12"]) - 1.3) < 0.02 and np.abs(res["R12"] - s["truth"]["R12"]).max() < 0.02
+    early = hc.ransac(s, early_exit=True)
+    assert early["res"]["raw"] == res["raw"] and (early["inlier"] == r["inlier"]).all()
+
+
+def test_eigenvector_and_rotation_are_what_double_precision_gives():
+    s = ss.issue_scene(ss.SEEDS[0])
+    N = hc.hypotheses(s, hc.points(s), s["samples"])["N"]
+    q = hc.eigenvectors(N)
+    worst_q = worst_R = 0.0
+    for Nk, qk in zip(N, q):
+        w, v = np.linalg.eigh(Nk.astype(F64))
+        if (w[-1] - w[-2]) < MIN_GAP * abs(w[-1]):
+            continue
+        u = qk / np.linalg.norm(qk)
+        u = -u if u @ v[:, -1] < 0 else u
+        worst_q = max(worst_q, np.abs(u - v[:, -1]).max())
+        a, b, c, d = v[:, -1]
+        R = np.array([[1 - 2 * (c * c + d * d), 2 * (b * c - a * d), 2 * (b * d + a * c)],
+                      [2 * (b * c + a * d), 1 - 2 * (b * b + d * d), 2 * (c * d - a * b)],
+                      [2 * (b * d - a * c), 2 * (c * d + a * b), 1 - 2 * (b * b + c * c)]])
+        worst_R = max(worst_R, np.abs(hc.rotations(qk)[0] - R).max())
+    assert worst_q < 1e-12 and worst_R <= 2.0 ** -24  # one rounding to float of entries below 1
+    # the sign of the quaternion changes no bit of the matrix
+    assert (hc.rotations(q).view(np.uint32) == hc.rotations(-q).view(np.uint32)).all()
+
+
+COUNT_CASES = {
+    "hit at 0": ([16] + [3] * 40, 15), "hit at 19": ([2] * 19 + [16] + [20] * 5, 15), "hit at 20": ([2] * 20 + [16] + [20] * 5, 15),
+    "hit at the last": ([4] * 59 + [16], 15), "never": ([3, 9, 4, 15, 2] * 9, 15), "tie, the last wins": ([3, 9, 4, 9, 2, 9, 1] * 4, 15),
+    "all zero": ([0] * 45, 15), "equal to the minimum is not above it": ([15] * 3 + [2] * 30 + [15] + [1] * 8, 15),
+    "one hypothesis": ([7], 15), "one hypothesis above": ([16], 15), "min 0": ([0, 0, 1, 5], 0),
+}
+
+
+@pytest.mark.parametrize("name", COUNT_CASES)
+def test_selection_is_iterates_loop(name):
+    counts, min_inliers = COUNT_CASES[name]
+    best, conv, no_more, its, _ = sr.iterate_transcribed(counts, min_inliers, len(counts))
+    got = hc.select(counts, min_inliers)
+    assert (got["best"], got["converged"], got["iterations"]) == (best, conv, its) and conv != no_more
+    c = np.array(counts)
+    if conv:
+        assert best == int(np.flatnonzero(c > min_inliers)[0])
+    else:
+        assert best == int(np.flatnonzero(c == c.max())[-1]) and its == len(counts)
+
+
+def test_selection_on_random_counts():
+    rng = np.random.default_rng(5)
+    for _ in range(300):
+        nh, mi = int(rng.integers(1, 70)), int(rng.integers(0, 12))
+        counts = rng.integers(0, mi + 3, nh)
+        best, conv, _, its, _ = sr.iterate_transcribed(counts, mi, nh)
+        got = hc.select(counts, mi)
+        assert (got["best"], got["converged"], got["iterations"]) == (best, conv, its)
+
+
+def _one_hypothesis(s, tri=(0, 1, 2), **kw):
+    return hc.hypotheses(s, hc.points(s), [tri], **kw)
+
+
+def test_quirk_threshold_is_truncated():
+    s = ss.issue_scene(ss.SEEDS[1])
+    # 9.210 * sigma2 of octave 0 is 9.21: an err of 9.1 lies between floor(t) = 9 and t
+    assert sr.max_err(ss.SIGMA2[:1])[0] == 9.0 and abs(sr.max_err(ss.SIGMA2[:1], truncated=False)[0] - 9.21) < 1e-6
+    k = int(np.flatnonzero(~s["outlier"])[0])
+    tri = [int(i) for i in np.flatnonzero(~s["outlier"])[1:4]]
+    base = dict(s, max_err1=np.full(s["n"], 1e9, F32), max_err2=np.full(s["n"], 1e9, F32))
+    e1 = _one_hypothesis(base, tri)["err"][0, k, 0]
+    # move the point's image in kf1 so that err1 of this hypothesis is 9.1 +- 0.01: shift X along camera x
+    X1, X2, p1, p2 = sr.set_up(s["kf1"], s["kf2"], s["Xw1"], s["Xw2"])
+    z = float(X1[k, 2])
+    for shift in np.linspace(2.0, 4.0, 4001):
+        Xc = X1[k].astype(F64) + np.array([shift * z / s["kf1"]["fx"], 0, 0])
+        moved = dict(base, Xw1=base["Xw1"].copy())
+        moved["Xw1"][k] = ss.to_world(s["kf1"], Xc[None])[0]
+        e = float(_one_hypothesis(moved, tri)["err"][0, k, 0])
+        if 9.05 < e < 9.15:
+            break
+    else:
+        pytest.fail("no shift puts err1 between 9 and 9.21 (started at %g)" % e1)
+    trunc = dict(moved, max_err1=sr.max_err(ss.SIGMA2[np.zeros(s["n"], int)]))
+    fixed = dict(moved, max_err1=sr.max_err(ss.SIGMA2[np.zeros(s["n"], int)], truncated=False))
+    assert not _one_hypothesis(trunc, tri)["inlier"][0, k]  # the header given the reference's threshold: outlier
+    assert _one_hypothesis(fixed, tri)["inlier"][0, k]      # a "fixed" threshold would take it
+    assert 9.0 < e < 9.21
+
+
+def test_quirk_zero_imaginary_part_is_nan_and_has_no_inlier():
+    s = ss.identical_triple(ss.issue_scene(ss.SEEDS[2]))
+    H = _one_hypothesis(s)
+    X1, X2, p1, p2 = sr.set_up(s["kf1"], s["kf2"], s["Xw1"], s["Xw2"])
+    assert (X1[:3] == X2[:3]).all()
+    assert np.isnan(H["R"]).all() and np.isnan(H["T12"][0, :3]).all() and not H["inlier"].any()
+    ref = sr.compute_sim3(X1[:3].T, X2[:3].T)
+    assert np.isnan(ref["R"]).all()
+    fixed = sr.compute_sim3(X1[:3].T, X2[:3].T, nan_on_zero_axis=False)
+    e1, e2 = sr.errors(fixed, s["kf1"], s["kf2"], X1, X2, p1, p2)
+    assert (fixed["R"] == np.eye(3)).all() and sr.inliers(e1, e2, s["max_err1"], s["max_err2"])[:3].all()
+    # the whole call: hypothesis 0 is the NaN one and nothing beats its zero count -> it is kept, canonical NaNs, no flag
+    far = dict(s, samples=np.array([[0, 1, 2]] * 3, I32))
+    r = hc.ransac(far)
+    assert r["res"]["best_hypothesis"] == 2 and r["res"]["n_inliers"] == 0 and not r["inlier"].any()
+    assert (np.frombuffer(r["res"]["raw"][:36], np.uint32) == 0x7FC00000).all() and (r["hyp_inliers"] == 0).all()
+
+
+def test_quirk_fix_scale():
+    s = ss.issue_scene(ss.SEEDS[3])
+    tri = [int(i) for i in np.flatnonzero(~s["outlier"])[:3]]
+    free, fixed = _one_hypothesis(s, tri), _one_hypothesis(s, tri, fix_scale=True)
+    assert fixed["s"][0] == 1.0 and abs(float(free["s"][0]) - 1.3) < 0.05
+    assert (fixed["R"] == free["R"]).all()  # the rotation does not depend on the scale
+    assert (fixed["T12"][0, :3, :3] == fixed["R"][0]).all() and (fixed["T21"][0, :3, :3] == fixed["R"][0].T).all()
+    X1, X2, _, _ = sr.set_up(s["kf1"], s["kf2"], s["Xw1"], s["Xw2"])
+    ref = sr.compute_sim3(X1[tri].T, X2[tri].T, fix_scale=True)
+    assert ref["s"] == 1.0 and np.abs(ref["t"] - fixed["t"][0]).max() < 1e-4
+
+
+def test_quirk_x3dc2_goes_through_kf2s_pose():
+    s = ss.issue_scene(ss.SEEDS[0])
+    other = ss.camera(np.random.default_rng(99))  # pKFm: a third keyframe some points were matched through
+    pts = hc.points(s)
+    X1, X2, p1, p2 = sr.set_up(s["kf1"], s["kf2"], s["Xw1"], s["Xw2"])
+    assert np.abs(pts[:, 3:6] - X2).max() < 1e-5
+    _, X2m, _, _ = sr.set_up(s["kf1"], s["kf2"], s["Xw1"], s["Xw2"], pose2=other)  # the "fix": through pKFm's pose
+    assert np.abs(pts[:, 3:6] - X2m).max() > 0.1 and (hc.points(s, pose2=other)[:, 3:6] != pts[:, 3:6]).any()
+
+
+@pytest.mark.parametrize("n", (15, 16, 20, 100))
+def test_ransac_iterations(n):
+    L = orb.load_library()
+    assert L.vsg_sim3_ransac_iterations(0.99, 15, 300, n) == sr.ransac_iterations(0.99, 15, 300, n) == orb.sim3_ransac_iterations(0.99, 15, 300, n)
+    if n == 15:
+        assert sr.ransac_iterations(0.99, 15, 300, n) == 1  # min_inliers == N
+    assert L.vsg_sim3_ransac_iterations(0.99, 15, 5, 100) == 5 and L.vsg_sim3_ransac_iterations(0.99, 40, 300, 30) == 1
+    assert L.vsg_sim3_ransac_iterations(0.99, 15, 300, -1) == -6 and L.vsg_sim3_ransac_iterations(0.99, -1, 300, 20) == -6
+
+
+def test_ransac_iterations_values():
+    # epsilon = 15 / N as a float: N = 16 -> 3, 20 -> 9, 100 -> 300 (1363 before the cap)
+    assert [sr.ransac_iterations(0.99, 15, 300, n) for n in (15, 16, 20, 100)] == [1, 3, 9, 300]
+    assert sr.ransac_iterations(0.99, 15, 10 ** 6, 100) == 1363
+
+
+def test_draw_samples_is_the_swap_and_pop():
+    script = [int(v) for v in np.random.default_rng(8).integers(0, 10 ** 6, 3 * 40)]
+
+    def scripted():
+        it = iter(script)
+        return lambda lo, hi: lo + next(it) % (hi - lo + 1)
+    for n in (3, 4, 60):
+        want = sr.draw_samples(n, 40, scripted())
+        got = orb.sim3_draw_samples(n, 40, scripted())
+        assert got.dtype == I32 and (got == want).all()
+        assert all(len(set(t)) == 3 and min(t) >= 0 and max(t) < n for t in got.tolist())
+        if n == 3:
+            assert all(sorted(t) == [0, 1, 2] for t in got.tolist())
+    # the built-in generator: distinct, in range
+    got = orb.sim3_draw_samples(7, 200)
+    assert all(len(set(t)) == 3 and min(t) >= 0 and max(t) < 7 for t in got.tolist())
+    L = orb.load_library()
+    out = np.full(6, -9, I32)
+    assert L.vsg_sim3_draw_samples(2, 2, orb._RANDOM_INT(), None, out.ctypes.data_as(C.POINTER(C.c_int32))) == -6 and (out == -9).all()
+    with pytest.raises(orb.VsgError):
+        orb.sim3_draw_samples(5, 3, lambda lo, hi: hi + 1)  # a generator that leaves its range is refused, not indexed

@@ -9,6 +9,7 @@
 #include "vsg_observations.h"
 #include "vsg_pose_opt.h"
 #include "vsg_project.h"
+#include "vsg_sim3.h"
 #include "vsg_triangulate.h"
 
 extern "C" {
@@ -168,6 +169,19 @@ int np_host_side(const vsg_triangulation_params *P, int n1, const float *const *
     k++;
   }
   return k;
+}
+
+// The caller-side Sim3Solver (Sim3Solver.cc) on positions read back from the stores: the header's set-up, then hypothesis after
+// hypothesis WITH the reference's early exit at the first one above min_inliers (sim3::ransac_host), on one thread.
+int s3_host_side(int n, const float *Xw1, const float *Xw2, const float *max_err1, const float *max_err2, const vsg_frame_pose *kf1,
+                 const vsg_frame_pose *kf2, int fix_scale, int min_inliers, int n_hyp, const int32_t *samples, uint8_t *inlier,
+                 vsg_sim3_result *res) {
+  static thread_local std::vector<vsg::sim3::Point> pts;
+  static thread_local std::vector<int32_t> counts;
+  pts.resize((size_t)n), counts.resize((size_t)n_hyp);
+  vsg::sim3::ransac_host(n, Xw1, Xw2, max_err1, max_err2, *kf1, *kf2, fix_scale != 0, min_inliers, n_hyp, samples, true, pts.data(),
+                         counts.data(), inlier, res, nullptr, nullptr);
+  return res->iterations;
 }
 
 }  // extern "C"

@@ -36,7 +36,14 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
                  thread (NOT Eigen: the header's own arithmetic) + vsg_mappoints_update + vsg_mappoints_refresh_from_observations
             B  = vsg_frame_create_new_map_points;  A2 / B2 = both again.  Every call asserts equal outputs and store
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints> [calls] [out.json]  -> runs the child, writes the record (default
+  sim3      Sim3Solver on resident map points (LoopClosing.cc:678-690): 30 / 100 / 300 correspondences between two stores of 4096
+            slots, 300 hypotheses, min_inliers 15; "loop" = a true loop (30 % outliers: the solver converges within the first few
+            hypotheses), "false" = a false candidate (no consistent similarity: all 300 are walked)
+            A  = vsg_mappoints_read of both point sets + the host build of csrc/vsg_sim3.h on one thread WITH the reference's
+                 early exit (NOT Eigen: the header's own arithmetic)
+            B  = vsg_mappoints_sim3_ransac (every hypothesis, no early exit);  A2 / B2 = both again.  Equal results asserted
+
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -65,7 +72,7 @@ def host_side(orb):
     so = out / "libresident_points_cpu.so"
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
-           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h"]
+           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
                                str(src[0])])
@@ -84,6 +91,8 @@ def host_side(orb):
     H.rf_take_rows.argtypes = [C.c_int, _i32p, _u8p, _i32p, _u8p]
     H.np_host_side.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _i32p, C.c_int, C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int,
                                _u8p, _u8p, _f32p, _i32p, _i32p, _f32p, _i32p]
+    H.s3_host_side.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _u8p,
+                               C.c_void_p]
     H.po_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, C.c_int, _u8p, _f32p,
                                C.POINTER(C.c_double), _i32p]
     return H
@@ -562,7 +571,69 @@ class NewPoints(Case):
                              "vsg_mappoints_update + vsg_mappoints_refresh_from_observations; B = vsg_frame_create_new_map_points"}
 
 
-CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints}
+class Sim3(Case):
+    """Sim3Solver on resident map points: a scene of tests/sim3_scenes.py (two keyframes in two maps, the point sets related by
+    a similarity of scale 1.3, 1 cm noise), its points in random slots of two stores.  A size is "<correspondences>:<loop|false>"."""
+    SIZES = tuple("%d:%s" % (n, c) for n in (30, 100, 300) for c in ("loop", "false"))
+    TH, DEST = 0.0, "sim3_ransac_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+    CAP, NHYP, MIN_INLIERS = 4096, 300, 15
+
+    def __init__(self, orb, fr, size):
+        import sim3_scenes as ss
+        n, kind = int(size.split(":")[0]), size.split(":")[1]
+        self.orb, self.n, self.kind = orb, n, kind
+        s = self.s = ss.make(7000 + n, n=n, outliers=0.3 if kind == "loop" else 1.0, n_hyp=self.NHYP)
+        rng = np.random.default_rng(n)
+        c = np.ascontiguousarray
+        self.mp = [orb.MapPoints(self.CAP), orb.MapPoints(self.CAP)]
+        self.slots = [c(rng.permutation(self.CAP)[:n], np.int32) for _ in range(2)]
+        self.mp[0].update(self.slots[0], world_pos=s["Xw1"])
+        self.mp[1].update(self.slots[1], world_pos=s["Xw2"])
+        self.err = [c(s["max_err1"], np.float32), c(s["max_err2"], np.float32)]
+        self.kf = [orb.FramePose.make(k["Rcw"], k["tcw"], np.zeros(3), k["fx"], k["fy"], k["cx"], k["cy"], 0.0, 0.0, 0)
+                   for k in (s["kf1"], s["kf2"])]
+        self.samples = c(s["samples"], np.int32)
+        self.Xw = [np.zeros(3 * n, np.float32), np.zeros(3 * n, np.float32)]
+        self.inlier, self.res = np.zeros(n, np.uint8), orb.Sim3Result()
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.inlier[:] = 9
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        n = self.n
+        if name.startswith("B"):
+            return L.vsg_mappoints_sim3_ransac(self.mp[0].handle, self.mp[1].handle, n, p(self.slots[0], _i32p), p(self.slots[1], _i32p),
+                                               p(self.err[0], _f32p), p(self.err[1], _f32p), C.byref(self.kf[0]), C.byref(self.kf[1]),
+                                               0, self.MIN_INLIERS, self.NHYP, p(self.samples, _i32p), p(self.inlier, _u8p),
+                                               C.byref(self.res), None, None)
+        for k in range(2):
+            rc = L.vsg_mappoints_read(self.mp[k].handle, n, p(self.slots[k], _i32p), p(self.Xw[k], _f32p), None, None, None, None, None)
+            if rc != 0:
+                return rc
+        H.s3_host_side(n, p(self.Xw[0], _f32p), p(self.Xw[1], _f32p), p(self.err[0], _f32p), p(self.err[1], _f32p),
+                       C.byref(self.kf[0]), C.byref(self.kf[1]), 0, self.MIN_INLIERS, self.NHYP, p(self.samples, _i32p),
+                       p(self.inlier, _u8p), C.byref(self.res))
+        return 0
+
+    def result(self, name, r):
+        return (r, self.inlier.copy(), np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.Sim3Result.from_buffer_copy(last["B"][2].tobytes())
+        return {"correspondences": self.n, "case": self.kind, "hypotheses": self.NHYP, "min_inliers": self.MIN_INLIERS,
+                "converged": bool(r.converged), "hypotheses_walked_by_the_reference_loop": int(r.iterations),
+                "n_inliers": int(r.n_inliers), "store_slots": self.CAP,
+                "host_side": "A = vsg_mappoints_read x 2 + the host build of csrc/vsg_sim3.h on one thread with the reference's early "
+                             "exit (tools/resident_points_cpu.cpp; NOT Eigen: the header's double Jacobi, no EigenSolver, no "
+                             "Sophus); B = vsg_mappoints_sim3_ransac, which computes all hypotheses"}
+
+
+CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3}
 
 
 def child(case, calls):

@@ -87,6 +87,8 @@ EXPORTS = [
     "vsg_frame_pose_optimization", "vsg_frame_pose_optimization_resume",
     # LocalMapping::CreateNewMapPoints on resident keyframes: triangulate, gate, write the new points into the store
     "vsg_frame_set_stereo_points", "vsg_frame_triangulate_matches", "vsg_frame_create_new_map_points",
+    # Sim3Solver on resident map points: every RANSAC hypothesis in one call, and the host-side set-up of the solver
+    "vsg_mappoints_sim3_ransac", "vsg_sim3_ransac_iterations", "vsg_sim3_draw_samples",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -153,6 +155,17 @@ class PoseResult(C.Structure):
     """include/vsg_orb.h vsg_pose_result."""
     _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("n_initial", C.c_int32), ("n_bad", C.c_int32),
                 ("rounds_run", C.c_int32), ("held", C.c_int32)]
+
+
+class Sim3Result(C.Structure):
+    """include/vsg_orb.h vsg_sim3_result: mBestRotation (row-major), mBestTranslation, mBestScale, mBestT12, bConverge,
+    bNoMore, mnBestInliers, the chosen hypothesis and mnIterations."""
+    _fields_ = [("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float), ("T12", C.c_float * 16),
+                ("converged", C.c_int32), ("no_more", C.c_int32), ("n_inliers", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("iterations", C.c_int32)]
+
+
+_RANDOM_INT = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)
 
 
 class VsgError(RuntimeError):
@@ -398,6 +411,10 @@ def load_library():
     L.vsg_frame_triangulate_matches.argtypes = [vp, vp, _i32p] + tri_tail + tri_outs
     L.vsg_frame_create_new_map_points.argtypes = [vp, _u8p, _i32p, _i32p, _i32p, ci, vp, _u8p, _i32p, _i32p, _i32p, ci, _f32p,
                                                   _f32p, ci, ci, ci] + tri_tail + [_i32p] + tri_outs
+    L.vsg_mappoints_sim3_ransac.argtypes = [vp, vp, ci, _i32p, _i32p, _f32p, _f32p, C.POINTER(FramePose), C.POINTER(FramePose),
+                                            ci, ci, ci, _i32p, _u8p, C.POINTER(Sim3Result), _i32p, _f32p]
+    L.vsg_sim3_ransac_iterations.argtypes = [C.c_double, ci, ci, ci]
+    L.vsg_sim3_draw_samples.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1163,6 +1180,56 @@ class MapPoints:
             _p(out["best"], _i32p), _p(out["normal"], _f32p), _p(out["min_dist"], _f32p), _p(out["max_dist"], _f32p)),
             "vsg_mappoints_refresh_from_observations")
         return {k: v[:n] for k, v in out.items()}
+
+
+    def Sim3Ransac(self, slots1, slots2, max_err1, max_err2, kf1, kf2, samples, min_inliers, fix_scale=False, other=None,
+                   per_hypothesis=False):
+        """Sim3Solver on resident map points (vsg_mappoints_sim3_ransac): correspondence i = slot slots1[i] of this store
+        against slot slots2[i] of `other` (None: this store); max_err1 / 2 = sim3_max_err(...); kf1 / kf2 = FramePose;
+        samples = n_hyp x 3 correspondence indices (sim3_draw_samples).  Returns dict(inlier, R12, t12, s12, T12, converged,
+        no_more, n_inliers, best_hypothesis, iterations) and, with per_hypothesis, hyp_inliers and hyp_T12."""
+        s1, s2, e1, e2 = _i32(slots1), _i32(slots2), _f32(max_err1), _f32(max_err2)
+        n = int(np.asarray(slots1).size)
+        if any(int(np.asarray(a).size) != n for a in (slots2, max_err1, max_err2)):
+            raise ValueError("the correspondence arrays differ in length")
+        sm = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 3)
+        nh = len(sm)
+        inlier, res = np.zeros(max(n, 1), np.uint8), Sim3Result()
+        hc = np.zeros(max(nh, 1), np.int32) if per_hypothesis else None
+        hT = np.zeros((max(nh, 1), 4, 4), np.float32) if per_hypothesis else None
+        _check(self._L.vsg_mappoints_sim3_ransac(
+            self._h, (other or self).handle, n, _p(s1, _i32p), _p(s2, _i32p), _p(e1, _f32p), _p(e2, _f32p), C.byref(kf1),
+            C.byref(kf2), int(bool(fix_scale)), int(min_inliers), nh, _p(_i32(sm), _i32p), _p(inlier, _u8p), C.byref(res),
+            _p(hc, _i32p) if per_hypothesis else None, _p(hT, _f32p) if per_hypothesis else None), "vsg_mappoints_sim3_ransac")
+        out = dict(inlier=inlier[:n].astype(bool), R12=np.array(res.R12, np.float32).reshape(3, 3), t12=np.array(res.t12, np.float32),
+                   s12=np.float32(res.s12), T12=np.array(res.T12, np.float32).reshape(4, 4), converged=bool(res.converged),
+                   no_more=bool(res.no_more), n_inliers=int(res.n_inliers), best_hypothesis=int(res.best_hypothesis),
+                   iterations=int(res.iterations), result=res)
+        if per_hypothesis:
+            out.update(hyp_inliers=hc[:nh], hyp_T12=hT[:nh])
+        return out
+
+
+def sim3_max_err(level_sigma2, octave):
+    """mvnMaxError of Sim3Solver (Sim3Solver.cc:96-97) as the comparison sees it: 9.210 * sigmaSquare, a double, truncated by
+    the std::vector<size_t> it is stored in, as a float."""
+    t = 9.210 * np.asarray(level_sigma2, np.float32)[np.asarray(octave, np.int64)].astype(np.float64)
+    return np.floor(t).astype(np.float32)
+
+
+def sim3_ransac_iterations(probability, min_inliers, max_iterations, n):
+    """Sim3Solver::SetRansacParameters: mRansacMaxIts for n correspondences (host only)."""
+    return _check(load_library().vsg_sim3_ransac_iterations(float(probability), int(min_inliers), int(max_iterations), int(n)),
+                  "vsg_sim3_ransac_iterations")
+
+
+def sim3_draw_samples(n, n_hyp, random_int=None):
+    """The minimal sets of Sim3Solver::iterate (:242-256) for n_hyp hypotheses over n correspondences: n_hyp x 3 int32.
+    random_int(lo, hi) stands for DUtils::Random::RandomInt; None: its formula over the C library's rand() (host only)."""
+    out = np.zeros((max(int(n_hyp), 1), 3), np.int32)
+    cb = _RANDOM_INT(lambda lo, hi, _ctx: int(random_int(lo, hi))) if random_int is not None else _RANDOM_INT()
+    _check(load_library().vsg_sim3_draw_samples(int(n), int(n_hyp), cb, None, _p(out, _i32p)), "vsg_sim3_draw_samples")
+    return out[:int(n_hyp)]
 
 
 def ComputeDistinctiveDescriptors(desc, off, device=0):
