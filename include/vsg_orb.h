@@ -1035,6 +1035,49 @@ int vsg_sim3_ransac_iterations(double probability, int min_inliers, int max_iter
  * DUtils::Random::RandomInt's formula over rand() (Random.cpp:47-50).  Host only.  n < 3, n_hyp < 0, NULL samples, or a
  * random_int result outside its range: VSG_ERR_INVALID. */
 int vsg_sim3_draw_samples(int n, int n_hyp, int (*random_int)(int lo, int hi, void *ctx), void *ctx, int32_t *samples);
+/* int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) (Optimizer.h,
+ * Optimizer.cc:3261-3529; called at LoopClosing.cc:538 and :747) on two resident keyframes and resident map points: the
+ * link between vsg_mappoints_sim3_ransac above and vsg_frame_search_sim3_points, which projects through the g2oS12 this
+ * routine refines.  One persistent workgroup gathers the pairs (:3313-3450), runs optimize(5), the first check on the
+ * errors AS THE LAST computeActiveErrors LEFT THEM (:3452-3486), the `< 10` gate, optimize(5 or 10) without the kernel and
+ * the second check on fresh errors (:3488-3522), in double, in one enqueue and one wait; only the slots and indices of the
+ * pairs, two poses and g2oS12 cross to the device.  The Jacobian is g2o's NUMERIC one (base_binary_edge.hpp:131-205,
+ * central differences with delta = 1e-9 through VertexSim3Expmap::oplusImpl, OptimizableTypes.h:172-181): neither edge
+ * defines linearizeOplus.  The arithmetic is csrc/vsg_sim3_opt.h, which a host build reproduces bit for bit (DESIGN.md
+ * section 8).
+ *   - Entry i, one per feature of kf1 (vpMatches1.size() = N): slots1[i] = the slot of vpMapPoints1[i] in mp1, slots2[i]
+ *     = the slot of vpMatches1[i] in mp2 (mp2 may be mp1), either < 0 for a missing OR BAD point: every such branch of
+ *     :3315-3373 adds no edge and leaves the match alone.  idx2[i] = get<0>(pMP2->GetIndexInKeyFrame(pKF2)) or < 0;
+ *     level2[i] = pMP2->mnTrackScaleLevel, read only when idx2[i] < 0.
+ *   - pose1 / pose2 = the keyframes' GetRotation(), GetTranslation() (Rcw, tcw) and Pinhole parameters (fx, fy, cx, cy);
+ *     nothing else of them is read.  inv_level_sigma2_1 / _2 = mvInvLevelSigma2 of pKF1 / pKF2, nlevels entries each.
+ *   - S12 = g2oS12 taken as it is (not normalised); th2, fix_scale = bFixScale, all_points = bAllPoints.
+ *   - state[i], written for ALL i: 0 = no edge, match untouched; 1 = inlier; 2 = vpMatches1[i] nulled at the first check;
+ *     3 = nulled at the second; 4 = skipped for P3D2c.z < 0 (:3381); 5 = skipped for i2 < 0 && !bAllPoints (:3375).  A
+ *     skipped entry keeps its match.  chi2[2 i], chi2[2 i + 1] (chi2 may be NULL) = the two doubles last compared for pair
+ *     i (e12, e21), NaN canonical; entries without an edge keep their bytes.
+ *   - Returns nIn (:3528), or 0 when nCorrespondences - nBad < 10 (:3494): the bad matches are nulled by then and g2oS12
+ *     is NOT updated (res->updated = 0, res->S12 = the input, byte for byte).  res->more_iterations = nMoreIterations.
+ *     mAcumHessian is only set to zero by the reference (:3502): the caller does that.
+ *   - No entry with both slots: nothing is enqueued, res holds the input S12, returns 0.
+ * Checked before anything is enqueued (an error writes nothing and leaves no kernel behind), VSG_ERR_INVALID: a NULL kf1,
+ * kf2, mp1, mp2, slots1, slots2, idx2, level2, pose1, pose2, either sigma table, S12, state or res; stores or frames on
+ * different devices; a slot >= its store's capacity; on an entry with both slots: idx2[i] >= kf2's feature count, and --
+ * unless it is skipped for i2 < 0 && !all_points -- an octave of kf1's feature i, of kf2's feature idx2[i], or a level2[i]
+ * (idx2[i] < 0) outside [0, nlevels); nlevels outside [1, 16]; th2 not finite or <= 0.  Nleft != -1 on either keyframe
+ * (KannalaBrandt8 pairs): VSG_ERR_UNSUPPORTED, as in vsg_frame_pose_optimization.  The scratch lives in the calling
+ * thread's arena, so two threads may optimise on the same stores and keyframes at the same time. */
+typedef struct vsg_sim3d { double q[4], t[3], s; } vsg_sim3d;             /* g2o::Sim3: r as x y z w, t, s */
+typedef struct vsg_sim3_opt_result {
+  vsg_sim3d S12;                 /* g2oS12 on return: the input when the call returned before :3526 */
+  int32_t n_correspondences, n_bad, n_in, n_in_kf2, n_out_kf2, more_iterations, updated;
+} vsg_sim3_opt_result;
+int vsg_frame_optimize_sim3(vsg_frame *kf1, vsg_frame *kf2, vsg_mappoints *mp1, vsg_mappoints *mp2,
+                            const int32_t *slots1, const int32_t *slots2, const int32_t *idx2, const int32_t *level2,
+                            const vsg_frame_pose *pose1, const vsg_frame_pose *pose2,
+                            const float *inv_level_sigma2_1, const float *inv_level_sigma2_2, int nlevels,
+                            const vsg_sim3d *S12, float th2, int fix_scale, int all_points,
+                            uint8_t *state, double *chi2, vsg_sim3_opt_result *res);
 /* Frame::ComputeBoW (Frame.cc:882-889) on the resident descriptors; outputs as vsg_bow_transform. */
 int vsg_frame_bow_transform(vsg_vocab *voc, vsg_frame *f, int levelsup, int32_t *bow_ids, double *bow_vals,
                             int bow_cap, int *n_bow, int32_t *fv_node, int32_t *fv_off, int32_t *fv_idx, int fv_cap,

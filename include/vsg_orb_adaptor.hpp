@@ -1412,4 +1412,55 @@ class ResidentSim3Solver {
   vsg_sim3_result res_;
 };
 
+// Optimizer::OptimizeSim3 (Optimizer.h, Optimizer.cc:3261-3529) on two resident keyframes and resident map points, with
+// the reference's shape, so that the call sites of LoopClosing.cc:538 and :747 stay as they are:
+//     vsg::ResidentSim3Optimizer opt(kf1, kf2, mp1, mp2, pose1, pose2, mvInvLevelSigma2_1, mvInvLevelSigma2_2);
+//     int numOptMatches = opt.OptimizeSim3(slots1, slots2, idx2, level2, nulled, gScm, 10, mbFixScale, mHessian7x7, true);
+// The maintainer fills, per feature i of pKF1: slots1[i] = the slot of vpMapPoints1[i] (-1: none or isBad()), slots2[i] =
+// the slot of vpMatches1[i] (-1: NULL or isBad()), idx2[i] = get<0>(pMP2->GetIndexInKeyFrame(pKF2)), level2[i] =
+// pMP2->mnTrackScaleLevel.  On return nulled[i] != 0 where the reference sets vpMatches1[i] = NULL (:3469, :3516) -- the
+// maintainer applies it to the pointers --, g2oS12 is updated unless the routine returned before :3526, and
+// mAcumHessian (49 doubles) is zero-filled as :3502 does, and only when that line is reached.
+class ResidentSim3Optimizer {
+ public:
+  ResidentSim3Optimizer(const ResidentFrame &kf1, const ResidentFrame &kf2, const ResidentMapPoints &mp1,
+                        const ResidentMapPoints &mp2, const FramePose &pose1, const FramePose &pose2,
+                        const std::vector<float> &mvInvLevelSigma2_1, const std::vector<float> &mvInvLevelSigma2_2)
+      : kf1_(kf1.handle()), kf2_(kf2.handle()), mp1_(mp1.handle()), mp2_(mp2.handle()), pose1_(pose1), pose2_(pose2),
+        sig1_(mvInvLevelSigma2_1), sig2_(mvInvLevelSigma2_2) {
+    if (sig1_.size() != sig2_.size()) check(VSG_ERR_INVALID, "vsg::ResidentSim3Optimizer");
+  }
+  int OptimizeSim3(const std::vector<int32_t> &slots1, const std::vector<int32_t> &slots2, const std::vector<int32_t> &idx2,
+                   const std::vector<int32_t> &level2, std::vector<uint8_t> &nulled, vsg_sim3d &g2oS12, float th2,
+                   bool bFixScale, double *mAcumHessian, bool bAllPoints = false) {
+    const size_t n = slots1.size();
+    if (slots2.size() != n || idx2.size() != n || level2.size() != n) check(VSG_ERR_INVALID, "vsg::ResidentSim3Optimizer");
+    state_.assign(n ? n : 1, 0), chi2_.assign(2 * (n ? n : 1), 0.0);
+    const int nIn = vsg_frame_optimize_sim3(kf1_, kf2_, mp1_, mp2_, slots1.data(), slots2.data(), idx2.data(), level2.data(),
+                                            &pose1_, &pose2_, sig1_.data(), sig2_.data(), (int)sig1_.size(), &g2oS12, th2,
+                                            bFixScale ? 1 : 0, bAllPoints ? 1 : 0, state_.data(), chi2_.data(), &res_);
+    check(nIn, "vsg_frame_optimize_sim3");
+    nulled.assign(n, 0);
+    for (size_t i = 0; i < n; ++i) nulled[i] = state_[i] == 2 || state_[i] == 3 ? 1 : 0;
+    if (res_.updated) {
+      g2oS12 = res_.S12;
+      if (mAcumHessian)
+        for (int k = 0; k < 49; ++k) mAcumHessian[k] = 0.0;  // Eigen::MatrixXd::Zero(7, 7): nothing accumulates into it
+    }
+    return nIn;
+  }
+  const vsg_sim3_opt_result &result() const { return res_; }
+  const std::vector<uint8_t> &state() const { return state_; }  // per feature, as vsg_frame_optimize_sim3 documents it
+  const std::vector<double> &chi2() const { return chi2_; }     // two per feature
+
+ private:
+  vsg_frame *kf1_, *kf2_;
+  vsg_mappoints *mp1_, *mp2_;
+  FramePose pose1_, pose2_;
+  std::vector<float> sig1_, sig2_;
+  std::vector<uint8_t> state_;
+  std::vector<double> chi2_;
+  vsg_sim3_opt_result res_ = {};
+};
+
 }  // namespace vsg

@@ -10,6 +10,7 @@
 #include "vsg_pose_opt.h"
 #include "vsg_project.h"
 #include "vsg_sim3.h"
+#include "vsg_sim3_opt.h"
 #include "vsg_triangulate.h"
 
 extern "C" {
@@ -182,6 +183,34 @@ int s3_host_side(int n, const float *Xw1, const float *Xw2, const float *max_err
   vsg::sim3::ransac_host(n, Xw1, Xw2, max_err1, max_err2, *kf1, *kf2, fix_scale != 0, min_inliers, n_hyp, samples, true, pts.data(),
                          counts.data(), inlier, res, nullptr, nullptr);
   return res->iterations;
+}
+
+// The caller-side Optimizer::OptimizeSim3 (Optimizer.cc:3261-3529) on positions read back from the stores: slots1 / slots2
+// index pos1 / pos2, the read-back arrays; k1 / k2 = the keyframes' x, y and octaves.  The header's argument check, gather,
+// both optimisations with their checks and the copy-out (vsg::sim3opt::HostCall), on one thread.
+int so_host_side(int n1, int n2, const int32_t *slots1, const int32_t *slots2, const int32_t *idx2, const int32_t *level2,
+                 int cap1, int cap2, const float *pos1, const float *pos2, const float *k1x, const float *k1y,
+                 const int32_t *oct1, const float *k2x, const float *k2y, const int32_t *oct2, const vsg_frame_pose *pose1,
+                 const vsg_frame_pose *pose2, const float *sig1, const float *sig2, int nlevels, const vsg_sim3d *S12, float th2,
+                 int fix_scale, int all_points, uint8_t *state, double *chi2, vsg_sim3_opt_result *res) {
+  namespace so = vsg::sim3opt;
+  if (nlevels < 1 || nlevels > 16 || !so::th2_ok(th2)) return -6;
+  int n_cand = 0;
+  if (!so::check_entries(n1, slots1, slots2, idx2, level2, cap1, cap2, n2, nlevels, all_points != 0,
+                         [&](int i) { return (int)oct1[i]; }, [&](int i) { return (int)oct2[i]; }, &n_cand))
+    return -6;
+  if (n_cand == 0) {
+    for (int i = 0; i < n1; i++) state[i] = so::kNoEdge;
+    so::fill_result(res, *S12, so::Counts{0, 0, 0}, 0, 0, 5, 0);
+    return 0;
+  }
+  static thread_local so::HostCall call;
+  call.gather(n1, slots1, slots2, idx2, level2, pos1, pos2, k1x, k1y, oct1, k2x, k2y, oct2, *pose1, *pose2, sig1, sig2, nlevels,
+              all_points != 0);
+  const so::Outcome o = call.optimise(*pose1, *pose2, so::sim3_of(*S12), th2, fix_scale != 0);
+  call.copy_out(n1, state, chi2);
+  so::fill_result(res, o.updated ? so::sim3d_canon(o.S12) : *S12, call.counts, o.n_bad, o.n_in, o.more_iterations, o.updated);
+  return o.ret;
 }
 
 }  // extern "C"

@@ -43,7 +43,13 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
                  early exit (NOT Eigen: the header's own arithmetic)
             B  = vsg_mappoints_sim3_ransac (every hypothesis, no early exit);  A2 / B2 = both again.  Equal results asserted
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3> [calls] [out.json]  -> runs the child, writes the record (default
+  sim3opt   Optimizer::OptimizeSim3 on two resident keyframes of 1000 features (LoopClosing.cc:538, :747): 30 / 100 / 300 pairs
+            between two stores of 4096 slots, 20 % outliers, th2 = 10, fix_scale 0 and 1 (a size is "<pairs>:<fix_scale>")
+            A  = vsg_mappoints_read of both point sets + the host build of csrc/vsg_sim3_opt.h on one thread (NOT g2o: the
+                 header's own arithmetic, numeric Jacobian included)
+            B  = vsg_frame_optimize_sim3;  A2 / B2 = both again.  Every call asserts A and B equal bit for bit
+
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -72,7 +78,8 @@ def host_side(orb):
     so = out / "libresident_points_cpu.so"
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
-           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h"]
+           csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
+           csrc / "vsg_sim3_opt.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
                                str(src[0])])
@@ -93,6 +100,9 @@ def host_side(orb):
                                _u8p, _u8p, _f32p, _i32p, _i32p, _f32p, _i32p]
     H.s3_host_side.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _u8p,
                                C.c_void_p]
+    H.so_host_side.argtypes = [C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _i32p,
+                               _f32p, _f32p, _i32p, C.c_void_p, C.c_void_p, _f32p, _f32p, C.c_int, C.c_void_p, C.c_float, C.c_int,
+                               C.c_int, _u8p, C.POINTER(C.c_double), C.c_void_p]
     H.po_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, C.c_int, _u8p, _f32p,
                                C.POINTER(C.c_double), _i32p]
     return H
@@ -633,7 +643,90 @@ class Sim3(Case):
                              "Sophus); B = vsg_mappoints_sim3_ransac, which computes all hypotheses"}
 
 
-CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3}
+class Sim3Opt(Case):
+    """Optimizer::OptimizeSim3 on resident keyframes and map points: a scene of tests/sim3opt_scenes.py (two keyframes of 1000
+    features, the pairs related by a similarity of scale 1.3, inlier noise within 0.8 sigma, 20 % outliers displaced by 6 sigma
+    or more, the input 2 cm / 1 degree / 2 % off).  A size is "<pairs>:<fix_scale>"."""
+    SIZES = tuple("%d:%d" % (n, f) for n in (30, 100, 300) for f in (0, 1))
+    TH, DEST = 10.0, "sim3_optimization_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+    CAP = 4096
+
+    def __init__(self, orb, fr, size):
+        import sim3opt_scenes as ss
+        n, fix = (int(v) for v in size.split(":"))
+        self.orb, self.n, self.fix = orb, n, fix
+        s = self.s = ss.make(7100 + n + fix, n, n1=NFEAT, outliers=0.2, fix_scale=fix, scale=1.3, capacity=self.CAP)
+        c = np.ascontiguousarray
+
+        def keys(k):
+            out = np.zeros(len(k["x"]), orb.KP_DTYPE)
+            out["x"], out["y"], out["octave"] = k["x"], k["y"], k["octave"]
+            return out
+        self.kf = [orb.Frame(len(k["x"]) + 1).upload(keys(k), np.zeros((len(k["x"]), 32), np.uint8), (0.0, 0.0, 640.0, 480.0))
+                   for k in (s["kps1"], s["kps2"])]
+        self.mp = [orb.MapPoints(self.CAP), orb.MapPoints(self.CAP)]
+        self.mp[0].update(np.arange(self.CAP), world_pos=s["pos1"])
+        self.mp[1].update(np.arange(self.CAP), world_pos=s["pos2"])
+        self.pose = [orb.FramePose.make(k["Rcw"], k["tcw"], np.zeros(3), k["fx"], k["fy"], k["cx"], k["cy"], 0.0, 0.0, 0)
+                     for k in (s["pose1"], s["pose2"])]
+        self.slots = [c(s["slots1"], np.int32), c(s["slots2"], np.int32)]
+        self.idx2, self.level2 = c(s["idx2"], np.int32), c(s["level2"], np.int32)
+        self.sig = c(s["sig1"], np.float32)
+        self.S12 = orb.Sim3d.make(*s["S12"])
+        # the caller-side path reads the points of the entries that have one: their slots, and where each lands in the read-back
+        self.rd, self.back, self.Xw = [], [], []
+        for sl in self.slots:
+            have = np.flatnonzero(sl >= 0)
+            back = np.full(len(sl), -1, np.int32)
+            back[have] = np.arange(len(have), dtype=np.int32)
+            self.rd.append(c(sl[have], np.int32)), self.back.append(back), self.Xw.append(np.zeros(3 * len(have), np.float32))
+        self.k = [[c(k["x"], np.float32), c(k["y"], np.float32), c(k["octave"], np.int32)] for k in (s["kps1"], s["kps2"])]
+        self.state, self.chi2, self.res = np.zeros(NFEAT, np.uint8), np.zeros(2 * NFEAT), orb.Sim3OptResult()
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.state[:], self.chi2[:] = 9, -1.0
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        f64p = C.POINTER(C.c_double)
+        if name.startswith("B"):
+            return L.vsg_frame_optimize_sim3(self.kf[0].handle, self.kf[1].handle, self.mp[0].handle, self.mp[1].handle,
+                                             p(self.slots[0], _i32p), p(self.slots[1], _i32p), p(self.idx2, _i32p),
+                                             p(self.level2, _i32p), C.byref(self.pose[0]), C.byref(self.pose[1]), p(self.sig, _f32p),
+                                             p(self.sig, _f32p), 8, C.byref(self.S12), self.TH, self.fix, 0, p(self.state, _u8p),
+                                             p(self.chi2, f64p), C.byref(self.res))
+        for k in range(2):
+            rc = L.vsg_mappoints_read(self.mp[k].handle, len(self.rd[k]), p(self.rd[k], _i32p), p(self.Xw[k], _f32p), None, None,
+                                      None, None, None)
+            if rc != 0:
+                return rc
+        return H.so_host_side(NFEAT, len(self.k[1][0]), p(self.back[0], _i32p), p(self.back[1], _i32p), p(self.idx2, _i32p),
+                              p(self.level2, _i32p), len(self.rd[0]), len(self.rd[1]), p(self.Xw[0], _f32p), p(self.Xw[1], _f32p),
+                              p(self.k[0][0], _f32p), p(self.k[0][1], _f32p), p(self.k[0][2], _i32p), p(self.k[1][0], _f32p),
+                              p(self.k[1][1], _f32p), p(self.k[1][2], _i32p), C.addressof(self.pose[0]), C.addressof(self.pose[1]),
+                              p(self.sig, _f32p), p(self.sig, _f32p), 8, C.addressof(self.S12), self.TH, self.fix, 0,
+                              p(self.state, _u8p), p(self.chi2, f64p), C.addressof(self.res))
+
+    def result(self, name, r):
+        return (r, self.state.copy(), self.chi2.view(np.uint64).copy(), np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.Sim3OptResult.from_buffer_copy(last["B"][3].tobytes())
+        return {"pairs": self.n, "fix_scale": self.fix, "features_per_keyframe": NFEAT, "store_slots": self.CAP,
+                "n_correspondences": int(r.n_correspondences), "n_bad": int(r.n_bad), "n_in": int(r.n_in),
+                "more_iterations": int(r.more_iterations),
+                "host_side": "A = vsg_mappoints_read x 2 + the host build of csrc/vsg_sim3_opt.h on one thread "
+                             "(tools/resident_points_cpu.cpp); it is THIS header's build and NOT g2o (no Eigen here): the same "
+                             "arithmetic, no virtual calls, no sparse block solver, so it likely flatters the host; "
+                             "B = vsg_frame_optimize_sim3"}
+
+
+CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3,
+         "sim3opt": Sim3Opt}
 
 
 def child(case, calls):

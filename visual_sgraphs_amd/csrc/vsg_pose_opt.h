@@ -434,7 +434,8 @@ struct HostTeam {
   float *chi2_out;  // per edge
   int n_edges;
 
-  static void tree(double (*part)[kAcc], int n, double *acc) {
+  template <int W>  // W accumulators per thread: kAcc here, 36 in vsg_sim3_opt.h, one tree
+  static void tree(double (*part)[W], int n, double *acc) {
     for (int k = 0; k < n; k++) {
       double wave_sum[kWaves];
       for (int w = 0; w < kWaves; w++) {

@@ -89,6 +89,8 @@ EXPORTS = [
     "vsg_frame_set_stereo_points", "vsg_frame_triangulate_matches", "vsg_frame_create_new_map_points",
     # Sim3Solver on resident map points: every RANSAC hypothesis in one call, and the host-side set-up of the solver
     "vsg_mappoints_sim3_ransac", "vsg_sim3_ransac_iterations", "vsg_sim3_draw_samples",
+    # Optimizer::OptimizeSim3 on two resident keyframes and resident map points
+    "vsg_frame_optimize_sim3",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
 ]
@@ -164,6 +166,29 @@ class Sim3Result(C.Structure):
                 ("converged", C.c_int32), ("no_more", C.c_int32), ("n_inliers", C.c_int32), ("best_hypothesis", C.c_int32),
                 ("iterations", C.c_int32)]
 
+
+class Sim3d(C.Structure):
+    """include/vsg_orb.h vsg_sim3d: g2o::Sim3, r as x y z w (taken as it is, not normalised), t, s."""
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double)]
+
+    @classmethod
+    def make(cls, q, t, s):
+        o = cls()
+        o.q[:] = [float(v) for v in np.asarray(q, np.float64).reshape(4)]
+        o.t[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+        o.s = float(s)
+        return o
+
+
+class Sim3OptResult(C.Structure):
+    """include/vsg_orb.h vsg_sim3_opt_result: g2oS12 on return, nCorrespondences, nBad, nIn, nInKF2, nOutKF2,
+    nMoreIterations and whether g2oS12 was updated (Optimizer.cc:3526)."""
+    _fields_ = [("S12", Sim3d), ("n_correspondences", C.c_int32), ("n_bad", C.c_int32), ("n_in", C.c_int32),
+                ("n_in_kf2", C.c_int32), ("n_out_kf2", C.c_int32), ("more_iterations", C.c_int32), ("updated", C.c_int32)]
+
+
+# vsg_frame_optimize_sim3: state[i]
+SIM3_OPT_STATES = ("no_edge", "inlier", "nulled_first_check", "nulled_second_check", "skipped_z_negative", "skipped_not_in_kf2")
 
 _RANDOM_INT = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)
 
@@ -414,6 +439,8 @@ def load_library():
     L.vsg_mappoints_sim3_ransac.argtypes = [vp, vp, ci, _i32p, _i32p, _f32p, _f32p, C.POINTER(FramePose), C.POINTER(FramePose),
                                             ci, ci, ci, _i32p, _u8p, C.POINTER(Sim3Result), _i32p, _f32p]
     L.vsg_sim3_ransac_iterations.argtypes = [C.c_double, ci, ci, ci]
+    L.vsg_frame_optimize_sim3.argtypes = [vp, vp, vp, vp, _i32p, _i32p, _i32p, _i32p, C.POINTER(FramePose), C.POINTER(FramePose),
+                                          _f32p, _f32p, ci, C.POINTER(Sim3d), cf, ci, ci, _u8p, _f64p, C.POINTER(Sim3OptResult)]
     L.vsg_sim3_draw_samples.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
@@ -1635,6 +1662,39 @@ class Frame:
             self._h, _p(rem, _u8p) if rem is not None else None, _p(out, _u8p), _p(c2, _f32p), C.byref(res)),
             "vsg_frame_pose_optimization_resume")
         return self._pose_result(ret, res, out[:len(self.kps)], c2[:len(self.kps)])
+
+    # ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, ...) on resident map points
+    # (Optimizer.cc:3261-3529); self is pKF1
+    def OptimizeSim3(self, kf2, mp1, mp2, slots1, slots2, idx2, level2, pose1, pose2, inv_level_sigma2_1,
+                     inv_level_sigma2_2, S12, th2, fix_scale, all_points=False, chi2=None):
+        """slots1[i] / slots2[i] = slot of vpMapPoints1[i] in mp1 / of vpMatches1[i] in mp2 (< 0: missing or bad), one per
+        feature of this keyframe; idx2[i] = the match's index in kf2 or < 0; level2[i] = its mnTrackScaleLevel (read when
+        idx2[i] < 0); pose1 / pose2: FramePose (Rcw, tcw, fx, fy, cx, cy are read); S12 = (q x y z w, t, s), taken as it is.
+        chi2 (an optional float64 array of shape (n, 2)) is updated IN A COPY for the pairs with an edge.  Returns a dict:
+        ret (nIn, or 0), S12 = (q, t, s) float64, S12_bytes, updated, n_correspondences, n_bad, n_in, n_in_kf2, n_out_kf2,
+        more_iterations, state (uint8 per feature, SIM3_OPT_STATES), chi2.  The caller nulls vpMatches1[i] where state[i]
+        is 2 or 3 and zero-fills mAcumHessian."""
+        n = len(self.kps)
+        arrs = [_i32(a) for a in (slots1, slots2, idx2, level2)]
+        if any(len(a) != n for a in arrs):
+            raise ValueError("slots1 / slots2 / idx2 / level2 length does not match the keyframe's features")
+        if len(inv_level_sigma2_1) != len(inv_level_sigma2_2):
+            raise ValueError("the two sigma tables differ in length")
+        arrs = [a if a.size else np.zeros(1, np.int32) for a in arrs]
+        sig1, sig2 = _f32(inv_level_sigma2_1), _f32(inv_level_sigma2_2)
+        state = np.zeros(max(n, 1), np.uint8)
+        c2 = np.zeros(2 * max(n, 1), np.float64) if chi2 is None else np.ascontiguousarray(chi2, np.float64).reshape(-1).copy()
+        if c2.size < 2 * n:
+            raise ValueError("chi2 needs two entries per feature")
+        s12, res = Sim3d.make(*S12), Sim3OptResult()
+        ret = _check(self._L.vsg_frame_optimize_sim3(
+            self._h, kf2.handle, mp1.handle, mp2.handle, *[_p(a, _i32p) for a in arrs], C.byref(pose1), C.byref(pose2),
+            _p(sig1, _f32p), _p(sig2, _f32p), len(sig1), C.byref(s12), float(np.float32(th2)), int(bool(fix_scale)),
+            int(bool(all_points)), _p(state, _u8p), _p(c2, C.POINTER(C.c_double)), C.byref(res)), "vsg_frame_optimize_sim3")
+        out = dict(ret=ret, S12=(np.array(res.S12.q[:], np.float64), np.array(res.S12.t[:], np.float64), float(res.S12.s)),
+                   S12_bytes=bytes(res.S12), input_bytes=bytes(s12), state=state[:n], chi2=c2[:2 * n].reshape(n, 2))
+        out.update({k: int(getattr(res, k)) for k, _ in Sim3OptResult._fields_[1:]})
+        return out
 
     # ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono) on resident map points  (ORBmatcher.cc:1667-1878)
     def SearchLastFrame(self, last, mp, last_slots, cur_pose, last_pose, mb, mono, th, scale_factors, train_blocked,
