@@ -176,7 +176,7 @@ def test_resident_feature_vector_needs_its_compute_bow(reference_scale_vocabular
 
 @pytest.mark.parametrize("scoring,weighting", [(0, 0), (1, 1), (5, 0), (2, 2), (0, 3)])
 def test_bow_assembly_on_the_device_and_on_the_host_agree_with_the_oracle(scoring, weighting):
-    """Frames of up to 2048 features are assembled by k_bow_assemble (bitonic sort in LDS, sums in the reference's order);
+    """Frames of up to 2048 features are ranked by k_bow_rank and assembled by k_bow_assemble (sums in the reference's order);
     larger ones by the same steps on the host.  Both against the oracle, bit for bit, incl. stopped words (a third of the
     leaves weigh 0 here) and features that share a word (descriptors repeated)."""
     blob = synth.synthetic_vocabulary(6, 3, seed=91, scoring=scoring, weighting=weighting, stop_fraction=0.3)

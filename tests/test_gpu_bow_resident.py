@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from bow_scenes import B, keypoints, near_dups
 from visual_sgraphs_amd import orb, synth
 
 pytestmark = pytest.mark.gpu
 
-B = (0.0, 0.0, 640.0, 480.0)
 RATIOS = [(0.6, True), (0.75, False), (0.9, True)]
 
 
@@ -30,26 +30,6 @@ def reference_vocab():
     """The reference's shape, k = 10, L = 6 (generated, 50 MB, never committed), with 5 % of the words stopped."""
     blob = synth.synthetic_vocabulary(10, 6, seed=17, stop_fraction=0.05)
     return ol.OracleVocabulary(blob), orb.ORBVocabulary(blob)
-
-
-def keypoints(angle, rng):
-    n = len(angle)
-    k = np.zeros(n, orb.KP_DTYPE)
-    k["x"], k["y"] = rng.uniform(0, 639, n), rng.uniform(0, 479, n)
-    k["size"], k["response"], k["octave"] = 31.0, 1.0, rng.integers(0, 8, n)
-    k["angle"] = angle
-    return k
-
-
-def near_dups(desc, rng, max_flips):
-    """Each row with up to `max_flips` random bits flipped (some rows stay exact copies)."""
-    out = desc.copy()
-    rows = np.arange(len(out))
-    for _ in range(max_flips):
-        m = rng.random(len(out)) < 0.6
-        bit = rng.integers(0, 256, len(out))
-        out[rows[m], bit[m] >> 3] ^= (1 << (bit[m] & 7)).astype(np.uint8)
-    return out
 
 
 def rotated(angle, rng):
