@@ -70,6 +70,13 @@ int vsg_orb_set_blur_taps(vsg_orb *h, const uint16_t taps[7]);
  * form stays a tested path instead of an environment switch. */
 int vsg_orb_set_pyramid_tiling(vsg_orb *h, int which);
 
+/* Launch form of the per-cell FAST kernel (k_fast_cells): -1 (default) = automatic, the form compiled without the paths
+ * that the handle's geometry rules out (sliver cells, tiles beyond the prefetch registers, one candidate list per level)
+ * where it applies; 0 = the general form, which handles every geometry.  Both produce the same bytes
+ * (tests/test_gpu_fast_forms.py); the setter serves tests and in-process A/B.  vsg_launch_forms.fast_specialised
+ * (include/vsg_orb_debug.h) reports which one a launch took. */
+int vsg_orb_set_fast_form(vsg_orb *h, int which);
+
 /* Keypoint capacity a caller must provide per frame for images of this size (>= nfeatures + 3*nlevels,
  * ORBextractor.cc:692,753-754), or a VSG_ERR_* code. */
 int vsg_orb_capacity(vsg_orb *h, int rows, int cols);

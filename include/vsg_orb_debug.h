@@ -44,6 +44,7 @@ typedef struct vsg_launch_forms {
   int cus;                /* compute units the FAST cells-per-workgroup gate used */
   int total_cells;        /* FAST cells per frame of the geometry (the gate's other input) */
   int nframes;            /* frames of the batch described */
+  int fast_specialised;   /* 1: k_fast_cells<kSeg, kPlain> (no sliver / unfetched-tile staging, no per-level list); 0: general */
 } vsg_launch_forms;
 
 /* Test hook: the launch forms of the handle's most recent enqueue (any entry point).  VSG_ERR_INVALID before the first

@@ -111,8 +111,27 @@ struct Geometry {
   std::vector<Short4> resizeTab;  // all levels, x tables then y tables (offsets in LevelGeom)
   std::vector<CellDesc> cells;
   std::vector<FastCellRec> fastRecs;  // one per cell, same order
+  bool fastPlain = false;             // fast_cells_plain(fastRecs, ...) for the geometry's tile class
   int maxQuota = 0;
 };
+
+// k_fast_cells' tile classes (launch_fast): bytes per tile row for the widest valid region of a geometry's cells, and the
+// 16-byte chunks of the next cell's tile that a workgroup of the class holds in registers (kPre * NT)
+inline int fast_tile_pitch(int maxVw) { return maxVw <= 40 ? 52 : maxVw <= 56 ? 68 : 84; }
+inline int fast_prefetch_chunks(int tile_pitch) { return 128 * ((tile_pitch - 52) / 16 + 2); }
+// No live cell is a sliver (tile rows shorter than one 16-byte chunk) and every live cell's tile fits the prefetch
+// registers: k_fast_cells then never stages a tile when its turn comes, and launch_fast takes the form compiled without
+// those two loops.  A pure function of the records (w3: tile dwords per row in bits 16-20, chunks per row in 21-23, rows
+// of the valid region in 7-13; 0 = empty cell).
+inline bool fast_cells_plain(const std::vector<FastCellRec> &recs, int prefetch_chunks) {
+  for (const FastCellRec &R : recs) {
+    const uint32_t w3 = R.w[3];
+    if (w3 == 0) continue;
+    const int tdw = (int)((w3 >> 16) & 31u), nq4 = (int)((w3 >> 21) & 7u), th = (int)((w3 >> 7) & 127u) + 6;
+    if (tdw < 4 || nq4 * th > prefetch_chunks) return false;
+  }
+  return true;
+}
 
 
 inline int16_t sat_short(float v) {
@@ -409,8 +428,9 @@ inline int build_geometry(Geometry &G, const ExtractorTables &T, int rows, int c
   {
     // k_fast_cells: a queue entry holds a run's dword index in the tile in 11 bits, a surviving pixel's byte offset in
     // 13 (vsg_kernels.hip); the tile pitch classes are launch_fast's.  The reference's 35 px cell grid gives <= 69 x 69.
-    const int tp = G.fastMaxVw <= 40 ? 52 : G.fastMaxVw <= 56 ? 68 : 84;
+    const int tp = fast_tile_pitch(G.fastMaxVw);
     if (G.fastMaxVw + 9 > tp || (G.fastMaxVh + 7) * tp > 8192) return -3;
+    G.fastPlain = fast_cells_plain(G.fastRecs, fast_prefetch_chunks(tp));
   }
   fg.cand_frame = cand_off;
   fg.sel_frame = sel_off;

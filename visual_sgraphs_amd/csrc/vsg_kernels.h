@@ -31,6 +31,7 @@ void launch_pyramid(hipStream_t s, uint8_t *pyr, const FrameGeom *d_fg, const Sh
 // what launch_fast / launch_octree chose (the hook vsg_debug_last_launch_forms reports it)
 struct FastForm {
   int cells_per_wg = 0, tile_pitch = 0;
+  int specialised = 0;  // 1: k_fast_cells<.., kSeg = true, kPlain = true>; 0: the general form
 };
 struct OctreeForm {
   int kernel = 0;  // VSG_OCT_* (include/vsg_orb_debug.h)
@@ -38,7 +39,7 @@ struct OctreeForm {
 };
 FastForm launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs, const Src0 &s0,
                      uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh, int maxVw, int maxArea,
-                     int nframes, int cus);
+                     int nframes, int cus, bool plain);
 OctreeForm launch_octree(hipStream_t s, const FrameGeom *d_fg, const uint32_t *cand, const int *cand_count,
                          const CellDesc *d_cells, const int *cell_count, uint32_t *cand2, uint16_t *node_of, uint32_t *sel,
                          int *sel_count, const FrameGeom &fg, int maxQuota, int maxCellsPerLevel, int nframes,

@@ -512,7 +512,16 @@ __device__ __forceinline__ FastKArgsPtr fast_kargs() {
 // life of a workgroup, and ~3 us of a one-cell workgroup's 6 us were launch + descriptor chain + the tile's trip from
 // L2 (profiles/r03_c_fast_ablation.txt: 0.065 / 0.074 / 0.108 / 0.221 ms for workgroups that end at once / after the
 // descriptors / after a staging pass without loads / after the real staging pass, of 0.441 ms).
-template <int NT, int kTileP, int kScoreP, int kPre>
+//
+// Two launch-invariant properties of the geometry are template parameters: what they rule out is not in the code object at
+// all -- under the register caps below, code that never runs still costs the cell loop spills (a block-frequency hint only
+// tells the allocator where to put them).
+//   kSeg    fg.cand_segmented: candidates go to per-cell segments.  Without it the kernel also carries the atomically
+//           appended per-level list (levels of more than kOctMaxCells cells) and reads which of the two from th_pack.
+//   kPlain  Geometry::fastPlain: no live cell is a sliver and every live cell's tile fits the prefetch registers, so a live
+//           cell always finds its tile fetched and the two loops that stage a tile when its turn comes are gone.
+// launch_fast takes <true, true> where the geometry allows it and <false, false>, which handles every geometry, otherwise.
+template <int NT, int kTileP, int kScoreP, int kPre, bool kSeg, bool kPlain>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amdgpu_waves_per_eu(kFastWaves, kFastWaves))) void k_fast_cells(
     const uint8_t *__restrict__ pyr, const FrameGeom *__restrict__ fg, const FastCellRec *__restrict__ recs, Src0 s0,
     uint32_t *__restrict__ cand, int *__restrict__ cand_count, int *__restrict__ cell_count, int tile_bytes,
@@ -533,7 +542,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
   const BlockXY blk = frame_major_block();
   const int frame = blk.y;
   const int tid = threadIdx.x, lane = tid & 63;
-  // th_pack = iniThFAST | minThFAST << 8 | cand_segmented << 16 (launch-invariant, ONE register for the whole loop)
+  // th_pack = iniThFAST | minThFAST << 8 | (kSeg ? 0 : cand_segmented << 16) (launch-invariant, ONE register for the whole loop)
   const int c_begin = blk.x * cells_per_wg, c_end = min(c_begin + cells_per_wg, total_cells);
   typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(4)));
   u32x4u pre[kPre];
@@ -557,7 +566,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
   int rc_nq4 = 0, rc_r[kKeepRC ? kPre : 1], rc_c[kKeepRC ? kPre : 1];
   auto fetch = [&](const FastCell &N) -> bool {
     const int n = N.nq4() * N.th();
-    if (!N.live() || N.tdw() < 4 || n > kPre * NT) return false;
+    if constexpr (kPlain) {
+      if (!N.live()) return false;
+    } else {
+      if (!N.live() || N.tdw() < 4 || n > kPre * NT) return false;
+    }
     if constexpr (kKeepRC) {
       if (N.nq4() != rc_nq4) {  // workgroup-uniform
         rc_nq4 = N.nq4();
@@ -599,7 +612,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
       N = load_fast_cell(recs + (ci + 1), ks0, ka->pyr, ka->pyr_frame_bytes, frame);
     }
     const bool live = C.live();
-    if (live) {
+    if constexpr (kPlain) {
+      if (live) {  // a live cell's tile is always in the prefetch registers
+        const int n = C.nq4() * C.th();
+#pragma unroll
+        for (int k = 0; k < kPre; k++)
+          if (tid + k * NT < n) put(pre_off[k], pre[k]);
+      }
+    } else if (live) {
       if (VSG_COLD(C.tdw() < 4)) {  // a sliver of a cell at the right edge of a level (cell-uniform)
         const float inv_tdw = __builtin_amdgcn_rcpf((float)C.tdw());
         for (int i = tid; i < C.tdw() * C.th(); i += NT) {
@@ -625,7 +645,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
     }
     // the next cell's tile is on its way while this one is worked on
     have_pre = ci + 1 < c_end && fetch(N);
-    const bool seg = (th_pack >> 16) != 0;
+    const bool seg = kSeg || (th_pack >> 16) != 0;
     auto my_count = [&]() -> int * {  // the cell's counter, from the kernarg segment at the moment it is written
       const FastKArgsPtr ka = fast_kargs();
       return ka->cell_count + ((size_t)frame * ka->total_cells + ci);
@@ -652,7 +672,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
         const uint32_t p1_mask = (p1_rr == 0 ? C.first_mask : 0xF0F0F0F0u) & (p1_rr == nrun - 1 ? C.last_mask : 0xF0F0F0F0u);
         const uint32_t p1_left = g0 == 0 && p1_rr == 0 ? 0u : ~0u;  // and-mask of the dword left of the run (see below)
         const int p1_off = (p1_row + 3) * kTileP + 4 * (g0 + 2 * p1_rr);
-        uint32_t keep = 0;
+        uint32_t keep = 0;  // (!kSeg only)
         int nq = 0, thr = iniTh;
         for (int pass = 0; pass < 2; pass++) {
           if (VSG_OPQ(tid) < 5) s_cnt[tid] = 0;
@@ -847,7 +867,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
           // ---- phase 3: non-max suppression inside the cell
           uint32_t *seg_out = cand + ((size_t)frame * cand_frame + C.cand_off);
           keep = 0;  // bit per loop iteration: queued pixel survives NMS
-          int it = 0;
+          int it = 0;  // (!kSeg only)
           int nbias = kScoreP + 1;  // the 3 x 3 neighbourhood at non-negative offsets from one register (see kBias)
           asm volatile("" : "+s"(nbias));
           const uint8_t *score_b = score - nbias;
@@ -861,7 +881,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
             asm volatile("" : "+v"(s), "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(n4), "+v"(n5), "+v"(n6), "+v"(n7));
             const int mx = max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7)));
             if (s > mx) {
-              if (VSG_HOT(seg)) {
+              if (kSeg || VSG_HOT(seg)) {
                 const int r1 = div_small((int)ent, 1.0f / kScoreP), c1 = (int)ent - r1 * kScoreP;  // row + 1, column + 1
                 seg_out[atomicAdd(&s_cnt[0], 1)] = pack_cand(cell_x0 + c1 - 1 - kFastBorder, cell_y0 + r1 - 1 - kFastBorder, s);
               } else {
@@ -881,7 +901,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kFastSgprs), amd
 
 
       const int nEmit = s_cnt[0];
-      if (VSG_HOT(seg)) {
+      if (kSeg || VSG_HOT(seg)) {
         if (VSG_OPQ(tid) == 0) *my_count() = nEmit;
       } else if (nEmit) {  // levels of more than 4096 cells: one unordered list per level (rare geometries)
         const FastKArgsPtr ka = fast_kargs();
@@ -2450,7 +2470,7 @@ void launch_pyramid(hipStream_t s, uint8_t *pyr, const FrameGeom *d_fg, const Sh
   hipLaunchKernelGGL(k_pyramid, dim3(ntiles, nframes), dim3(kPyrThreads), lds, s, pyr, d_fg,
                      d_tile_tab, s0, d_tiles, a16, ab16, cand_count);
 }
-template <int NT, int TP, int SP, int PRE>
+template <int NT, int TP, int SP, int PRE, bool SEG, bool PLAIN>
 static FastForm launch_fast_t(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs,
                           const Src0 &s0, uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh,
                           int maxArea, int nframes, int cus) {
@@ -2469,25 +2489,34 @@ static FastForm launch_fast_t(hipStream_t s, const uint8_t *pyr, const FrameGeom
   // the pixel queue's region also holds the 6-bit copy of the tile during the necessary test
   const size_t queue_bytes = std::max<size_t>(((size_t)maxArea * 2 + 15) & ~(size_t)15, (size_t)tile_bytes);
   const size_t lds = (size_t)tile_bytes + score_bytes + queue_bytes;
-  const int th_pack = (fg.iniTh & 0xFF) | ((fg.minTh & 0xFF) << 8) | ((fg.cand_segmented ? 1 : 0) << 16);
-  hipLaunchKernelGGL((k_fast_cells<NT, TP, SP, PRE>), grid, block, lds, s, pyr, d_fg, d_recs, s0, cand, cand_count,
+  static_assert(PRE * NT == 128 * ((TP - 52) / 16 + 2), "fast_prefetch_chunks (vsg_geometry.h) restates kPre * NT");
+  const int th_pack = (fg.iniTh & 0xFF) | ((fg.minTh & 0xFF) << 8) | ((!SEG && fg.cand_segmented ? 1 : 0) << 16);
+  hipLaunchKernelGGL((k_fast_cells<NT, TP, SP, PRE, SEG, PLAIN>), grid, block, lds, s, pyr, d_fg, d_recs, s0, cand, cand_count,
                      cell_count, tile_bytes, score_bytes, maxArea, cells_per_wg, fg.pyr_frame_bytes, fg.total_cells,
                      fg.cand_frame, th_pack);
   FastForm f;
-  f.cells_per_wg = cells_per_wg, f.tile_pitch = TP;
+  f.cells_per_wg = cells_per_wg, f.tile_pitch = TP, f.specialised = SEG && PLAIN ? 1 : 0;
   return f;
 }
 FastForm launch_fast(hipStream_t s, const uint8_t *pyr, const FrameGeom *d_fg, const FastCellRec *d_recs, const Src0 &s0,
                      uint32_t *cand, int *cand_count, int *cell_count, const FrameGeom &fg, int maxVh, int maxVw, int maxArea,
-                     int nframes, int cus) {
+                     int nframes, int cus, bool plain) {
   // tile row = up to 3 alignment bytes + vw + 6 ring bytes, rounded up to dwords; score rows (vw + 2 used) have the
   // tile's pitch: a pixel's score sits a constant away from its tile byte (k_fast_cells phase 2)
-  if (maxVw <= 40)
-    return launch_fast_t<kFastThreads, 52, 52, 2 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
-  else if (maxVw <= 56)
-    return launch_fast_t<kFastThreads, 68, 68, 3 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+  // `plain` (Geometry::fastPlain, or false when the general form is forced) with segmented candidate lists selects the
+  // form compiled without the cold paths.  The widest class has it on no reference configuration and stays general.
+  const bool spec = plain && fg.cand_segmented;
+  const int tp = fast_tile_pitch(maxVw);
+#define VSG_FAST_ARGS s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus
+  if (tp == 52)
+    return spec ? launch_fast_t<kFastThreads, 52, 52, 2 * (128 / kFastThreads), true, true>(VSG_FAST_ARGS)
+                : launch_fast_t<kFastThreads, 52, 52, 2 * (128 / kFastThreads), false, false>(VSG_FAST_ARGS);
+  else if (tp == 68)
+    return spec ? launch_fast_t<kFastThreads, 68, 68, 3 * (128 / kFastThreads), true, true>(VSG_FAST_ARGS)
+                : launch_fast_t<kFastThreads, 68, 68, 3 * (128 / kFastThreads), false, false>(VSG_FAST_ARGS);
   else
-    return launch_fast_t<kFastThreads, 84, 84, 4 * (128 / kFastThreads)>(s, pyr, d_fg, d_recs, s0, cand, cand_count, cell_count, fg, maxVh, maxArea, nframes, cus);
+    return launch_fast_t<kFastThreads, 84, 84, 4 * (128 / kFastThreads), false, false>(VSG_FAST_ARGS);
+#undef VSG_FAST_ARGS
 }
 // dynamic LDS of one octree workgroup (also what every blur workgroup of the fused launch is charged)
 size_t octree_lds_bytes(const FrameGeom &fg, int maxQuota, int maxCellsPerLevel) {

@@ -166,6 +166,7 @@ struct vsg_orb {
   uint32_t *d_cand2 = nullptr;    // [max_batch][fg.cand_frame] compacted candidates of levels too large for the octree's registers
   int pyr_tiling = 0;                   // the tiling calibration found faster for a full batch of this geometry
   int force_tiling = -1;                // vsg_orb_set_pyramid_tiling (tests: every launch form against the oracle)
+  int force_fast_form = -1;             // vsg_orb_set_fast_form: -1 = automatic, 0 = k_fast_cells' general form
   vsg_post_chain_fn post_fn = nullptr;  // vsg_orb_set_post_chain: enqueued behind the next submit's chain, then cleared
   void *post_ctx = nullptr;
   int cus = 256;                        // compute units of `device` (k_fast_cells' cells-per-workgroup choice)
@@ -484,8 +485,8 @@ static int enqueue_pipeline(vsg_orb *h, const Src0 &s0, int nf, int lap0, int la
   // 254 k frames/s against 250 k with the blur released right after the pyramid.
   if (tm || tmf) HIP_TRY(hipEventRecord(h->ev[8], s));
   const FastForm ff = launch_fast(s, pyr, h->d_fg, h->d_fast, s0, cand, cand_count, cell_count, fg, h->G.fastMaxVh,
-                                  h->G.fastMaxVw, h->G.fastMaxArea, nf, h->cus);
-  rec.fast_cells_per_wg = ff.cells_per_wg, rec.fast_tile_pitch = ff.tile_pitch;
+                                  h->G.fastMaxVw, h->G.fastMaxArea, nf, h->cus, h->G.fastPlain && h->force_fast_form != 0);
+  rec.fast_cells_per_wg = ff.cells_per_wg, rec.fast_tile_pitch = ff.tile_pitch, rec.fast_specialised = ff.specialised;
   if (tm || tmf) HIP_TRY(hipEventRecord(h->ev[2], s));
   // The blur's workgroups ride in the octree's launch (k_octree_blur): both need only the pyramid, the octree is a
   // latency-bound handful of workgroups per frame and the blur issue-bound filler, and inside ONE kernel (one register
@@ -847,6 +848,12 @@ int vsg_orb_set_blur_taps(vsg_orb *h, const uint16_t taps[7]) {
 int vsg_orb_set_pyramid_tiling(vsg_orb *h, int which) {
   if (!h || which < -1 || which > kPyrTilings) return VSG_ERR_INVALID;
   h->force_tiling = which;
+  return VSG_OK;
+}
+
+int vsg_orb_set_fast_form(vsg_orb *h, int which) {
+  if (!h || which < -1 || which > 0) return VSG_ERR_INVALID;
+  h->force_fast_form = which;
   return VSG_OK;
 }
 

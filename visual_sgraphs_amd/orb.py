@@ -93,12 +93,14 @@ EXPORTS = [
     "vsg_frame_optimize_sim3",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
+    # k_fast_cells' launch form: automatic / general
+    "vsg_orb_set_fast_form",
 ]
 
 # include/vsg_orb_debug.h vsg_launch_forms, field for field
 LAUNCH_FORM_FIELDS = ("latency_chain", "pyramid_tiling", "fast_cells_per_wg", "fast_tile_pitch", "cand_segmented",
                       "fused_blur", "octree_kernel", "octree_hist_big", "octree_label_bytes", "octree_lead", "self_slots",
-                      "orient_mirror", "cus", "total_cells", "nframes")
+                      "orient_mirror", "cus", "total_cells", "nframes", "fast_specialised")
 # vsg_launch_forms.octree_kernel (VSG_OCT_*)
 OCT_BLUR_MEMBATCH, OCT_BLUR_MEMBATCH_FUSED, OCT_FEW_MEMBATCH, OCT_FEW_MEMBATCH_FUSED, OCT_STANDALONE = 1, 2, 3, 4, 5
 
@@ -264,6 +266,7 @@ def load_library():
     L.vsg_orb_set_blur_taps.argtypes = [C.c_void_p, _u16p]
     L.vsg_orb_capacity.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.vsg_orb_set_pyramid_tiling.argtypes = [C.c_void_p, C.c_int]
+    L.vsg_orb_set_fast_form.argtypes = [C.c_void_p, C.c_int]
     L.vsg_orb_extract.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _u8p,
                                   C.c_int, _i32p]
     L.vsg_orb_extract_batch.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -556,6 +559,10 @@ class ORBextractor:
         """ComputePyramid's launch form: -1 automatic (default), 0 / 1 / 2 the fused tilings (32 / 36 / 16 px), 3 one launch
         per level."""
         _check(self._L.vsg_orb_set_pyramid_tiling(self._h, int(which)), "vsg_orb_set_pyramid_tiling")
+
+    def set_fast_form(self, which):
+        """k_fast_cells' launch form: -1 automatic (default), 0 the general form (every geometry)."""
+        _check(self._L.vsg_orb_set_fast_form(self._h, int(which)), "vsg_orb_set_fast_form")
 
     def set_direct_registered(self, on=True):
         """Opt in to in-place device access of hipHostRegister-ed caller memory (`pin()`); by default such memory is staged
