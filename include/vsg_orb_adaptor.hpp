@@ -263,7 +263,7 @@ class ORBVocabulary {
     std::vector<int32_t> a, b;
     std::vector<double> av, bv;
     flatten(v1, a, av), flatten(v2, b, bv);
-    const int32_t off[2] = {0, (int32_t)b.size()};
+    const int32_t off[2] = {0, (int32_t)v2.size()};  // not b.size(): flatten() appends a padding element
     double out = 0;
     check(vsg_vocab_score(v_, a.data(), av.data(), (int)v1.size(), off, b.data(), bv.data(), 1, &out), "vsg_vocab_score");
     return out;

@@ -51,6 +51,12 @@ typedef struct vsg_launch_forms {
  * enqueue. */
 int vsg_debug_last_launch_forms(vsg_orb *h, vsg_launch_forms *out);
 
+/* Test hook, read-only: the six KeyFrame members the database's queries read and write, as the device holds them for
+ * keyframe `kf_id` after everything enqueued so far: query = {mnRelocQuery, mnPlaceRecognitionQuery}, words =
+ * {mnRelocWords, mnPlaceRecognitionWords}, score = {mRelocScore, mPlaceRecognitionScore}.  VSG_ERR_INVALID for an id the
+ * database never saw (never added, mapped or named as a neighbour); the outputs are then left alone. */
+int vsg_debug_kfdb_state(vsg_kfdb *db, uint64_t kf_id, uint64_t query[2], int32_t words[2], float score[2]);
+
 #ifdef __cplusplus
 }
 #endif

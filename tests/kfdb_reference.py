@@ -92,6 +92,40 @@ class KeyFrameDatabase:
         self.inv = {}  # word -> list of KeyFrame (mvInvertedFile)
         self.kfs = {}  # every keyframe id seen -> KeyFrame (the objects outlive their database entries)
 
+    # ---- seams: every default is the reference's own behaviour.  tests/kfdb_scenes.py overrides one at a time, to show
+    # that a directed scene tells the reference from one named mistake.
+    N_COVIS = 10  # GetBestCovisibilityKeyFrames(10)
+
+    def _same_query(self, stored, query_id):
+        return stored == query_id
+
+    def _passes_gate(self, words, minCommonWords):
+        return words > minCommonWords
+
+    def _retained(self, accScore, minScoreToRetain):
+        return accScore > minScoreToRetain
+
+    def _better(self, score, bestScore):
+        return score > bestScore
+
+    def _acc_chain(self, si, neighbour_scores):
+        accScore = si
+        for sc in neighbour_scores:
+            accScore = F32(accScore + sc)
+        return accScore
+
+    def _sorted(self, acc_list):
+        return sorted(acc_list, key=lambda p: float(p[0]), reverse=True)  # stable, like std::list::sort(compFirst)
+
+    def _erase_pos(self, lst, k):
+        for p, x in enumerate(lst):
+            if x is k:
+                return p
+        return None
+
+    def _is_connected(self, k, connected):
+        return k.mnId in connected
+
     def kf(self, kf_id):
         k = self.kfs.get(kf_id)
         if k is None:
@@ -110,10 +144,9 @@ class KeyFrameDatabase:
         k = self.kf(kf_id)
         for w in k.bow[0]:
             lst = self.inv.get(int(w), [])
-            for p, x in enumerate(lst):
-                if x is k:
-                    del lst[p]
-                    break
+            p = self._erase_pos(lst, k)
+            if p is not None:
+                del lst[p]
 
     def clear(self):
         self.inv = {}
@@ -126,7 +159,7 @@ class KeyFrameDatabase:
         self.kf(kf_id).map = map_id
 
     def set_covisibility(self, kf_id, neighbours):
-        self.kf(kf_id).covis = [self.kf(n) for n in list(neighbours)[:10]]
+        self.kf(kf_id).covis = [self.kf(n) for n in list(neighbours)[:self.N_COVIS]]
 
     def _score(self, q_ids, q_vals, k):
         return score(self.scoring, q_ids, q_vals, k.bow[0], k.bow[1])
@@ -136,7 +169,7 @@ class KeyFrameDatabase:
         sharing = []
         for w in q_ids:
             for k in self.inv.get(int(w), []):
-                if k.mnRelocQuery != query_id:
+                if not self._same_query(k.mnRelocQuery, query_id):
                     k.mnRelocWords = 0
                     k.mnRelocQuery = query_id
                     sharing.append(k)
@@ -147,7 +180,7 @@ class KeyFrameDatabase:
         minCommonWords = int(F32(maxCommonWords) * F32(0.8))
         scored = []
         for k in sharing:
-            if k.mnRelocWords > minCommonWords:
+            if self._passes_gate(k.mnRelocWords, minCommonWords):
                 si = F32(self._score(q_ids, q_vals, k))
                 k.mRelocScore = si
                 scored.append((si, k))
@@ -157,13 +190,11 @@ class KeyFrameDatabase:
         bestAccScore = F32(0)
         for si, k in scored:
             bestScore = si
-            accScore = bestScore
             best = k
-            for k2 in k.covis:
-                if k2.mnRelocQuery != query_id:
-                    continue
-                accScore = F32(accScore + k2.mRelocScore)
-                if k2.mRelocScore > bestScore:
+            seen = [k2 for k2 in k.covis if self._same_query(k2.mnRelocQuery, query_id)]
+            accScore = self._acc_chain(si, [k2.mRelocScore for k2 in seen])
+            for k2 in seen:
+                if self._better(k2.mRelocScore, bestScore):
                     best = k2
                     bestScore = k2.mRelocScore
             acc_list.append((accScore, best))
@@ -172,7 +203,7 @@ class KeyFrameDatabase:
         minScoreToRetain = F32(F32(0.75) * bestAccScore)
         added, out = set(), []
         for s, k in acc_list:
-            if s > minScoreToRetain:
+            if self._retained(s, minScoreToRetain):
                 if k.map != map_id:
                     continue
                 if k.mnId not in added:
@@ -187,9 +218,9 @@ class KeyFrameDatabase:
         sharing = []
         for w in q_ids:
             for k in self.inv.get(int(w), []):
-                if k.mnPlaceRecognitionQuery != query_kf_id:
+                if not self._same_query(k.mnPlaceRecognitionQuery, query_kf_id):
                     k.mnPlaceRecognitionWords = 0
-                    if k.mnId not in connected:
+                    if not self._is_connected(k, connected):
                         k.mnPlaceRecognitionQuery = query_kf_id
                         sharing.append(k)
                 k.mnPlaceRecognitionWords += 1
@@ -199,7 +230,7 @@ class KeyFrameDatabase:
         minCommonWords = int(F32(maxCommonWords) * F32(0.8))
         scored = []
         for k in sharing:
-            if k.mnPlaceRecognitionWords > minCommonWords:
+            if self._passes_gate(k.mnPlaceRecognitionWords, minCommonWords):
                 si = F32(self._score(q_ids, q_vals, k))
                 k.mPlaceRecognitionScore = si
                 scored.append((si, k))
@@ -208,17 +239,15 @@ class KeyFrameDatabase:
         acc_list = []
         for si, k in scored:
             bestScore = si
-            accScore = bestScore
             best = k
-            for k2 in k.covis:
-                if k2.mnPlaceRecognitionQuery != query_kf_id:
-                    continue
-                accScore = F32(accScore + k2.mPlaceRecognitionScore)
-                if k2.mPlaceRecognitionScore > bestScore:
+            seen = [k2 for k2 in k.covis if self._same_query(k2.mnPlaceRecognitionQuery, query_kf_id)]
+            accScore = self._acc_chain(si, [k2.mPlaceRecognitionScore for k2 in seen])
+            for k2 in seen:
+                if self._better(k2.mPlaceRecognitionScore, bestScore):
                     best = k2
                     bestScore = k2.mPlaceRecognitionScore
             acc_list.append((accScore, best))
-        acc_list = sorted(acc_list, key=lambda p: float(p[0]), reverse=True)  # stable, like std::list::sort(compFirst)
+        acc_list = self._sorted(acc_list)
         bad = set(bad_map_ids)
         loop, merge, added = [], [], set()
         i = 0

@@ -1,22 +1,18 @@
 """GPU parity of TemplatedVocabulary::score and of the device-resident KeyFrameDatabase (vsg_kfdb_*) against
-tests/kfdb_reference.py: scores bit for bit, candidate lists id for id, order included."""
-import struct
+tests/kfdb_reference.py: scores bit for bit, candidate lists id for id, order included, and after every query the six
+KeyFrame members the queries read and write (tests/kfdb_both.py)."""
 import threading
 
 import numpy as np
 import pytest
 
 import kfdb_reference as kr
+from kfdb_both import Both, with_scoring
 from visual_sgraphs_amd import orb, synth
 
 pytestmark = pytest.mark.gpu
 
 SCORINGS = (kr.L1_NORM, kr.L2_NORM, kr.CHI_SQUARE, kr.BHATTACHARYYA, kr.DOT_PRODUCT)
-
-
-def with_scoring(blob, scoring):
-    """The same vocabulary image with another scoring type (the third int of the header)."""
-    return blob[:8] + struct.pack("<i", scoring) + blob[12:]
 
 
 @pytest.fixture(scope="module")
@@ -68,55 +64,6 @@ def test_score_every_type_bit_identical(voc_blob, descriptors):
     assert ei.value.code == -3
     db.close()
     kl.close()
-
-
-class Both:
-    """The GPU database and the restatement, driven by the same operations."""
-
-    def __init__(self, voc):
-        self.gpu = orb.KeyFrameDatabase(voc)
-        self.ref = kr.KeyFrameDatabase(voc.scoring)
-        self.n_queries = 0
-
-    def add(self, kf, bow, m):
-        self.gpu.add(kf, bow, m)
-        self.ref.add(kf, *bow, m)
-
-    def erase(self, kf):
-        self.gpu.erase(kf)
-        self.ref.erase(kf)
-
-    def clear(self):
-        self.gpu.clear()
-        self.ref.clear()
-
-    def clear_map(self, m):
-        self.gpu.clearMap(m)
-        self.ref.clearMap(m)
-
-    def set_map(self, kfs, maps):
-        self.gpu.set_map(kfs, maps)
-        for k, m in zip(kfs, maps):
-            self.ref.set_map(k, m)
-
-    def set_covisibility(self, neigh):
-        self.gpu.set_covisibility(neigh)
-        for k, n in neigh.items():
-            self.ref.set_covisibility(k, n)
-
-    def reloc(self, qid, bow, m):
-        got = self.gpu.DetectRelocalizationCandidates(qid, bow, m)
-        want = self.ref.DetectRelocalizationCandidates(qid, *bow, m)
-        assert got == want, (qid, got, want)
-        self.n_queries += 1
-        return got
-
-    def nbest(self, qid, bow, conn, m, n, bad=()):
-        got = self.gpu.DetectNBestCandidates(qid, bow, conn, m, n, bad)
-        want = self.ref.DetectNBestCandidates(qid, *bow, conn, m, n, bad)
-        assert got == want, (qid, got, want)
-        self.n_queries += 1
-        return got
 
 
 def window_covisibility(kf, present_ids):
@@ -195,6 +142,7 @@ def test_scripted_database_matches_the_reference(voc_blob, descriptors):
     assert n_reloc >= 40 and n_nbest >= 30
     hits = sum(1 for k in db.ref.kfs.values() if k.mnRelocQuery)
     assert hits > 50
+    assert db.n_states >= 60 * db.n_queries  # the state of every keyframe known, from the first 60 on, after every query
 
 
 def test_stale_score_and_double_add_on_the_device():
@@ -249,7 +197,8 @@ def test_scale_twenty_thousand_keyframes(voc_blob):
     rng = np.random.default_rng(77)
     n = 20000
     bows = zipf_bows(rng, n + 100, 150, voc.nwords)
-    db = Both(voc)
+    # the state of a fixed sample of 300 keyframes is compared after every query
+    db = Both(voc, sample=[int(k) for k in np.random.default_rng(4).choice(n, 300, replace=False) + 1])
     for k in range(n):
         db.add(k + 1, bows[k], k % 4)
     db.set_covisibility({k: [k + d for d in (1, -1, 2, -2, 3) if 0 < k + d <= n] for k in range(1, n + 1, 3)})
@@ -259,6 +208,7 @@ def test_scale_twenty_thousand_keyframes(voc_blob):
         lens.append(len(db.reloc(10 ** 6 + q, b, q % 4)))
         db.nbest(int(rng.integers(1, n + 1)), b, [], q % 4, 3, [3] if q % 5 == 0 else [])
     assert max(lens) > 0
+    assert db.n_states == 100 * 300
 
 
 def test_two_threads_add_while_querying(voc_blob):

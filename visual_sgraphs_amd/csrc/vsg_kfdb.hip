@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/vsg_orb.h"
+#include "../../include/vsg_orb_debug.h"
 #include "vsg_ctx.h"
 #include "vsg_frame_int.h"
 
@@ -737,6 +738,24 @@ int vsg_kfdb_detect_n_best_candidates(vsg_kfdb *db, uint64_t query_kf_id, const 
     added.insert(b);
   }
   *n_loop = (int)nl, *n_merge = (int)nm;
+  return VSG_OK;
+}
+
+// test hook (include/vsg_orb_debug.h): the KfState row of one keyframe, read back after everything enqueued
+int vsg_debug_kfdb_state(vsg_kfdb *db, uint64_t kf_id, uint64_t query[2], int32_t words[2], float score[2]) {
+  if (!db || !query || !words || !score) return VSG_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(db->mu);
+  auto it = db->index.find(kf_id);
+  if (it == db->index.end()) return VSG_ERR_INVALID;
+  int rc = VSG_OK;
+  vsg::ThreadCtx *c = vsg::thread_ctx(db->device, &rc);
+  if (!c) return rc;
+  TRY_HIP(hipStreamSynchronize(c->stream));
+  KfState s;
+  TRY_HIP(hipMemcpy(&s, db->d_st + it->second, sizeof s, hipMemcpyDeviceToHost));
+  query[0] = s.rq, query[1] = s.pq;
+  words[0] = s.rw, words[1] = s.pw;
+  score[0] = s.rs, score[1] = s.ps;
   return VSG_OK;
 }
 

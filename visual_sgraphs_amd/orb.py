@@ -93,6 +93,8 @@ EXPORTS = [
     "vsg_frame_optimize_sim3",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
+    # test hook: the query state of one keyframe of the resident KeyFrameDatabase
+    "vsg_debug_kfdb_state",
     # k_fast_cells' launch form: automatic / general
     "vsg_orb_set_fast_form",
 ]
@@ -457,6 +459,7 @@ def load_library():
     L.vsg_kfdb_detect_relocalization_candidates.argtypes = [vp, u64, _i32p, _f64p, ci, i32, _u64p, ci, _i32p]
     L.vsg_kfdb_detect_n_best_candidates.argtypes = [vp, u64, _i32p, _f64p, ci, _u64p, ci, i32, _i32p, ci, ci, _u64p,
                                                     _i32p, _u64p, _i32p]
+    L.vsg_debug_kfdb_state.argtypes = [vp, u64, _u64p, _i32p, _f32p]
     _lib = L
     return L
 
@@ -1119,6 +1122,15 @@ class KeyFrameDatabase:
                                                          _p(lo, u64p), C.byref(nl), _p(me, u64p), C.byref(nm)),
                "vsg_kfdb_detect_n_best_candidates")
         return [int(x) for x in lo[:nl.value]], [int(x) for x in me[:nm.value]]
+
+    def debug_state(self, kf_id):
+        """Test hook (include/vsg_orb_debug.h): the six query-state members of keyframe `kf_id` as the device holds
+        them: (mnRelocQuery, mnRelocWords, mRelocScore, mnPlaceRecognitionQuery, mnPlaceRecognitionWords,
+        mPlaceRecognitionScore), the scores as np.float32.  An id the database never saw raises VSG_ERR_INVALID."""
+        q, w, s = (C.c_uint64 * 2)(), (C.c_int32 * 2)(), (C.c_float * 2)()
+        _check(self._L.vsg_debug_kfdb_state(self._h, int(kf_id), q, w, s), "vsg_debug_kfdb_state")
+        sc = np.frombuffer(s, np.float32)
+        return int(q[0]), int(w[0]), sc[0], int(q[1]), int(w[1]), sc[1]
 
 
 REFRESH_DESC, REFRESH_NORMAL = 1, 2  # include/vsg_orb.h VSG_REFRESH_*
