@@ -78,11 +78,50 @@ struct CellDesc {  // one FAST cell: valid region [x0,x1) x [y0,y1) in level coo
 
 // Fused pyramid: one workgroup computes, for one tile of the TOP level, the regions of every lower level that
 // feed it ("need"), and writes the part of each level it owns ("own").  Rects are {x0, y0, x1, y1}, x1/y1 exclusive.
+// Everything k_pyramid's per-level set-up reads about one (tile, level), 32 bytes = ONE scalar load: the two rects, the
+// level's place in a frame's pyramid block (LevelGeom::pitch / img_off) and the thread split of the row loop, which is a
+// constant of the (tile, level) -- threads = nrg row groups x ncg column groups of 4 columns, `chunk` rows per row group.
+struct alignas(32) PyrTileLevel {
+  int16_t need[4], own[4];
+  int32_t pitch, img_off;
+  int16_t ncg, nrg, chunk;  // ncg = LDS pitch / 4, nrg = kPyrThreads / ncg, chunk = ceil(needed rows / nrg)
+  int16_t tab;              // first x entry of the level in the tile's table slice (its y entries follow)
+};
+static_assert(sizeof(PyrTileLevel) == 32, "k_pyramid loads a level record as 8 dwords");
 struct PyrTile {
-  int16_t need[kMaxLevels][4];
-  int16_t own[kMaxLevels][4];
+  PyrTileLevel lv[kMaxLevels];
   int32_t tab_off, tab_n;  // this tile's slice of Geometry::pyrTileTab
 };
+constexpr int kPyrThreads = 256;  // threads per pyramid tile (512: 0.196 -> 0.203 ms, 1024: 0.31 ms per 256 C2 frames)
+
+// The row loop of k_pyramid stores a level to HBM as aligned dwords: the 4-column groups that lie wholly inside the
+// tile's owned columns [ox0, ox1), which are the aligned groups in [a0, a1).  The owned columns in no such group -- at
+// most 3 on each side; the level's right edge is one when w % 4 != 0 -- are the tile's SEAM columns, stored byte by byte
+// in a pass of their own: column j < nl is ox0 + j, column nl <= j < n is a1 + (j - nl).
+struct PyrSeam {
+  int a0, a1, nl, n;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+    inline PyrSeam
+    pyr_seam(int ox0, int ox1) {
+  const int a0 = (ox0 + 3) & ~3, a1 = ox1 & ~3, w = ox1 > ox0 ? ox1 - ox0 : 0;
+  const bool none = a1 < a0;  // no whole group: every owned column (<= 3) is a seam column
+  PyrSeam S;
+  S.a0 = none ? a1 : a0;
+  S.a1 = a1;
+  S.nl = none ? w : a0 - ox0;
+  S.n = none ? w : S.nl + (ox1 - a1);
+  return S;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+    inline int
+    pyr_seam_column(const PyrSeam &S, int ox0, int j) {
+  return j < S.nl ? ox0 + j : S.a1 + (j - S.nl);
+}
 // Candidate top-level tile edges of the fused pyramid.  A larger tile recomputes less halo but needs more LDS and
 // yields fewer workgroups: 36 is ahead for >= ~2000 workgroups per launch (0.214 -> 0.194 ms per 256 C2 frames),
 // 32 for small batches and for geometries whose 36-tiling would not leave three workgroups per CU.
@@ -330,17 +369,18 @@ inline int build_geometry(Geometry &G, const ExtractorTables &T, int rows, int c
       for (int tx = 0; tx < ntx; tx++) {
         PyrTile t;
         memset(&t, 0, sizeof(t));
-        int16_t *o = t.own[top];
+        int16_t need[kMaxLevels][4] = {}, own[kMaxLevels][4] = {};
+        int16_t *o = own[top];
         o[0] = (int16_t)((long long)tx * tw / ntx);
         o[1] = (int16_t)((long long)ty * thh / nty);
         o[2] = (int16_t)((long long)(tx + 1) * tw / ntx);
         o[3] = (int16_t)((long long)(ty + 1) * thh / nty);
-        memcpy(t.need[top], o, sizeof(t.need[top]));
+        memcpy(need[top], o, sizeof(need[top]));
         for (int l = top; l >= 1; l--) {
           const LevelGeom &D = fg.lv[l], &S = fg.lv[l - 1];
           const Short4 *tabx = &G.resizeTab[D.tab_x_off], *taby = &G.resizeTab[D.tab_y_off];
-          const int16_t *od = t.own[l], *nd = t.need[l];
-          int16_t *os = t.own[l - 1], *ns = t.need[l - 1];
+          const int16_t *od = own[l], *nd = need[l];
+          int16_t *os = own[l - 1], *ns = need[l - 1];
           // ownership boundaries follow the (monotone) source index of the destination boundary
           os[0] = (int16_t)(tx == 0 ? 0 : tabx[od[0]].a);
           os[2] = (int16_t)(tx + 1 == ntx ? S.w : tabx[od[2]].a);
@@ -354,21 +394,21 @@ inline int build_geometry(Geometry &G, const ExtractorTables &T, int rows, int c
           ns[3] = (int16_t)(ny1 > os[3] ? ny1 : os[3]);
         }
         int tabn = 0;
-        for (int l = 1; l <= top; l++) tabn += (t.need[l][2] - t.need[l][0]) + (t.need[l][3] - t.need[l][1]);
+        for (int l = 1; l <= top; l++) tabn += (need[l][2] - need[l][0]) + (need[l][3] - need[l][1]);
         if (tabn > PT.tabMax) PT.tabMax = tabn;
         t.tab_off = (int32_t)PT.tab.size();
         t.tab_n = tabn;
         for (int l = 1; l <= top; l++) {
           const LevelGeom &D = fg.lv[l];
-          const int sx0a = t.need[l - 1][0] & ~3, sy0 = t.need[l - 1][1];
-          const int spitch = ((t.need[l - 1][2] - sx0a) + 3) & ~3;
-          for (int x = t.need[l][0]; x < t.need[l][2]; x++) {
+          const int sx0a = need[l - 1][0] & ~3, sy0 = need[l - 1][1];
+          const int spitch = ((need[l - 1][2] - sx0a) + 3) & ~3;
+          for (int x = need[l][0]; x < need[l][2]; x++) {
             Short4 e = G.resizeTab[D.tab_x_off + x];
             e.a = (int16_t)(e.a - sx0a);
             e.d = (int16_t)(e.d - sx0a);
             PT.tab.push_back(e);
           }
-          for (int y = t.need[l][1]; y < t.need[l][3]; y++) {
+          for (int y = need[l][1]; y < need[l][3]; y++) {
             Short4 e = G.resizeTab[D.tab_y_off + y];
             if ((e.b - sy0) * spitch > 32767) PT.ok = false;  // LDS row offsets are kept in 16 bits
             e.a = (int16_t)((e.a - sy0) * spitch);
@@ -376,16 +416,35 @@ inline int build_geometry(Geometry &G, const ExtractorTables &T, int rows, int c
             PT.tab.push_back(e);
           }
         }
-        for (int l = 0; l <= top; l++) {
+        if (tabn > 32767) PT.ok = false;  // PyrTileLevel::tab
+        for (int l = 0, tab = 0; l <= top; l++) {
           // LDS image of a level: columns start at the 4-byte aligned column below need.x0, pitch multiple of 4
-          const int x0a = t.need[l][0] & ~3;
-          const int pitch = ((t.need[l][2] - x0a) + 3) & ~3;
-          const int bytes = pitch * (t.need[l][3] - t.need[l][1]);
+          const int x0a = need[l][0] & ~3;
+          const int pitch = ((need[l][2] - x0a) + 3) & ~3;
+          const int bytes = pitch * (need[l][3] - need[l][1]);
           if (l & 1) {
             if (bytes > PT.ldsB) PT.ldsB = bytes;
           } else {
             if (bytes > PT.ldsA) PT.ldsA = bytes;
           }
+          PyrTileLevel &R = t.lv[l];
+          memcpy(R.need, need[l], sizeof(R.need));
+          memcpy(R.own, own[l], sizeof(R.own));
+          R.pitch = fg.lv[l].pitch;
+          R.img_off = fg.lv[l].img_off;
+          // the row loop's thread split (level 0 is staged, not produced: the fields stay 0)
+          if (l == 0) continue;
+          const int ncg = pitch >> 2, dh = need[l][3] - need[l][1];
+          if (ncg < 1 || ncg > kPyrThreads) {  // an LDS image wider than one column group per thread
+            PT.ok = false;
+            continue;
+          }
+          const int nrg = kPyrThreads / ncg;
+          R.ncg = (int16_t)ncg;
+          R.nrg = (int16_t)nrg;
+          R.chunk = (int16_t)((dh + nrg - 1) / nrg);
+          R.tab = (int16_t)tab;
+          tab += (need[l][2] - need[l][0]) + dh;
         }
         PT.tiles.push_back(t);
       }

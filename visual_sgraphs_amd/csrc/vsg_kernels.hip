@@ -100,8 +100,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 // ORBextractor.cc:1184), writing to HBM only the part of each level it owns.  Ownership boundaries are the source
 // indices of the destination boundaries, so tiles partition every level without gaps or overlaps; the ~25 % halo
 // is recomputed instead of communicated.  HBM traffic: level 0 read once (+halo), levels 1.. written once.
-constexpr int kPyrThreads = 256;  // threads per pyramid tile (512: 0.196 -> 0.203 ms, 1024: 0.31 ms per 256 C2 frames)
-
 __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ pyr, const FrameGeom *__restrict__ fg,
                                                  const Short4 *__restrict__ tile_tab, Src0 s0,
                                                  const PyrTile *__restrict__ tiles, int ldsA, int ldsAB,
@@ -113,6 +111,9 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
   // the per-level FAST candidate counters of this frame start the call at zero (k_fast_cells adds to them after this
   // kernel): one workgroup per frame clears them here instead of a launch of its own
   if (cand_count && blk.x == 0 && tid < kMaxLevels) cand_count[frame * kMaxLevels + tid] = 0;
+  // read once, ahead of the staging round: the level loop re-loads nothing of the frame geometry
+  const int nlevels = fg->nlevels;
+  uint8_t *frame_base = pyr + (size_t)frame * fg->pyr_frame_bytes;
   uint8_t *buf0 = pyr_lds, *buf1 = pyr_lds + ldsA;
   Short4 *s_tab = (Short4 *)(pyr_lds + ldsAB);  // the tile's slices of the resize tables, all levels
   // One round of independent global loads: the tile's (pre-rebased, contiguous) table slice and the level-0 region.
@@ -126,8 +127,9 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
     Short4 tv[kTabAhead];
 #pragma unroll
     for (int k = 0; k < kTabAhead; k++) tv[k] = tt[min(tid + k * kPyrThreads, tab_n - 1)];
-    const int x0a = T.need[0][0] & ~3, y0 = T.need[0][1];
-    const int w4 = ((T.need[0][2] - x0a) + 3) >> 2, hh = T.need[0][3] - y0, pitch = 4 * w4;
+    const int16_t *need0 = T.lv[0].need;
+    const int x0a = need0[0] & ~3, y0 = need0[1];
+    const int w4 = ((need0[2] - x0a) + 3) >> 2, hh = need0[3] - y0, pitch = 4 * w4;
     const uint8_t *src = s0.base + (size_t)frame * s0.frame_stride + (size_t)y0 * s0.pitch + x0a;
     if (w4 < 4) {
       const float inv = __builtin_amdgcn_rcpf((float)w4);
@@ -169,16 +171,27 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
     for (int i = tid + kTabAhead * kPyrThreads; i < tab_n; i += kPyrThreads) s_tab[i] = tt[i];
   }
   __syncthreads();
-  uint8_t *frame_base = pyr + (size_t)frame * fg->pyr_frame_bytes;
-  int toff = 0;
-  for (int l = 1; l < fg->nlevels; l++) {
-    const LevelGeom &D = fg->lv[l];
+  for (int l = 1; l < nlevels; l++) {
+    // everything the set-up needs to know about the (tile, level) comes in ONE 32-byte scalar load (the rects, the level's
+    // pitch and offset and the thread split used to be four dependent trips, each waited for by every wave right after
+    // the barrier)
+    typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+    u32x8 rw = *(const u32x8 *)&T.lv[l];
+    asm volatile("" : "+s"(rw));  // all eight dwords at one point: the load is not split around the first use
+    const PyrTileLevel R = __builtin_bit_cast(PyrTileLevel, rw);
     const uint8_t *src = (l & 1) ? buf0 : buf1;
     uint8_t *dst = (l & 1) ? buf1 : buf0;
-    const int dx0 = T.need[l][0], dy0 = T.need[l][1], dw = T.need[l][2] - dx0, dh = T.need[l][3] - dy0;
-    const int dx0a = dx0 & ~3, dpitch = ((T.need[l][2] - dx0a) + 3) & ~3;
-    const Short4 *txv = &s_tab[toff], *tyv = &s_tab[toff + dw];
-    toff += dw + dh;
+    const int dx0 = R.need[0], dy0 = R.need[1], dw = R.need[2] - dx0, dh = R.need[3] - dy0;
+    const int dx0a = dx0 & ~3, ncg = R.ncg, dpitch = 4 * ncg;  // column groups (<= 64 in practice, <= kPyrThreads)
+    const Short4 *txv = &s_tab[R.tab], *tyv = txv + dw;
+    // ownership: the rows through a buffer descriptor that covers exactly the owned rows of the level, the columns as the
+    // aligned groups [S.a0, S.a1) of the row loop plus the seam columns of the pass after the barrier
+    const int ox0 = R.own[0], oy0 = R.own[1], ox1 = R.own[2], oy1 = R.own[3];
+    const PyrSeam S = pyr_seam(ox0, ox1);
+    const uint32_t gpitch = (uint32_t)R.pitch;
+    const int own_rows = max(oy1 - oy0, 0);
+    const __amdgpu_buffer_rsrc_t own_img = __builtin_amdgcn_make_buffer_rsrc(
+        frame_base + R.img_off + (size_t)oy0 * gpitch, 0, own_rows * (int)gpitch, 0x00020000);
     // Thread = 4 adjacent destination columns (one aligned dword of the LDS image and of the level in HBM)
     // walking DOWN a chunk of rows.
     //  * a source row is fetched as 12 aligned bytes, shifted to start at the first source column, and the
@@ -193,23 +206,33 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
     //  * the dword goes to the LDS image (source of the next level) and, where this tile OWNS it, straight to HBM.
     // threads = row groups x column groups with the EXACT column-group count (a power-of-two split left 13-44 % of
     // the lanes idle on most levels: 78 % -> 97 % busy lanes over the chain)
-    const int ncg = dpitch >> 2;  // column groups (<= 64)
-    const int nrg = kPyrThreads / ncg;
+    // The split itself (nrg = kPyrThreads / ncg row groups of `chunk` = ceil(dh / nrg) rows) is a constant of the (tile,
+    // level): build_geometry carries it in the record, no division is emulated here.
+    const int nrg = R.nrg, chunk = R.chunk;
     const int rg = div_small(tid, __builtin_amdgcn_rcpf((float)ncg)), cg = tid - rg * ncg;
-    const int chunk = (dh + nrg - 1) / nrg, ya = rg * chunk, yb = min(dh, ya + chunk);
+    const int ya = rg * chunk, yb = min(dh, ya + chunk);
     if (rg < nrg && ya < yb) {
       uint32_t sel[4];
       u16x2 wgt[4];
       int o = 0;
+      // The four x entries and the first y entry are requested as one group and waited for once.  Each is a whole 8-byte
+      // entry in ONE aligned LDS read: left alone the compiler fetches the three fields it needs as ds_read_i16 +
+      // ds_read_b32 at offset 2 -- a mis-aligned dword read, which the LDS serves one lane at a time (64 cycles,
+      // profiles/r03_g_ubench_lds_rates.txt); the empty asm makes it need all 64 bits of all of them at one point.
+      // (A y entry is described at the row loop below.)
+      const uint2 *typ = (const uint2 *)(tyv + ya);
+      uint2 tw[4], e0 = typ[0];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int ci = min(max(4 * cg + k - (dx0 - dx0a), 0), dw - 1);  // columns outside the needed range: any value
-        // the whole 8-byte entry in ONE aligned LDS read: left alone the compiler fetches the three fields it needs as
-        // ds_read_i16 + ds_read_b32 at offset 2 -- a mis-aligned dword read, which the LDS serves one lane at a time
-        // (64 cycles, profiles/r03_g_ubench_lds_rates.txt); the empty asm makes it need all 64 bits
-        uint2 tw = *(const uint2 *)&txv[ci];
-        asm volatile("" : "+v"(tw.x), "+v"(tw.y));
-        const Short4 tx = {(int16_t)(tw.x & 0xFFFFu), (int16_t)(tw.x >> 16), (int16_t)(tw.y & 0xFFFFu), 0};
+        tw[k] = *(const uint2 *)&txv[ci];
+      }
+      asm volatile(""
+                   : "+v"(tw[0].x), "+v"(tw[0].y), "+v"(tw[1].x), "+v"(tw[1].y), "+v"(tw[2].x), "+v"(tw[2].y), "+v"(tw[3].x),
+                     "+v"(tw[3].y), "+v"(e0.x), "+v"(e0.y));
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const Short4 tx = {(int16_t)(tw[k].x & 0xFFFFu), (int16_t)(tw[k].x >> 16), (int16_t)(tw[k].y & 0xFFFFu), 0};
         if (k == 0) o = tx.a;
         const uint32_t f = (uint32_t)(tx.a - o);  // 0..6 (vsg_geometry.h checks the span)
         sel[k] = 0x0Cu | (f << 8) | (0x0Cu << 16) | ((f + 1) << 24);
@@ -227,10 +250,10 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
           H[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(B, A, sel[k])), wgt[k], 0u, false);
         }
       };
-      // ownership of this column group: all 4 bytes, some (a seam between tiles), or none
+      // this lane stores its dword to HBM if the tile owns all 4 columns of the group (the columns of a group owned in
+      // part go out with the seam pass below)
       const int gx = dx0a + 4 * cg;  // level column of byte 0
-      const int ox0 = T.own[l][0], oy0 = T.own[l][1], ox1 = T.own[l][2], oy1 = T.own[l][3];
-      const bool full = gx >= ox0 && gx + 4 <= ox1, part = !full && gx < ox1 && gx + 4 > ox0;
+      const bool full = gx >= S.a0 && gx < S.a1;
       // Two destination rows per trip with the roles of the two horizontal-sum sets swapped (the lower source row of one
       // destination row is the upper one of the next 5 times out of 6: no register copies), the next row's table entry
       // requested before the current row is worked on, and the lower row's sums formed unconditionally (where the
@@ -240,16 +263,14 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
       // rows left count down, and the ROW ownership test is the range check of a buffer descriptor that covers exactly
       // the owned rows of the level -- a store to a row above or below them has an offset outside [0, num_records) (a
       // negative one wraps to a large unsigned one) and is dropped by the address unit.  (Rows the tile does not own hold
-      // the bytes their owner writes, so the check only saves the traffic.)
+      // the bytes their owner writes, so the check only saves the traffic.)  The COLUMN ownership test is the same check:
+      // a lane that does not store carries an offset of 3 << 30, which the row bumps (< 2^24 in all) leave far outside any
+      // image, so every lane issues the one store of its row and nothing branches or masks lanes around it.
       uint32_t HA[4] = {0, 0, 0, 0}, HB[4];
       typedef __attribute__((address_space(3))) uint32_t lds_u32;
       uint32_t doff = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)dst +
                       (uint32_t)(ya * dpitch + 4 * cg);  // LDS address of this row's dword
-      const uint32_t gpitch = (uint32_t)D.pitch;
-      const int own_rows = max(oy1 - oy0, 0);
-      const __amdgpu_buffer_rsrc_t own_img = __builtin_amdgcn_make_buffer_rsrc(
-          frame_base + D.img_off + (size_t)oy0 * gpitch, 0, own_rows * (int)gpitch, 0x00020000);
-      uint32_t goff = (uint32_t)((dy0 + ya - oy0) * (int)gpitch + gx);  // offset in the owned rows' image
+      uint32_t goff = full ? (uint32_t)((dy0 + ya - oy0) * (int)gpitch + gx) : 0xC0000000u;  // offset in the owned rows' image
       // Vertical pass of one destination row from the horizontal sums of its two source rows (H = S >> 4, the high halves):
       //   v = (((b0 * H0) >> 16) + ((b1 * H1) >> 16) + 2) >> 2            ([OCV] resize.cpp, VResizeLinear 8U)
       // The two products are truncated SEPARATELY.  With P0 = b0 * H0 + (2 << 16) and its low 16 bits cleared,
@@ -271,14 +292,7 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
         const uint32_t t = __builtin_amdgcn_perm(Q[2], Q[0], 0x07060302u), u = __builtin_amdgcn_perm(Q[3], Q[1], 0x07060302u);
         const uint32_t out = __builtin_amdgcn_perm(u >> 2, t >> 2, 0x06020400u);
         *(lds_u32 *)(uintptr_t)doff = out;
-        if (full) {
-          __builtin_amdgcn_raw_buffer_store_b32(out, own_img, (int)goff, 0, 0);
-        } else if (part) {
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            if (gx + j >= ox0 && gx + j < ox1)
-              __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(out >> (8 * j)), own_img, (int)goff + j, 0, 0);
-        }
+        __builtin_amdgcn_raw_buffer_store_b32(out, own_img, (int)goff, 0, 0);
         doff += (uint32_t)dpitch;
         goff += gpitch;
         asm volatile("" : "+v"(doff), "+v"(goff));
@@ -287,8 +301,6 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
       // are cached (in the set that is "upper" next) is the high half of the previous entry's first word.
       // (the entry after a chunk's last row is read and not used: within the table, or the one entry of padding the
       // launch allocates after it)
-      const uint2 *typ = (const uint2 *)(tyv + ya);
-      uint2 e0 = typ[0];
       uint2 e1 = {0xFFFFFFFFu, 0};  // no row offset is 0xFFFF
       for (int n = yb - ya;; typ += 2) {
         const bool up0 = (e0.x & 0xFFFFu) != (e1.x >> 16);
@@ -307,6 +319,19 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t *__restrict__ p
       }
     }
     __syncthreads();
+    // Seam pass: the level's LDS image is complete now and nobody writes it before the barrier that closes level l + 1
+    // (which reads it, like this pass), so the owned columns that lie in no fully owned group -- at most 3 on each side of
+    // the tile, the level's right edge among them when w % 4 != 0 -- go to HBM from there, lane -> (owned row, seam
+    // column), one byte each, through the same descriptor.  No barrier of its own.
+    {
+      const int n = S.n * own_rows;
+      const float inv = __builtin_amdgcn_rcpf((float)S.n);
+      const int row0 = oy0 - dy0;  // the first owned row in the LDS image, whose columns start at dx0a
+      for (int i = tid; i < n; i += kPyrThreads) {
+        const int r = div_small(i, inv), x = pyr_seam_column(S, ox0, i - r * S.n);
+        __builtin_amdgcn_raw_buffer_store_b8(dst[(row0 + r) * dpitch + (x - dx0a)], own_img, (int)(r * gpitch + x), 0, 0);
+      }
+    }
   }
 }
 
