@@ -111,7 +111,13 @@ int vsg_orb_extract_batch_device(vsg_orb *h, const uint8_t *d_gray, int nframes,
  * COLOR_{RGB,BGR,RGBA,BGRA}2GRAY) before building the Frame (Tracking.cc:1526-1551, 1595-1608, 1643-1656).  This
  * entry takes the interleaved 8-bit colour frames (channels = 3 or 4; rgb_order != 0 for RGB(A), 0 for BGR(A) =
  * Tracking::mbRGB) on the device and fuses the conversion into the level-0 staging.  Coefficients are data
- * (default = OpenCV 4.2: R2Y 4899, G2Y 9617, B2Y 1868, shift 14); they must sum to 1 << shift. */
+ * (default = OpenCV 4.2: R2Y 4899, G2Y 9617, B2Y 1868, shift 14); they must sum to 1 << shift, 1 <= shift <= 20.
+ * vsg_orb_set_gray_coeffs stores the table in the handle: it applies to every later call of both colour entries on that
+ * handle, image-size changes included, until it is set again; a refused table (VSG_ERR_INVALID) leaves the previous one
+ * in force.
+ * Layout: frame i starts at img + i*frame_stride, a row is `stride` bytes apart from the next and holds cols * channels
+ * bytes.  stride < cols * channels is refused with VSG_ERR_INVALID before any copy or launch; apart from that, base,
+ * stride and frame_stride need no alignment (pad bytes are never read). */
 int vsg_orb_set_gray_coeffs(vsg_orb *h, const int coeffs[3], int shift);
 int vsg_orb_extract_batch_device_color(vsg_orb *h, const uint8_t *d_img, int channels, int rgb_order, int nframes,
                                        size_t frame_stride, int rows, int cols, int stride, int lap0, int lap1,

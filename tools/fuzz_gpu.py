@@ -110,14 +110,62 @@ def case_batch_big(rng):
 
 def case_colour(rng):
     w, h, nf, sc, nl, ini, mn = geometry(rng)
+    """The colour entries through the C ABI with a random layout: host or device entry, 1..4 distinct frames, row and frame
+    padding, an unaligned base, channels of their own gain and offset over the full range (alpha uniform).  Level 0 of every
+    frame and the extractor's output against the oracle's conversion and extraction."""
+    import ctypes as C
     ch, rgb = int(rng.choice([3, 4])), bool(rng.integers(0, 2))
-    base = synth.frame(w, h, int(rng.integers(0, 1 << 20)))
-    col = np.stack([np.clip(base.astype(np.int32) + rng.integers(-25, 26, base.shape), 0, 255).astype(np.uint8)
-                    for _ in range(ch)], axis=-1)
-    gray = ol.cvt_gray(col, rgb)
-    ex = orb.ORBextractor(nf, sc, nl, ini, mn, max_batch=1)
-    got = ex.extract_batch_color(col[None], rgb)[0]
-    return same(got, ol.OracleExtractor(nf, sc, nl, ini, mn)(gray)), ("colour", w, h, nf, sc, nl, ini, mn, ch, rgb)
+    device, B = bool(rng.integers(0, 2)), int(rng.integers(1, 5))
+    col = np.empty((B, h, w, ch), np.uint8)
+    for f in range(B):
+        base = synth.frame(w, h, int(rng.integers(0, 1 << 20))).astype(np.int32)
+        for c in range(3):  # gain in [-1, 1] quarters, an offset that keeps the full range reachable, +-8 of noise
+            gain = int(rng.choice([-4, -3, -2, 2, 3, 4]))
+            off = int(rng.integers(0, 256 - 64 * abs(gain) + 1)) + (255 * abs(gain) // 4 if gain < 0 else 0)
+            col[f, ..., c] = np.clip(off + gain * base // 4 + rng.integers(-8, 9, base.shape), 0, 255)
+        if ch == 4:
+            col[f, ..., 3] = rng.integers(0, 256, (h, w))
+    row = w * ch
+    stride, offset = row + int(rng.integers(0, 9)), int(rng.integers(0, 4))
+    fs = h * stride + int(rng.integers(0, 17))
+    raw = np.full(offset + B * fs + 16, int(rng.integers(0, 256)), np.uint8)
+    np.lib.stride_tricks.as_strided(raw[offset:], (B, h, row), (fs, stride, 1))[:] = col.reshape(B, h, row)
+    ex = orb.ORBextractor(nf, sc, nl, ini, mn, max_batch=4)
+    cap = ex.capacity(h, w)
+    L = orb.load_library()
+    if device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_raw = torch.from_numpy(raw).to(dev)
+        d_kps = torch.zeros((B, cap, 28), dtype=torch.uint8, device=dev)
+        d_desc = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+        st = torch.cuda.Stream(device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(st):
+            ex.extract_batch_device_color(d_raw.data_ptr() + offset, ch, rgb, B, fs, h, w, stride, d_kps.data_ptr(),
+                                          d_desc.data_ptr(), d_counts.data_ptr(), cap, (0, 0), st.cuda_stream)
+        st.synchronize()
+        counts, kps, desc = d_counts.cpu().numpy(), d_kps.cpu().numpy().view(orb.KP_DTYPE).reshape(B, cap), d_desc.cpu().numpy()
+    else:
+        counts, kps, desc = np.zeros((B, 2), np.int32), np.zeros((B, cap), orb.KP_DTYPE), np.zeros((B, cap, 32), np.uint8)
+        n, mono = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        rc = L.vsg_orb_extract_batch_color(ex.handle, C.cast(raw.ctypes.data + offset, u8p), ch, int(rgb), B, fs, h, w, stride,
+                                           0, 0, kps.ctypes.data_as(C.c_void_p), desc.ctypes.data_as(u8p), cap,
+                                           n.ctypes.data_as(i32p), mono.ctypes.data_as(i32p))
+        if rc < 0:
+            raise orb.VsgError(rc, "vsg_orb_extract_batch_color", L.vsg_last_error().decode(errors="replace"))
+        counts[:, 0], counts[:, 1] = n, mono
+    ok = True
+    ref = ol.OracleExtractor(nf, sc, nl, ini, mn)
+    for f in range(B):
+        gray = ol.cvt_gray(col[f], rgb)
+        k = int(counts[f, 0])
+        got = (int(counts[f, 1]), kps[f, :k], desc[f, :k])
+        ok = ok and np.array_equal(ex.image_pyramid(0, frame=f), gray) and same(got, ref(gray))
+    return ok, ("colour", w, h, nf, sc, nl, ini, mn, ch, rgb, "device" if device else "host", B, stride - row, fs - h * stride,
+                offset)
 
 
 def case_best2(rng):

@@ -904,6 +904,14 @@ int vsg_orb_set_gray_coeffs(vsg_orb *h, const int coeffs[3], int shift) {
   return VSG_OK;
 }
 
+// a row of a colour frame holds cols * channels bytes: a smaller stride would make rows overlap (the device entry) or
+// fail inside the 2-D upload (the host entry), so both refuse it before any copy or launch
+static bool color_stride_ok(int cols, int channels, int stride) {
+  if ((long long)stride >= (long long)cols * channels) return true;
+  set_err("stride is smaller than cols * channels bytes");
+  return false;
+}
+
 int vsg_orb_extract_batch_device_color(vsg_orb *h, const uint8_t *d_img, int channels, int rgb_order, int nframes,
                                        size_t frame_stride, int rows, int cols, int stride, int lap0, int lap1,
                                        vsg_keypoint *d_kps, uint8_t *d_desc, int *d_counts, int capacity,
@@ -911,6 +919,7 @@ int vsg_orb_extract_batch_device_color(vsg_orb *h, const uint8_t *d_img, int cha
   if (!h || !d_kps || !d_desc || !d_counts || nframes < 1 || nframes > h->max_batch) return VSG_ERR_INVALID;
   if (channels != 3 && channels != 4) return VSG_ERR_INVALID;
   if (!d_img || rows <= 0 || cols <= 0) return VSG_ERR_EMPTY_IMAGE;
+  if (!color_stride_ok(cols, channels, stride)) return VSG_ERR_INVALID;
   HIP_TRY(hipSetDevice(h->device));
   int rc = ensure_geometry(h, rows, cols);
   if (rc != VSG_OK) return rc;
@@ -1179,6 +1188,7 @@ int vsg_orb_extract_batch_color(vsg_orb *h, const uint8_t *img, int channels, in
   if (!h || nframes < 1 || nframes > h->max_batch || !n || !mono_index) return VSG_ERR_INVALID;
   if (channels != 3 && channels != 4) return VSG_ERR_INVALID;
   if (!img || rows <= 0 || cols <= 0) return VSG_ERR_EMPTY_IMAGE;
+  if (!color_stride_ok(cols, channels, stride)) return VSG_ERR_INVALID;
   HIP_TRY(hipSetDevice(h->device));
   int rc = ensure_geometry(h, rows, cols);
   if (rc != VSG_OK) return rc;
