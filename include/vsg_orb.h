@@ -184,8 +184,23 @@ int vsg_hamming_pairs(int device, const uint8_t *a, int na, const uint8_t *b, in
  * Ties resolve to the lowest B index (strict '<' scan).  Host pointers. */
 int vsg_hamming_block_best2(int device, const uint8_t *a, int na, const uint8_t *b, int nb, int32_t *best,
                             int32_t *second, int32_t *argbest);
-/* Same on device pointers, batched over `nblocks` independent (A_i, B_i) blocks laid out with fixed
- * strides (rows per block: na[i], nb[i] from d_counts[i*count_stride]); asynchronous on `stream`. */
+/* Same on device pointers, batched over `nblocks` independent (A_i, B_i) blocks laid out with fixed strides: block i has
+ * its rows at d_a + i * block_stride_bytes and d_b + i * block_stride_bytes (0: every block reads the same rows; d_a == d_b
+ * and d_b = d_a - block_stride_bytes, "block i against block i - 1", are fine: nothing is written there).  Rows need 4-byte
+ * alignment: d_a, d_b and block_stride_bytes are multiples of 4.
+ * Counts: na[i] = d_counts_a[i * count_stride], nb[i] = d_counts_b[i * count_stride] (int32 on the device, read when the
+ * kernel runs), each clamped to [0, max_rows]: a negative count is an empty side, a count above max_rows is max_rows.  A NULL
+ * count pointer means max_rows rows on that side in every block.  Rows at or past the clamped count are never read as
+ * data, whatever they hold (stale descriptors of an earlier, larger frame do not take part); each block must still have
+ * its row 0 readable on both sides, also where its count is 0.
+ * Outputs are [nblocks][max_rows] int32: row q < na[i] of block i goes to index i * max_rows + q; rows at or past the clamped
+ * na[i] are NOT written and keep what they held.  Ties go to the lowest B index, `second` counts duplicates (two rows at
+ * the best distance: second == best), and a query with no train row (nb[i] == 0, or every row at distance 256) gets
+ * best = second = 256, argbest = -1.
+ * Refused before anything is enqueued: a NULL d_a, d_b or output, nblocks < 1, max_rows < 1 (VSG_ERR_INVALID);
+ * max_rows > 2^20 (the row index has 20 bits of the packed key) or nblocks > 65535 (VSG_ERR_UNSUPPORTED).
+ * Asynchronous on `stream` (NULL: the NULL stream): the call returns once the kernel is enqueued; the inputs, the counts
+ * and the outputs belong to it until the caller has synchronised with `stream`. */
 int vsg_hamming_block_best2_device(int device, const uint8_t *d_a, const uint8_t *d_b, size_t block_stride_bytes,
                                    const int32_t *d_counts_a, const int32_t *d_counts_b, int count_stride,
                                    int nblocks, int max_rows, int32_t *d_best, int32_t *d_second,

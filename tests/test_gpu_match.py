@@ -460,7 +460,7 @@ def test_search_for_triangulation(frames, seed, n_nodes, p_ok, ori):
 
 
 def test_block_best2_tile_boundaries_of_the_mfma_kernel():
-    """The matrix-core matcher works on 32-row train tiles, 32-query column blocks, 128-query workgroups and an
+    """The matrix-core matcher works on 32-row train tiles, 32-query column blocks, 256-query workgroups and an
     8-tile prefetch group: sizes on and around every one of those boundaries, tie-heavy data."""
     rng = np.random.default_rng(5)
     m = orb.ORBmatcher()

@@ -123,8 +123,10 @@ __global__ __launch_bounds__(256) void k_block_best2_mfma(const uint8_t *a_base,
     lut[threadIdx.x] = 0xAAAAAAAAu ^ m;  // bit set -> 0x2 (+1), bit clear -> 0xA (-1)
   }
   const int blk = blockIdx.y;
-  const int na = counts_a ? min(counts_a[blk * count_stride], max_rows) : fixed_na;
-  const int nb = counts_b ? min(counts_b[blk * count_stride], max_rows) : fixed_nb;
+  // counts clamp to [0, max_rows].  A negative na has to become 0 HERE: the early return below compares unsigned, so a
+  // block with na = -1 would not leave and would scan all of B for rows it never writes
+  const int na = counts_a ? min(max(counts_a[blk * count_stride], 0), max_rows) : fixed_na;
+  const int nb = counts_b ? min(max(counts_b[blk * count_stride], 0), max_rows) : fixed_nb;
   const uint8_t *A = a_base + (size_t)blk * block_stride, *B = b_base + (size_t)blk * block_stride;
   if (blockIdx.x * kBest2Rows >= na) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
@@ -1102,6 +1104,8 @@ int vsg_hamming_block_best2_device(int device, const uint8_t *d_a, const uint8_t
                                    int nblocks, int max_rows, int32_t *d_best, int32_t *d_second,
                                    int32_t *d_argbest, void *stream) {
   if (!d_a || !d_b || !d_best || !d_second || !d_argbest || nblocks < 1 || max_rows < 1) return VSG_ERR_INVALID;
+  // the packed key has 20 bits for the train row, gridDim.y carries the block
+  if (max_rows > (1 << 20) || nblocks > 65535) return VSG_ERR_UNSUPPORTED;
   if (vsg::use_device(device) != VSG_OK) return VSG_ERR_NO_DEVICE;
   dim3 grid((max_rows + kBest2Rows - 1) / kBest2Rows, nblocks);
   // stream == NULL is the caller's NULL stream (see vsg_orb_extract_batch_device for how the extractor orders itself
