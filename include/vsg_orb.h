@@ -817,7 +817,7 @@ int vsg_frame_search_sim3_points(vsg_frame *kf, vsg_mappoints *mp, int n, const 
  * Tcw, inv_level_sigma2, outlier or res, a slot >= capacity, nlevels outside [1, 16], a feature with a slot whose octave
  * is >= nlevels, a hold_round other than -1 or 2, store and frame on different devices: VSG_ERR_INVALID; Nleft != -1
  * (EdgeSE3ProjectXYZOnlyPoseToBody :1182-1246, KannalaBrandt8): VSG_ERR_UNSUPPORTED.
- * Future work: a chain "search -> optimise" in one enqueue (the search's matches feeding feat_slots on the device). */
+ * vsg_frame_track_with_motion_model below runs a search and this routine in one enqueue. */
 typedef struct vsg_pose_se3 {
   float q[4]; /* Tcw.unit_quaternion() as x y z w */
   float t[3]; /* Tcw.translation() */
@@ -831,6 +831,50 @@ int vsg_frame_pose_optimization(vsg_frame *F, vsg_mappoints *mp, const int32_t *
                                 int nlevels, int hold_round, uint8_t *outlier, float *chi2, vsg_pose_result *res);
 int vsg_frame_pose_optimization_resume(vsg_frame *F, const uint8_t *removed, uint8_t *outlier, float *chi2,
                                        vsg_pose_result *res);
+
+/* Tracking's motion-model step on resident data as ONE enqueue and ONE wait: the projection kernel, the window search,
+ * the ordered walk of the search (csrc/vsg_walks_dev.h: on the device what vsg_frame_search_last_frame does on the host
+ * after its wait) and vsg_frame_pose_optimization, whose edges are the walk's matches in ascending feature order
+ * (Optimizer.cc:1109-1180) and never leave the device in between.  Every call that is accepted gives, bit for bit, what
+ * the two existing calls give with the caller's loops between them; the checks are stricter in one place (below).
+ * Frames with Nleft != -1: VSG_ERR_UNSUPPORTED.  The intrinsics of the
+ * solve are cur_pose's fx, fy, cx, cy, mbf; Tcw is the same pose as the caller's quaternion (both paths get the same
+ * bits); inv_level_sigma2, nlevels (shared with the search, 1..16) and hold_round as in vsg_frame_pose_optimization.
+ * Checked before anything is enqueued, with the codes of the two calls: everything vsg_frame_search_last_frame and
+ * vsg_frame_pose_optimization check; here EVERY feature of cur must have its octave in [0, nlevels) (any of them may
+ * end with a slot).
+ * 2 * features + queries above about 16000 (the walk's state is one workgroup's LDS, kept to 64 KB by choice):
+ * VSG_ERR_CAPACITY, also before anything is enqueued.  An error after an enqueue waits for the stream before it returns.
+ * No error writes *res or an output array, or drops a hold that is pending on cur.
+ *
+ * bool Tracking::TrackWithMotionModel() (Tracking.cc:2945-3005): fill(mvpMapPoints, NULL) and SearchByProjection(
+ * mCurrentFrame, mLastFrame, th, bMono) (:2945-2956); if nmatches < 20 the same once more with 2 * th from all-free
+ * features (:2958-2963, a second enqueue and wait, in this rare case only); still below 20: return (:2967), here with
+ * res->optimized = 0, the input pose, the wide search's matches and no outlier writes.  Then PoseOptimization (:2978) and
+ * the discard loop (:2980-3005): a matched feature flagged outlier loses its slot and its flag is cleared.
+ *   - cur .. check_orientation: as vsg_frame_search_last_frame (every feature of cur starts free).
+ *   - feat_slots_out[i], one per feature of cur: the slot of mvpMapPoints[i] after the discard, or -1.  train_match (may
+ *     be NULL): as vsg_frame_search_last_frame defines it, for the search whose matches were used.  outlier, chi2 (may be
+ *     NULL): as vsg_frame_pose_optimization, entries of features with a match only; after the discard every written flag
+ *     is 0.
+ *   - res: pose = the solve's result (the input pose when it did not run); n_search = nmatches of the first search;
+ *     wide = 1 when the 2 * th search ran; n_matches_searched = nmatches of the search that was used; optimized = 0 when
+ *     both searches stayed below 20; n_matches = nmatches after the discard's decrements; n_matches_map = nmatchesMap,
+ *     the survivors whose point has `observed` set in the store; direction as vsg_frame_search_last_frame.
+ *   - hold_round = 2 is passed through: with res->pose.held = 1 the discard is NOT applied, feat_slots_out and outlier
+ *     are as after round 1 and n_matches = n_matches_searched; the caller runs the plane step, calls
+ *     vsg_frame_pose_optimization_resume(cur, ...) and discards itself.
+ * Returns res->n_matches, or an error code. */
+typedef struct vsg_track_result {
+  vsg_pose_result pose;
+  int32_t n_search, wide, n_matches_searched, optimized, n_matches, n_matches_map, direction, pad;
+} vsg_track_result;
+int vsg_frame_track_with_motion_model(vsg_frame *cur, vsg_frame *last, vsg_mappoints *mp, const int32_t *last_slots,
+                                      const vsg_frame_pose *cur_pose, const vsg_frame_pose *last_pose, float mb, int mono,
+                                      float th, const float *scale_factors, int nlevels, int check_orientation,
+                                      const vsg_pose_se3 *Tcw, const float *inv_level_sigma2, int hold_round,
+                                      int32_t *feat_slots_out, int32_t *train_match, uint8_t *outlier, float *chi2,
+                                      vsg_track_result *res);
 
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, S12, th) (ORBmatcher.h:76,
  * ORBmatcher.cc:1448-1665).  Direction 1 (:1489-1565): for each KF1 feature i1 with a usable, not yet matched map

@@ -105,6 +105,7 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
 }
 
 enum { kWinList = 0, kWinBest = 1 };
+enum { kWinInline = 16 };  // entries of a query's inline slot in list mode (vsg_window.hip)
 enum { VSG_RETRY = -100 };  // internal: candidate lists overflowed the compact array; the entry point runs again
 enum { kGateNone = 0, kGateUr = 1, kGateChi2 = 2 };
 
@@ -119,6 +120,13 @@ struct WindowCall {
   bool with_desc = true;
   size_t base = 0;  // offset of this call's blocks inside the arena (several calls can share one arena)
   bool range_open = false;  // a roctx range pushed by begin() and not yet popped (every exit path pops exactly once)
+  // The chain calls (vsg_track.hip): {start, length} per query and the candidate array at these DEVICE addresses instead of
+  // the pinned arena's blocks, for a kernel behind this one to read (nullptr: the pinned arena).  Such a call ends with
+  // account(), not finish(): the kernel behind it sums what the waves took from the counter.
+  // dev_lists (set before begin()): the pinned arena holds none of the three blocks.
+  int *x_off = nullptr, *x_cnt = nullptr;
+  uint32_t *x_out = nullptr;
+  bool dev_lists = false;
   ~WindowCall();
 
   int begin(int device, int nq, int mode, bool with_desc, size_t arena_base = 0, size_t arena_extra = 0);
@@ -128,6 +136,8 @@ struct WindowCall {
              const uint8_t *qdesc_dev = nullptr,   // qdesc_dev: query descriptors already on the device
              const WinQuery *q_dev = nullptr);     // q_dev: queries a kernel in front of this one wrote on the device
   int finish();  // waits for the stream; VSG_RETRY when the lists overflowed (list mode)
+  // the second half of finish() alone: `total` entries went to the overflow area; VSG_RETRY when that is more than cap
+  int account(long long total);
   // launch() then finish(): what an entry point with ONE window kernel does between its fill and its host pass
   int run(const vsg_frame *f, int gate_mode, int best_init = 256, const float *inv_sigma2 = nullptr, int nlevels = 0,
           const uint8_t *qdesc_dev = nullptr) {
@@ -135,6 +145,7 @@ struct WindowCall {
     return rc != VSG_OK ? rc : finish();
   }
   size_t bytes() const;
+  size_t out_bytes() const;
   walk::CandView lists() const;
   const int32_t *best() const { return (const int32_t *)(c->h_pin + base + oOut); }  // pairs {idx, dist}
   // Fuse's copy-out of best mode: bestIdx / bestDist per query (no candidate: -1 / the scan's start value); returns

@@ -25,6 +25,7 @@
 #include "vsg_obs_args.h"
 #include "vsg_observations.h"
 #include "vsg_project.h"
+#include "vsg_track_int.h"
 
 using namespace vsg;
 
@@ -500,29 +501,53 @@ struct ResidentCall {
   PointStage st;
 
   // want: the optional fields of PointOut the projection kernel is to write; launch(ResidentDev) enqueues it.
-  // VSG_RETRY: the lists overflowed, the whole call runs again
+  // enqueue(): both kernels on the thread's stream, no wait.  dev_lists (the chain calls, vsg_track_int.h): {start, length}
+  // and the candidate array go to the device arena behind the queries and descriptors, where a kernel behind these two
+  // reads them, and the pinned arena holds none of the three; *lists = where they are.  pin_extra / dev_extra: room for
+  // the caller's own blocks behind this call's in both arenas; dev_used = where the device one starts.  n == 0 enqueues
+  // nothing.
+  size_t dev_used = 0;
+  struct DevLists {
+    int *off, *cnt;
+    uint32_t *ent;
+    size_t entries;
+  };
   template <class Launch>
-  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, unsigned want, const ResidentMode &M,
-          Launch launch) {
+  int enqueue(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, unsigned want, const ResidentMode &M,
+              Launch launch, bool dev_lists = false, size_t pin_extra = 0, size_t dev_extra = 0, DevLists *lists = nullptr) {
     st.lay_out(n, slots, skip, want);
-    Stage sd;
-    const size_t dQ = sd.add(st.N * sizeof(WinQuery)), dD = sd.add(st.N * 32);
-    int rc = wc.begin(F->device, n, M.mode, false, 0, st.total);
+    wc.dev_lists = dev_lists;
+    int rc = wc.begin(F->device, n, M.mode, false, 0, st.total + pin_extra);
     if (rc != VSG_OK) return rc;
     ThreadCtx *c = wc.c;
-    rc = ctx_reserve(c, 0, sd.total);
+    const size_t Q = (size_t)(n > 0 ? n : 1), entries = Q * kWinInline + (size_t)wc.cap;
+    Stage sd;
+    const size_t dQ = sd.add(Q * sizeof(WinQuery)), dD = sd.add(Q * 32);
+    const size_t dOff = sd.add(dev_lists ? Q * 4 : 0), dCnt = sd.add(dev_lists ? Q * 4 : 0),
+                 dOut = sd.add(dev_lists ? entries * 4 : 0);
+    dev_used = sd.total;
+    rc = ctx_reserve(c, 0, sd.total + dev_extra);
     if (rc != VSG_OK) return rc;
     // both reserves first, pointers after: either reserve may move its arena
     st.bind(c->h_pin + wc.bytes(), c->d_pin + wc.bytes());
+    if (dev_lists) {
+      wc.x_off = (int *)(c->d_buf + dOff), wc.x_cnt = (int *)(c->d_buf + dCnt), wc.x_out = (uint32_t *)(c->d_buf + dOut);
+      if (lists) *lists = {wc.x_off, wc.x_cnt, wc.x_out, entries};
+    }
+    if (n == 0) return VSG_OK;
     const ResidentDev R = {st.slots, st.skip, st.dev, (WinQuery *)(c->d_buf + dQ), c->d_buf + dD, c->stream};
     launch(R);
     rc = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
     if (rc == VSG_OK) rc = wc.launch(F, M.gate_mode, M.best_init, M.inv_sigma2, M.nlevels, R.qdesc, R.Q);
-    if (rc != VSG_OK) {
-      hipStreamSynchronize(c->stream);  // nothing of this call may still write the arena when the next one fills it
-      return rc;
-    }
-    return wc.finish();
+    if (rc != VSG_OK) hipStreamSynchronize(c->stream);  // nothing of this call may still write the arena when the next one fills it
+    return rc;
+  }
+  // enqueue() and the wait.  VSG_RETRY: the lists overflowed, the whole call runs again
+  template <class Launch>
+  int run(const vsg_frame *F, int n, const int32_t *slots, const uint8_t *skip, unsigned want, const ResidentMode &M,
+          Launch launch) {
+    const int rc = enqueue(F, n, slots, skip, want, M, launch);
+    return rc != VSG_OK ? rc : wc.finish();
   }
 };
 
@@ -559,6 +584,53 @@ int fuse_points(vsg_frame *kf, vsg_mappoints *mp, int n, const int32_t *slots, c
 }
 
 }  // namespace
+
+namespace vsg {
+
+const uint8_t *store_observed_dev(const vsg_mappoints *mp) { return mp->d_observed; }
+
+int track_last_check(const vsg_frame *cur, const vsg_frame *last, const vsg_mappoints *mp, const int32_t *last_slots,
+                     const vsg_frame_pose *cur_pose, const vsg_frame_pose *last_pose, float mb, int mono,
+                     const float *scale_factors, int nlevels, int *dir) {
+  if (!last || !last->d_block || !last_pose || !last_slots) return VSG_ERR_INVALID;
+  const int n = last->n;
+  const int rc = resident_check(cur, mp, cur_pose, n, true, true, scale_factors, nlevels);
+  if (rc != VSG_OK) return rc;
+  if (last->nleft != -1) return VSG_ERR_UNSUPPORTED;  // the right-camera block (ORBmatcher.cc:1785-1853)
+  if (last->device != cur->device) return VSG_ERR_INVALID;
+  const vsg_keypoint *lk = last->h_kps.data();
+  for (int i = 0; i < n; i++) {
+    if (last_slots[i] >= mp->capacity) return VSG_ERR_INVALID;
+    if (last_slots[i] >= 0 && (lk[i].octave < 0 || lk[i].octave >= nlevels)) return VSG_ERR_INVALID;
+  }
+  *dir = motion_direction(*cur_pose, *last_pose, mb, mono ? 1 : 0);  // :1677-1684
+  return VSG_OK;
+}
+
+int track_last_enqueue(TrackSearch *T, const vsg_frame *cur, const vsg_frame *last, const vsg_mappoints *mp,
+                       const int32_t *last_slots, const vsg_frame_pose *cur_pose, float th, int dir,
+                       const float *scale_factors, int nlevels, size_t pin_extra_bytes, size_t dev_extra_bytes) {
+  PointArgs A = point_args(cur, cur_pose, last->n, kFrameBounds, th, scale_factors, nlevels);
+  A.direction = dir;
+  // the stereo gate of :1742-1748 applies to frames with mvuRight (Nleft == -1 here)
+  ResidentCall call;
+  ResidentCall::DevLists lists = {};
+  const int rc = call.enqueue(cur, last->n, last_slots, nullptr, kXr | kObserved,
+                              resident_lists(cur->has_uright ? kGateUr : kGateNone),
+                              [&](const ResidentDev &R) { launch_project<kProjLast>(R, mp, last, A); }, true,
+                              pin_extra_bytes, dev_extra_bytes, &lists);
+  if (rc != VSG_OK) return rc;
+  // what the entry point needs after this frame is gone: the window call (its counter accounting) and plain pointers
+  T->wc = call.wc;
+  call.wc.range_open = false;  // T->wc pops the range now
+  T->c = T->wc.c, T->nq = last->n, T->list_total = (int)lists.entries;
+  T->pin_extra = T->wc.bytes() + call.st.total, T->dev_extra = call.dev_used;
+  T->d_observed = call.st.dev.observed, T->d_slots = call.st.slots;
+  T->d_off = lists.off, T->d_cnt = lists.cnt, T->d_ent = lists.ent;
+  return VSG_OK;
+}
+
+}  // namespace vsg
 
 extern "C" {
 

@@ -17,6 +17,7 @@
 
 #include "vsg_frame_int.h"
 #include "vsg_pose_opt.h"
+#include "vsg_track_int.h"
 
 using namespace vsg;
 
@@ -34,6 +35,9 @@ struct PoseArgs {
   float *chi2;
   const int32_t *feat, *slot;  // per edge, in the pinned arena (kModeAll / kModeHold)
   const uint8_t *removed;      // per edge, in the pinned arena (kModeResume; nullptr: none)
+  // a chain call (vsg_track.hip): the status words of the walk kernel in front of this one, {nmatches, n_edges, flags};
+  // feat / slot are that kernel's edge list in the device arena and n_edges is status[1].  nullptr: the host's n_edges
+  const int32_t *chain;
   const float *pos;            // the store's world positions
   const KeyPointPOD *kps;
   const float *uright;  // nullptr: every feature is monocular
@@ -102,7 +106,18 @@ struct DevTeam {
 __global__ __launch_bounds__(pose::kThreads) void k_pose_optimize(PoseArgs A) {
   __shared__ double lds[pose::kWaves * pose::kAcc];
   __shared__ pose::Ctl ctl;
-  const int tid = threadIdx.x, E = A.n_edges;
+  const int tid = threadIdx.x, E = A.chain ? A.chain[1] : A.n_edges;
+  if (A.chain && A.chain[2] != 0) {
+    // the lists overflowed, the search found fewer than 20 matches or there are fewer than 3 edges: the header alone
+    if (tid == 0) {
+      PoseOut o;
+      for (int k = 0; k < 4; k++) o.q[k] = A.input.q[k];
+      for (int k = 0; k < 3; k++) o.t[k] = A.input.t[k];
+      o.n_bad = 0, o.rounds_run = 0, o.held = 0, o.pad = 0;
+      *A.out = o;
+    }
+    return;
+  }
   if (A.mode == pose::kModeResume) {
     // round 2's plane step on the host (:1270-1335): mvpMapPoints[j] = NULL, mvbOutlier[j] = true
     if (A.removed)
@@ -187,6 +202,69 @@ int run_pose(vsg_frame *F, ThreadCtx *c, PoseArgs &A, size_t oOutFlags, size_t o
 }
 
 }  // namespace
+
+namespace vsg {
+
+size_t pose_chain_bytes(int nf) {
+  const size_t N = (size_t)(nf > 0 ? nf : 1);
+  Stage st;
+  st.add(N), st.add(N * 4), st.add(sizeof(PoseOut));
+  return st.total;
+}
+
+int pose_chain_enqueue(vsg_frame *F, ThreadCtx *c, const StoreView &S, const int32_t *d_edge_feat,
+                       const int32_t *d_edge_slot, const int32_t *d_status, const vsg_pose_se3 *Tcw,
+                       const vsg_frame_pose *cam, const float *inv_level_sigma2, int nlevels, int hold_round,
+                       size_t pin_base) {
+  if (!F->d_pose) {  // allocated on first use, freed with the frame
+    const PoseLayout L((size_t)F->capacity);
+    TRY_HIP(hipMalloc((void **)&F->d_pose, L.total));
+  }
+  const size_t N = (size_t)(F->n > 0 ? F->n : 1);
+  Stage st;
+  const size_t oOutFlags = pin_base + st.add(N), oOutChi2 = pin_base + st.add(N * 4), oOut = pin_base + st.add(sizeof(PoseOut));
+  PoseArgs A;
+  memset(&A, 0, sizeof(A));
+  A.feat = d_edge_feat, A.slot = d_edge_slot, A.chain = d_status;
+  A.pos = S.pos, A.kps = F->d_kps, A.uright = F->has_uright ? F->d_uright : nullptr;
+  for (int l = 0; l < 16; l++) A.inv_sigma2[l] = inv_level_sigma2[l < nlevels ? l : nlevels - 1];
+  A.cam = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->mbf};
+  A.input = pose::est_from_pose(Tcw->q, Tcw->t);
+  A.n_edges = 0, A.mode = hold_round == 2 ? pose::kModeHold : pose::kModeAll;
+  const PoseLayout L((size_t)F->capacity);
+  A.ctl = (pose::Ctl *)(F->d_pose + L.oCtl), A.edges = (pose::Edge *)(F->d_pose + L.oEdges);
+  A.flags = F->d_pose + L.oFlags, A.chi2 = (float *)(F->d_pose + L.oChi2);
+  A.out_flags = c->d_pin + oOutFlags, A.out_chi2 = (float *)(c->d_pin + oOutChi2), A.out = (PoseOut *)(c->d_pin + oOut);
+  F->pose_held = false;
+  hipLaunchKernelGGL(k_pose_optimize, dim3(1), dim3(pose::kThreads), 0, c->stream, A);
+  return hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+}
+
+int pose_chain_finish(vsg_frame *F, ThreadCtx *c, size_t pin_base, const int32_t *h_edge_feat, int n_edges,
+                      uint8_t *outlier, float *chi2, vsg_pose_result *res) {
+  const size_t N = (size_t)(F->n > 0 ? F->n : 1);
+  Stage st;
+  const size_t oOutFlags = pin_base + st.add(N), oOutChi2 = pin_base + st.add(N * 4), oOut = pin_base + st.add(sizeof(PoseOut));
+  const PoseOut *o = (const PoseOut *)(c->h_pin + oOut);
+  const uint8_t *fl = c->h_pin + oOutFlags;
+  const float *ch = (const float *)(c->h_pin + oOutChi2);
+  F->pose_feat.assign(h_edge_feat, h_edge_feat + n_edges);  // what _resume maps its edges through
+  for (int e = 0; e < n_edges; e++) {
+    const int i = h_edge_feat[e];
+    outlier[i] = (fl[e] & pose::kOutlier) ? 1 : 0;
+    if (chi2) chi2[i] = ch[e];
+  }
+  fill_result(res, o->q, o->t, n_edges, o->n_bad, o->rounds_run, o->held);
+  F->pose_held = o->held != 0;
+  return o->held ? 0 : n_edges - o->n_bad;
+}
+
+void pose_result_input(const vsg_pose_se3 *Tcw, int n_edges, vsg_pose_result *res) {
+  const pose::Est input = pose::est_from_pose(Tcw->q, Tcw->t);
+  fill_result(res, input.q, input.t, n_edges, 0, 0, 0);
+}
+
+}  // namespace vsg
 
 extern "C" {
 

@@ -1,0 +1,241 @@
+// vsg_track.hip -- Tracking::TrackWithMotionModel (Tracking.cc:2945-3005) as ONE enqueue and ONE wait:
+// vsg_frame_track_with_motion_model (include/vsg_orb.h).
+//
+//   projection kernel -> k_window_search -> k_track_walk -> k_pose_optimize          (one stream, no host step between)
+//
+// The first two are the resident searches' own (vsg_mappoints.hip, vsg_window.hip) with the candidate lists left in the
+// device arena; the last is Optimizer::PoseOptimization (vsg_pose.hip) reading its edges from the buffer k_track_walk
+// wrote.  k_track_walk is what used to be the host's ordered pass (vsg_walks.h) between two waits: ONE workgroup runs
+// csrc/vsg_walks_dev.h -- rounds to the fixed point of "a feature is blocked for q iff it was blocked on entry or an
+// observed point q' < q claimed it", the last-writer rule, the rotation filter on claims, the per-feature slots and the
+// edge list in feature order -- with the per-feature and per-query state in LDS.  It sits IN FRONT of the optimisation,
+// not inside it: k_pose_optimize already runs at its register limit.  The matches never leave the device between the
+// search and the solve; the host reads them once, after the wait, together with the pose.
+#include <cstring>
+#include <vector>
+
+#include "vsg_track_int.h"
+#include "vsg_walks_dev.h"
+
+using namespace vsg;
+
+namespace {
+
+// kWalkLdsMax: what one workgroup may take of LDS without raising the function's limit, static part included.  The cap is
+// this file's choice, not the part's (a CU of gfx950 has 160 KB): a frame and a last frame with 2 nf + nq above about
+// 16000 are refused with VSG_ERR_CAPACITY.
+enum { kWalkThreads = 1024, kWalkWaves = kWalkThreads / 64, kWalkStaticLds = kWalkWaves * 4, kWalkLdsMax = 64 * 1024 };
+
+struct DevTeam {
+  int *wsum;  // [kWalkWaves], LDS
+  template <class F>
+  __device__ void each(int n, F f) {
+    for (int i = threadIdx.x; i < n; i += kWalkThreads) f(i);
+    __syncthreads();
+  }
+  __device__ void amin(int32_t *p, int v) { atomicMin(p, v); }
+  __device__ void amax(int32_t *p, int v) { atomicMax(p, v); }
+  __device__ void aadd(int32_t *p, int v) { atomicAdd(p, v); }
+  // positions in ascending i: a ballot inside the wave, the waves' counts through LDS, kWalkThreads items at a time
+  template <class P, class E>
+  __device__ int compact(int n, P pred, E emit) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += kWalkThreads) {
+      const int i = i0 + (int)threadIdx.x;
+      const bool p = i < n && pred(i);
+      const unsigned long long m = __ballot(p);
+      if (lane == 0) wsum[wave] = __popcll(m);
+      __syncthreads();
+      int before = __popcll(m & ((1ull << lane) - 1ull)), total = 0;
+      for (int w = 0; w < kWalkWaves; w++) {
+        const int s = wsum[w];
+        before += w < wave ? s : 0;
+        total += s;
+      }
+      if (p) emit(i, base + before);
+      base += total;
+      __syncthreads();
+    }
+    return base;
+  }
+};
+
+// LDS: [claim nf | tm nf | choice nq | scratch] as int32, then the bytes [observed nq | q_valid nq | blocked nf]: the flags
+// the rounds read again and again are fetched from the pinned arena once.
+__host__ __device__ inline size_t walk_lds_bytes(int nq, int nf) {
+  return ((size_t)2 * nf + nq + walkdev::kScratchInts) * 4 + (size_t)2 * nq + nf;
+}
+
+__global__ __launch_bounds__(kWalkThreads) void k_track_walk(walkdev::Args A) {
+  extern __shared__ int32_t lds[];
+  __shared__ int wsum[kWalkWaves];
+  A.claim = lds, A.tm = lds + A.nf, A.choice = lds + 2 * A.nf, A.scratch = lds + 2 * A.nf + A.nq;
+  uint8_t *b_obs = (uint8_t *)(A.scratch + walkdev::kScratchInts), *b_valid = b_obs + A.nq, *b_blk = b_valid + A.nq;
+  for (int q = threadIdx.x; q < A.nq; q += kWalkThreads) {
+    b_obs[q] = A.observed ? A.observed[q] : 0;
+    b_valid[q] = A.q_valid ? A.q_valid[q] : 1;
+  }
+  for (int i = threadIdx.x; i < A.nf; i += kWalkThreads) b_blk[i] = A.blocked_in ? A.blocked_in[i] : 0;
+  A.observed = b_obs, A.q_valid = b_valid, A.blocked_in = b_blk;
+  __syncthreads();
+  DevTeam T = {wsum};
+  walkdev::run(T, A);
+}
+
+// The caller's block of a chain call behind the search's blocks.  Pinned: what the host reads after the wait.  Device: the
+// edge list and the status.
+struct TrackLayout {
+  size_t pTm, pTb, pFs, pFo, pStatus, pPose, pin_total;
+  size_t dFeat, dSlot, dStatus, dev_total;
+  explicit TrackLayout(int nf) {
+    const size_t N = (size_t)(nf > 0 ? nf : 1);
+    Stage sp;
+    pTm = sp.add(N * 4), pTb = sp.add(N), pFs = sp.add(N * 4), pFo = sp.add(N), pStatus = sp.add(sizeof(walkdev::Status));
+    pPose = sp.add(pose_chain_bytes(nf));
+    pin_total = sp.total;
+    Stage sd;
+    dFeat = sd.add(N * 4), dSlot = sd.add(N * 4), dStatus = sd.add(sizeof(walkdev::Status));
+    dev_total = sd.total;
+  }
+};
+
+// k_track_walk behind the search's two kernels, k_pose_optimize behind it, then the call's one wait and the overflow
+// accounting of WindowCall::finish from the sum the walk kernel took.  VSG_RETRY: the lists overflowed, nothing was solved.
+int walk_solve_wait(TrackSearch &T, const TrackLayout &L, walkdev::Args &A, vsg_frame *F, const StoreView &S,
+                    const vsg_pose_se3 *Tcw, const vsg_frame_pose *cam, const float *inv_level_sigma2, int nlevels,
+                    int hold_round, walkdev::Status *st) {
+  ThreadCtx *c = T.c;
+  uint8_t *hp = c->h_pin + T.pin_extra, *dp = c->d_pin + T.pin_extra, *dv = c->d_buf + T.dev_extra;
+  A.inline_len = kWinInline, A.cap = T.wc.cap, A.list_total = T.list_total;
+  A.ent = T.d_ent, A.off = T.d_off, A.cnt = T.d_cnt;
+  A.train_match = (int32_t *)(dp + L.pTm), A.train_blocked = dp + L.pTb, A.feat_slots = (int32_t *)(dp + L.pFs);
+  A.feat_observed = dp + L.pFo;
+  A.edge_feat = (int32_t *)(dv + L.dFeat), A.edge_slot = (int32_t *)(dv + L.dSlot);
+  A.status = (walkdev::Status *)(dv + L.dStatus), A.status2 = (walkdev::Status *)(dp + L.pStatus);
+  hipLaunchKernelGGL(k_track_walk, dim3(1), dim3(kWalkThreads), walk_lds_bytes(A.nq, A.nf), c->stream, A);
+  const int launched = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+  int rc = launched;
+  if (rc == VSG_OK)
+    rc = pose_chain_enqueue(F, c, S, A.edge_feat, A.edge_slot, (const int32_t *)A.status, Tcw, cam, inv_level_sigma2,
+                            nlevels, hold_round, T.pin_extra + L.pPose);
+  const bool walked = launched == VSG_OK;
+  const hipError_t e = hipStreamSynchronize(c->stream);  // an error after an enqueue waits for the stream too
+  if (e != hipSuccess || !walked) return VSG_ERR_HIP;
+  // the walk kernel ran to its end: what the window kernel's waves took from the counter is known and is accounted for,
+  // whatever else went wrong, so that the thread's next call starts from the right base
+  *st = *(const walkdev::Status *)(hp + L.pStatus);
+  const int acc = T.wc.account(st->overflow_sum);
+  if (rc != VSG_OK) return VSG_ERR_HIP;
+  if (acc != VSG_OK) return acc;
+  return (st->flags & walkdev::kStOverflow) ? VSG_ERR_HIP : VSG_OK;  // a list outside the array: never seen
+}
+
+bool octaves_in_pyramid(const vsg_frame *F, int nlevels) {
+  const size_t n = (size_t)F->n < F->h_kps.size() ? (size_t)F->n : F->h_kps.size();
+  for (size_t i = 0; i < n; i++)
+    if (F->h_kps[i].octave < 0 || F->h_kps[i].octave >= nlevels) return false;
+  return true;
+}
+
+const int kAngleStride = (int)sizeof(KeyPointPOD);
+
+}  // namespace
+
+extern "C" {
+
+int vsg_frame_track_with_motion_model(vsg_frame *cur, vsg_frame *last, vsg_mappoints *mp, const int32_t *last_slots,
+                                      const vsg_frame_pose *cur_pose, const vsg_frame_pose *last_pose, float mb, int mono,
+                                      float th, const float *scale_factors, int nlevels, int check_orientation,
+                                      const vsg_pose_se3 *Tcw, const float *inv_level_sigma2, int hold_round,
+                                      int32_t *feat_slots_out, int32_t *train_match, uint8_t *outlier, float *chi2,
+                                      vsg_track_result *res) {
+  if (!Tcw || !inv_level_sigma2 || !res || !outlier || !feat_slots_out) return VSG_ERR_INVALID;
+  if (hold_round != -1 && hold_round != 2) return VSG_ERR_INVALID;
+  int dir = 0;
+  int rc = track_last_check(cur, last, mp, last_slots, cur_pose, last_pose, mb, mono, scale_factors, nlevels, &dir);
+  if (rc != VSG_OK) return rc;
+  StoreView S;
+  if (!store_view(mp, &S) || !octaves_in_pyramid(cur, nlevels)) return VSG_ERR_INVALID;
+  // everything the kernels index has been bounded; nothing has been enqueued
+  const int nf = cur->n, nq = last->n;
+  if (nf > 0 && nq > 0 && walk_lds_bytes(nq, nf) + kWalkStaticLds > kWalkLdsMax) return VSG_ERR_CAPACITY;
+  // an error from here on leaves *res, the outputs and a pending hold as they were: R becomes *res on success only
+  vsg_track_result R;
+  memset(&R, 0, sizeof(R));
+  R.direction = dir;
+  pose_result_input(Tcw, 0, &R.pose);
+  if (nf == 0 || nq == 0) {  // both searches find nothing (:2958, :2967)
+    for (int i = 0; i < nf; i++) {
+      feat_slots_out[i] = -1;
+      if (train_match) train_match[i] = -1;
+    }
+    R.wide = 1;
+    *res = R;
+    return 0;
+  }
+  const TrackLayout L(nf);
+  walkdev::Status st;
+  TrackSearch T;
+  for (int pass = 0; pass < 2; pass++) {
+    const float th_now = pass ? 2 * th : th;  // :2961: every feature is free again, the window twice as wide
+    rc = with_retry([&]() -> int {
+      T = TrackSearch();
+      int r = track_last_enqueue(&T, cur, last, mp, last_slots, cur_pose, th_now, dir, scale_factors, nlevels, L.pin_total,
+                                 L.dev_total);
+      if (r != VSG_OK) return r;
+      walkdev::Args A;
+      memset(&A, 0, sizeof(A));
+      A.form = walkdev::kFormLast, A.nq = nq, A.nf = nf;
+      A.check_orientation = check_orientation != 0, A.min_matches = 20;
+      A.observed = T.d_observed;
+      A.q_angle = &last->d_kps->angle, A.t_angle = &cur->d_kps->angle, A.q_angle_stride = A.t_angle_stride = kAngleStride;
+      A.q_slot = T.d_slots, A.slot_observed = store_observed_dev(mp);
+      return walk_solve_wait(T, L, A, cur, S, Tcw, cur_pose, inv_level_sigma2, nlevels, hold_round, &st);
+    });
+    if (rc != VSG_OK) return rc;
+    if (pass == 0) R.n_search = st.nmatches;
+    if (st.nmatches >= 20) break;
+    R.wide = 1;
+  }
+  const uint8_t *hp = T.c->h_pin + T.pin_extra;
+  const int32_t *tm = (const int32_t *)(hp + L.pTm), *fs = (const int32_t *)(hp + L.pFs);
+  const uint8_t *fo = hp + L.pFo;
+  R.n_matches_searched = st.nmatches, R.n_matches = st.nmatches;
+  std::vector<int32_t> feat;  // the edge list read back: the features with a slot, ascending
+  for (int i = 0; i < nf; i++)
+    if (fs[i] >= 0) feat.push_back(i);
+  const bool solved = st.nmatches >= 20 && !(st.flags & walkdev::kStFewEdges);
+  if (solved && (int)feat.size() != st.n_edges) return VSG_ERR_HIP;
+  memcpy(feat_slots_out, fs, (size_t)nf * 4);
+  if (train_match) memcpy(train_match, tm, (size_t)nf * 4);
+  if (st.nmatches < 20) {  // :2967: the pose stays, nothing is flagged
+    *res = R;
+    return st.nmatches;
+  }
+  R.optimized = 1;
+  if (!solved) {  // Optimizer.cc:1251
+    for (int i = 0; i < nf; i++)
+      if (fs[i] >= 0) outlier[i] = 0;
+    pose_result_input(Tcw, st.n_edges, &R.pose);
+  } else {
+    pose_chain_finish(cur, T.c, T.pin_extra + L.pPose, feat.data(), st.n_edges, outlier, chi2, &R.pose);
+    if (R.pose.held) {  // the caller runs the plane step, _resume and the discard
+      *res = R;
+      return st.nmatches;
+    }
+  }
+  int n_matches = st.nmatches, n_map = 0;  // :2980-3005
+  for (int i = 0; i < nf; i++) {
+    if (feat_slots_out[i] < 0) continue;
+    if (outlier[i])
+      feat_slots_out[i] = -1, outlier[i] = 0, n_matches--;
+    else if (fo[i])
+      n_map++;
+  }
+  R.n_matches = n_matches, R.n_matches_map = n_map;
+  *res = R;
+  return n_matches;
+}
+
+}  // extern "C"

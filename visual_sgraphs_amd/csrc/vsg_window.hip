@@ -36,7 +36,7 @@ struct WinLaunch {
 // list there.  {start, length} per query say where the list is.  Best mode: first minimum over the candidates.
 // Completion is the stream's: a variant whose last workgroup stamped a pinned flag for the host to spin on needed a
 // system-scope fence per wave and took 32 us instead of 13 (MI355X, 1004 queries).
-enum { kInline = 16 };
+enum { kInline = kWinInline };
 
 __global__ __launch_bounds__(256) void k_window_search(FrameDev F, const WinQuery *__restrict__ Q,
                                                        const uint8_t *__restrict__ qdesc, WinLaunch W,
@@ -253,9 +253,10 @@ int WindowCall::begin(int device, int nq_, int mode_, bool with_desc_, size_t ar
   Stage st;
   oQ = st.add(Q * sizeof(WinQuery));
   oD = st.add(with_desc ? Q * 32 : 0);
-  oOff = st.add(mode == kWinList ? Q * 4 : 0);
-  oCnt = st.add(mode == kWinList ? Q * 4 : 0);
-  oOut = st.add(mode == kWinList ? (Q * kInline + (size_t)cap) * 4 : Q * 8);
+  const bool lists_here = mode == kWinList && !dev_lists;
+  oOff = st.add(lists_here ? Q * 4 : 0);
+  oCnt = st.add(lists_here ? Q * 4 : 0);
+  oOut = st.add(out_bytes());
   return ctx_reserve(c, base + st.total + arena_extra, 0);
 }
 
@@ -263,10 +264,13 @@ WindowCall::~WindowCall() {
   if (range_open) range_pop();  // an error return between begin() and finish()
 }
 
-size_t WindowCall::bytes() const {
+// bytes of the candidate array (list mode; none with dev_lists) or of the {idx, dist} pairs (best mode) in the pinned arena
+size_t WindowCall::out_bytes() const {
   const size_t Q = (size_t)(nq > 0 ? nq : 1);
-  return oOut + (((mode == kWinList ? (Q * kInline + (size_t)cap) * 4 : Q * 8) + 63) & ~(size_t)63);
+  return mode == kWinList ? (dev_lists ? 0 : (Q * kInline + (size_t)cap) * 4) : Q * 8;
 }
+
+size_t WindowCall::bytes() const { return oOut + ((out_bytes() + 63) & ~(size_t)63); }
 
 int WindowCall::launch(const vsg_frame *f, int gate_mode, int best_init, const float *inv_sigma2, int nlevels,
                        const uint8_t *qdesc_dev, const WinQuery *q_dev) {
@@ -281,7 +285,8 @@ int WindowCall::launch(const vsg_frame *f, int gate_mode, int best_init, const f
   hipLaunchKernelGGL(k_window_search, dim3((nq + 3) / 4), dim3(256), 0, c->stream, frame_dev(f),
                      q_dev ? q_dev : (const WinQuery *)(d + oQ),
                      qdesc_dev ? qdesc_dev : with_desc ? (const uint8_t *)(d + oD) : (const uint8_t *)nullptr, W,
-                     (int *)(d + oOff), (int *)(d + oCnt), (uint32_t *)(d + oOut), (int *)(d + oOut), c->d_counter);
+                     x_out ? x_off : (int *)(d + oOff), x_out ? x_cnt : (int *)(d + oCnt),
+                     x_out ? x_out : (uint32_t *)(d + oOut), (int *)(d + oOut), c->d_counter);
   t_prof.launch = now_us() - tl;
   return hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
 }
@@ -295,6 +300,11 @@ int WindowCall::finish() {
   const int32_t *cn = (const int32_t *)(c->h_pin + base + oCnt);
   long long total = 0;  // entries of the lists that went to the overflow area = what the waves added to the counter
   for (int q = 0; q < nq; q++) total += cn[q] > kInline ? cn[q] : 0;
+  return account(total);
+}
+
+int WindowCall::account(long long total) {
+  if (range_open) range_pop(), range_open = false;
   c->counter_base += (uint32_t)total;
   if (total <= cap) return VSG_OK;
   const long long per = (2 * total + nq - 1) / (nq > 0 ? nq : 1);

@@ -85,6 +85,8 @@ EXPORTS = [
     "vsg_mappoints_refresh_from_observations",
     # Optimizer::PoseOptimization on a resident frame and resident map points
     "vsg_frame_pose_optimization", "vsg_frame_pose_optimization_resume",
+    # Tracking::TrackWithMotionModel: search, ordered walk and PoseOptimization in one enqueue and one wait
+    "vsg_frame_track_with_motion_model",
     # LocalMapping::CreateNewMapPoints on resident keyframes: triangulate, gate, write the new points into the store
     "vsg_frame_set_stereo_points", "vsg_frame_triangulate_matches", "vsg_frame_create_new_map_points",
     # Sim3Solver on resident map points: every RANSAC hypothesis in one call, and the host-side set-up of the solver
@@ -161,6 +163,12 @@ class PoseResult(C.Structure):
     """include/vsg_orb.h vsg_pose_result."""
     _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("n_initial", C.c_int32), ("n_bad", C.c_int32),
                 ("rounds_run", C.c_int32), ("held", C.c_int32)]
+
+
+class TrackResult(C.Structure):
+    """include/vsg_orb.h vsg_track_result."""
+    _fields_ = [("pose", PoseResult)] + [(k, C.c_int32) for k in (
+        "n_search", "wide", "n_matches_searched", "optimized", "n_matches", "n_matches_map", "direction", "pad")]
 
 
 class Sim3Result(C.Structure):
@@ -435,6 +443,9 @@ def load_library():
     L.vsg_frame_pose_optimization.argtypes = [vp, vp, _i32p, C.POINTER(PoseSE3), cf, cf, cf, cf, cf, _f32p, ci, ci, _u8p,
                                               _f32p, C.POINTER(PoseResult)]
     L.vsg_frame_pose_optimization_resume.argtypes = [vp, _u8p, _u8p, _f32p, C.POINTER(PoseResult)]
+    L.vsg_frame_track_with_motion_model.argtypes = [vp, vp, vp, _i32p, C.POINTER(FramePose), C.POINTER(FramePose), cf, ci,
+                                                    cf, _f32p, ci, ci, C.POINTER(PoseSE3), _f32p, ci, _i32p, _i32p, _u8p,
+                                                    _f32p, C.POINTER(TrackResult)]
     tri_tail = [C.POINTER(TriangulationParams), _f32p, _f32p, _f32p, _f32p, ci, vp, _i32p, ci]
     tri_outs = [_u8p, _u8p, _f32p, _i32p, _i32p]
     L.vsg_frame_set_stereo_points.argtypes = [vp, _f32p, _f32p]
@@ -1681,6 +1692,44 @@ class Frame:
             self._h, _p(rem, _u8p) if rem is not None else None, _p(out, _u8p), _p(c2, _f32p), C.byref(res)),
             "vsg_frame_pose_optimization_resume")
         return self._pose_result(ret, res, out[:len(self.kps)], c2[:len(self.kps)])
+
+    # ---- Tracking::TrackWithMotionModel (Tracking.cc:2945-3005) on resident map points: search, ordered walk and
+    # PoseOptimization in one enqueue and one wait
+    @staticmethod
+    def _se3(q, t):
+        pose = PoseSE3()
+        pose.q[:] = [float(v) for v in np.asarray(q, np.float32).reshape(4)]
+        pose.t[:] = [float(v) for v in np.asarray(t, np.float32).reshape(3)]
+        return pose
+
+    def TrackWithMotionModel(self, last, mp, last_slots, cur_pose, last_pose, mb, mono, th, scale_factors, q, t,
+                             inv_level_sigma2, outlier, check_orientation=True, hold_round=-1, chi2=None):
+        """self = mCurrentFrame, last = the resident LastFrame; the arguments of SearchLastFrame and pose_optimization (the
+        camera is cur_pose's).  outlier / chi2 are updated IN A COPY.  Returns a dict: ret, feat_slots (one per feature,
+        after the discard), train_match, outlier, chi2, q, t, n_initial, n_bad, rounds_run, held, n_search, wide,
+        n_matches_searched, optimized, n_matches, n_matches_map, direction."""
+        if last_slots is not None and len(last_slots) != len(last.kps):
+            raise ValueError("last_slots length does not match the last frame's features")
+        n = len(self.kps)
+        _, slp, _, _, _ = self._resident_points(last_slots, None, (), len(last.kps))
+        sf, sig = _f32(scale_factors), _f32(inv_level_sigma2)
+        if len(sf) != len(sig):
+            raise ValueError("inv_level_sigma2 length does not match the scale factors")
+        out = np.zeros(max(n, 1), np.uint8)
+        out[:n] = _u8(outlier)
+        c2 = np.zeros(max(n, 1), np.float32)
+        if chi2 is not None:
+            c2[:n] = _f32(chi2)
+        fs, tm = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)
+        res = TrackResult()
+        ret = _check(self._L.vsg_frame_track_with_motion_model(
+            self._h, last.handle, mp.handle, slp, C.byref(cur_pose), C.byref(last_pose), float(np.float32(mb)), int(bool(mono)), float(th), _p(sf, _f32p), len(sf),
+            int(bool(check_orientation)), C.byref(self._se3(q, t)), _p(sig, _f32p), int(hold_round), _p(fs, _i32p),
+            _p(tm, _i32p), _p(out, _u8p), _p(c2, _f32p), C.byref(res)), "vsg_frame_track_with_motion_model")
+        d = self._pose_result(ret, res.pose, out[:n], c2[:n])
+        d.update(feat_slots=fs[:n], train_match=tm[:n])
+        d.update({k: int(getattr(res, k)) for k, _ in TrackResult._fields_[1:-1]})
+        return d
 
     # ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, ...) on resident map points
     # (Optimizer.cc:3261-3529); self is pKF1
