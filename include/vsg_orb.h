@@ -876,6 +876,62 @@ int vsg_frame_track_with_motion_model(vsg_frame *cur, vsg_frame *last, vsg_mappo
                                       int32_t *feat_slots_out, int32_t *train_match, uint8_t *outlier, float *chi2,
                                       vsg_track_result *res);
 
+/* Tracking's local-map step on resident data as ONE enqueue and ONE wait: k_frustum and the window search exactly as
+ * vsg_frame_search_local_points enqueues them, the ordered walk of that search on the device (csrc/vsg_walks_dev.h in its
+ * local form: what vsg_frame_search_local_points does on the host after its wait) and vsg_frame_pose_optimization on the
+ * walk's edges.  Every call that is accepted gives, bit for bit, what the two existing calls give with the caller's loops
+ * between them.
+ *
+ * bool Tracking::TrackLocalMap() (Tracking.cc:3019-3131; pinhole, Nleft == -1, no IMU): the second loop of
+ * SearchLocalPoints (:3446-3466, isInFrustum(pMP, 0.5)), SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th,
+ * bFarPoints, thFarPoints) (ORBmatcher.cc:42-143), Optimizer::PoseOptimization(&mCurrentFrame) (:3041,
+ * Optimizer.cc:1063-1452) and the statistics loop (:3074-3095).
+ * WHAT STAYS WITH THE CALLER: UpdateLocalMap (:3026); the first loop of SearchLocalPoints (:3426-3443: a bad point of the
+ * frame becomes slot -1 in feat_slots_in, mnLastFrameSeen == mnId becomes skip[i]); IncreaseVisible (in_view) and
+ * IncreaseFound (a feature that ends with a slot and no outlier flag); the choice of th (:3471-3491); the threshold on
+ * mnMatchesInliers (:3100-3130).
+ *   - F .. nlevels: as vsg_frame_search_local_points.
+ *   - feat_slots_in[i], one per feature of F: the slot of mvpMapPoints[i] on entry, < 0 for none (what
+ *     vsg_frame_track_with_motion_model returned).  No train_blocked array is sent: a feature is blocked on entry iff it
+ *     has a slot whose point is `observed` in the store (ORBmatcher.cc:86-88), which the walk kernel derives on the device.
+ *     A feature that holds an unobserved point can be taken by a local point (:130); after the walk a feature holds its
+ *     claimant's slot, or else its entry slot.  There is no rotation filter in this routine.
+ *   - Tcw, inv_level_sigma2, hold_round: as vsg_frame_pose_optimization; the intrinsics of the solve are pose's fx, fy, cx,
+ *     cy, mbf.  The solve runs whatever the search found; fewer than 3 features with a slot (Optimizer.cc:1251): their
+ *     outlier flags are cleared and res->pose holds the input pose.
+ *   - only_tracking = mbOnlyTracking (:3084); drop_outliers = (mSensor == System::STEREO) (:3092).
+ *   - feat_slots_out[i]: the slot of mvpMapPoints[i] after the walk; with drop_outliers (and no hold) an outlier's slot is -1
+ *     (:3093) and its outlier flag STAYS set (unlike the motion-model discard).  train_match (may be NULL): as
+ *     vsg_frame_search_local_points from all -1, an index into the n queried points.  outlier, chi2 (may be NULL): as
+ *     vsg_frame_pose_optimization, written only for features that end the walk with a slot.  in_view, proj_x, proj_y (n
+ *     entries each, any may be NULL): as vsg_frame_search_local_points, for IncreaseVisible and mmProjectPoints.
+ *   - res: pose = the solve's result; n_to_match = nToMatch (:3460); n_matches_searched = the search's return value;
+ *     n_matches_inliers = mnMatchesInliers: the features with a slot that are no outlier and, with only_tracking == 0, whose
+ *     point is `observed`; walk_rounds = rounds the walk kernel took to its fixed point.
+ *   - hold_round = 2 is passed through: with res->pose.held = 1 neither the statistics nor the drop are applied
+ *     (n_matches_inliers = 0, the call returns 0), feat_slots_out and outlier are as after round 1; the caller runs the plane
+ *     step, vsg_frame_pose_optimization_resume(F, ...) and both loops itself.
+ *   - n == 0, every point skipped or nothing in view: exactly vsg_frame_pose_optimization on feat_slots_in, then the
+ *     statistics.  A frame without features: returns 0 with the input pose, nothing is enqueued, no array is written.
+ * Checked before anything is enqueued, with the codes of the calls it joins: everything vsg_frame_search_local_points and
+ * vsg_frame_pose_optimization check (Nleft != -1: VSG_ERR_UNSUPPORTED); feat_slots_in == NULL or a slot >= capacity:
+ * VSG_ERR_INVALID.  DEVIATIONS: EVERY feature of F must have its octave in [0, nlevels) (any of them may end with a slot),
+ * else VSG_ERR_INVALID; 2 * features + n above about 16000 (the walk's state is one workgroup's LDS, kept to 64 KB by
+ * choice): VSG_ERR_CAPACITY -- take the two-call path for such a local map.  Candidate lists that overflow are retried
+ * as in vsg_frame_track_with_motion_model.  An error after an enqueue waits for the stream before it returns.  No error
+ * writes *res or an output array, or drops a hold that is pending on F.
+ * Returns res->n_matches_inliers, or an error code. */
+typedef struct vsg_track_local_result {
+  vsg_pose_result pose;
+  int32_t n_to_match, n_matches_searched, n_matches_inliers, walk_rounds;
+} vsg_track_local_result;
+int vsg_frame_track_local_map(vsg_frame *F, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                              const vsg_frame_pose *pose, float viewing_cos_limit, float th, float nnratio, int far_points,
+                              float th_far_points, const float *scale_factors, int nlevels, const int32_t *feat_slots_in,
+                              const vsg_pose_se3 *Tcw, const float *inv_level_sigma2, int hold_round, int only_tracking,
+                              int drop_outliers, int32_t *feat_slots_out, int32_t *train_match, uint8_t *outlier,
+                              float *chi2, uint8_t *in_view, float *proj_x, float *proj_y, vsg_track_local_result *res);
+
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, S12, th) (ORBmatcher.h:76,
  * ORBmatcher.cc:1448-1665).  Direction 1 (:1489-1565): for each KF1 feature i1 with a usable, not yet matched map
  * point that projects into KF2: idx1[k] = i1, its descriptor, (u, v, radius, predicted level) in KF2; direction 2

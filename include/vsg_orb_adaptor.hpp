@@ -791,6 +791,86 @@ class ResidentFrame {
     return poseResult(rc, res, n, outlier, chi2, out);
   }
 
+  // bool Tracking::TrackWithMotionModel() (Tracking.cc:2945-3005) in one call and one wait
+  // (vsg_frame_track_with_motion_model): this = mCurrentFrame, last = the resident mLastFrame, lastSlots[i] = the slot of
+  // its mvpMapPoints[i] (< 0: none, or an outlier); Tcw = the predicted pose, the solve's camera is curPose's.  featSlots =
+  // mvpMapPoints after the discard loop, outlier = mvbOutlier (written for matched features only).  Returns nmatches after
+  // the discard; the caller applies :3007-3016 to out.nMatches / out.nMatchesMap.
+  struct TrackMotionResult {
+    PoseOptResult pose;
+    std::vector<int32_t> featSlots, trainMatch;
+    int nSearch = 0, nMatchesSearched = 0, nMatches = 0, nMatchesMap = 0, direction = 0;
+    bool wide = false, optimized = false;
+  };
+  int TrackWithMotionModel(const ResidentFrame &last, const ResidentMapPoints &mp, const std::vector<int32_t> &lastSlots,
+                           const FramePose &curPose, const FramePose &lastPose, float mb, bool bMono, float th,
+                           const std::vector<float> &mvScaleFactors, bool checkOrientation, const vsg_pose_se3 &Tcw,
+                           const std::vector<float> &invLevelSigma2, std::vector<uint8_t> &outlier, TrackMotionResult &out,
+                           bool holdForPlaneStep = false, std::vector<float> *chi2 = nullptr) const {
+    if ((int)lastSlots.size() != last.N()) throw std::runtime_error("TrackWithMotionModel: one slot per last-frame feature");
+    if (invLevelSigma2.size() != mvScaleFactors.size())
+      throw std::runtime_error("TrackWithMotionModel: one sigma per pyramid level");
+    const size_t n = (size_t)N(), m = n ? n : 1;
+    static const int32_t none = -1;
+    outlier.resize(m, 0), out.featSlots.assign(m, -1), out.trainMatch.assign(m, -1);
+    if (chi2) chi2->resize(m, 0.f);
+    vsg_track_result res;
+    const int rc = vsg_frame_track_with_motion_model(
+        f_, last.handle(), mp.handle(), lastSlots.empty() ? &none : lastSlots.data(), &curPose, &lastPose, mb, bMono ? 1 : 0,
+        th, mvScaleFactors.data(), (int)mvScaleFactors.size(), checkOrientation ? 1 : 0, &Tcw, invLevelSigma2.data(),
+        holdForPlaneStep ? 2 : -1, out.featSlots.data(), out.trainMatch.data(), outlier.data(),
+        chi2 ? chi2->data() : nullptr, &res);
+    check(rc, "vsg_frame_track_with_motion_model");
+    out.featSlots.resize(n), out.trainMatch.resize(n);
+    out.nSearch = res.n_search, out.nMatchesSearched = res.n_matches_searched, out.nMatches = res.n_matches;
+    out.nMatchesMap = res.n_matches_map, out.direction = res.direction;
+    out.wide = res.wide != 0, out.optimized = res.optimized != 0;
+    return poseResult(rc, res.pose, n, outlier, chi2, out.pose);
+  }
+
+  // bool Tracking::TrackLocalMap() (Tracking.cc:3019-3131) from SearchLocalPoints' second loop to the statistics loop in
+  // one call and one wait (vsg_frame_track_local_map).  featSlotsIn[i] = the slot of mvpMapPoints[i] on entry (< 0: none;
+  // a bad point is the caller's to clear, :3426-3443), skip[i] != 0 = mnLastFrameSeen == mnId || isBad() (nullptr: none).
+  // out.featSlots = mvpMapPoints after the search and, with dropOutliers (mSensor == System::STEREO), the drop of :3093;
+  // outlier = mvbOutlier, written for features that hold a point after the search.  out.inView drives IncreaseVisible,
+  // a feature with a slot and no outlier flag IncreaseFound.  Returns mnMatchesInliers (0 when held: the caller runs the
+  // plane step, PoseOptimizationResume and the loop of :3074-3095 itself).
+  struct TrackLocalResult {
+    PoseOptResult pose;
+    std::vector<int32_t> featSlots, trainMatch;
+    std::vector<uint8_t> inView;
+    std::vector<float> projX, projY;
+    int nToMatch = 0, nMatchesSearched = 0, nMatchesInliers = 0, walkRounds = 0;
+  };
+  int TrackLocalMap(const ResidentMapPoints &mp, int n, const int32_t *slots, const uint8_t *skip, const FramePose &pose,
+                    float th, float nnratio, bool bFarPoints, float thFarPoints, const std::vector<float> &mvScaleFactors,
+                    const std::vector<int32_t> &featSlotsIn, const vsg_pose_se3 &Tcw,
+                    const std::vector<float> &invLevelSigma2, bool bOnlyTracking, bool dropOutliers,
+                    std::vector<uint8_t> &outlier, TrackLocalResult &out, bool holdForPlaneStep = false,
+                    std::vector<float> *chi2 = nullptr, float viewingCosLimit = 0.5f) const {
+    if ((int)featSlotsIn.size() != N()) throw std::runtime_error("TrackLocalMap: one slot per feature");
+    if (invLevelSigma2.size() != mvScaleFactors.size()) throw std::runtime_error("TrackLocalMap: one sigma per pyramid level");
+    const size_t nf = (size_t)N(), mf = nf ? nf : 1, m = n > 0 ? n : 1;
+    static const int32_t none = -1;
+    outlier.resize(mf, 0), out.featSlots.assign(mf, -1), out.trainMatch.assign(mf, -1);
+    if (chi2) chi2->resize(mf, 0.f);
+    out.inView.assign(m, 0), out.projX.assign(m, -1.f), out.projY.assign(m, -1.f);
+    vsg_track_local_result res;
+    const int rc = vsg_frame_track_local_map(
+        f_, mp.handle(), n, slots, skip, &pose, viewingCosLimit, th, nnratio, bFarPoints ? 1 : 0, thFarPoints,
+        mvScaleFactors.data(), (int)mvScaleFactors.size(), featSlotsIn.empty() ? &none : featSlotsIn.data(), &Tcw,
+        invLevelSigma2.data(), holdForPlaneStep ? 2 : -1, bOnlyTracking ? 1 : 0, dropOutliers ? 1 : 0, out.featSlots.data(),
+        out.trainMatch.data(), outlier.data(), chi2 ? chi2->data() : nullptr, out.inView.data(), out.projX.data(),
+        out.projY.data(), &res);
+    check(rc, "vsg_frame_track_local_map");
+    out.featSlots.resize(nf), out.trainMatch.resize(nf);
+    out.inView.resize(n > 0 ? n : 0), out.projX.resize(n > 0 ? n : 0), out.projY.resize(n > 0 ? n : 0);
+    out.nToMatch = res.n_to_match, out.nMatchesSearched = res.n_matches_searched;
+    out.nMatchesInliers = res.n_matches_inliers, out.walkRounds = res.walk_rounds;
+    poseResult(rc, res.pose, nf, outlier, chi2, out.pose);
+    return rc;
+  }
+
  private:
   static int poseResult(int rc, const vsg_pose_result &res, size_t n, std::vector<uint8_t> &outlier,
                         std::vector<float> *chi2, PoseOptResult &out) {

@@ -33,6 +33,43 @@ void lp_host_side(const vsg_frame_pose *pose, const float *bounds /* minX, minY,
   }
 }
 
+// The caller's loops around the two calls of a tracking step (cases track / track_local), on resident data.
+// mvpMapPoints[i] = the matched query's point, or what the feature held on entry (slots_in == nullptr: nothing)
+void tk_slots_from_matches(int nf, const int32_t *train_match, const int32_t *q_slots, const int32_t *slots_in,
+                           int32_t *feat_slots) {
+  for (int i = 0; i < nf; i++)
+    feat_slots[i] = train_match[i] >= 0 ? q_slots[train_match[i]] : (slots_in ? slots_in[i] : -1);
+}
+// a feature is blocked on entry iff it holds an observed point (ORBmatcher.cc:86-88)
+void tk_blocked_from_slots(int nf, const int32_t *slots_in, const uint8_t *observed, uint8_t *blocked) {
+  for (int i = 0; i < nf; i++) blocked[i] = slots_in[i] >= 0 && observed[slots_in[i]] ? 1 : 0;
+}
+// TrackWithMotionModel's discard loop (Tracking.cc:2980-3005): returns nmatches, *n_map = nmatchesMap
+int tk_discard(int nf, int nmatches, int32_t *feat_slots, uint8_t *outlier, const uint8_t *observed, int32_t *n_map) {
+  *n_map = 0;
+  for (int i = 0; i < nf; i++) {
+    if (feat_slots[i] < 0) continue;
+    if (outlier[i])
+      feat_slots[i] = -1, outlier[i] = 0, nmatches--;
+    else if (observed[feat_slots[i]])
+      ++*n_map;
+  }
+  return nmatches;
+}
+// TrackLocalMap's statistics loop (Tracking.cc:3074-3095): returns mnMatchesInliers
+int tk_local_stats(int nf, int32_t *feat_slots, const uint8_t *outlier, const uint8_t *observed, int only_tracking,
+                   int drop_outliers) {
+  int inliers = 0;
+  for (int i = 0; i < nf; i++) {
+    if (feat_slots[i] < 0) continue;
+    if (!outlier[i])
+      inliers += only_tracking || observed[feat_slots[i]] ? 1 : 0;
+    else if (drop_outliers)
+      feat_slots[i] = -1;
+  }
+  return inliers;
+}
+
 // the projection loop of SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:1686-1715), compacted to the
 // projected points, for vsg_frame_search_by_projection_last
 int tl_host_side(const vsg_frame_pose *pose, const float *bounds, int n, const int32_t *slots,

@@ -49,7 +49,12 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
                  header's own arithmetic, numeric Jacobian included)
             B  = vsg_frame_optimize_sim3;  A2 / B2 = both again.  Every call asserts A and B equal bit for bit
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt> [calls] [out.json]  -> runs the child, writes the record (default
+  track / track_local   Tracking's two per-frame steps as chain calls (vsg_frame_track_with_motion_model,
+            vsg_frame_track_local_map), 1000 / 2000 / 4000 points, against the caller-side path on the SAME library: the two
+            existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
+            carries them.  Both write into profiles/track_chain_latency.json, one key each
+
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -103,6 +108,11 @@ def host_side(orb):
     H.so_host_side.argtypes = [C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _i32p,
                                _f32p, _f32p, _i32p, C.c_void_p, C.c_void_p, _f32p, _f32p, C.c_int, C.c_void_p, C.c_float, C.c_int,
                                C.c_int, _u8p, C.POINTER(C.c_double), C.c_void_p]
+    H.tk_slots_from_matches.restype = H.tk_blocked_from_slots.restype = None
+    H.tk_slots_from_matches.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p]
+    H.tk_blocked_from_slots.argtypes = [C.c_int, _i32p, _u8p, _u8p]
+    H.tk_discard.argtypes = [C.c_int, C.c_int, _i32p, _u8p, _u8p, _i32p]
+    H.tk_local_stats.argtypes = [C.c_int, _i32p, _u8p, _u8p, C.c_int, C.c_int]
     H.po_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, C.c_int, _u8p, _f32p,
                                C.POINTER(C.c_double), _i32p]
     return H
@@ -175,7 +185,7 @@ class Local(Case):
         self.f = {k: np.ascontiguousarray(v) for k, v in f.items()}
         ref = fr.is_in_frustum(self.pose, self.bounds, f["world_pos"], f["normal"], f["min_dist"], f["max_dist"])
         iv = np.flatnonzero(ref["in_view"])
-        src = iv[rng.integers(0, len(iv), NFEAT)]
+        src = self.src = iv[rng.integers(0, len(iv), NFEAT)]
         x = ref["proj_x"][src] + rng.normal(0, 2.0, NFEAT).astype(np.float32)
         y = ref["proj_y"][src] + rng.normal(0, 2.0, NFEAT).astype(np.float32)
         self.frame(x, y, np.maximum(ref["scale_level"][src] - rng.integers(0, 2, NFEAT), 0), f["desc"][src], rng)
@@ -725,7 +735,143 @@ class Sim3Opt(Case):
                              "B = vsg_frame_optimize_sim3"}
 
 
-CASES = {"local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3,
+class Chain:
+    """What the two chain cases add to their search's scene: a pose per call that stays within the search windows (a
+    hundredth of a radian at most), the same pose as the solve's start, the solve's arrays, and the walk's rounds."""
+    VARIANTS = ("A", "B", "A2", "B2")
+    SIZES, DEST = (1000, 2000, 4000), "track_chain_latency.json"
+
+    def chain_arrays(self):
+        import pose_reference as pref
+        self.pref = pref
+        self.sig = (np.float32(1) / (self.sf * self.sf)).astype(np.float32)
+        z = np.zeros
+        self.fs, self.out, self.chi2 = z(NFEAT, np.int32), z(NFEAT, np.uint8), z(NFEAT, np.float32)
+        self.pres, self.qt, self.ri, self.n_map = self.orb.PoseResult(), z(7), z(6, np.int32), C.c_int32(0)
+        self.poses, self.rounds = {}, []
+
+    def pose_at(self, k):
+        k %= 50
+        if k not in self.poses:
+            a = 0.0002 * k
+            Ry = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+            po = self.pose
+            R, t = Ry @ po["Rcw"].astype(np.float64), (Ry @ po["tcw"].astype(np.float64)).astype(np.float32)
+            P = self.orb.FramePose.make(**self.fr.make_pose(R.astype(np.float32), t, po["fx"], po["fy"], po["cx"], po["cy"],
+                                                            po["mbf"]))
+            se3 = self.orb.PoseSE3()
+            se3.q[:] = [float(v) for v in self.pref.q_from_matrix(R).astype(np.float32)]
+            se3.t[:] = [float(v) for v in t]
+            self.poses[k] = (P, se3)
+        self.se3 = self.poses[k][1]
+        return self.poses[k][0]
+
+    def reset(self):
+        self.tb[:], self.tm[:], self.fs[:], self.out[:], self.chi2[:], self.qt[:], self.ri[:] = 0, -1, -1, 7, -1.0, 0, 0
+
+    def solve(self, L, P):
+        """side A's second call: vsg_frame_pose_optimization on the slots the caller's loop made"""
+        rc = L.vsg_frame_pose_optimization(self.F.handle, self.mp.handle, p(self.fs, _i32p), C.byref(self.se3), P.fx, P.fy, P.cx,
+                                           P.cy, P.mbf, p(self.sig, _f32p), 8, -1, p(self.out, _u8p), p(self.chi2, _f32p),
+                                           C.byref(self.pres))
+        assert rc >= 0, rc
+        self.take(self.pres)
+
+    def take(self, pres):
+        self.qt[:4], self.qt[4:] = pres.q[:], pres.t[:]
+        self.ri[:3] = pres.n_initial, pres.n_bad, pres.rounds_run
+
+    def result(self, name, r):
+        return (r, self.fs.copy(), self.tm.copy(), self.out.copy(), self.chi2.view(np.uint32).copy(),
+                self.qt.view(np.uint64).copy(), self.ri.copy())
+
+    def chain_facts(self, last):
+        b = last["B"]
+        f = {"returned_last": int(b[0]), "edges_last": int(b[6][0]), "n_bad_last": int(b[6][1]), "rounds_run_last": int(b[6][2]),
+             "caller_side": "A = the two existing calls of THIS library with the caller's loops between and after them "
+                            "(tools/resident_points_cpu.cpp, one thread); B = the chain call"}
+        if self.rounds:
+            f["walk_rounds"] = {"min": int(min(self.rounds)), "median": float(np.median(self.rounds)),
+                                "max": int(max(self.rounds))}
+        return f
+
+
+class Track(Chain, Last):
+    """Tracking::TrackWithMotionModel: the scene of `last` with 1000 / 2000 / 4000 points (a quarter more last-frame
+    features carry none).  A = vsg_frame_search_last_frame, the loop to mvpMapPoints, vsg_frame_pose_optimization, the
+    discard loop; B = vsg_frame_track_with_motion_model.  (The walk's status is not part of vsg_track_result: no rounds.)"""
+    TH = 7.0
+
+    def __init__(self, orb, fr, n):
+        Last.__init__(self, orb, fr, n)
+        self.chain_arrays()
+        self.tres = orb.TrackResult()
+
+    def run(self, name, L, H, P):
+        if name[0] == "B":
+            rc = L.vsg_frame_track_with_motion_model(
+                self.F.handle, self.L.handle, self.mp.handle, p(self.slots, _i32p), C.byref(P), C.byref(self.last_pose), self.mb,
+                1, self.TH, p(self.sf, _f32p), 8, 1, C.byref(self.se3), p(self.sig, _f32p), -1, p(self.fs, _i32p),
+                p(self.tm, _i32p), p(self.out, _u8p), p(self.chi2, _f32p), C.byref(self.tres))
+            assert rc >= 0 and self.tres.optimized == 1 and self.tres.wide == 0, rc
+            self.take(self.tres.pose)
+            self.ri[3] = self.tres.n_matches_map
+            return rc
+        nm = Last.B(self, L, P)
+        assert nm >= 20, nm  # the scene never needs the 2 * th search
+        H.tk_slots_from_matches(NFEAT, p(self.tm, _i32p), p(self.slots, _i32p), None, p(self.fs, _i32p))
+        self.solve(L, P)
+        nm = H.tk_discard(NFEAT, nm, p(self.fs, _i32p), p(self.out, _u8p), p(self.observed, _u8p), C.byref(self.n_map))
+        self.ri[3] = self.n_map.value
+        return nm
+
+    def facts(self, last):
+        return dict(Last.facts(self, last), **self.chain_facts(last))
+
+
+class TrackLocal(Chain, Local):
+    """Tracking::TrackLocalMap: the scene of `local`; every third feature holds the point it was made from on entry and
+    those points are flagged as seen.  A = the blocked array from the entry slots, vsg_frame_search_local_points, the loop
+    to mvpMapPoints, vsg_frame_pose_optimization, the statistics loop; B = vsg_frame_track_local_map."""
+    TH = 3.0
+
+    def __init__(self, orb, fr, n):
+        Local.__init__(self, orb, fr, n)
+        self.chain_arrays()
+        self.entry = np.where(np.arange(NFEAT) % 3 == 0, self.src, -1).astype(np.int32)
+        self.skip = np.isin(self.slots, self.entry[self.entry >= 0]).astype(np.uint8)
+        self.lres = orb.TrackLocalResult()
+
+    def run(self, name, L, H, P):
+        f = self.f
+        if name[0] == "B":
+            rc = L.vsg_frame_track_local_map(
+                self.F.handle, self.mp.handle, self.n, p(self.slots, _i32p), p(self.skip, _u8p), C.byref(P), 0.5, self.TH,
+                self.NNRATIO, 0, 0.0, p(self.sf, _f32p), 8, p(self.entry, _i32p), C.byref(self.se3), p(self.sig, _f32p), -1, 0,
+                1, p(self.fs, _i32p), p(self.tm, _i32p), p(self.out, _u8p), p(self.chi2, _f32p), p(self.in_view, _u8p),
+                p(self.px, _f32p), p(self.py, _f32p), C.byref(self.lres))
+            self.take(self.lres.pose)
+            self.ri[3], self.ri[4] = self.lres.n_to_match, self.lres.n_matches_searched
+            self.rounds.append(self.lres.walk_rounds)
+            return rc
+        H.tk_blocked_from_slots(NFEAT, p(self.entry, _i32p), p(f["observed"], _u8p), p(self.tb, _u8p))
+        nm = L.vsg_frame_search_local_points(
+            self.F.handle, self.mp.handle, self.n, p(self.slots, _i32p), p(self.skip, _u8p), C.byref(P), 0.5, self.TH,
+            self.NNRATIO, 0, 0.0, p(self.sf, _f32p), 8, p(self.tb, _u8p), p(self.tm, _i32p), p(self.in_view, _u8p),
+            p(self.px, _f32p), p(self.py, _f32p), C.byref(self.ntm))
+        assert nm >= 0, nm
+        H.tk_slots_from_matches(NFEAT, p(self.tm, _i32p), p(self.slots, _i32p), p(self.entry, _i32p), p(self.fs, _i32p))
+        self.solve(L, P)
+        self.ri[3], self.ri[4] = self.ntm.value, nm
+        return H.tk_local_stats(NFEAT, p(self.fs, _i32p), p(self.out, _u8p), p(f["observed"], _u8p), 0, 1)
+
+    def facts(self, last):
+        b = last["B"]
+        return dict(self.chain_facts(last), n_to_match_last=int(b[6][3]), nmatches_last=int(b[6][4]),
+                    entry_slots=int((self.entry >= 0).sum()))
+
+
+CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3,
          "sim3opt": Sim3Opt}
 
 
@@ -797,6 +943,10 @@ def main(argv):
         return r.returncode
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     dest.parent.mkdir(parents=True, exist_ok=True)
+    if issubclass(CASES[argv[0]], Chain):  # both chain cases share one record, one key each
+        both = json.loads(dest.read_text()) if dest.exists() else {}
+        both[argv[0]] = rec
+        rec = both
     dest.write_text(json.dumps(rec, indent=1) + "\n")
     print(json.dumps(rec))
     return 0

@@ -551,6 +551,24 @@ struct ResidentCall {
   }
 };
 
+// SearchLocalPoints' second loop and its search as vsg_frame_search_local_points and the chain call
+// (track_local_enqueue) both enqueue them: one definition of the arguments, of the fields k_frustum writes and of the gate.
+PointArgs local_point_args(const vsg_frame *F, const vsg_frame_pose *pose, int n, float viewing_cos_limit, float th,
+                           int far_points, float th_far_points, const float *scale_factors, int nlevels) {
+  PointArgs A = point_args(F, pose, n, kFrameBounds, th, scale_factors, nlevels);
+  A.viewing_cos_limit = viewing_cos_limit;
+  A.b_factor = th != 1.0;  // ORBmatcher.cc:46
+  A.far_points = far_points ? 1 : 0, A.th_far_points = th_far_points;
+  return A;
+}
+int local_enqueue(ResidentCall &call, const vsg_frame *F, const vsg_mappoints *mp, int n, const int32_t *slots,
+                  const uint8_t *skip, const PointArgs &A, bool dev_lists = false, size_t pin_extra = 0,
+                  size_t dev_extra = 0, ResidentCall::DevLists *lists = nullptr) {
+  // the stereo gate of :97-102 applies to frames with mvuRight (Nleft == -1 here)
+  return call.enqueue(F, n, slots, skip, kObserved, resident_lists(F->has_uright ? kGateUr : kGateNone),
+                      [&](const ResidentDev &R) { launch_frustum(R, mp, A); }, dev_lists, pin_extra, dev_extra, lists);
+}
+
 // The caller's arrays of the three routines that project into one KeyFrame, by name (ur: Fuse's pose form alone)
 PointOut keyframe_outs(uint8_t *projected, float *u, float *v, float *ur, int32_t *predicted_level) {
   PointOut dst = {};
@@ -627,6 +645,32 @@ int track_last_enqueue(TrackSearch *T, const vsg_frame *cur, const vsg_frame *la
   T->pin_extra = T->wc.bytes() + call.st.total, T->dev_extra = call.dev_used;
   T->d_observed = call.st.dev.observed, T->d_slots = call.st.slots;
   T->d_off = lists.off, T->d_cnt = lists.cnt, T->d_ent = lists.ent;
+  return VSG_OK;
+}
+
+int track_local_check(const vsg_frame *F, const vsg_mappoints *mp, int n, const int32_t *slots, const vsg_frame_pose *pose,
+                      const float *scale_factors, int nlevels) {
+  const int rc = resident_check(F, mp, pose, n, true, true, scale_factors, nlevels);
+  if (rc != VSG_OK) return rc;
+  return n == 0 || slots_in_store(mp, n, slots) ? VSG_OK : VSG_ERR_INVALID;
+}
+
+int track_local_enqueue(TrackSearch *T, const vsg_frame *F, const vsg_mappoints *mp, int n, const int32_t *slots,
+                        const uint8_t *skip, const vsg_frame_pose *pose, float viewing_cos_limit, float th, int far_points,
+                        float th_far_points, const float *scale_factors, int nlevels, size_t pin_extra_bytes,
+                        size_t dev_extra_bytes) {
+  const PointArgs A = local_point_args(F, pose, n, viewing_cos_limit, th, far_points, th_far_points, scale_factors, nlevels);
+  ResidentCall call;
+  ResidentCall::DevLists lists = {};
+  const int rc = local_enqueue(call, F, mp, n, slots, skip, A, true, pin_extra_bytes, dev_extra_bytes, &lists);
+  if (rc != VSG_OK) return rc;
+  T->wc = call.wc;
+  call.wc.range_open = false;  // T->wc pops the range now
+  T->c = T->wc.c, T->nq = n, T->list_total = (int)lists.entries;
+  T->pin_extra = T->wc.bytes() + call.st.total, T->dev_extra = call.dev_used;
+  T->d_observed = call.st.dev.observed, T->d_slots = call.st.slots;
+  T->d_off = lists.off, T->d_cnt = lists.cnt, T->d_ent = lists.ent;
+  T->d_valid = call.st.dev.valid, T->h_valid = call.st.host.valid, T->h_x = call.st.host.x, T->h_y = call.st.host.y;
   return VSG_OK;
 }
 
@@ -863,17 +907,13 @@ int vsg_frame_search_local_points(vsg_frame *F, vsg_mappoints *mp, int n, const 
   if (n_to_match) *n_to_match = 0;
   if (n == 0) return 0;
   if (!slots_in_store(mp, n, slots)) return VSG_ERR_INVALID;
-  PointArgs A = point_args(F, pose, n, kFrameBounds, th, scale_factors, nlevels);
-  A.viewing_cos_limit = viewing_cos_limit;
-  A.b_factor = th != 1.0;  // ORBmatcher.cc:46
-  A.far_points = far_points ? 1 : 0, A.th_far_points = th_far_points;
+  const PointArgs A = local_point_args(F, pose, n, viewing_cos_limit, th, far_points, th_far_points, scale_factors, nlevels);
   PointOut dst = {};
   dst.valid = in_view, dst.x = proj_x, dst.y = proj_y;
   return with_retry([&]() -> int {
     ResidentCall call;
-    // the stereo gate of :97-102 applies to frames with mvuRight (Nleft == -1 here)
-    rc = call.run(F, n, slots, skip, kObserved, resident_lists(F->has_uright ? kGateUr : kGateNone),
-                  [&](const ResidentDev &R) { launch_frustum(R, mp, A); });
+    rc = local_enqueue(call, F, mp, n, slots, skip, A);
+    if (rc == VSG_OK) rc = call.wc.finish();
     if (rc != VSG_OK) return rc;
     const PointOut &h = call.st.host;
     int to_match = 0;

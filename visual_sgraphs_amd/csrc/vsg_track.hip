@@ -11,10 +11,17 @@
 // edge list in feature order -- with the per-feature and per-query state in LDS.  It sits IN FRONT of the optimisation,
 // not inside it: k_pose_optimize already runs at its register limit.  The matches never leave the device between the
 // search and the solve; the host reads them once, after the wait, together with the pose.
+//
+// Tracking::TrackLocalMap (Tracking.cc:3019-3131) is the same chain behind k_frustum: vsg_frame_track_local_map.  The walk
+// runs in its local form (q_valid = mbTrackInView, the ratio test) and is given the features' slots on entry instead of a
+// blocked array: k_track_walk's prologue derives "blocked on entry" from them and the store's observed flags, and
+// walkdev::run keeps the entry slot of every feature nobody claims.  The statistics loop that ends the routine runs on the
+// host after the wait (vsg_track_stats.h).
 #include <cstring>
 #include <vector>
 
 #include "vsg_track_int.h"
+#include "vsg_track_stats.h"
 #include "vsg_walks_dev.h"
 
 using namespace vsg;
@@ -76,7 +83,17 @@ __global__ __launch_bounds__(kWalkThreads) void k_track_walk(walkdev::Args A) {
     b_obs[q] = A.observed ? A.observed[q] : 0;
     b_valid[q] = A.q_valid ? A.q_valid[q] : 1;
   }
-  for (int i = threadIdx.x; i < A.nf; i += kWalkThreads) b_blk[i] = A.blocked_in ? A.blocked_in[i] : 0;
+  // Without a blocked array but with the features' entry slots (the local-map form): a feature is blocked on entry iff
+  // its point is observed (ORBmatcher.cc:86-88).  The host bounded every slot by the store's capacity.
+  const bool from_slots = !A.blocked_in && A.slots_in && A.slot_observed;
+  for (int i = threadIdx.x; i < A.nf; i += kWalkThreads) {
+    uint8_t b = A.blocked_in ? A.blocked_in[i] : 0;
+    if (from_slots) {
+      const int s = A.slots_in[i];
+      b = s >= 0 ? A.slot_observed[s] : 0;
+    }
+    b_blk[i] = b;
+  }
   A.observed = b_obs, A.q_valid = b_valid, A.blocked_in = b_blk;
   __syncthreads();
   DevTeam T = {wsum};
@@ -86,13 +103,15 @@ __global__ __launch_bounds__(kWalkThreads) void k_track_walk(walkdev::Args A) {
 // The caller's block of a chain call behind the search's blocks.  Pinned: what the host reads after the wait.  Device: the
 // edge list and the status.
 struct TrackLayout {
-  size_t pTm, pTb, pFs, pFo, pStatus, pPose, pin_total;
+  size_t pTm, pTb, pFs, pFo, pStatus, pPose, pSlotsIn, pin_total;
   size_t dFeat, dSlot, dStatus, dev_total;
-  explicit TrackLayout(int nf) {
+  // entry_slots: room for the features' slots on entry (the local-map form sends them; the walk reads them)
+  explicit TrackLayout(int nf, bool entry_slots = false) {
     const size_t N = (size_t)(nf > 0 ? nf : 1);
     Stage sp;
     pTm = sp.add(N * 4), pTb = sp.add(N), pFs = sp.add(N * 4), pFo = sp.add(N), pStatus = sp.add(sizeof(walkdev::Status));
     pPose = sp.add(pose_chain_bytes(nf));
+    pSlotsIn = sp.add(entry_slots ? N * 4 : 0);
     pin_total = sp.total;
     Stage sd;
     dFeat = sd.add(N * 4), dSlot = sd.add(N * 4), dStatus = sd.add(sizeof(walkdev::Status));
@@ -236,6 +255,90 @@ int vsg_frame_track_with_motion_model(vsg_frame *cur, vsg_frame *last, vsg_mappo
   R.n_matches = n_matches, R.n_matches_map = n_map;
   *res = R;
   return n_matches;
+}
+
+int vsg_frame_track_local_map(vsg_frame *F, vsg_mappoints *mp, int n, const int32_t *slots, const uint8_t *skip,
+                              const vsg_frame_pose *pose, float viewing_cos_limit, float th, float nnratio, int far_points,
+                              float th_far_points, const float *scale_factors, int nlevels, const int32_t *feat_slots_in,
+                              const vsg_pose_se3 *Tcw, const float *inv_level_sigma2, int hold_round, int only_tracking,
+                              int drop_outliers, int32_t *feat_slots_out, int32_t *train_match, uint8_t *outlier,
+                              float *chi2, uint8_t *in_view, float *proj_x, float *proj_y, vsg_track_local_result *res) {
+  if (!Tcw || !inv_level_sigma2 || !res || !outlier || !feat_slots_out || !feat_slots_in) return VSG_ERR_INVALID;
+  if (hold_round != -1 && hold_round != 2) return VSG_ERR_INVALID;
+  if (nlevels < 1 || nlevels > 16) return VSG_ERR_INVALID;
+  int rc = track_local_check(F, mp, n, slots, pose, scale_factors, nlevels);
+  if (rc != VSG_OK) return rc;
+  StoreView S;
+  if (!store_view(mp, &S) || !octaves_in_pyramid(F, nlevels)) return VSG_ERR_INVALID;
+  const int nf = F->n, nq = n;
+  for (int i = 0; i < nf; i++)
+    if (feat_slots_in[i] >= S.capacity) return VSG_ERR_INVALID;
+  // everything the kernels index has been bounded; nothing has been enqueued
+  if (nf > 0 && walk_lds_bytes(nq, nf) + kWalkStaticLds > kWalkLdsMax) return VSG_ERR_CAPACITY;
+  // an error from here on leaves *res, the outputs and a pending hold as they were: R becomes *res on success only
+  vsg_track_local_result R;
+  memset(&R, 0, sizeof(R));
+  pose_result_input(Tcw, 0, &R.pose);
+  if (nf == 0) {  // no feature to match or to solve with: nothing is enqueued, the per-query outs stay as they are
+    *res = R;
+    return 0;
+  }
+  std::vector<int32_t> own_slots;  // slots == NULL is slot i: the walk reads the queries' slots from the staged list
+  if (!slots && nq > 0) {
+    own_slots.resize((size_t)nq);
+    for (int i = 0; i < nq; i++) own_slots[(size_t)i] = i;
+    slots = own_slots.data();
+  }
+  const TrackLayout L(nf, true);
+  walkdev::Status st;
+  TrackSearch T;
+  rc = with_retry([&]() -> int {
+    T = TrackSearch();
+    int r = track_local_enqueue(&T, F, mp, nq, slots, skip, pose, viewing_cos_limit, th, far_points, th_far_points,
+                                scale_factors, nlevels, L.pin_total, L.dev_total);
+    if (r != VSG_OK) return r;
+    memcpy(T.c->h_pin + T.pin_extra + L.pSlotsIn, feat_slots_in, (size_t)nf * 4);
+    walkdev::Args A;
+    memset(&A, 0, sizeof(A));
+    A.form = walkdev::kFormLocal, A.nq = nq, A.nf = nf;
+    A.check_orientation = 0, A.min_matches = 0, A.nnratio = nnratio;  // no rotation filter; the solve always runs
+    A.q_valid = T.d_valid, A.observed = T.d_observed;
+    A.q_slot = T.d_slots, A.slot_observed = store_observed_dev(mp);
+    // blocked on entry = the entry slot's point is observed: k_track_walk derives it from these two
+    A.slots_in = (const int32_t *)(T.c->d_pin + T.pin_extra + L.pSlotsIn);
+    return walk_solve_wait(T, L, A, F, S, Tcw, pose, inv_level_sigma2, nlevels, hold_round, &st);
+  });
+  if (rc != VSG_OK) return rc;
+  const uint8_t *hp = T.c->h_pin + T.pin_extra;
+  const int32_t *tm = (const int32_t *)(hp + L.pTm), *fs = (const int32_t *)(hp + L.pFs);
+  const uint8_t *fo = hp + L.pFo;
+  std::vector<int32_t> feat;  // the edge list read back: the features with a slot, ascending
+  for (int i = 0; i < nf; i++)
+    if (fs[i] >= 0) feat.push_back(i);
+  const bool solved = !(st.flags & walkdev::kStFewEdges);
+  if ((int)feat.size() != st.n_edges) return VSG_ERR_HIP;
+  int to_match = 0;  // nToMatch (Tracking.cc:3460)
+  for (int q = 0; q < nq; q++) to_match += T.h_valid[q];
+  R.n_to_match = to_match, R.n_matches_searched = st.nmatches, R.walk_rounds = st.rounds;
+  memcpy(feat_slots_out, fs, (size_t)nf * 4);
+  if (train_match) memcpy(train_match, tm, (size_t)nf * 4);
+  if (in_view && nq > 0) memcpy(in_view, T.h_valid, (size_t)nq);
+  if (proj_x && nq > 0) memcpy(proj_x, T.h_x, (size_t)nq * 4);
+  if (proj_y && nq > 0) memcpy(proj_y, T.h_y, (size_t)nq * 4);
+  if (!solved) {  // Optimizer.cc:1251
+    for (int i = 0; i < nf; i++)
+      if (fs[i] >= 0) outlier[i] = 0;
+    pose_result_input(Tcw, st.n_edges, &R.pose);
+  } else {
+    pose_chain_finish(F, T.c, T.pin_extra + L.pPose, feat.data(), st.n_edges, outlier, chi2, &R.pose);
+    if (R.pose.held) {  // the caller runs the plane step, _resume, the statistics and the drop
+      *res = R;
+      return 0;
+    }
+  }
+  R.n_matches_inliers = track_local_stats(nf, feat_slots_out, outlier, fo, only_tracking, drop_outliers);  // :3074-3095
+  *res = R;
+  return R.n_matches_inliers;
 }
 
 }  // extern "C"

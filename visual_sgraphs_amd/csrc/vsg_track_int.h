@@ -1,4 +1,5 @@
-// vsg_track_int.h -- the halves of a chain call (vsg_track.hip: vsg_frame_track_with_motion_model)
+// vsg_track_int.h -- the halves of a chain call (vsg_track.hip: vsg_frame_track_with_motion_model,
+// vsg_frame_track_local_map)
 // that live beside the kernels they enqueue: the projection + window search (vsg_mappoints.hip) with its candidate lists
 // left in the DEVICE arena, and the pose optimisation (vsg_pose.hip) taking its edges from the walk kernel's buffer.
 // Nothing here waits: the entry point owns the one wait of the call.
@@ -18,6 +19,10 @@ struct TrackSearch {
   const int32_t *d_slots = nullptr;  // the caller's slot list in the pinned arena (device alias; nullptr: slot i)
   const int32_t *d_off = nullptr, *d_cnt = nullptr;  // the lists, device arena
   const uint32_t *d_ent = nullptr;
+  // the local-map form: mbTrackInView per query for the walk (device alias), and the host side of the fields the caller
+  // may ask for after the wait
+  const uint8_t *d_valid = nullptr, *h_valid = nullptr;
+  const float *h_x = nullptr, *h_y = nullptr;
 };
 
 // vsg_frame_search_last_frame's checks in its order and with its codes; *dir = bForward / bBackward
@@ -28,6 +33,15 @@ int track_last_check(const vsg_frame *cur, const vsg_frame *last, const vsg_mapp
 int track_last_enqueue(TrackSearch *T, const vsg_frame *cur, const vsg_frame *last, const vsg_mappoints *mp,
                        const int32_t *last_slots, const vsg_frame_pose *cur_pose, float th, int dir,
                        const float *scale_factors, int nlevels, size_t pin_extra_bytes, size_t dev_extra_bytes);
+// vsg_frame_search_local_points' checks in its order and with its codes (its own output arrays apart)
+int track_local_check(const vsg_frame *F, const vsg_mappoints *mp, int n, const int32_t *slots, const vsg_frame_pose *pose,
+                      const float *scale_factors, int nlevels);
+// k_frustum and k_window_search on the calling thread's stream, as vsg_frame_search_local_points launches them.  slots must
+// not be nullptr (the walk reads the queries' slots from the staged list); n == 0 enqueues nothing.
+int track_local_enqueue(TrackSearch *T, const vsg_frame *F, const vsg_mappoints *mp, int n, const int32_t *slots,
+                        const uint8_t *skip, const vsg_frame_pose *pose, float viewing_cos_limit, float th, int far_points,
+                        float th_far_points, const float *scale_factors, int nlevels, size_t pin_extra_bytes,
+                        size_t dev_extra_bytes);
 const uint8_t *store_observed_dev(const vsg_mappoints *mp);  // Observations() > 0 per slot, on the device
 
 // The solve half.  Pinned block of pose_chain_bytes(nf) at pin_base: [flags | chi2 | result header].

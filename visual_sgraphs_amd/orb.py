@@ -87,6 +87,8 @@ EXPORTS = [
     "vsg_frame_pose_optimization", "vsg_frame_pose_optimization_resume",
     # Tracking::TrackWithMotionModel: search, ordered walk and PoseOptimization in one enqueue and one wait
     "vsg_frame_track_with_motion_model",
+    # Tracking::TrackLocalMap: frustum, search, ordered walk, PoseOptimization and the statistics in one enqueue and one wait
+    "vsg_frame_track_local_map",
     # LocalMapping::CreateNewMapPoints on resident keyframes: triangulate, gate, write the new points into the store
     "vsg_frame_set_stereo_points", "vsg_frame_triangulate_matches", "vsg_frame_create_new_map_points",
     # Sim3Solver on resident map points: every RANSAC hypothesis in one call, and the host-side set-up of the solver
@@ -169,6 +171,12 @@ class TrackResult(C.Structure):
     """include/vsg_orb.h vsg_track_result."""
     _fields_ = [("pose", PoseResult)] + [(k, C.c_int32) for k in (
         "n_search", "wide", "n_matches_searched", "optimized", "n_matches", "n_matches_map", "direction", "pad")]
+
+
+class TrackLocalResult(C.Structure):
+    """include/vsg_orb.h vsg_track_local_result."""
+    _fields_ = [("pose", PoseResult)] + [(k, C.c_int32) for k in (
+        "n_to_match", "n_matches_searched", "n_matches_inliers", "walk_rounds")]
 
 
 class Sim3Result(C.Structure):
@@ -446,6 +454,9 @@ def load_library():
     L.vsg_frame_track_with_motion_model.argtypes = [vp, vp, vp, _i32p, C.POINTER(FramePose), C.POINTER(FramePose), cf, ci,
                                                     cf, _f32p, ci, ci, C.POINTER(PoseSE3), _f32p, ci, _i32p, _i32p, _u8p,
                                                     _f32p, C.POINTER(TrackResult)]
+    L.vsg_frame_track_local_map.argtypes = [vp, vp, ci, _i32p, _u8p, C.POINTER(FramePose), cf, cf, cf, ci, cf, _f32p, ci,
+                                            _i32p, C.POINTER(PoseSE3), _f32p, ci, ci, ci, _i32p, _i32p, _u8p, _f32p, _u8p,
+                                            _f32p, _f32p, C.POINTER(TrackLocalResult)]
     tri_tail = [C.POINTER(TriangulationParams), _f32p, _f32p, _f32p, _f32p, ci, vp, _i32p, ci]
     tri_outs = [_u8p, _u8p, _f32p, _i32p, _i32p]
     L.vsg_frame_set_stereo_points.argtypes = [vp, _f32p, _f32p]
@@ -1729,6 +1740,45 @@ class Frame:
         d = self._pose_result(ret, res.pose, out[:n], c2[:n])
         d.update(feat_slots=fs[:n], train_match=tm[:n])
         d.update({k: int(getattr(res, k)) for k, _ in TrackResult._fields_[1:-1]})
+        return d
+
+    # ---- Tracking::TrackLocalMap (Tracking.cc:3019-3131) on resident map points: frustum, search, ordered walk,
+    # PoseOptimization and the statistics loop in one enqueue and one wait
+    def TrackLocalMap(self, mp, pose, th, nnratio, scale_factors, feat_slots, q, t, inv_level_sigma2, outlier, n=None,
+                      slots=None, skip=None, viewing_cos_limit=0.5, far_points=False, th_far_points=0.0, hold_round=-1,
+                      only_tracking=False, drop_outliers=False, chi2=None):
+        """The arguments of SearchLocalPoints and pose_optimization (the camera is pose's); feat_slots[i] = the slot of
+        mvpMapPoints[i] on entry (< 0: none), e.g. TrackWithMotionModel's feat_slots.  outlier / chi2 are updated IN A COPY.
+        Returns a dict: ret (= n_matches_inliers), feat_slots (after the walk and the drop), train_match, outlier, chi2,
+        in_view, proj_x, proj_y, q, t, n_initial, n_bad, rounds_run, held, n_to_match, n_matches_searched,
+        n_matches_inliers, walk_rounds."""
+        nf = len(self.kps)
+        if len(feat_slots) != nf:
+            raise ValueError("feat_slots length does not match the frame's features")
+        n, slp, skp, o, trimmed = self._resident_points(slots, skip, (np.uint8, np.float32, np.float32),
+                                                        mp.capacity if n is None else n, "the map points")
+        sf, sig = _f32(scale_factors), _f32(inv_level_sigma2)
+        if len(sf) != len(sig):
+            raise ValueError("inv_level_sigma2 length does not match the scale factors")
+        fin = np.full(max(nf, 1), -1, np.int32)
+        fin[:nf] = _i32(feat_slots)
+        out = np.zeros(max(nf, 1), np.uint8)
+        out[:nf] = _u8(outlier)
+        c2 = np.zeros(max(nf, 1), np.float32)
+        if chi2 is not None:
+            c2[:nf] = _f32(chi2)
+        fs, tm = np.full(max(nf, 1), -1, np.int32), np.full(max(nf, 1), -1, np.int32)
+        res = TrackLocalResult()
+        ret = _check(self._L.vsg_frame_track_local_map(
+            self._h, mp.handle, n, slp, skp, C.byref(pose), float(np.float32(viewing_cos_limit)), float(th),
+            float(np.float32(nnratio)), int(bool(far_points)), float(np.float32(th_far_points)), _p(sf, _f32p), len(sf),
+            _p(fin, _i32p), C.byref(self._se3(q, t)), _p(sig, _f32p), int(hold_round), int(bool(only_tracking)),
+            int(bool(drop_outliers)), _p(fs, _i32p), _p(tm, _i32p), _p(out, _u8p), _p(c2, _f32p), *o, C.byref(res)),
+            "vsg_frame_track_local_map")
+        d = self._pose_result(ret, res.pose, out[:nf], c2[:nf])
+        d.update(feat_slots=fs[:nf], train_match=tm[:nf])
+        d.update(zip(("in_view", "proj_x", "proj_y"), trimmed()))
+        d.update({k: int(getattr(res, k)) for k, _ in TrackLocalResult._fields_[1:]})
         return d
 
     # ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, ...) on resident map points
