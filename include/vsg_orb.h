@@ -1277,6 +1277,57 @@ int vsg_shard_send_recv_boundary(vsg_shard *s, const int *d_counts, const vsg_ke
                                  int src_capacity, int frame, void *stream);
 int vsg_shard_boundary_record(vsg_shard *s, const int **d_counts, const vsg_keypoint **d_kps, const uint8_t **d_desc);
 
+/* The visual part of void Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, ...) (Optimizer.cc:1454-2454) on
+ * resident keyframes and resident map points: the keyframe vertices (:1762-1793), the point vertices and their monocular
+ * and stereo edges (:1850-1948), optimize(iterations) (:2288), the classification (:2296-2340) and the recovery
+ * (:2398-2414), in double, with the arithmetic of csrc/vsg_local_ba.h, which a host build reproduces bit for bit (DESIGN.md
+ * section 8).  The marker, plane, room and door vertices and their edges (:1995-2274, :2342-2369, :2416-2452) are NOT
+ * part of it: a caller whose local lists of those are not empty keeps the reference routine.
+ *   - Point i = slot slots[i] of mp, with the observations [obs_off[i], obs_off[i + 1]) of obs_kf (index into kfs) and
+ *     obs_idx (leftIndex in that keyframe), as vsg_mappoints_refresh_from_observations takes them: the observations that
+ *     pass !pKFi->isBad() && GetMap() == pCurrentMap (:1881), in mObservations' order.  The edges are these entries in this
+ *     order (g2o's insertion order); edge e is stereo when that keyframe's u_right[idx] >= 0 (:1886, :1913), else mono.
+ *   - kfs = the local keyframes AND the fixed ones, resident with mvKeysUn and mvuRight, in ascending mnId; kf_Tcw[k] =
+ *     GetPose(); kf_fixed[k] != 0 for lFixedCameras and for the map's initial keyframe (:1772, :1789); kf_cam[k] = that
+ *     keyframe's fx, fy, cx, cy, mbf.  inv_level_sigma2 = mvInvLevelSigma2, nlevels entries.  iterations = 10 at :2288.
+ *   - stop_flag (may be NULL) = pbStopFlag: read before optimising (:2283) and each time the host looks at the solver's
+ *     state between iterations; a set flag then ends the run with stop_reason 3.  The kernels never read it.
+ *   - kf_Tcw_out[k]: an optimised keyframe with at least one edge gets vSE3->estimate(); every other keyframe (fixed, or
+ *     without an edge: g2o drops such a vertex) gets its input, widened.  world_pos_out[3 i] (may be NULL) = the float
+ *     position of point i, ALSO written into the slot's world_pos on the device (SetWorldPos, :2412); a point with an
+ *     empty list is no vertex: its slot keeps its bytes and its out is what the slot holds.  The other fields of the slots
+ *     are untouched: follow with vsg_mappoints_refresh_from_observations(VSG_REFRESH_NORMAL) (:2413).
+ *   - erase[e] = whether (keyframe, point) of observation e goes into vToErase; chi2[e] (may be NULL) = the double
+ *     compared, NaN canonical: e->chi2() as the LAST computeActiveErrors left it (after a rejected last trial that is the
+ *     rejected state's), compared with > 5.991 / > 7.815; isDepthPositive() on the restored estimates.
+ *   - res->ran = 0: the reference returned before optimize -- no fixed keyframe (:1734), no edge (:2277), the stop flag
+ *     (:2283) -- or n_points == 0; nothing is enqueued and no out but res is written.  stop_reason: 0 = the iterations
+ *     are done, 1 = Terminate (qmax == 10 || rho == 0), 2 = _nBad >= 3, 3 = the stop flag.
+ * Checked before anything is enqueued (an error writes nothing and leaves no kernel behind), VSG_ERR_INVALID: a NULL mp,
+ * slots, obs_off, kfs, a keyframe, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2, kf_Tcw_out, erase or res; obs_kf / obs_idx
+ * NULL with observations; offsets that do not ascend from 0; an observation outside [0, n_kf) x [0, N of that keyframe); a
+ * slot outside [0, capacity) or listed twice; nlevels outside [1, 16]; an observed keypoint's octave >= nlevels;
+ * iterations outside [1, 100]; a keyframe on another device than the store.  VSG_ERR_UNSUPPORTED: a keyframe with
+ * Nleft != -1 (EdgeSE3ProjectXYZToBody, KannalaBrandt8: :1950-1989), edges but no optimised keyframe with one, more than
+ * 128 optimised keyframes with edges (the reduced system's one code path holds 768 rows).
+ * The scratch lives in the calling thread's arena: two threads may solve on the same store at the same time ONLY when
+ * their point sets are disjoint (each writes its points' world_pos).  The call waits for its stream before it returns,
+ * on an error too. */
+typedef struct vsg_pose_se3d { double q[4], t[3]; } vsg_pose_se3d;
+typedef struct vsg_ba_camera { float fx, fy, cx, cy, bf; } vsg_ba_camera;
+typedef struct vsg_local_ba_result {
+  int32_t ran;              /* 0: returned before optimize (:1734 no fixed keyframe, :2277 no edge, :2283 stop flag) */
+  int32_t n_opt_kf, n_fixed_kf, n_points, n_edges, n_mono, n_stereo, n_erase;
+  int32_t iterations_run, trials_run, stop_reason;   /* iterations done | Terminate | nBad >= 3 */
+  double lambda, chi2_initial, chi2_final;
+} vsg_local_ba_result;
+int vsg_mappoints_local_bundle_adjustment(
+    vsg_mappoints *mp, int n_points, const int32_t *slots,
+    const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx,   /* as vsg_mappoints_refresh_from_observations */
+    int n_kf, vsg_frame *const *kfs, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed, const vsg_ba_camera *kf_cam,
+    const float *inv_level_sigma2, int nlevels, int iterations, const volatile uint8_t *stop_flag,
+    vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *erase, double *chi2, vsg_local_ba_result *res);
+
 #ifdef __cplusplus
 }
 #endif

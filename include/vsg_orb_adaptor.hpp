@@ -544,6 +544,17 @@ struct RefreshResult {
   std::vector<float> normal, minDist, maxDist;
 };
 
+// What vsg::ResidentMapPoints::LocalBundleAdjustment returns: vSE3->estimate() per keyframe (a fixed keyframe, or one
+// without an edge: its input, widened), the float position per point (also written into its slot), per observation whether
+// (keyframe, point) goes into vToErase and the chi2 compared, and the counters of vsg_local_ba_result.
+struct LocalBAResult {
+  std::vector<vsg_pose_se3d> kfTcw;
+  std::vector<float> worldPos;
+  std::vector<uint8_t> erase;
+  std::vector<double> chi2;
+  vsg_local_ba_result res;
+};
+
 class ResidentMapPoints {
  public:
   explicit ResidentMapPoints(int capacity, int device = 0) {
@@ -583,6 +594,43 @@ class ResidentMapPoints {
                                                   mvScaleFactors.data(), (int)mvScaleFactors.size(), what, r.best.data(),
                                                   r.normal.data(), r.minDist.data(), r.maxDist.data()),
           "vsg_mappoints_refresh_from_observations");
+    return r;
+  }
+  // The visual part of Optimizer::LocalBundleAdjustment (Optimizer.cc:1454-2454) on the device
+  // (vsg_mappoints_local_bundle_adjustment): point i = slot slots[i] with the observations [obsOff[i], obsOff[i + 1]) of
+  // obsKf (index into keyFrames: the local keyframes AND the fixed ones, ascending mnId) and obsIdx (leftIndex), as
+  // Refresh takes them, filtered by !pKFi->isBad() && GetMap() == pCurrentMap.  kfTcw = GetPose() per keyframe, kfFixed
+  // != 0 for lFixedCameras and the map's initial keyframe, kfCam = fx, fy, cx, cy, mbf.  The points' new positions are
+  // written into the slots; follow with Refresh(..., VSG_REFRESH_NORMAL).  Marker, plane, room and door vertices are
+  // not part of it: keep the reference routine when the keyframe's local lists of those are not empty.
+  LocalBAResult LocalBundleAdjustment(const std::vector<int32_t> &slots, const std::vector<int32_t> &obsOff,
+                                      const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                                      const std::vector<vsg_frame *> &keyFrames, const std::vector<vsg_pose_se3> &kfTcw,
+                                      const std::vector<uint8_t> &kfFixed, const std::vector<vsg_ba_camera> &kfCam,
+                                      const std::vector<float> &mvInvLevelSigma2, int iterations = 10,
+                                      const volatile uint8_t *pbStopFlag = nullptr) {
+    const size_t n = slots.size(), K = keyFrames.size();
+    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || kfTcw.size() != K || kfFixed.size() != K ||
+        kfCam.size() != K || (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())))
+      throw std::runtime_error("ResidentMapPoints::LocalBundleAdjustment: the arrays' sizes do not match");
+    const size_t E = n ? (size_t)obsOff[n] : 0;
+    LocalBAResult r;
+    r.kfTcw.resize(K), r.worldPos.assign(3 * n, 0.0f), r.erase.assign(E, 0), r.chi2.assign(E, 0.0);
+    vsg_pose_se3d none_kf;
+    uint8_t none_erase = 0;
+    check(vsg_mappoints_local_bundle_adjustment(mp_, (int)n, slots.data(), obsOff.data(), obsKf.data(), obsIdx.data(), (int)K,
+                                                keyFrames.data(), kfTcw.data(), kfFixed.data(), kfCam.data(),
+                                                mvInvLevelSigma2.data(), (int)mvInvLevelSigma2.size(), iterations, pbStopFlag,
+                                                K ? r.kfTcw.data() : &none_kf, n ? r.worldPos.data() : nullptr,
+                                                E ? r.erase.data() : &none_erase, E ? r.chi2.data() : nullptr, &r.res),
+          "vsg_mappoints_local_bundle_adjustment");
+    if (!r.res.ran) {  // the reference returned before optimize: nothing was written, the outs are the inputs
+      for (size_t k = 0; k < K; ++k)
+        for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
+      if (n)
+        check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+              "vsg_mappoints_read");
+    }
     return r;
   }
   vsg_mappoints *handle() const { return mp_; }

@@ -1,0 +1,306 @@
+"""vsg_mappoints_local_bundle_adjustment on the GPU (the visual part of Optimizer::LocalBundleAdjustment on resident
+keyframes and resident map points) against the host build of the same header (tests/_localbacore) BIT FOR BIT -- return
+value, res, kf_Tcw_out, world_pos_out, erase and chi2 -- and against tests/lba_reference.py (the NumPy restatement) under
+the measured tolerance of tests/lba_scenes.py with all flags equal.  Every scene of lba_scenes.scenes(); no edge is excluded
+from any comparison."""
+import ctypes as C
+import subprocess
+import threading
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import lba_hostcore as hc
+import lba_scenes as ls
+from test_lba_hostmath import check_against_reference, error_cases
+from visual_sgraphs_amd import orb
+
+pytestmark = pytest.mark.gpu
+ADAPTOR = Path(__file__).resolve().parent / "_adaptor_localba"
+BOUNDS = (0.0, 0.0, 640.0, 480.0)
+U8, F32, I32, F64 = np.uint8, np.float32, np.int32, np.float64
+NAMES = list(ls.scenes())
+INVALID, UNSUPPORTED = -6, -3  # include/vsg_orb.h: VSG_ERR_INVALID, VSG_ERR_UNSUPPORTED
+FIELDS = ("world_pos", "normal", "min_dist", "max_dist", "desc", "observed")
+
+
+def upload(f, nleft=-1):
+    n = len(f["x"])
+    kps = np.zeros(n, orb.KP_DTYPE)
+    kps["x"], kps["y"], kps["octave"], kps["size"], kps["angle"] = f["x"], f["y"], f["octave"], 31.0, -1.0
+    return orb.Frame(n + 1).upload(kps, np.zeros((n, 32), U8), BOUNDS, u_right=f["ur"], nleft=nleft)
+
+
+class Device:
+    """A scene's keyframes and its store on the device; every field of every slot holds seeded values."""
+
+    def __init__(self, s, nleft=None):
+        self.s = s
+        self.kfs = [upload(f, -1 if nleft is None else int(nleft[k])) for k, f in enumerate(s["kfs"])]
+        cap = s["capacity"]
+        rng = np.random.default_rng(cap)
+        self.fields = dict(world_pos=np.ascontiguousarray(s["store_pos"], F32), normal=rng.normal(0, 1, (cap, 3)).astype(F32),
+                           min_dist=rng.uniform(1, 2, cap).astype(F32), max_dist=rng.uniform(5, 9, cap).astype(F32),
+                           desc=rng.integers(0, 256, (cap, 32)).astype(U8), observed=rng.integers(0, 2, cap).astype(U8))
+        self.mp = orb.MapPoints(cap)
+        self.reset()
+
+    def reset(self):
+        self.mp.update(np.arange(self.s["capacity"]), **self.fields)
+
+    def store(self):
+        return self.mp.read(np.arange(self.s["capacity"]))
+
+    def call(self, stop_flag=None, null=(), trial_slots=0, reset=True, read=True, **over):
+        """One raw call of the C entry in the form of lba_hostcore.run: sentinels in every out, NULL for the names in
+        `null`; the store is put back to the scene's values first."""
+        if reset:
+            self.reset()
+        s = dict(self.s, **over)
+        a = hc.marshal(s)
+        L = orb.load_library()
+        handles = (C.c_void_p * max(a["K"], 1))(*[f.handle for f in self.kfs])
+        flag = None if stop_flag is None else np.array([stop_flag], U8)
+        res = orb.LocalBaResult()  # the binding's own type: test_abi_lba.py holds its layout to the header's
+        C.memset(C.addressof(res), 0x5A, C.sizeof(res))
+        arg = lambda name, v, t: None if name in null else v.ctypes.data_as(t)
+        ip, fp, bp, dp = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+        if trial_slots:
+            assert L.vsg_debug_local_ba_trial_slots(trial_slots) == 0
+        try:
+            rc = L.vsg_mappoints_local_bundle_adjustment(
+                self.mp.handle, a["P"], arg("slots", a["slots"], ip), arg("obs_off", a["off"], ip), arg("obs_kf", a["kf"], ip),
+                arg("obs_idx", a["idx"], ip), a["K"], handles,
+                None if "kf_Tcw" in null else C.cast(a["Tcw"].ctypes.data, C.POINTER(orb.PoseSE3)), arg("kf_fixed", a["fixed"], bp),
+                None if "kf_cam" in null else C.cast(a["cam"].ctypes.data, C.POINTER(orb.BaCamera)),
+                arg("inv_level_sigma2", a["sig"], fp), s["nlevels"], s["iterations"], None if flag is None else flag.ctypes.data_as(bp),
+                None if "kf_Tcw_out" in null else C.cast(a["kf_out"].ctypes.data, C.POINTER(orb.PoseSE3d)),
+                arg("world_pos_out", a["pos_out"], fp), arg("erase", a["erase"], bp), arg("chi2", a["chi2"], dp),
+                None if "res" in null else C.byref(res))
+        finally:
+            if trial_slots:
+                L.vsg_debug_local_ba_trial_slots(0)
+        if not read:
+            return hc.result(rc, res, a, None)
+        self.after = self.store()
+        return hc.result(rc, res, a, self.after["world_pos"].copy())
+
+
+@pytest.fixture(scope="module")
+def devices():
+    return {name: Device(s) for name, s in ls.scenes().items()}
+
+
+@pytest.fixture(scope="module")
+def device_results(devices):
+    return {name: d.call() for name, d in devices.items()}
+
+
+@pytest.fixture(scope="module")
+def host_results():
+    return {name: hc.run(s) for name, s in ls.scenes().items()}
+
+
+def same_bits(got, want, what):
+    assert got["ret"] == want["ret"], (what, got["ret"], want["ret"])
+    for k in hc.RES_INTS + hc.RES_DOUBLES:
+        assert got[k] == want[k] or (got[k] != got[k] and want[k] != want[k]), (what, k, got[k], want[k])
+    assert got["res_bytes"] == want["res_bytes"], what
+    assert got["erase"].tobytes() == want["erase"].tobytes(), (what, np.flatnonzero(got["erase"] != want["erase"])[:8])
+    for k in ("kf_out", "pos_out", "chi2", "store_pos"):
+        assert got[k].tobytes() == want[k].tobytes(), (what, k, np.argwhere(got[k] != want[k])[:4])
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_device_equals_the_host_build_bit_for_bit(name, device_results, host_results):
+    same_bits(device_results[name], host_results[name], name)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_device_agrees_with_the_restatement(name, device_results):
+    print(name, ls.deviations(ls.references()[name], device_results[name]))
+    check_against_reference(name, device_results[name])
+
+
+@pytest.mark.parametrize("name", ("special_vertices", "points_257", "kf_40"))
+def test_store_after_the_call(name, devices):
+    """The listed vertices' world_pos equals world_pos_out; every other slot and every other field keeps its bytes."""
+    d = devices[name]
+    got = d.call()
+    s = d.s
+    vertex = np.diff(s["obs_off"]) > 0
+    assert got["ran"] == 1 and (got["pos_out"][vertex] != s["store_pos"][s["slots"][vertex]]).any()
+    expect = dict(d.fields)
+    expect["world_pos"] = d.fields["world_pos"].copy()
+    expect["world_pos"][s["slots"][vertex]] = got["pos_out"][vertex]
+    for k in FIELDS:
+        assert d.after[k].tobytes() == np.ascontiguousarray(expect[k]).tobytes(), k
+    assert (got["pos_out"][~vertex] == s["store_pos"][s["slots"][~vertex]]).all()
+
+
+@pytest.mark.parametrize("name", ("kf_2_1", "points_257", "kf_40", "negative_information", "stale_errors"))
+def test_result_does_not_depend_on_the_trial_slots(name, devices, device_results):
+    d = devices[name]
+    for slots in (1, 10):
+        same_bits(d.call(trial_slots=slots), device_results[name], "%s S=%d" % (name, slots))
+
+
+def test_device_carries_the_stale_errors(device_results):
+    ref, got = ls.references()["stale_errors"], device_results["stale_errors"]
+    differ = np.flatnonzero(np.isfinite(ref["chi2"]) & (ref["chi2"] != ref["chi2_fresh"]))
+    nearer = np.abs(got["chi2"][differ] - ref["chi2"][differ]) < np.abs(got["chi2"][differ] - ref["chi2_fresh"][differ])
+    assert len(differ) >= 20 and nearer.mean() > 0.9
+
+
+def assert_untouched(d, s, got):
+    assert (got["kf_out"] == hc.SENTINEL_F).all() and (got["pos_out"] == hc.SENTINEL_F).all()
+    assert (got["erase"] == hc.SENTINEL_ERASE).all() and (got["chi2"] == hc.SENTINEL_F).all()
+    for k in FIELDS:
+        assert d.after[k].tobytes() == np.ascontiguousarray(d.fields[k]).tobytes(), k
+
+
+@pytest.mark.parametrize("case", list(error_cases()[1]))
+def test_argument_error_then_a_valid_call(case, devices, device_results):
+    """Every error leaves outputs and store untouched, and a second, valid call on the same thread gives the right answer."""
+    s, cases, _ = error_cases()
+    kw, code = cases[case]
+    over = {k: v for k, v in kw.items() if k not in ("null", "nleft")}
+    d = devices["kf_2_1"] if "kfs" not in over and "nleft" not in kw else Device(dict(s, **over), kw.get("nleft"))
+    got = d.call(null=kw.get("null", ()), **{k: v for k, v in over.items() if k != "kfs"})
+    assert got["ret"] == code
+    assert_untouched(d, s, got)
+    if "res" not in kw.get("null", ()):
+        assert got["res_bytes"] == b"\x5a" * len(got["res_bytes"])
+    same_bits(devices["kf_2_1"].call(), device_results["kf_2_1"], "after " + case)
+
+
+def test_other_handle_errors(devices):
+    d = devices["kf_2_1"]
+    L = orb.load_library()
+    res = orb.LocalBaResult()
+    a = hc.marshal(d.s)
+    ip = C.POINTER(C.c_int32)
+    p = lambda v, t: v.ctypes.data_as(t)
+    handles = (C.c_void_p * 3)(d.kfs[0].handle, None, d.kfs[2].handle)
+    for mp, hs in ((None, (C.c_void_p * 3)(*[f.handle for f in d.kfs])), (d.mp.handle, handles), (d.mp.handle, None)):
+        rc = L.vsg_mappoints_local_bundle_adjustment(
+            mp, a["P"], p(a["slots"], ip), p(a["off"], ip), p(a["kf"], ip), p(a["idx"], ip), 3, hs,
+            C.cast(a["Tcw"].ctypes.data, C.POINTER(orb.PoseSE3)), p(a["fixed"], C.POINTER(C.c_uint8)),
+            C.cast(a["cam"].ctypes.data, C.POINTER(orb.BaCamera)), p(a["sig"], C.POINTER(C.c_float)), 8, 10, None,
+            C.cast(a["kf_out"].ctypes.data, C.POINTER(orb.PoseSE3d)), None, p(a["erase"], C.POINTER(C.c_uint8)), None, C.byref(res))
+        assert rc == INVALID and (a["kf_out"] == hc.SENTINEL_F).all()
+
+
+def test_more_than_128_optimised_keyframes():
+    _, _, many = error_cases()
+    d = Device(many)
+    got = d.call()
+    assert got["ret"] == UNSUPPORTED
+    assert_untouched(d, many, got)
+
+
+def test_returns_before_optimize(devices):
+    d = devices["kf_2_1"]
+    s = d.s
+    empty = dict(slots=s["slots"][:0], obs_off=np.zeros(1, I32), obs_kf=s["obs_kf"][:0], obs_idx=s["obs_idx"][:0])
+    for kw, over in ((dict(stop_flag=1), {}), ({}, dict(fixed=np.zeros(3, U8))), ({}, dict(obs_off=np.zeros_like(s["obs_off"]))),
+                     ({}, empty)):
+        got = d.call(**kw, **over)
+        assert got["ret"] == 0 and got["ran"] == 0
+        assert_untouched(d, s, got)
+        assert got["res_bytes"] == hc.run(s, **kw, **over)["res_bytes"]
+
+
+def test_optional_outs_and_a_second_call(devices, device_results):
+    d = devices["points_64_all"]
+    got = d.call(null=("world_pos_out", "chi2"))
+    want = device_results["points_64_all"]
+    assert got["ret"] == 0 and got["res_bytes"] == want["res_bytes"] and got["erase"].tobytes() == want["erase"].tobytes()
+    assert (got["pos_out"] == hc.SENTINEL_F).all() and (got["chi2"] == hc.SENTINEL_F).all()
+    assert got["store_pos"].tobytes() == want["store_pos"].tobytes() and got["kf_out"].tobytes() == want["kf_out"].tobytes()
+
+
+def test_python_binding(devices, device_results):
+    d = devices["kf_3_2"]
+    s = d.s
+    d.reset()
+    got = d.mp.LocalBundleAdjustment(s["slots"], s["obs_off"], s["obs_kf"], s["obs_idx"], d.kfs, s["Tcw"], s["fixed"], s["cam"],
+                                     s["sig"], iterations=s["iterations"])
+    want = device_results["kf_3_2"]
+    assert got["kf_Tcw"].tobytes() == want["kf_out"].tobytes() and got["world_pos"].tobytes() == want["pos_out"].tobytes()
+    assert got["erase"].tobytes() == want["erase"].tobytes() and got["chi2"].tobytes() == want["chi2"].tobytes()
+    assert got["ran"] == 1 and got["stop_reason"] == want["stop_reason"] and got["chi2_final"] == want["chi2_final"]
+    d.reset()
+    flag = np.array([1], U8)
+    got = d.mp.LocalBundleAdjustment(s["slots"], s["obs_off"], s["obs_kf"], s["obs_idx"], d.kfs, s["Tcw"], s["fixed"], s["cam"],
+                                     s["sig"], stop_flag=flag)
+    assert got["ran"] == 0 and (got["kf_Tcw"] == np.asarray(s["Tcw"], F64)).all()
+    assert (got["world_pos"] == s["store_pos"][s["slots"]]).all()
+
+
+def _half(s, lo, hi):
+    off = s["obs_off"]
+    return dict(s, slots=s["slots"][lo:hi], obs_off=(off[lo:hi + 1] - off[lo]).astype(I32), obs_kf=s["obs_kf"][off[lo]:off[hi]],
+                obs_idx=s["obs_idx"][off[lo]:off[hi]])
+
+
+def test_two_threads_on_disjoint_point_sets_of_one_store(devices):
+    """The scratch is the calling thread's; each call writes its own points' world_pos alone."""
+    d = devices["points_256"]
+    d.reset()
+    halves = [_half(d.s, 0, 128), _half(d.s, 128, 256)]
+    want = [hc.run(h) for h in halves]
+    out, errors = {}, []
+
+    def work(k):
+        try:
+            h = halves[k]
+            out[k] = d.call(reset=False, read=False, slots=h["slots"], obs_off=h["obs_off"], obs_kf=h["obs_kf"], obs_idx=h["obs_idx"])
+        except Exception as e:  # noqa: BLE001 -- reported below
+            errors.append(e)
+        finally:
+            orb.load_library().vsg_thread_release()  # the thread's stream and arenas are never freed implicitly
+    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for k in range(2):
+        for f in ("kf_out", "pos_out", "chi2", "erase"):
+            assert out[k][f].tobytes() == want[k][f].tobytes(), (k, f)
+        assert out[k]["res_bytes"] == want[k]["res_bytes"]
+    final = d.store()["world_pos"]
+    expect = d.fields["world_pos"].copy()
+    for k in range(2):
+        expect[halves[k]["slots"]] = want[k]["pos_out"]
+    assert final.tobytes() == expect.tobytes()
+
+
+@pytest.mark.parametrize("name", ("special_vertices", "mono_outliers"))
+def test_cpp_adaptor_gives_the_same_bytes(name, device_results, tmp_path):
+    s, want = ls.scenes()[name], device_results[name]
+    subprocess.check_call(["make", "-C", str(ADAPTOR)], stdout=subprocess.DEVNULL)
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+
+    def block(a, t, per=1):
+        a = np.ascontiguousarray(a, t)
+        return np.array([a.size // per], I32).tobytes() + a.tobytes()
+    blob = block([s["capacity"], s["iterations"], len(s["kfs"])], I32)
+    for f in s["kfs"]:
+        kps = np.zeros(len(f["x"]), orb.KP_DTYPE)
+        kps["x"], kps["y"], kps["octave"], kps["size"], kps["angle"] = f["x"], f["y"], f["octave"], 31.0, -1.0
+        blob += np.array([len(kps)], I32).tobytes() + kps.tobytes() + block([] if f["ur"] is None else f["ur"], F32)
+    blob += block(s["store_pos"], F32) + block(s["slots"], I32) + block(s["obs_off"], I32) + block(s["obs_kf"], I32) + \
+        block(s["obs_idx"], I32) + block(s["Tcw"], F32, 7) + block(s["fixed"], U8) + block(s["cam"], F32, 5) + block(s["sig"], F32)
+    src.write_bytes(blob)
+    subprocess.check_call([str(ADAPTOR / "localba_check"), str(src), str(dst)], timeout=120)
+    raw, at, got = dst.read_bytes(), 0, []
+    for size in (56, 4, 1, 8, C.sizeof(orb.LocalBaResult), 4):
+        n = int(np.frombuffer(raw[at:at + 4], I32)[0])
+        got.append(raw[at + 4:at + 4 + n * size])
+        at += 4 + n * size
+    assert at == len(raw)
+    assert got[0] == want["kf_out"].tobytes() and got[1] == want["pos_out"].tobytes() and got[2] == want["erase"].tobytes()
+    assert got[3] == want["chi2"].tobytes() and got[4] == want["res_bytes"] and got[5] == want["store_pos"].tobytes()

@@ -49,12 +49,20 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
                  header's own arithmetic, numeric Jacobian included)
             B  = vsg_frame_optimize_sim3;  A2 / B2 = both again.  Every call asserts A and B equal bit for bit
 
+  localba   the visual part of Optimizer::LocalBundleAdjustment on 10 + 10 / 20 + 20 / 40 + 40 optimised + fixed resident
+            keyframes of 1000 features with 1500 / 3000 / 6000 points of 6 observations, half stereo, 5 % outliers, the start
+            1 cm / 0.5 degrees off (a size is "<optimised = fixed keyframes>:<points>")
+            A  = vsg_mappoints_read + the host build of csrc/vsg_local_ba.h on one thread (NOT g2o: the header's own
+                 arithmetic and its DENSE reduced solve) + vsg_mappoints_update
+            B  = vsg_mappoints_local_bundle_adjustment;  A2 / B2 = both again;  B_S1 / B_S2 / B_S10 = B with 1 / 2 / 10 trial
+                 slots enqueued ahead per iteration instead of the library's.  Every call asserts all seven equal bit for bit
+
   track / track_local   Tracking's two per-frame steps as chain calls (vsg_frame_track_with_motion_model,
             vsg_frame_track_local_map), 1000 / 2000 / 4000 points, against the caller-side path on the SAME library: the two
             existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
             carries them.  Both write into profiles/track_chain_latency.json, one key each
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt|localba|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -84,7 +92,7 @@ def host_side(orb):
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
            csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
-           csrc / "vsg_sim3_opt.h"]
+           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
                                str(src[0])])
@@ -108,6 +116,9 @@ def host_side(orb):
     H.so_host_side.argtypes = [C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _i32p,
                                _f32p, _f32p, _i32p, C.c_void_p, C.c_void_p, _f32p, _f32p, C.c_int, C.c_void_p, C.c_float, C.c_int,
                                C.c_int, _u8p, C.POINTER(C.c_double), C.c_void_p]
+    H.lb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
+                               C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
+                               C.POINTER(C.c_double), C.c_void_p]
     H.tk_slots_from_matches.restype = H.tk_blocked_from_slots.restype = None
     H.tk_slots_from_matches.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p]
     H.tk_blocked_from_slots.argtypes = [C.c_int, _i32p, _u8p, _u8p]
@@ -735,6 +746,102 @@ class Sim3Opt(Case):
                              "B = vsg_frame_optimize_sim3"}
 
 
+class LocalBA(Case):
+    """The visual part of Optimizer::LocalBundleAdjustment on resident keyframes and map points: a scene of
+    tests/lba_scenes.py (n optimised + n fixed keyframes padded to 1000 features each, points of 6 observations, half of them
+    stereo, 5 % outliers displaced by 20 px or more, the optimised keyframes and the points started 1 cm / 0.5 degrees off).
+    A size is "<optimised = fixed keyframes>:<points>".  B, B_S1, B_S2 and B_S10 are the resident call with the library's trial
+    slots, 1, 2 and 10 of them enqueued ahead per iteration."""
+    SIZES = ("10:1500", "20:3000", "40:6000")
+    TH, DEST = 0.0, "local_ba_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2", "B_S1", "B_S2", "B_S10")
+
+    def __init__(self, orb, fr, size):
+        import lba_scenes as ls
+        nk, npts = (int(v) for v in size.split(":"))
+        self.orb, self.nk, self.npts = orb, nk, npts
+        s = self.s = ls.make(7300 + nk, nk, nk, npts, 6, "mixed", outliers=0.05)
+        c = np.ascontiguousarray
+        rng = np.random.default_rng(nk)
+        self.kf, feats = [], []
+        for f in s["kfs"]:  # pad to NFEAT features: the observed ones keep their indices
+            n, pad = len(f["x"]), max(NFEAT - len(f["x"]), 0)
+            x = np.concatenate([f["x"], rng.uniform(20, 620, pad)]).astype(np.float32)
+            y = np.concatenate([f["y"], rng.uniform(20, 460, pad)]).astype(np.float32)
+            o = np.concatenate([f["octave"], rng.integers(0, 8, pad)]).astype(np.int32)
+            ur = np.concatenate([np.full(n, -1, np.float32) if f["ur"] is None else f["ur"], np.full(pad, -1)]).astype(np.float32)
+            keys = np.zeros(len(x), orb.KP_DTYPE)
+            keys["x"], keys["y"], keys["octave"] = x, y, o
+            self.kf.append(orb.Frame(len(x) + 1).upload(keys, np.zeros((len(x), 32), np.uint8), (0.0, 0.0, 640.0, 480.0), u_right=ur))
+            feats.append((x, y, o, ur))
+        self.K = len(self.kf)
+        self.handles = (C.c_void_p * self.K)(*[f.handle for f in self.kf])
+        self.kf_off = np.zeros(self.K + 1, np.int32)
+        self.kf_off[1:] = np.cumsum([len(f[0]) for f in feats])
+        self.kx, self.ky, self.oct, self.ur = (c(np.concatenate([f[i] for f in feats])) for i in range(4))
+        self.cap = s["capacity"]
+        self.mp = orb.MapPoints(self.cap)
+        self.all, self.pos0 = np.arange(self.cap, dtype=np.int32), c(s["store_pos"], np.float32)
+        self.slots, self.off = c(s["slots"], np.int32), c(s["obs_off"], np.int32)
+        self.okf, self.oidx = c(s["obs_kf"], np.int32), c(s["obs_idx"], np.int32)
+        self.Tcw, self.fixed = c(s["Tcw"], np.float32), c(s["fixed"], np.uint8)
+        self.cam, self.sig = c(s["cam"], np.float32), c(s["sig"], np.float32)
+        E = int(self.off[-1])
+        self.Xw = np.zeros(3 * npts, np.float32)
+        self.kf_out, self.pos_out = np.zeros((self.K, 7)), np.zeros(3 * npts, np.float32)
+        self.erase, self.chi2, self.res = np.zeros(E, np.uint8), np.zeros(E), orb.LocalBaResult()
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):  # outside the clock: the store goes back to the start, the outs are cleared
+        self.mp.update(self.all, world_pos=self.pos0)
+        self.kf_out[:], self.pos_out[:], self.erase[:], self.chi2[:] = 0, 0, 9, -1.0
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        f64p = C.POINTER(C.c_double)
+        if name.startswith("B"):
+            L.vsg_debug_local_ba_trial_slots({"B_S1": 1, "B_S2": 2, "B_S10": 10}.get(name, 0))
+            rc = L.vsg_mappoints_local_bundle_adjustment(
+                self.mp.handle, self.npts, p(self.slots, _i32p), p(self.off, _i32p), p(self.okf, _i32p), p(self.oidx, _i32p), self.K,
+                self.handles, C.cast(self.Tcw.ctypes.data, C.POINTER(self.orb.PoseSE3)), p(self.fixed, _u8p),
+                C.cast(self.cam.ctypes.data, C.POINTER(self.orb.BaCamera)), p(self.sig, _f32p), 8, 10, None,
+                C.cast(self.kf_out.ctypes.data, C.POINTER(self.orb.PoseSE3d)), p(self.pos_out, _f32p), p(self.erase, _u8p),
+                p(self.chi2, f64p), C.byref(self.res))
+            L.vsg_debug_local_ba_trial_slots(0)
+            return rc
+        rc = L.vsg_mappoints_read(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), None, None, None, None, None)
+        if rc != 0:
+            return rc
+        rc = H.lb_host_side(self.cap, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), p(self.off, _i32p), p(self.okf, _i32p),
+                            p(self.oidx, _i32p), self.K, p(self.kf_off, _i32p), p(self.kx, _f32p), p(self.ky, _f32p),
+                            p(self.oct, _i32p), p(self.ur, _f32p), self.Tcw.ctypes.data, p(self.fixed, _u8p), self.cam.ctypes.data,
+                            p(self.sig, _f32p), 8, 10, self.kf_out.ctypes.data, p(self.pos_out, _f32p), p(self.erase, _u8p),
+                            p(self.chi2, f64p), C.addressof(self.res))
+        if rc != 0:
+            return rc
+        return L.vsg_mappoints_update(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.pos_out, _f32p), None, None, None,
+                                      None, None)
+
+    def result(self, name, r):
+        after = self.mp.read(self.slots)["world_pos"]
+        return (r, self.kf_out.view(np.uint64).copy(), self.pos_out.copy(), after.reshape(-1).copy(), self.erase.copy(),
+                self.chi2.view(np.uint64).copy(), np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.LocalBaResult.from_buffer_copy(last["B"][6].tobytes())
+        return {"optimised_keyframes": self.nk, "fixed_keyframes": self.nk, "points": self.npts, "edges": int(r.n_edges),
+                "mono": int(r.n_mono), "stereo": int(r.n_stereo), "erased": int(r.n_erase), "features_per_keyframe": NFEAT,
+                "iterations_run": int(r.iterations_run), "trials_run": int(r.trials_run), "stop_reason": int(r.stop_reason),
+                "every_call_equals_the_host_build": True,
+                "host_side": "A = vsg_mappoints_read + the host build of csrc/vsg_local_ba.h on one thread "
+                             "(tools/resident_points_cpu.cpp) + vsg_mappoints_update; it is THIS header's build and NOT g2o (no "
+                             "Eigen here).  Which way that flatters it: g2o's sparse reduced solve is cheaper than this dense "
+                             "one for many keyframes, its virtual calls and allocations are dearer; "
+                             "B = vsg_mappoints_local_bundle_adjustment (B_S1 / B_S2 / B_S10: 1 / 2 / 10 trial slots enqueued ahead)"}
+
+
 class Chain:
     """What the two chain cases add to their search's scene: a pose per call that stays within the search windows (a
     hundredth of a radian at most), the same pose as the solve's start, the solve's arrays, and the walk's rounds."""
@@ -872,7 +979,7 @@ class TrackLocal(Chain, Local):
 
 
 CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3,
-         "sim3opt": Sim3Opt}
+         "sim3opt": Sim3Opt, "localba": LocalBA}
 
 
 def child(case, calls):
@@ -921,6 +1028,13 @@ def trace(case="local"):
             c.reset()
             assert c.B(L) == 0
         print({"n": 8000, "observations": len(c.kf), "best_not_first": int((c.best != 0).sum())})
+        return
+    if case == "localba":
+        L, c = orb.load_library(), LocalBA(orb, fr, "20:3000")
+        for k in range(5):
+            c.reset()
+            assert c.run("B", L, None, None) == 0
+        print({"size": "20:3000", "calls": 5, "iterations_run": int(c.res.iterations_run), "trials_run": int(c.res.trials_run)})
         return
     L, c = orb.load_library(), Local(orb, fr, 4000)
     for k in range(10):

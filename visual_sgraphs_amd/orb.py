@@ -95,6 +95,10 @@ EXPORTS = [
     "vsg_mappoints_sim3_ransac", "vsg_sim3_ransac_iterations", "vsg_sim3_draw_samples",
     # Optimizer::OptimizeSim3 on two resident keyframes and resident map points
     "vsg_frame_optimize_sim3",
+    # the visual part of Optimizer::LocalBundleAdjustment on resident keyframes and resident map points (its test hook,
+    # vsg_debug_local_ba_trial_slots of include/vsg_orb_debug_local_ba.h, is bound below but is no part of the two headers
+    # this list mirrors)
+    "vsg_mappoints_local_bundle_adjustment",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
     # test hook: the query state of one keyframe of the resident KeyFrameDatabase
@@ -205,6 +209,28 @@ class Sim3OptResult(C.Structure):
     nMoreIterations and whether g2oS12 was updated (Optimizer.cc:3526)."""
     _fields_ = [("S12", Sim3d), ("n_correspondences", C.c_int32), ("n_bad", C.c_int32), ("n_in", C.c_int32),
                 ("n_in_kf2", C.c_int32), ("n_out_kf2", C.c_int32), ("more_iterations", C.c_int32), ("updated", C.c_int32)]
+
+
+class PoseSE3d(C.Structure):
+    """include/vsg_orb.h vsg_pose_se3d: a g2o::SE3Quat, the rotation as x y z w."""
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3)]
+
+
+class BaCamera(C.Structure):
+    """include/vsg_orb.h vsg_ba_camera: a keyframe's fx, fy, cx, cy, mbf."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float)]
+
+
+LOCAL_BA_RESULT_INTS = ("ran", "n_opt_kf", "n_fixed_kf", "n_points", "n_edges", "n_mono", "n_stereo", "n_erase",
+                        "iterations_run", "trials_run", "stop_reason")
+LOCAL_BA_RESULT_DOUBLES = ("lambda", "chi2_initial", "chi2_final")
+# vsg_local_ba_result.stop_reason
+LOCAL_BA_STOP_REASONS = ("iterations_done", "terminate", "n_bad", "stop_flag")
+
+
+class LocalBaResult(C.Structure):
+    """include/vsg_orb.h vsg_local_ba_result."""
+    _fields_ = [(k, C.c_int32) for k in LOCAL_BA_RESULT_INTS] + [(k, C.c_double) for k in LOCAL_BA_RESULT_DOUBLES]
 
 
 # vsg_frame_optimize_sim3: state[i]
@@ -469,6 +495,10 @@ def load_library():
     L.vsg_frame_optimize_sim3.argtypes = [vp, vp, vp, vp, _i32p, _i32p, _i32p, _i32p, C.POINTER(FramePose), C.POINTER(FramePose),
                                           _f32p, _f32p, ci, C.POINTER(Sim3d), cf, ci, ci, _u8p, _f64p, C.POINTER(Sim3OptResult)]
     L.vsg_sim3_draw_samples.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
+    L.vsg_mappoints_local_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
+                                                        _u8p, C.POINTER(BaCamera), _f32p, ci, ci, _u8p, C.POINTER(PoseSE3d),
+                                                        _f32p, _u8p, _f64p, C.POINTER(LocalBaResult)]
+    L.vsg_debug_local_ba_trial_slots.argtypes = [ci]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1249,6 +1279,53 @@ class MapPoints:
             "vsg_mappoints_refresh_from_observations")
         return {k: v[:n] for k, v in out.items()}
 
+
+    def LocalBundleAdjustment(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
+                              iterations=10, stop_flag=None, trial_slots=0):
+        """The visual part of Optimizer::LocalBundleAdjustment (vsg_mappoints_local_bundle_adjustment): point i = slot
+        slots[i] with the observations [obs_off[i], obs_off[i + 1]) of obs_kf (index into `keyframes`, a list of resident
+        orb.Frame in ascending mnId: the local keyframes AND the fixed ones) and obs_idx (leftIndex), as refresh() takes
+        them.  kf_Tcw = (K, 7) floats q (x y z w), t; kf_fixed[k] != 0 for lFixedCameras and the map's initial keyframe;
+        kf_cam = (K, 5) fx fy cx cy mbf; inv_level_sigma2 = mvInvLevelSigma2.  stop_flag = None or a uint8 array of one
+        element (pbStopFlag).  trial_slots: the test hook's trial slots enqueued ahead (0 = the library's default); the
+        result does not depend on it.  Returns dict(kf_Tcw (K, 7) float64, world_pos (n, 3) float32 -- also written into
+        the slots -- erase and chi2 per observation, and the fields of vsg_local_ba_result).  Follow with
+        refresh(what=REFRESH_NORMAL)."""
+        n, K = int(np.asarray(slots).size), len(keyframes)
+        sl, off, kf, idx = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx)
+        if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != np.asarray(obs_kf).size:
+            raise ValueError("observation arrays do not match the slot list")
+        nobs = int(off[n]) if n else 0
+        if int(np.asarray(obs_kf).size) < nobs:
+            raise ValueError("obs_off runs past the observation arrays")
+        T, fx, cam = _f32(kf_Tcw).reshape(-1), _u8(kf_fixed), _f32(kf_cam).reshape(-1)
+        if np.asarray(kf_Tcw).size != 7 * K or np.asarray(kf_fixed).size != K or np.asarray(kf_cam).size != 5 * K:
+            raise ValueError("kf_Tcw needs 7 floats, kf_fixed one byte and kf_cam 5 floats per keyframe")
+        sig = _f32(inv_level_sigma2)
+        handles = (C.c_void_p * max(K, 1))(*[f.handle for f in keyframes])
+        out = {"kf_Tcw": np.zeros((max(K, 1), 7), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
+               "erase": np.zeros(max(nobs, 1), np.uint8), "chi2": np.zeros(max(nobs, 1), np.float64)}
+        res = LocalBaResult()
+        flag = None if stop_flag is None else _p(stop_flag, _u8p)
+        if trial_slots:
+            _check(self._L.vsg_debug_local_ba_trial_slots(int(trial_slots)), "vsg_debug_local_ba_trial_slots")
+        try:
+            _check(self._L.vsg_mappoints_local_bundle_adjustment(
+                self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
+                C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
+                int(np.asarray(inv_level_sigma2).size), int(iterations), flag, C.cast(_p(out["kf_Tcw"], C.POINTER(C.c_double)), C.POINTER(PoseSE3d)),
+                _p(out["world_pos"], _f32p), _p(out["erase"], _u8p), _p(out["chi2"], C.POINTER(C.c_double)), C.byref(res)),
+                "vsg_mappoints_local_bundle_adjustment")
+        finally:
+            if trial_slots:
+                self._L.vsg_debug_local_ba_trial_slots(0)
+        if not res.ran:  # nothing was written: the outs are the inputs
+            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
+            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
+        got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "erase": out["erase"][:nobs], "chi2": out["chi2"][:nobs]}
+        got.update({k: int(getattr(res, k)) for k in LOCAL_BA_RESULT_INTS})
+        got.update({k: float(getattr(res, k)) for k in LOCAL_BA_RESULT_DOUBLES})
+        return got
 
     def Sim3Ransac(self, slots1, slots2, max_err1, max_err2, kf1, kf2, samples, min_inliers, fix_scale=False, other=None,
                    per_hypothesis=False):
