@@ -1328,6 +1328,74 @@ int vsg_mappoints_local_bundle_adjustment(
     const float *inv_level_sigma2, int nlevels, int iterations, const volatile uint8_t *stop_flag,
     vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *erase, double *chi2, vsg_local_ba_result *res);
 
+/* bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, T21, vP3D, vbTriangulated)
+ * (TwoViewReconstruction.cc:40-129; Tracking::MonocularInitialization, Tracking.cc:2568, through
+ * Pinhole::ReconstructWithTwoViews, Pinhole.cpp:91-101): the monocular initialisation behind
+ * vsg_frame_search_for_initialization.  Hypothesis `it` of either model depends on mvSets[it] alone, each loop keeps the
+ * first `it` whose score is strictly greater than every earlier one (:172, :222), the two model searches are independent
+ * (:104-109) and so are the 4 (F) or 8 (H) motion hypotheses of CheckRT: all of it runs in ONE enqueue and ONE wait.
+ *   f1 / f2 = the reference and the current frame, resident with mvKeysUn; matches12[i] (f1's N entries) = vMatches12, -1
+ * or a feature of f2; K = mK row-major; sets = mvSets, n_iter rows of 8 indices into the COMPACTED matches (:51-63: the
+ * entries >= 0 in ascending i; vsg_two_view_draw_sets draws them as :82-97); n_iter = mMaxIterations (200).  params: sigma
+ * = mSigma; rh_threshold = the 0.50 of :119, min_parallax and min_triangulated = the 1.0 and 50 of :116-127.
+ *   res: ok = the return value; reason = 0 success, 1 SH + SF == 0 (:112), 2 the singular-value gate of ReconstructH (:598),
+ * 3 no clear winner or too few points (:518, :724), 4 the parallax gate; model = 0 H / 1 F; SH, SF, best_it_h / best_it_f
+ * (-1: no hypothesis scored above 0; the matrix is then zeros) and H21 / F21 (row-major) = what the two searches return;
+ * R21 (row-major) / t21 = T21 (zeros unless ok); n_good[k] = nGood of motion hypothesis k in the order of :498-501 / :702
+ * (4 or 8 entries, the rest 0); parallax = that of the chosen hypothesis (0 where the routine returned before it);
+ * n_inliers = N of :476 / :575.
+ *   triangulated[i] (f1's N entries) = vbTriangulated and x3d[3 i] = vP3D are written ONLY when ok, and x3d ONLY on the F
+ * path: ReconstructH never assigns vP3D (:724-730), so after an H success the caller's x3d holds what it held before --
+ * kept as the reference has it.  Both are then written whole (zero where CheckRT wrote nothing).  A point with
+ * cosParallax >= 0.99998 has its position written but is not flagged (:879-884).  inlier_h / inlier_f (one byte per
+ * COMPACTED match) and score_h / score_f (n_iter floats) may each be NULL: vbMatchesInliersH / F of the two winners and
+ * every hypothesis's score.
+ *   Arithmetic (csrc/vsg_two_view.h, host and device from one source): float in the reference's order,
+ * the scores summed in float in the reference's order; every singular vector comes from a double one-sided Jacobi rounded
+ * once instead of Eigen's float JacobiSVD, a deviation by rounding -- the sign of a singular pair only permutes the motion
+ * hypotheses (n_good's order).  Triangulate's x3Dh(3) == 0, where the reference reads an unset vector, counts as not
+ * finite.  acos runs on the host behind the wait.  NaNs in the outputs are canonical.
+ *   Checked before anything is enqueued (an error writes nothing and leaves no kernel behind), VSG_ERR_INVALID: a NULL
+ * frame, matches12, K, params, sets, res, triangulated or x3d; frames on different devices; a match outside [-1, N of f2);
+ * fewer than 8 matches (the reference would index an empty vector); n_iter outside [1, 1024]; a set entry outside [0,
+ * matches); two equal entries in one set; sigma or a K entry not finite; sigma <= 0.  Only the matches, the sets and a
+ * few scalars go up; the scratch lives in the calling thread's arena, so two threads may initialise on the same frames
+ * at the same time. */
+#define VSG_TWO_VIEW_H 0
+#define VSG_TWO_VIEW_F 1
+typedef struct vsg_two_view_params {
+  float sigma, rh_threshold, min_parallax;
+  int32_t min_triangulated;
+} vsg_two_view_params;
+typedef struct vsg_two_view_result {
+  int32_t ok, reason, model;
+  float SH, SF;
+  int32_t best_it_h, best_it_f;
+  float H21[9], F21[9], R21[9], t21[3];
+  int32_t n_good[8];
+  float parallax;
+  int32_t n_inliers;
+} vsg_two_view_result;
+/* sigma 1.0, rh_threshold 0.50, min_parallax 1.0, min_triangulated 50 (Pinhole.cpp:97, TwoViewReconstruction.cc:116-127) */
+void vsg_two_view_default_params(vsg_two_view_params *params);
+int vsg_frame_two_view_reconstruct(vsg_frame *f1, vsg_frame *f2, const int32_t *matches12, const float K[9],
+                                   const vsg_two_view_params *params, int n_iter, const int32_t *sets,
+                                   vsg_two_view_result *res, uint8_t *triangulated, float *x3d, uint8_t *inlier_h,
+                                   uint8_t *inlier_f, float *score_h, float *score_f);
+/* The same on keypoints the caller holds: xy1 / xy2 = {x, y} of the n1 / n2 undistorted keypoints of the two frames --
+ * what KannalaBrandt8::ReconstructWithTwoViews (KannalaBrandt8.cpp:181-211) has after it undistorted on its own.  One
+ * implementation behind both forms; here the matched coordinates go up as well.  Also refused: a NULL xy1 / xy2, n1 or n2
+ * below 1. */
+int vsg_two_view_reconstruct(int device, const float *xy1, int n1, const float *xy2, int n2, const int32_t *matches12,
+                             const float K[9], const vsg_two_view_params *params, int n_iter, const int32_t *sets,
+                             vsg_two_view_result *res, uint8_t *triangulated, float *x3d, uint8_t *inlier_h,
+                             uint8_t *inlier_f, float *score_h, float *score_f);
+/* The draw of :82-97 for n_iter sets over n matches: per set a copy of vAllIndices (0 .. n-1), then eight times randi =
+ * random_int(0, size - 1, ctx), the element is taken, back() moves into its place, pop_back().  random_int == NULL:
+ * DUtils::Random::RandomInt's formula over rand() (Random.cpp:47-50); SeedRandOnce(0) (:80) stays with the caller.  Host
+ * only.  n < 8, n_iter < 0, NULL sets, or a random_int result outside its range: VSG_ERR_INVALID. */
+int vsg_two_view_draw_sets(int n, int n_iter, int (*random_int)(int lo, int hi, void *ctx), void *ctx, int32_t *sets);
+
 #ifdef __cplusplus
 }
 #endif

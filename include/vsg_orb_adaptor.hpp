@@ -1591,4 +1591,82 @@ class ResidentSim3Optimizer {
   vsg_sim3_opt_result res_ = {};
 };
 
+// TwoViewReconstruction (TwoViewReconstruction.h, .cc:31-129) on two resident frames, with the reference's constructor and
+// Reconstruct, so that Pinhole::ReconstructWithTwoViews (Pinhole.cpp:91-101) keeps its shape:
+//     vsg::ResidentTwoViewReconstruction tvr(K, 1.0f, 200);                          // K = mK row-major
+//     bool ok = tvr.Reconstruct(initialFrame, currentFrame, vMatches12, R21, t21, vP3D, vbTriangulated);
+// T21 comes back as R21 (row-major) and t21, vP3D as {x, y, z} per keypoint of the first frame.  KEPT as the reference has
+// it: vP3D is assigned only when the call succeeds from the fundamental matrix -- ReconstructH never assigns it (:724-730),
+// so after a success from the homography it is exactly what the caller passed in -- and nothing is assigned on failure.
+// The second form takes the undistorted keypoints themselves (KannalaBrandt8::ReconstructWithTwoViews, which undistorts on
+// its own first).  mvSets comes from vsg_two_view_draw_sets with DUtils::Random::RandomInt's formula over rand() -- the caller
+// keeps SeedRandOnce(0) -- or from randomInt.
+class ResidentTwoViewReconstruction {
+ public:
+  ResidentTwoViewReconstruction(const float K[9], float sigma = 1.0f, int iterations = 200, int device = 0,
+                                int (*randomInt)(int, int, void *) = nullptr, void *randomCtx = nullptr)
+      : mMaxIterations_(iterations), device_(device), randomInt_(randomInt), randomCtx_(randomCtx) {
+    for (int k = 0; k < 9; ++k) mK_[k] = K[k];
+    vsg_two_view_default_params(&params_);
+    params_.sigma = sigma;
+    memset(&res_, 0, sizeof res_);
+  }
+  vsg_two_view_params &params() { return params_; }  // rh_threshold, min_parallax, min_triangulated of :116-127
+  bool Reconstruct(const ResidentFrame &F1, const ResidentFrame &F2, const std::vector<int> &vMatches12, float R21[9],
+                   float t21[3], std::vector<float> &vP3D, std::vector<bool> &vbTriangulated) {
+    if ((int)vMatches12.size() != F1.N()) check(VSG_ERR_INVALID, "vsg::ResidentTwoViewReconstruction");
+    begin(vMatches12);
+    check(vsg_frame_two_view_reconstruct(F1.handle(), F2.handle(), matches_.data(), mK_, &params_, mMaxIterations_, sets_.data(),
+                                         &res_, tri_.data(), x3d_.data(), nullptr, nullptr, nullptr, nullptr),
+          "vsg_frame_two_view_reconstruct");
+    return end(R21, t21, vP3D, vbTriangulated);
+  }
+  bool Reconstruct(const std::vector<vsg_keypoint> &vKeys1, const std::vector<vsg_keypoint> &vKeys2,
+                   const std::vector<int> &vMatches12, float R21[9], float t21[3], std::vector<float> &vP3D,
+                   std::vector<bool> &vbTriangulated) {
+    if (vMatches12.size() != vKeys1.size()) check(VSG_ERR_INVALID, "vsg::ResidentTwoViewReconstruction");
+    std::vector<float> xy1(2 * vKeys1.size() + 2), xy2(2 * vKeys2.size() + 2);
+    for (size_t i = 0; i < vKeys1.size(); ++i) xy1[2 * i] = vKeys1[i].x, xy1[2 * i + 1] = vKeys1[i].y;
+    for (size_t i = 0; i < vKeys2.size(); ++i) xy2[2 * i] = vKeys2[i].x, xy2[2 * i + 1] = vKeys2[i].y;
+    begin(vMatches12);
+    check(vsg_two_view_reconstruct(device_, xy1.data(), (int)vKeys1.size(), xy2.data(), (int)vKeys2.size(), matches_.data(), mK_,
+                                   &params_, mMaxIterations_, sets_.data(), &res_, tri_.data(), x3d_.data(), nullptr, nullptr,
+                                   nullptr, nullptr),
+          "vsg_two_view_reconstruct");
+    return end(R21, t21, vP3D, vbTriangulated);
+  }
+  const vsg_two_view_result &result() const { return res_; }
+  const std::vector<int32_t> &sets() const { return sets_; }  // mvSets, 8 per iteration
+
+ private:
+  void begin(const std::vector<int> &vMatches12) {
+    matches_.assign(vMatches12.begin(), vMatches12.end());
+    int N = 0;
+    for (int m : vMatches12) N += m >= 0 ? 1 : 0;
+    if (N < 8 || mMaxIterations_ < 1) check(VSG_ERR_INVALID, "vsg::ResidentTwoViewReconstruction");
+    sets_.assign(8 * (size_t)mMaxIterations_, 0);
+    check(vsg_two_view_draw_sets(N, mMaxIterations_, randomInt_, randomCtx_, sets_.data()), "vsg_two_view_draw_sets");
+    tri_.assign(matches_.size() + 1, 0), x3d_.assign(3 * matches_.size() + 3, 0.0f);
+  }
+  bool end(float R21[9], float t21[3], std::vector<float> &vP3D, std::vector<bool> &vbTriangulated) {
+    if (!res_.ok) return false;
+    for (int k = 0; k < 9; ++k) R21[k] = res_.R21[k];
+    for (int k = 0; k < 3; ++k) t21[k] = res_.t21[k];
+    const size_t n1 = matches_.size();
+    vbTriangulated.assign(n1, false);
+    for (size_t i = 0; i < n1; ++i) vbTriangulated[i] = tri_[i] != 0;
+    if (res_.model == VSG_TWO_VIEW_F) vP3D.assign(x3d_.begin(), x3d_.begin() + 3 * n1);  // :528; never on the H path
+    return true;
+  }
+  float mK_[9];
+  vsg_two_view_params params_;
+  int mMaxIterations_, device_;
+  int (*randomInt_)(int, int, void *);
+  void *randomCtx_;
+  std::vector<int32_t> matches_, sets_;
+  std::vector<uint8_t> tri_;
+  std::vector<float> x3d_;
+  vsg_two_view_result res_;
+};
+
 }  // namespace vsg

@@ -13,6 +13,7 @@
 #include "vsg_sim3.h"
 #include "vsg_sim3_opt.h"
 #include "vsg_triangulate.h"
+#include "vsg_two_view.h"
 
 extern "C" {
 
@@ -221,6 +222,17 @@ int s3_host_side(int n, const float *Xw1, const float *Xw2, const float *max_err
   vsg::sim3::ransac_host(n, Xw1, Xw2, max_err1, max_err2, *kf1, *kf2, fix_scale != 0, min_inliers, n_hyp, samples, true, pts.data(),
                          counts.data(), inlier, res, nullptr, nullptr);
   return res->iterations;
+}
+
+// The caller-side TwoViewReconstruction::Reconstruct on keypoints the caller holds (two_view::reconstruct_host), the two model
+// searches on one thread or, as the reference runs them (:104-109), on two
+int tv_host_side(const float *xy1, int n1, const float *xy2, int n2, const int32_t *matches12, const float *K,
+                 const vsg_two_view_params *params, int n_iter, const int32_t *sets, int two_threads, vsg_two_view_result *res,
+                 uint8_t *triangulated, float *x3d) {
+  static thread_local vsg::two_view::HostScratch W;
+  vsg::two_view::reconstruct_host(xy1, n1, xy2, n2, matches12, K, *params, n_iter, sets, two_threads != 0, W, res, triangulated, x3d,
+                                  nullptr, nullptr, nullptr, nullptr);
+  return res->ok;
 }
 
 // The caller-side Optimizer::OptimizeSim3 (Optimizer.cc:3261-3529) on positions read back from the stores: slots1 / slots2

@@ -43,6 +43,10 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
                  early exit (NOT Eigen: the header's own arithmetic)
             B  = vsg_mappoints_sim3_ransac (every hypothesis, no early exit);  A2 / B2 = both again.  Equal results asserted
 
+  twoview   TwoViewReconstruction::Reconstruct (Tracking.cc:2568): 100 / 300 / 1000 matches between two frames of 1000 / 1000 /
+            2000 features, 200 sets.  A = the host build of csrc/vsg_two_view.h on one thread, given the keypoint arrays (NOT
+            Eigen), AT = the same with H and F on two threads as the reference runs them, B = vsg_frame_two_view_reconstruct;
+            A2 / B2 = both again.  Equal results asserted on every call
   sim3opt   Optimizer::OptimizeSim3 on two resident keyframes of 1000 features (LoopClosing.cc:538, :747): 30 / 100 / 300 pairs
             between two stores of 4096 slots, 20 % outliers, th2 = 10, fix_scale 0 and 1 (a size is "<pairs>:<fix_scale>")
             A  = vsg_mappoints_read of both point sets + the host build of csrc/vsg_sim3_opt.h on one thread (NOT g2o: the
@@ -62,7 +66,7 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
             existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
             carries them.  Both write into profiles/track_chain_latency.json, one key each
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt|localba|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt|localba|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -92,10 +96,10 @@ def host_side(orb):
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
            csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
-           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h"]
+           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(csrc), "-o", str(so),
-                               str(src[0])])
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-pthread", "-I", str(csrc), "-o",
+                               str(so), str(src[0])])
     H = C.CDLL(str(so))
     pose = C.POINTER(orb.FramePose)
     H.lp_host_side.restype = None
@@ -119,6 +123,7 @@ def host_side(orb):
     H.lb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
                                C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
                                C.POINTER(C.c_double), C.c_void_p]
+    H.tv_host_side.argtypes = [_f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_void_p, C.c_int, _i32p, C.c_int, C.c_void_p, _u8p, _f32p]
     H.tk_slots_from_matches.restype = H.tk_blocked_from_slots.restype = None
     H.tk_slots_from_matches.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p]
     H.tk_blocked_from_slots.argtypes = [C.c_int, _i32p, _u8p, _u8p]
@@ -664,6 +669,61 @@ class Sim3(Case):
                              "Sophus); B = vsg_mappoints_sim3_ransac, which computes all hypotheses"}
 
 
+class TwoView(Case):
+    """TwoViewReconstruction::Reconstruct (Tracking::MonocularInitialization, Tracking.cc:2568): a general scene of
+    tests/two_view_scenes.py, 200 sets.  A size is "<matches>:<features per frame>".  AT = A with the two model searches on two
+    threads, as the reference runs them."""
+    SIZES = ("100:1000", "300:1000", "1000:2000")
+    TH, DEST = 0.0, "two_view_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2", "AT")
+    NITER = 200
+
+    def __init__(self, orb, fr, size):
+        import two_view_scenes as ts
+        n, feat = (int(v) for v in size.split(":"))
+        self.orb, self.n, self.feat = orb, n, feat
+        s = self.s = ts.make(9000 + n, n=n, extra1=feat - n, extra2=feat - n, n_iter=self.NITER)
+        c = np.ascontiguousarray
+        self.xy = [c(s["xy1"], np.float32), c(s["xy2"], np.float32)]
+        self.m12, self.K, self.sets = c(s["matches12"], np.int32), c(s["K"], np.float32), c(s["sets"], np.int32)
+        self.F = []
+        for xy in self.xy:
+            keys = np.zeros(feat, orb.KP_DTYPE)
+            keys["x"], keys["y"], keys["size"] = xy[:, 0], xy[:, 1], 31.0
+            self.F.append(orb.Frame(feat + 1).upload(keys, np.zeros((feat, 32), np.uint8), (0.0, 0.0, 640.0, 480.0)))
+        self.params = orb.TwoViewParams()
+        orb.load_library().vsg_two_view_default_params(C.byref(self.params))
+        self.res, self.tri, self.x3d = orb.TwoViewResult(), np.zeros(feat, np.uint8), np.zeros(3 * feat, np.float32)
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.tri[:], self.x3d[:] = 9, -1.0
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        if name.startswith("B"):
+            return L.vsg_frame_two_view_reconstruct(self.F[0].handle, self.F[1].handle, p(self.m12, _i32p), p(self.K, _f32p),
+                                                    C.byref(self.params), self.NITER, p(self.sets, _i32p), C.byref(self.res),
+                                                    p(self.tri, _u8p), p(self.x3d, _f32p), None, None, None, None)
+        return H.tv_host_side(p(self.xy[0], _f32p), self.feat, p(self.xy[1], _f32p), self.feat, p(self.m12, _i32p), p(self.K, _f32p),
+                              C.byref(self.params), self.NITER, p(self.sets, _i32p), 1 if name == "AT" else 0, C.byref(self.res),
+                              p(self.tri, _u8p), p(self.x3d, _f32p))
+
+    def result(self, name, r):
+        return (0 if r >= 0 else r, self.tri.copy(), self.x3d.copy(), np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.TwoViewResult.from_buffer_copy(last["B"][3].tobytes())
+        return {"matches": self.n, "features_per_frame": self.feat, "sets": self.NITER, "ok": bool(r.ok), "model": "F" if r.model else "H",
+                "n_inliers": int(r.n_inliers), "n_good": [int(v) for v in r.n_good],
+                "host_side": "A = the host build of csrc/vsg_two_view.h on one thread, given the keypoint arrays "
+                             "(tools/resident_points_cpu.cpp; NOT Eigen: the header's double Jacobi with one rounding per operation, "
+                             "no JacobiSVD); AT = the same with the two model searches on two threads, as the reference runs them; "
+                             "B = vsg_frame_two_view_reconstruct"}
+
+
 class Sim3Opt(Case):
     """Optimizer::OptimizeSim3 on resident keyframes and map points: a scene of tests/sim3opt_scenes.py (two keyframes of 1000
     features, the pairs related by a similarity of scale 1.3, inlier noise within 0.8 sigma, 20 % outliers displaced by 6 sigma
@@ -979,7 +1039,7 @@ class TrackLocal(Chain, Local):
 
 
 CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3,
-         "sim3opt": Sim3Opt, "localba": LocalBA}
+         "sim3opt": Sim3Opt, "localba": LocalBA, "twoview": TwoView}
 
 
 def child(case, calls):

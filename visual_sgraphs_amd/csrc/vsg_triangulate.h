@@ -20,6 +20,7 @@
 #include <stddef.h>
 
 #include "../../include/vsg_orb.h"
+#include "vsg_jacobi.h"
 #include "vsg_math.h"
 #include "vsg_observations.h"
 
@@ -79,55 +80,15 @@ VSG_HD float tri_camera_coord(const vsg_frame_pose &c, int r, const float *X) {
 }
 VSG_HD float tri_norm3(const float *v) { return fsqrt(dot3(v[0], v[1], v[2], v[0], v[1], v[2])); }
 
-// The right singular vector of A's least singular value (A row-major, float), in double.  One-sided Jacobi: U starts as
-// A, V as the identity; a sweep visits the column pairs (p, q), p < q, in lexicographic order and rotates the pair to
-// orthogonality (gamma == 0: already orthogonal, skipped); after kTriSweeps sweeps the column of V whose column of U has
-// the least squared norm is the answer, the lowest index on a tie.  Loops are compile-time bounded and the column is taken
-// with selects, so U and V stay in registers.
+// The right singular vector of A's least singular value (A row-major, float), in double: the one-sided Jacobi of
+// vsg_jacobi.h on the columns of A, kTriSweeps sweeps, the matrix in registers (loops are compile-time bounded and the
+// column is taken with selects).
 VSG_HD void tri_null_vector(const float *A, double *v) {
-  double U[4][4], V[4][4];  // [row][column]
+  JacobiRegs<4, 4> s;
   for (int r = 0; r < 4; r++)
-    for (int c = 0; c < 4; c++) U[r][c] = (double)A[4 * r + c], V[r][c] = r == c ? 1.0 : 0.0;
-VSG_TRI_UNROLL
-  for (int sweep = 0; sweep < kTriSweeps; sweep++) {
-VSG_TRI_UNROLL
-    for (int p = 0; p < 3; p++) {
-VSG_TRI_UNROLL
-      for (int q = p + 1; q < 4; q++) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-VSG_TRI_UNROLL
-        for (int k = 0; k < 4; k++) {
-          alpha = dadd(alpha, dmul(U[k][p], U[k][p]));
-          beta = dadd(beta, dmul(U[k][q], U[k][q]));
-          gamma = dadd(gamma, dmul(U[k][p], U[k][q]));
-        }
-        if (gamma == 0.0) continue;
-        const double zeta = ddiv(dsub(beta, alpha), dmul(2.0, gamma));
-        const double az = zeta < 0.0 ? -zeta : zeta;
-        const double ta = ddiv(1.0, dadd(az, dsqrt(dadd(1.0, dmul(zeta, zeta)))));
-        const double t = zeta < 0.0 ? -ta : ta;
-        const double cs = ddiv(1.0, dsqrt(dadd(1.0, dmul(t, t)))), sn = dmul(cs, t);
-VSG_TRI_UNROLL
-        for (int k = 0; k < 4; k++) {
-          const double up = U[k][p], uq = U[k][q], vp = V[k][p], vq = V[k][q];
-          U[k][p] = dsub(dmul(cs, up), dmul(sn, uq)), U[k][q] = dadd(dmul(sn, up), dmul(cs, uq));
-          V[k][p] = dsub(dmul(cs, vp), dmul(sn, vq)), V[k][q] = dadd(dmul(sn, vp), dmul(cs, vq));
-        }
-      }
-    }
-  }
-  double best = 0.0;
-VSG_TRI_UNROLL
-  for (int c = 0; c < 4; c++) {
-    double nrm = 0.0;
-VSG_TRI_UNROLL
-    for (int k = 0; k < 4; k++) nrm = dadd(nrm, dmul(U[k][c], U[k][c]));
-    if (c == 0 || nrm < best) {
-      best = nrm;
-VSG_TRI_UNROLL
-      for (int k = 0; k < 4; k++) v[k] = V[k][c];
-    }
-  }
+    for (int c = 0; c < 4; c++) s.at(r, c) = (double)A[4 * r + c], s.at(4 + r, c) = r == c ? 1.0 : 0.0;
+  jacobi_sweeps<4, 4, kTriSweeps>(s);
+  jacobi_null_vector<4, 4>(s, v);
 }
 
 // GeometricTools::Triangulate (GeometricTools.cc:47-66): false = x3Dh(3) == 0

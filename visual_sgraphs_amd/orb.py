@@ -99,6 +99,9 @@ EXPORTS = [
     # vsg_debug_local_ba_trial_slots of include/vsg_orb_debug_local_ba.h, is bound below but is no part of the two headers
     # this list mirrors)
     "vsg_mappoints_local_bundle_adjustment",
+    # TwoViewReconstruction::Reconstruct (the monocular initialisation) on two resident frames or on caller arrays, the
+    # reference's default parameters and the host-side draw of the minimal sets
+    "vsg_frame_two_view_reconstruct", "vsg_two_view_reconstruct", "vsg_two_view_default_params", "vsg_two_view_draw_sets",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
     # test hook: the query state of one keyframe of the resident KeyFrameDatabase
@@ -232,6 +235,24 @@ class LocalBaResult(C.Structure):
     """include/vsg_orb.h vsg_local_ba_result."""
     _fields_ = [(k, C.c_int32) for k in LOCAL_BA_RESULT_INTS] + [(k, C.c_double) for k in LOCAL_BA_RESULT_DOUBLES]
 
+
+class TwoViewParams(C.Structure):
+    """include/vsg_orb.h vsg_two_view_params: mSigma, the RH threshold of TwoViewReconstruction.cc:119, minParallax and
+    minTriangulated (:116-127)."""
+    _fields_ = [("sigma", C.c_float), ("rh_threshold", C.c_float), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32)]
+
+
+class TwoViewResult(C.Structure):
+    """include/vsg_orb.h vsg_two_view_result."""
+    _fields_ = [("ok", C.c_int32), ("reason", C.c_int32), ("model", C.c_int32), ("SH", C.c_float), ("SF", C.c_float),
+                ("best_it_h", C.c_int32), ("best_it_f", C.c_int32), ("H21", C.c_float * 9), ("F21", C.c_float * 9),
+                ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("n_good", C.c_int32 * 8), ("parallax", C.c_float),
+                ("n_inliers", C.c_int32)]
+
+
+# vsg_two_view_result.reason / .model
+TWO_VIEW_REASONS = ("ok", "no_score", "singular_values", "no_winner", "low_parallax")
+TWO_VIEW_H, TWO_VIEW_F = 0, 1
 
 # vsg_frame_optimize_sim3: state[i]
 SIM3_OPT_STATES = ("no_edge", "inlier", "nulled_first_check", "nulled_second_check", "skipped_z_negative", "skipped_not_in_kf2")
@@ -495,6 +516,12 @@ def load_library():
     L.vsg_frame_optimize_sim3.argtypes = [vp, vp, vp, vp, _i32p, _i32p, _i32p, _i32p, C.POINTER(FramePose), C.POINTER(FramePose),
                                           _f32p, _f32p, ci, C.POINTER(Sim3d), cf, ci, ci, _u8p, _f64p, C.POINTER(Sim3OptResult)]
     L.vsg_sim3_draw_samples.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
+    tv_tail = [_i32p, _f32p, C.POINTER(TwoViewParams), ci, _i32p, C.POINTER(TwoViewResult), _u8p, _f32p, _u8p, _u8p, _f32p, _f32p]
+    L.vsg_frame_two_view_reconstruct.argtypes = [vp, vp] + tv_tail
+    L.vsg_two_view_reconstruct.argtypes = [ci, _f32p, ci, _f32p, ci] + tv_tail
+    L.vsg_two_view_default_params.argtypes = [C.POINTER(TwoViewParams)]
+    L.vsg_two_view_default_params.restype = None
+    L.vsg_two_view_draw_sets.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
     L.vsg_mappoints_local_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
                                                         _u8p, C.POINTER(BaCamera), _f32p, ci, ci, _u8p, C.POINTER(PoseSE3d),
                                                         _f32p, _u8p, _f64p, C.POINTER(LocalBaResult)]
@@ -1375,6 +1402,71 @@ def sim3_draw_samples(n, n_hyp, random_int=None):
     cb = _RANDOM_INT(lambda lo, hi, _ctx: int(random_int(lo, hi))) if random_int is not None else _RANDOM_INT()
     _check(load_library().vsg_sim3_draw_samples(int(n), int(n_hyp), cb, None, _p(out, _i32p)), "vsg_sim3_draw_samples")
     return out[:int(n_hyp)]
+
+
+def two_view_draw_sets(n, n_iter, random_int=None):
+    """mvSets of TwoViewReconstruction::Reconstruct (:82-97) for n_iter iterations over n matches: n_iter x 8 int32.
+    random_int(lo, hi) stands for DUtils::Random::RandomInt; None: its formula over the C library's rand() (host only;
+    SeedRandOnce(0) stays with the caller)."""
+    out = np.zeros((max(int(n_iter), 1), 8), np.int32)
+    cb = _RANDOM_INT(lambda lo, hi, _ctx: int(random_int(lo, hi))) if random_int is not None else _RANDOM_INT()
+    _check(load_library().vsg_two_view_draw_sets(int(n), int(n_iter), cb, None, _p(out, _i32p)), "vsg_two_view_draw_sets")
+    return out[:int(n_iter)]
+
+
+class TwoViewReconstruction:
+    """TwoViewReconstruction(k, sigma, iterations) (TwoViewReconstruction.cc:31-38) with Reconstruct on the device: every
+    homography and fundamental-matrix hypothesis, the selection, the motion hypotheses and CheckRT in one enqueue and one wait
+    (vsg_frame_two_view_reconstruct / vsg_two_view_reconstruct)."""
+
+    def __init__(self, K, sigma=1.0, iterations=200, device=0):
+        self._L = load_library()
+        self.K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self.params = TwoViewParams()
+        self._L.vsg_two_view_default_params(C.byref(self.params))
+        self.params.sigma = float(sigma)
+        self.iterations, self.device = int(iterations), int(device)
+
+    def Reconstruct(self, keys1, keys2, matches12, sets=None, random_int=None, x3d=None, per_hypothesis=False):
+        """keys1 / keys2: two resident Frames, or two [n, 2] arrays of undistorted keypoint coordinates.  matches12 =
+        vMatches12.  sets: n_iter x 8 indices into the compacted matches (None: drawn as the reference draws them, through
+        random_int).  x3d: the caller's vP3D [n1, 3] (None: zeros) -- left as it is unless the call succeeds from F.  Returns
+        dict(ok, reason, model, R21, t21, x3d, triangulated, SH, SF, best_it_h, best_it_f, H21, F21, n_good, parallax,
+        n_inliers) and, with per_hypothesis, inlier_h, inlier_f, score_h, score_f."""
+        m12 = _i32(matches12)
+        resident = isinstance(keys1, Frame)
+        n_matches = int((np.asarray(matches12) >= 0).sum())
+        if sets is None:
+            sets = two_view_draw_sets(n_matches, self.iterations, random_int)
+        st = np.ascontiguousarray(sets, np.int32).reshape(-1, 8)
+        n1 = keys1.N if resident else len(np.asarray(keys1).reshape(-1, 2))
+        if int(np.asarray(matches12).size) != n1:
+            raise ValueError("matches12 has not one entry per keypoint of the first frame")
+        tri, res = np.zeros(max(n1, 1), np.uint8), TwoViewResult()
+        pts = np.zeros((max(n1, 1), 3), np.float32) if x3d is None else np.ascontiguousarray(x3d, np.float32).reshape(-1, 3).copy()
+        if len(pts) < n1:
+            raise ValueError("x3d is shorter than the first frame")
+        opt = [None] * 4
+        if per_hypothesis:
+            opt = [np.zeros(max(n_matches, 1), np.uint8), np.zeros(max(n_matches, 1), np.uint8),
+                   np.zeros(max(len(st), 1), np.float32), np.zeros(max(len(st), 1), np.float32)]
+        tail = (_p(m12, _i32p), _p(self.K, _f32p), C.byref(self.params), len(st), _p(_i32(st), _i32p), C.byref(res),
+                _p(tri, _u8p), _p(pts, _f32p), *[None if a is None else _p(a, _u8p if a.dtype == np.uint8 else _f32p) for a in opt])
+        if resident:
+            _check(self._L.vsg_frame_two_view_reconstruct(keys1.handle, keys2.handle, *tail), "vsg_frame_two_view_reconstruct")
+        else:
+            a, b = _f32(np.asarray(keys1).reshape(-1, 2)), _f32(np.asarray(keys2).reshape(-1, 2))
+            _check(self._L.vsg_two_view_reconstruct(self.device, _p(a, _f32p), n1, _p(b, _f32p), len(np.asarray(keys2).reshape(-1, 2)),
+                                                    *tail), "vsg_two_view_reconstruct")
+        out = dict(ok=bool(res.ok), reason=int(res.reason), model=int(res.model), R21=np.array(res.R21, np.float32).reshape(3, 3),
+                   t21=np.array(res.t21, np.float32), x3d=pts[:n1], triangulated=tri[:n1].astype(bool), SH=np.float32(res.SH),
+                   SF=np.float32(res.SF), best_it_h=int(res.best_it_h), best_it_f=int(res.best_it_f),
+                   H21=np.array(res.H21, np.float32).reshape(3, 3), F21=np.array(res.F21, np.float32).reshape(3, 3),
+                   n_good=np.array(res.n_good, np.int32), parallax=np.float32(res.parallax), n_inliers=int(res.n_inliers), result=res)
+        if per_hypothesis:
+            out.update(inlier_h=opt[0][:n_matches].astype(bool), inlier_f=opt[1][:n_matches].astype(bool), score_h=opt[2][:len(st)],
+                       score_f=opt[3][:len(st)])
+        return out
 
 
 def ComputeDistinctiveDescriptors(desc, off, device=0):
