@@ -1396,6 +1396,62 @@ int vsg_two_view_reconstruct(int device, const float *xy1, int n1, const float *
  * only.  n < 8, n_iter < 0, NULL sets, or a random_int result outside its range: VSG_ERR_INVALID. */
 int vsg_two_view_draw_sets(int n, int n_iter, int (*random_int)(int lo, int hi, void *ctx), void *ctx, int32_t *sets);
 
+/* MLPnPsolver (MLPnPsolver.cpp; constructed at Tracking.cc:3735, iterated at :3762) on a resident frame and resident map
+ * points: one call of iterate(n_iterations, ...) entered at mnIterations == first, EVERY hypothesis side by side.
+ * Hypothesis k depends on its six sampled correspondences alone, and what iterate returns is a selection over the
+ * hypotheses' inlier counts c[k].  Refine() (:303-362) solves over the best set into a local variable and never installs
+ * that pose: its CheckInliers counts hypothesis k's inliers again, so it succeeds iff c[k] > min_inliers and hands back
+ * hypothesis k's pose and flags; the solve changes nothing a caller can see and is not run here.  The loop (:120) walks
+ * k = first .. end - 1 with end = max(max_its, first + n_iterations): a k with c[k] >= min_inliers replaces the best on a
+ * strict maximum, and when c[k] > min_inliers the call returns hypothesis k (found = 1, refined = 1, no_more = 0,
+ * iterations = k + 1; the best may be an earlier hypothesis of a call before); past the loop, iterations >= max_its gives
+ * no_more = 1 and the best hypothesis when there is one (refined = 0).  The state between the reference's
+ * calls is (mnIterations, best), both functions of the sets and of first: a resumed call is this call with
+ * first = res->iterations of the call before, and the library keeps nothing.
+ *   slots[i] (one per feature of f) = the slot of vpMapPointMatches[i] in mp, < 0 for none or a bad one; correspondence
+ * index = rank among the entries >= 0.  fx, fy, cx, cy = the Pinhole parameters; level_sigma2 = mvLevelSigma2 (nlevels
+ * entries); th2 as SetRansacParameters takes it; min_inliers / max_its = mRansacMinInliers / mRansacMaxIts AFTER
+ * SetRansacParameters (vsg_mlpnp_ransac_parameters); sets[6 k .. 6 k + 5] = the six correspondence indices of hypothesis k
+ * in drawing order (vsg_mlpnp_draw_sets).
+ *   Outputs: inlier[i] (one per feature) = vbInliers; res as below; hyp_inliers[k] / hyp_T[12 k ..] (either may be NULL) =
+ * mnInliersi and [R | t] (3 x 4, row-major, double) of every hypothesis.  n < min_inliers (:111): no_more = 1, found = 0,
+ * the identity, flags cleared, nothing is enqueued.
+ *   Arithmetic (csrc/vsg_mlpnp.h, host and device from one source): double where the reference is,
+ * CheckInliers in its mixed double / float order with no positive-depth test; the nullspace of a bearing comes from a
+ * Householder reflection, the null vector of A^T A and the nearest rotation from a one-sided Jacobi, the 6 x 6 solve is
+ * an LDL^T without pivoting, acos / cbrt / sin / cos are written out -- deviations by rounding; the Jacobian is analytic
+ * and takes its limit at w = 0.  NaNs in res and hyp_T are canonical.
+ *   Checked before anything is enqueued (an error writes nothing and leaves no kernel behind), VSG_ERR_INVALID: a NULL
+ * handle, slots, level_sigma2, sets, inlier or res; frame and store on different devices; a slot >= capacity; nlevels
+ * outside [1, 16]; an octave of a used feature outside [0, nlevels); th2 not finite or <= 0; min_inliers < 6; max_its < 1;
+ * first < 0; n_iterations < 0; n_hyp outside [1, 1024]; max(max_its, first + n_iterations) > n_hyp; and when
+ * n >= min_inliers: a sample outside [0, n), two equal samples in one set.  Nleft != -1 (a KannalaBrandt8 pair):
+ * VSG_ERR_UNSUPPORTED, as in vsg_frame_pose_optimization.  One enqueue (three kernels) on the calling thread's stream and
+ * one wait; only the slots, the sets and a few scalars cross to the device. */
+typedef struct vsg_mlpnp_result {
+  float Tcw[16];           /* Tout, row-major */
+  int32_t found, no_more;  /* iterate's return value, bNoMore */
+  int32_t n_inliers;       /* nInliers */
+  int32_t refined;         /* 1 = returned through Refine(): hypothesis iterations - 1; 0 = the best at the loop's end (or nothing) */
+  int32_t best_hypothesis; /* b, or -1 */
+  int32_t iterations;      /* mnIterations on return */
+  int32_t n_correspondences; /* N */
+  int32_t n_records;         /* how often the best set was replaced up to the return, calls before included */
+} vsg_mlpnp_result;
+int vsg_frame_mlpnp_ransac(vsg_frame *f, vsg_mappoints *mp, const int32_t *slots, float fx, float fy, float cx, float cy,
+                           const float *level_sigma2, int nlevels, float th2, int min_inliers, int max_its, int first,
+                           int n_iterations, int n_hyp, const int32_t *sets, uint8_t *inlier, vsg_mlpnp_result *res,
+                           int32_t *hyp_inliers, double *hyp_T);
+/* MLPnPsolver::SetRansacParameters (:231-267) for n correspondences: the float N * epsilon truncated, the raise to
+ * min_inliers and min_set, the epsilon raise, ceil(log(1 - p) / log(1 - pow(epsilon, 3))) -- the exponent is 3 although
+ * the minimal set is 6 -- and max(1, min(nIterations, max_iterations)).  Host only.  n < 0, a NULL output: VSG_ERR_INVALID. */
+int vsg_mlpnp_ransac_parameters(double probability, int min_inliers, int max_iterations, int min_set, float epsilon, int n,
+                                int *min_inliers_out, int *max_its_out);
+/* The draw of :125-145 for n_hyp hypotheses over n correspondences, six per hypothesis, with the semantics of
+ * vsg_sim3_draw_samples.  Host only.  n < 6, n_hyp < 0, NULL sets, or a random_int result outside its range:
+ * VSG_ERR_INVALID. */
+int vsg_mlpnp_draw_sets(int n, int n_hyp, int (*random_int)(int lo, int hi, void *ctx), void *ctx, int32_t *sets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1540,6 +1540,91 @@ class ResidentSim3Solver {
   vsg_sim3_result res_;
 };
 
+// MLPnPsolver (MLPnPsolver.h, MLPnPsolver.cpp) on a resident frame and resident map points, with the reference's shape, so
+// that the relocalisation loop of Tracking.cc:3735-3762 stays as it is:
+//     vsg::MLPnPsolver *pSolver = new vsg::MLPnPsolver(F, mp, slots, K4, mCurrentFrame.mvLevelSigma2);
+//     pSolver->SetRansacParameters(0.99, 10, 300, 6, 0.5, 5.991);
+//     bool bTcw = pSolver->iterate(5, bNoMore, vbInliers, nInliers, Tcw);   // Tcw: row-major 4 x 4
+// The maintainer hands over slots[i] = the slot of vpMapPointMatches[i] in mp, -1 for a NULL or isBad() point, one entry per
+// feature of F (the constructor's filter, :66-98); K4 = {fx, fy, cx, cy} of the Pinhole camera.  Every iterate is ONE device
+// call (vsg_frame_mlpnp_ransac) that computes every hypothesis drawn so far side by side and selects as the reference's loop
+// does from mnIterations on (Refine()'s solve over the best set, whose result the reference never installs, is left out); the library keeps no state, the solver keeps mnIterations and the minimal sets.  The sets come
+// from vsg_mlpnp_draw_sets in the reference's drawing order -- DUtils::Random::RandomInt's formula over rand(), or randomInt
+// -- and are drawn as far as a call can walk: max(mRansacMaxIts, mnIterations + nIterations) hypotheses, 1024 at the most.
+class MLPnPsolver {
+ public:
+  typedef std::vector<float> Matrix;  // row-major 4 x 4
+  MLPnPsolver(const ResidentFrame &F, const ResidentMapPoints &mp, const std::vector<int32_t> &slots, const float K4[4],
+              const std::vector<float> &mvLevelSigma2, int (*randomInt)(int, int, void *) = nullptr, void *randomCtx = nullptr)
+      : f_(F.handle()), mp_(mp.handle()), slots_(slots), sigma2_(mvLevelSigma2), randomInt_(randomInt), randomCtx_(randomCtx) {
+    for (int k = 0; k < 4; ++k) K_[k] = K4[k];
+    if ((int)slots_.size() != F.N()) check(VSG_ERR_INVALID, "vsg::MLPnPsolver");
+    for (int32_t s : slots_) N_ += s >= 0 ? 1 : 0;
+    memset(&res_, 0, sizeof res_);
+    SetRansacParameters();
+  }
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6,
+                           float epsilon = 0.4f, float th2 = 5.991f) {
+    if (minSet != 6) check(VSG_ERR_UNSUPPORTED, "vsg::MLPnPsolver::SetRansacParameters");  // the minimal set of the device call
+    check(vsg_mlpnp_ransac_parameters(probability, minInliers, maxIterations, minSet, epsilon, N_, &mRansacMinInliers_, &mRansacMaxIts_),
+          "vsg_mlpnp_ransac_parameters");
+    th2_ = th2;
+  }
+  // MLPnPsolver::iterate (:104-229)
+  bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, Matrix &Tout) {
+    Tout.assign(16, 0.0f);
+    Tout[0] = Tout[5] = Tout[10] = Tout[15] = 1.0f;
+    bNoMore = false;
+    vbInliers.clear();
+    nInliers = 0;
+    if (N_ < mRansacMinInliers_) {  // :111-115
+      bNoMore = true;
+      return false;
+    }
+    if (nIterations < 0) nIterations = 0;
+    const int walk = mnIterations_ + nIterations, end = mRansacMaxIts_ > walk ? mRansacMaxIts_ : walk;
+    if (end > 1024) check(VSG_ERR_UNSUPPORTED, "vsg::MLPnPsolver::iterate");  // more hypotheses than one call takes
+    const int have = (int)(sets_.size() / 6);
+    if (end > have) {  // the draw goes on where it stopped: the sequence of RandomInt calls is the reference's
+      sets_.resize(6 * (size_t)end);
+      check(vsg_mlpnp_draw_sets(N_, end - have, randomInt_, randomCtx_, sets_.data() + 6 * (size_t)have), "vsg_mlpnp_draw_sets");
+    }
+    inlier_.assign(slots_.size() ? slots_.size() : 1, 0);
+    check(vsg_frame_mlpnp_ransac(f_, mp_, slots_.data(), K_[0], K_[1], K_[2], K_[3], sigma2_.data(), (int)sigma2_.size(), th2_,
+                                 mRansacMinInliers_, mRansacMaxIts_, mnIterations_, nIterations, (int)(sets_.size() / 6),
+                                 sets_.data(), inlier_.data(), &res_, nullptr, nullptr),
+          "vsg_frame_mlpnp_ransac");
+    mnIterations_ = res_.iterations;
+    bNoMore = res_.no_more != 0;
+    if (!res_.found) return false;
+    nInliers = res_.n_inliers;
+    vbInliers.assign(slots_.size(), false);
+    for (size_t i = 0; i < slots_.size(); ++i)
+      if (inlier_[i]) vbInliers[i] = true;
+    Tout.assign(res_.Tcw, res_.Tcw + 16);
+    return true;
+  }
+  int correspondences() const { return N_; }              // N
+  int iterations() const { return mnIterations_; }        // mnIterations
+  int minInliers() const { return mRansacMinInliers_; }   // mRansacMinInliers
+  int maxIterations() const { return mRansacMaxIts_; }    // mRansacMaxIts
+  const vsg_mlpnp_result &result() const { return res_; }
+  const std::vector<int32_t> &sets() const { return sets_; }
+
+ private:
+  vsg_frame *f_;
+  vsg_mappoints *mp_;
+  std::vector<int32_t> slots_;
+  std::vector<float> sigma2_;
+  float K_[4], th2_ = 5.991f;
+  int (*randomInt_)(int, int, void *);
+  void *randomCtx_;
+  int N_ = 0, mRansacMinInliers_ = 8, mRansacMaxIts_ = 300, mnIterations_ = 0;
+  std::vector<int32_t> sets_;
+  std::vector<uint8_t> inlier_;
+  vsg_mlpnp_result res_;
+};
+
 // Optimizer::OptimizeSim3 (Optimizer.h, Optimizer.cc:3261-3529) on two resident keyframes and resident map points, with
 // the reference's shape, so that the call sites of LoopClosing.cc:538 and :747 stay as they are:
 //     vsg::ResidentSim3Optimizer opt(kf1, kf2, mp1, mp2, pose1, pose2, mvInvLevelSigma2_1, mvInvLevelSigma2_2);

@@ -1,0 +1,170 @@
+"""The host build of csrc/vsg_mlpnp.h (tests/_mlpnpcore) against the NumPy restatement of MLPnPsolver (tests/mlpnp_reference.py):
+per hypothesis (R, t, count, flags), per solve over a best set (what Refine() computes and discards; the library keeps it for
+the caller-side path of the latency probe only), and as whole iterate sequences, resumed calls included.
+
+The library's deviations are roundings (a Householder nullspace basis, one-sided Jacobi instead of Eigen's SVD, the sums' order,
+an unpivoted LDL^T, written-out acos / cbrt / sin / cos), so the tolerances on R and t are TWICE THE LARGEST DIFFERENCE MEASURED
+on these scenes.  Measured (general and plane0 scenes of mlpnp_scenes.make(SEEDS[0] + n, n) for n = 30 / 100 / 300, the first 60
+sets each, 360 hypotheses, plus the solves over their best sets):
+    hypotheses   max |dR| = 8.1e-10   max |dt| = 1.98e-09   (general n = 30; every other scene stays below 1.4e-10)
+    best sets    max |dR| = 5.6e-16   max |dt| = 4.4e-16
+so TOL_R = 1.62e-9, TOL_T = 3.96e-9, for both.  Two caps bound what is left out of a comparison:
+  * a hypothesis only if its A^T A has a relative gap between its two smallest singular values below GAP_CUT = 1e-9 (the null
+    vector is then undetermined at double precision: its error is about 1e-16 / gap), or one of the restatement's Gauss-Newton
+    branch quantities (max|dx| vs 5, min|dx| vs 1, max|J dx| vs 1e-5, the two direction-test errors against each other) lies
+    within 1e-6 relative of its limit; at most 5 % of a scene's hypotheses.  Measured share: 0 of 360.
+  * an inlier decision only within 1e-3 relative of its threshold; at most 1 % of the decisions.  Measured share: 0 of 51600.
+No compared decision differs.  A plane OFF the origin ("plane1") takes the 12-column branch, where coplanar points leave the
+null vector undetermined (gap 0): for those scenes the branch alone is asserted, as the issue has it.  The scenes are the
+issue's as they stand (noise 0.5 px times the level scale, 30 % outliers, depth 1..6 m): nothing had to be changed to stay
+inside a cap."""
+import numpy as np
+import pytest
+
+import mlpnp_hostcore as hc
+import mlpnp_reference as mr
+import mlpnp_scenes as ms
+
+TOL_R, TOL_T = 1.62e-9, 3.96e-9
+GAP_CUT, NEAR, NEAR_INLIER = 1e-9, 1e-6, 1e-3
+N_SETS = 60
+MEASURED = {}
+
+
+def both(s):
+    pts = hc.points(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2)
+    rp = mr.make_points(ms.CAM, s["kx"], s["ky"], s["octave"], s["world_pos"], s["slots"], ms.LEVEL_SIGMA2, ms.TH2)
+    return pts, rp
+
+
+def left_out(info):
+    d = info["direction"]
+    near = any(abs(a - b) <= NEAR * b for a, b in info["gn"]["margins"]) or abs(d[0] - d[1]) <= NEAR * abs(d[1])
+    return info["gap"] < GAP_CUT or near
+
+
+def compare_pose(T, R, t, rp, flags, tally):
+    dR, dt = np.abs(T[:, :3] - R).max(), np.abs(T[:, 3] - t).max()
+    tally["dR"], tally["dt"] = max(tally["dR"], dR), max(tally["dt"], dt)
+    assert dR <= TOL_R and dt <= TOL_T, (dR, dt)
+    fl, e2 = mr.check_inliers(rp, R, t)
+    far = np.abs(e2.astype(np.float64) - rp["max_err"]) > NEAR_INLIER * rp["max_err"]
+    tally["decisions"] += len(fl)
+    tally["decisions_out"] += int((~far).sum())
+    assert np.array_equal(fl[far], flags[far])
+
+
+@pytest.mark.parametrize("kind", ("general", "plane0"))
+@pytest.mark.parametrize("n", ms.SIZES)
+def test_hypotheses_and_refinements(kind, n):
+    s = ms.make(ms.SEEDS[0] + n, n=n, kind=kind, n_hyp=N_SETS)
+    pts, rp = both(s)
+    assert np.array_equal(np.frombuffer(pts.tobytes(), np.float32).reshape(-1, 8)[:, 7], rp["max_err"])  # mvMaxError, exactly
+    H = hc.hypotheses(pts, ms.CAM, s["sets"])
+    tally, out = dict(dR=0.0, dt=0.0, decisions=0, decisions_out=0), 0
+    best = 0
+    rt = dict(dR=0.0, dt=0.0, decisions=0, decisions_out=0)
+    for k, idx in enumerate(s["sets"]):
+        R, t, info = mr.compute_pose(rp["f"][idx], rp["X"][idx])
+        assert info["planar"] == bool(H["info"][k, 0]) == (kind == "plane0")  # which branch the scene takes
+        if left_out(info):
+            out += 1
+            continue
+        compare_pose(H["T"][k], R, t, rp, H["flags"][k], tally)
+        if H["counts"][k] >= 10 and H["counts"][k] > best:  # a new best set: the solve Refine() runs over it (and discards)
+            best = H["counts"][k]
+            member = np.flatnonzero(H["flags"][k])
+            Rr, tr, ri = mr.compute_pose(rp["f"][member], rp["X"][member])
+            if not left_out(ri):
+                r = hc.refine(pts, ms.CAM, H["flags"][k])
+                assert bool(r["info"][0]) == ri["planar"]
+                compare_pose(r["T"], Rr, tr, rp, r["flags"], rt)
+    MEASURED[(kind, n)] = (tally, rt, out)
+    print("\n%s %d: hypotheses dR %.2g dt %.2g, refinements dR %.2g dt %.2g, left out %d of %d, decisions left out %d of %d"
+          % (kind, n, tally["dR"], tally["dt"], rt["dR"], rt["dt"], out, N_SETS, tally["decisions_out"], tally["decisions"]))
+    assert out <= 0.05 * N_SETS
+    assert tally["decisions_out"] <= 0.01 * tally["decisions"] and rt["decisions_out"] <= 0.01 * max(rt["decisions"], 1)
+
+
+@pytest.mark.parametrize("n", ms.SIZES)
+def test_a_plane_off_the_origin_takes_the_12_column_branch(n):
+    s = ms.make(ms.SEEDS[0] + n, n=n, kind="plane1", n_hyp=12)
+    pts, rp = both(s)
+    H = hc.hypotheses(pts, ms.CAM, s["sets"])
+    assert not H["info"][:, 0].any()
+    assert not any(mr.compute_pose(rp["f"][idx], rp["X"][idx])[2]["planar"] for idx in s["sets"])
+
+
+def drive(s, outliers_all=False):
+    """The reference's use of iterate (Tracking.cc:3762: iterate(5, ...) until it returns or bNoMore), on the restatement and,
+    call by call with first = the iterations so far, on the library."""
+    pts, rp = both(s)
+    mi, mx = mr.ransac_parameters(0.99, 10, 300, 6, 0.5, s["n"])
+    assert (mi, mx) == hc.parameters(0.99, 10, 300, 6, 0.5, s["n"])
+    solver = mr.Solver(rp, s["sets"], mi, mx)
+    first, calls = 0, 0
+    while True:
+        want = solver.iterate(5)
+        got = hc.ransac(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2, mi, mx, first, 5)
+        r = got["res"]
+        calls += 1
+        assert (r["found"], r["no_more"], r["iterations"], r["refined"]) == \
+            (int(want["found"]), int(want["no_more"]), solver.iterations, int(want["refined"])), (calls, r, want)
+        if want["found"]:
+            assert np.abs(r["Tcw"] - want["T"]).max() <= 1e-6  # float32 of poses TOL apart
+            fl = np.zeros(s["n_feat"], bool)
+            fl[s["where"]] = want["inlier"]
+            _, e2 = mr.check_inliers(rp, want["T"][:3, :3].astype(np.float64), want["T"][:3, 3].astype(np.float64))
+            assert r["n_inliers"] == want["n_inliers"] and np.array_equal(got["inlier"].astype(bool), fl)
+            assert r["best_hypothesis"] == solver.best_k
+        else:
+            assert not got["inlier"].any() and (r["Tcw"] == np.eye(4)).all() and r["n_inliers"] == 0
+        first = r["iterations"]
+        if want["found"] or want["no_more"]:
+            return calls, want, solver
+
+
+@pytest.mark.parametrize("kind", ("general", "plane0"))
+@pytest.mark.parametrize("n", ms.SIZES)
+def test_iterate_sequences_on_a_true_candidate(kind, n):
+    s = ms.make(ms.SEEDS[1] + n, n=n, kind=kind, n_hyp=320)
+    calls, want, solver = drive(s)
+    assert want["found"]
+
+
+@pytest.mark.parametrize("n", ms.SIZES)
+def test_iterate_sequences_on_a_false_candidate(n):
+    s = ms.make(ms.SEEDS[2] + n, n=n, outliers=1.0, n_hyp=320)
+    calls, want, solver = drive(s)
+    assert calls == 1 and want["no_more"] and not want["found"] and solver.iterations == solver.max_its  # the first call walks them all
+
+
+def test_resumed_calls_past_max_its():
+    """A caller that goes on after a converged return: every later call walks at least 5 more, past mRansacMaxIts."""
+    s = ms.make(ms.SEEDS[1] + 100, n=100, n_hyp=60)
+    pts, rp = both(s)
+    mi, mx = 50, 8
+    solver = mr.Solver(rp, s["sets"], mi, mx)
+    first = 0
+    for call in range(6):
+        want = solver.iterate(5)
+        r = hc.ransac(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2, mi, mx, first, 5)["res"]
+        assert (r["found"], r["no_more"], r["iterations"], r["refined"]) == \
+            (int(want["found"]), int(want["no_more"]), solver.iterations, int(want["refined"])), call
+        if want["found"]:
+            assert r["n_inliers"] == want["n_inliers"]
+        first = r["iterations"]
+    assert first > mx
+
+
+def test_the_selection_alone_against_the_loop():
+    rng = np.random.default_rng(4)
+    for trial in range(300):
+        nh = int(rng.integers(1, 40))
+        c = rng.integers(0, 14, nh).astype(np.int32)
+        mi, mx = int(rng.integers(6, 12)), int(rng.integers(1, nh + 1))
+        first = int(rng.integers(0, nh + 1))
+        n_it = int(rng.integers(0, nh - first + 1))
+        got = hc.select(c, first, n_it, mx, mi)
+        want = mr.loop_on_counts(c, first, n_it, mx, mi)
+        assert got == want, (trial, c, first, n_it, mx, mi)

@@ -13,6 +13,7 @@
 #include "vsg_sim3.h"
 #include "vsg_sim3_opt.h"
 #include "vsg_triangulate.h"
+#include "vsg_mlpnp.h"
 #include "vsg_two_view.h"
 
 extern "C" {
@@ -222,6 +223,64 @@ int s3_host_side(int n, const float *Xw1, const float *Xw2, const float *max_err
   vsg::sim3::ransac_host(n, Xw1, Xw2, max_err1, max_err2, *kf1, *kf2, fix_scale != 0, min_inliers, n_hyp, samples, true, pts.data(),
                          counts.data(), inlier, res, nullptr, nullptr);
   return res->iterations;
+}
+
+// The caller-side MLPnPsolver (MLPnPsolver.cpp) on positions read back from the store: Xw = the positions of the features with a
+// slot, in feature order.  The header's set-up, then iterate's loop (:120-228) as the reference runs it from mnIterations == 0,
+// hypothesis after hypothesis on one thread WITH the early return.  Refine() (:303-362) is run as the reference runs it: the
+// solve over the best set, whose result the reference drops (it stays in a local), then CheckInliers on hypothesis k's pose
+// again.  The device call leaves that solve out; ml_discarded keeps the compiler from doing the same here.
+volatile double ml_discarded;
+int ml_host_side(int n_feat, const int32_t *slots, const float *Xw, const float *kx, const float *ky, const int32_t *octave,
+                 const float *cam, const float *level_sigma2, float th2, int min_inliers, int max_its, int n_iterations,
+                 const int32_t *sets, uint8_t *inlier, vsg_mlpnp_result *res) {
+  namespace ml = vsg::mlpnp;
+  static thread_local std::vector<ml::Point> pts;
+  static thread_local std::vector<uint8_t> flags, best_flags;
+  const ml::Camera c = {cam[0], cam[1], cam[2], cam[3]};
+  pts.clear();
+  for (int i = 0; i < n_feat; i++) {
+    inlier[i] = 0;
+    if (slots[i] >= 0) pts.push_back(ml::make_point(c, kx[i], ky[i], level_sigma2[octave[i]], th2, Xw + 3 * pts.size()));
+  }
+  const int n = (int)pts.size();
+  if (n < min_inliers) {
+    ml::fill_no_more(n, res);
+    return 0;
+  }
+  flags.assign((size_t)n, 0), best_flags.assign((size_t)n, 0);
+  auto scatter = [&](const uint8_t *fl) {
+    for (int i = 0, e = 0; i < n_feat; i++)
+      if (slots[i] >= 0) inlier[i] = fl[e++];
+  };
+  ml::Selection s = {0, 0, 0, -1, -1, 0, 0};
+  ml::Pose best_T{}, T, dropped;
+  int best_count = 0, cur = 0;
+  while (s.iterations < max_its || cur < n_iterations) {
+    cur++;
+    const int k = s.iterations++;
+    ml::hypothesis_host(pts.data(), sets + 6 * (size_t)k, &T, nullptr);
+    int cnt = 0;
+    for (int i = 0; i < n; i++) cnt += (flags[(size_t)i] = ml::is_inlier(T, c, pts[(size_t)i]) ? 1 : 0);
+    if (cnt < min_inliers) continue;
+    if (cnt > best_count) best_count = cnt, best_T = T, best_flags = flags, s.best = k, s.records++;
+    ml::member_pose_host(pts.data(), best_flags.data(), n, &dropped, nullptr);  // :305-337
+    ml_discarded = dropped.t[0];
+    int rc = 0;  // :340: mRi / mti are still hypothesis k's
+    for (int i = 0; i < n; i++) rc += (flags[(size_t)i] = ml::is_inlier(T, c, pts[(size_t)i]) ? 1 : 0);
+    if (rc > min_inliers) {
+      s.found = 1, s.refined = 1, s.pose = k;
+      scatter(flags.data());
+      ml::fill_result(s, &T, rc, n, res);
+      return s.iterations;
+    }
+  }
+  if (s.iterations >= max_its) {
+    s.no_more = 1;
+    if (s.best >= 0) s.found = 1, s.pose = s.best, scatter(best_flags.data());
+  }
+  ml::fill_result(s, s.found ? &best_T : nullptr, s.found ? best_count : 0, n, res);
+  return s.iterations;
 }
 
 // The caller-side TwoViewReconstruction::Reconstruct on keypoints the caller holds (two_view::reconstruct_host), the two model

@@ -43,6 +43,16 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
                  early exit (NOT Eigen: the header's own arithmetic)
             B  = vsg_mappoints_sim3_ransac (every hypothesis, no early exit);  A2 / B2 = both again.  Equal results asserted
 
+  mlpnp     MLPnPsolver on a resident 1000-feature frame and a store of 4096 slots (Tracking::Relocalization, Tracking.cc:3735-3762):
+            30 / 100 / 300 correspondences, SetRansacParameters(0.99, 10, 300, 6, 0.5, 5.991), the first iterate(5, ...); "true" = a
+            true candidate (30 % outliers: the reference returns after a handful of hypotheses), "false" = a false one (every
+            correspondence an outlier: all of mRansacMaxIts are walked)
+            A  = vsg_mappoints_read + the host build of csrc/vsg_mlpnp.h on one thread WITH the reference's early return and
+                 WITH Refine()'s solve over the best set, whose result the reference drops (NOT Eigen: the header's own Jacobi
+                 and LDL^T)
+            B  = vsg_frame_mlpnp_ransac (every hypothesis, no early return, no dropped solve);  A2 / B2 = both again.  Equal
+                 results asserted on every call
+
   twoview   TwoViewReconstruction::Reconstruct (Tracking.cc:2568): 100 / 300 / 1000 matches between two frames of 1000 / 1000 /
             2000 features, 200 sets.  A = the host build of csrc/vsg_two_view.h on one thread, given the keypoint arrays (NOT
             Eigen), AT = the same with H and F on two threads as the reference runs them, B = vsg_frame_two_view_reconstruct;
@@ -66,7 +76,7 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
             existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
             carries them.  Both write into profiles/track_chain_latency.json, one key each
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|sim3opt|localba|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -96,7 +106,7 @@ def host_side(orb):
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
            csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
-           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h"]
+           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-pthread", "-I", str(csrc), "-o",
                                str(so), str(src[0])])
@@ -123,6 +133,8 @@ def host_side(orb):
     H.lb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
                                C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
                                C.POINTER(C.c_double), C.c_void_p]
+    H.ml_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, _i32p,
+                               _u8p, C.c_void_p]
     H.tv_host_side.argtypes = [_f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_void_p, C.c_int, _i32p, C.c_int, C.c_void_p, _u8p, _f32p]
     H.tk_slots_from_matches.restype = H.tk_blocked_from_slots.restype = None
     H.tk_slots_from_matches.argtypes = [C.c_int, _i32p, _i32p, _i32p, _i32p]
@@ -669,6 +681,69 @@ class Sim3(Case):
                              "Sophus); B = vsg_mappoints_sim3_ransac, which computes all hypotheses"}
 
 
+class Mlpnp(Case):
+    """MLPnPsolver on a resident frame: a scene of tests/mlpnp_scenes.py (TUM1 intrinsics, 0.5 px noise times the level scale),
+    its correspondences scattered among 1000 features and 4096 store slots.  A size is "<correspondences>:<true|false>"."""
+    SIZES = tuple("%d:%s" % (n, c) for n in (30, 100, 300) for c in ("true", "false"))
+    TH, DEST = 0.0, "mlpnp_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+    CAP = 4096
+
+    def __init__(self, orb, fr, size):
+        import mlpnp_scenes as ms
+        n, kind = int(size.split(":")[0]), size.split(":")[1]
+        self.orb, self.n, self.kind, self.ms = orb, n, kind, ms
+        s = self.s = ms.make(8000 + n, n=n, outliers=0.3 if kind == "true" else 1.0, n_hyp=300, capacity=self.CAP, extra=NFEAT - n - 7)
+        c = np.ascontiguousarray
+        keys = np.zeros(s["n_feat"], orb.KP_DTYPE)
+        keys["x"], keys["y"], keys["octave"], keys["size"], keys["angle"] = s["kx"], s["ky"], s["octave"], 31.0, -1.0
+        self.F = orb.Frame(s["n_feat"] + 1).upload(keys, np.zeros((s["n_feat"], 32), np.uint8), (0.0, 0.0, 640.0, 480.0))
+        self.mp = orb.MapPoints(self.CAP)
+        self.mp.update(np.arange(self.CAP), world_pos=s["world_pos"])
+        self.min_inliers, self.max_its = orb.mlpnp_ransac_parameters(n)
+        self.slots, self.sets = c(s["slots"], np.int32), c(s["sets"][:self.max_its], np.int32)
+        self.used = c(s["slots"][s["slots"] >= 0], np.int32)
+        self.kx, self.ky, self.oct = c(s["kx"], np.float32), c(s["ky"], np.float32), c(s["octave"], np.int32)
+        self.cam, self.sig = np.array(ms.CAM, np.float32), c(ms.LEVEL_SIGMA2, np.float32)
+        self.Xw = np.zeros(3 * n, np.float32)
+        self.inlier, self.res = np.zeros(s["n_feat"], np.uint8), orb.MlpnpResult()
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.inlier[:] = 9
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        ms = self.ms
+        if name.startswith("B"):
+            return L.vsg_frame_mlpnp_ransac(self.F.handle, self.mp.handle, p(self.slots, _i32p), *[float(v) for v in self.cam],
+                                            p(self.sig, _f32p), ms.NLEVELS, ms.TH2, self.min_inliers, self.max_its, 0, 5, self.max_its,
+                                            p(self.sets, _i32p), p(self.inlier, _u8p), C.byref(self.res), None, None)
+        rc = L.vsg_mappoints_read(self.mp.handle, self.n, p(self.used, _i32p), p(self.Xw, _f32p), None, None, None, None, None)
+        if rc != 0:
+            return rc
+        H.ml_host_side(len(self.slots), p(self.slots, _i32p), p(self.Xw, _f32p), p(self.kx, _f32p), p(self.ky, _f32p), p(self.oct, _i32p),
+                       p(self.cam, _f32p), p(self.sig, _f32p), ms.TH2, self.min_inliers, self.max_its, 5, p(self.sets, _i32p),
+                       p(self.inlier, _u8p), C.byref(self.res))
+        return 0
+
+    def result(self, name, r):
+        return (r, self.inlier.copy(), np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.MlpnpResult.from_buffer_copy(last["B"][2].tobytes())
+        return {"correspondences": self.n, "case": self.kind, "features": len(self.slots), "min_inliers": self.min_inliers,
+                "hypotheses_computed_by_the_device_call": self.max_its, "found": bool(r.found), "refined": bool(r.refined),
+                "no_more": bool(r.no_more), "hypotheses_walked_by_the_reference_loop": int(r.iterations), "n_inliers": int(r.n_inliers),
+                "store_slots": self.CAP,
+                "host_side": "A = vsg_mappoints_read + the host build of csrc/vsg_mlpnp.h on one thread with the reference's early "
+                             "return and Refine()'s dropped solve over the best set (tools/resident_points_cpu.cpp; THIS header's "
+                             "build and NOT Eigen: its one-sided Jacobi and unpivoted LDL^T, no JacobiSVD, no sparse matrices); "
+                             "B = vsg_frame_mlpnp_ransac, which computes all hypotheses and leaves the dropped solve out"}
+
+
 class TwoView(Case):
     """TwoViewReconstruction::Reconstruct (Tracking::MonocularInitialization, Tracking.cc:2568): a general scene of
     tests/two_view_scenes.py, 200 sets.  A size is "<matches>:<features per frame>".  AT = A with the two model searches on two
@@ -1038,7 +1113,7 @@ class TrackLocal(Chain, Local):
                     entry_slots=int((self.entry >= 0).sum()))
 
 
-CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3,
+CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3, "mlpnp": Mlpnp,
          "sim3opt": Sim3Opt, "localba": LocalBA, "twoview": TwoView}
 
 

@@ -102,6 +102,9 @@ EXPORTS = [
     # TwoViewReconstruction::Reconstruct (the monocular initialisation) on two resident frames or on caller arrays, the
     # reference's default parameters and the host-side draw of the minimal sets
     "vsg_frame_two_view_reconstruct", "vsg_two_view_reconstruct", "vsg_two_view_default_params", "vsg_two_view_draw_sets",
+    # MLPnPsolver on a resident frame and resident map points: one iterate() call with every hypothesis side by side, and
+    # the host-side set-up of the solver
+    "vsg_frame_mlpnp_ransac", "vsg_mlpnp_ransac_parameters", "vsg_mlpnp_draw_sets",
     # test hook: the launch forms of the last enqueue
     "vsg_debug_last_launch_forms",
     # test hook: the query state of one keyframe of the resident KeyFrameDatabase
@@ -248,6 +251,14 @@ class TwoViewResult(C.Structure):
                 ("best_it_h", C.c_int32), ("best_it_f", C.c_int32), ("H21", C.c_float * 9), ("F21", C.c_float * 9),
                 ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("n_good", C.c_int32 * 8), ("parallax", C.c_float),
                 ("n_inliers", C.c_int32)]
+
+
+class MlpnpResult(C.Structure):
+    """include/vsg_orb.h vsg_mlpnp_result: Tout (row-major), iterate's return value, bNoMore, nInliers, whether the return went
+    through Refine() (hypothesis iterations - 1) or is the best at the loop's end, the best hypothesis, mnIterations on return,
+    the correspondences and how often the best set was replaced."""
+    _fields_ = [("Tcw", C.c_float * 16)] + [(k, C.c_int32) for k in (
+        "found", "no_more", "n_inliers", "refined", "best_hypothesis", "iterations", "n_correspondences", "n_records")]
 
 
 # vsg_two_view_result.reason / .model
@@ -522,6 +533,10 @@ def load_library():
     L.vsg_two_view_default_params.argtypes = [C.POINTER(TwoViewParams)]
     L.vsg_two_view_default_params.restype = None
     L.vsg_two_view_draw_sets.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
+    L.vsg_frame_mlpnp_ransac.argtypes = [vp, vp, _i32p, cf, cf, cf, cf, _f32p, ci, cf, ci, ci, ci, ci, ci, _i32p, _u8p,
+                                         C.POINTER(MlpnpResult), _i32p, _f64p]
+    L.vsg_mlpnp_ransac_parameters.argtypes = [C.c_double, ci, ci, ci, cf, ci, _i32p, _i32p]
+    L.vsg_mlpnp_draw_sets.argtypes = [ci, ci, _RANDOM_INT, vp, _i32p]
     L.vsg_mappoints_local_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
                                                         _u8p, C.POINTER(BaCamera), _f32p, ci, ci, _u8p, C.POINTER(PoseSE3d),
                                                         _f32p, _u8p, _f64p, C.POINTER(LocalBaResult)]
@@ -1414,6 +1429,25 @@ def two_view_draw_sets(n, n_iter, random_int=None):
     return out[:int(n_iter)]
 
 
+def mlpnp_ransac_parameters(n, probability=0.99, min_inliers=10, max_iterations=300, min_set=6, epsilon=0.5):
+    """MLPnPsolver::SetRansacParameters for n correspondences (the defaults are Tracking.cc:3736's): (mRansacMinInliers,
+    mRansacMaxIts) as the solver holds them afterwards (host only)."""
+    out = np.zeros(2, np.int32)
+    _check(load_library().vsg_mlpnp_ransac_parameters(float(probability), int(min_inliers), int(max_iterations), int(min_set),
+                                                      float(epsilon), int(n), _p(out[:1], _i32p), _p(out[1:], _i32p)),
+           "vsg_mlpnp_ransac_parameters")
+    return int(out[0]), int(out[1])
+
+
+def mlpnp_draw_sets(n, n_hyp, random_int=None):
+    """The minimal sets of MLPnPsolver::iterate (:125-145) for n_hyp hypotheses over n correspondences: n_hyp x 6 int32.
+    random_int(lo, hi) stands for DUtils::Random::RandomInt; None: its formula over the C library's rand() (host only)."""
+    out = np.zeros((max(int(n_hyp), 1), 6), np.int32)
+    cb = _RANDOM_INT(lambda lo, hi, _ctx: int(random_int(lo, hi))) if random_int is not None else _RANDOM_INT()
+    _check(load_library().vsg_mlpnp_draw_sets(int(n), int(n_hyp), cb, None, _p(out, _i32p)), "vsg_mlpnp_draw_sets")
+    return out[:int(n_hyp)]
+
+
 class TwoViewReconstruction:
     """TwoViewReconstruction(k, sigma, iterations) (TwoViewReconstruction.cc:31-38) with Reconstruct on the device: every
     homography and fundamental-matrix hypothesis, the selection, the motion hypotheses and CheckRT in one enqueue and one wait
@@ -1857,6 +1891,34 @@ class Frame:
             len(inv_level_sigma2), int(hold_round), _p(out, _u8p), _p(c2, _f32p), C.byref(res)),
             "vsg_frame_pose_optimization")
         return self._pose_result(ret, res, out[:len(self.kps)], c2[:len(self.kps)])
+
+    def mlpnp_ransac(self, mp, slots, camera, level_sigma2, sets, min_inliers, max_its, first=0, n_iterations=5, th2=5.991,
+                     per_hypothesis=False):
+        """MLPnPsolver::iterate(n_iterations, ...) entered at mnIterations == first (vsg_frame_mlpnp_ransac): slots[i] = slot of
+        vpMapPointMatches[i] in mp (< 0: none), one per feature; camera = (fx, fy, cx, cy); level_sigma2 = mvLevelSigma2;
+        sets = n_hyp x 6 correspondence indices (mlpnp_draw_sets); min_inliers / max_its from mlpnp_ransac_parameters.  A
+        resumed call passes first = the `iterations` of the call before.  Returns a dict: found, no_more, n_inliers, refined,
+        best_hypothesis, iterations, n_correspondences, n_records, Tcw (4 x 4 float32), inlier (bool per feature), result
+        (the raw MlpnpResult) and, with per_hypothesis, hyp_inliers and hyp_T (n_hyp x 3 x 4 float64)."""
+        if len(slots) != len(self.kps):
+            raise ValueError("slots length does not match the frame's features")
+        sl, sig = _i32(slots), _f32(level_sigma2)
+        sm = np.ascontiguousarray(sets, np.int32).reshape(-1, 6)
+        nh = len(sm)
+        inl = np.zeros(max(len(self.kps), 1), np.uint8)
+        hc, hT = np.zeros(max(nh, 1), np.int32), np.zeros((max(nh, 1), 3, 4), np.float64)
+        res = MlpnpResult()
+        _check(self._L.vsg_frame_mlpnp_ransac(
+            self._h, mp.handle, _p(sl, _i32p), *[float(np.float32(c)) for c in camera], _p(sig, _f32p), len(sig), float(th2),
+            int(min_inliers), int(max_its), int(first), int(n_iterations), nh, _p(sm, _i32p), _p(inl, _u8p), C.byref(res),
+            _p(hc, _i32p) if per_hypothesis else None, _p(hT, C.POINTER(C.c_double)) if per_hypothesis else None), "vsg_frame_mlpnp_ransac")
+        out = dict(found=bool(res.found), no_more=bool(res.no_more), n_inliers=res.n_inliers, refined=bool(res.refined),
+                   best_hypothesis=res.best_hypothesis, iterations=res.iterations, n_correspondences=res.n_correspondences,
+                   n_records=res.n_records, Tcw=np.array(res.Tcw[:], np.float32).reshape(4, 4),
+                   inlier=inl[:len(self.kps)].astype(bool), result=res)
+        if per_hypothesis:
+            out.update(hyp_inliers=hc[:nh], hyp_T=hT[:nh])
+        return out
 
     def pose_optimization_resume(self, outlier, removed=None, chi2=None):
         """Round 2's classification and round 3 of a held pose_optimization.  removed[i] != 0: the plane step set
