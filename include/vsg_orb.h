@@ -1328,6 +1328,58 @@ int vsg_mappoints_local_bundle_adjustment(
     const float *inv_level_sigma2, int nlevels, int iterations, const volatile uint8_t *stop_flag,
     vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *erase, double *chi2, vsg_local_ba_result *res);
 
+/* The visual part of void Optimizer::BundleAdjustment(vpKFs, vpMP, ..., nIterations, pbStopFlag, nLoopKF, bRobust, ...)
+ * (Optimizer.cc:60-287, :500-610) as Optimizer::GlobalBundleAdjustemnt calls it (:45-58) on resident keyframes and resident
+ * map points: from Tracking::CreateInitialMapMonocular (Tracking.cc:2652: 20 iterations, bRobust = true, nLoopKF = 0) and from
+ * LoopClosing::RunGlobalBundleAdjustment (LoopClosing.cc:2157: 10 iterations, bRobust = false).  The keyframe vertices
+ * (:117-130), the point vertices with their monocular and stereo edges (:143-287), optimize(nIterations) and the write-back
+ * (:500-610), in double, with the arithmetic of csrc/vsg_local_ba.h and csrc/vsg_global_ba.h, which a host build reproduces
+ * bit for bit.  The marker, plane, room and door vertices and their edges (:289-498, :612-640) are NOT
+ * part of it: a caller whose lists of those are not empty keeps the reference routine; at the monocular
+ * initialisation they are always empty.  The arguments are those of vsg_mappoints_local_bundle_adjustment except:
+ *   - kfs = EVERY keyframe of the map with !isBad() (:120), in ascending mnId; kf_fixed[k] != 0 for mnId ==
+ *     pMap->GetInitKFid() (:126).  No fixed keyframe is NO reason to return: the reference has no such check here.
+ *   - the lists hold the observations that pass :166-169, in mObservations' order; edge e is stereo when that keyframe's
+ *     u_right[idx] >= 0 (:204), else mono (:174).
+ *   - robust (:189, :221): 1 = RobustKernelHuber with the float deltas sqrt(5.99) / sqrt(7.815) of :133-134 (5.99, not the
+ *     5.991 of the local call); 0 = no kernel, rho = chi2 and weight 1.  iterations = nIterations, within [1, 100].
+ *   - nothing is classified: there is no erase out, and no recovery beyond g2o's own pop.  The counts of :529-584 are read
+ *     by nothing and are left out.  chi2[e] (may be NULL) = e->chi2() as the LAST computeActiveErrors left it, NaN canonical.
+ *   - write_store (:516, :600): 1 = the case nLoopKF == pMap->GetOriginKF()->mnId: the float position of every included
+ *     point is written into its slot's world_pos (SetWorldPos); follow with
+ *     vsg_mappoints_refresh_from_observations(VSG_REFRESH_NORMAL) (UpdateNormalAndDepth).  0 = the store's bytes are
+ *     untouched and the positions come back in world_pos_out alone (mPosGBA, mnBAGlobalForKF stay with the caller), which
+ *     must then be non-NULL.
+ *   - kf_Tcw_out[k]: an optimised keyframe with at least one edge gets vSE3->estimate(), every other keyframe its input,
+ *     widened; the float casts of :518 / :522 stay with the caller.  included[i] = 0 for a point with an empty list
+ *     (vbNotIncludedMP, :278-286): its out is what its slot holds and the slot is not written.
+ *   - res->ran = 0: no edge, the stop flag set on entry, or n_points == 0: nothing is enqueued and only res and included
+ *     are written.  stop_reason as in the local call.
+ * Checked before anything is enqueued (an error writes nothing and leaves no kernel behind; so does a failed reservation of
+ * the arenas: included, the first out written, is filled behind it.  Only VSG_ERR_HIP from a launch or the stream's wait can
+ * leave included written), VSG_ERR_INVALID: everything the
+ * local call lists (with included in the place of erase), and: robust or write_store outside {0, 1}; write_store == 0 with
+ * a NULL world_pos_out; a NULL included.  VSG_ERR_UNSUPPORTED: a keyframe with Nleft != -1 (EdgeSE3ProjectXYZToBody, :241-275),
+ * edges but no optimised keyframe with one, more than 512 optimised keyframes with edges.  At that cap the reduced system has
+ * 3072 rows and is a matrix of 75.5 MB; with the lists and the per-edge blocks of a map of 60000 points and 500000
+ * observations (664 bytes of blocks per observation) the calling thread's device arena then holds about 450 MB.
+ * The reduced system is solved by a chain of kernels over the whole chip whatever its size.  Two threads
+ * may solve on the same store at the same time ONLY when their point sets are disjoint.  The call waits for its stream
+ * before it returns, on an error too. */
+typedef struct vsg_global_ba_result {
+  int32_t ran;              /* 0: returned before optimize (no edge, the stop flag, no point) */
+  int32_t n_opt_kf, n_fixed_kf, n_points, n_edges, n_mono, n_stereo;
+  int32_t iterations_run, trials_run, stop_reason;   /* iterations done | Terminate | nBad >= 3 | the stop flag */
+  double lambda, chi2_initial, chi2_final;
+} vsg_global_ba_result;
+int vsg_mappoints_global_bundle_adjustment(
+    vsg_mappoints *mp, int n_points, const int32_t *slots,
+    const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx,
+    int n_kf, vsg_frame *const *kfs, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed, const vsg_ba_camera *kf_cam,
+    const float *inv_level_sigma2, int nlevels, int iterations, int robust, int write_store,
+    const volatile uint8_t *stop_flag,
+    vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *included, double *chi2, vsg_global_ba_result *res);
+
 /* bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, T21, vP3D, vbTriangulated)
  * (TwoViewReconstruction.cc:40-129; Tracking::MonocularInitialization, Tracking.cc:2568, through
  * Pinhole::ReconstructWithTwoViews, Pinhole.cpp:91-101): the monocular initialisation behind

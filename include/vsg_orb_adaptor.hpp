@@ -555,6 +555,18 @@ struct LocalBAResult {
   vsg_local_ba_result res;
 };
 
+// What vsg::ResidentMapPoints::GlobalBundleAdjustment returns: vSE3->estimate() per keyframe (the fixed keyframe, or one
+// without an edge: its input, widened), the float position per point (mPosGBA; written into its slot only in the
+// nLoopKF == origin case), included[i] = !vbNotIncludedMP[i], the chi2 per observation, and the counters of
+// vsg_global_ba_result.
+struct GlobalBAResult {
+  std::vector<vsg_pose_se3d> kfTcw;
+  std::vector<float> worldPos;
+  std::vector<uint8_t> included;
+  std::vector<double> chi2;
+  vsg_global_ba_result res;
+};
+
 class ResidentMapPoints {
  public:
   explicit ResidentMapPoints(int capacity, int device = 0) {
@@ -625,6 +637,47 @@ class ResidentMapPoints {
                                                 E ? r.erase.data() : &none_erase, E ? r.chi2.data() : nullptr, &r.res),
           "vsg_mappoints_local_bundle_adjustment");
     if (!r.res.ran) {  // the reference returned before optimize: nothing was written, the outs are the inputs
+      for (size_t k = 0; k < K; ++k)
+        for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
+      if (n)
+        check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+              "vsg_mappoints_read");
+    }
+    return r;
+  }
+  // The visual part of Optimizer::BundleAdjustment as Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag,
+  // nLoopKF, bRobust) calls it (Optimizer.cc:45-287, :500-610) on the device (vsg_mappoints_global_bundle_adjustment): the
+  // lists are LocalBundleAdjustment's, with keyFrames = EVERY keyframe of the map with !isBad() in ascending mnId and
+  // kfFixed != 0 for mnId == GetInitKFid() alone.  loopKFIsOrigin = (nLoopKF == pMap->GetOriginKF()->mnId): the positions
+  // are then written into the slots (follow with Refresh(..., VSG_REFRESH_NORMAL)) and the caller SetPose()s kfTcw;
+  // otherwise the store is untouched and the caller keeps kfTcw / worldPos as mTcwGBA / mPosGBA.  Tracking.cc:2652 passes
+  // 20, nullptr, true and loopKFIsOrigin = true; LoopClosing.cc:2157 passes 10, &mbStopGBA, false.  Marker, plane, room and
+  // door vertices are not part of it: keep the reference routine when the map's lists of those are not empty.
+  GlobalBAResult GlobalBundleAdjustment(const std::vector<int32_t> &slots, const std::vector<int32_t> &obsOff,
+                                        const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                                        const std::vector<vsg_frame *> &keyFrames, const std::vector<vsg_pose_se3> &kfTcw,
+                                        const std::vector<uint8_t> &kfFixed, const std::vector<vsg_ba_camera> &kfCam,
+                                        const std::vector<float> &mvInvLevelSigma2, int nIterations = 5,
+                                        const volatile uint8_t *pbStopFlag = nullptr, bool bRobust = true,
+                                        bool loopKFIsOrigin = false) {
+    const size_t n = slots.size(), K = keyFrames.size();
+    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || kfTcw.size() != K || kfFixed.size() != K ||
+        kfCam.size() != K || (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())))
+      throw std::runtime_error("ResidentMapPoints::GlobalBundleAdjustment: the arrays' sizes do not match");
+    const size_t E = n ? (size_t)obsOff[n] : 0;
+    GlobalBAResult r;
+    r.kfTcw.resize(K), r.worldPos.assign(3 * n, 0.0f), r.included.assign(n, 0), r.chi2.assign(E, 0.0);
+    vsg_pose_se3d none_kf;
+    uint8_t none_included = 0;
+    float none_pos[3];
+    check(vsg_mappoints_global_bundle_adjustment(mp_, (int)n, slots.data(), obsOff.data(), obsKf.data(), obsIdx.data(), (int)K,
+                                                 keyFrames.data(), kfTcw.data(), kfFixed.data(), kfCam.data(),
+                                                 mvInvLevelSigma2.data(), (int)mvInvLevelSigma2.size(), nIterations,
+                                                 bRobust ? 1 : 0, loopKFIsOrigin ? 1 : 0, pbStopFlag,
+                                                 K ? r.kfTcw.data() : &none_kf, n ? r.worldPos.data() : none_pos,
+                                                 n ? r.included.data() : &none_included, E ? r.chi2.data() : nullptr, &r.res),
+          "vsg_mappoints_global_bundle_adjustment");
+    if (!r.res.ran) {  // no edge or the stop flag: only res and included were written, the outs are the inputs
       for (size_t k = 0; k < K; ++k)
         for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
       if (n)

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "vsg_global_ba.h"
 #include "vsg_local_ba.h"
 #include "vsg_observations.h"
 #include "vsg_pose_opt.h"
@@ -354,6 +355,38 @@ int lb_host_side(int capacity, int n_points, const int32_t *slots, const float *
   int n_erase = 0;
   for (size_t e = 0; e < E; e++) n_erase += erase[e] != 0;
   res->n_erase = n_erase;
+  return VSG_OK;
+}
+
+// globalba: the host build of csrc/vsg_global_ba.h on the positions vsg_mappoints_read returned; the caller follows with
+// vsg_mappoints_update when write_store
+int gb_host_side(int capacity, int n_points, const int32_t *slots, const float *pos, const int32_t *obs_off, const int32_t *obs_kf,
+                 const int32_t *obs_idx, int n_kf, const int32_t *kf_off, const float *kx, const float *ky, const int32_t *oct,
+                 const float *ur, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed, const vsg_ba_camera *kf_cam,
+                 const float *inv_level_sigma2, int nlevels, int iterations, int robust, vsg_pose_se3d *kf_Tcw_out, float *pos_out,
+                 uint8_t *included, double *chi2, vsg_global_ba_result *res) {
+  namespace gb = vsg::gba;
+  std::vector<int32_t> kf_n((size_t)n_kf), nleft((size_t)n_kf, -1);
+  for (int k = 0; k < n_kf; k++) kf_n[(size_t)k] = kf_off[k + 1] - kf_off[k];
+  static thread_local gb::HostRun run;  // its vectors keep their capacity from call to call, as the library's arenas do
+  int ran = 0;
+  const int rc = gb::check_and_build(
+      n_points, slots, obs_off, obs_kf, obs_idx, n_kf, kf_n.data(), nleft.data(), [&](int k, int i) { return (int)oct[kf_off[k] + i]; },
+      kf_fixed, capacity, nlevels, iterations, robust, 1, pos_out, nullptr, &run.T, &ran);
+  if (rc != VSG_OK || !ran) return rc != VSG_OK ? rc : -100;
+  gb::fill_included(included, n_points, obs_off);
+  const size_t E = (size_t)run.T.E;
+  std::vector<float> ex(E), ey(E), eur(E);
+  std::vector<int32_t> eoct(E);
+  for (size_t e = 0; e < E; e++) {
+    const size_t f = (size_t)kf_off[run.T.e_kf[e]] + (size_t)run.T.e_idx[e];
+    ex[e] = kx[f], ey[e] = ky[f], eoct[e] = oct[f], eur[e] = ur[f];
+  }
+  run.kernel.robust = robust;
+  run.setup(pos, ex.data(), ey.data(), eur.data(), eoct.data(), kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2, nlevels, iterations);
+  run.run(nullptr);
+  run.outputs(kf_Tcw, pos, kf_Tcw_out, pos_out, chi2);
+  gb::fill_result(res, run.T, &run.S);
   return VSG_OK;
 }
 }  // extern "C"

@@ -71,12 +71,23 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
             B  = vsg_mappoints_local_bundle_adjustment;  A2 / B2 = both again;  B_S1 / B_S2 / B_S10 = B with 1 / 2 / 10 trial
                  slots enqueued ahead per iteration instead of the library's.  Every call asserts all seven equal bit for bit
 
+  globalba  the visual part of Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt: "init" = 1 fixed + 1 optimised
+            keyframe, 300 mono points, robust, 20 iterations (CreateInitialMapMonocular); "50" / "100" / "200" / "500" = that many
+            keyframes, one of them fixed, 15 points per keyframe of 8 observations (120 observed features per keyframe), half
+            stereo, not robust, 10 iterations, write_store = 1 (RunGlobalBundleAdjustment).  Calls per size: 200 / 50 / 20 / 5 / 3
+            (the host side takes seconds per call at the last two)
+            A  = vsg_mappoints_read + the host build of csrc/vsg_global_ba.h on one thread (NOT g2o: the header's own
+                 arithmetic and its DENSE reduced solve) + vsg_mappoints_update
+            B  = vsg_mappoints_global_bundle_adjustment;  A2 / B2 = both again.  Every call asserts all four equal bit for bit
+            `child globalba <calls> <size,size>` runs the listed sizes alone; `globalba trace [size]` runs the 100-keyframe problem
+            (or the given size) through the new call and, up to 129 keyframes, through the local call, for rocprofv3 --kernel-trace --stats with VSG_NO_OVERLAP=1
+
   track / track_local   Tracking's two per-frame steps as chain calls (vsg_frame_track_with_motion_model,
             vsg_frame_track_local_map), 1000 / 2000 / 4000 points, against the caller-side path on the SAME library: the two
             existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
             carries them.  Both write into profiles/track_chain_latency.json, one key each
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|globalba|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -106,7 +117,7 @@ def host_side(orb):
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
            csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
-           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h"]
+           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_global_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-pthread", "-I", str(csrc), "-o",
                                str(so), str(src[0])])
@@ -132,6 +143,9 @@ def host_side(orb):
                                C.c_int, _u8p, C.POINTER(C.c_double), C.c_void_p]
     H.lb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
                                C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
+                               C.POINTER(C.c_double), C.c_void_p]
+    H.gb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
+                               C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
                                C.POINTER(C.c_double), C.c_void_p]
     H.ml_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, _i32p,
                                _u8p, C.c_void_p]
@@ -894,8 +908,11 @@ class LocalBA(Case):
     def __init__(self, orb, fr, size):
         import lba_scenes as ls
         nk, npts = (int(v) for v in size.split(":"))
-        self.orb, self.nk, self.npts = orb, nk, npts
-        s = self.s = ls.make(7300 + nk, nk, nk, npts, 6, "mixed", outliers=0.05)
+        self.setup(orb, ls.make(7300 + nk, nk, nk, npts, 6, "mixed", outliers=0.05), nk, npts)
+
+    def setup(self, orb, s, nk, npts):
+        """The scene's keyframes padded and uploaded, the store, and the arrays both sides take."""
+        self.orb, self.nk, self.npts, self.s = orb, nk, npts, s
         c = np.ascontiguousarray
         rng = np.random.default_rng(nk)
         self.kf, feats = [], []
@@ -975,6 +992,73 @@ class LocalBA(Case):
                              "Eigen here).  Which way that flatters it: g2o's sparse reduced solve is cheaper than this dense "
                              "one for many keyframes, its virtual calls and allocations are dearer; "
                              "B = vsg_mappoints_local_bundle_adjustment (B_S1 / B_S2 / B_S10: 1 / 2 / 10 trial slots enqueued ahead)"}
+
+
+class GlobalBA(LocalBA):
+    """The visual part of Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt on resident keyframes and map points:
+    scenes of tests/lba_scenes.py with ONE fixed keyframe, keyframes padded to 1000 features.  "init": 1 + 1 keyframes, 300
+    mono points, robust, 20 iterations.  "<K>": K keyframes, 15 K points of 8 observations, half stereo, 5 % outliers, not
+    robust, 10 iterations.  write_store = 1 in both, so that the host side ends with vsg_mappoints_update."""
+    SIZES = ("init", "50", "200", "500")
+    TH, DEST = 0.0, "global_ba_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+    CALLS = {"init": (20, 200), "50": (5, 50), "100": (3, 20), "200": (1, 5), "500": (0, 3)}  # size -> (warm-up, timed calls)
+
+    def __init__(self, orb, fr, size):
+        import lba_scenes as ls
+        if size == "init":
+            nk, npts, self.robust, self.iterations = 2, 300, 1, 20
+            scene = ls.make(7400, 1, 1, npts, 2, "mono")
+        else:
+            nk, self.robust, self.iterations = int(size), 0, 10
+            npts = 15 * nk
+            scene = ls.make(7400 + nk, nk - 1, 1, npts, 8, "mixed", outliers=0.05)
+        self.setup(orb, scene, nk, npts)
+        self.included, self.res = np.zeros(npts, np.uint8), orb.GlobalBaResult()
+
+    def reset(self):
+        self.mp.update(self.all, world_pos=self.pos0)
+        self.kf_out[:], self.pos_out[:], self.included[:], self.chi2[:] = 0, 0, 9, -1.0
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        f64p = C.POINTER(C.c_double)
+        if name.startswith("B"):
+            return L.vsg_mappoints_global_bundle_adjustment(
+                self.mp.handle, self.npts, p(self.slots, _i32p), p(self.off, _i32p), p(self.okf, _i32p), p(self.oidx, _i32p), self.K,
+                self.handles, C.cast(self.Tcw.ctypes.data, C.POINTER(self.orb.PoseSE3)), p(self.fixed, _u8p),
+                C.cast(self.cam.ctypes.data, C.POINTER(self.orb.BaCamera)), p(self.sig, _f32p), 8, self.iterations, self.robust, 1,
+                None, C.cast(self.kf_out.ctypes.data, C.POINTER(self.orb.PoseSE3d)), p(self.pos_out, _f32p), p(self.included, _u8p),
+                p(self.chi2, f64p), C.byref(self.res))
+        rc = L.vsg_mappoints_read(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), None, None, None, None, None)
+        if rc != 0:
+            return rc
+        rc = H.gb_host_side(self.cap, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), p(self.off, _i32p), p(self.okf, _i32p),
+                            p(self.oidx, _i32p), self.K, p(self.kf_off, _i32p), p(self.kx, _f32p), p(self.ky, _f32p),
+                            p(self.oct, _i32p), p(self.ur, _f32p), self.Tcw.ctypes.data, p(self.fixed, _u8p), self.cam.ctypes.data,
+                            p(self.sig, _f32p), 8, self.iterations, self.robust, self.kf_out.ctypes.data, p(self.pos_out, _f32p),
+                            p(self.included, _u8p), p(self.chi2, f64p), C.addressof(self.res))
+        if rc != 0:
+            return rc
+        return L.vsg_mappoints_update(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.pos_out, _f32p), None, None, None,
+                                      None, None)
+
+    def result(self, name, r):
+        after = self.mp.read(self.slots)["world_pos"]
+        return (r, self.kf_out.view(np.uint64).copy(), self.pos_out.copy(), after.reshape(-1).copy(), self.included.copy(),
+                self.chi2.view(np.uint64).copy(), np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.GlobalBaResult.from_buffer_copy(last["B"][6].tobytes())
+        return {"keyframes": self.K, "optimised_keyframes": int(r.n_opt_kf), "fixed_keyframes": int(r.n_fixed_kf),
+                "reduced_rows": 6 * int(r.n_opt_kf), "points": self.npts, "edges": int(r.n_edges), "mono": int(r.n_mono),
+                "stereo": int(r.n_stereo), "robust": self.robust, "iterations": self.iterations, "features_per_keyframe": NFEAT,
+                "iterations_run": int(r.iterations_run), "trials_run": int(r.trials_run), "stop_reason": int(r.stop_reason),
+                "every_call_equals_the_host_build": True,
+                "host_side": "A = vsg_mappoints_read + the host build of csrc/vsg_global_ba.h on one thread "
+                             "(tools/resident_points_cpu.cpp) + vsg_mappoints_update; it is THIS header's build and NOT g2o (no "
+                             "Eigen here).  Its DENSE reduced solve is dearer than g2o's sparse one for many keyframes, so the "
+                             "larger sizes flatter the device; B = vsg_mappoints_global_bundle_adjustment"}
 
 
 class Chain:
@@ -1114,19 +1198,20 @@ class TrackLocal(Chain, Local):
 
 
 CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3, "mlpnp": Mlpnp,
-         "sim3opt": Sim3Opt, "localba": LocalBA, "twoview": TwoView}
+         "sim3opt": Sim3Opt, "localba": LocalBA, "globalba": GlobalBA, "twoview": TwoView}
 
 
-def child(case, calls):
+def child(case, calls, sizes=None):
     import frustum_reference as fr
     from visual_sgraphs_amd import orb
     L, H, K = orb.load_library(), host_side(orb), CASES[case]
     out = {"calls": calls, "features": NFEAT, "th": K.TH, "sizes": {}}
-    for n in K.SIZES:
+    for n in sizes or K.SIZES:
         c = K(orb, fr, n)
         t = {k: [] for k in K.VARIANTS}
         last = {}
-        for k in range(calls + 20):
+        warm, ncalls = getattr(K, "CALLS", {}).get(n, (20, calls))  # a case whose sizes differ by orders of magnitude says how many
+        for k in range(ncalls + warm):
             P = c.pose_at(k)
             for name in K.VARIANTS:
                 c.reset()
@@ -1135,12 +1220,12 @@ def child(case, calls):
                 dt = (time.perf_counter() - t0) * 1e6
                 last[name] = c.result(name, r)
                 assert last[name][0] >= 0, (name, last[name][0])
-                if k >= 20:
+                if k >= warm:
                     t[name].append(dt)
             for name in K.VARIANTS[1:]:  # the variants compute the same thing
                 assert all(np.array_equal(a, b) for a, b in zip(last["A"], last[name])), name
         res = {k: stats(v) for k, v in t.items()}
-        res.update(c.facts(last))
+        res.update(c.facts(last), timed_calls=ncalls, warm_up_calls=warm)
         res["a_vs_a_median_gap_us"] = round(abs(res["A"]["median_us"] - res["A2"]["median_us"]), 1)
         if "B2" in t:  # the resident call timed twice: its own repeat gap
             res["b_vs_b_median_gap_us"] = round(abs(res["B"]["median_us"] - res["B2"]["median_us"]), 1)
@@ -1154,7 +1239,7 @@ def child(case, calls):
     print(json.dumps(out))
 
 
-def trace(case="local"):
+def trace(case="local", size=None):
     import frustum_reference as fr
     from visual_sgraphs_amd import orb
     if case == "refresh":
@@ -1171,6 +1256,21 @@ def trace(case="local"):
             assert c.run("B", L, None, None) == 0
         print({"size": "20:3000", "calls": 5, "iterations_run": int(c.res.iterations_run), "trials_run": int(c.res.trials_run)})
         return
+    if case == "globalba":  # a loop-closing problem through the new call and, where it accepts it, through the local call
+        L, c = orb.load_library(), GlobalBA(orb, fr, size or "100")
+        for k in range(3):
+            c.reset()
+            assert c.run("B", L, None, None) == 0
+        out = {"size": size or "100", "calls_each": 3,
+               "global (iterations, trials, optimised keyframes)": (int(c.res.iterations_run), int(c.res.trials_run), int(c.res.n_opt_kf))}
+        if int(c.res.n_opt_kf) <= 128:  # the local call's cap
+            c.erase, c.res = np.zeros(len(c.chi2), np.uint8), orb.LocalBaResult()
+            for k in range(3):
+                LocalBA.reset(c)
+                assert LocalBA.run(c, "B", L, None, None) == 0
+            out["local (iterations, trials)"] = (int(c.res.iterations_run), int(c.res.trials_run))
+        print(out)
+        return
     L, c = orb.load_library(), Local(orb, fr, 4000)
     for k in range(10):
         c.reset()
@@ -1180,9 +1280,9 @@ def trace(case="local"):
 
 def main(argv):
     if argv[0] == "child":
-        return child(argv[1], int(argv[2]) if len(argv) > 2 else 200)
-    if argv[1:] == ["trace"]:
-        return trace(argv[0])
+        return child(argv[1], int(argv[2]) if len(argv) > 2 else 200, argv[3].split(",") if len(argv) > 3 else None)
+    if argv[1:2] == ["trace"]:
+        return trace(argv[0], argv[2] if len(argv) > 2 else None)
     calls = int(argv[1]) if len(argv) > 1 else 200
     dest = Path(argv[2]) if len(argv) > 2 else ROOT / "profiles" / CASES[argv[0]].DEST
     r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "child", argv[0], str(calls)], capture_output=True,

@@ -13,7 +13,8 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libvsg_orb.so"
 SOURCES = ["vsg_kernels.hip", "vsg_orb.hip", "vsg_match.hip", "vsg_bow.hip", "vsg_frame.hip", "vsg_window.hip", "vsg_ctx.hip",
            "vsg_shard.hip", "vsg_kfdb.hip", "vsg_mappoints.hip", "vsg_pose.hip", "vsg_triangulate.hip",
-           "vsg_sim3.hip", "vsg_sim3_opt.hip", "vsg_track.hip", "vsg_local_ba.hip", "vsg_two_view.hip", "vsg_mlpnp.hip"]
+           "vsg_sim3.hip", "vsg_sim3_opt.hip", "vsg_track.hip", "vsg_local_ba.hip", "vsg_two_view.hip", "vsg_mlpnp.hip",
+           "vsg_global_ba.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wno-unused-value",
          # MFMA results in VGPRs (the matcher's epilogue is VALU): no v_accvgpr_read per accumulator register
@@ -45,7 +46,8 @@ def needs_build():
     if not LIB.exists():
         return True
     deps = list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + \
-        [PKG.parent / "include" / n for n in ("vsg_orb.h", "vsg_orb_debug.h", "vsg_orb_debug_epipolar.h", "vsg_orb_debug_local_ba.h")]
+        [PKG.parent / "include" / n for n in ("vsg_orb.h", "vsg_orb_debug.h", "vsg_orb_debug_epipolar.h", "vsg_orb_debug_local_ba.h",
+                                                "vsg_orb_debug_global_ba.h")]
     return any(d.stat().st_mtime > LIB.stat().st_mtime for d in deps)
 
 
@@ -68,7 +70,8 @@ def build(force=False, verbose=False):
     headers = list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + [PKG.parent / "include" / "vsg_orb.h",
                                                                     PKG.parent / "include" / "vsg_orb_debug.h",
                                                                     PKG.parent / "include" / "vsg_orb_debug_epipolar.h",
-                                                                    PKG.parent / "include" / "vsg_orb_debug_local_ba.h", Path(__file__)]
+                                                                    PKG.parent / "include" / "vsg_orb_debug_local_ba.h",
+                                                                    PKG.parent / "include" / "vsg_orb_debug_global_ba.h", Path(__file__)]
     hdr_time = max(h.stat().st_mtime for h in headers)
 
     def compile_one(src):

@@ -150,22 +150,33 @@ VSG_HD pose::Edge edge_of(const Prob &p, int e, const double *X) {
   return E;
 }
 
+// The robust kernel of the local call: Huber with the float deltas of :1847-1848 on every edge.  edge_cost and
+// linearise_edge take the kernel as a type so that vsg_global_ba.h can pass one that is optional (bRobust) and has its own
+// deltas; with this default they compile to the operations they always had.
+struct HuberLocal {
+  VSG_HD void operator()(double chi2, bool stereo, double *rho0, double *rho1) const {
+    pose::huber(chi2, pose::huber_delta(stereo), rho0, rho1);
+  }
+};
+
 // computeError + the robust cost of edge e at estimate buffer `buf`; stores chi2[e]
-VSG_HD double edge_cost(const Prob &p, int e, int buf, double *err, double *Xc, double *rho1) {
+template <class Kernel = HuberLocal>
+VSG_HD double edge_cost(const Prob &p, int e, int buf, double *err, double *Xc, double *rho1, const Kernel &kernel = Kernel()) {
   const bool stereo = (p.flag[e] & kStereo) != 0;
   const pose::Edge E = edge_of(p, e, p.X[buf]);
   const int kf = p.e_kf[e];
   const double chi2 = pose::edge_error(p.cam[kf], p.est[buf][kf], E, stereo, err, Xc);
   p.chi2[e] = chi2;
   double rho0;
-  pose::huber(chi2, pose::huber_delta(stereo), &rho0, rho1);
+  kernel(chi2, stereo, &rho0, rho1);
   return rho0;
 }
 
 // PHASE linearise, one edge: linearizeOplus + constructQuadraticForm into the edge's own blocks.  Returns rho0.
-VSG_HD double linearise_edge(const Prob &p, int e, int buf) {
+template <class Kernel = HuberLocal>
+VSG_HD double linearise_edge(const Prob &p, int e, int buf, const Kernel &kernel = Kernel()) {
   double err[3], Xc[3], rho1;
-  const double rho0 = edge_cost(p, e, buf, err, Xc, &rho1);
+  const double rho0 = edge_cost(p, e, buf, err, Xc, &rho1, kernel);
   const bool stereo = (p.flag[e] & kStereo) != 0;
   const int kf = p.e_kf[e], rows = stereo ? 3 : 2;
   const size_t E = (size_t)p.E;
@@ -440,12 +451,14 @@ struct Topology {
 
 // Everything vsg_mappoints_local_bundle_adjustment checks that needs no device.  kf_n[k] = features of keyframe k whose
 // octave the host can see, octave(k, idx) = that octave, nleft[k] = Nleft.  *ran = 0: VSG_OK and the call returns before
-// optimize (:1734, :2277, :2283).
+// optimize (:1734, :2277, :2283).  max_opt_kf / need_fixed: the local call's cap and its return without a fixed keyframe
+// (:1734); vsg_global_ba.h passes its own cap and no such return.
 template <class OctaveOf>
 inline int check_and_build(int n_points, const int32_t *slots, const int32_t *obs_off, const int32_t *obs_kf,
                            const int32_t *obs_idx, int n_kf, const int32_t *kf_n, const int32_t *nleft, OctaveOf octave,
                            const uint8_t *kf_fixed, int capacity, int nlevels, int iterations,
-                           const volatile uint8_t *stop_flag, Topology *T, int *ran) {
+                           const volatile uint8_t *stop_flag, Topology *T, int *ran, int max_opt_kf = kMaxOptKf,
+                           bool need_fixed = true) {
   *ran = 0;
   if (n_points < 0 || n_kf < 0 || nlevels < 1 || nlevels > 16 || iterations < 1 || iterations > 100) return VSG_ERR_INVALID;
   if (n_points == 0) return VSG_OK;
@@ -473,14 +486,14 @@ inline int check_and_build(int n_points, const int32_t *slots, const int32_t *ob
     if (nleft[k] != -1) return VSG_ERR_UNSUPPORTED;
   T->K = n_kf, T->P = n_points, T->E = E, T->n_fixed = T->n_opt = 0;
   for (int k = 0; k < n_kf; k++) (kf_fixed[k] ? T->n_fixed : T->n_opt)++;
-  if (T->n_fixed == 0 || E == 0) return VSG_OK;  // :1734, :2277
+  if ((need_fixed && T->n_fixed == 0) || E == 0) return VSG_OK;  // :1734, :2277
   std::vector<int32_t> cnt((size_t)n_kf, 0);
   for (int e = 0; e < E; e++) cnt[(size_t)obs_kf[e]]++;
   T->opt_of.assign((size_t)n_kf, -1), T->opt_kf.clear();
   for (int k = 0; k < n_kf; k++)
     if (!kf_fixed[k] && cnt[(size_t)k] > 0) T->opt_of[(size_t)k] = (int32_t)T->opt_kf.size(), T->opt_kf.push_back(k);
   T->Ko = (int)T->opt_kf.size();
-  if (T->Ko == 0 || T->Ko > kMaxOptKf) return VSG_ERR_UNSUPPORTED;
+  if (T->Ko == 0 || T->Ko > max_opt_kf) return VSG_ERR_UNSUPPORTED;
   if (stop_flag && *stop_flag) return VSG_OK;  // :2283
   const size_t Es = (size_t)E;
   T->p_off.assign(obs_off, obs_off + n_points + 1), T->e_kf.assign(obs_kf, obs_kf + E), T->e_idx.assign(obs_idx, obs_idx + E), T->e_pt.resize(Es), T->e_opt.resize(Es);

@@ -99,6 +99,10 @@ EXPORTS = [
     # vsg_debug_local_ba_trial_slots of include/vsg_orb_debug_local_ba.h, is bound below but is no part of the two headers
     # this list mirrors)
     "vsg_mappoints_local_bundle_adjustment",
+    # the visual part of Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt on resident keyframes and resident map
+    # points (its test hooks, vsg_debug_ba_reduced_solve and vsg_debug_ba_solver_geometry of
+    # include/vsg_orb_debug_global_ba.h, are bound below but are no part of the two headers this list mirrors)
+    "vsg_mappoints_global_bundle_adjustment",
     # TwoViewReconstruction::Reconstruct (the monocular initialisation) on two resident frames or on caller arrays, the
     # reference's default parameters and the host-side draw of the minimal sets
     "vsg_frame_two_view_reconstruct", "vsg_two_view_reconstruct", "vsg_two_view_default_params", "vsg_two_view_draw_sets",
@@ -237,6 +241,15 @@ LOCAL_BA_STOP_REASONS = ("iterations_done", "terminate", "n_bad", "stop_flag")
 class LocalBaResult(C.Structure):
     """include/vsg_orb.h vsg_local_ba_result."""
     _fields_ = [(k, C.c_int32) for k in LOCAL_BA_RESULT_INTS] + [(k, C.c_double) for k in LOCAL_BA_RESULT_DOUBLES]
+
+
+GLOBAL_BA_RESULT_INTS = tuple(k for k in LOCAL_BA_RESULT_INTS if k != "n_erase")
+GLOBAL_BA_RESULT_DOUBLES = LOCAL_BA_RESULT_DOUBLES
+
+
+class GlobalBaResult(C.Structure):
+    """include/vsg_orb.h vsg_global_ba_result: the local call's counters without n_erase."""
+    _fields_ = [(k, C.c_int32) for k in GLOBAL_BA_RESULT_INTS] + [(k, C.c_double) for k in GLOBAL_BA_RESULT_DOUBLES]
 
 
 class TwoViewParams(C.Structure):
@@ -541,6 +554,11 @@ def load_library():
                                                         _u8p, C.POINTER(BaCamera), _f32p, ci, ci, _u8p, C.POINTER(PoseSE3d),
                                                         _f32p, _u8p, _f64p, C.POINTER(LocalBaResult)]
     L.vsg_debug_local_ba_trial_slots.argtypes = [ci]
+    L.vsg_mappoints_global_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
+                                                         _u8p, C.POINTER(BaCamera), _f32p, ci, ci, ci, ci, _u8p,
+                                                         C.POINTER(PoseSE3d), _f32p, _u8p, _f64p, C.POINTER(GlobalBaResult)]
+    L.vsg_debug_ba_reduced_solve.argtypes = [ci, _f64p, _f64p, _f64p, _i32p]
+    L.vsg_debug_ba_solver_geometry.argtypes = [_i32p, _i32p]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
     L.vsg_kfdb_destroy.argtypes = [vp]
     L.vsg_kfdb_destroy.restype = None
@@ -1369,6 +1387,48 @@ class MapPoints:
         got.update({k: float(getattr(res, k)) for k in LOCAL_BA_RESULT_DOUBLES})
         return got
 
+    def GlobalBundleAdjustment(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
+                               iterations=10, robust=False, write_store=False, stop_flag=None):
+        """The visual part of Optimizer::BundleAdjustment as GlobalBundleAdjustemnt calls it
+        (vsg_mappoints_global_bundle_adjustment).  The arguments are LocalBundleAdjustment's with `keyframes` = every
+        keyframe of the map in ascending mnId and kf_fixed[k] != 0 for the map's initial keyframe alone.  robust = bRobust
+        (Huber with sqrt(5.99) / sqrt(7.815)); iterations = nIterations (20 and robust at CreateInitialMapMonocular, 10 and
+        not robust at RunGlobalBundleAdjustment); write_store = the case nLoopKF == the origin keyframe: the positions are
+        written into the slots (follow with refresh(what=REFRESH_NORMAL)); otherwise the store is untouched and the
+        positions come back in world_pos alone (mPosGBA).  Returns dict(kf_Tcw (K, 7) float64, world_pos (n, 3) float32,
+        included (n) uint8 -- 0 for a point with an empty list --, chi2 per observation, and the fields of
+        vsg_global_ba_result)."""
+        n, K = int(np.asarray(slots).size), len(keyframes)
+        sl, off, kf, idx = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx)
+        if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != np.asarray(obs_kf).size:
+            raise ValueError("observation arrays do not match the slot list")
+        nobs = int(off[n]) if n else 0
+        if int(np.asarray(obs_kf).size) < nobs:
+            raise ValueError("obs_off runs past the observation arrays")
+        T, fx, cam = _f32(kf_Tcw).reshape(-1), _u8(kf_fixed), _f32(kf_cam).reshape(-1)
+        if np.asarray(kf_Tcw).size != 7 * K or np.asarray(kf_fixed).size != K or np.asarray(kf_cam).size != 5 * K:
+            raise ValueError("kf_Tcw needs 7 floats, kf_fixed one byte and kf_cam 5 floats per keyframe")
+        sig = _f32(inv_level_sigma2)
+        handles = (C.c_void_p * max(K, 1))(*[f.handle for f in keyframes])
+        out = {"kf_Tcw": np.zeros((max(K, 1), 7), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
+               "included": np.zeros(max(n, 1), np.uint8), "chi2": np.zeros(max(nobs, 1), np.float64)}
+        res = GlobalBaResult()
+        flag = None if stop_flag is None else _p(stop_flag, _u8p)
+        _check(self._L.vsg_mappoints_global_bundle_adjustment(
+            self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
+            C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
+            int(np.asarray(inv_level_sigma2).size), int(iterations), int(bool(robust)), int(bool(write_store)), flag,
+            C.cast(_p(out["kf_Tcw"], C.POINTER(C.c_double)), C.POINTER(PoseSE3d)), _p(out["world_pos"], _f32p),
+            _p(out["included"], _u8p), _p(out["chi2"], C.POINTER(C.c_double)), C.byref(res)),
+            "vsg_mappoints_global_bundle_adjustment")
+        if not res.ran:  # only res and included were written: the outs are the inputs
+            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
+            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
+        got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "included": out["included"][:n], "chi2": out["chi2"][:nobs]}
+        got.update({k: int(getattr(res, k)) for k in GLOBAL_BA_RESULT_INTS})
+        got.update({k: float(getattr(res, k)) for k in GLOBAL_BA_RESULT_DOUBLES})
+        return got
+
     def Sim3Ransac(self, slots1, slots2, max_err1, max_err2, kf1, kf2, samples, min_inliers, fix_scale=False, other=None,
                    per_hypothesis=False):
         """Sim3Solver on resident map points (vsg_mappoints_sim3_ransac): correspondence i = slot slots1[i] of this store
@@ -1395,6 +1455,26 @@ class MapPoints:
         if per_hypothesis:
             out.update(hyp_inliers=hc[:nh], hyp_T12=hT[:nh])
         return out
+
+
+def debug_ba_solver_geometry():
+    """include/vsg_orb_debug_global_ba.h vsg_debug_ba_solver_geometry -> (columns per panel, rows per tile)."""
+    panel, tile = C.c_int32(0), C.c_int32(0)
+    _check(load_library().vsg_debug_ba_solver_geometry(C.byref(panel), C.byref(tile)), "vsg_debug_ba_solver_geometry")
+    return int(panel.value), int(tile.value)
+
+
+def debug_ba_reduced_solve(M, b):
+    """include/vsg_orb_debug_global_ba.h vsg_debug_ba_reduced_solve: the global call's reduced solve on the lower triangle
+    of M (n, n) float64 and b (n) on the current device -> (ok, x)."""
+    M, b = np.ascontiguousarray(M, np.float64), np.ascontiguousarray(b, np.float64)
+    n = int(b.size)
+    if M.shape != (n, n):
+        raise ValueError("M must be (n, n) for b of n")
+    x, ok = np.zeros(max(n, 1), np.float64), C.c_int32(-1)
+    dp = C.POINTER(C.c_double)
+    _check(load_library().vsg_debug_ba_reduced_solve(n, _p(M, dp), _p(b, dp), _p(x, dp), C.byref(ok)), "vsg_debug_ba_reduced_solve")
+    return int(ok.value), x[:n]
 
 
 def sim3_max_err(level_sigma2, octave):
