@@ -64,6 +64,40 @@ def make(seed, n=100, kind="general", outliers=0.3, noise=0.5, n_hyp=300, capaci
                 outlier=out, Rcw=Rcw, tcw=tcw, where=where, kind=kind)
 
 
+# (n, extra): correspondences around the 256-lane stride of k_mlpnp_points and k_mlpnp_select, among n + extra + 7 features
+LARGE = ((255, 40), (256, 300), (257, 100), (513, 200))
+
+
+def large_scene(n, extra, kind="general"):
+    """n correspondences interleaved with extra + 7 slot-less features, 5 hypotheses; (513, 200): 720 features, so that the
+    clearing loop over the features and the scatter through feat[] both take three trips of 256.  Hypotheses 2 and 4 are drawn
+    from true correspondences, so the returned pose has inliers at every index range.  The planar scene takes the viewpoint of
+    SEEDS[1]: from some viewpoints (seed 500 + 257 is one) the 9-column branch finds no pose even from true correspondences."""
+    s = make(500 + n if kind == "general" else SEEDS[1], n=n, kind=kind, n_hyp=5, extra=extra)
+    # the last correspondence (the only entry of the last trip at 257 and 513): noise-free at octave 7, so that every pose
+    # near the truth flags it
+    w = s["where"][-1]
+    Xc = s["Rcw"] @ s["world_pos"][s["slots"][w]].astype(np.float64) + s["tcw"]
+    s["kx"][w], s["ky"][w], s["octave"][w] = CAM[0] * Xc[0] / Xc[2] + CAM[2], CAM[1] * Xc[1] / Xc[2] + CAM[3], NLEVELS - 1
+    s["outlier"][-1] = False
+    s["sets"][[2, 4]] = good_sets(s, 2, n)
+    return s
+
+
+def winner_last(n_hyp, seed=31, n=100):
+    """(scene, sets [n_hyp x 6]): n_hyp - 1 different sets of outliers only, then one set of true correspondences."""
+    s = make(seed, n=n, n_hyp=1)
+    return s, np.concatenate([bad_sets(s, n_hyp - 1, seed), good_sets(s, 1, seed)])
+
+
+def winner_last_min_inliers(hyp_inliers):
+    """The min_inliers of winner_last from the host build's counts: the largest count of an outlier set (6 at the least, the
+    smallest the call takes), which only the last hypothesis is above."""
+    mi = max(6, int(np.max(hyp_inliers[:-1])))
+    assert hyp_inliers[-1] > mi
+    return mi
+
+
 def good_sets(s, count, seed=0):
     """`count` minimal sets drawn from the scene's true correspondences only."""
     rng = np.random.default_rng(seed)

@@ -63,6 +63,49 @@ def issue_scene(seed):
 SEEDS = (11, 12, 13, 14)
 
 
+LARGE_SIZES = (255, 256, 257, 513)  # around the 256-lane stride of k_sim3_points and k_sim3_select, and two strides + 1
+
+
+@functools.lru_cache(maxsize=None)
+def large_scene(n):
+    """n correspondences with 9 hypotheses: more than one workgroup of k_sim3_points, more than one trip of k_sim3_select.
+    Scale 1, so that the hypotheses of fix_scale have inliers too; triples 4 and 8 are drawn from true correspondences and the
+    last correspondence (the only entry of the last trip at 257 and 513) is a noise-free one of octave 7, which every
+    hypothesis near the truth flags: a flag is set in every trip."""
+    s = make(400 + n, n=n, n_hyp=9, scale=1.0)
+    tr, k1, k2 = s["truth"], s["kf1"], s["kf2"]
+    X2 = k2["Rcw"].astype(F64) @ s["Xw2"][-1].astype(F64) + k2["tcw"].astype(F64)
+    s["Xw1"][-1] = to_world(k1, (tr["s12"] * tr["R12"] @ X2 + tr["t12"])[None])[0]
+    s["oct1"][-1] = s["oct2"][-1] = 7
+    s["max_err1"], s["max_err2"] = sr.max_err(SIGMA2[s["oct1"]]), sr.max_err(SIGMA2[s["oct2"]])
+    s["outlier"][-1] = False
+    good = np.flatnonzero(~s["outlier"])
+    rng = np.random.default_rng(n)
+    s["samples"][4], s["samples"][8] = rng.choice(good, 3, replace=False), rng.choice(good, 3, replace=False)
+    return s
+
+
+def winner_last(n_hyp, seed=21):
+    """(scene, samples [n_hyp x 3]) at n = 60: n_hyp - 1 different triples that each hold a gross outlier, then one all-inlier
+    triple.  With min_inliers = the largest count among the former only the last triple can be above it."""
+    s = make(seed, n_hyp=1)
+    rng = np.random.default_rng(seed + 1000)
+    good, bad = np.flatnonzero(~s["outlier"]), np.flatnonzero(s["outlier"])
+    sm = np.zeros((n_hyp, 3), I32)
+    for k in range(n_hyp - 1):
+        sm[k] = [bad[k % len(bad)], *rng.choice(good, 2, replace=False)]
+        sm[k] = sm[k][rng.permutation(3)]
+    sm[-1] = good[:3]
+    return s, sm
+
+
+def winner_last_min_inliers(hyp_inliers):
+    """The min_inliers of winner_last from the host build's counts: the largest count of a triple with an outlier."""
+    mi = int(np.max(hyp_inliers[:-1]))
+    assert hyp_inliers[-1] > mi  # the all-inlier triple is the only one above it
+    return mi
+
+
 def identical_triple(s):
     """Correspondences 0..2 get the SAME camera coordinates on both sides (M symmetric, N block diagonal, the eigenvector
     exactly (1, 0, 0, 0)): hypothesis (0, 1, 2) has a zero imaginary part."""

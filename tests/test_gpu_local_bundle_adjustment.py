@@ -1,7 +1,8 @@
 """vsg_mappoints_local_bundle_adjustment on the GPU (the visual part of Optimizer::LocalBundleAdjustment on resident
 keyframes and resident map points) against the host build of the same header (tests/_localbacore) BIT FOR BIT -- return
 value, res, kf_Tcw_out, world_pos_out, erase and chi2 -- and against tests/lba_reference.py (the NumPy restatement) under
-the measured tolerance of tests/lba_scenes.py with all flags equal.  Every scene of lba_scenes.scenes(); no edge is excluded
+the measured tolerance of tests/lba_scenes.py with all flags equal.  Every scene of lba_scenes.scenes(), and those of
+lba_scenes.cap_scenes() (the reduced system at 96, 102 and 768 rows) under their own measured tolerance; no edge is excluded
 from any comparison."""
 import ctypes as C
 import subprocess
@@ -121,6 +122,26 @@ def test_device_equals_the_host_build_bit_for_bit(name, device_results, host_res
 def test_device_agrees_with_the_restatement(name, device_results):
     print(name, ls.deviations(ls.references()[name], device_results[name]))
     check_against_reference(name, device_results[name])
+
+
+@pytest.fixture(scope="module")
+def cap_devices():
+    return {name: Device(s) for name, s in ls.cap_scenes().items()}
+
+
+@pytest.mark.parametrize("name", ls.CAP_NAMES)
+def test_reduced_system_at_its_tile_and_at_its_cap(name, cap_devices):
+    """k_solve at 96 rows (whole tiles of lba::kSolveTile), 102 rows and 768 rows (6 * lba::kMaxOptKf: l, D and y full): bit
+    for bit the host build, and the restatement under the tolerance measured over these scenes."""
+    d = cap_devices[name]
+    got, want = d.call(), hc.run(d.s)
+    assert want["ret"] == 0 and want["ran"] == 1 and want["n_opt_kf"] * 6 == int(name[5:])
+    same_bits(got, want, name)
+    print(name, ls.deviations(ls.cap_references()[name], got))
+    check_against_reference(name, got, cap=True)
+    if name == "rows_768":
+        for slots in (1, 10):
+            same_bits(d.call(trial_slots=slots), want, "%s S=%d" % (name, slots))
 
 
 @pytest.mark.parametrize("name", ("special_vertices", "points_257", "kf_40"))

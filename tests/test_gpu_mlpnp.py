@@ -3,10 +3,11 @@ k_mlpnp_select of csrc/vsg_mlpnp.hip) against the HOST BUILD of the same header
 (tests/_mlpnpcore): res, inlier, hyp_inliers and hyp_T byte for byte (both sides canonicalise NaNs), with no exemptions -- the
 measured tolerance belongs to the CPU test of the host build against the restatement.  Shapes: the correspondences at the
 wave's stride, scattered among the features of a frame whose feature count is no multiple of 64 with negative slots in
-between and a store larger than the scene; n_hyp around the waves of a workgroup and past 300; a directed scene of groups of
-growing size, each consistent with a pose of its own, for every way the call can end and for resumed calls; the planar
-branch; degenerate sets, one of which gives a NaN pose; the optional outputs NULL; sentinels behind every output; every
-refusal a single device can show."""
+between and a store larger than the scene, and past the 256 lanes of a workgroup among up to 720 features; n_hyp around the
+waves of a workgroup, past 300 and at its cap of 1024; a directed scene of groups of growing size (284 correspondences, the
+last 28 in the second workgroup of k_mlpnp_points), each consistent with a pose of its own, for every way the call can end and
+for resumed calls; the planar branch; degenerate sets, one of which gives a NaN pose; the optional outputs NULL; sentinels
+behind every output; every refusal a single device can show."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -100,6 +101,42 @@ def test_wave_stride_over_the_correspondences(n):
     w = check(d, 6, 5, what="n %d" % n)
     assert w["res"]["n_correspondences"] == n
     check(d, n, 3, what="only a full count qualifies")
+    d.close()
+
+
+@pytest.mark.parametrize("n,extra", ms.LARGE)
+def test_more_than_one_workgroup_of_correspondences(n, extra):
+    """blockIdx.x >= 1 in k_mlpnp_points, the later trips of k_mlpnp_select's clearing loop over the features and of its
+    scatter through feat[e] with feat[e] != e."""
+    s = ms.large_scene(n, extra)
+    assert s["n_feat"] > n and (s["where"][256:] != np.arange(256, n)).all()
+    d = Device(s)
+    w = check(d, 6, 5, what="n %d of %d features" % (n, s["n_feat"]))
+    assert w["res"]["n_correspondences"] == n and w["res"]["found"]
+    assert w["inlier"][s["where"][256:]].any() or n <= 256  # flags set past the first trip: a dropped trip shows
+    check(d, n, 5, what="only a full count qualifies")
+    d.close()
+
+
+def test_planar_branch_past_a_workgroup():
+    s = ms.large_scene(257, 100, kind="plane0")
+    pts = hc.points(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2)
+    assert hc.hypotheses(pts, ms.CAM, s["sets"])["info"][:, 0].all()  # the 9-column branch, every hypothesis
+    d = Device(s)
+    w = check(d, 50, 5, what="planar, n 257")
+    assert w["res"]["found"] and w["inlier"][s["where"][256:]].any()
+    d.close()
+
+
+@pytest.mark.parametrize("first,n_iterations,max_its,want_hyp", ((0, 1024, 1, True), (1019, 5, 1024, False)))
+def test_hypotheses_at_the_cap_with_the_returned_one_last(first, n_iterations, max_its, want_hyp):
+    """n_hyp = mlpnp::kMaxHypotheses: s_counts full, the last sets, counts, hyp and hyp_T records read and written, and the
+    selection walks all 1024 counts (a first call, and a resumed one whose max_its reaches the end)."""
+    s, sets = ms.winner_last(1024)
+    mi = ms.winner_last_min_inliers(hc.ransac(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2, s["n"], 1024, 0, 0, sets)["hyp_inliers"])
+    d = Device(s)
+    w = check(d, mi, max_its, first, n_iterations, sets=sets, want_hyp=want_hyp, what="n_hyp 1024")
+    assert w["res"]["found"] and w["res"]["refined"] and w["res"]["best_hypothesis"] == 1023 and w["res"]["iterations"] == 1024
     d.close()
 
 

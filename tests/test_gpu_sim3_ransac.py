@@ -1,8 +1,9 @@
 """Sim3Solver on resident map points on the device (vsg_mappoints_sim3_ransac; k_sim3_points, k_sim3_hypotheses, k_sim3_select
 of csrc/vsg_sim3.hip) against the HOST BUILD of the same header (tests/_sim3core): res, inlier, hyp_inliers and hyp_T12 byte for
 byte (both sides canonicalise NaNs), with no exemptions -- the measured tolerance belongs to the CPU test of the host build
-against the restatement.  Shapes: n at the wave's stride over the correspondences, n_hyp around the waves of a workgroup, every
-way the selection can end, the degenerate triples, fix_scale, two stores, sentinels behind every output, and the refusals."""
+against the restatement.  Shapes: n at the wave's stride over the correspondences and past the 256 lanes of a workgroup, n_hyp
+around the waves of a workgroup and at its cap of 1024, every way the selection can end, the degenerate triples, fix_scale, two
+stores, sentinels behind every output, and the refusals."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -18,6 +19,7 @@ pytestmark = pytest.mark.gpu
 F32, I32, U8 = np.float32, np.int32, np.uint8
 INVALID = -6
 CAP1, CAP2, PAD = 640, 320, 64
+BIG1, BIG2 = 1500, 900  # the stores of the cases with more than 256 correspondences: 513 random slots each
 SRC = Path(__file__).resolve().parent.parent / "visual_sgraphs_amd" / "csrc" / "vsg_sim3.hip"
 WAVES = int(re.search(r"kSim3Waves = (\d+)", SRC.read_text()).group(1))
 
@@ -38,17 +40,29 @@ def stores():
         mp.close()
 
 
+@pytest.fixture(scope="module")
+def big_stores():
+    rng = np.random.default_rng(4)
+    fill = [rng.normal(size=(BIG1, 3)).astype(F32), rng.normal(size=(BIG2, 3)).astype(F32)]
+    mps = [orb.MapPoints(BIG1), orb.MapPoints(BIG2)]
+    for mp, f in zip(mps, fill):
+        mp.update(np.arange(len(f)), world_pos=f)
+    yield mps, fill
+    for mp in mps:
+        mp.close()
+
+
 def place(stores, s, seed=0, one_store=False):
     """The scene's points into random slots of the two stores (one_store: both sets into the first).  Returns mp1, mp2, slots1,
     slots2 and what both stores hold afterwards."""
     (mp1, mp2), fill = stores
     rng = np.random.default_rng(seed)
-    n = s["n"]
+    n, cap1, cap2 = s["n"], len(fill[0]), len(fill[1])
     if one_store:
-        perm = rng.permutation(CAP1)
+        perm = rng.permutation(cap1)
         sl1, sl2, mp2 = perm[:n].astype(I32), perm[n:2 * n].astype(I32), mp1
     else:
-        sl1, sl2 = rng.permutation(CAP1)[:n].astype(I32), rng.permutation(CAP2)[:n].astype(I32)
+        sl1, sl2 = rng.permutation(cap1)[:n].astype(I32), rng.permutation(cap2)[:n].astype(I32)
     if n:
         mp1.update(sl1, world_pos=s["Xw1"])
         mp2.update(sl2, world_pos=s["Xw2"])
@@ -106,6 +120,30 @@ def test_wave_stride_over_the_correspondences(stores, n):
     w = check(stores, s, min_inliers=n, what="never")  # every hypothesis counts every correspondence
     assert not w["res"]["converged"] and w["res"]["iterations"] == 2 * WAVES + 1
     check(stores, s, min_inliers=15, fix_scale=True)
+
+
+@pytest.mark.parametrize("fix_scale", (False, True))
+@pytest.mark.parametrize("n", ss.LARGE_SIZES)
+def test_more_than_one_workgroup_of_correspondences(big_stores, n, fix_scale):
+    """blockIdx.x >= 1 in k_sim3_points and the second and third trips of k_sim3_select's loop over the correspondences."""
+    s = ss.large_scene(n)
+    w = check(big_stores, s, min_inliers=n, fix_scale=fix_scale, what="never")  # every hypothesis counts every correspondence
+    assert not w["res"]["converged"] and w["res"]["iterations"] == 9
+    assert w["inlier"][256:].any() or n <= 256  # the flags past the first trip are not all zero: a dropped trip shows
+    check(big_stores, s, min_inliers=15, fix_scale=fix_scale)
+    (mp1, mp2), fill = big_stores
+    assert mp1.read(np.arange(BIG1))["world_pos"].tobytes() == fill[0].tobytes()
+    assert mp2.read(np.arange(BIG2))["world_pos"].tobytes() == fill[1].tobytes()
+
+
+@pytest.mark.parametrize("n_hyp", (1023, 1024))
+def test_hypotheses_at_the_cap_with_the_returned_one_last(stores, n_hyp):
+    """n_hyp = sim3::kMaxHypotheses: s_counts full, the last samples, counts and hyp_T12 records read and written."""
+    s, sm = ss.winner_last(n_hyp)
+    mi = ss.winner_last_min_inliers(hc.ransac(s, 0, False, sm)["hyp_inliers"])
+    w = check(stores, s, min_inliers=mi, samples=sm, what="n_hyp %d" % n_hyp)
+    assert w["res"]["converged"] and w["res"]["best_hypothesis"] == n_hyp - 1 and w["res"]["iterations"] == n_hyp
+    check(stores, s, min_inliers=mi, samples=sm, want_hyp=False, what="n_hyp %d, optional outs NULL" % n_hyp)
 
 
 def test_three_correspondences(stores):

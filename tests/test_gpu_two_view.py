@@ -2,8 +2,9 @@
 k_tv_hypotheses, k_tv_select, k_tv_check_rt of csrc/vsg_two_view.hip) against the HOST BUILD of the same header
 (tests/_twoviewcore): the result, triangulated, x3d, both inlier vectors and every score byte for byte (both sides canonicalise
 NaNs), with no exemptions -- the measured tolerance belongs to the CPU test of the host build against the restatement.  Shapes:
-the number of matches at the wave's stride, n_iter around the waves of a workgroup, the index rule min(50, size - 1) at its
-edge, every reason the routine can end with, both models, both forms, sentinels behind every output, and the refusals."""
+the number of matches at the wave's stride and around the 1024-entry LDS tile of the rank count (a rank holder and a tie past the
+first tile), n_iter around the waves of a workgroup and at its cap of 1024, the index rule min(50, size - 1) at its edge, every
+reason the routine can end with, both models, both forms, sentinels behind every output, and the refusals."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -13,6 +14,7 @@ import pytest
 
 import two_view_hostcore as hc
 import two_view_scenes as ts
+from test_two_view_reference import tile_cases
 from visual_sgraphs_amd import orb
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +125,45 @@ def test_index_rule_at_its_edge(frames, n):
     s = ts.make(300 + n, n=n, outliers=0.0, noise=0.0, n_iter=16)
     r = check(frames, s, what="n=%d" % n)
     assert r["ok"] == 1 and r["model"] == 1 and max(r["n_good"]) == n
+
+
+@pytest.mark.parametrize("n", ts.TILE_SIZES)
+def test_match_counts_around_the_tile_of_the_rank_count(frames, n):
+    """k_tv_check_rt past its first LDS tile: a partial last tile, whole tiles, one match in the last tile, three tiles."""
+    r = check(frames, tile_cases()["matches_%d" % n], what="n=%d" % n)
+    assert r["ok"] == 1 and r["model"] == 1 and max(r["n_good"]) > 0.8 * n
+
+
+def test_rank_holder_past_the_first_tile(frames):
+    """The candidate trips reach base >= 1024 (tests/test_two_view_reference.py asserts where the rank holder lies)."""
+    r = check(frames, tile_cases()["rank_holder_late"])
+    assert r["ok"] == 1 and max(r["n_good"]) == 1500
+
+
+def test_tie_across_the_tile_boundary(frames):
+    """Two matches of one cosine, the rank-50 value, at the compacted indices 1023 and 1024: the last entry of the first tile
+    and the first of the second."""
+    r = check(frames, tile_cases()["tie_across_the_tile"])
+    assert r["ok"] == 1
+
+
+def test_iterations_at_the_cap_with_the_winner_last(frames):
+    """n_iter = two_view::kMaxIterations: s_score full, the last records of score and models read."""
+    s = tile_cases()["winner_last"]
+    r = check(frames, s)
+    assert r["best_it_f"] == 1023 and len(s["sets"]) == 1024
+    check(frames, s, optional=False)
+
+
+def test_host_array_form_past_the_tile(frames):
+    s = tile_cases()["matches_1025"]
+    upload(frames, s)
+    rc1, b1 = raw_call(frames, s, hc.params_blob(), s["sets"], resident=True)
+    rc2, b2 = raw_call(frames, s, hc.params_blob(), s["sets"], resident=False)
+    assert rc1 == 0 and rc2 == 0
+    for k in b1:
+        assert b1[k].tobytes() == b2[k].tobytes(), k
+    check(frames, s, resident=False)
 
 
 def test_f_path_success_and_the_optional_outputs_null(frames):

@@ -11,9 +11,11 @@ NAMES = list(ls.scenes())
 INVALID, UNSUPPORTED = -6, -3
 
 
-def check_against_reference(name, got):
-    """got: a result in lba_hostcore.result's form (the host build's or the device's)."""
-    s, ref = ls.scenes()[name], ls.references()[name]
+def check_against_reference(name, got, cap=False):
+    """got: a result in lba_hostcore.result's form (the host build's or the device's).  cap: a scene of cap_scenes(), under
+    the tolerance measured over those."""
+    s, ref = (ls.cap_scenes()[name], ls.cap_references()[name]) if cap else (ls.scenes()[name], ls.references()[name])
+    tol = ls.TOL_CAP if cap else ls.TOL
     assert got["ret"] == 0 and got["ran"] == 1
     for k in ("n_opt_kf", "n_fixed_kf", "n_points", "n_edges", "n_mono", "n_stereo", "n_erase", "iterations_run", "trials_run",
               "stop_reason"):
@@ -21,9 +23,9 @@ def check_against_reference(name, got):
     assert (got["erase"] == ref["erase"]).all()
     dev = ls.deviations(ref, got)
     for k, v in dev.items():
-        assert v <= ls.TOL[k], (k, v)
+        assert v <= tol[k], (k, v)
     for k in ("lambda", "chi2_initial", "chi2_final"):
-        assert abs(got[k] - ref[k]) <= ls.TOL["chi2_rel"] * max(abs(ref[k]), 1e-6), k
+        assert abs(got[k] - ref[k]) <= tol["chi2_rel"] * max(abs(ref[k]), 1e-6), k
     # the store: the listed vertices' positions are the outs, everything else keeps its bytes
     vertex = np.diff(s["obs_off"]) > 0
     expect = s["store_pos"].copy()
@@ -34,6 +36,14 @@ def check_against_reference(name, got):
 @pytest.mark.parametrize("name", NAMES)
 def test_scene(name):
     check_against_reference(name, hc.run(ls.scenes()[name]))
+
+
+@pytest.mark.parametrize("name", list(ls.CAP_NAMES))
+def test_cap_scene(name):
+    """The reduced system at whole tiles, one keyframe past them and at its cap of 768 rows."""
+    got = hc.run(ls.cap_scenes()[name])
+    print(name, ls.deviations(ls.cap_references()[name], got))
+    check_against_reference(name, got, cap=True)
 
 
 def test_stale_rule_decides():

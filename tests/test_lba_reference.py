@@ -42,6 +42,44 @@ def test_committed_spread_bounds_the_measured_one():
         assert ls.TOL[k] == 64 * ls.SPREAD[k]
 
 
+@pytest.mark.parametrize("name", ls.CAP_NAMES)
+def test_cap_fixture_condition(name):
+    """test_fixture_condition on the scenes of the reduced system at its tile and at its cap."""
+    ref = ls.cap_references()[name]
+    assert ref["ran"] == 1
+    assert _margin(ref) > 1e-3
+    for p in ls.cap_permuted_references()[name]:
+        assert _margin(p) > 1e-3
+        assert (p["erase"] == ref["erase"]).all()
+        assert (p["depth_positive"] == ref["depth_positive"]).all()
+        for k in ("iterations_run", "trials_run", "stop_reason", "n_mono", "n_stereo"):
+            assert p[k] == ref[k], k
+        assert [[t[1:] for t in it] for it in p["trace"]] == [[t[1:] for t in it] for it in ref["trace"]]
+
+
+def test_committed_cap_spread_bounds_the_measured_one():
+    """lba_scenes.SPREAD_CAP against a fresh measurement over cap_scenes() alone, by the rule of
+    test_committed_spread_bounds_the_measured_one."""
+    sp = ls.measure(cap=True)
+    floor = dict(q=2.0 ** -52, t=2.0 ** -52, pos_rel=2.0 ** -23, chi2_rel=2.0 ** -52)
+    for k, v in sp.items():
+        m = max(v, floor[k])
+        assert m <= 4 * ls.SPREAD_CAP[k] and ls.SPREAD_CAP[k] <= 4 * m, (k, v, ls.SPREAD_CAP[k])
+        assert ls.TOL_CAP[k] == 64 * ls.SPREAD_CAP[k]
+
+
+def test_cap_scene_sizes():
+    """96 rows are three whole tiles of lba::kSolveTile, 102 are six rows more, 768 are the cap; every optimised keyframe has
+    edges and every point four observations; and the scenes are not among those SPREAD is measured over."""
+    assert list(ls.cap_scenes()) == ["rows_96", "rows_102", "rows_768"] and not set(ls.cap_scenes()) & set(ls.scenes())
+    for name, s in ls.cap_scenes().items():
+        n_opt = int((s["fixed"] == 0).sum())
+        assert 6 * n_opt == int(name[5:]) == 6 * ls.cap_references()[name]["n_opt_kf"]
+        assert np.bincount(s["obs_kf"], minlength=len(s["kfs"]))[s["fixed"] == 0].min() >= 3
+        assert (np.diff(s["obs_off"]) == 4).all()
+        assert ls.cap_references()[name]["iterations_run"] >= 3  # the reduced solve runs several times
+
+
 def test_scene_sizes():
     sc = ls.scenes()
     count = lambda s, k: int((s["obs_kf"] == k).sum())

@@ -168,3 +168,46 @@ def test_the_selection_alone_against_the_loop():
         got = hc.select(c, first, n_it, mx, mi)
         want = mr.loop_on_counts(c, first, n_it, mx, mi)
         assert got == want, (trial, c, first, n_it, mx, mi)
+    # at mlpnp::kMaxHypotheses: anywhere, and walks that reach the last count (nothing before it above the minimum)
+    nh = 1024
+    for trial in range(60):
+        mi = int(rng.integers(6, 12))
+        mx, first = int(rng.integers(1, nh + 1)), int(rng.integers(0, nh + 1))
+        n_it = int(rng.integers(0, nh - first + 1))
+        c = rng.integers(0, 14, nh).astype(np.int32)
+        assert hc.select(c, first, n_it, mx, mi) == mr.loop_on_counts(c, first, n_it, mx, mi), (trial, first, n_it, mx, mi)
+        c = np.minimum(c, mi)
+        c[-1] = mi + 1
+        first = min(first, nh - 1)
+        for f, n, m in ((0, nh, 1), (0, 0, nh), (first, nh - first, mx), (first, 0, nh)):
+            got = hc.select(c, f, n, m, mi)
+            assert got == mr.loop_on_counts(c, f, n, m, mi), (trial, f, n, m, mi)
+            assert (got["found"], got["refined"], got["best"], got["pose"], got["iterations"]) == (1, 1, nh - 1, nh - 1, nh)
+
+
+def test_winner_last_scene_returns_the_last_hypothesis():
+    """The precondition of the device test at the cap, on the host build and on the loop over its counts."""
+    s, sets = ms.winner_last(1024)
+    assert len({tuple(t) for t in sets.tolist()}) == 1024 and s["outlier"][sets[:-1]].all() and not s["outlier"][sets[-1]].any()
+    counts = hc.ransac(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2, s["n"], 1024, 0, 0, sets)["hyp_inliers"]
+    mi = ms.winner_last_min_inliers(counts)
+    for first, n_it, mx in ((0, 1024, 1), (1019, 5, 1024)):
+        r = hc.ransac(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2, mi, mx, first, n_it, sets)["res"]
+        assert (r["found"], r["refined"], r["best_hypothesis"], r["iterations"]) == (1, 1, 1023, 1024)
+        want = mr.loop_on_counts(counts, first, n_it, mx, mi)
+        assert (want["pose"], want["iterations"]) == (1023, 1024)
+
+
+@pytest.mark.parametrize("n,extra", ms.LARGE)
+def test_large_scenes_have_interleaved_features_and_flags_past_the_first_256(n, extra):
+    """The preconditions of the device tests past a workgroup."""
+    for kind in ("general", "plane0") if n == 257 else ("general",):
+        s = ms.large_scene(n, extra, kind)
+        assert s["n"] == n and s["n_feat"] == n + extra + 7 and (s["where"][256:] > np.arange(256, n)).all()
+        for mi in (6, 50, n):
+            r = hc.ransac(s, ms.CAM, ms.LEVEL_SIGMA2, ms.TH2, mi, 5, 0, 5)
+            assert r["res"]["found"] == (mi < n)
+            if mi < n:
+                f = r["inlier"][s["where"]].astype(bool)
+                assert all(f[a:a + 256].any() for a in range(0, n, 256)) and not r["inlier"][s["slots"] < 0].any()
+    assert max(s_["n_feat"] for s_ in (ms.large_scene(*p) for p in ms.LARGE)) >= 700

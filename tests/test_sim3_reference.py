@@ -127,6 +127,46 @@ def test_selection_on_random_counts():
         best, conv, _, its, _ = sr.iterate_transcribed(counts, mi, nh)
         got = hc.select(counts, mi)
         assert (got["best"], got["converged"], got["iterations"]) == (best, conv, its)
+    # at and one below sim3::kMaxHypotheses: never, a tie of the maximum that ends at the last count, a hit at the last count
+    for nh in (1023, 1024):
+        for _ in range(20):
+            mi = int(rng.integers(0, 12))
+            low = rng.integers(0, mi + 1, nh)  # none above the minimum: the walk reaches the last count
+            hit = low.copy()
+            hit[-1] = mi + 1                   # only the last is above it
+            tie = low.copy()
+            tie[-1] = low.max()                # never, and the last of the tied maxima is the last count
+            anywhere = rng.integers(0, mi + 2, nh)
+            for counts in (low, hit, tie, anywhere):
+                best, conv, _, its, _ = sr.iterate_transcribed(counts, mi, nh)
+                got = hc.select(counts, mi)
+                assert (got["best"], got["converged"], got["iterations"]) == (best, conv, its), (nh, mi)
+            assert hc.select(hit, mi) == dict(best=nh - 1, converged=True, iterations=nh)
+            assert hc.select(tie, mi) == dict(best=nh - 1, converged=False, iterations=nh)
+
+
+@pytest.mark.parametrize("n_hyp", (1023, 1024))
+def test_winner_last_scene_returns_the_last_hypothesis(n_hyp):
+    """The precondition of the device test at the cap, on the host build and on iterate's loop transcribed."""
+    s, sm = ss.winner_last(n_hyp)
+    assert len(sm) == n_hyp and len({tuple(t) for t in sm.tolist()}) > n_hyp // 2
+    assert all(s["outlier"][t].any() for t in sm[:-1]) and not s["outlier"][sm[-1]].any()
+    counts = hc.ransac(s, 0, False, sm)["hyp_inliers"]
+    mi = ss.winner_last_min_inliers(counts)
+    r = hc.ransac(s, mi, False, sm)["res"]
+    assert (r["best_hypothesis"], r["converged"], r["iterations"]) == (n_hyp - 1, 1, n_hyp)
+    assert sr.iterate_transcribed(counts, mi, n_hyp)[:2] == (n_hyp - 1, True)
+
+
+@pytest.mark.parametrize("n", ss.LARGE_SIZES)
+def test_large_scenes_flag_correspondences_past_the_first_256(n):
+    """The precondition of the device test past a workgroup: the returned flags are set on both sides of every multiple of 256
+    below n, so a trip or a workgroup left out shows."""
+    s = ss.large_scene(n)
+    for fix_scale in (False, True):
+        for mi in (n, 15):
+            f = hc.ransac(s, mi, fix_scale)["inlier"].astype(bool)
+            assert all(f[a:a + 256].any() for a in range(0, n, 256)), (n, fix_scale, mi)
 
 
 def _one_hypothesis(s, tri=(0, 1, 2), **kw):

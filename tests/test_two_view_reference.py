@@ -15,6 +15,8 @@ Two caps keep the comparison honest and are asserted:
     for F -- and at most 5 % of a scene's hypotheses are (measured: at most 7 of 200, all of them F);
     an inlier decision is left out only within 1e-3 (relative) of its threshold, at most 1 % of the decisions (measured: 0.0092 %).
 No compared decision may differ.  The planar scenes reach ReconstructH with rh_threshold = 0.40."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -138,6 +140,111 @@ def test_whole_routine_agrees_and_recovers_the_motion(runs):
     # 0.5 px of noise is 0.055 degrees of a ray at f = 517 px and the baseline subtends about 40 px: the rotation to a degree,
     # the direction of a translation that trades against the rotation at this field of view to ten
     assert worst["rot"] <= 1.0 and worst["dir"] <= 10.0
+
+
+def selected_motions(s, params=None, sets=None):
+    """The host build's call on a scene and CheckRT of every motion hypothesis of the selected model, from the call's own
+    outputs: (reconstruct's dict, [check_rt's dict per motion hypothesis])."""
+    h = hc.reconstruct(s, params, sets)
+    res = h["res"]
+    M21, inl = (res["H21"], h["inlier_h"]) if res["model"] == 0 else (res["F21"], h["inlier_f"])
+    Rs, tt = hc.motions(res["model"], M21, s["K"])
+    out = [hc.check_rt(R, t, s["K"], hc.matches_of(s)[1], inl) for R, t in zip(Rs, tt)]
+    assert [c["n_good"] for c in out] == list(res["n_good"][:len(out)])  # the hypotheses in the call's own order
+    return h, out
+
+
+def rank_holder(c):
+    """The first counted match whose cosine holds rank min(50, n_good - 1), and the numbers below and not above it."""
+    counted = c["state"] != 0
+    v, idx = c["cos"][counted], min(50, int(counted.sum()) - 1)
+    for j in np.flatnonzero(counted):
+        lo, le = int((v < c["cos"][j]).sum()), int((v <= c["cos"][j]).sum())
+        if lo <= idx < le:
+            return int(j), lo, le
+    return -1, 0, 0
+
+
+@functools.lru_cache(maxsize=None)
+def tie_scene():
+    """ts.tie_across_the_tile on the match that holds rank 50 under the chosen motion hypothesis of ts.tie_base() and the
+    match of the largest cosine."""
+    _, checks = selected_motions(ts.tie_base())
+    c = max(checks, key=lambda c: c["n_good"])
+    a = rank_holder(c)[0]
+    b = int(np.argmax(np.where(c["state"] != 0, c["cos"], -2.0)))
+    assert a >= 0 and a != b
+    return ts.tie_across_the_tile(a, b)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_cases():
+    """name -> scene: what tests/test_gpu_two_view.py runs past the first tile of k_tv_check_rt's rank count and at the cap
+    of the iterations."""
+    out = {"matches_%d" % n: ts.tile_scene(n) for n in ts.TILE_SIZES}
+    out["rank_holder_late"], out["tie_across_the_tile"], out["winner_last"] = ts.rank_holder_late(), tie_scene(), ts.winner_last()
+    return out
+
+
+@pytest.mark.parametrize("name", ["matches_%d" % n for n in ts.TILE_SIZES] + ["rank_holder_late", "tie_across_the_tile", "winner_last"])
+def test_rank_count_equals_the_sort_past_the_tile(name):
+    """vCosParallax[min(50, size - 1)] after std::sort, as TwoViewReconstruction.cc has it, against the header's rank count,
+    for every motion hypothesis of the selected model."""
+    s = tile_cases()[name]
+    h, checks = selected_motions(s)
+    assert len(checks) in (4, 8) and max(c["n_good"] for c in checks) > 51
+    for c in checks:
+        counted = c["state"] != 0
+        assert int(counted.sum()) == c["n_good"]
+        if c["n_good"] == 0:
+            assert np.isnan(hc.ranked_cosine(c["cos"], c["state"]))
+            continue
+        want = np.sort(c["cos"][counted])[min(50, c["n_good"] - 1)]
+        got = hc.ranked_cosine(c["cos"], c["state"])
+        assert got.tobytes() == want.tobytes() == c["cosine"].tobytes(), (name, c["n_good"])
+
+
+def test_tile_scene_sizes():
+    for n in ts.TILE_SIZES:
+        s = ts.tile_scene(n)
+        assert int((s["matches12"] >= 0).sum()) == n and 0.08 * n <= s["is_outlier"].sum() <= 0.12 * n and 8 <= len(s["sets"]) <= 16
+        r = hc.reconstruct(s)["res"]
+        assert r["ok"] == 1 and r["model"] == 1 and max(r["n_good"]) > 0.8 * n and max(len(s["xy1"]), len(s["xy2"])) <= 4096
+
+
+def test_rank_holder_lies_past_the_first_tile():
+    """The directed scene: the candidate trips of the rank count pass index 1024 before a match holds rank 50."""
+    s = ts.rank_holder_late()
+    h, checks = selected_motions(s)
+    assert int((s["matches12"] >= 0).sum()) == 1500 and h["res"]["ok"] == 1 and h["res"]["model"] == 1
+    c = max(checks, key=lambda c: c["n_good"])
+    j, lo, le = rank_holder(c)
+    assert c["n_good"] == 1500 and j >= ts.TILE and lo <= 50 < le
+    assert c["cos"][j] == hc.ranked_cosine(c["cos"], c["state"])
+
+
+def test_tie_sits_across_the_tile_boundary():
+    s = tie_scene()
+    i1 = np.nonzero(s["matches12"] >= 0)[0]
+    a, b = ts.TILE - 1, ts.TILE
+    assert (s["xy1"][i1[a]] == s["xy1"][i1[b]]).all() and (s["xy2"][s["matches12"][i1[a]]] == s["xy2"][s["matches12"][i1[b]]]).all()
+    assert i1[a] != i1[b] and s["matches12"][i1[a]] != s["matches12"][i1[b]] and len(i1) == 1100
+    h, checks = selected_motions(s)
+    c = max(checks, key=lambda c: c["n_good"])
+    assert h["res"]["ok"] == 1 and c["state"][a] != 0 and c["state"][b] != 0
+    v = c["cos"][c["state"] != 0]
+    assert c["cos"][a].tobytes() == c["cos"][b].tobytes()
+    for j in (a, b):
+        assert (v < c["cos"][j]).sum() <= 50 < (v <= c["cos"][j]).sum()
+    assert rank_holder(c)[0] == a and hc.ranked_cosine(c["cos"], c["state"]) == c["cos"][a]
+
+
+def test_winner_last_scene_selects_the_last_iteration():
+    s = ts.winner_last()
+    assert len(s["sets"]) == 1024 and (s["sets"][:1023] == s["sets"][0]).all()
+    assert s["is_outlier"][s["sets"][0]].all() and not s["is_outlier"][s["sets"][1023]].any()
+    h = hc.reconstruct(s)
+    assert h["res"]["best_it_f"] == 1023 and ref.first_maximum(h["score_f"])[0] == 1023
 
 
 def test_sweep_counts_are_one_past_convergence():

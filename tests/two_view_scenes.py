@@ -41,9 +41,10 @@ def project(X):
 
 
 def make(seed, n=100, planar=False, extra1=37, extra2=53, noise=0.5, outliers=0.2, deg=4.0, t=(-0.4, 0.05, 0.02), n_iter=200,
-         depth=(3.0, 8.0)):
+         depth=(3.0, 8.0), farthest_first=False):
     """n matches between a frame of n + extra1 and a frame of n + extra2 keypoints.  Returns dict(xy1, xy2, matches12, K,
-    sets, R, t, n, n1, n2, is_outlier [n, in the order of the compacted matches])."""
+    sets, R, t, n, n1, n2, is_outlier [n, in the order of the compacted matches]).  farthest_first: the compacted matches in
+    descending order of their point's depth."""
     rng = np.random.default_rng(seed)
     R, t = rot_y(deg), np.asarray(t, np.float64)
     X = np.zeros((0, 3))
@@ -58,6 +59,8 @@ def make(seed, n=100, planar=False, extra1=37, extra2=53, noise=0.5, outliers=0.
         ok = (P2[:, 2] > 0.1) & (p2[:, 0] > 0) & (p2[:, 0] < W) & (p2[:, 1] > 0) & (p2[:, 1] < H)
         X = np.concatenate([X, P[ok]])
     X = X[:n]
+    if farthest_first:
+        X = X[np.argsort(-X[:, 2], kind="stable")]
     p1 = project(X) + rng.normal(0, noise, (n, 2)) if noise else project(X)
     p2 = project(X @ R.T + t) + (rng.normal(0, noise, (n, 2)) if noise else 0)
     is_out = np.zeros(n, bool)
@@ -84,6 +87,51 @@ def issue_scene(seed, n, planar):
 def issue_scenes():
     """The sixteen scenes of the issue: general and planar, 100 and 300 matches, four seeds each."""
     return [(planar, n, seed, issue_scene(seed, n, planar)) for planar in (False, True) for n in SIZES for seed in SEEDS[(planar, n)]]
+
+
+TILE = 1024               # kTvTile of csrc/vsg_two_view.hip: the rank count of k_tv_check_rt goes through LDS tiles of this size
+TILE_SIZES = (1023, 1024, 1025, 2049)
+
+
+def tile_scene(n):
+    """A general scene of n matches around the tile, 10 % outliers, 16 sets.  0.25 px of noise: with so few sets the best
+    eight-point F of a 0.5 px scene often passes too few matches through CheckRT for the routine to initialise, and the
+    rank count is at work only where more than 51 matches are counted."""
+    return make(700 + n, n=n, outliers=0.1, noise=0.25, n_iter=16, extra1=21, extra2=34)
+
+
+def rank_holder_late():
+    """1500 noise-free matches, the farthest point first: the small cosines (the near points) sit at the highest indices, so
+    the candidate trips of the rank count go past index 1024 before one holds rank 50."""
+    return make(731, n=1500, outliers=0.0, noise=0.0, n_iter=12, extra1=21, extra2=34, farthest_first=True)
+
+
+def tie_base():
+    return make(741, n=1100, outliers=0.0, noise=0.0, n_iter=12, extra1=21, extra2=34)
+
+
+def tie_across_the_tile(a, b):
+    """tie_base() in which the match b takes the keypoints of the match a in both frames (one keypoint twice in each frame)
+    and the matches are permuted so that the two sit at the compacted indices 1023 and 1024.  The caller chooses a (the
+    match whose cosine holds rank 50) and b (one of a larger cosine) on tie_base() with the host build."""
+    base = tie_base()
+    s = dict(base, xy1=base["xy1"].copy(), xy2=base["xy2"].copy(), matches12=base["matches12"].copy())
+    i1 = np.nonzero(s["matches12"] >= 0)[0]
+    i2 = s["matches12"][i1]
+    s["xy1"][i1[b]], s["xy2"][i2[b]] = s["xy1"][i1[a]], s["xy2"][i2[a]]
+    order = [k for k in range(len(i1)) if k not in (a, b)]
+    order[TILE - 1:TILE - 1] = [a, b]
+    s["xy1"][i1], s["matches12"][i1] = s["xy1"][i1[order]], i2[order]
+    return s
+
+
+def winner_last(n_iter=1024, seed=751):
+    """100 matches; n_iter - 1 copies of one set of outlier matches, then one set of true matches: the last hypothesis wins."""
+    s = make(seed, n=100, n_iter=1)
+    rng = np.random.default_rng(seed)
+    bad, good = np.flatnonzero(s["is_outlier"]), np.flatnonzero(~s["is_outlier"])
+    s["sets"] = np.concatenate([np.tile(rng.choice(bad, 8, replace=False), (n_iter - 1, 1)), rng.choice(good, 8, replace=False)[None]]).astype(I32)
+    return s
 
 
 def pure_rotation(seed, n=120):
