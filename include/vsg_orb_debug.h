@@ -57,6 +57,40 @@ int vsg_debug_last_launch_forms(vsg_orb *h, vsg_launch_forms *out);
  * database never saw (never added, mapped or named as a neighbour); the outputs are then left alone. */
 int vsg_debug_kfdb_state(vsg_kfdb *db, uint64_t kf_id, uint64_t query[2], int32_t words[2], float score[2]);
 
+/* Words of the `status` vsg_debug_track_walk hands back: walkdev::Status of csrc/vsg_walks_dev.h as int32 */
+enum {
+  VSG_WALK_ST_NMATCHES = 0,
+  VSG_WALK_ST_N_EDGES = 1,
+  VSG_WALK_ST_FLAGS = 2, /* 1: the lists overflowed (nothing else was written), 2: nmatches < min_matches, 4: < 3 edges */
+  VSG_WALK_ST_ROUNDS = 3,
+  VSG_WALK_ST_OVERFLOW_SUM = 4,
+  VSG_WALK_ST_BINS = 5, /* 30 words: claims per rotation bin before the filter */
+  VSG_WALK_ST_WORDS = 36
+};
+
+/* Test hook: the ordered walk of the two chain calls (k_track_walk: vsg_frame_track_with_motion_model's and
+ * vsg_frame_track_local_map's pass between the window search and the pose solve) ALONE, on candidate lists the caller
+ * wrote: one launch of the kernel through the chain calls' own launch function on the calling thread's stream and arenas,
+ * one wait, then the copies out.
+ *   form: 0 the last-frame walk, 1 the local one.  Lists as the window search lays them out: list q is ent[off[q] ..
+ *   off[q] + cnt[q]) of n_ent entries in all, a list longer than 16 lies in the overflow area of `cap` entries; off and cnt
+ *   are NOT validated here (the kernel does that: a list outside the array ends the call as an overflow).  q_valid,
+ *   observed [nq], blocked_in [nf], q_slot [nq], slots_in [nf] and slot_observed [n_slots] may be NULL with the meaning
+ *   walkdev::Args gives that; q_angle [nq] and t_angle [nf] are plain float arrays.
+ *   Outputs, [nf] each: what the kernel does not write comes back as the caller passed it (edge_feat / edge_slot behind
+ *   n_edges; feat_observed without slot_observed; everything but `status` after an overflow).  status: VSG_WALK_ST_WORDS
+ *   int32.
+ * Before a device is touched, with nothing written: VSG_ERR_INVALID for a NULL among ent, off, cnt, q_angle, t_angle, the
+ * outputs and status, a negative count, nf > 32768 (an entry's index field has 15 bits), form outside {0, 1}, and, with
+ * slot_observed, a q_slot or slots_in entry outside [-1, n_slots); VSG_ERR_CAPACITY for a shape whose LDS the chain
+ * calls refuse.  nq == 0 and nf == 0 are launched. */
+int vsg_debug_track_walk(int form, int nq, int nf, int n_ent, const uint32_t *ent, const int32_t *off, const int32_t *cnt,
+                         int cap, const uint8_t *q_valid, const uint8_t *observed, const uint8_t *blocked_in,
+                         const float *q_angle, const float *t_angle, const int32_t *q_slot, const int32_t *slots_in,
+                         const uint8_t *slot_observed, int n_slots, int check_orientation, int min_matches, float nnratio,
+                         int32_t *train_match, uint8_t *train_blocked, int32_t *feat_slots, uint8_t *feat_observed,
+                         int32_t *edge_feat, int32_t *edge_slot, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,47 @@ def test_struct_layout_matches_the_header(tmp_path):
     assert got == [104, 0, 72, 76, 80, 84, 88, 92, 96, 100]
 
 
+def test_the_walk_hook_is_a_debug_symbol_and_refuses_without_a_device():
+    """vsg_debug_track_walk (k_track_walk alone): declared in include/vsg_orb_debug.h, exported by the shipped library, no
+    part of the boundary a maintainer binds; NULL, negative and out-of-range arguments and a shape over the LDS cap are
+    refused before a device is touched, with nothing written."""
+    import walk_cases as wc
+    L, hook = orb.load_library(), "vsg_debug_track_walk"
+    assert re.search(r"\bint %s\(" % hook, (ROOT / "include" / "vsg_orb_debug.h").read_text())
+    assert hasattr(L, hook) and hook in orb.EXPORTS and len(getattr(L, hook).argtypes) == len(orb.WALK_ARGS) == 27
+    assert hook not in (ROOT / "include" / "vsg_orb.h").read_text() and hook not in (ROOT / "INTEGRATION.md").read_text()
+    assert "vsg_orb_debug.h" not in (ROOT / "INTEGRATION.md").read_text()
+    c = wc.directed_high()["from_slots_50"]
+    pos = {k: i for i, k in enumerate(orb.WALK_ARGS)}
+
+    def raw(case=c, table=c["slot_observed"], **replace):
+        args, out, keep = orb.debug_track_walk_args(case, slot_observed=table)
+        for k, v in replace.items():
+            args[pos[k]] = v
+        rc = L.vsg_debug_track_walk(*args)
+        if rc < 0:  # nothing is written by a refused call
+            assert all((out[k] == orb.WALK_SENTINEL_I32).all() for k in ("tm", "feat_slots", "edges_feat", "edges_slot", "status"))
+            assert all((out[k] == orb.WALK_SENTINEL_U8).all() for k in ("tb", "feat_observed"))
+        return rc
+
+    for k in ("ent", "off", "cnt", "q_angle", "t_angle", "train_match", "train_blocked", "feat_slots", "feat_observed",
+              "edge_feat", "edge_slot", "status"):
+        assert raw(**{k: None}) == INVALID, k
+    for k in ("nq", "nf", "n_ent", "cap", "n_slots"):
+        assert raw(**{k: -1}) == INVALID, k
+    assert raw(nf=32769) == INVALID and raw(form=2) == INVALID and raw(form=-1) == INVALID
+    bad = c["q_slot"].copy()
+    bad[-1] = len(c["slot_observed"])
+    assert raw(case=dict(c, q_slot=bad)) == INVALID
+    bad = c["slots_in"].copy()
+    bad[0] = -2
+    assert raw(case=dict(c, slots_in=bad)) == INVALID
+    for name in sorted(wc.OVER_CAP_SHAPES):  # VSG_ERR_CAPACITY, by the chain calls' expression
+        assert raw(case=wc.cap_cases()[name], table=None) == -2, name
+    if L.vsg_device_count() <= 0:  # the same call with valid arguments gets as far as the device
+        assert raw() == -4 and raw(case=wc.cap_cases()["cap_queries"], table=None) == -4
+
+
 def test_refusals_need_no_device():
     L = orb.load_library()
     n = 4

@@ -41,8 +41,8 @@ class Local:
     """A scene of tests/track_scenes.py with its local map: every point of the store in a seeded order, the entry slots of
     the motion-model call, and the points those features hold marked as seen (mnLastFrameSeen == mnId)."""
 
-    def __init__(self, ex, seed, rgbd):
-        s = self.s = ts.Scene(ex, seed, rgbd)
+    def __init__(self, ex, seed, rgbd, per_keypoint=3):
+        s = self.s = ts.Scene(ex, seed, rgbd, per_keypoint=per_keypoint)
         f2, self.desc, _ = ts.make_frame(ex, seed, rgbd)  # the scene's own frame once more, for its descriptors
         assert f2.kps.tobytes() == s.F.kps.tobytes()
         rng = np.random.default_rng(900 + seed)
@@ -149,6 +149,24 @@ def test_equal_to_the_two_call_path(loc, th):
         assert want["n_bad"] > 0
     assert not (blocked.astype(bool) & (tm >= 0)).any() and got["walk_rounds"] >= 1
     assert (want["outlier"][want["after_walk"] < 0] == ts.FLAG).all()
+
+
+def test_past_1024_features_equal_to_the_two_call_path():
+    """2000 features asked for, as the reference's KITTI settings do: the walk kernel's lanes go round their stride for the
+    feature arrays, its prologue derives "blocked on entry" for features past the first 1024, and its edge compaction
+    carries its base into a second chunk.  (Two points per keypoint: with three the call comes within 60 bytes of the
+    walk's LDS cap.)"""
+    loc = Local(orb.ORBextractor(2000, 1.2, 8, 20, 7), 3, False, per_keypoint=2)
+    got, want = loc.both(3)
+    s, after_walk = loc.s, want["after_walk"]
+    print(f"n {s.n} local {len(loc.local)} entry {int((loc.entry >= 0).sum())} new {int((want['train_match'] >= 0).sum())} "
+          f"edges {want['n_initial']} slots at >= 1024: {int((after_walk[1024:] >= 0).sum())} "
+          f"claimed at >= 1024: {int((want['train_match'][1024:] >= 0).sum())} rounds {want['rounds_run']} "
+          f"walk rounds {got['walk_rounds']}")
+    assert s.n > 1024 and int((after_walk[1024:] >= 0).sum()) >= 50
+    assert want["held"] == 0 and want["rounds_run"] == 4  # the solve ran all its rounds
+    assert int((want["train_match"][1024:] >= 0).sum()) >= 1 and int((loc.entry[1024:] >= 0).sum()) >= 1
+    assert got["n_initial"] == int((after_walk >= 0).sum())
 
 
 @pytest.mark.parametrize("only_tracking", [0, 1])

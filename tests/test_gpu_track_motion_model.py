@@ -50,6 +50,21 @@ def test_equal_to_the_two_call_path(scene, th):
     both(scene, th, mono=True)
 
 
+def test_past_1024_features_equal_to_the_two_call_path():
+    """2000 features asked for, as the reference's KITTI settings do: the walk kernel's lanes go round their stride for the
+    feature arrays and its edge compaction carries its base into a second chunk.  (Two points per keypoint: with three the
+    last frame comes within 60 bytes of the walk's LDS cap.)"""
+    s = ts.Scene(orb.ORBextractor(2000, 1.2, 8, 20, 7), 3, False, per_keypoint=2)
+    got, want = both(s, 15)
+    tm = want["train_match"]
+    after_walk = np.where(tm >= 0, s.slots[np.maximum(tm, 0)], -1)  # the caller's loop, before the discard
+    print(f"n {s.n} last {len(s.slots)} nmatches {want['n_matches_searched']} edges {want['n_initial']} "
+          f"slots at >= 1024: {int((after_walk[1024:] >= 0).sum())} bad {want['n_bad']} rounds {want['rounds_run']}")
+    assert s.n > 1024 and int((after_walk[1024:] >= 0).sum()) >= 50
+    assert want["optimized"] == 1 and want["rounds_run"] == 4 and want["wide"] == 0
+    assert got["n_initial"] == int((after_walk >= 0).sum())
+
+
 def test_threshold_sweep_of_20_matches(scene):
     """15 .. 25 active last_slots around Tracking.cc:2958 / :2967: below 20 and lifted by the 2 * th search, below 20 and
     staying there, 20 or more at once."""

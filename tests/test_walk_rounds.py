@@ -103,3 +103,108 @@ def test_an_overflow_is_summed_over_every_long_list_and_nothing_is_walked():
     # with room for all of them the same lists are no overflow (67 entries behind the slots)
     flags, total, _ = wc.overflow_status(off, cnt, 67)
     assert flags & 1 == 0 and total == 67
+
+
+# ---- the cases past one trip of the workgroup's loops and at the LDS cap (walk_cases.big_cases, directed_high, cap_cases):
+# what makes each of them what it claims to be, from the serial definition, so that the GPU tests that walk them on the
+# device (tests/test_gpu_track_walk.py) cannot quietly lose their point
+
+def test_the_lds_restatement_follows_the_kernels_constants():
+    from pathlib import Path
+    csrc = Path(__file__).resolve().parent.parent / "visual_sgraphs_amd" / "csrc"
+    track, dev = (csrc / "vsg_track.hip").read_text(), (csrc / "vsg_walks_dev.h").read_text()
+    assert "kWalkThreads = 1024, kWalkWaves = kWalkThreads / 64, kWalkStaticLds = kWalkWaves * 4, kWalkLdsMax = 64 * 1024" in track
+    assert "return ((size_t)2 * nf + nq + walkdev::kScratchInts) * 4 + (size_t)2 * nq + nf;" in track
+    assert "walk_lds_bytes(nq, nf) + kWalkStaticLds > kWalkLdsMax" in track and "enum { kScratchInts = 40 };" in dev
+    assert (wc.LANES, wc.LDS_STATIC, wc.LDS_MAX) == (1024, 1024 // 64 * 4, 64 * 1024)
+    for name, (nq, nf) in wc.CAP_SHAPES.items():  # the largest accepted shapes: one query more is refused
+        assert wc.lds_bytes(nq, nf) + wc.LDS_STATIC == 65534 and not wc.over_cap(nq, nf), name
+        assert wc.lds_bytes(nq + 1, nf) + wc.LDS_STATIC == 65540 and wc.over_cap(nq + 1, nf), name
+        assert wc.OVER_CAP_SHAPES["over_" + name] == (nq + 1, nf)
+    assert {(c["nq"], c["nf"]) for c in wc.cap_cases().values()} == set(wc.CAP_SHAPES.values()) | set(wc.OVER_CAP_SHAPES.values())
+    assert all(c["form"] == wc.LOCAL for c in wc.cap_cases().values())
+
+
+@pytest.mark.parametrize("name", sorted(wc.big_cases()))
+def test_big_cases_go_round_the_workgroups_loops_and_equal_the_serial_walk(name):
+    c = wc.big_cases()[name]
+    nq, nf = c["nq"], c["nf"]
+    r, d = wc.run(c)
+    print(f"{name}: overwrites {r['overwrites']} dropped {r['dropped']} rounds {d['rounds']} edges {r['n_edges']} "
+          f"edges >= 1024: {int((r['edge_feat'] >= wc.LANES).sum())} nmatches {r['nmatches']}")
+    assert wc.same(r, d) == []
+    assert (nq, nf) in wc.BIG_SHAPES and nq > wc.LANES and (c["cnt"] <= 40).all() and (c["cnt"] > wc.INLINE).any()
+    assert r["n_edges"] > 0 and r["edge_feat"][-1] == nf - 1 and r["tm"][nf - 1] == -1 and r["tb"][nf - 1] == 1
+    assert d["rounds"] >= 3
+    if nf == 2049:
+        assert int((r["edge_feat"] >= wc.LANES).sum()) >= 500 and int((r["tm"] >= wc.LANES).sum()) >= 1
+    if c["form"] == wc.LAST:
+        assert r["overwrites"] >= 100 and r["dropped"] >= 100
+
+
+@pytest.mark.parametrize("name", ["pile_up_high", "pile_up_high_local"])
+def test_a_pile_up_behind_1024_empty_lists_takes_more_than_32_rounds_and_finishes(name):
+    c = wc.directed_high()[name]
+    r, d = wc.run(c)
+    assert c["nq"] == 1088 and (c["cnt"][:1024] == 0).all() and (c["cnt"][1024:] == 70).all()
+    assert r["tm"][:64].tolist() == list(range(1024, 1088)) and r["nmatches"] == 64  # query 1024 + k ends on feature k
+    assert 32 < d["rounds"] <= c["nq"] + 1
+    assert wc.same(r, d) == []
+
+
+@pytest.mark.parametrize("nf", [50, 2049])
+def test_from_slots_blocks_features_by_their_entry_slots_alone(nf):
+    c = wc.directed_high()["from_slots_%d" % nf]
+    assert c["form"] == wc.LOCAL and c["blocked"] is None and c["nf"] == nf and len(c["slot_observed"]) == wc.N_STORE
+    assert 0.4 < c["slot_observed"].mean() < 0.6
+    blocked = wc.blocked_from_slots(c)
+    r, d = wc.reference(c)
+    assert wc.same(r, d) == [] and r["tb"][blocked != 0].all() and not (blocked.astype(bool) & (r["tm"] >= 0)).any()
+    blocked_best = 0  # how often a feature blocked by the rule is the nearest candidate of a valid query
+    for q in np.flatnonzero((c["q_valid"] != 0) & (c["cnt"] > 0)):
+        l = c["ent"][c["off"][q]:c["off"][q] + c["cnt"][q]].astype(np.int64)
+        blocked_best += int(blocked[(l & 0x7FFF)[np.argmin((l >> 15) & 0x1FF)]])
+    print(f"from_slots_{nf}: blocked {int(blocked.sum())} blocked-best {blocked_best} rounds {d['rounds']} "
+          f"edges {r['n_edges']} nmatches {r['nmatches']}")
+    assert int(blocked.sum()) >= 10 and blocked_best >= 1
+    if nf > wc.LANES:
+        assert int(blocked[wc.LANES:].sum()) >= 10 and int((r["edge_feat"] >= wc.LANES).sum()) >= 100
+    # without the rule the walk ends differently: the case depends on it
+    r0, _ = wc.run(c)
+    assert r0["tm"].tobytes() != r["tm"].tobytes()
+
+
+def test_few_matches_and_few_edges_sit_on_both_sides_of_their_thresholds():
+    D = wc.directed_high()
+    for name, nm, flags in (("few_matches_19", 19, wc.ST_FEW_MATCHES), ("few_matches_20", 20, 0),
+                            ("few_edges_2", 2, wc.ST_FEW_EDGES), ("few_edges_3", 3, 0)):
+        c = D[name]
+        r, d = wc.run(c)
+        assert wc.same(r, d) == [] and r["nmatches"] == nm and r["n_edges"] == nm, name
+        assert r["tm"][:nm].tolist() == list(range(nm)) and wc.status_flags(r, c) == flags, name
+        assert d["flags"] == flags & wc.ST_FEW_EDGES, name  # the host build runs with min_matches = 0
+    assert D["few_matches_19"]["min_matches"] == 20 == D["few_matches_20"]["min_matches"]
+
+
+@pytest.mark.parametrize("name", sorted(wc.CAP_SHAPES))
+def test_the_largest_accepted_shapes_equal_the_serial_walk(name):
+    c = wc.cap_cases()[name]
+    r, d = wc.run(c)
+    print(f"{name}: rounds {d['rounds']} edges {r['n_edges']} edges >= 1024: {int((r['edge_feat'] >= wc.LANES).sum())} "
+          f"nmatches {r['nmatches']}")
+    assert wc.same(r, d) == [] and (c["nq"], c["nf"]) == wc.CAP_SHAPES[name]
+    assert r["edge_feat"][-1] == c["nf"] - 1 and int((r["edge_feat"] >= wc.LANES).sum()) >= 500 and r["nmatches"] >= 100
+    if c["nq"] > wc.LANES:  # (385 queries on 7000 features hardly collide)
+        assert d["rounds"] >= 3 and int((r["tm"] >= wc.LANES).sum()) >= 100
+
+
+def test_the_first_400_random_cases_cover_what_the_device_run_needs(random_results):
+    """tests/test_gpu_track_walk.py walks seeds 0 .. 399 on the device."""
+    res, cases = random_results[:400], wc.random_cases()[:400]
+    overwrite = sum(1 for r, _ in res if r["overwrites"] > 0)
+    dropped = sum(1 for r, _ in res if r["dropped"] > 0)
+    long_walks = sum(1 for _, d in res if d["rounds"] > 3)
+    inline = sum(1 for c in cases if ((c["cnt"] > 0) & (c["cnt"] <= wc.INLINE)).any())
+    overflow = sum(1 for c in cases if (c["cnt"] > wc.INLINE).any())
+    print(f"overwrite {overwrite} dropped {dropped} rounds > 3: {long_walks} inline {inline} overflow {overflow}")
+    assert min(overwrite, dropped, long_walks, inline, overflow) >= 100

@@ -1,7 +1,8 @@
 """Candidate lists for the ordered walks (csrc/vsg_walks.h, csrc/vsg_walks_dev.h) in the layout k_window_search writes:
 every query owns an inline slot of 16 entries, a longer list lies whole in the overflow area behind the slots, segments in
-no particular order.  Shared by tests/test_walk_rounds.py and tests/test_sanitizers_walk.py; run() walks one case through
-the host build tests/_walkcore, by the serial definition and by the round form."""
+no particular order.  Shared by tests/test_walk_rounds.py, tests/test_sanitizers_walk.py and tests/test_gpu_track_walk.py
+(the same case dictionaries feed k_track_walk on the device); run() walks one case through the host build
+tests/_walkcore, by the serial definition and by the round form."""
 import ctypes as C
 import functools
 import subprocess
@@ -172,6 +173,132 @@ def directed():
     D["second_open"] = case(LOCAL, [entry([1], [30]), entry([2, 1, 3], [50, 55, 90], [1, 1, 1])], 10, observed=[0, 1],
                             nnratio=0.8)
     return D
+
+
+# ---- cases past one trip of the workgroup's loops (k_track_walk: 1024 lanes) and at its LDS cap.  A case may carry two
+# keys more than case() gives it: "min_matches" (Args::min_matches, else 0) and "slot_observed" (the store's flags per slot:
+# with them and without a blocked array the kernel derives "blocked on entry" itself; reference() restates that).
+N_STORE = 5000
+LANES = 1024  # kWalkThreads of csrc/vsg_track.hip
+ST_OVERFLOW, ST_FEW_MATCHES, ST_FEW_EDGES = 1, 2, 4  # walkdev::kSt*
+
+
+def lds_bytes(nq, nf):
+    """walk_lds_bytes of csrc/vsg_track.hip: claim[nf], tm[nf], choice[nq] and kScratchInts = 40 words, then the bytes
+    observed[nq], q_valid[nq], blocked[nf]."""
+    return (2 * nf + nq + 40) * 4 + 2 * nq + nf
+
+
+LDS_STATIC, LDS_MAX = 64, 64 * 1024  # kWalkStaticLds (wsum: one word per wave of 64), kWalkLdsMax
+
+
+def over_cap(nq, nf):
+    """the refusal of the chain calls and of the hook: VSG_ERR_CAPACITY"""
+    return lds_bytes(nq, nf) + LDS_STATIC > LDS_MAX
+
+
+# the largest accepted shapes with many queries and with many features (65534 bytes each), and one query more (65540)
+CAP_SHAPES = {"cap_queries": (7885, 2000), "cap_features": (385, 7000)}
+OVER_CAP_SHAPES = {"over_cap_queries": (7886, 2000), "over_cap_features": (386, 7000)}
+BIG_SHAPES = ((1500, 1023), (1500, 1024), (1500, 1025), (3000, 2049))
+
+
+def _windows(rng, nq, nf):
+    """random_case's lists without its size limits: 0 .. 40 entries (15 % of the lists empty) out of a window of 60
+    features around the query's own centre, modulo nf"""
+    lists = []
+    for _ in range(nq):
+        n = int(rng.integers(0, 41)) if rng.random() > 0.15 else 0
+        idx = (int(rng.integers(0, nf)) + rng.permutation(60)[:n]) % nf
+        lists.append(entry(idx, rng.choice(DISTS, n), rng.integers(0, 3, n)))
+    return lists
+
+
+def big_case(form, nq, nf, seed):
+    rng = np.random.default_rng(seed)
+    lists = _windows(rng, nq, nf)
+    blocked = rng.random(nf) < 0.1
+    slots_in = np.where(rng.random(nf) < 0.3, rng.integers(0, N_STORE, nf), -1)
+    blocked[nf - 1], slots_in[nf - 1] = True, 4999  # the last feature is always in the edge list, and nobody claims it
+    return case(form, lists, nf, observed=rng.random(nq) < 0.7, blocked=blocked, q_angle=rng.choice(ANGLES, nq),
+                t_angle=rng.choice(ANGLES, nf), q_slot=rng.integers(0, N_STORE, nq), slots_in=slots_in,
+                q_valid=None if form == LAST else rng.random(nq) < 0.9, check=1, nnratio=0.8, rng=rng)
+
+
+@functools.lru_cache(maxsize=None)
+def big_cases():
+    """name -> case: both forms at BIG_SHAPES; nobody writes to a case."""
+    return {"big_%s_%d_%d" % ("last" if form == LAST else "local", nq, nf): big_case(form, nq, nf, 7 + nf)
+            for form in (LAST, LOCAL) for nq, nf in BIG_SHAPES}
+
+
+@functools.lru_cache(maxsize=None)
+def cap_cases():
+    """name -> case, local form: CAP_SHAPES (accepted) and OVER_CAP_SHAPES (refused)."""
+    return {name: big_case(LOCAL, nq, nf, 11 + nf) for name, (nq, nf) in {**CAP_SHAPES, **OVER_CAP_SHAPES}.items()}
+
+
+def from_slots(nf):
+    """Local form without a blocked array: the features' entry slots and the store's observed flags (about half set) stand
+    for it.  The queries' observed flags are their own points'."""
+    rng = np.random.default_rng(500 + nf)
+    nq = 40 if nf < 1000 else 3000
+    slot_observed = (rng.random(N_STORE) < 0.5).astype(U8)
+    q_slot = rng.integers(0, N_STORE, nq)
+    c = case(LOCAL, _windows(rng, nq, nf), nf, observed=slot_observed[q_slot] != 0, q_slot=q_slot,
+             slots_in=np.where(rng.random(nf) < 0.6, rng.integers(0, N_STORE, nf), -1), q_valid=rng.random(nq) < 0.9,
+             check=0, nnratio=0.8, rng=rng)
+    c["slot_observed"] = slot_observed
+    return c
+
+
+def blocked_from_slots(c):
+    """what k_track_walk's prologue derives (ORBmatcher.cc:86-88): the entry slot's point is observed"""
+    si = c["slots_in"]
+    return ((si >= 0) & (c["slot_observed"][np.maximum(si, 0)] != 0)).astype(U8)
+
+
+def single_claims(form, n, min_matches=0):
+    """n queries with one candidate each, query k on feature k: n matches and n edges"""
+    c = case(form, [entry([k], [10]) for k in range(n)], 30, observed=np.ones(n), check=0)
+    c["min_matches"] = min_matches
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def directed_high():
+    """name -> case: the directed cases that need the hook's extra arguments or more than one trip of the workgroup's loops."""
+    D = {}
+    # pile_up_64 behind 1024 queries with empty lists: the claimants are lanes 0 .. 63 of the loops' SECOND trip
+    empty = [entry([], [])] * LANES
+    observed = np.arange(LANES + 64) >= LANES
+    D["pile_up_high"] = case(LAST, empty + [entry(np.arange(70), np.arange(70))] * 64, 80, observed=observed)
+    D["pile_up_high_local"] = case(LOCAL, empty + [entry(np.arange(70), np.arange(70), np.arange(70) % 2)] * 64, 80,
+                                   observed=observed)
+    D["from_slots_50"], D["from_slots_2049"] = from_slots(50), from_slots(2049)
+    D["few_matches_19"], D["few_matches_20"] = single_claims(LAST, 19, 20), single_claims(LAST, 20, 20)
+    D["few_edges_2"], D["few_edges_3"] = single_claims(LOCAL, 2), single_claims(LOCAL, 3)
+    return D
+
+
+def reference(c):
+    """run() on the case as the serial definition has to be given it: (ref, dev)"""
+    if c.get("slot_observed") is not None and c["blocked"] is None:
+        c = dict(c, blocked=blocked_from_slots(c))
+    return run(c)
+
+
+def status_flags(ref, c):
+    """the flags of walkdev::Status from the definition's counts (no overflow)"""
+    return (ST_FEW_MATCHES if ref["nmatches"] < c.get("min_matches", 0) else 0) | (ST_FEW_EDGES if ref["n_edges"] < 3 else 0)
+
+
+def feat_slots_of(ref, c):
+    """the caller-side rule per feature: the claimant's q_slot, else slots_in, else -1"""
+    tm = ref["tm"]
+    qs = np.append(c["q_slot"], -1) if c["q_slot"] is not None else np.full(c["nq"] + 1, -1, I32)
+    si = c["slots_in"] if c["slots_in"] is not None else np.full(c["nf"], -1, I32)
+    return np.where(tm >= 0, qs[np.maximum(tm, 0)], si).astype(I32)
 
 
 def record(c):

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/vsg_orb_debug.h"
 #include "vsg_track_int.h"
 #include "vsg_track_stats.h"
 #include "vsg_walks_dev.h"
@@ -100,6 +101,16 @@ __global__ __launch_bounds__(kWalkThreads) void k_track_walk(walkdev::Args A) {
   walkdev::run(T, A);
 }
 
+// Does a walk of this shape ask for more LDS than kWalkLdsMax?  The refusal of the two chain calls and of the test hook.
+inline bool walk_over_cap(int nq, int nf) { return walk_lds_bytes(nq, nf) + kWalkStaticLds > kWalkLdsMax; }
+
+// The one launch of k_track_walk: one workgroup, its LDS sized by the shape.  The chain calls and the test hook
+// (vsg_debug_track_walk) enqueue it here and nowhere else.
+int walk_launch(hipStream_t stream, const walkdev::Args &A) {
+  hipLaunchKernelGGL(k_track_walk, dim3(1), dim3(kWalkThreads), walk_lds_bytes(A.nq, A.nf), stream, A);
+  return hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+}
+
 // The caller's block of a chain call behind the search's blocks.  Pinned: what the host reads after the wait.  Device: the
 // edge list and the status.
 struct TrackLayout {
@@ -132,8 +143,7 @@ int walk_solve_wait(TrackSearch &T, const TrackLayout &L, walkdev::Args &A, vsg_
   A.feat_observed = dp + L.pFo;
   A.edge_feat = (int32_t *)(dv + L.dFeat), A.edge_slot = (int32_t *)(dv + L.dSlot);
   A.status = (walkdev::Status *)(dv + L.dStatus), A.status2 = (walkdev::Status *)(dp + L.pStatus);
-  hipLaunchKernelGGL(k_track_walk, dim3(1), dim3(kWalkThreads), walk_lds_bytes(A.nq, A.nf), c->stream, A);
-  const int launched = hipGetLastError() == hipSuccess ? VSG_OK : VSG_ERR_HIP;
+  const int launched = walk_launch(c->stream, A);
   int rc = launched;
   if (rc == VSG_OK)
     rc = pose_chain_enqueue(F, c, S, A.edge_feat, A.edge_slot, (const int32_t *)A.status, Tcw, cam, inv_level_sigma2,
@@ -159,9 +169,91 @@ bool octaves_in_pyramid(const vsg_frame *F, int nlevels) {
 
 const int kAngleStride = (int)sizeof(KeyPointPOD);
 
+static_assert(sizeof(walkdev::Status) == VSG_WALK_ST_WORDS * 4, "vsg_debug_track_walk hands the status back as int32 words");
+
 }  // namespace
 
 extern "C" {
+
+// Test hook (include/vsg_orb_debug.h): k_track_walk alone on the caller's lists.
+int vsg_debug_track_walk(int form, int nq, int nf, int n_ent, const uint32_t *ent, const int32_t *off, const int32_t *cnt,
+                         int cap, const uint8_t *q_valid, const uint8_t *observed, const uint8_t *blocked_in,
+                         const float *q_angle, const float *t_angle, const int32_t *q_slot, const int32_t *slots_in,
+                         const uint8_t *slot_observed, int n_slots, int check_orientation, int min_matches, float nnratio,
+                         int32_t *train_match, uint8_t *train_blocked, int32_t *feat_slots, uint8_t *feat_observed,
+                         int32_t *edge_feat, int32_t *edge_slot, int32_t *status) {
+  if (!ent || !off || !cnt || !q_angle || !t_angle || !train_match || !train_blocked || !feat_slots || !feat_observed ||
+      !edge_feat || !edge_slot || !status)
+    return VSG_ERR_INVALID;
+  if (form != walkdev::kFormLast && form != walkdev::kFormLocal) return VSG_ERR_INVALID;
+  if (nq < 0 || nf < 0 || n_ent < 0 || cap < 0 || n_slots < 0 || nf > 32768) return VSG_ERR_INVALID;
+  if (slot_observed) {
+    for (int q = 0; q_slot && q < nq; q++)
+      if (q_slot[q] < -1 || q_slot[q] >= n_slots) return VSG_ERR_INVALID;
+    for (int i = 0; slots_in && i < nf; i++)
+      if (slots_in[i] < -1 || slots_in[i] >= n_slots) return VSG_ERR_INVALID;
+  }
+  if (walk_over_cap(nq, nf)) return VSG_ERR_CAPACITY;
+  // everything the kernel indexes has been bounded (the lists: list_ok, in the kernel); nothing has been enqueued
+  int device = 0, rc = VSG_OK;
+  if (hipGetDevice(&device) != hipSuccess) return VSG_ERR_NO_DEVICE;
+  ThreadCtx *c = thread_ctx(device, &rc);
+  if (!c) return rc;
+  const size_t Q = (size_t)nq, N = (size_t)nf;
+  // one block with the same layout in the pinned and in the device arena: the inputs, then what the kernel writes to
+  // device memory (the edge list and the status, as in the chain calls); behind it, pinned only, what it writes for the host
+  Stage s;
+  const size_t oEnt = s.add((size_t)n_ent * 4), oOff = s.add(Q * 4), oCnt = s.add(Q * 4), oValid = s.add(Q), oObs = s.add(Q),
+               oBlk = s.add(N), oQa = s.add(Q * 4), oTa = s.add(N * 4), oQs = s.add(Q * 4), oSi = s.add(N * 4),
+               oSo = s.add((size_t)n_slots);
+  const size_t oFeat = s.add(N * 4), oSlot = s.add(N * 4), oStatus = s.add(sizeof(walkdev::Status));
+  const size_t dev_total = s.total;
+  const size_t pTm = s.add(N * 4), pTb = s.add(N), pFs = s.add(N * 4), pFo = s.add(N);
+  const size_t pStatus = s.add(sizeof(walkdev::Status));
+  rc = ctx_reserve(c, s.total, dev_total);
+  if (rc != VSG_OK) return rc;
+  uint8_t *hp = c->h_pin, *dp = c->d_pin, *dv = c->d_buf;
+  auto put = [&](size_t at, const void *src, size_t bytes) {
+    if (src && bytes) memcpy(hp + at, src, bytes);
+  };
+  put(oEnt, ent, (size_t)n_ent * 4), put(oOff, off, Q * 4), put(oCnt, cnt, Q * 4), put(oValid, q_valid, Q);
+  put(oObs, observed, Q), put(oBlk, blocked_in, N), put(oQa, q_angle, Q * 4), put(oTa, t_angle, N * 4);
+  put(oQs, q_slot, Q * 4), put(oSi, slots_in, N * 4), put(oSo, slot_observed, (size_t)n_slots);
+  // the outputs start as the caller's arrays are, so that an entry the kernel leaves out shows as what the caller put there
+  put(oFeat, edge_feat, N * 4), put(oSlot, edge_slot, N * 4), put(pTm, train_match, N * 4), put(pTb, train_blocked, N);
+  put(pFs, feat_slots, N * 4), put(pFo, feat_observed, N);
+  memset(hp + oStatus, 0, sizeof(walkdev::Status)), memset(hp + pStatus, 0, sizeof(walkdev::Status));
+  walkdev::Args A;
+  memset(&A, 0, sizeof(A));
+  A.form = form, A.nq = nq, A.nf = nf;
+  A.inline_len = kWinInline, A.cap = cap, A.list_total = n_ent;
+  A.check_orientation = check_orientation != 0, A.min_matches = min_matches, A.nnratio = nnratio;
+  A.ent = (const uint32_t *)(dv + oEnt), A.off = (const int32_t *)(dv + oOff), A.cnt = (const int32_t *)(dv + oCnt);
+  A.q_valid = q_valid ? dv + oValid : nullptr, A.observed = observed ? dv + oObs : nullptr;
+  A.blocked_in = blocked_in ? dv + oBlk : nullptr;
+  A.q_angle = dv + oQa, A.t_angle = dv + oTa, A.q_angle_stride = A.t_angle_stride = 4;
+  A.q_slot = q_slot ? (const int32_t *)(dv + oQs) : nullptr, A.slots_in = slots_in ? (const int32_t *)(dv + oSi) : nullptr;
+  A.slot_observed = slot_observed ? dv + oSo : nullptr;
+  A.train_match = (int32_t *)(dp + pTm), A.train_blocked = dp + pTb, A.feat_slots = (int32_t *)(dp + pFs);
+  A.feat_observed = dp + pFo;
+  A.edge_feat = (int32_t *)(dv + oFeat), A.edge_slot = (int32_t *)(dv + oSlot);
+  A.status = (walkdev::Status *)(dv + oStatus), A.status2 = (walkdev::Status *)(dp + pStatus);
+  hipStream_t st = c->stream;
+  TRY_HIP(hipMemcpyAsync(dv, hp, dev_total, hipMemcpyHostToDevice, st));
+  bool failed = walk_launch(st, A) != VSG_OK;
+  if (!failed && hipMemcpyAsync(hp + oFeat, dv + oFeat, dev_total - oFeat, hipMemcpyDeviceToHost, st) != hipSuccess)
+    failed = true;
+  if (hipStreamSynchronize(st) != hipSuccess || failed) return VSG_ERR_HIP;
+  // the kernel writes its status twice, to device memory for the pose solve and to the pinned arena for the host
+  if (memcmp(hp + oStatus, hp + pStatus, sizeof(walkdev::Status)) != 0) return VSG_ERR_HIP;
+  memcpy(status, hp + pStatus, sizeof(walkdev::Status));
+  if (((const walkdev::Status *)(hp + pStatus))->flags & walkdev::kStOverflow) return VSG_OK;  // nothing else was written
+  if (nf > 0) {
+    memcpy(train_match, hp + pTm, N * 4), memcpy(train_blocked, hp + pTb, N), memcpy(feat_slots, hp + pFs, N * 4);
+    memcpy(feat_observed, hp + pFo, N), memcpy(edge_feat, hp + oFeat, N * 4), memcpy(edge_slot, hp + oSlot, N * 4);
+  }
+  return VSG_OK;
+}
 
 int vsg_frame_track_with_motion_model(vsg_frame *cur, vsg_frame *last, vsg_mappoints *mp, const int32_t *last_slots,
                                       const vsg_frame_pose *cur_pose, const vsg_frame_pose *last_pose, float mb, int mono,
@@ -178,7 +270,7 @@ int vsg_frame_track_with_motion_model(vsg_frame *cur, vsg_frame *last, vsg_mappo
   if (!store_view(mp, &S) || !octaves_in_pyramid(cur, nlevels)) return VSG_ERR_INVALID;
   // everything the kernels index has been bounded; nothing has been enqueued
   const int nf = cur->n, nq = last->n;
-  if (nf > 0 && nq > 0 && walk_lds_bytes(nq, nf) + kWalkStaticLds > kWalkLdsMax) return VSG_ERR_CAPACITY;
+  if (nf > 0 && nq > 0 && walk_over_cap(nq, nf)) return VSG_ERR_CAPACITY;
   // an error from here on leaves *res, the outputs and a pending hold as they were: R becomes *res on success only
   vsg_track_result R;
   memset(&R, 0, sizeof(R));
@@ -274,7 +366,7 @@ int vsg_frame_track_local_map(vsg_frame *F, vsg_mappoints *mp, int n, const int3
   for (int i = 0; i < nf; i++)
     if (feat_slots_in[i] >= S.capacity) return VSG_ERR_INVALID;
   // everything the kernels index has been bounded; nothing has been enqueued
-  if (nf > 0 && walk_lds_bytes(nq, nf) + kWalkStaticLds > kWalkLdsMax) return VSG_ERR_CAPACITY;
+  if (nf > 0 && walk_over_cap(nq, nf)) return VSG_ERR_CAPACITY;
   // an error from here on leaves *res, the outputs and a pending hold as they were: R becomes *res on success only
   vsg_track_local_result R;
   memset(&R, 0, sizeof(R));

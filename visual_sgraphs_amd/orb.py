@@ -113,6 +113,8 @@ EXPORTS = [
     "vsg_debug_last_launch_forms",
     # test hook: the query state of one keyframe of the resident KeyFrameDatabase
     "vsg_debug_kfdb_state",
+    # test hook: the chain calls' ordered walk (k_track_walk) alone, on lists the caller wrote
+    "vsg_debug_track_walk",
     # k_fast_cells' launch form: automatic / general
     "vsg_orb_set_fast_form",
 ]
@@ -572,6 +574,8 @@ def load_library():
     L.vsg_kfdb_detect_n_best_candidates.argtypes = [vp, u64, _i32p, _f64p, ci, _u64p, ci, i32, _i32p, ci, ci, _u64p,
                                                     _i32p, _u64p, _i32p]
     L.vsg_debug_kfdb_state.argtypes = [vp, u64, _u64p, _i32p, _f32p]
+    L.vsg_debug_track_walk.argtypes = [ci, ci, ci, ci, _u32p, _i32p, _i32p, ci, _u8p, _u8p, _u8p, _f32p, _f32p, _i32p, _i32p,
+                                       _u8p, ci, ci, ci, cf, _i32p, _u8p, _i32p, _u8p, _i32p, _i32p, _i32p]
     _lib = L
     return L
 
@@ -1475,6 +1479,69 @@ def debug_ba_reduced_solve(M, b):
     dp = C.POINTER(C.c_double)
     _check(load_library().vsg_debug_ba_reduced_solve(n, _p(M, dp), _p(b, dp), _p(x, dp), C.byref(ok)), "vsg_debug_ba_reduced_solve")
     return int(ok.value), x[:n]
+
+
+WALK_SENTINEL_I32, WALK_SENTINEL_U8 = 0x55555555, 0x55  # what debug_track_walk's outputs hold before the call
+# vsg_debug_track_walk's arguments by position (tests replace single ones)
+WALK_ARGS = ("form", "nq", "nf", "n_ent", "ent", "off", "cnt", "cap", "q_valid", "observed", "blocked_in", "q_angle", "t_angle",
+             "q_slot", "slots_in", "slot_observed", "n_slots", "check_orientation", "min_matches", "nnratio", "train_match",
+             "train_blocked", "feat_slots", "feat_observed", "edge_feat", "edge_slot", "status")
+
+
+def debug_track_walk_args(case, cap=None, min_matches=0, slot_observed=None):
+    """The argument list of vsg_debug_track_walk (in the order of WALK_ARGS) for one case dictionary of tests/walk_cases.py,
+    the outputs as arrays filled with sentinels, and the input arrays the pointers point into (keep them while calling).
+    As the host build of the walk (tests/_walkcore) takes a case: q_valid and the rotation filter belong to one form each."""
+    c = case
+    nq, nf, local = int(c["nq"]), int(c["nf"]), int(c["form"]) == 1
+    keep = []
+
+    def ptr(a, dtype, t):  # None stays NULL, an empty array gets an address
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        keep.append(a if a.size else np.zeros(1, dtype))
+        return _p(keep[-1], t)
+
+    i32 = lambda: np.full(max(nf, 1), WALK_SENTINEL_I32, np.int32)
+    u8 = lambda: np.full(max(nf, 1), WALK_SENTINEL_U8, np.uint8)
+    tm, tb, fs, fo, ef, es = i32(), u8(), i32(), u8(), i32(), i32()
+    status = np.full(36, WALK_SENTINEL_I32, np.int32)
+    out = dict(tm=tm[:max(nf, 0)], tb=tb[:max(nf, 0)], feat_slots=fs[:max(nf, 0)], feat_observed=fo[:max(nf, 0)],
+               edges_feat=ef[:max(nf, 0)], edges_slot=es[:max(nf, 0)], status=status)
+    args = [int(c["form"]), nq, nf, int(c["n_ent"]), ptr(c["ent"], np.uint32, _u32p), ptr(c["off"], np.int32, _i32p),
+            ptr(c["cnt"], np.int32, _i32p), 0x7FFFFFFF if cap is None else int(cap),
+            ptr(c["q_valid"] if local else None, np.uint8, _u8p), ptr(c["observed"], np.uint8, _u8p),
+            ptr(c["blocked"], np.uint8, _u8p), ptr(c["q_angle"], np.float32, _f32p), ptr(c["t_angle"], np.float32, _f32p),
+            ptr(c["q_slot"], np.int32, _i32p), ptr(c["slots_in"], np.int32, _i32p), ptr(slot_observed, np.uint8, _u8p),
+            0 if slot_observed is None else int(np.asarray(slot_observed).size), 0 if local else int(c["check"]),
+            int(min_matches), float(c["nnratio"]), _p(tm, _i32p), _p(tb, _u8p), _p(fs, _i32p), _p(fo, _u8p), _p(ef, _i32p),
+            _p(es, _i32p), _p(status, _i32p)]
+    return args, out, keep
+
+
+def debug_track_walk(case, cap=None, min_matches=0, slot_observed=None):
+    """include/vsg_orb_debug.h vsg_debug_track_walk: k_track_walk alone on one case dictionary of tests/walk_cases.py
+    (form, nq, nf, n_ent, ent, off, cnt, q_valid, observed, blocked, q_angle, t_angle, q_slot, slots_in, check, nnratio; an
+    absent array is None).  cap: the overflow area's entries (None: no bound, as the host build of the walk takes it);
+    slot_observed: the store's observed flags per slot, or None.  Every output starts as a sentinel (WALK_SENTINEL_*), so an
+    entry the kernel did not write shows: tm, tb, feat_slots, feat_observed and the raw edge arrays `edges_feat` /
+    `edges_slot` have nf entries, edge_feat / edge_slot are their first n_edges.  A refused call raises VsgError with the
+    outputs as they are after it in its `outputs`."""
+    args, out, keep = debug_track_walk_args(case, cap, min_matches, slot_observed)
+    rc = load_library().vsg_debug_track_walk(*args)
+    del keep
+    if rc < 0:
+        e = VsgError(rc, "vsg_debug_track_walk", load_library().vsg_last_error().decode(errors="replace"))
+        e.outputs = out
+        raise e
+    status = out["status"]
+    flags = int(status[2])
+    n_edges = int(status[1]) if not flags & 1 else 0
+    out.update(nmatches=int(status[0]), n_edges=n_edges, flags=flags, rounds=int(status[3]), overflow_sum=int(status[4]),
+               bins=status[5:35].copy(), edge_feat=out["edges_feat"][:n_edges].copy(),
+               edge_slot=out["edges_slot"][:n_edges].copy())
+    return out
 
 
 def sim3_max_err(level_sigma2, octave):
