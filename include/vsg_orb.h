@@ -1380,6 +1380,77 @@ int vsg_mappoints_global_bundle_adjustment(
     const volatile uint8_t *stop_flag,
     vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *included, double *chi2, vsg_global_ba_result *res);
 
+/* void Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
+ * (Optimizer.cc:2456-2734, the first overload; LoopClosing::CorrectLoop, LoopClosing.cc:1150) on resident map points: the
+ * Sim3 vertices (:2490-2525), the EdgeSim3 edges with the 7 x 7 identity as information, g2o's Levenberg loop with
+ * setUserLambdaInit(1e-16) and optimize(iterations) (:2469, :2684), and the correction of every listed map point through
+ * its reference keyframe (:2704-2731), in double, with the arithmetic of csrc/vsg_essential_graph.h, which a host build
+ * reproduces bit for bit.  The merge overload (:2736 ff.), OptimizeEssentialGraph4DoF and the inertial
+ * edges (:2662-2679) are NOT part of it: a caller with bImu keyframes keeps the reference routine.
+ *   - kf_Scw[k] = vScw of keyframe k (:2502-2511): CorrectedSim3's entry where the keyframe has one, else (GetPose(), 1.0);
+ *     the keyframes are those with !isBad() in ascending mnId.  kf_has_non_corrected[k] != 0: kf_non_corrected[k] is the
+ *     keyframe's entry of NonCorrectedSim3.  kf_fixed[k] != 0 for mnId == pMap->GetInitKFid() (:2514).
+ *   - edge e joins vertex 0 = edge_i[e] and vertex 1 = edge_j[e] (setVertex(0, nIDi), setVertex(1, nIDj)), in g2o's
+ *     insertion order; vsg::essential_graph_edges (vsg_orb_adaptor.hpp) builds the list with the reference's filters.
+ *     edge_loop[e] != 0: a "Set Loop edges" edge (:2529-2560), both sides of Sji = Sjw * Swi from vScw; 0: a "Set normal
+ *     edges" edge (:2563-2660), each side from NonCorrectedSim3 where the keyframe has an entry, else from vScw.  Two edges
+ *     between one pair of keyframes are legal and both count.
+ *   - fix_scale = bFixScale (VertexSim3Expmap::_fix_scale); iterations = 20 at :2684, within [1, 100].
+ *   - slots[i] = the store slot of map point i, point_ref[i] = nIDr of :2712-2721 as an index into the keyframes.  Each
+ *     listed slot's world_pos becomes float(correctedSwr.map(Srw.map(double(pos)))) (:2723-2728), also written to
+ *     world_pos_out[3 i ..] when that is not NULL; no other slot is touched.  mp may be NULL when n_points == 0: the pose
+ *     graph alone, on the calling thread's current device.  Follow with
+ *     vsg_mappoints_refresh_from_observations(VSG_REFRESH_NORMAL) for UpdateNormalAndDepth (:2730).
+ *   - kf_Scw_out[k] = VSim3->estimate() (:2696): a keyframe that is not fixed and has at least one edge gets its optimised
+ *     estimate, NaN canonical, every other keyframe its input's bytes (g2o drops a vertex without an edge).  The SE3 recovery
+ *     of :2700 (t / s, the float casts) stays with the caller.  chi2[e] (may be NULL) = the edge's chi2() after the
+ *     computeActiveErrors of :2685.
+ *   - res->ran = 0: no edge, or no edge at a keyframe that is not fixed: nothing is enqueued, kf_Scw_out holds the inputs,
+ *     and the store, world_pos_out and chi2 are untouched (the reference maps every point through Srw and its own inverse
+ *     there: a rounding of the float position at most).  stop_reason: 0 the iterations are done, 1 Terminate (ten rejected
+ *     trials, or rho == 0), 2 _nBad >= 3; there is no stop flag in this routine.
+ * Checked before anything is enqueued (an error writes nothing and leaves no kernel behind), VSG_ERR_INVALID: a negative
+ * count; a NULL kf_Scw_out or res; with n_kf > 0 a NULL kf_Scw, kf_has_non_corrected or kf_fixed, or a NULL
+ * kf_non_corrected with an entry flagged; with n_edges > 0 a NULL edge_i, edge_j or edge_loop; with n_points > 0 a NULL mp,
+ * slots or point_ref; fix_scale outside {0, 1}; iterations outside [1, 100]; an edge index outside [0, n_kf), or
+ * edge_i[e] == edge_j[e]; a slot outside [0, capacity), or listed twice; a point_ref outside [0, n_kf); an input Sim3 (an
+ * entry of kf_Scw, or a flagged entry of kf_non_corrected) that is not finite or whose scale is <= 0.  VSG_ERR_UNSUPPORTED:
+ * more than 438 keyframes that are not fixed and have an edge.  THE CAP: g2o solves this system sparsely; here it is a dense
+ * LDL^T of 7 rows per such keyframe through the chain of kernels the global BA's reduced solve uses, tested up to 3072
+ * rows (7 x 438 = 3066, a matrix of 75 MB in the calling thread's device arena).  Real maps exceed that: their callers keep
+ * the reference routine until a sparse solve exists.  The call waits for its stream before it
+ * returns, on an error too. */
+typedef struct vsg_essential_graph_result {
+  int32_t ran;              /* 0: nothing to optimise */
+  int32_t n_opt_kf, n_fixed_kf, n_kf, n_edges, n_points;
+  int32_t iterations_run, trials_run, stop_reason;
+  int32_t pad;
+  double lambda, chi2_initial, chi2_final;
+} vsg_essential_graph_result;
+int vsg_mappoints_optimize_essential_graph(
+    vsg_mappoints *mp,
+    int n_kf, const vsg_sim3d *kf_Scw,
+    const vsg_sim3d *kf_non_corrected, const uint8_t *kf_has_non_corrected, const uint8_t *kf_fixed,
+    int n_edges, const int32_t *edge_i, const int32_t *edge_j, const uint8_t *edge_loop,
+    int fix_scale, int iterations,
+    int n_points, const int32_t *slots, const int32_t *point_ref,
+    vsg_sim3d *kf_Scw_out, float *world_pos_out, double *chi2,
+    vsg_essential_graph_result *res);
+
+/* The point correction of LoopClosing::CorrectLoop (LoopClosing.cc:1060-1064: eigCorrectedP3Dw =
+ * g2oCorrectedSwi.map(g2oSiw.map(P3Dw))) and of Optimizer::OptimizeEssentialGraph (Optimizer.cc:2723-2728) on resident map
+ * points: one kernel, two callers.  The world_pos of slot slots[i] becomes float(S_to_inverse[r].map(S_from[r].map(
+ * double(pos)))) with r = point_ref[i], also written to world_pos_out[3 i ..] when that is not NULL; no other slot is
+ * touched.  In CorrectLoop S_from[r] = g2oSiw of connected keyframe r (NonCorrectedSim3) and S_to_inverse[r] =
+ * g2oCorrectedSiw.inverse(); mnCorrectedByKF / mnCorrectedReference stay with the caller.  Follow with
+ * vsg_mappoints_refresh_from_observations(VSG_REFRESH_NORMAL) (UpdateNormalAndDepth, :1067).  n_points == 0 returns VSG_OK
+ * and enqueues nothing.  Checked before anything is enqueued (an error writes nothing), VSG_ERR_INVALID: a NULL mp; a negative
+ * count; with n_points > 0 a NULL slots, point_ref, S_from or S_to_inverse; a slot outside [0, capacity), or listed twice;
+ * a point_ref outside [0, n_ref); an entry of S_from or S_to_inverse that is not finite or whose scale is <= 0. */
+int vsg_mappoints_correct_sim3(
+    vsg_mappoints *mp, int n_points, const int32_t *slots, const int32_t *point_ref,
+    int n_ref, const vsg_sim3d *S_from, const vsg_sim3d *S_to_inverse, float *world_pos_out);
+
 /* bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, T21, vP3D, vbTriangulated)
  * (TwoViewReconstruction.cc:40-129; Tracking::MonocularInitialization, Tracking.cc:2568, through
  * Pinhole::ReconstructWithTwoViews, Pinhole.cpp:91-101): the monocular initialisation behind

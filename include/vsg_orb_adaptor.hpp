@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstring>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -567,6 +568,86 @@ struct GlobalBAResult {
   vsg_global_ba_result res;
 };
 
+// What vsg::ResidentMapPoints::OptimizeEssentialGraph returns: VSim3->estimate() per keyframe (a fixed keyframe, or one
+// without an edge: its input), the corrected float position per listed point (also written into its slot), chi2 per edge
+// and the counters of vsg_essential_graph_result.
+struct EssentialGraphResult {
+  std::vector<vsg_sim3d> kfScw;
+  std::vector<float> worldPos;
+  std::vector<double> chi2;
+  vsg_essential_graph_result res;
+};
+
+// The edge list of Optimizer::OptimizeEssentialGraph (Optimizer.cc:2529-2660) in the reference's insertion order, host only.
+struct EssentialGraphEdges {
+  std::vector<int32_t> i, j;  // vertex 0 (nIDi), vertex 1 (nIDj)
+  std::vector<uint8_t> loop;  // 1: a "Set Loop edges" edge
+};
+// Keyframes are the map's !isBad() keyframes in ascending mnId and are named by their index in that order, so `index <`
+// is `mnId <`; a pointer to a bad (or null) keyframe is the index -1.  Per keyframe k: parent[k] = GetParent(); its
+// GetLoopEdges() are loopIdx[loopOff[k] .. loopOff[k + 1]), its children (hasChild) childIdx[childOff[k] ..), its
+// GetCovisiblesByWeight(100) in that vector's order covIdx[covOff[k] ..).  LoopConnections in the map's iteration order:
+// entry m is keyframe lcKf[m] with the connections lcIdx[lcOff[m] .. lcOff[m + 1]) in the set's order and
+// lcWeight = pKF->GetWeight(connection).  curKF / loopKF = pCurKF / pLoopKF.  The filters are the reference's: :2542
+// (minFeat, except the pair current -> loop), :2608 (mnId <), :2634-2639 (not the parent, not a child, not bad, mnId <, not
+// in sInsertedEdges).  Two edges between one pair of keyframes are legal and both are listed (a loop connection and a
+// spanning-tree edge).  The walk over the keyframes is in index order; the reference's is GetAllKeyFrames()' (the map's
+// set, by address), which changes the order of the sums and nothing else.
+inline EssentialGraphEdges essential_graph_edges(int nKF, const std::vector<int32_t> &parent, const std::vector<int32_t> &loopOff,
+                                                 const std::vector<int32_t> &loopIdx, const std::vector<int32_t> &childOff,
+                                                 const std::vector<int32_t> &childIdx, const std::vector<int32_t> &covOff,
+                                                 const std::vector<int32_t> &covIdx, const std::vector<int32_t> &lcKf,
+                                                 const std::vector<int32_t> &lcOff, const std::vector<int32_t> &lcIdx,
+                                                 const std::vector<int32_t> &lcWeight, int curKF, int loopKF, int minFeat = 100) {
+  const size_t K = (size_t)(nKF < 0 ? 0 : nKF), M = lcKf.size();
+  auto csr_ok = [](const std::vector<int32_t> &off, size_t rows, size_t entries) {
+    if (off.size() != rows + 1 || off[0] != 0 || (size_t)off[rows] != entries) return false;
+    for (size_t r = 0; r < rows; ++r)
+      if (off[r + 1] < off[r]) return false;
+    return true;
+  };
+  if (parent.size() != K || !csr_ok(loopOff, K, loopIdx.size()) || !csr_ok(childOff, K, childIdx.size()) ||
+      !csr_ok(covOff, K, covIdx.size()) || !csr_ok(lcOff, M, lcIdx.size()) || lcWeight.size() != lcIdx.size())
+    throw std::runtime_error("essential_graph_edges: the arrays' sizes do not match");
+  auto in_range = [K](int32_t v) { return v >= -1 && (size_t)(v + 1) <= K; };
+  for (const std::vector<int32_t> *v : {&parent, &loopIdx, &childIdx, &covIdx, &lcIdx})
+    for (int32_t x : *v)
+      if (!in_range(x)) throw std::runtime_error("essential_graph_edges: a keyframe index is out of range");
+  for (int32_t x : lcKf)
+    if (x < 0 || (size_t)x >= K) throw std::runtime_error("essential_graph_edges: a keyframe index is out of range");
+  EssentialGraphEdges E;
+  auto push = [&E](int i, int j, int loop) { E.i.push_back(i), E.j.push_back(j), E.loop.push_back((uint8_t)loop); };
+  std::set<std::pair<int32_t, int32_t>> inserted;  // sInsertedEdges
+  for (size_t m = 0; m < M; ++m) {
+    const int32_t i = lcKf[m];
+    for (int32_t x = lcOff[m]; x < lcOff[m + 1]; ++x) {
+      const int32_t j = lcIdx[(size_t)x];
+      if (j < 0 || j == i) continue;  // a bad keyframe has no vertex
+      if ((i != curKF || j != loopKF) && lcWeight[(size_t)x] < minFeat) continue;
+      push(i, j, 1);
+      inserted.insert(std::make_pair(std::min(i, j), std::max(i, j)));
+    }
+  }
+  for (int32_t i = 0; i < (int32_t)K; ++i) {
+    const int32_t par = parent[(size_t)i];
+    if (par >= 0 && par != i) push(i, par, 0);  // spanning tree
+    for (int32_t x = loopOff[(size_t)i]; x < loopOff[(size_t)i + 1]; ++x) {
+      const int32_t l = loopIdx[(size_t)x];
+      if (l >= 0 && l < i) push(i, l, 0);
+    }
+    for (int32_t x = covOff[(size_t)i]; x < covOff[(size_t)i + 1]; ++x) {
+      const int32_t n = covIdx[(size_t)x];
+      if (n < 0 || n == par) continue;
+      bool child = false;
+      for (int32_t y = childOff[(size_t)i]; y < childOff[(size_t)i + 1]; ++y) child = child || childIdx[(size_t)y] == n;
+      if (child || !(n < i)) continue;
+      if (inserted.count(std::make_pair(std::min(i, n), std::max(i, n)))) continue;
+      push(i, n, 0);
+    }
+  }
+  return E;
+}
+
 class ResidentMapPoints {
  public:
   explicit ResidentMapPoints(int capacity, int device = 0) {
@@ -685,6 +766,50 @@ class ResidentMapPoints {
               "vsg_mappoints_read");
     }
     return r;
+  }
+  // Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
+  // (Optimizer.cc:2456-2734) on the device (vsg_mappoints_optimize_essential_graph).  kfScw = vScw per !isBad() keyframe in
+  // ascending mnId (CorrectedSim3's entry where present, else (GetPose(), 1.0)); kfNonCorrected / kfHasNonCorrected =
+  // NonCorrectedSim3; kfFixed != 0 for mnId == GetInitKFid(); edges = essential_graph_edges(...); slots / pointRef = every
+  // !isBad() map point's slot and nIDr (:2712-2721) as a keyframe index.  The corrected positions are written into the
+  // slots; follow with Refresh(..., VSG_REFRESH_NORMAL).  The caller SetPose()s from kfScw (t / s, :2700).  Inertial edges
+  // are not part of it, and at most 438 keyframes that are not fixed may have an edge (a dense solve): beyond either, keep the
+  // reference routine.
+  EssentialGraphResult OptimizeEssentialGraph(const std::vector<vsg_sim3d> &kfScw, const std::vector<vsg_sim3d> &kfNonCorrected,
+                                              const std::vector<uint8_t> &kfHasNonCorrected, const std::vector<uint8_t> &kfFixed,
+                                              const EssentialGraphEdges &edges, bool bFixScale, const std::vector<int32_t> &slots,
+                                              const std::vector<int32_t> &pointRef, int iterations = 20) {
+    const size_t K = kfScw.size(), E = edges.i.size(), n = slots.size();
+    if (kfNonCorrected.size() != K || kfHasNonCorrected.size() != K || kfFixed.size() != K || edges.j.size() != E ||
+        edges.loop.size() != E || pointRef.size() != n)
+      throw std::runtime_error("ResidentMapPoints::OptimizeEssentialGraph: the arrays' sizes do not match");
+    EssentialGraphResult r;
+    r.kfScw.resize(K), r.worldPos.assign(3 * n, 0.0f), r.chi2.assign(E, 0.0);
+    vsg_sim3d none_kf;
+    check(vsg_mappoints_optimize_essential_graph(mp_, (int)K, kfScw.data(), kfNonCorrected.data(), kfHasNonCorrected.data(),
+                                                 kfFixed.data(), (int)E, edges.i.data(), edges.j.data(), edges.loop.data(),
+                                                 bFixScale ? 1 : 0, iterations, (int)n, slots.data(), pointRef.data(),
+                                                 K ? r.kfScw.data() : &none_kf, n ? r.worldPos.data() : nullptr,
+                                                 E ? r.chi2.data() : nullptr, &r.res),
+          "vsg_mappoints_optimize_essential_graph");
+    if (!r.res.ran && n)  // nothing to optimise: the store was not written, the positions are what the slots hold
+      check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+            "vsg_mappoints_read");
+    return r;
+  }
+  // The point correction of LoopClosing::CorrectLoop (LoopClosing.cc:1060-1064) on the device (vsg_mappoints_correct_sim3):
+  // slot slots[i] becomes float(SToInverse[r].map(SFrom[r].map(double(pos)))), r = pointRef[i]; there SFrom = g2oSiw and
+  // SToInverse = g2oCorrectedSiw.inverse() of connected keyframe r.  Returns the new positions; follow with
+  // Refresh(..., VSG_REFRESH_NORMAL).
+  std::vector<float> CorrectSim3(const std::vector<int32_t> &slots, const std::vector<int32_t> &pointRef,
+                                 const std::vector<vsg_sim3d> &SFrom, const std::vector<vsg_sim3d> &SToInverse) {
+    if (pointRef.size() != slots.size() || SFrom.size() != SToInverse.size())
+      throw std::runtime_error("ResidentMapPoints::CorrectSim3: the arrays' sizes do not match");
+    std::vector<float> out(3 * slots.size(), 0.0f);
+    check(vsg_mappoints_correct_sim3(mp_, (int)slots.size(), slots.data(), pointRef.data(), (int)SFrom.size(), SFrom.data(),
+                                     SToInverse.data(), slots.empty() ? nullptr : out.data()),
+          "vsg_mappoints_correct_sim3");
+    return out;
   }
   vsg_mappoints *handle() const { return mp_; }
 

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "vsg_essential_graph.h"
 #include "vsg_global_ba.h"
 #include "vsg_local_ba.h"
 #include "vsg_observations.h"
@@ -387,6 +388,27 @@ int gb_host_side(int capacity, int n_points, const int32_t *slots, const float *
   run.run(nullptr);
   run.outputs(kf_Tcw, pos, kf_Tcw_out, pos_out, chi2);
   gb::fill_result(res, run.T, &run.S);
+  return VSG_OK;
+}
+
+// essgraph: the host build of csrc/vsg_essential_graph.h on the positions vsg_mappoints_read returned (pos: 3 floats per
+// LISTED point); the caller follows with vsg_mappoints_update
+int eg_host_side(int capacity, int n_kf, const vsg_sim3d *kf_Scw, const vsg_sim3d *kf_nonc, const uint8_t *kf_has_nonc,
+                 const uint8_t *kf_fixed, int n_edges, const int32_t *edge_i, const int32_t *edge_j, const uint8_t *edge_loop,
+                 int fix_scale, int iterations, int n_points, const int32_t *slots, const int32_t *point_ref, const float *pos,
+                 vsg_sim3d *kf_Scw_out, float *pos_out, double *chi2, vsg_essential_graph_result *res) {
+  namespace eg = vsg::eg;
+  static thread_local eg::HostRun run;  // its vectors keep their capacity from call to call, as the library's arenas do
+  int ran = 0;
+  run.accepted.clear();
+  const int rc = eg::check_and_build(n_kf, kf_Scw, kf_nonc, kf_has_nonc, kf_fixed, n_edges, edge_i, edge_j, edge_loop, fix_scale,
+                                     iterations, n_points, slots, point_ref, capacity, kf_Scw_out, res, &run.T, &ran);
+  if (rc != VSG_OK || !ran) return rc != VSG_OK ? rc : -100;
+  run.setup(kf_Scw, kf_nonc, kf_has_nonc, fix_scale, iterations);
+  run.run();
+  run.outputs(kf_Scw, kf_Scw_out, chi2);
+  run.correct(kf_Scw, n_points, point_ref, pos, pos_out);
+  eg::fill_result(res, run.T, &run.S);
   return VSG_OK;
 }
 }  // extern "C"

@@ -82,12 +82,20 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
             `child globalba <calls> <size,size>` runs the listed sizes alone; `globalba trace [size]` runs the 100-keyframe problem
             (or the given size) through the new call and, up to 129 keyframes, through the local call, for rocprofv3 --kernel-trace --stats with VSG_NO_OVERLAP=1
 
+  essgraph  Optimizer::OptimizeEssentialGraph (the pose graph of loop closing) on resident map points: 50 / 200 / 438 keyframes, one
+            fixed, about 6 edges per keyframe and one loop edge, 10 map points per keyframe, fix_scale 0 and 1 (a size is
+            "<keyframes>:<fix_scale>"), 3 iterations.  Calls per size: 200 / 50 / 5
+            A  = vsg_mappoints_read + the host build of csrc/vsg_essential_graph.h on one thread (NOT g2o: the header's own
+                 arithmetic, numeric Jacobian and DENSE solve included) + vsg_mappoints_update
+            B  = vsg_mappoints_optimize_essential_graph;  A2 / B2 = both again.  Every call asserts all four equal bit for bit
+            `essgraph trace [size]` runs the 200-keyframe problem three times, for rocprofv3 --kernel-trace --stats with VSG_NO_OVERLAP=1
+
   track / track_local   Tracking's two per-frame steps as chain calls (vsg_frame_track_with_motion_model,
             vsg_frame_track_local_map), 1000 / 2000 / 4000 points, against the caller-side path on the SAME library: the two
             existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
             carries them.  Both write into profiles/track_chain_latency.json, one key each
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|globalba|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|globalba|essgraph|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -117,7 +125,7 @@ def host_side(orb):
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
            csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
-           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_global_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h"]
+           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_global_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h", csrc / "vsg_essential_graph.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-pthread", "-I", str(csrc), "-o",
                                str(so), str(src[0])])
@@ -147,6 +155,8 @@ def host_side(orb):
     H.gb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
                                C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
                                C.POINTER(C.c_double), C.c_void_p]
+    H.eg_host_side.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, _u8p, _u8p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int,
+                               C.c_int, _i32p, _i32p, _f32p, C.c_void_p, _f32p, C.POINTER(C.c_double), C.c_void_p]
     H.ml_host_side.argtypes = [C.c_int, _i32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, _i32p,
                                _u8p, C.c_void_p]
     H.tv_host_side.argtypes = [_f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_void_p, C.c_int, _i32p, C.c_int, C.c_void_p, _u8p, _f32p]
@@ -1197,8 +1207,84 @@ class TrackLocal(Chain, Local):
                     entry_slots=int((self.entry >= 0).sum()))
 
 
+class EssGraph:
+    """Optimizer::OptimizeEssentialGraph on resident map points: a size is "<keyframes>:<fix_scale>".  One keyframe is fixed,
+    every keyframe is joined to its five predecessors on the chain (about 6 edges per keyframe) and one loop edge closes the
+    chain; the last three keyframes carry CorrectedSim3 (scale drift 1.3 without fix_scale, 1.0 with it); 10 map points per
+    keyframe.  ITERATIONS = 3, not the reference's 20: the host side's dense solve takes seconds per trial at 438 keyframes, and
+    three iterations are where the loop converges on these scenes (tests/eg_scenes.py)."""
+    SIZES = ("50:0", "50:1", "200:0", "200:1", "438:0", "438:1")
+    TH, DEST = 0.0, "essential_graph_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2")
+    CALLS = {"50:0": (20, 200), "50:1": (20, 200), "200:0": (3, 50), "200:1": (3, 50), "438:0": (1, 5), "438:1": (1, 5)}
+    ITERATIONS = 3
+
+    def __init__(self, orb, fr, size):
+        import eg_scenes as es
+        nk, fix = (int(v) for v in size.split(":"))
+        s = es.sized(8000 + nk, nk - 1, covis=5, scale=1.0 if fix else 1.3, fix_scale=fix, iterations=self.ITERATIONS, points_per_kf=10)
+        self.orb, self.fix, self.K = orb, fix, nk
+        f64 = np.float64
+        self.Scw, self.nonc = np.ascontiguousarray(s["Scw"], f64), np.ascontiguousarray(s["nonc"], f64)
+        self.has, self.fixed = np.ascontiguousarray(s["has"], np.uint8), np.ascontiguousarray(s["fixed"], np.uint8)
+        self.ei = np.ascontiguousarray(np.append(s["ei"], nk - 1), np.int32)  # the loop edge: current -> keyframe 1
+        self.ej = np.ascontiguousarray(np.append(s["ej"], 1), np.int32)
+        self.el = np.ascontiguousarray(np.append(s["eloop"], 1), np.uint8)
+        self.slots, self.ref = np.ascontiguousarray(s["slots"], np.int32), np.ascontiguousarray(s["point_ref"], np.int32)
+        self.cap, self.npts, self.E = int(s["capacity"]), len(self.slots), len(self.ei)
+        self.pos0 = np.ascontiguousarray(s["store_pos"], np.float32)
+        self.all = np.arange(self.cap, dtype=np.int32)
+        self.mp = orb.MapPoints(self.cap)
+        self.Xw, self.pos_out = np.zeros((self.npts, 3), np.float32), np.zeros((self.npts, 3), np.float32)
+        self.kf_out, self.chi2, self.res = np.zeros((nk, 8), f64), np.zeros(self.E, f64), orb.EssentialGraphResult()
+
+    def pose_at(self, k):
+        return None
+
+    def reset(self):
+        self.mp.update(self.all, world_pos=self.pos0)
+        self.kf_out[:], self.pos_out[:], self.chi2[:] = 0, 0, -1.0
+        C.memset(C.byref(self.res), 0, C.sizeof(self.res))
+
+    def run(self, name, L, H, P):
+        f64p, sp = C.POINTER(C.c_double), C.POINTER(self.orb.Sim3d)
+        if name.startswith("B"):
+            return L.vsg_mappoints_optimize_essential_graph(
+                self.mp.handle, self.K, C.cast(self.Scw.ctypes.data, sp), C.cast(self.nonc.ctypes.data, sp), p(self.has, _u8p),
+                p(self.fixed, _u8p), self.E, p(self.ei, _i32p), p(self.ej, _i32p), p(self.el, _u8p), self.fix, self.ITERATIONS, self.npts,
+                p(self.slots, _i32p), p(self.ref, _i32p), C.cast(self.kf_out.ctypes.data, sp), p(self.pos_out, _f32p), p(self.chi2, f64p),
+                C.byref(self.res))
+        rc = L.vsg_mappoints_read(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), None, None, None, None, None)
+        if rc != 0:
+            return rc
+        rc = H.eg_host_side(self.cap, self.K, self.Scw.ctypes.data, self.nonc.ctypes.data, p(self.has, _u8p), p(self.fixed, _u8p), self.E,
+                            p(self.ei, _i32p), p(self.ej, _i32p), p(self.el, _u8p), self.fix, self.ITERATIONS, self.npts,
+                            p(self.slots, _i32p), p(self.ref, _i32p), p(self.Xw, _f32p), self.kf_out.ctypes.data, p(self.pos_out, _f32p),
+                            p(self.chi2, f64p), C.addressof(self.res))
+        if rc != 0:
+            return rc
+        return L.vsg_mappoints_update(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.pos_out, _f32p), None, None, None,
+                                      None, None)
+
+    def result(self, name, r):
+        after = self.mp.read(self.all)["world_pos"]
+        return (r, self.kf_out.view(np.uint64).copy(), self.pos_out.copy(), after.reshape(-1).copy(), self.chi2.view(np.uint64).copy(),
+                np.frombuffer(bytes(self.res), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.EssentialGraphResult.from_buffer_copy(last["B"][5].tobytes())
+        return {"keyframes": self.K, "optimised_keyframes": int(r.n_opt_kf), "rows": 7 * int(r.n_opt_kf), "edges": self.E,
+                "points": self.npts, "fix_scale": self.fix, "iterations": self.ITERATIONS, "iterations_run": int(r.iterations_run),
+                "trials_run": int(r.trials_run), "stop_reason": int(r.stop_reason), "chi2_initial": float(r.chi2_initial),
+                "chi2_final": float(r.chi2_final), "every_call_equals_the_host_build": True,
+                "host_side": "A = vsg_mappoints_read + the host build of csrc/vsg_essential_graph.h on one thread "
+                             "(tools/resident_points_cpu.cpp) + vsg_mappoints_update; it is THIS header's build and NOT g2o (no "
+                             "Eigen here).  Its DENSE solve is dearer than g2o's sparse one, which flatters the device at the "
+                             "larger sizes; B = vsg_mappoints_optimize_essential_graph"}
+
+
 CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3, "mlpnp": Mlpnp,
-         "sim3opt": Sim3Opt, "localba": LocalBA, "globalba": GlobalBA, "twoview": TwoView}
+         "sim3opt": Sim3Opt, "localba": LocalBA, "globalba": GlobalBA, "twoview": TwoView, "essgraph": EssGraph}
 
 
 def child(case, calls, sizes=None):
@@ -1255,6 +1341,14 @@ def trace(case="local", size=None):
             c.reset()
             assert c.run("B", L, None, None) == 0
         print({"size": "20:3000", "calls": 5, "iterations_run": int(c.res.iterations_run), "trials_run": int(c.res.trials_run)})
+        return
+    if case == "essgraph":
+        L, c = orb.load_library(), EssGraph(orb, fr, size or "200:0")
+        for k in range(3):
+            c.reset()
+            assert c.run("B", L, None, None) == 0
+        print({"size": size or "200:0", "calls": 3, "iterations_run": int(c.res.iterations_run), "trials_run": int(c.res.trials_run),
+               "edges": c.E, "rows": 7 * int(c.res.n_opt_kf)})
         return
     if case == "globalba":  # a loop-closing problem through the new call and, where it accepts it, through the local call
         L, c = orb.load_library(), GlobalBA(orb, fr, size or "100")

@@ -103,6 +103,9 @@ EXPORTS = [
     # points (its test hooks, vsg_debug_ba_reduced_solve and vsg_debug_ba_solver_geometry of
     # include/vsg_orb_debug_global_ba.h, are bound below but are no part of the two headers this list mirrors)
     "vsg_mappoints_global_bundle_adjustment",
+    # Optimizer::OptimizeEssentialGraph (the pose graph of loop closing) and the Sim3 point correction it shares with
+    # LoopClosing::CorrectLoop, on resident map points
+    "vsg_mappoints_optimize_essential_graph", "vsg_mappoints_correct_sim3",
     # TwoViewReconstruction::Reconstruct (the monocular initialisation) on two resident frames or on caller arrays, the
     # reference's default parameters and the host-side draw of the minimal sets
     "vsg_frame_two_view_reconstruct", "vsg_two_view_reconstruct", "vsg_two_view_default_params", "vsg_two_view_draw_sets",
@@ -252,6 +255,17 @@ GLOBAL_BA_RESULT_DOUBLES = LOCAL_BA_RESULT_DOUBLES
 class GlobalBaResult(C.Structure):
     """include/vsg_orb.h vsg_global_ba_result: the local call's counters without n_erase."""
     _fields_ = [(k, C.c_int32) for k in GLOBAL_BA_RESULT_INTS] + [(k, C.c_double) for k in GLOBAL_BA_RESULT_DOUBLES]
+
+
+ESSENTIAL_GRAPH_RESULT_INTS = ("ran", "n_opt_kf", "n_fixed_kf", "n_kf", "n_edges", "n_points", "iterations_run", "trials_run",
+                               "stop_reason", "pad")
+ESSENTIAL_GRAPH_RESULT_DOUBLES = LOCAL_BA_RESULT_DOUBLES
+ESSENTIAL_GRAPH_MAX_OPT_KF = 438  # 7 rows each: 3066 <= 3072, the dense solve's tested range
+
+
+class EssentialGraphResult(C.Structure):
+    """include/vsg_orb.h vsg_essential_graph_result."""
+    _fields_ = [(k, C.c_int32) for k in ESSENTIAL_GRAPH_RESULT_INTS] + [(k, C.c_double) for k in ESSENTIAL_GRAPH_RESULT_DOUBLES]
 
 
 class TwoViewParams(C.Structure):
@@ -559,6 +573,10 @@ def load_library():
     L.vsg_mappoints_global_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
                                                          _u8p, C.POINTER(BaCamera), _f32p, ci, ci, ci, ci, _u8p,
                                                          C.POINTER(PoseSE3d), _f32p, _u8p, _f64p, C.POINTER(GlobalBaResult)]
+    L.vsg_mappoints_optimize_essential_graph.argtypes = [vp, ci, C.POINTER(Sim3d), C.POINTER(Sim3d), _u8p, _u8p, ci, _i32p, _i32p,
+                                                         _u8p, ci, ci, ci, _i32p, _i32p, C.POINTER(Sim3d), _f32p, _f64p,
+                                                         C.POINTER(EssentialGraphResult)]
+    L.vsg_mappoints_correct_sim3.argtypes = [vp, ci, _i32p, _i32p, ci, C.POINTER(Sim3d), C.POINTER(Sim3d), _f32p]
     L.vsg_debug_ba_reduced_solve.argtypes = [ci, _f64p, _f64p, _f64p, _i32p]
     L.vsg_debug_ba_solver_geometry.argtypes = [_i32p, _i32p]
     L.vsg_kfdb_create.argtypes = [vp, C.POINTER(vp)]
@@ -578,6 +596,40 @@ def load_library():
                                        _u8p, ci, ci, ci, cf, _i32p, _u8p, _i32p, _u8p, _i32p, _i32p, _i32p]
     _lib = L
     return L
+
+
+def optimize_essential_graph(L, store_handle, kf_Scw, kf_non_corrected, kf_has_non_corrected, kf_fixed, edge_i, edge_j, edge_loop,
+                             fix_scale, slots=(), point_ref=(), iterations=20):
+    """Optimizer::OptimizeEssentialGraph, first overload (Optimizer.cc:2456-2734; vsg_mappoints_optimize_essential_graph).
+    kf_Scw (K, 8) float64 = vScw per keyframe in ascending mnId (q x y z w, t, s): CorrectedSim3 where present, else
+    (GetPose(), 1); kf_non_corrected (K, 8) with kf_has_non_corrected (K) = NonCorrectedSim3; kf_fixed (K) != 0 for the map's
+    initial keyframe.  Edge e joins vertex 0 = edge_i[e] and vertex 1 = edge_j[e]; edge_loop[e] != 0 for a loop-connection
+    edge.  slots / point_ref: the map points to correct and nIDr as a keyframe index; store_handle None with no points runs
+    the pose graph alone.  Returns dict(kf_Scw (K, 8), world_pos (n, 3) float32, chi2 per edge and the fields of
+    vsg_essential_graph_result).  At most 438 keyframes that are not fixed and have an edge (a dense solve)."""
+    S = np.ascontiguousarray(kf_Scw, np.float64).reshape(-1, 8)
+    K = S.shape[0]
+    N = np.ascontiguousarray(kf_non_corrected, np.float64).reshape(-1, 8)
+    has, fx = _u8(kf_has_non_corrected), _u8(kf_fixed)
+    ei, ej, el = _i32(edge_i), _i32(edge_j), _u8(edge_loop)
+    E, n = int(np.asarray(edge_i).size), int(np.asarray(slots).size)
+    sl, ref = _i32(slots), _i32(point_ref)
+    if N.shape[0] != K or has.size != K or fx.size != K or np.asarray(edge_j).size != E or np.asarray(edge_loop).size != E or \
+            np.asarray(point_ref).size != n:
+        raise ValueError("the keyframe, edge or point arrays differ in length")
+    out = {"kf_Scw": np.zeros((max(K, 1), 8), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
+           "chi2": np.zeros(max(E, 1), np.float64)}
+    res = EssentialGraphResult()
+    f64p = C.POINTER(C.c_double)
+    _check(L.vsg_mappoints_optimize_essential_graph(
+        store_handle, K, C.cast(_p(S, f64p), C.POINTER(Sim3d)), C.cast(_p(N, f64p), C.POINTER(Sim3d)), _p(has, _u8p), _p(fx, _u8p),
+        E, _p(ei, _i32p), _p(ej, _i32p), _p(el, _u8p), int(bool(fix_scale)), int(iterations), n, _p(sl, _i32p), _p(ref, _i32p),
+        C.cast(_p(out["kf_Scw"], f64p), C.POINTER(Sim3d)), _p(out["world_pos"], _f32p), _p(out["chi2"], f64p), C.byref(res)),
+        "vsg_mappoints_optimize_essential_graph")
+    got = {"kf_Scw": out["kf_Scw"][:K], "world_pos": out["world_pos"][:n], "chi2": out["chi2"][:E]}
+    got.update({k: int(getattr(res, k)) for k in ESSENTIAL_GRAPH_RESULT_INTS if k != "pad"})
+    got.update({k: float(getattr(res, k)) for k in ESSENTIAL_GRAPH_RESULT_DOUBLES})
+    return got
 
 
 def _check(rc, where):
@@ -1432,6 +1484,30 @@ class MapPoints:
         got.update({k: int(getattr(res, k)) for k in GLOBAL_BA_RESULT_INTS})
         got.update({k: float(getattr(res, k)) for k in GLOBAL_BA_RESULT_DOUBLES})
         return got
+
+    def OptimizeEssentialGraph(self, kf_Scw, kf_non_corrected, kf_has_non_corrected, kf_fixed, edge_i, edge_j, edge_loop,
+                               fix_scale, slots=(), point_ref=(), iterations=20):
+        """Optimizer::OptimizeEssentialGraph, first overload (vsg_mappoints_optimize_essential_graph): see
+        optimize_essential_graph, which this calls with the store's handle."""
+        return optimize_essential_graph(self._L, self._h, kf_Scw, kf_non_corrected, kf_has_non_corrected, kf_fixed, edge_i, edge_j,
+                                        edge_loop, fix_scale, slots, point_ref, iterations)
+
+    def CorrectSim3(self, slots, point_ref, S_from, S_to_inverse):
+        """The point correction of LoopClosing::CorrectLoop (LoopClosing.cc:1060-1064) and Optimizer.cc:2723-2728
+        (vsg_mappoints_correct_sim3): slot slots[i] becomes float(S_to_inverse[r].map(S_from[r].map(double(pos)))) with
+        r = point_ref[i]; S_from / S_to_inverse are (R, 8) float64 (q x y z w, t, s).  Follow with
+        refresh(what=REFRESH_NORMAL).  Returns the new positions, (n, 3) float32."""
+        n = int(np.asarray(slots).size)
+        sl, ref = _i32(slots), _i32(point_ref)
+        a, b = np.ascontiguousarray(S_from, np.float64).reshape(-1, 8), np.ascontiguousarray(S_to_inverse, np.float64).reshape(-1, 8)
+        if np.asarray(point_ref).size != n or a.shape != b.shape:
+            raise ValueError("slots / point_ref or S_from / S_to_inverse differ in length")
+        out = np.zeros((max(n, 1), 3), np.float32)
+        f64p = C.POINTER(C.c_double)
+        _check(self._L.vsg_mappoints_correct_sim3(self._h, n, _p(sl, _i32p), _p(ref, _i32p), a.shape[0],
+                                                  C.cast(_p(a, f64p), C.POINTER(Sim3d)), C.cast(_p(b, f64p), C.POINTER(Sim3d)),
+                                                  _p(out, _f32p)), "vsg_mappoints_correct_sim3")
+        return out[:n]
 
     def Sim3Ransac(self, slots1, slots2, max_err1, max_err2, kf1, kf2, samples, min_inliers, fix_scale=False, other=None,
                    per_hypothesis=False):
