@@ -1282,7 +1282,8 @@ int vsg_shard_boundary_record(vsg_shard *s, const int **d_counts, const vsg_keyp
  * and stereo edges (:1850-1948), optimize(iterations) (:2288), the classification (:2296-2340) and the recovery
  * (:2398-2414), in double, with the arithmetic of csrc/vsg_local_ba.h, which a host build reproduces bit for bit (DESIGN.md
  * section 8).  The marker, plane, room and door vertices and their edges (:1995-2274, :2342-2369, :2416-2452) are NOT
- * part of it: a caller whose local lists of those are not empty keeps the reference routine.
+ * part of it: a caller whose local lists of planes and rooms are not empty calls
+ * vsg_mappoints_local_bundle_adjustment_sgraph below instead.
  *   - Point i = slot slots[i] of mp, with the observations [obs_off[i], obs_off[i + 1]) of obs_kf (index into kfs) and
  *     obs_idx (leftIndex in that keyframe), as vsg_mappoints_refresh_from_observations takes them: the observations that
  *     pass !pKFi->isBad() && GetMap() == pCurrentMap (:1881), in mObservations' order.  The edges are these entries in this
@@ -1327,6 +1328,57 @@ int vsg_mappoints_local_bundle_adjustment(
     int n_kf, vsg_frame *const *kfs, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed, const vsg_ba_camera *kf_cam,
     const float *inv_level_sigma2, int nlevels, int iterations, const volatile uint8_t *stop_flag,
     vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *erase, double *chi2, vsg_local_ba_result *res);
+
+/* Optimizer::LocalBundleAdjustment WITH its planes and rooms: the visual part above, and behind it the plane vertices with
+ * their keyframe edges (Optimizer.cc:2018-2130), the room vertices with their wall edges (:2155-2214), their classification
+ * (:2342-2369) and recovery (:2426-2441), with the arithmetic of csrc/vsg_sgraph_ba.h, which a host build reproduces bit
+ * for bit (DESIGN.md sections 7 and 8).  The planes and rooms are rows of the reduced system behind the keyframes; the
+ * Jacobians of their edges are g2o's numeric ones.  The arguments up to chi2 are the visual call's; then:
+ *   - plane_eq[4 i] = localPlaneList's getGlobalEquation().coeffs(), taken as held (setEstimate does not renormalise).
+ *     Plane i has the observations [pl_obs_off[i], pl_obs_off[i + 1]) of pl_obs_kf (index into kfs): the entries of
+ *     getObservations() that pass :2070-2083, in the map's order.  Per observation: pl_obs_local[4] = obs.localPlane's
+ *     coefficients, pl_obs_G[16] = obs.Gij row-major, w_plane_kf = obs.confidence * plane_kf.information_gain or 0 when
+ *     that edge is not added (plane_kf disabled), w_plane_point = obs.confidence * plane_point.information_gain or 0 when
+ *     not added (plane_point disabled, or getClassIdFromPlaneType == -1).
+ *   - the rooms that get a vertex (walls.size() >= 2, :2163): room_center[3 r] = getRoomCenter(), room_n_walls[r] = 2
+ *     (getIsCorridor()) or 4, room_wall[4 r + k] = wall k as an index into the planes.  The reference's :2198 tests walls[2]
+ *     twice and would dereference a missing walls[3]; here all four must exist.
+ *   - plane_eq_out[4 i] = vPlane->estimate() (:2431); a plane without an edge gets its input bytes (g2o drops the vertex).
+ *     room_center_out[3 r] = the room vertex's translation (:2441).  erase_plane[o] = whether (keyframe, plane) of
+ *     observation o goes into vToErasePlane: chi2 > 7.815 of its plane-keyframe edge, chi2 > 3.841 of its point-to-plane
+ *     edge, or !isDistanceCorrect() of either on the restored estimates; the std::find of :2352 / :2366 is this one flag.
+ *     chi2_plane_kf[o] / chi2_plane_point[o] (may be NULL) = the doubles compared, NaN canonical, NaN where the edge does
+ *     not exist.  A keyframe whose only edges are plane edges is optimised too.
+ *   - res->local is the visual call's result; n_edges counts the visual edges.  ran = 0 as there, where "no edge" (:2277)
+ *     counts the visual and the plane edges but NOT the room edges: the reference never increments nEdges for them.
+ *   - the edge order of every sum: the visual edges, then per plane and observation the plane-keyframe edge before the
+ *     point-to-plane edge, then the rooms.  With n_planes == 0 and n_rooms == 0 every out the two calls share is
+ *     byte-equal to vsg_mappoints_local_bundle_adjustment's.
+ * NOT part of it (the caller keeps the reference routine): marginalize_planes = true and the plane_map_point factor
+ * (:2026, :2037); the plane / room section of Optimizer::BundleAdjustment (:289-498).  Markers have no edge in this version
+ * of the reference (g2o drops them, their recovery returns the input) and doors are commented out: neither is an argument.
+ * Checked before anything is enqueued, VSG_ERR_INVALID: everything the visual call lists; a NULL new array with a non-zero
+ * count (plane_eq_out, room_center_out, erase_plane among them); plane offsets that do not ascend from 0; an observation
+ * keyframe outside [0, n_kf) or listed twice for one plane; a negative or NaN weight; a non-finite plane or one with a zero
+ * normal; room_n_walls outside {2, 4}; a wall outside [0, n_planes) or listed twice in a room.  VSG_ERR_UNSUPPORTED: what
+ * the visual call lists, and 6 optimised keyframes + 3 planes with an edge + 6 rooms > 768 rows. */
+typedef struct vsg_sgraph_local_ba_result {
+  vsg_local_ba_result local;
+  int32_t n_planes_active, n_rooms_active;          /* vertices with an edge */
+  int32_t n_plane_kf, n_plane_point, n_room_edges;  /* edges of each kind */
+  int32_t n_rows, n_erase_plane, reserved;          /* rows of the reduced system; erase_plane flags set */
+} vsg_sgraph_local_ba_result;
+int vsg_mappoints_local_bundle_adjustment_sgraph(
+    vsg_mappoints *mp, int n_points, const int32_t *slots,
+    const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx,
+    int n_kf, vsg_frame *const *kfs, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed, const vsg_ba_camera *kf_cam,
+    const float *inv_level_sigma2, int nlevels, int iterations, const volatile uint8_t *stop_flag,
+    vsg_pose_se3d *kf_Tcw_out, float *world_pos_out, uint8_t *erase, double *chi2,
+    int n_planes, const double *plane_eq, const int32_t *pl_obs_off, const int32_t *pl_obs_kf, const double *pl_obs_local,
+    const double *pl_obs_G, const double *w_plane_kf, const double *w_plane_point,
+    int n_rooms, const double *room_center, const int32_t *room_n_walls, const int32_t *room_wall,
+    double *plane_eq_out, double *room_center_out, uint8_t *erase_plane, double *chi2_plane_kf, double *chi2_plane_point,
+    vsg_sgraph_local_ba_result *res);
 
 /* The visual part of void Optimizer::BundleAdjustment(vpKFs, vpMP, ..., nIterations, pbStopFlag, nLoopKF, bRobust, ...)
  * (Optimizer.cc:60-287, :500-610) as Optimizer::GlobalBundleAdjustemnt calls it (:45-58) on resident keyframes and resident

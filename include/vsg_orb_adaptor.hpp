@@ -556,6 +556,30 @@ struct LocalBAResult {
   vsg_local_ba_result res;
 };
 
+// The planes and rooms vsg::ResidentMapPoints::LocalBundleAdjustmentSGraph takes (include/vsg_orb.h names each array):
+// planeEq = 4 per plane of localPlaneList (getGlobalEquation().coeffs()); plane i's observations are [planeObsOff[i],
+// planeObsOff[i + 1]) of planeObsKf (index into keyFrames), planeObsLocal (4: obs.localPlane), planeObsG (16: obs.Gij
+// row-major), wPlaneKf / wPlanePoint (obs.confidence * information_gain, 0 = that edge is not added); roomCenter = 3 per
+// room of localRoomList with walls.size() >= 2, roomNWalls = 2 (corridor) or 4, roomWall = 4 plane indices per room.
+struct SGraphLists {
+  std::vector<double> planeEq;
+  std::vector<int32_t> planeObsOff{0}, planeObsKf;
+  std::vector<double> planeObsLocal, planeObsG, wPlaneKf, wPlanePoint, roomCenter;
+  std::vector<int32_t> roomNWalls, roomWall;
+};
+// What it returns: LocalBAResult's fields, vPlane->estimate() per plane (a plane without an edge: its input), the room
+// vertices' translations, per plane observation whether (keyframe, plane) goes into vToErasePlane and the two chi2
+// compared (NaN where the edge does not exist), and the counters of vsg_sgraph_local_ba_result.
+struct SGraphLocalBAResult {
+  std::vector<vsg_pose_se3d> kfTcw;
+  std::vector<float> worldPos;
+  std::vector<uint8_t> erase;
+  std::vector<double> chi2, planeEq, roomCenter;
+  std::vector<uint8_t> erasePlane;
+  std::vector<double> chi2PlaneKf, chi2PlanePoint;
+  vsg_sgraph_local_ba_result res;
+};
+
 // What vsg::ResidentMapPoints::GlobalBundleAdjustment returns: vSE3->estimate() per keyframe (the fixed keyframe, or one
 // without an edge: its input, widened), the float position per point (mPosGBA; written into its slot only in the
 // nLoopKF == origin case), included[i] = !vbNotIncludedMP[i], the chi2 per observation, and the counters of
@@ -718,6 +742,48 @@ class ResidentMapPoints {
                                                 E ? r.erase.data() : &none_erase, E ? r.chi2.data() : nullptr, &r.res),
           "vsg_mappoints_local_bundle_adjustment");
     if (!r.res.ran) {  // the reference returned before optimize: nothing was written, the outs are the inputs
+      for (size_t k = 0; k < K; ++k)
+        for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
+      if (n)
+        check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+              "vsg_mappoints_read");
+    }
+    return r;
+  }
+  // Optimizer::LocalBundleAdjustment WITH its planes and rooms (vsg_mappoints_local_bundle_adjustment_sgraph): the arguments
+  // of LocalBundleAdjustment, then the planes and rooms as SGraphLists names them.  A caller
+  // with marginalize_planes or the plane_map_point factor keeps the reference routine.
+  SGraphLocalBAResult LocalBundleAdjustmentSGraph(const std::vector<int32_t> &slots, const std::vector<int32_t> &obsOff,
+                                                  const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                                                  const std::vector<vsg_frame *> &keyFrames, const std::vector<vsg_pose_se3> &kfTcw,
+                                                  const std::vector<uint8_t> &kfFixed, const std::vector<vsg_ba_camera> &kfCam,
+                                                  const std::vector<float> &mvInvLevelSigma2, const SGraphLists &sg,
+                                                  int iterations = 10, const volatile uint8_t *pbStopFlag = nullptr) {
+    const size_t n = slots.size(), K = keyFrames.size(), Pl = sg.planeEq.size() / 4, R = sg.roomCenter.size() / 3;
+    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || kfTcw.size() != K || kfFixed.size() != K ||
+        kfCam.size() != K || (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())) || sg.planeEq.size() != 4 * Pl ||
+        sg.planeObsOff.size() != Pl + 1 || sg.roomCenter.size() != 3 * R || sg.roomNWalls.size() != R || sg.roomWall.size() != 4 * R)
+      throw std::runtime_error("ResidentMapPoints::LocalBundleAdjustmentSGraph: the arrays' sizes do not match");
+    const size_t E = n ? (size_t)obsOff[n] : 0, NO = sg.planeObsOff[Pl] > 0 ? (size_t)sg.planeObsOff[Pl] : 0;
+    if (sg.planeObsKf.size() < NO || sg.planeObsLocal.size() < 4 * NO || sg.planeObsG.size() < 16 * NO || sg.wPlaneKf.size() < NO ||
+        sg.wPlanePoint.size() < NO)
+      throw std::runtime_error("ResidentMapPoints::LocalBundleAdjustmentSGraph: planeObsOff runs past the observation arrays");
+    SGraphLocalBAResult r;
+    r.kfTcw.resize(K), r.worldPos.assign(3 * n, 0.0f), r.erase.assign(E, 0), r.chi2.assign(E, 0.0);
+    r.planeEq = sg.planeEq, r.roomCenter = sg.roomCenter, r.erasePlane.assign(NO, 0);
+    r.chi2PlaneKf.assign(NO, 0.0), r.chi2PlanePoint.assign(NO, 0.0);
+    vsg_pose_se3d none_kf;
+    uint8_t none_erase = 0;
+    check(vsg_mappoints_local_bundle_adjustment_sgraph(
+              mp_, (int)n, slots.data(), obsOff.data(), obsKf.data(), obsIdx.data(), (int)K, keyFrames.data(), kfTcw.data(),
+              kfFixed.data(), kfCam.data(), mvInvLevelSigma2.data(), (int)mvInvLevelSigma2.size(), iterations, pbStopFlag,
+              K ? r.kfTcw.data() : &none_kf, n ? r.worldPos.data() : nullptr, E ? r.erase.data() : &none_erase,
+              E ? r.chi2.data() : nullptr, (int)Pl, sg.planeEq.data(), sg.planeObsOff.data(), sg.planeObsKf.data(),
+              sg.planeObsLocal.data(), sg.planeObsG.data(), sg.wPlaneKf.data(), sg.wPlanePoint.data(), (int)R, sg.roomCenter.data(),
+              sg.roomNWalls.data(), sg.roomWall.data(), r.planeEq.data(), r.roomCenter.data(), r.erasePlane.data(),
+              NO ? r.chi2PlaneKf.data() : nullptr, NO ? r.chi2PlanePoint.data() : nullptr, &r.res),
+          "vsg_mappoints_local_bundle_adjustment_sgraph");
+    if (!r.res.local.ran) {  // the reference returned before optimize: nothing was written, the outs are the inputs
       for (size_t k = 0; k < K; ++k)
         for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
       if (n)

@@ -14,6 +14,7 @@
 #include "vsg_project.h"
 #include "vsg_sim3.h"
 #include "vsg_sim3_opt.h"
+#include "vsg_sgraph_ba.h"
 #include "vsg_triangulate.h"
 #include "vsg_mlpnp.h"
 #include "vsg_two_view.h"
@@ -356,6 +357,46 @@ int lb_host_side(int capacity, int n_points, const int32_t *slots, const float *
   int n_erase = 0;
   for (size_t e = 0; e < E; e++) n_erase += erase[e] != 0;
   res->n_erase = n_erase;
+  return VSG_OK;
+}
+
+// sgraphba: the same path with the planes and rooms of csrc/vsg_sgraph_ba.h behind the visual part (vsg::sgba::HostRun)
+int sg_host_side(int capacity, int n_points, const int32_t *slots, const float *pos, const int32_t *obs_off, const int32_t *obs_kf,
+                 const int32_t *obs_idx, int n_kf, const int32_t *kf_off, const float *kx, const float *ky, const int32_t *oct,
+                 const float *ur, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed, const vsg_ba_camera *kf_cam,
+                 const float *inv_level_sigma2, int nlevels, int iterations, vsg_pose_se3d *kf_Tcw_out, float *pos_out,
+                 uint8_t *erase, double *chi2, int n_planes, const double *plane_eq, const int32_t *pl_obs_off,
+                 const int32_t *pl_obs_kf, const double *pl_obs_local, const double *pl_obs_G, const double *w_plane_kf,
+                 const double *w_plane_point, int n_rooms, const double *room_center, const int32_t *room_n_walls,
+                 const int32_t *room_wall, double *plane_eq_out, double *room_center_out, uint8_t *erase_plane,
+                 double *chi2_plane_kf, double *chi2_plane_point, vsg_sgraph_local_ba_result *res) {
+  namespace sg = vsg::sgba;
+  const sg::SemIn in = {n_planes, plane_eq, pl_obs_off, pl_obs_kf, pl_obs_local, pl_obs_G, w_plane_kf, w_plane_point,
+                        n_rooms,  room_center, room_n_walls, room_wall};
+  std::vector<int32_t> kf_n((size_t)n_kf), nleft((size_t)n_kf, -1);
+  for (int k = 0; k < n_kf; k++) kf_n[(size_t)k] = kf_off[k + 1] - kf_off[k];
+  static thread_local sg::HostRun run;  // its vectors keep their capacity from call to call, as the library's arenas do
+  int ran = 0;
+  const int rc = sg::check_and_build(
+      n_points, slots, obs_off, obs_kf, obs_idx, n_kf, kf_n.data(), nleft.data(), [&](int k, int i) { return (int)oct[kf_off[k] + i]; },
+      kf_fixed, capacity, nlevels, iterations, nullptr, in, &run.V.T, &run.ST, &ran);
+  if (rc != VSG_OK || !ran) return rc != VSG_OK ? rc : -100;
+  const size_t E = (size_t)run.V.T.E;
+  std::vector<float> ex(E), ey(E), eur(E);
+  std::vector<int32_t> eoct(E);
+  for (size_t e = 0; e < E; e++) {
+    const size_t f = (size_t)kf_off[run.V.T.e_kf[e]] + (size_t)run.V.T.e_idx[e];
+    ex[e] = kx[f], ey[e] = ky[f], eoct[e] = oct[f], eur[e] = ur[f];
+  }
+  run.setup(pos, ex.data(), ey.data(), eur.data(), eoct.data(), kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2, nlevels, iterations, in);
+  run.run(nullptr);
+  run.V.outputs(kf_Tcw, pos, kf_Tcw_out, pos_out, erase, chi2);
+  run.outputs(in, plane_eq_out, room_center_out, erase_plane, chi2_plane_kf, chi2_plane_point);
+  sg::fill_result(res, run.V.T, &run.ST, &run.V.S);
+  int n_erase = 0, n_erase_plane = 0;
+  for (size_t e = 0; e < E; e++) n_erase += erase[e] != 0;
+  for (int o = 0; o < run.ST.n_obs; o++) n_erase_plane += erase_plane[o] != 0;
+  res->local.n_erase = n_erase, res->n_erase_plane = n_erase_plane;
   return VSG_OK;
 }
 

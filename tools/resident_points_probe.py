@@ -71,6 +71,16 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
             B  = vsg_mappoints_local_bundle_adjustment;  A2 / B2 = both again;  B_S1 / B_S2 / B_S10 = B with 1 / 2 / 10 trial
                  slots enqueued ahead per iteration instead of the library's.  Every call asserts all seven equal bit for bit
 
+  sgraphba  Optimizer::LocalBundleAdjustment WITH its planes and rooms: the localba leg's scenes with 8 / 16 / 32 planes, each seen
+            by a third of the keyframes, and 1 / 2 / 4 rooms (the first of four walls, the others corridors); a size is
+            "<optimised = fixed keyframes>:<points>:<0 = the default factors, plane_point alone | 1 = plane_kf too>"
+            A  = vsg_mappoints_read + the host build of csrc/vsg_sgraph_ba.h on one thread (NOT g2o: the header's own
+                 arithmetic, numeric Jacobians and DENSE reduced solve included) + vsg_mappoints_update
+            B  = vsg_mappoints_local_bundle_adjustment_sgraph;  A2 / B2 = both again;  V / V2 = the VISUAL call on the same
+                 scene without its planes and rooms: B - V is the price of the semantic part.  Every call asserts A, B, A2
+                 and B2 equal bit for bit
+            `sgraphba trace [size]` runs one size five times, for rocprofv3 --kernel-trace --stats with VSG_NO_OVERLAP=1
+
   globalba  the visual part of Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt: "init" = 1 fixed + 1 optimised
             keyframe, 300 mono points, robust, 20 iterations (CreateInitialMapMonocular); "50" / "100" / "200" / "500" = that many
             keyframes, one of them fixed, 15 points per keyframe of 8 observations (120 observed features per keyframe), half
@@ -95,7 +105,7 @@ through ctypes with preallocated arrays on both sides.  Every call asserts that 
             existing calls plus the caller's loops on one thread.  A2 / B2 = both again; the walk's rounds where the result
             carries them.  Both write into profiles/track_chain_latency.json, one key each
 
-usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|globalba|essgraph|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
+usage: resident_points_probe.py <local|last|keyframe|refresh|pose|newpoints|sim3|mlpnp|sim3opt|localba|sgraphba|globalba|essgraph|twoview|track|track_local> [calls] [out.json]  -> runs the child, writes the record (default
                                   profiles/local_points_latency.json, track_last_latency.json, keyframe_points_latency.json,
                                   mappoints_refresh_latency.json, pose_optimization_latency.json)
        resident_points_probe.py child <case> [calls]  -> one JSON object on stdout (medians, 10-90 % range, microseconds)
@@ -125,7 +135,8 @@ def host_side(orb):
     csrc = ROOT / "visual_sgraphs_amd" / "csrc"
     src = [ROOT / "tools" / "resident_points_cpu.cpp", csrc / "vsg_project.h", csrc / "vsg_frustum.h", csrc / "vsg_math.h",
            csrc / "vsg_observations.h", csrc / "vsg_pose_opt.h", csrc / "vsg_triangulate.h", csrc / "vsg_sim3.h",
-           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_global_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h", csrc / "vsg_essential_graph.h"]
+           csrc / "vsg_sim3_opt.h", csrc / "vsg_local_ba.h", csrc / "vsg_global_ba.h", csrc / "vsg_two_view.h", csrc / "vsg_jacobi.h", csrc / "vsg_mlpnp.h", csrc / "vsg_essential_graph.h",
+           csrc / "vsg_sgraph_ba.h"]
     if not so.exists() or any(f.stat().st_mtime > so.stat().st_mtime for f in src):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-pthread", "-I", str(csrc), "-o",
                                str(so), str(src[0])])
@@ -152,6 +163,9 @@ def host_side(orb):
     H.lb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
                                C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
                                C.POINTER(C.c_double), C.c_void_p]
+    f64p = C.POINTER(C.c_double)
+    H.sg_host_side.argtypes = H.lb_host_side.argtypes[:-1] + [C.c_int, f64p, _i32p, _i32p, f64p, f64p, f64p, f64p, C.c_int, f64p, _i32p,
+                                                              _i32p, f64p, f64p, _u8p, f64p, f64p, C.c_void_p]
     H.gb_host_side.argtypes = [C.c_int, C.c_int, _i32p, _f32p, _i32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _f32p, _i32p, _f32p,
                                C.c_void_p, _u8p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, _f32p, _u8p,
                                C.POINTER(C.c_double), C.c_void_p]
@@ -1004,6 +1018,97 @@ class LocalBA(Case):
                              "B = vsg_mappoints_local_bundle_adjustment (B_S1 / B_S2 / B_S10: 1 / 2 / 10 trial slots enqueued ahead)"}
 
 
+class SGraphBA(LocalBA):
+    """Optimizer::LocalBundleAdjustment with its planes and rooms: LocalBA's scene and the planes, observations and rooms of
+    tests/sgba_scenes.py on it.  A size is "<optimised = fixed keyframes>:<points>:<plane_kf factor too>"."""
+    SIZES = ("10:1500:0", "20:3000:0", "40:6000:0", "10:1500:1", "20:3000:1", "40:6000:1")
+    TH, DEST = 0.0, "sgraph_local_ba_latency.json"
+    VARIANTS = ("A", "B", "A2", "B2", "V", "V2")
+    SAME = ("B", "A2", "B2")  # V and V2 solve another problem
+
+    def __init__(self, orb, fr, size):
+        import lba_scenes as ls
+        import sgba_scenes as ss
+        nk, npts, both = (int(v) for v in size.split(":"))
+        s = ls.make(7300 + nk, nk, nk, npts, 6, "mixed", outliers=0.05)
+        self.setup(orb, s, nk, npts)
+        rng = np.random.default_rng(7400 + nk)
+        n_planes, n_rooms, K = (4 * nk) // 5, max(nk // 10, 1), 2 * nk
+        planes = [ss.face(i) for i in range(6)] + [ss.oblique(rng) for _ in range(n_planes - 6)]
+        c = np.ascontiguousarray
+        off, okf, loc, G, wk, wp = [0], [], [], [], [], []
+        for pl in planes:  # seen by a third of the keyframes, from where the keyframes start
+            for k in np.sort(rng.choice(K, K // 3, replace=False)):
+                l, g = ss.observation(rng, s["Tcw"][k].astype(np.float64), pl)
+                conf = rng.uniform(0.5, 1.0)
+                okf.append(k), loc.append(l), G.append(g), wk.append(conf * ss.GAIN_KF if both else 0.0), wp.append(conf * ss.GAIN_PP)
+            off.append(len(okf))
+        rooms = [(0, 1, 2, 3)] + [(6 + 2 * r, 7 + 2 * r) for r in range(n_rooms - 1)]
+        self.eq = c([ss.start_plane(rng, pl) for pl in planes], np.float64)
+        self.poff, self.pkf = c(off, np.int32), c(okf, np.int32)
+        self.loc, self.G, self.wk, self.wp = c(loc, np.float64), c(G, np.float64), c(wk, np.float64), c(wp, np.float64)
+        self.rc = c([ss.room_center([planes[w] for w in r]) + rng.normal(0, 0.02, 3) for r in rooms], np.float64)
+        self.rn = c([len(r) for r in rooms], np.int32)
+        self.rw = c([list(r) + [0] * (4 - len(r)) for r in rooms], np.int32)
+        self.n_planes, self.n_rooms, NO = n_planes, n_rooms, len(okf)
+        self.plane_out, self.room_out = np.zeros((n_planes, 4)), np.zeros((n_rooms, 3))
+        self.erase_plane, self.chi2k, self.chi2p = np.zeros(NO, np.uint8), np.zeros(NO), np.zeros(NO)
+        self.sres, self.vres = orb.SGraphLocalBaResult(), orb.LocalBaResult()
+
+    def reset(self):
+        LocalBA.reset(self)
+        self.plane_out[:], self.room_out[:], self.erase_plane[:], self.chi2k[:], self.chi2p[:] = 0, 0, 9, -1.0, -1.0
+        C.memset(C.byref(self.sres), 0, C.sizeof(self.sres))
+
+    def run(self, name, L, H, P):
+        f64p = C.POINTER(C.c_double)
+        sem = (self.n_planes, p(self.eq, f64p), p(self.poff, _i32p), p(self.pkf, _i32p), p(self.loc, f64p), p(self.G, f64p),
+               p(self.wk, f64p), p(self.wp, f64p), self.n_rooms, p(self.rc, f64p), p(self.rn, _i32p), p(self.rw, _i32p),
+               p(self.plane_out, f64p), p(self.room_out, f64p), p(self.erase_plane, _u8p), p(self.chi2k, f64p), p(self.chi2p, f64p))
+        if name.startswith("V"):
+            return LocalBA.run(self, "B", L, H, P)
+        if name.startswith("B"):
+            return L.vsg_mappoints_local_bundle_adjustment_sgraph(
+                self.mp.handle, self.npts, p(self.slots, _i32p), p(self.off, _i32p), p(self.okf, _i32p), p(self.oidx, _i32p), self.K,
+                self.handles, C.cast(self.Tcw.ctypes.data, C.POINTER(self.orb.PoseSE3)), p(self.fixed, _u8p),
+                C.cast(self.cam.ctypes.data, C.POINTER(self.orb.BaCamera)), p(self.sig, _f32p), 8, 10, None,
+                C.cast(self.kf_out.ctypes.data, C.POINTER(self.orb.PoseSE3d)), p(self.pos_out, _f32p), p(self.erase, _u8p),
+                p(self.chi2, f64p), *sem, C.byref(self.sres))
+        rc = L.vsg_mappoints_read(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), None, None, None, None, None)
+        if rc != 0:
+            return rc
+        rc = H.sg_host_side(self.cap, self.npts, p(self.slots, _i32p), p(self.Xw, _f32p), p(self.off, _i32p), p(self.okf, _i32p),
+                            p(self.oidx, _i32p), self.K, p(self.kf_off, _i32p), p(self.kx, _f32p), p(self.ky, _f32p),
+                            p(self.oct, _i32p), p(self.ur, _f32p), self.Tcw.ctypes.data, p(self.fixed, _u8p), self.cam.ctypes.data,
+                            p(self.sig, _f32p), 8, 10, self.kf_out.ctypes.data, p(self.pos_out, _f32p), p(self.erase, _u8p),
+                            p(self.chi2, f64p), *sem, C.addressof(self.sres))
+        if rc != 0:
+            return rc
+        return L.vsg_mappoints_update(self.mp.handle, self.npts, p(self.slots, _i32p), p(self.pos_out, _f32p), None, None, None,
+                                      None, None)
+
+    def result(self, name, r):
+        return LocalBA.result(self, name, r)[:6] + (
+            self.plane_out.view(np.uint64).copy(), self.room_out.view(np.uint64).copy(), self.erase_plane.copy(),
+            self.chi2k.view(np.uint64).copy(), self.chi2p.view(np.uint64).copy(), np.frombuffer(bytes(self.sres), np.uint8).copy())
+
+    def facts(self, last):
+        r = self.orb.SGraphLocalBaResult.from_buffer_copy(last["B"][11].tobytes())
+        v = self.orb.LocalBaResult.from_buffer_copy(bytes(self.res))
+        return {"optimised_keyframes": self.nk, "fixed_keyframes": self.nk, "points": self.npts, "edges": int(r.local.n_edges),
+                "planes": self.n_planes, "rooms": self.n_rooms, "plane_observations": len(self.pkf),
+                "plane_kf_edges": int(r.n_plane_kf), "plane_point_edges": int(r.n_plane_point), "rows": int(r.n_rows),
+                "erased": int(r.local.n_erase), "erased_plane_observations": int(r.n_erase_plane), "features_per_keyframe": NFEAT,
+                "iterations_run": int(r.local.iterations_run), "trials_run": int(r.local.trials_run),
+                "stop_reason": int(r.local.stop_reason), "visual_call (iterations, trials)": (int(v.iterations_run), int(v.trials_run)),
+                "every_call_equals_the_host_build": True,
+                "host_side": "A = vsg_mappoints_read + the host build of csrc/vsg_sgraph_ba.h on one thread "
+                             "(tools/resident_points_cpu.cpp) + vsg_mappoints_update; it is THIS header's build and NOT g2o (no "
+                             "Eigen here): the same numeric Jacobians, no virtual calls, a DENSE reduced solve where g2o's is "
+                             "sparse; B = vsg_mappoints_local_bundle_adjustment_sgraph; V = vsg_mappoints_local_bundle_adjustment "
+                             "on the same scene without planes and rooms (B - V: the price of the semantic part)"}
+
+
 class GlobalBA(LocalBA):
     """The visual part of Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt on resident keyframes and map points:
     scenes of tests/lba_scenes.py with ONE fixed keyframe, keyframes padded to 1000 features.  "init": 1 + 1 keyframes, 300
@@ -1284,7 +1389,7 @@ class EssGraph:
 
 
 CASES = {"track": Track, "track_local": TrackLocal, "local": Local, "last": Last, "keyframe": KeyFrame, "refresh": Refresh, "pose": Pose, "newpoints": NewPoints, "sim3": Sim3, "mlpnp": Mlpnp,
-         "sim3opt": Sim3Opt, "localba": LocalBA, "globalba": GlobalBA, "twoview": TwoView, "essgraph": EssGraph}
+         "sim3opt": Sim3Opt, "localba": LocalBA, "sgraphba": SGraphBA, "globalba": GlobalBA, "twoview": TwoView, "essgraph": EssGraph}
 
 
 def child(case, calls, sizes=None):
@@ -1308,7 +1413,7 @@ def child(case, calls, sizes=None):
                 assert last[name][0] >= 0, (name, last[name][0])
                 if k >= warm:
                     t[name].append(dt)
-            for name in K.VARIANTS[1:]:  # the variants compute the same thing
+            for name in getattr(K, "SAME", K.VARIANTS[1:]):  # the variants compute the same thing
                 assert all(np.array_equal(a, b) for a, b in zip(last["A"], last[name])), name
         res = {k: stats(v) for k, v in t.items()}
         res.update(c.facts(last), timed_calls=ncalls, warm_up_calls=warm)
@@ -1319,6 +1424,9 @@ def child(case, calls, sizes=None):
         res["resident_not_slower"] = bool(res["B"]["p10_us"] <= max(res["A"]["p90_us"], res["A2"]["p90_us"]))
         res["resident_faster"] = bool(res["B"]["p90_us"] < min(res["A"]["p10_us"], res["A2"]["p10_us"]))
         # ... and its median gain counts when it is larger than the run's own A-vs-A gap
+        if "V2" in t:  # the visual call on the same scene, twice: what the planes and rooms cost on the device
+            res["semantic_part_median_us"] = round(res["B"]["median_us"] - res["V"]["median_us"], 1)
+            res["v_vs_v_median_gap_us"] = round(abs(res["V"]["median_us"] - res["V2"]["median_us"]), 1)
         res["resident_median_gain_us"] = round(res["A"]["median_us"] - res["B"]["median_us"], 1)
         res["gain_exceeds_a_vs_a_gap"] = bool(res["resident_median_gain_us"] > res["a_vs_a_median_gap_us"])
         out["sizes"][str(n)] = res
@@ -1341,6 +1449,14 @@ def trace(case="local", size=None):
             c.reset()
             assert c.run("B", L, None, None) == 0
         print({"size": "20:3000", "calls": 5, "iterations_run": int(c.res.iterations_run), "trials_run": int(c.res.trials_run)})
+        return
+    if case == "sgraphba":
+        L, c = orb.load_library(), SGraphBA(orb, fr, size or "20:3000:1")
+        for k in range(5):
+            c.reset()
+            assert c.run("B", L, None, None) == 0
+        print({"size": size or "20:3000:1", "calls": 5, "iterations_run": int(c.sres.local.iterations_run),
+               "trials_run": int(c.sres.local.trials_run), "rows": int(c.sres.n_rows)})
         return
     if case == "essgraph":
         L, c = orb.load_library(), EssGraph(orb, fr, size or "200:0")

@@ -14,7 +14,7 @@ LIB = PKG / "libvsg_orb.so"
 SOURCES = ["vsg_kernels.hip", "vsg_orb.hip", "vsg_match.hip", "vsg_bow.hip", "vsg_frame.hip", "vsg_window.hip", "vsg_ctx.hip",
            "vsg_shard.hip", "vsg_kfdb.hip", "vsg_mappoints.hip", "vsg_pose.hip", "vsg_triangulate.hip",
            "vsg_sim3.hip", "vsg_sim3_opt.hip", "vsg_track.hip", "vsg_local_ba.hip", "vsg_two_view.hip", "vsg_mlpnp.hip",
-           "vsg_global_ba.hip", "vsg_essential_graph.hip"]
+           "vsg_global_ba.hip", "vsg_essential_graph.hip", "vsg_sgraph_ba.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wno-unused-value",
          # MFMA results in VGPRs (the matcher's epilogue is VALU): no v_accvgpr_read per accumulator register

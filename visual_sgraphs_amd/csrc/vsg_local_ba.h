@@ -452,13 +452,14 @@ struct Topology {
 // Everything vsg_mappoints_local_bundle_adjustment checks that needs no device.  kf_n[k] = features of keyframe k whose
 // octave the host can see, octave(k, idx) = that octave, nleft[k] = Nleft.  *ran = 0: VSG_OK and the call returns before
 // optimize (:1734, :2277, :2283).  max_opt_kf / need_fixed: the local call's cap and its return without a fixed keyframe
-// (:1734); vsg_global_ba.h passes its own cap and no such return.
+// (:1734); vsg_global_ba.h passes its own cap and no such return.  extra_cnt[k] / extra_edges: edges of keyframe k and in
+// all that are not in the lists (vsg_sgraph_ba.h's plane edges): they make a keyframe a vertex and keep :2277 from returning.
 template <class OctaveOf>
 inline int check_and_build(int n_points, const int32_t *slots, const int32_t *obs_off, const int32_t *obs_kf,
                            const int32_t *obs_idx, int n_kf, const int32_t *kf_n, const int32_t *nleft, OctaveOf octave,
                            const uint8_t *kf_fixed, int capacity, int nlevels, int iterations,
                            const volatile uint8_t *stop_flag, Topology *T, int *ran, int max_opt_kf = kMaxOptKf,
-                           bool need_fixed = true) {
+                           bool need_fixed = true, const int32_t *extra_cnt = nullptr, int extra_edges = 0) {
   *ran = 0;
   if (n_points < 0 || n_kf < 0 || nlevels < 1 || nlevels > 16 || iterations < 1 || iterations > 100) return VSG_ERR_INVALID;
   if (n_points == 0) return VSG_OK;
@@ -486,9 +487,10 @@ inline int check_and_build(int n_points, const int32_t *slots, const int32_t *ob
     if (nleft[k] != -1) return VSG_ERR_UNSUPPORTED;
   T->K = n_kf, T->P = n_points, T->E = E, T->n_fixed = T->n_opt = 0;
   for (int k = 0; k < n_kf; k++) (kf_fixed[k] ? T->n_fixed : T->n_opt)++;
-  if ((need_fixed && T->n_fixed == 0) || E == 0) return VSG_OK;  // :1734, :2277
+  if ((need_fixed && T->n_fixed == 0) || E + extra_edges == 0) return VSG_OK;  // :1734, :2277
   std::vector<int32_t> cnt((size_t)n_kf, 0);
   for (int e = 0; e < E; e++) cnt[(size_t)obs_kf[e]]++;
+  for (int k = 0; extra_cnt && k < n_kf; k++) cnt[(size_t)k] += extra_cnt[k];
   T->opt_of.assign((size_t)n_kf, -1), T->opt_kf.clear();
   for (int k = 0; k < n_kf; k++)
     if (!kf_fixed[k] && cnt[(size_t)k] > 0) T->opt_of[(size_t)k] = (int32_t)T->opt_kf.size(), T->opt_kf.push_back(k);

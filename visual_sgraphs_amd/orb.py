@@ -99,6 +99,8 @@ EXPORTS = [
     # vsg_debug_local_ba_trial_slots of include/vsg_orb_debug_local_ba.h, is bound below but is no part of the two headers
     # this list mirrors)
     "vsg_mappoints_local_bundle_adjustment",
+    # Optimizer::LocalBundleAdjustment with its planes and rooms behind the visual part
+    "vsg_mappoints_local_bundle_adjustment_sgraph",
     # the visual part of Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt on resident keyframes and resident map
     # points (its test hooks, vsg_debug_ba_reduced_solve and vsg_debug_ba_solver_geometry of
     # include/vsg_orb_debug_global_ba.h, are bound below but are no part of the two headers this list mirrors)
@@ -246,6 +248,16 @@ LOCAL_BA_STOP_REASONS = ("iterations_done", "terminate", "n_bad", "stop_flag")
 class LocalBaResult(C.Structure):
     """include/vsg_orb.h vsg_local_ba_result."""
     _fields_ = [(k, C.c_int32) for k in LOCAL_BA_RESULT_INTS] + [(k, C.c_double) for k in LOCAL_BA_RESULT_DOUBLES]
+
+
+SGRAPH_LOCAL_BA_RESULT_INTS = ("n_planes_active", "n_rooms_active", "n_plane_kf", "n_plane_point", "n_room_edges", "n_rows",
+                               "n_erase_plane", "reserved")
+SGRAPH_LOCAL_BA_MAX_ROWS = 768  # 6 optimised keyframes + 3 planes with an edge + 6 rooms
+
+
+class SGraphLocalBaResult(C.Structure):
+    """include/vsg_orb.h vsg_sgraph_local_ba_result: the local call's result, then the semantic counters."""
+    _fields_ = [("local", LocalBaResult)] + [(k, C.c_int32) for k in SGRAPH_LOCAL_BA_RESULT_INTS]
 
 
 GLOBAL_BA_RESULT_INTS = tuple(k for k in LOCAL_BA_RESULT_INTS if k != "n_erase")
@@ -569,6 +581,9 @@ def load_library():
     L.vsg_mappoints_local_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
                                                         _u8p, C.POINTER(BaCamera), _f32p, ci, ci, _u8p, C.POINTER(PoseSE3d),
                                                         _f32p, _u8p, _f64p, C.POINTER(LocalBaResult)]
+    L.vsg_mappoints_local_bundle_adjustment_sgraph.argtypes = L.vsg_mappoints_local_bundle_adjustment.argtypes[:-1] + [
+        ci, _f64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, ci, _f64p, _i32p, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p,
+        C.POINTER(SGraphLocalBaResult)]
     L.vsg_debug_local_ba_trial_slots.argtypes = [ci]
     L.vsg_mappoints_global_bundle_adjustment.argtypes = [vp, ci, _i32p, _i32p, _i32p, _i32p, ci, C.POINTER(vp), C.POINTER(PoseSE3),
                                                          _u8p, C.POINTER(BaCamera), _f32p, ci, ci, ci, ci, _u8p,
@@ -1441,6 +1456,71 @@ class MapPoints:
         got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "erase": out["erase"][:nobs], "chi2": out["chi2"][:nobs]}
         got.update({k: int(getattr(res, k)) for k in LOCAL_BA_RESULT_INTS})
         got.update({k: float(getattr(res, k)) for k in LOCAL_BA_RESULT_DOUBLES})
+        return got
+
+    def LocalBundleAdjustmentSGraph(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
+                                    plane_eq=(), pl_obs_off=(0,), pl_obs_kf=(), pl_obs_local=(), pl_obs_G=(), w_plane_kf=(),
+                                    w_plane_point=(), room_center=(), room_n_walls=(), room_wall=(), iterations=10, stop_flag=None):
+        """Optimizer::LocalBundleAdjustment with its planes and rooms (vsg_mappoints_local_bundle_adjustment_sgraph).  The
+        first arguments are LocalBundleAdjustment's.  plane_eq = (n_planes, 4) doubles; plane i has the observations
+        [pl_obs_off[i], pl_obs_off[i + 1]) of pl_obs_kf (index into `keyframes`), each with pl_obs_local (4), pl_obs_G (4, 4)
+        and the two weights confidence * information_gain (0 = that edge is not added).  room_center = (n_rooms, 3),
+        room_n_walls = 2 or 4 per room, room_wall = (n_rooms, 4) indices into the planes.  Returns LocalBundleAdjustment's
+        dict plus plane_eq (n_planes, 4), room_center (n_rooms, 3), erase_plane, chi2_plane_kf and chi2_plane_point per plane
+        observation, and the fields of vsg_sgraph_local_ba_result."""
+        f64 = lambda a, per: (lambda v: v if v.size else np.zeros(per, np.float64))(np.ascontiguousarray(a, np.float64).reshape(-1))
+        n, K = int(np.asarray(slots).size), len(keyframes)
+        sl, off, kf, idx = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx)
+        if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != np.asarray(obs_kf).size:
+            raise ValueError("observation arrays do not match the slot list")
+        nobs = int(off[n]) if n else 0
+        if int(np.asarray(obs_kf).size) < nobs:
+            raise ValueError("obs_off runs past the observation arrays")
+        T, fx, cam = _f32(kf_Tcw).reshape(-1), _u8(kf_fixed), _f32(kf_cam).reshape(-1)
+        if np.asarray(kf_Tcw).size != 7 * K or np.asarray(kf_fixed).size != K or np.asarray(kf_cam).size != 5 * K:
+            raise ValueError("kf_Tcw needs 7 floats, kf_fixed one byte and kf_cam 5 floats per keyframe")
+        eq, poff, pkf = f64(plane_eq, 4), _i32(pl_obs_off), _i32(pl_obs_kf)
+        n_planes, n_rooms = int(np.asarray(plane_eq).size) // 4, int(np.asarray(room_center).size) // 3
+        if np.asarray(pl_obs_off).size != n_planes + 1:
+            raise ValueError("pl_obs_off needs n_planes + 1 entries")
+        npo = int(poff[n_planes])
+        loc, G, wk, wp = f64(pl_obs_local, 4), f64(pl_obs_G, 16), f64(w_plane_kf, 1), f64(w_plane_point, 1)
+        if min(np.asarray(pl_obs_kf).size, loc.size // 4, G.size // 16, np.asarray(w_plane_kf).size, np.asarray(w_plane_point).size) < npo:
+            raise ValueError("pl_obs_off runs past the plane observation arrays")
+        rc_, rn, rw = f64(room_center, 3), _i32(room_n_walls), _i32(np.asarray(room_wall, np.int32).reshape(-1))
+        if np.asarray(room_n_walls).size != n_rooms or np.asarray(room_wall).size != 4 * n_rooms:
+            raise ValueError("room_n_walls needs one entry and room_wall four per room")
+        sig = _f32(inv_level_sigma2)
+        handles = (C.c_void_p * max(K, 1))(*[f.handle for f in keyframes])
+        dp = C.POINTER(C.c_double)
+        out = {"kf_Tcw": np.zeros((max(K, 1), 7), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
+               "erase": np.zeros(max(nobs, 1), np.uint8), "chi2": np.zeros(max(nobs, 1), np.float64),
+               "plane_eq": np.zeros((max(n_planes, 1), 4), np.float64), "room_center": np.zeros((max(n_rooms, 1), 3), np.float64),
+               "erase_plane": np.zeros(max(npo, 1), np.uint8), "chi2_plane_kf": np.full(max(npo, 1), np.nan),
+               "chi2_plane_point": np.full(max(npo, 1), np.nan)}
+        res = SGraphLocalBaResult()
+        flag = None if stop_flag is None else _p(stop_flag, _u8p)
+        _check(self._L.vsg_mappoints_local_bundle_adjustment_sgraph(
+            self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
+            C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
+            int(np.asarray(inv_level_sigma2).size), int(iterations), flag, C.cast(_p(out["kf_Tcw"], dp), C.POINTER(PoseSE3d)),
+            _p(out["world_pos"], _f32p), _p(out["erase"], _u8p), _p(out["chi2"], dp),
+            n_planes, _p(eq, dp), _p(poff, _i32p), _p(pkf, _i32p), _p(loc, dp), _p(G, dp), _p(wk, dp), _p(wp, dp),
+            n_rooms, _p(rc_, dp), _p(rn, _i32p), _p(rw, _i32p), _p(out["plane_eq"], dp), _p(out["room_center"], dp),
+            _p(out["erase_plane"], _u8p), _p(out["chi2_plane_kf"], dp), _p(out["chi2_plane_point"], dp), C.byref(res)),
+            "vsg_mappoints_local_bundle_adjustment_sgraph")
+        if not res.local.ran:  # nothing was written: the outs are the inputs
+            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
+            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
+            out["plane_eq"][:n_planes] = eq.reshape(-1, 4)[:n_planes]
+            out["room_center"][:n_rooms] = rc_.reshape(-1, 3)[:n_rooms]
+        got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "erase": out["erase"][:nobs], "chi2": out["chi2"][:nobs],
+               "plane_eq": out["plane_eq"][:n_planes], "room_center": out["room_center"][:n_rooms],
+               "erase_plane": out["erase_plane"][:npo], "chi2_plane_kf": out["chi2_plane_kf"][:npo],
+               "chi2_plane_point": out["chi2_plane_point"][:npo]}
+        got.update({k: int(getattr(res.local, k)) for k in LOCAL_BA_RESULT_INTS})
+        got.update({k: float(getattr(res.local, k)) for k in LOCAL_BA_RESULT_DOUBLES})
+        got.update({k: int(getattr(res, k)) for k in SGRAPH_LOCAL_BA_RESULT_INTS if k != "reserved"})
         return got
 
     def GlobalBundleAdjustment(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
