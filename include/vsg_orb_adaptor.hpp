@@ -727,9 +727,7 @@ class ResidentMapPoints {
                                       const std::vector<float> &mvInvLevelSigma2, int iterations = 10,
                                       const volatile uint8_t *pbStopFlag = nullptr) {
     const size_t n = slots.size(), K = keyFrames.size();
-    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || kfTcw.size() != K || kfFixed.size() != K ||
-        kfCam.size() != K || (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())))
-      throw std::runtime_error("ResidentMapPoints::LocalBundleAdjustment: the arrays' sizes do not match");
+    ba_check_sizes("LocalBundleAdjustment", slots, obsOff, obsKf, obsIdx, K, kfTcw.size(), kfFixed.size(), kfCam.size());
     const size_t E = n ? (size_t)obsOff[n] : 0;
     LocalBAResult r;
     r.kfTcw.resize(K), r.worldPos.assign(3 * n, 0.0f), r.erase.assign(E, 0), r.chi2.assign(E, 0.0);
@@ -741,13 +739,8 @@ class ResidentMapPoints {
                                                 K ? r.kfTcw.data() : &none_kf, n ? r.worldPos.data() : nullptr,
                                                 E ? r.erase.data() : &none_erase, E ? r.chi2.data() : nullptr, &r.res),
           "vsg_mappoints_local_bundle_adjustment");
-    if (!r.res.ran) {  // the reference returned before optimize: nothing was written, the outs are the inputs
-      for (size_t k = 0; k < K; ++k)
-        for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
-      if (n)
-        check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
-              "vsg_mappoints_read");
-    }
+    // the reference returned before optimize: nothing was written
+    if (!r.res.ran) ba_outs_are_inputs(slots, kfTcw, &r.kfTcw, &r.worldPos);
     return r;
   }
   // Optimizer::LocalBundleAdjustment WITH its planes and rooms (vsg_mappoints_local_bundle_adjustment_sgraph): the arguments
@@ -760,10 +753,9 @@ class ResidentMapPoints {
                                                   const std::vector<float> &mvInvLevelSigma2, const SGraphLists &sg,
                                                   int iterations = 10, const volatile uint8_t *pbStopFlag = nullptr) {
     const size_t n = slots.size(), K = keyFrames.size(), Pl = sg.planeEq.size() / 4, R = sg.roomCenter.size() / 3;
-    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || kfTcw.size() != K || kfFixed.size() != K ||
-        kfCam.size() != K || (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())) || sg.planeEq.size() != 4 * Pl ||
-        sg.planeObsOff.size() != Pl + 1 || sg.roomCenter.size() != 3 * R || sg.roomNWalls.size() != R || sg.roomWall.size() != 4 * R)
-      throw std::runtime_error("ResidentMapPoints::LocalBundleAdjustmentSGraph: the arrays' sizes do not match");
+    ba_check_sizes("LocalBundleAdjustmentSGraph", slots, obsOff, obsKf, obsIdx, K, kfTcw.size(), kfFixed.size(), kfCam.size(),
+                   sg.planeEq.size() != 4 * Pl || sg.planeObsOff.size() != Pl + 1 || sg.roomCenter.size() != 3 * R ||
+                       sg.roomNWalls.size() != R || sg.roomWall.size() != 4 * R);
     const size_t E = n ? (size_t)obsOff[n] : 0, NO = sg.planeObsOff[Pl] > 0 ? (size_t)sg.planeObsOff[Pl] : 0;
     if (sg.planeObsKf.size() < NO || sg.planeObsLocal.size() < 4 * NO || sg.planeObsG.size() < 16 * NO || sg.wPlaneKf.size() < NO ||
         sg.wPlanePoint.size() < NO)
@@ -783,13 +775,8 @@ class ResidentMapPoints {
               sg.roomNWalls.data(), sg.roomWall.data(), r.planeEq.data(), r.roomCenter.data(), r.erasePlane.data(),
               NO ? r.chi2PlaneKf.data() : nullptr, NO ? r.chi2PlanePoint.data() : nullptr, &r.res),
           "vsg_mappoints_local_bundle_adjustment_sgraph");
-    if (!r.res.local.ran) {  // the reference returned before optimize: nothing was written, the outs are the inputs
-      for (size_t k = 0; k < K; ++k)
-        for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
-      if (n)
-        check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
-              "vsg_mappoints_read");
-    }
+    // the reference returned before optimize: nothing was written
+    if (!r.res.local.ran) ba_outs_are_inputs(slots, kfTcw, &r.kfTcw, &r.worldPos);
     return r;
   }
   // The visual part of Optimizer::BundleAdjustment as Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag,
@@ -808,9 +795,7 @@ class ResidentMapPoints {
                                         const volatile uint8_t *pbStopFlag = nullptr, bool bRobust = true,
                                         bool loopKFIsOrigin = false) {
     const size_t n = slots.size(), K = keyFrames.size();
-    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || kfTcw.size() != K || kfFixed.size() != K ||
-        kfCam.size() != K || (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())))
-      throw std::runtime_error("ResidentMapPoints::GlobalBundleAdjustment: the arrays' sizes do not match");
+    ba_check_sizes("GlobalBundleAdjustment", slots, obsOff, obsKf, obsIdx, K, kfTcw.size(), kfFixed.size(), kfCam.size());
     const size_t E = n ? (size_t)obsOff[n] : 0;
     GlobalBAResult r;
     r.kfTcw.resize(K), r.worldPos.assign(3 * n, 0.0f), r.included.assign(n, 0), r.chi2.assign(E, 0.0);
@@ -824,13 +809,8 @@ class ResidentMapPoints {
                                                  K ? r.kfTcw.data() : &none_kf, n ? r.worldPos.data() : none_pos,
                                                  n ? r.included.data() : &none_included, E ? r.chi2.data() : nullptr, &r.res),
           "vsg_mappoints_global_bundle_adjustment");
-    if (!r.res.ran) {  // no edge or the stop flag: only res and included were written, the outs are the inputs
-      for (size_t k = 0; k < K; ++k)
-        for (int d = 0; d < 7; ++d) (d < 4 ? r.kfTcw[k].q[d] : r.kfTcw[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
-      if (n)
-        check(vsg_mappoints_read(mp_, (int)n, slots.data(), r.worldPos.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
-              "vsg_mappoints_read");
-    }
+    // no edge or the stop flag: only res and included were written
+    if (!r.res.ran) ba_outs_are_inputs(slots, kfTcw, &r.kfTcw, &r.worldPos);
     return r;
   }
   // Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
@@ -880,6 +860,24 @@ class ResidentMapPoints {
   vsg_mappoints *handle() const { return mp_; }
 
  private:
+  // the lists and per-keyframe arrays the three bundle adjustments take; `more`: a mismatch among the caller's further arrays
+  static void ba_check_sizes(const char *who, const std::vector<int32_t> &slots, const std::vector<int32_t> &obsOff,
+                             const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx, size_t K, size_t nTcw,
+                             size_t nFixed, size_t nCam, bool more = false) {
+    const size_t n = slots.size();
+    if (obsOff.size() != n + 1 || obsKf.size() != obsIdx.size() || nTcw != K || nFixed != K || nCam != K ||
+        (n > 0 && (obsOff[n] < 0 || (size_t)obsOff[n] > obsKf.size())) || more)
+      throw std::runtime_error(std::string("ResidentMapPoints::") + who + ": the arrays' sizes do not match");
+  }
+  // a bundle adjustment that did not run wrote no pose and no position: the outs are the inputs
+  void ba_outs_are_inputs(const std::vector<int32_t> &slots, const std::vector<vsg_pose_se3> &kfTcw,
+                          std::vector<vsg_pose_se3d> *kfOut, std::vector<float> *worldPos) {
+    for (size_t k = 0; k < kfTcw.size(); ++k)
+      for (int d = 0; d < 7; ++d) (d < 4 ? (*kfOut)[k].q[d] : (*kfOut)[k].t[d - 4]) = d < 4 ? kfTcw[k].q[d] : kfTcw[k].t[d - 4];
+    if (!slots.empty())
+      check(vsg_mappoints_read(mp_, (int)slots.size(), slots.data(), worldPos->data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+            "vsg_mappoints_read");
+  }
   vsg_mappoints *mp_ = nullptr;
 };
 

@@ -1,9 +1,11 @@
-// vsg_ba_kernels.inc -- the kernels and helpers vsg_local_ba.hip and vsg_global_ba.hip have in common, ONE copy: the
-// reduction tree on the wavefronts, the set-up, and the phases around the per-item functions of vsg_local_ba.h that do not
-// depend on the reduced solve or on the outs.  Included inside each file's anonymous namespace (after vsg_frame_int.h and
-// vsg_local_ba.h), so each library object gets its own internal instances.  k_linearise and k_error take the robust kernel
-// as a type: lba::HuberLocal for the local call (an empty object: the operations it always had), gba::Kernel for the global.
-// stage_problem at the end lays one call's lists, start values and scratch out in the calling thread's arenas.
+// vsg_ba_kernels.inc -- the kernels and helpers vsg_local_ba.hip, vsg_sgraph_ba.hip and vsg_global_ba.hip have in common,
+// ONE copy: the set-up, the phases around the per-item functions of vsg_local_ba.h, the one-workgroup reduced solve of the
+// two local calls (k_solve; the global call has vsg_ldl_chain.inc), k_backsub, and the visual write-back their final
+// kernels share.  Included inside each file's anonymous namespace (after vsg_frame_int.h, vsg_local_ba.h, vsg_block_tree.h
+// and vsg_lm_driver.h), so each library object gets its own internal instances of the kernels it launches.  k_linearise and
+// k_error take the robust kernel as a type: lba::HuberLocal for the local calls (an empty object: the operations they always
+// had), gba::Kernel for the global.  At the end, the host's side: ba_prologue checks the store and the keyframes of a call,
+// stage_problem lays its lists, start values and scratch out in the calling thread's arenas.
 
 struct KfTab {
   const KeyPointPOD *kps;
@@ -16,38 +18,6 @@ struct SetupArgs {
   const float *pos;  // the store's GetWorldPos()
   float sig[16];
 };
-
-// the fixed tree of vsg_pose_opt.h over one workgroup of lba::kThreads lanes: butterfly over the wave, the waves serially
-template <int N, bool kMax>
-__device__ __forceinline__ void block_tree(double *acc, double *lds) {
-  const int lane = threadIdx.x & (pose::kWave - 1), wave = threadIdx.x / pose::kWave;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    double v = acc[k];
-#pragma unroll
-    for (int s = 1; s < pose::kWave; s <<= 1) {
-      const double o = __shfl_xor(v, s, pose::kWave);
-      v = kMax ? (v < o ? o : v) : v + o;
-    }
-    acc[k] = v;
-  }
-  __syncthreads();  // the previous tree's readers are done with lds
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < N; k++) lds[wave * N + k] = acc[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    double t = lds[k];
-#pragma unroll
-    for (int w = 1; w < pose::kWaves; w++) {
-      const double o = lds[w * N + k];
-      t = kMax ? (t < o ? o : t) : t + o;
-    }
-    acc[k] = t;
-  }
-}
 
 // Optimizer.cc:1850-1948 (local) / :143-287 (global) for the listed observations: the measurement, the information and the
 // kind of every edge; the points' estimates from the store into both buffers
@@ -138,6 +108,74 @@ __global__ __launch_bounds__(lba::kThreads) void k_schur(lba::Prob p, int it, in
   if (tid == 0) lba::bschur_store(p, g - Gs, acc);
 }
 
+// The reduced system in ONE workgroup: a right-looking LDL^T sweep over the lower triangle in global memory (6 x 128
+// keyframes are 768 rows, 4.7 MB of doubles: past LDS, inside L2), column k's multipliers staged in LDS, then the forward
+// and backward substitutions with the right-hand side in LDS.  Element (i, j) takes -(L_ik L_jk) D_k in ascending k, which
+// is what lba::solve_reduced_host's left-looking loops give it.  One code path for every n <= kN = kSolveRows; a template
+// so that only a file that launches it gets an instance (vsg_global_ba.hip does not).
+enum { kSolveRows = 6 * lba::kMaxOptKf };
+template <int kN>
+__global__ __launch_bounds__(lba::kSolveThreads) void k_solve(lba::Prob p, int it, int q) {
+  enum { T = lba::kSolveThreads, W = lba::kSolveTile };
+  __shared__ double l[kN], D[kN], y[kN];
+  __shared__ int bad;
+  if (!lba::run_trial(*p.S, it, q)) return;
+  const int n = p.n, tid = threadIdx.x, tx = tid % W, ty = tid / W;
+  double *M = p.M;
+  if (tid == 0) bad = 0;
+  for (int k = 0; k < n; k++) {
+    __syncthreads();  // step k - 1's updates are visible; its readers are done with l
+    const double d = M[(size_t)k * n + k];
+    if (tid == 0) {
+      D[k] = d;
+      if (d <= 0.0) bad = 1;
+    }
+    for (int i = k + 1 + tid; i < n; i += T) {
+      const double v = M[(size_t)i * n + k] / d;
+      M[(size_t)i * n + k] = v, l[i] = v;
+    }
+    __syncthreads();
+    for (int i = k + 1 + ty; i < n; i += T / W) {
+      const double li = l[i];
+      for (int j = k + 1 + tx; j <= i; j += W) M[(size_t)i * n + j] = M[(size_t)i * n + j] - (li * l[j]) * d;
+    }
+  }
+  for (int i = tid; i < n; i += T) y[i] = p.bs[i];
+  for (int k = 0; k < n; k++) {
+    __syncthreads();
+    const double yk = y[k];
+    for (int i = k + 1 + tid; i < n; i += T) y[i] = y[i] - M[(size_t)i * n + k] * yk;
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += T) y[i] = y[i] / D[i];
+  for (int k = n - 1; k >= 0; k--) {
+    __syncthreads();
+    const double xk = y[k];
+    for (int i = tid; i < k; i += T) y[i] = y[i] - M[(size_t)k * n + i] * xk;
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += T) p.xp[i] = y[i];
+  if (tid == 0) *p.ok2 = bad ? 0 : 1;
+}
+
+// workgroups [0, Gp): one lane per point; [Gp, ...): the optimised keyframes' oplus, one lane per keyframe.  The local
+// calls launch ONE such workgroup (Ko <= lba::kMaxOptKf < lba::kThreads), the global call as many as its keyframes need.
+__global__ __launch_bounds__(lba::kThreads) void k_backsub(lba::Prob p, int it, int q) {
+  __shared__ double lds[pose::kWaves];
+  if (!lba::run_trial(*p.S, it, q)) return;
+  const int g = blockIdx.x, tid = threadIdx.x, cur = p.S->cur;
+  if (g >= p.Gp) {
+    const int i = (g - p.Gp) * lba::kThreads + tid;
+    if (i < p.Ko) lba::oplus_kf(p, i, cur);
+    return;
+  }
+  const int pt = g * lba::kThreads + tid;
+  double v = pt < p.P ? lba::backsub_point(p, pt, cur, p.S->lambda) : 0.0;
+  block_tree<1, false>(&v, lds);
+  if (tid == 0) p.scalePart[g] = v;
+}
+static_assert(lba::kMaxOptKf <= lba::kThreads, "one workgroup of k_backsub takes the local calls' keyframes");
+
 template <class Kernel>
 __global__ __launch_bounds__(lba::kThreads) void k_error(lba::Prob p, int it, int q, Kernel kernel) {
   __shared__ double lds[pose::kWaves];
@@ -158,9 +196,56 @@ __global__ void k_decide(lba::Prob p, int it, int q, lba::State *mirror) {
   *mirror = *p.S;
 }
 
-template <class T>
-void put(uint8_t *base, size_t off, const std::vector<T> &v) {
-  if (!v.empty()) memcpy(base + off, v.data(), v.size() * sizeof(T));
+// what the final kernels' visual write-back writes and reads: the caller's two outs, then what stage_problem fills
+struct WriteBack {
+  vsg_pose_se3d *kf_out;
+  float *pos_out;
+  const int32_t *slots;
+  float *pos;  // the store's, written when write_store
+  const vsg_pose_se3 *Tcw;
+  const int32_t *opt_of;
+};
+
+// Lane i of a final kernel: keyframe i's pose (a vertex's estimate, else its input, widened) and point i's position (a
+// vertex's estimate, else what the store holds), which goes back into the store when write_store
+__device__ __forceinline__ void write_back(const lba::Prob &p, const WriteBack &A, int i, int cur, bool write_store) {
+  if (i < p.K) A.kf_out[i] = A.opt_of[i] >= 0 ? lba::pose_out(p.est[cur][i]) : lba::pose_widened(A.Tcw[i]);
+  if (i < p.P) {
+    const size_t s = (size_t)A.slots[i];
+    const bool vertex = p.p_off[i] != p.p_off[i + 1];
+    for (int d = 0; d < 3; d++) {
+      const float v = vertex ? pose::canonf((float)p.X[cur][3 * (size_t)i + d]) : A.pos[3 * s + d];
+      A.pos_out[3 * (size_t)i + d] = v;
+      if (vertex && write_store) A.pos[3 * s + d] = v;
+    }
+  }
+}
+
+// What the three entry points check before their topology: the store, the keyframes (resident, on the store's device) and
+// the pointers every one of them needs, with outs_ok the caller's own.  Then, per keyframe, what check_and_build asks for:
+// kf_n = the features whose octave the host can see, nleft, and the octave itself.
+struct KfLists {
+  vsg_frame *const *kfs;
+  std::vector<int32_t> kf_n, nleft;
+  auto octave() const {
+    vsg_frame *const *f = kfs;
+    return [f](int k, int i) { return (int)f[k]->h_kps[(size_t)i].octave; };
+  }
+};
+
+int ba_prologue(vsg_mappoints *mp, int n_kf, vsg_frame *const *kfs, const vsg_pose_se3 *kf_Tcw, const uint8_t *kf_fixed,
+                const vsg_ba_camera *kf_cam, const float *inv_level_sigma2, bool outs_ok, StoreFields *F, KfLists *L) {
+  if (!store_fields(mp, F) || n_kf < 0 || !inv_level_sigma2 || !outs_ok) return VSG_ERR_INVALID;
+  if (n_kf > 0 && (!kfs || !kf_Tcw || !kf_fixed || !kf_cam)) return VSG_ERR_INVALID;
+  for (int k = 0; k < n_kf; k++)
+    if (frame_check(kfs[k]) != VSG_OK || kfs[k]->device != F->device) return VSG_ERR_INVALID;
+  L->kfs = kfs, L->kf_n.resize((size_t)n_kf), L->nleft.resize((size_t)n_kf);
+  for (int k = 0; k < n_kf; k++) {
+    const size_t have = kfs[k]->h_kps.size();
+    L->kf_n[(size_t)k] = (int32_t)((size_t)kfs[k]->n < have ? (size_t)kfs[k]->n : have);
+    L->nleft[(size_t)k] = kfs[k]->nleft;
+  }
+  return VSG_OK;
 }
 
 // One call's problem in the CALLING THREAD's arenas.  The pinned arena holds the lists and start values (copied to the device
@@ -172,8 +257,7 @@ struct Staged {
   size_t in_bytes, Ge, Gp, out_off[4], dev_off[4];
   uint8_t *hp, *dp, *dv;            // pinned arena (host address, device alias), device arena
   lba::State *mirror, *mirror_dev;  // the controller's record for the host's look
-  const vsg_pose_se3 *Tcw_dev;      // the keyframes' input poses and their index among the optimised ones, on the device
-  const int32_t *opt_of_dev;
+  WriteBack wb;                     // the final kernel's: slots, the store, the input poses, opt_of; the caller sets the outs
   unsigned gAll;                    // workgroups that cover edges, points and keyframes
   int Gs;                           // workgroups of Schur blocks
 };
@@ -245,7 +329,8 @@ int stage_problem(ThreadCtx *c, const StoreFields &F, const lba::Topology &T, co
   memset(&SA, 0, sizeof(SA));
   SA.tab = (const KfTab *)(dv + oTab), SA.e_idx = (const int32_t *)(dv + oEidx), SA.slots = (const int32_t *)(dv + oSlots), SA.pos = F.pos;
   for (int l = 0; l < 16; l++) SA.sig[l] = inv_level_sigma2[l < nlevels ? l : nlevels - 1];
-  G->Tcw_dev = (const vsg_pose_se3 *)(dv + oTcw), G->opt_of_dev = (const int32_t *)(dv + oOptOf);
+  memset(&G->wb, 0, sizeof(G->wb));
+  G->wb.slots = SA.slots, G->wb.pos = F.pos, G->wb.Tcw = (const vsg_pose_se3 *)(dv + oTcw), G->wb.opt_of = (const int32_t *)(dv + oOptOf);
   const size_t most = E > P ? (E > K ? E : K) : (P > K ? P : K);
   G->gAll = (unsigned)((most + lba::kThreads - 1) / lba::kThreads);
   G->Gs = (int)((nb + kBlocksPerGroup - 1) / kBlocksPerGroup);

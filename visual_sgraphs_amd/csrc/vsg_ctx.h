@@ -15,6 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <vector>
 
 #include "../../include/vsg_orb.h"
 
@@ -60,6 +63,11 @@ struct Stage {
     return off;
   }
 };
+// a list into its block of an arena laid out with Stage
+template <class T>
+void put(uint8_t *base, size_t off, const std::vector<T> &v) {
+  if (!v.empty()) memcpy(base + off, v.data(), v.size() * sizeof(T));
+}
 
 // roctx ranges around stages and entry points (the REGISTER_TIMES analogue for profilers: SURVEY 5 "tracing";
 // orb_slam3/include/Settings.h:23).  Off unless VSG_ROCTX=1 (one getenv at first use); the marker library

@@ -7,7 +7,7 @@
 // and vsg_global_ba.hip: no grid-wide barrier, no cooperative launch, no flag between workgroups, nothing spins.  The
 // Levenberg controller (lba::State) lives in device memory, is written by the one-lane steps k_eg_begin and k_eg_decide
 // alone, and is read first by every kernel, the solver's included, which returns at once when its iteration or trial is not
-// to run.  The host enqueues one trial and looks at the controller's mirror in the pinned arena, the global call's policy.
+// to run.  The host's enqueue policy is csrc/vsg_lm_driver.h, the bundle adjustments' too.
 //
 // Per iteration: k_eg_linearise (ONE WAVE PER EDGE: lanes 0-27 each take one (vertex, column, sign) of the numeric Jacobian,
 // lane 28 the error itself -- 29 evaluations of Sim3::log() side by side -- then the 64 lanes split the 119 entries of the
@@ -18,8 +18,10 @@
 // All stores are plain vector stores; there is no atomic of any kind.
 #include <cstring>
 
+#include "vsg_block_tree.h"
 #include "vsg_essential_graph.h"
 #include "vsg_frame_int.h"
+#include "vsg_lm_driver.h"
 
 using namespace vsg;
 
@@ -27,20 +29,6 @@ namespace {
 
 enum { kThreads = lba::kThreads, W = gba::kPanel, TS = gba::kTile, WP = W + 1, kEdgesPerGroup = kThreads / pose::kWave };
 #include "vsg_ldl_chain.inc"
-
-// the fixed tree of vsg_pose_opt.h over one workgroup: butterfly over the wave, the waves serially
-__device__ __forceinline__ double chi_tree(double v, double *lds) {
-  const int lane = threadIdx.x & (pose::kWave - 1), wave = threadIdx.x / pose::kWave;
-#pragma unroll
-  for (int s = 1; s < pose::kWave; s <<= 1) v = v + __shfl_xor(v, s, pose::kWave);
-  __syncthreads();
-  if (lane == 0) lds[wave] = v;
-  __syncthreads();
-  double t = lds[0];
-#pragma unroll
-  for (int w = 1; w < pose::kWaves; w++) t = t + lds[w];
-  return t;
-}
 
 struct FinalArgs {
   const int32_t *opt_of, *slots, *point_ref;
@@ -102,7 +90,8 @@ __global__ __launch_bounds__(kThreads) void k_eg_gather(eg::Prob p, int it) {
   const int g = blockIdx.x, tid = threadIdx.x;
   if (g < p.Ge) {
     const int e = g * kThreads + tid;
-    const double v = chi_tree(e < p.E ? p.chi2[e] : 0.0, lds);
+    double v = e < p.E ? p.chi2[e] : 0.0;
+    block_tree<1, false>(&v, lds);
     if (tid == 0) p.chiPart[g] = v;
     return;
   }
@@ -134,7 +123,8 @@ __global__ __launch_bounds__(kThreads) void k_eg_error(eg::Prob p, int it, int q
   __shared__ double lds[pose::kWaves];
   if (!lba::run_trial(*p.S, it, q)) return;
   const int e = blockIdx.x * kThreads + threadIdx.x;
-  const double v = chi_tree(e < p.E ? eg::edge_cost(p, e, p.S->cur ^ 1) : 0.0, lds);
+  double v = e < p.E ? eg::edge_cost(p, e, p.S->cur ^ 1) : 0.0;
+  block_tree<1, false>(&v, lds);
   if (threadIdx.x == 0) p.chiPart[blockIdx.x] = v;
 }
 
@@ -168,11 +158,6 @@ __global__ __launch_bounds__(kThreads) void k_eg_correct(CorrectArgs A) {
   float out[3];
   eg::correct_point(sim3opt::sim3_of(A.from[r]), sim3opt::sim3_of(A.to_inv[r]), in, out);
   for (int d = 0; d < 3; d++) A.pos[3 * s + d] = out[d], A.pos_out[3 * (size_t)i + d] = out[d];
-}
-
-template <class T>
-void put(uint8_t *base, size_t off, const std::vector<T> &v) {
-  if (!v.empty()) memcpy(base + off, v.data(), v.size() * sizeof(T));
 }
 
 }  // namespace
@@ -257,38 +242,30 @@ int vsg_mappoints_optimize_essential_graph(vsg_mappoints *mp, int n_kf, const vs
   FA.pos_out = (float *)(dp + oPosOut), FA.P = n_points;
 
   TRY_HIP(hipMemcpyAsync(dv, hp, in_bytes, hipMemcpyHostToDevice, c->stream));
-  // from here on an error waits for the stream before it returns: the arenas belong to the next call
   hipStream_t st = c->stream;
   const dim3 B(kThreads);
   const size_t most = E > K ? (E > P ? E : P) : (K > P ? K : P), most14 = most > (size_t)eg::kPert ? most : (size_t)eg::kPert;
   const unsigned gAll = (unsigned)((most14 + kThreads - 1) / kThreads), gLin = (unsigned)((E + kEdgesPerGroup - 1) / kEdgesPerGroup);
   const unsigned gAsm = (unsigned)((nb * eg::kDim * eg::kDim + kThreads - 1) / kThreads), gKo = (unsigned)((Ko + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(k_eg_setup, dim3(gAll), B, 0, st, p);
-  bool failed = false;
-  for (int it = 0; it < iterations && !failed; it++) {
-    hipLaunchKernelGGL(k_eg_linearise, dim3(gLin), B, 0, st, p, it);
-    hipLaunchKernelGGL(k_eg_gather, dim3((unsigned)(Ge + Gb)), B, 0, st, p, it);
-    hipLaunchKernelGGL(k_eg_begin, dim3(1), dim3(1), 0, st, p, it, mirror_dev);
-    bool closed = false;
-    // one trial is enqueued, then the host looks (the global call's policy: every further slot is a chain of launches that
-    // return at once in the common case of one trial per iteration)
-    for (int q = 0; q < lba::kTrials && !closed && !failed; q++) {
-      hipLaunchKernelGGL(k_eg_assemble, dim3(gAsm), B, 0, st, p, it, q);
-      enqueue_solve(st, sv, it, q);
-      hipLaunchKernelGGL(k_eg_oplus, dim3(gKo), B, 0, st, p, it, q);
-      hipLaunchKernelGGL(k_eg_error, dim3((unsigned)Ge), B, 0, st, p, it, q);
-      hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(1), 0, st, p, it, q, mirror_dev);
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) failed = true;
-      closed = failed || mirror->finished || !(mirror->iter == it && mirror->trial_open);
-    }
-    if (failed || mirror->finished) break;
-  }
-  if (!failed) {
-    hipLaunchKernelGGL(k_eg_final, dim3(gAll), B, 0, st, p, FA);
-    if (hipGetLastError() != hipSuccess) failed = true;
-  }
-  if (hipStreamSynchronize(st) != hipSuccess || failed) return VSG_ERR_HIP;
-  const lba::State Sfin = *mirror;
+  lba::State Sfin;
+  const bool done = lm::run(
+      st, mirror, iterations, lm::kTrialSlots, nullptr,
+      [&](int it) {
+        hipLaunchKernelGGL(k_eg_linearise, dim3(gLin), B, 0, st, p, it);
+        hipLaunchKernelGGL(k_eg_gather, dim3((unsigned)(Ge + Gb)), B, 0, st, p, it);
+        hipLaunchKernelGGL(k_eg_begin, dim3(1), dim3(1), 0, st, p, it, mirror_dev);
+      },
+      [&](int it, int q) {
+        hipLaunchKernelGGL(k_eg_assemble, dim3(gAsm), B, 0, st, p, it, q);
+        enqueue_solve(st, sv, it, q);
+        hipLaunchKernelGGL(k_eg_oplus, dim3(gKo), B, 0, st, p, it, q);
+        hipLaunchKernelGGL(k_eg_error, dim3((unsigned)Ge), B, 0, st, p, it, q);
+        hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(1), 0, st, p, it, q, mirror_dev);
+      },
+      [&] { hipLaunchKernelGGL(k_eg_final, dim3(gAll), B, 0, st, p, FA); },
+      &Sfin);
+  if (!done) return VSG_ERR_HIP;
   eg::fill_result(res, T, &Sfin);
   memcpy(kf_Scw_out, hp + oKfOut, K * sizeof(vsg_sim3d));
   if (chi2) memcpy(chi2, hp + oChi2, E * 8);

@@ -1,9 +1,9 @@
 // vsg_global_ba.hip -- the visual part of Optimizer::BundleAdjustment (Optimizer.cc:60-287, :500-610) on resident keyframes
 // and resident map points: vsg_mappoints_global_bundle_adjustment (include/vsg_orb.h).  The arithmetic is csrc/vsg_local_ba.h
 // with the kernel type and the blocked schedule of csrc/vsg_global_ba.h, shared with the host build bit for bit; this file
-// adds the kernels that differ from the local call's (k_backsub, k_final) and the enqueue policy; the kernels both calls have in
-// common are ONE copy, csrc/vsg_ba_kernels.inc, and the reduced solve's chain is csrc/vsg_ldl_chain.inc, which
-// vsg_essential_graph.hip includes too.
+// adds the final kernel and the entry points.  The kernels both calls have in common are ONE copy, csrc/vsg_ba_kernels.inc;
+// the reduced solve's chain is csrc/vsg_ldl_chain.inc, which vsg_essential_graph.hip includes too; the enqueue policy is
+// csrc/vsg_lm_driver.h.
 //
 // KERNEL BOUNDARIES ON THE CALLING THREAD'S STREAM ARE THE ONLY SYNCHRONISATION BETWEEN WORKGROUPS, as in vsg_local_ba.hip:
 // no grid-wide barrier, no cooperative launch, no flag between workgroups, nothing spins.  The Levenberg controller
@@ -28,8 +28,10 @@
 #include <cstring>
 
 #include "../../include/vsg_orb_debug_global_ba.h"
+#include "vsg_block_tree.h"
 #include "vsg_frame_int.h"
 #include "vsg_global_ba.h"
+#include "vsg_lm_driver.h"
 
 using namespace vsg;
 
@@ -39,48 +41,18 @@ enum { kThreads = lba::kThreads, W = gba::kPanel, TS = gba::kTile, WP = W + 1 };
 #include "vsg_ba_kernels.inc"
 
 struct FinalArgs {
-  const int32_t *slots;
-  float *pos;  // the store's, written when write_store
-  const vsg_pose_se3 *Tcw;
-  const int32_t *opt_of;
+  WriteBack wb;
   double *chi2;
-  vsg_pose_se3d *kf_out;
-  float *pos_out;
   int write_store;
 };
 
 #include "vsg_ldl_chain.inc"
 
-// workgroups [0, Gp): one lane per point; [Gp, Gp + Gk): the optimised keyframes' oplus, one lane per keyframe
-__global__ __launch_bounds__(kThreads) void k_backsub(lba::Prob p, int it, int q) {
-  __shared__ double lds[pose::kWaves];
-  if (!lba::run_trial(*p.S, it, q)) return;
-  const int g = blockIdx.x, tid = threadIdx.x, cur = p.S->cur;
-  if (g >= p.Gp) {
-    const int i = (g - p.Gp) * kThreads + tid;
-    if (i < p.Ko) lba::oplus_kf(p, i, cur);
-    return;
-  }
-  const int pt = g * kThreads + tid;
-  double v = pt < p.P ? lba::backsub_point(p, pt, cur, p.S->lambda) : 0.0;
-  block_tree<1, false>(&v, lds);
-  if (tid == 0) p.scalePart[g] = v;
-}
-
 // the write-back (:500-610): the poses, the positions (into the store when write_store), chi2 per edge
 __global__ __launch_bounds__(kThreads) void k_final(lba::Prob p, FinalArgs A) {
   const int i = blockIdx.x * kThreads + threadIdx.x, cur = p.S->cur;
   if (i < p.E) A.chi2[i] = pose::canon(p.chi2[i]);
-  if (i < p.K) A.kf_out[i] = A.opt_of[i] >= 0 ? lba::pose_out(p.est[cur][i]) : lba::pose_widened(A.Tcw[i]);
-  if (i < p.P) {
-    const size_t s = (size_t)A.slots[i];
-    const bool vertex = p.p_off[i] != p.p_off[i + 1];
-    for (int d = 0; d < 3; d++) {
-      const float v = vertex ? pose::canonf((float)p.X[cur][3 * (size_t)i + d]) : A.pos[3 * s + d];
-      A.pos_out[3 * (size_t)i + d] = v;
-      if (vertex && A.write_store) A.pos[3 * s + d] = v;
-    }
-  }
+  write_back(p, A.wb, i, cur, A.write_store != 0);
 }
 
 // a controller record under which every kernel of the chain runs as trial (0, 0): the debug hook's
@@ -143,22 +115,13 @@ int vsg_mappoints_global_bundle_adjustment(vsg_mappoints *mp, int n_points, cons
                                            int write_store, const volatile uint8_t *stop_flag, vsg_pose_se3d *kf_Tcw_out,
                                            float *world_pos_out, uint8_t *included, double *chi2, vsg_global_ba_result *res) {
   StoreFields F;
-  if (!store_fields(mp, &F) || n_kf < 0 || !inv_level_sigma2 || !kf_Tcw_out || !included || !res) return VSG_ERR_INVALID;
-  if (n_kf > 0 && (!kfs || !kf_Tcw || !kf_fixed || !kf_cam)) return VSG_ERR_INVALID;
-  for (int k = 0; k < n_kf; k++)
-    if (frame_check(kfs[k]) != VSG_OK || kfs[k]->device != F.device) return VSG_ERR_INVALID;
-  std::vector<int32_t> kf_n((size_t)n_kf), nleft((size_t)n_kf);
-  for (int k = 0; k < n_kf; k++) {
-    const size_t have = kfs[k]->h_kps.size();
-    kf_n[(size_t)k] = (int32_t)((size_t)kfs[k]->n < have ? (size_t)kfs[k]->n : have);
-    nleft[(size_t)k] = kfs[k]->nleft;
-  }
+  KfLists L;
+  int rc = ba_prologue(mp, n_kf, kfs, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2, kf_Tcw_out && included && res, &F, &L);
+  if (rc != VSG_OK) return rc;
   lba::Topology T;
   int ran = 0;
-  int rc = gba::check_and_build(
-      n_points, slots, obs_off, obs_kf, obs_idx, n_kf, kf_n.data(), nleft.data(),
-      [&](int k, int i) { return (int)kfs[k]->h_kps[(size_t)i].octave; }, kf_fixed, F.capacity, nlevels, iterations, robust,
-      write_store, world_pos_out, stop_flag, &T, &ran);
+  rc = gba::check_and_build(n_points, slots, obs_off, obs_kf, obs_idx, n_kf, L.kf_n.data(), L.nleft.data(), L.octave(), kf_fixed,
+                            F.capacity, nlevels, iterations, robust, write_store, world_pos_out, stop_flag, &T, &ran);
   if (rc != VSG_OK) return rc;
   if (!ran) {
     if (n_points == 0) T.n_fixed = T.n_opt = 0;
@@ -178,58 +141,41 @@ int vsg_mappoints_global_bundle_adjustment(vsg_mappoints *mp, int n_points, cons
   if (rc != VSG_OK) return rc;
   gba::fill_included(included, n_points, obs_off);  // the first out written: no refusal and no failed reservation is left
   const lba::Prob &p = G.p;
-  const SetupArgs &SA = G.SA;
   uint8_t *hp = G.hp, *dp = G.dp, *dv = G.dv;
-  const size_t in_bytes = G.in_bytes, Ge = G.Ge, Gp = G.Gp, oChi2 = G.out_off[0], oKfOut = G.out_off[1], oPosOut = G.out_off[2];
-  lba::State *mirror = G.mirror, *mirror_dev = G.mirror_dev;
+  const size_t Ge = G.Ge, Gp = G.Gp, oChi2 = G.out_off[0], oKfOut = G.out_off[1], oPosOut = G.out_off[2];
+  lba::State *mirror_dev = G.mirror_dev;
   Solve sv;
   sv.n = (int)n, sv.M = p.M, sv.bs = p.bs, sv.xp = p.xp, sv.D = (double *)(dv + G.dev_off[0]), sv.y = (double *)(dv + G.dev_off[1]);
   sv.acc = (double *)(dv + G.dev_off[2]), sv.ok2 = p.ok2, sv.S = p.S;
   FinalArgs FA;
-  FA.slots = SA.slots, FA.pos = F.pos, FA.Tcw = G.Tcw_dev, FA.opt_of = G.opt_of_dev;
-  FA.chi2 = (double *)(dp + oChi2), FA.kf_out = (vsg_pose_se3d *)(dp + oKfOut), FA.pos_out = (float *)(dp + oPosOut);
-  FA.write_store = write_store;
+  FA.wb = G.wb, FA.wb.kf_out = (vsg_pose_se3d *)(dp + oKfOut), FA.wb.pos_out = (float *)(dp + oPosOut);
+  FA.chi2 = (double *)(dp + oChi2), FA.write_store = write_store;
   const gba::Kernel kernel{robust};
 
-  TRY_HIP(hipMemcpyAsync(dv, hp, in_bytes, hipMemcpyHostToDevice, c->stream));
-  // from here on an error waits for the stream before it returns: the arenas belong to the next call
+  TRY_HIP(hipMemcpyAsync(dv, hp, G.in_bytes, hipMemcpyHostToDevice, c->stream));
   hipStream_t st = c->stream;
   const dim3 B(kThreads);
-  const unsigned gAll = G.gAll;
   const int Gs = G.Gs;
-  hipLaunchKernelGGL(k_setup, dim3(gAll), B, 0, st, p, SA);
-  bool failed = false, stopped = false;
-  for (int it = 0; it < iterations && !failed; it++) {
-    hipLaunchKernelGGL(k_linearise<gba::Kernel>, dim3((unsigned)Ge), B, 0, st, p, it, kernel);
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)(Gp + Ko)), B, 0, st, p, it);
-    hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, st, p, it, mirror_dev);
-    bool closed = false;
-    // one trial is enqueued, then the host looks (the local call's measured policy: every further slot is a chain of
-    // launches that return at once in the common case of one trial per iteration)
-    for (int q = 0; q < lba::kTrials && !closed && !failed; q++) {
-      hipLaunchKernelGGL(k_trial_edges, dim3((unsigned)Ge), B, 0, st, p, it, q);
-      hipLaunchKernelGGL(k_schur, dim3((unsigned)(Gs + (int)Ko)), B, 0, st, p, it, q, Gs);
-      enqueue_solve(st, sv, it, q);
-      hipLaunchKernelGGL(k_backsub, dim3((unsigned)(Gp + Gk)), B, 0, st, p, it, q);
-      hipLaunchKernelGGL(k_error<gba::Kernel>, dim3((unsigned)Ge), B, 0, st, p, it, q, kernel);
-      hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, st, p, it, q, mirror_dev);
-      // the look: the record in the pinned arena as the last one-lane step left it
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) failed = true;
-      closed = failed || mirror->finished || !(mirror->iter == it && mirror->trial_open);
-    }
-    if (failed || mirror->finished) break;
-    if (stop_flag && *stop_flag) {  // terminate() between iterations (sparse_optimizer.cpp:423)
-      stopped = true;
-      break;
-    }
-  }
-  if (!failed) {
-    hipLaunchKernelGGL(k_final, dim3(gAll), B, 0, st, p, FA);
-    if (hipGetLastError() != hipSuccess) failed = true;
-  }
-  if (hipStreamSynchronize(st) != hipSuccess || failed) return VSG_ERR_HIP;
-  lba::State Sfin = *mirror;
-  if (stopped) Sfin.finished = 1, Sfin.stop_reason = lba::kStopFlag;
+  hipLaunchKernelGGL(k_setup, dim3(G.gAll), B, 0, st, p, G.SA);
+  lba::State Sfin;
+  const bool done = lm::run(
+      st, G.mirror, iterations, lm::kTrialSlots, stop_flag,
+      [&](int it) {
+        hipLaunchKernelGGL(k_linearise<gba::Kernel>, dim3((unsigned)Ge), B, 0, st, p, it, kernel);
+        hipLaunchKernelGGL(k_gather, dim3((unsigned)(Gp + Ko)), B, 0, st, p, it);
+        hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, st, p, it, mirror_dev);
+      },
+      [&](int it, int q) {
+        hipLaunchKernelGGL(k_trial_edges, dim3((unsigned)Ge), B, 0, st, p, it, q);
+        hipLaunchKernelGGL(k_schur, dim3((unsigned)(Gs + (int)Ko)), B, 0, st, p, it, q, Gs);
+        enqueue_solve(st, sv, it, q);
+        hipLaunchKernelGGL(k_backsub, dim3((unsigned)(Gp + Gk)), B, 0, st, p, it, q);
+        hipLaunchKernelGGL(k_error<gba::Kernel>, dim3((unsigned)Ge), B, 0, st, p, it, q, kernel);
+        hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, st, p, it, q, mirror_dev);
+      },
+      [&] { hipLaunchKernelGGL(k_final, dim3(G.gAll), B, 0, st, p, FA); },
+      &Sfin);
+  if (!done) return VSG_ERR_HIP;
   gba::fill_result(res, T, &Sfin);
   if (chi2) memcpy(chi2, hp + oChi2, E * 8);
   memcpy(kf_Tcw_out, hp + oKfOut, K * sizeof(vsg_pose_se3d));

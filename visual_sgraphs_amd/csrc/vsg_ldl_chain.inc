@@ -3,7 +3,8 @@
 // csrc/vsg_global_ba.h (gba::solve_reduced_blocked_host is its host form), gated by lba::run_trial on an lba::State.
 // Included inside each file's anonymous namespace, after vsg_global_ba.h and an
 //   enum { kThreads = lba::kThreads, W = gba::kPanel, TS = gba::kTile, WP = W + 1 };
-// so each library object gets its own internal instances.
+// so each library object gets its own internal instances.  (The two local bundle adjustments solve in one workgroup:
+// k_solve of vsg_ba_kernels.inc.)
 
 static_assert(W % 6 == 0 && W <= kThreads && TS == 64 && kThreads == 256, "the solver's thread maps assume these");
 

@@ -1,7 +1,7 @@
 // vsg_sgraph_ba.hip -- Optimizer::LocalBundleAdjustment with its planes and rooms (Optimizer.cc:1454-2454) on resident
 // keyframes and resident map points: vsg_mappoints_local_bundle_adjustment_sgraph (include/vsg_orb.h).  The arithmetic is
 // csrc/vsg_local_ba.h (the visual part) and csrc/vsg_sgraph_ba.h (planes and rooms), shared with the host build bit for
-// bit; this file adds the semantic kernels, the reduced solve and the enqueue policy.
+// bit; this file adds the semantic kernels and the entry point.  The enqueue policy is csrc/vsg_lm_driver.h.
 //
 // KERNEL BOUNDARIES ON THE CALLING THREAD'S STREAM ARE THE ONLY SYNCHRONISATION BETWEEN WORKGROUPS, as in vsg_local_ba.hip:
 // no grid-wide barrier, no cooperative launch, no flag between workgroups, nothing spins.  The Levenberg controller
@@ -16,11 +16,13 @@
 // the diagonal per semantic row, the keyframes' semantic blocks into Hpp / bp), k_begin.  Per trial: k_trial_edges, k_schur,
 // k_sg_assemble (the blocks behind the keyframes' Schur complement, one lane per entry, and bs), k_solve (ONE workgroup),
 // k_backsub, k_sg_oplus (planes, rooms, computeScale's terms), k_error, k_sg_error, k_decide.  Then k_sg_final.
-// k_solve and k_backsub are the local call's, restated here because vsg_local_ba.hip keeps them in its own unnamed
-// namespace.  All stores are plain vector stores; the two visual edge counts are integer atomics.
+// k_solve and k_backsub are the local call's, in vsg_ba_kernels.inc with the other visual phases.  All stores are plain
+// vector stores; the two visual edge counts are integer atomics.
 #include <cstring>
 
+#include "vsg_block_tree.h"
 #include "vsg_frame_int.h"
+#include "vsg_lm_driver.h"
 #include "vsg_sgraph_ba.h"
 
 using namespace vsg;
@@ -29,78 +31,17 @@ namespace {
 
 #include "vsg_ba_kernels.inc"
 
+static_assert(sgba::kMaxRows == kSolveRows, "k_solve's LDS arrays hold every row this call admits");
+
+// erase and chi2 stand before wb, unlike in the other two calls' structs: k_sg_final allocates 62 SGPRs with this order and 60
+// with wb first, the same occupancy either way
 struct FinalArgs {
-  const int32_t *slots;
-  float *pos;  // the store's, written
-  const vsg_pose_se3 *Tcw;
-  const int32_t *opt_of;
   uint8_t *erase;
   double *chi2;
-  vsg_pose_se3d *kf_out;
-  float *pos_out;
+  WriteBack wb;
   uint8_t *erase_plane;
   double *chi2_kf, *chi2_pp, *plane_out, *room_out;
 };
-
-// vsg_local_ba.hip's k_solve: a right-looking LDL^T sweep over the lower triangle in global memory, column k's multipliers
-// staged in LDS, then the two substitutions; element (i, j) takes -(L_ik L_jk) D_k in ascending k
-__global__ __launch_bounds__(lba::kSolveThreads) void k_solve(lba::Prob p, int it, int q) {
-  enum { kN = sgba::kMaxRows, T = lba::kSolveThreads, W = lba::kSolveTile };
-  __shared__ double l[kN], D[kN], y[kN];
-  __shared__ int bad;
-  if (!lba::run_trial(*p.S, it, q)) return;
-  const int n = p.n, tid = threadIdx.x, tx = tid % W, ty = tid / W;
-  double *M = p.M;
-  if (tid == 0) bad = 0;
-  for (int k = 0; k < n; k++) {
-    __syncthreads();  // step k - 1's updates are visible; its readers are done with l
-    const double d = M[(size_t)k * n + k];
-    if (tid == 0) {
-      D[k] = d;
-      if (d <= 0.0) bad = 1;
-    }
-    for (int i = k + 1 + tid; i < n; i += T) {
-      const double v = M[(size_t)i * n + k] / d;
-      M[(size_t)i * n + k] = v, l[i] = v;
-    }
-    __syncthreads();
-    for (int i = k + 1 + ty; i < n; i += T / W) {
-      const double li = l[i];
-      for (int j = k + 1 + tx; j <= i; j += W) M[(size_t)i * n + j] = M[(size_t)i * n + j] - (li * l[j]) * d;
-    }
-  }
-  for (int i = tid; i < n; i += T) y[i] = p.bs[i];
-  for (int k = 0; k < n; k++) {
-    __syncthreads();
-    const double yk = y[k];
-    for (int i = k + 1 + tid; i < n; i += T) y[i] = y[i] - M[(size_t)i * n + k] * yk;
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += T) y[i] = y[i] / D[i];
-  for (int k = n - 1; k >= 0; k--) {
-    __syncthreads();
-    const double xk = y[k];
-    for (int i = tid; i < k; i += T) y[i] = y[i] - M[(size_t)k * n + i] * xk;
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += T) p.xp[i] = y[i];
-  if (tid == 0) *p.ok2 = bad ? 0 : 1;
-}
-
-// vsg_local_ba.hip's k_backsub: workgroups [0, Gp): one lane per point; workgroup Gp: the optimised keyframes' oplus
-__global__ __launch_bounds__(lba::kThreads) void k_backsub(lba::Prob p, int it, int q) {
-  __shared__ double lds[pose::kWaves];
-  if (!lba::run_trial(*p.S, it, q)) return;
-  const int g = blockIdx.x, tid = threadIdx.x, cur = p.S->cur;
-  if (g == p.Gp) {
-    if (tid < p.Ko) lba::oplus_kf(p, tid, cur);
-    return;
-  }
-  const int pt = g * lba::kThreads + tid;
-  double v = pt < p.P ? lba::backsub_point(p, pt, cur, p.S->lambda) : 0.0;
-  block_tree<1, false>(&v, lds);
-  if (tid == 0) p.scalePart[g] = v;
-}
 
 // one wave per semantic edge, kEdgesPerGroup edges per workgroup
 __global__ __launch_bounds__(lba::kThreads) void k_sg_linearise(lba::Prob p, sgba::Sem s, int it) {
@@ -207,16 +148,7 @@ __global__ __launch_bounds__(lba::kThreads) void k_sg_error(lba::Prob p, sgba::S
 __global__ __launch_bounds__(lba::kThreads) void k_sg_final(lba::Prob p, sgba::Sem s, FinalArgs A) {
   const int i = blockIdx.x * lba::kThreads + threadIdx.x, cur = p.S->cur;
   if (i < p.E) lba::classify_edge(p, i, cur, A.erase, A.chi2);
-  if (i < p.K) A.kf_out[i] = A.opt_of[i] >= 0 ? lba::pose_out(p.est[cur][i]) : lba::pose_widened(A.Tcw[i]);
-  if (i < p.P) {
-    const size_t sl = (size_t)A.slots[i];
-    const bool vertex = p.p_off[i] != p.p_off[i + 1];
-    for (int d = 0; d < 3; d++) {
-      const float v = vertex ? pose::canonf((float)p.X[cur][3 * (size_t)i + d]) : A.pos[3 * sl + d];
-      A.pos_out[3 * (size_t)i + d] = v;
-      if (vertex) A.pos[3 * sl + d] = v;
-    }
-  }
+  write_back(p, A.wb, i, cur, true);
   if (i < s.n_obs) sgba::classify_obs(p, s, i, cur, A.erase_plane, A.chi2_kf, A.chi2_pp);
   if (i < s.Pl && s.pl_act[i] >= 0)
     for (int k = 0; k < 4; k++) A.plane_out[4 * (size_t)i + k] = pose::canon(sgba::planes_of(s, cur)[4 * (size_t)i + k]);
@@ -263,27 +195,18 @@ int vsg_mappoints_local_bundle_adjustment_sgraph(
     double *plane_eq_out, double *room_center_out, uint8_t *erase_plane, double *chi2_plane_kf, double *chi2_plane_point,
     vsg_sgraph_local_ba_result *res) {
   StoreFields F;
-  if (!store_fields(mp, &F) || n_kf < 0 || !inv_level_sigma2 || !kf_Tcw_out || !erase || !res) return VSG_ERR_INVALID;
-  if (n_kf > 0 && (!kfs || !kf_Tcw || !kf_fixed || !kf_cam)) return VSG_ERR_INVALID;
-  for (int k = 0; k < n_kf; k++)
-    if (frame_check(kfs[k]) != VSG_OK || kfs[k]->device != F.device) return VSG_ERR_INVALID;
+  KfLists KL;
+  int rc = ba_prologue(mp, n_kf, kfs, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2, kf_Tcw_out && erase && res, &F, &KL);
+  if (rc != VSG_OK) return rc;
   if ((n_planes > 0 && !plane_eq_out) || (n_rooms > 0 && !room_center_out)) return VSG_ERR_INVALID;
   if (n_planes > 0 && pl_obs_off && pl_obs_off[0] == 0 && pl_obs_off[n_planes] > 0 && !erase_plane) return VSG_ERR_INVALID;
   const sgba::SemIn in = {n_planes, plane_eq, pl_obs_off, pl_obs_kf, pl_obs_local, pl_obs_G, w_plane_kf, w_plane_point,
                           n_rooms,  room_center, room_n_walls, room_wall};
-  std::vector<int32_t> kf_n((size_t)n_kf), nleft((size_t)n_kf);
-  for (int k = 0; k < n_kf; k++) {
-    const size_t have = kfs[k]->h_kps.size();
-    kf_n[(size_t)k] = (int32_t)((size_t)kfs[k]->n < have ? (size_t)kfs[k]->n : have);
-    nleft[(size_t)k] = kfs[k]->nleft;
-  }
   lba::Topology T;
   sgba::SemTopology ST;
   int ran = 0;
-  int rc = sgba::check_and_build(
-      n_points, slots, obs_off, obs_kf, obs_idx, n_kf, kf_n.data(), nleft.data(),
-      [&](int k, int i) { return (int)kfs[k]->h_kps[(size_t)i].octave; }, kf_fixed, F.capacity, nlevels, iterations, stop_flag, in,
-      &T, &ST, &ran);
+  rc = sgba::check_and_build(n_points, slots, obs_off, obs_kf, obs_idx, n_kf, KL.kf_n.data(), KL.nleft.data(), KL.octave(), kf_fixed,
+                             F.capacity, nlevels, iterations, stop_flag, in, &T, &ST, &ran);
   if (rc != VSG_OK) return rc;
   if (!ran) {
     if (n_points == 0) T.n_fixed = T.n_opt = 0;
@@ -333,62 +256,54 @@ int vsg_mappoints_local_bundle_adjustment_sgraph(
   p.chiPart = (double *)(ds + L.dChiPart), p.maxPart = (double *)(ds + L.dMaxPart), p.scalePart = (double *)(ds + L.dScalePart);
   lba::Prob pc = p;
   pc.Ge = s.Ge0 + s.Gse, pc.Gp = s.Gp0 + s.Gsr;
-  const SetupArgs &SA = G.SA;
-  lba::State *mirror = G.mirror, *mirror_dev = G.mirror_dev;
+  lba::State *mirror_dev = G.mirror_dev;
   uint8_t *dso = dp + oSem;
   FinalArgs FA;
-  FA.slots = SA.slots, FA.pos = F.pos, FA.Tcw = G.Tcw_dev, FA.opt_of = G.opt_of_dev;
-  FA.erase = dp + oErase, FA.chi2 = (double *)(dp + oChi2), FA.kf_out = (vsg_pose_se3d *)(dp + oKfOut), FA.pos_out = (float *)(dso + sPos);
+  FA.wb = G.wb, FA.wb.kf_out = (vsg_pose_se3d *)(dp + oKfOut), FA.wb.pos_out = (float *)(dso + sPos);
+  FA.erase = dp + oErase, FA.chi2 = (double *)(dp + oChi2);
   FA.erase_plane = dso + sErase, FA.chi2_kf = (double *)(dso + sChiK), FA.chi2_pp = (double *)(dso + sChiP);
   FA.plane_out = (double *)(dso + sPlane), FA.room_out = (double *)(dso + sRoom);
 
   TRY_HIP(hipMemcpyAsync(dv, hp, in_bytes, hipMemcpyHostToDevice, c->stream));
-  // from here on an error waits for the stream before it returns: the arenas belong to the next call
   hipStream_t st = c->stream;
-  bool failed = L.in.total > 0 && hipMemcpyAsync(ds, hs, L.in.total, hipMemcpyHostToDevice, st) != hipSuccess;
+  if (L.in.total > 0 && hipMemcpyAsync(ds, hs, L.in.total, hipMemcpyHostToDevice, st) != hipSuccess) {
+    (void)hipStreamSynchronize(st);  // the first copy reads the pinned arena, which belongs to the next call
+    return VSG_ERR_HIP;
+  }
   const dim3 B(lba::kThreads);
-  const unsigned gAll = G.gAll, gLin = (unsigned)((ST.Es + sgba::kEdgesPerGroup - 1) / sgba::kEdgesPerGroup),
+  const unsigned gLin = (unsigned)((ST.Es + sgba::kEdgesPerGroup - 1) / sgba::kEdgesPerGroup),
                  gGather = (unsigned)(s.Gse + s.Gsr) + (unsigned)((Ko + lba::kThreads - 1) / lba::kThreads);
   const int Gs = G.Gs, Gb = (ST.nbs + sgba::kBlocksPerGroup - 1) / sgba::kBlocksPerGroup;
   const bool sem = ST.Es > 0;  // no semantic edge: no semantic vertex, no semantic row
-  bool stopped = false;
-  if (!failed) hipLaunchKernelGGL(k_setup, dim3(gAll), B, 0, st, p, SA);
-  for (int it = 0; it < iterations && !failed; it++) {
-    if (Ge) hipLaunchKernelGGL(k_linearise<lba::HuberLocal>, dim3((unsigned)Ge), B, 0, st, p, it, lba::HuberLocal());
-    if (sem) hipLaunchKernelGGL(k_sg_linearise, dim3(gLin), B, 0, st, p, s, it);
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)(Gp + Ko)), B, 0, st, p, it);
-    if (sem) hipLaunchKernelGGL(k_sg_gather, dim3(gGather), B, 0, st, p, s, it);
-    hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, st, pc, it, mirror_dev);
-    bool closed = false;
-    for (int q = 0; q < lba::kTrials && !closed && !failed; q++) {
-      if (Ge) hipLaunchKernelGGL(k_trial_edges, dim3((unsigned)Ge), B, 0, st, p, it, q);
-      hipLaunchKernelGGL(k_schur, dim3((unsigned)(Gs + (int)Ko)), B, 0, st, p, it, q, Gs);
-      if (sem) hipLaunchKernelGGL(k_sg_assemble, dim3((unsigned)(Gb + s.Gsr)), B, 0, st, p, s, it, q, Gb);
-      hipLaunchKernelGGL(k_solve, dim3(1), dim3(lba::kSolveThreads), 0, st, p, it, q);
-      hipLaunchKernelGGL(k_backsub, dim3((unsigned)(Gp + 1)), B, 0, st, p, it, q);
-      if (sem) hipLaunchKernelGGL(k_sg_oplus, dim3((unsigned)s.Gsr), B, 0, st, p, s, it, q);
-      if (Ge) hipLaunchKernelGGL(k_error<lba::HuberLocal>, dim3((unsigned)Ge), B, 0, st, p, it, q, lba::HuberLocal());
-      if (sem) hipLaunchKernelGGL(k_sg_error, dim3((unsigned)s.Gse), B, 0, st, p, s, it, q);
-      hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, st, pc, it, q, mirror_dev);
-      // the look: the record in the pinned arena as the last one-lane step left it
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) failed = true;
-      closed = failed || mirror->finished || !(mirror->iter == it && mirror->trial_open);
-    }
-    if (failed || mirror->finished) break;
-    if (stop_flag && *stop_flag) {  // terminate() between iterations (sparse_optimizer.cpp:423)
-      stopped = true;
-      break;
-    }
-  }
-  if (!failed) {
-    size_t most = E > P ? E : P;
-    most = most > K ? most : K, most = most > NO ? most : NO, most = most > Pl ? most : Pl, most = most > R ? most : R;
-    hipLaunchKernelGGL(k_sg_final, dim3((unsigned)((most + lba::kThreads - 1) / lba::kThreads)), B, 0, st, p, s, FA);
-    if (hipGetLastError() != hipSuccess) failed = true;
-  }
-  if (hipStreamSynchronize(st) != hipSuccess || failed) return VSG_ERR_HIP;
-  lba::State Sfin = *mirror;
-  if (stopped) Sfin.finished = 1, Sfin.stop_reason = lba::kStopFlag;
+  hipLaunchKernelGGL(k_setup, dim3(G.gAll), B, 0, st, p, G.SA);
+  lba::State Sfin;
+  const bool done = lm::run(
+      st, G.mirror, iterations, lm::kTrialSlots, stop_flag,
+      [&](int it) {
+        if (Ge) hipLaunchKernelGGL(k_linearise<lba::HuberLocal>, dim3((unsigned)Ge), B, 0, st, p, it, lba::HuberLocal());
+        if (sem) hipLaunchKernelGGL(k_sg_linearise, dim3(gLin), B, 0, st, p, s, it);
+        hipLaunchKernelGGL(k_gather, dim3((unsigned)(Gp + Ko)), B, 0, st, p, it);
+        if (sem) hipLaunchKernelGGL(k_sg_gather, dim3(gGather), B, 0, st, p, s, it);
+        hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, st, pc, it, mirror_dev);
+      },
+      [&](int it, int q) {
+        if (Ge) hipLaunchKernelGGL(k_trial_edges, dim3((unsigned)Ge), B, 0, st, p, it, q);
+        hipLaunchKernelGGL(k_schur, dim3((unsigned)(Gs + (int)Ko)), B, 0, st, p, it, q, Gs);
+        if (sem) hipLaunchKernelGGL(k_sg_assemble, dim3((unsigned)(Gb + s.Gsr)), B, 0, st, p, s, it, q, Gb);
+        hipLaunchKernelGGL(k_solve<kSolveRows>, dim3(1), dim3(lba::kSolveThreads), 0, st, p, it, q);
+        hipLaunchKernelGGL(k_backsub, dim3((unsigned)(Gp + 1)), B, 0, st, p, it, q);
+        if (sem) hipLaunchKernelGGL(k_sg_oplus, dim3((unsigned)s.Gsr), B, 0, st, p, s, it, q);
+        if (Ge) hipLaunchKernelGGL(k_error<lba::HuberLocal>, dim3((unsigned)Ge), B, 0, st, p, it, q, lba::HuberLocal());
+        if (sem) hipLaunchKernelGGL(k_sg_error, dim3((unsigned)s.Gse), B, 0, st, p, s, it, q);
+        hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, st, pc, it, q, mirror_dev);
+      },
+      [&] {
+        size_t most = E > P ? E : P;
+        most = most > K ? most : K, most = most > NO ? most : NO, most = most > Pl ? most : Pl, most = most > R ? most : R;
+        hipLaunchKernelGGL(k_sg_final, dim3((unsigned)((most + lba::kThreads - 1) / lba::kThreads)), B, 0, st, p, s, FA);
+      },
+      &Sfin);
+  if (!done) return VSG_ERR_HIP;
   sgba::fill_result(res, T, &ST, &Sfin);
   const uint8_t *he = hp + oErase, *hso = hp + oSem;
   int n_erase = 0, n_erase_plane = 0;

@@ -1411,17 +1411,10 @@ class MapPoints:
         return {k: v[:n] for k, v in out.items()}
 
 
-    def LocalBundleAdjustment(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
-                              iterations=10, stop_flag=None, trial_slots=0):
-        """The visual part of Optimizer::LocalBundleAdjustment (vsg_mappoints_local_bundle_adjustment): point i = slot
-        slots[i] with the observations [obs_off[i], obs_off[i + 1]) of obs_kf (index into `keyframes`, a list of resident
-        orb.Frame in ascending mnId: the local keyframes AND the fixed ones) and obs_idx (leftIndex), as refresh() takes
-        them.  kf_Tcw = (K, 7) floats q (x y z w), t; kf_fixed[k] != 0 for lFixedCameras and the map's initial keyframe;
-        kf_cam = (K, 5) fx fy cx cy mbf; inv_level_sigma2 = mvInvLevelSigma2.  stop_flag = None or a uint8 array of one
-        element (pbStopFlag).  trial_slots: the test hook's trial slots enqueued ahead (0 = the library's default); the
-        result does not depend on it.  Returns dict(kf_Tcw (K, 7) float64, world_pos (n, 3) float32 -- also written into
-        the slots -- erase and chi2 per observation, and the fields of vsg_local_ba_result).  Follow with
-        refresh(what=REFRESH_NORMAL)."""
+    def _ba_begin(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2, iterations, stop_flag):
+        """What the three bundle adjustments share of a call, validated: n, K, the number of listed observations, the C
+        arguments from the store's handle to `iterations`, the stop flag's pointer, the pointers of the outs kf_Tcw and
+        world_pos, and the dict of those two outs and chi2 per observation (each call adds its own)."""
         n, K = int(np.asarray(slots).size), len(keyframes)
         sl, off, kf, idx = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx)
         if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != np.asarray(obs_kf).size:
@@ -1435,28 +1428,53 @@ class MapPoints:
         sig = _f32(inv_level_sigma2)
         handles = (C.c_void_p * max(K, 1))(*[f.handle for f in keyframes])
         out = {"kf_Tcw": np.zeros((max(K, 1), 7), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
-               "erase": np.zeros(max(nobs, 1), np.uint8), "chi2": np.zeros(max(nobs, 1), np.float64)}
+               "chi2": np.zeros(max(nobs, 1), np.float64)}
+        head = (self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
+                C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
+                int(np.asarray(inv_level_sigma2).size), int(iterations))
+        outs = (C.cast(_p(out["kf_Tcw"], C.POINTER(C.c_double)), C.POINTER(PoseSE3d)), _p(out["world_pos"], _f32p))
+        return n, K, nobs, head, None if stop_flag is None else _p(stop_flag, _u8p), outs, out
+
+    def _ba_finish(self, out, lens, res, ints, doubles, slots, kf_Tcw, restore=()):
+        """The result dict of a bundle adjustment: out's arrays cut to `lens`, then res's fields.  A call that did not run
+        wrote no pose and no position: those outs are the inputs, and so are the `restore` ones."""
+        if not res.ran:
+            K, n = lens["kf_Tcw"], lens["world_pos"]
+            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
+            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
+            for k, v in restore:
+                out[k][:lens[k]] = v[:lens[k]]
+        got = {k: out[k][:lens[k]] for k in lens}
+        got.update({k: int(getattr(res, k)) for k in ints})
+        got.update({k: float(getattr(res, k)) for k in doubles})
+        return got
+
+    def LocalBundleAdjustment(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
+                              iterations=10, stop_flag=None, trial_slots=0):
+        """The visual part of Optimizer::LocalBundleAdjustment (vsg_mappoints_local_bundle_adjustment): point i = slot
+        slots[i] with the observations [obs_off[i], obs_off[i + 1]) of obs_kf (index into `keyframes`, a list of resident
+        orb.Frame in ascending mnId: the local keyframes AND the fixed ones) and obs_idx (leftIndex), as refresh() takes
+        them.  kf_Tcw = (K, 7) floats q (x y z w), t; kf_fixed[k] != 0 for lFixedCameras and the map's initial keyframe;
+        kf_cam = (K, 5) fx fy cx cy mbf; inv_level_sigma2 = mvInvLevelSigma2.  stop_flag = None or a uint8 array of one
+        element (pbStopFlag).  trial_slots: the test hook's trial slots enqueued ahead (0 = the library's default); the
+        result does not depend on it.  Returns dict(kf_Tcw (K, 7) float64, world_pos (n, 3) float32 -- also written into
+        the slots -- erase and chi2 per observation, and the fields of vsg_local_ba_result).  Follow with
+        refresh(what=REFRESH_NORMAL)."""
+        n, K, nobs, head, flag, outs, out = self._ba_begin(slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam,
+                                                           inv_level_sigma2, iterations, stop_flag)
+        out["erase"] = np.zeros(max(nobs, 1), np.uint8)
         res = LocalBaResult()
-        flag = None if stop_flag is None else _p(stop_flag, _u8p)
         if trial_slots:
             _check(self._L.vsg_debug_local_ba_trial_slots(int(trial_slots)), "vsg_debug_local_ba_trial_slots")
         try:
             _check(self._L.vsg_mappoints_local_bundle_adjustment(
-                self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
-                C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
-                int(np.asarray(inv_level_sigma2).size), int(iterations), flag, C.cast(_p(out["kf_Tcw"], C.POINTER(C.c_double)), C.POINTER(PoseSE3d)),
-                _p(out["world_pos"], _f32p), _p(out["erase"], _u8p), _p(out["chi2"], C.POINTER(C.c_double)), C.byref(res)),
+                *head, flag, *outs, _p(out["erase"], _u8p), _p(out["chi2"], C.POINTER(C.c_double)), C.byref(res)),
                 "vsg_mappoints_local_bundle_adjustment")
         finally:
             if trial_slots:
                 self._L.vsg_debug_local_ba_trial_slots(0)
-        if not res.ran:  # nothing was written: the outs are the inputs
-            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
-            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
-        got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "erase": out["erase"][:nobs], "chi2": out["chi2"][:nobs]}
-        got.update({k: int(getattr(res, k)) for k in LOCAL_BA_RESULT_INTS})
-        got.update({k: float(getattr(res, k)) for k in LOCAL_BA_RESULT_DOUBLES})
-        return got
+        return self._ba_finish(out, {"kf_Tcw": K, "world_pos": n, "erase": nobs, "chi2": nobs}, res, LOCAL_BA_RESULT_INTS,
+                               LOCAL_BA_RESULT_DOUBLES, slots, kf_Tcw)
 
     def LocalBundleAdjustmentSGraph(self, slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam, inv_level_sigma2,
                                     plane_eq=(), pl_obs_off=(0,), pl_obs_kf=(), pl_obs_local=(), pl_obs_G=(), w_plane_kf=(),
@@ -1469,16 +1487,8 @@ class MapPoints:
         dict plus plane_eq (n_planes, 4), room_center (n_rooms, 3), erase_plane, chi2_plane_kf and chi2_plane_point per plane
         observation, and the fields of vsg_sgraph_local_ba_result."""
         f64 = lambda a, per: (lambda v: v if v.size else np.zeros(per, np.float64))(np.ascontiguousarray(a, np.float64).reshape(-1))
-        n, K = int(np.asarray(slots).size), len(keyframes)
-        sl, off, kf, idx = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx)
-        if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != np.asarray(obs_kf).size:
-            raise ValueError("observation arrays do not match the slot list")
-        nobs = int(off[n]) if n else 0
-        if int(np.asarray(obs_kf).size) < nobs:
-            raise ValueError("obs_off runs past the observation arrays")
-        T, fx, cam = _f32(kf_Tcw).reshape(-1), _u8(kf_fixed), _f32(kf_cam).reshape(-1)
-        if np.asarray(kf_Tcw).size != 7 * K or np.asarray(kf_fixed).size != K or np.asarray(kf_cam).size != 5 * K:
-            raise ValueError("kf_Tcw needs 7 floats, kf_fixed one byte and kf_cam 5 floats per keyframe")
+        n, K, nobs, head, flag, outs, out = self._ba_begin(slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam,
+                                                           inv_level_sigma2, iterations, stop_flag)
         eq, poff, pkf = f64(plane_eq, 4), _i32(pl_obs_off), _i32(pl_obs_kf)
         n_planes, n_rooms = int(np.asarray(plane_eq).size) // 4, int(np.asarray(room_center).size) // 3
         if np.asarray(pl_obs_off).size != n_planes + 1:
@@ -1490,36 +1500,22 @@ class MapPoints:
         rc_, rn, rw = f64(room_center, 3), _i32(room_n_walls), _i32(np.asarray(room_wall, np.int32).reshape(-1))
         if np.asarray(room_n_walls).size != n_rooms or np.asarray(room_wall).size != 4 * n_rooms:
             raise ValueError("room_n_walls needs one entry and room_wall four per room")
-        sig = _f32(inv_level_sigma2)
-        handles = (C.c_void_p * max(K, 1))(*[f.handle for f in keyframes])
         dp = C.POINTER(C.c_double)
-        out = {"kf_Tcw": np.zeros((max(K, 1), 7), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
-               "erase": np.zeros(max(nobs, 1), np.uint8), "chi2": np.zeros(max(nobs, 1), np.float64),
-               "plane_eq": np.zeros((max(n_planes, 1), 4), np.float64), "room_center": np.zeros((max(n_rooms, 1), 3), np.float64),
-               "erase_plane": np.zeros(max(npo, 1), np.uint8), "chi2_plane_kf": np.full(max(npo, 1), np.nan),
-               "chi2_plane_point": np.full(max(npo, 1), np.nan)}
+        out.update({"erase": np.zeros(max(nobs, 1), np.uint8),
+                    "plane_eq": np.zeros((max(n_planes, 1), 4), np.float64), "room_center": np.zeros((max(n_rooms, 1), 3), np.float64),
+                    "erase_plane": np.zeros(max(npo, 1), np.uint8), "chi2_plane_kf": np.full(max(npo, 1), np.nan),
+                    "chi2_plane_point": np.full(max(npo, 1), np.nan)})
         res = SGraphLocalBaResult()
-        flag = None if stop_flag is None else _p(stop_flag, _u8p)
         _check(self._L.vsg_mappoints_local_bundle_adjustment_sgraph(
-            self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
-            C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
-            int(np.asarray(inv_level_sigma2).size), int(iterations), flag, C.cast(_p(out["kf_Tcw"], dp), C.POINTER(PoseSE3d)),
-            _p(out["world_pos"], _f32p), _p(out["erase"], _u8p), _p(out["chi2"], dp),
+            *head, flag, *outs, _p(out["erase"], _u8p), _p(out["chi2"], dp),
             n_planes, _p(eq, dp), _p(poff, _i32p), _p(pkf, _i32p), _p(loc, dp), _p(G, dp), _p(wk, dp), _p(wp, dp),
             n_rooms, _p(rc_, dp), _p(rn, _i32p), _p(rw, _i32p), _p(out["plane_eq"], dp), _p(out["room_center"], dp),
             _p(out["erase_plane"], _u8p), _p(out["chi2_plane_kf"], dp), _p(out["chi2_plane_point"], dp), C.byref(res)),
             "vsg_mappoints_local_bundle_adjustment_sgraph")
-        if not res.local.ran:  # nothing was written: the outs are the inputs
-            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
-            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
-            out["plane_eq"][:n_planes] = eq.reshape(-1, 4)[:n_planes]
-            out["room_center"][:n_rooms] = rc_.reshape(-1, 3)[:n_rooms]
-        got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "erase": out["erase"][:nobs], "chi2": out["chi2"][:nobs],
-               "plane_eq": out["plane_eq"][:n_planes], "room_center": out["room_center"][:n_rooms],
-               "erase_plane": out["erase_plane"][:npo], "chi2_plane_kf": out["chi2_plane_kf"][:npo],
-               "chi2_plane_point": out["chi2_plane_point"][:npo]}
-        got.update({k: int(getattr(res.local, k)) for k in LOCAL_BA_RESULT_INTS})
-        got.update({k: float(getattr(res.local, k)) for k in LOCAL_BA_RESULT_DOUBLES})
+        lens = {"kf_Tcw": K, "world_pos": n, "erase": nobs, "chi2": nobs, "plane_eq": n_planes, "room_center": n_rooms,
+                "erase_plane": npo, "chi2_plane_kf": npo, "chi2_plane_point": npo}
+        got = self._ba_finish(out, lens, res.local, LOCAL_BA_RESULT_INTS, LOCAL_BA_RESULT_DOUBLES, slots, kf_Tcw,
+                              restore=(("plane_eq", eq.reshape(-1, 4)), ("room_center", rc_.reshape(-1, 3))))
         got.update({k: int(getattr(res, k)) for k in SGRAPH_LOCAL_BA_RESULT_INTS if k != "reserved"})
         return got
 
@@ -1534,36 +1530,15 @@ class MapPoints:
         positions come back in world_pos alone (mPosGBA).  Returns dict(kf_Tcw (K, 7) float64, world_pos (n, 3) float32,
         included (n) uint8 -- 0 for a point with an empty list --, chi2 per observation, and the fields of
         vsg_global_ba_result)."""
-        n, K = int(np.asarray(slots).size), len(keyframes)
-        sl, off, kf, idx = _i32(slots), _i32(obs_off), _i32(obs_kf), _i32(obs_idx)
-        if np.asarray(obs_off).size != n + 1 or np.asarray(obs_idx).size != np.asarray(obs_kf).size:
-            raise ValueError("observation arrays do not match the slot list")
-        nobs = int(off[n]) if n else 0
-        if int(np.asarray(obs_kf).size) < nobs:
-            raise ValueError("obs_off runs past the observation arrays")
-        T, fx, cam = _f32(kf_Tcw).reshape(-1), _u8(kf_fixed), _f32(kf_cam).reshape(-1)
-        if np.asarray(kf_Tcw).size != 7 * K or np.asarray(kf_fixed).size != K or np.asarray(kf_cam).size != 5 * K:
-            raise ValueError("kf_Tcw needs 7 floats, kf_fixed one byte and kf_cam 5 floats per keyframe")
-        sig = _f32(inv_level_sigma2)
-        handles = (C.c_void_p * max(K, 1))(*[f.handle for f in keyframes])
-        out = {"kf_Tcw": np.zeros((max(K, 1), 7), np.float64), "world_pos": np.zeros((max(n, 1), 3), np.float32),
-               "included": np.zeros(max(n, 1), np.uint8), "chi2": np.zeros(max(nobs, 1), np.float64)}
+        n, K, nobs, head, flag, outs, out = self._ba_begin(slots, obs_off, obs_kf, obs_idx, keyframes, kf_Tcw, kf_fixed, kf_cam,
+                                                           inv_level_sigma2, iterations, stop_flag)
+        out["included"] = np.zeros(max(n, 1), np.uint8)
         res = GlobalBaResult()
-        flag = None if stop_flag is None else _p(stop_flag, _u8p)
         _check(self._L.vsg_mappoints_global_bundle_adjustment(
-            self._h, n, _p(sl, _i32p), _p(off, _i32p), _p(kf, _i32p), _p(idx, _i32p), K, handles,
-            C.cast(_p(T, _f32p), C.POINTER(PoseSE3)), _p(fx, _u8p), C.cast(_p(cam, _f32p), C.POINTER(BaCamera)), _p(sig, _f32p),
-            int(np.asarray(inv_level_sigma2).size), int(iterations), int(bool(robust)), int(bool(write_store)), flag,
-            C.cast(_p(out["kf_Tcw"], C.POINTER(C.c_double)), C.POINTER(PoseSE3d)), _p(out["world_pos"], _f32p),
-            _p(out["included"], _u8p), _p(out["chi2"], C.POINTER(C.c_double)), C.byref(res)),
-            "vsg_mappoints_global_bundle_adjustment")
-        if not res.ran:  # only res and included were written: the outs are the inputs
-            out["kf_Tcw"][:K] = np.asarray(kf_Tcw, np.float32).reshape(K, 7) if K else 0
-            out["world_pos"][:n] = self.read(slots)["world_pos"] if n else 0
-        got = {"kf_Tcw": out["kf_Tcw"][:K], "world_pos": out["world_pos"][:n], "included": out["included"][:n], "chi2": out["chi2"][:nobs]}
-        got.update({k: int(getattr(res, k)) for k in GLOBAL_BA_RESULT_INTS})
-        got.update({k: float(getattr(res, k)) for k in GLOBAL_BA_RESULT_DOUBLES})
-        return got
+            *head, int(bool(robust)), int(bool(write_store)), flag, *outs, _p(out["included"], _u8p),
+            _p(out["chi2"], C.POINTER(C.c_double)), C.byref(res)), "vsg_mappoints_global_bundle_adjustment")
+        return self._ba_finish(out, {"kf_Tcw": K, "world_pos": n, "included": n, "chi2": nobs}, res, GLOBAL_BA_RESULT_INTS,
+                               GLOBAL_BA_RESULT_DOUBLES, slots, kf_Tcw)
 
     def OptimizeEssentialGraph(self, kf_Scw, kf_non_corrected, kf_has_non_corrected, kf_fixed, edge_i, edge_j, edge_loop,
                                fix_scale, slots=(), point_ref=(), iterations=20):
